@@ -5,7 +5,8 @@ Default = configs[1]: synthetic 128x128x64 volume (1 048 576 voxels), nTE=32, nT
 flip angle.  One "step" = one pass of the hot path over one rank's voxels (gates + FA bucketing [+ brute-force FA estimation
 when the config has it] + per-voxel solve + metrics epilogue), inputs and outputs resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W [--config {0,1,2,3,4}] [--scaling {weak,strong}] [--gather {maps,all}]
+  python bench.py --gpus N --steps K --warmup W [--config {0,1,2,3,4}] [--scaling {weak,strong}] [--gather {maps,all}] [--full]
+                  [--dump-outputs DIR]
 
   --config   0: 32x32x1 X2/I single FA (the reference's own CPU-runnable case; cpu_baseline also at 1 thread)
              1: 128x128x64 X2/L2 single FA (the metric's config; default)
@@ -21,9 +22,13 @@ plainly (`python bench.py --gpus N`) this process starts them itself -- as a CHI
 anything touches the GPU -- relays the child's JSON line and exits with its code.  Fewer than N visible devices is an error, never
 a silent 1-rank run.
 
-Besides `value` (region (i) of SURVEY.md section 8d: device-resident in -> device-resident out) the line carries
-`dict_build_ms` (region (ii): EPG dictionary + Gram matrices + seeds, once per run) and `end_to_end` (region (iii): host volume ->
-blocks H2D -> fit -> D2H of every output through the C ABI's host entry met2_fit_host, rank 0's volume).
+A plain run sets up, warms up, times the K steps and prints `value` (region (i) of SURVEY.md section 8d: device-resident in ->
+device-resident out) with the roofline blocks derived from those steps.  --full adds what takes runs of its own: `dict_build_ms`
+(region (ii): EPG dictionary + Gram matrices + seeds, once per run), `end_to_end` (region (iii): host volume -> blocks H2D -> fit ->
+D2H of every output through the C ABI's host entry met2_fit_host, rank 0's volume), the CPU baselines with the parity block against
+the oracle, and with N > 1 both gather payloads timed once more.
+  --dump-outputs DIR: after the timed steps, what the last step computed as DIR/<name>.npy (float64; a fixed, seeded sample of at
+  most 65 536 voxels, <= 64 MB in all, their indices in voxel_index.npy; rank 0's voxels when N > 1).  Same arguments, same inputs.
   --driver host: ONE process drives all N devices through that entry (pinned host arrays in and out); see host_driver_main.
 
 Prints ONE JSON line on rank 0.
@@ -101,6 +106,28 @@ def kernel_resources(method, nb):
         except Exception:
             continue
     return None
+
+
+DUMP_MAX_VOXELS = 1 << 16
+DUMP_MAX_BYTES = 56 << 20            # well under the 64 MB a dump may take, .npy headers included
+DUMP_SEED = 20260103
+
+
+def dump_outputs(path, arrays, nvox):
+    """--dump-outputs: write `arrays` ({name: (torch tensor or numpy array, voxel axis or None)}) as path/<name>.npy in float64.
+    Arrays with a voxel axis keep the same fixed, seeded sample of at most DUMP_MAX_VOXELS voxels (all of them when they fit),
+    whose indices go to voxel_index.npy; arrays without one (per-echo figures) are written whole."""
+    os.makedirs(path, exist_ok=True)
+    per_voxel = 8 * (1 + sum(int(np.prod(a.shape)) // a.shape[ax] for a, ax in arrays.values() if ax is not None))
+    n = min(nvox, DUMP_MAX_VOXELS, DUMP_MAX_BYTES // per_voxel)
+    idx = np.arange(nvox) if n == nvox else np.sort(np.random.default_rng(DUMP_SEED).choice(nvox, n, replace=False))
+    np.save(os.path.join(path, "voxel_index.npy"), idx.astype(np.float64))
+    for name, (a, ax) in arrays.items():
+        if torch.is_tensor(a):
+            a = (a if ax is None else a.index_select(ax, torch.as_tensor(idx, device=a.device))).cpu().numpy()
+        elif ax is not None:
+            a = np.take(a, idx, axis=ax)
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def cpu_baseline(method, pen, brute, data_cpu, nte, nt2, T2s, T1s, alphas, lam_grid, cores, seconds=15.0):
@@ -292,6 +319,8 @@ def tv_main(args, rank, local_rank, world):
         tt = torch.tensor([dt], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"denoised": (out.reshape(nvox, nte), 0), "sigma": (sig, None), "iterations": (its, None)}, nvox)
     if rank == 0:
         it_sum = int(its.sum())
         bytes_iter = 56.0 * nvox * it_sum                     # read p (3) + f (1), write p (3) per active (voxel, echo) and iteration
@@ -413,6 +442,9 @@ def host_driver_main(args):
         plan_ms.append(res["plan_ms"].copy())
         kernel_ms.append([pl.last_kernel_ms() for pl in plans]); second_ms.append([pl.last_second_pass_ms() for pl in plans])
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: (res[k], 1 if k == "maps" else 0) for k in ("fsol", "sig", "reg", "lam", "maps", "status")}
+                     | ({"fa_index": (res["fa_index"], 0)} if brute else {}), nvox)
     pm = np.mean(plan_ms, axis=0)
     fitted = int((res["status"] > 0).sum())
     bpv = BYTES_PER_VOXEL.get((nte, nt2), 8 * (2 * nte + nt2) + 65)
@@ -484,10 +516,20 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--parity-sample", type=int, default=1 << 17, help="upper bound on the voxels the oracle is run on for the parity block")
     ap.add_argument("--dump-fail", type=str, default="", help="npz path: inputs/outputs of sample voxels whose fsol is >1e-5 off the oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: the timed dictionary build, the CPU baselines and the parity block, "
+                         "the host-to-host leg, and with N > 1 both gather payloads once more.  Without it a run does only what `value` needs")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64, a fixed sample of the voxels)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
-    if args.gpus > 1:       # the CPU baseline and the host-to-host leg are rank 0's alone (15-25 s with N - 1 GPUs idle): single-GPU runs report them
+    if not args.full:
+        for flag, given in (("--cpu-baseline", args.cpu_baseline), ("--end-to-end", args.end_to_end), ("--dump-fail", args.dump_fail)):
+            if given:
+                ap.error("%s belongs to a --full run" % flag)
+        args.no_cpu_baseline = args.no_end_to_end = True
+    elif args.gpus > 1:     # the CPU baseline and the host-to-host leg are rank 0's alone (15-25 s with N - 1 GPUs idle): single-GPU runs report them
         args.no_cpu_baseline = not args.cpu_baseline
         args.no_end_to_end = not args.end_to_end
 
@@ -541,14 +583,16 @@ def main():
     brute = cfg["fa"] == "brute-force"
     alphas = np.linspace(90.0, 180.0, 91) if brute else np.array([150.0])   # "single FA" = index 60 of the 91-grid
     plan = pkg.Met2Plan(nte, nt2, alphas.shape[0], device=local_rank)
-    # region (ii): dictionary (EPG) + Gram matrices + penalty + plan-level seeds, once per run; timed on the second build
+    # region (ii): dictionary (EPG) + Gram matrices + penalty + plan-level seeds, once per run; --full times it on a second build
     # (the first one also pays for loading the code object)
     plan.build_dictionary_epg(T2s, T1s, 10.0, alphas, 3000.0).set_penalty(pen, T2s)
     torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    plan.build_dictionary_epg(T2s, T1s, 10.0, alphas, 3000.0).set_penalty(pen, T2s)
-    torch.cuda.synchronize()
-    dict_build_ms = 1e3 * (time.perf_counter() - t0)
+    dict_build_ms = None
+    if args.full:
+        t0 = time.perf_counter()
+        plan.build_dictionary_epg(T2s, T1s, 10.0, alphas, 3000.0).set_penalty(pen, T2s)
+        torch.cuda.synchronize()
+        dict_build_ms = 1e3 * (time.perf_counter() - t0)
     strong = args.scaling == "strong"
     # weak: a volume per rank (its own seed).  strong: the one volume (same seed everywhere), this rank's interleaved blocks of it
     data, _, _ = synth.make_voxels(nvox_total, nte=nte, seed=20260102 + (0 if strong else rank), fa_deg=150.0,
@@ -607,6 +651,8 @@ def main():
         def ms(self):
             return 1e3 * (self.t1 - self.t0) if gloo else self.e0.elapsed_time(self.e1)
 
+    last = {}
+
     def step():
         fa_idx = None
         if brute:       # driver step 2 (motor:349-373) on the device, then step 3+4
@@ -617,6 +663,7 @@ def main():
             with GatherTimer() as gt:
                 do_gather(res, args.gather)
             gather_ms.append(gt)
+        last["res"], last["fa_index"] = res, fa_idx
         return res
 
     def sync():
@@ -637,6 +684,10 @@ def main():
     sync()
     spill_voxels = plan.last_spill_count()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        res = last["res"]
+        dump_outputs(args.dump_outputs, {k: (res[k], 1 if k == "maps" else 0) for k in ("fsol", "sig", "reg", "lam", "maps", "status")}
+                     | ({"fa_index": (last["fa_index"], 0)} if brute else {}), nvox)
     multi = None
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=gdev)
@@ -648,9 +699,9 @@ def main():
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         allr = torch.stack(allr).cpu().numpy()
-        # both payloads once more, untimed for `value`: the maps' 56 B/voxel and SURVEY section 8e's full 8 (nT2 + nTE + 7) B/voxel in the same run
+        # --full: both payloads once more, untimed for `value`: the maps' 56 B/voxel and SURVEY section 8e's full 8 (nT2 + nTE + 7) B/voxel in the same run
         each = {}
-        for kind in ("maps", "all"):
+        for kind in (("maps", "all") if args.full else ()):
             do_gather(out, kind)                       # (allocates the buffers of the kind the timed steps did not use)
             sync()
             with GatherTimer() as gt:
@@ -706,7 +757,6 @@ def main():
                        "sharding": ("one volume, interleaved 4096-voxel blocks over the ranks" if strong else "one volume per rank") if world > 1 else "single GPU",
                        "gather": args.gather, "gather_bytes_per_voxel": 8 * W,
                        "collective": ("one gather of %s (%d B/voxel) to rank 0" % ("[fsol | Est_Signal | reg_param | maps]" if gather_all else "[maps | reg_param]", 8 * W)) if world > 1 else None},
-            "dict_build_ms": dict_build_ms,
             "roofline": {"bound": "hbm", "kernel": "fit_kernel<%s>" % method, "achieved": achieved, "peak": HBM_PEAK_GBPS,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
                          "kernel_ms": kms, "second_pass_ms": float(np.mean(pass2_ms)), "spill_voxels": spill_voxels, "bytes_per_voxel": bpv, "counters": pmc_note,
@@ -739,6 +789,8 @@ def main():
         except Exception:
             pass
         line["roofline_fp64"] = fp
+        if dict_build_ms is not None:
+            line["dict_build_ms"] = dict_build_ms
         if multi:
             line["multi_gpu"] = multi
         if valu:

@@ -4,7 +4,7 @@ TAG=${1:-rXX}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${TAG}_other.jsonl
 : > $O
-run() { timeout -k 5 300 python3 $R/bench.py --no-cpu-baseline "$@" >> $O 2>> $R/gpurun_out/${TAG}_other.err || echo "{\"failed\": \"$*\"}" >> $O; }
+run() { timeout -k 5 300 python3 $R/bench.py --full --no-cpu-baseline "$@" >> $O 2>> ${O%.jsonl}.err || echo "{\"failed\": \"$*\"}" >> $O; }
 run --dims 64,64,64 --method L_curve --penalty L1
 run --dims 64,64,64 --method BayesReg --penalty InvT2
 run --dims 64,64,32 --method GCV --penalty L2

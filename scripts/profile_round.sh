@@ -10,11 +10,11 @@ OUT=$R/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-timeout -k 5 400 python3 $R/bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit 1
-timeout -k 5 400 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o s --output-format csv -- python3 $R/bench.py --no-cpu-baseline > $OUT/${TAG}_stats.log 2>&1 || exit 2
+timeout -k 5 400 python3 $R/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit 1
+timeout -k 5 400 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o s --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline > $OUT/${TAG}_stats.log 2>&1 || exit 2
 cp $OUT/${TAG}_stats/s_kernel_stats.csv $OUT/${TAG}_kernel_stats.csv
-timeout -k 5 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/${TAG}_pf -o f --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline > $OUT/${TAG}_pf.log 2>&1 || exit 3
-timeout -k 5 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/${TAG}_pw -o w --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline > $OUT/${TAG}_pw.log 2>&1 || exit 4
+timeout -k 5 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/${TAG}_pf -o f --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > $OUT/${TAG}_pf.log 2>&1 || exit 3
+timeout -k 5 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/${TAG}_pw -o w --output-format csv -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > $OUT/${TAG}_pw.log 2>&1 || exit 4
 python3 - <<PY
 import csv
 for tag, f in (("fetch", "$OUT/${TAG}_pf/f_counter_collection.csv"), ("write", "$OUT/${TAG}_pw/w_counter_collection.csv")):

@@ -703,7 +703,7 @@ def main():
         gen_tail_x2(65536, 20260123)
     if "tailX2S2" in which:      # the same at config 5's shape (48 x 120: the two-bins-per-lane kernels), 8 192 voxels; ~10 minutes on 7 processes
         gen_tail_x2(8192, 20260124, nte=48, npc=120, name="golden_tail_X2_S2.npz")
-    if "x2fail" in which:        # needs gpurun_out/fail_x2l2.npz (bench.py --config 1 --dump-fail on the GPU box)
+    if "x2fail" in which:        # needs the npz of `bench.py --full --config 1 --dump-fail PATH` (MET2_FAILSET, default below)
         gen_x2_failset(os.environ.get("MET2_FAILSET", os.path.join(HERE, "..", "..", "gpurun_out", "fail_x2l2.npz")))
     if "tailS2b" in which:       # BayesReg/I at 48 x 120 on 2 048 voxels (the method with rounding-level parity: pins the panel Cholesky); ~3 minutes
         gen_tail("S2b", 48, 120, 2048, [("BayesReg", "I", 2048)], 20260125)

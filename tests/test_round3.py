@@ -50,6 +50,35 @@ def test_bench_refuses_to_run_fewer_ranks_than_asked():
     assert p.returncode != 0 and line is None
 
 
+def test_bench_legs_of_a_full_run_need_full():
+    # the CPU baseline, the host-to-host leg and the parity dump are --full's: asked for without it they are an error, not silently dropped
+    for extra in (["--cpu-baseline"], ["--end-to-end"], ["--dump-fail", "fail.npz"]):
+        p, line = _run_bench(["--steps", "1", "--warmup", "0"] + extra, {})
+        assert p.returncode == 2 and line is None and "--full" in p.stderr, extra
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    # a plain run: set-up, warm-up, the timed steps and the line -- none of --full's legs (timed dictionary re-build, CPU baselines and
+    # parity, host-to-host leg); --dump-outputs writes what the last timed step computed, the same numbers from run to run
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        p, line = _run_bench(["--steps", "2", "--warmup", "1", "--dims", "16,16,8", "--dump-outputs", str(d)], {})
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "voxels/s" and line["dtype"] == "f64"
+        for k in ("cpu_baseline", "parity", "end_to_end", "dict_build_ms"):
+            assert k not in line, k
+        dumps.append({f.stem: np.load(f) for f in d.glob("*.npy")})
+        assert int((dumps[-1]["status"] > 0).sum()) == line["config"]["fitted_voxels_per_gpu"]
+    a, b = dumps
+    assert sorted(a) == ["fsol", "lam", "maps", "reg", "sig", "status", "voxel_index"]
+    assert a["fsol"].shape == (2048, 60) and a["sig"].shape == (2048, 32) and a["maps"].shape == (6, 2048)
+    assert np.array_equal(a["voxel_index"], np.arange(2048.0))
+    for k in a:
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], b[k]), k
+
+
 def test_x2_failset_is_brent_ties_inside_the_references_own_tolerance():
     # bench.py --config 1 --dump-fail: the 13 of 209 305 voxels where the HIP path and the oracle differ by more than 1e-5, put through
     # the REFERENCE's nnls_x2 (make_goldens.py x2fail).  In every one the reference agrees with one of the two to rounding, and
@@ -157,7 +186,7 @@ def test_hip_vs_reference_8192_x2_voxels_at_48x120(tail_x2_s2):
 def test_bench_two_ranks_share_the_gpu_with_the_hip_fit():
     # the launcher end to end on the one-GPU box: two ranks, both on cuda:0, gloo for the collective, the HIP fit as compute
     # (N > 1 skips rank 0's CPU baseline unless asked: --cpu-baseline brings the parity block back)
-    p, line = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--dims", "16,16,8", "--gather", "all", "--cpu-seconds", "1", "--cpu-baseline"],
+    p, line = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--dims", "16,16,8", "--gather", "all", "--cpu-seconds", "1", "--full", "--cpu-baseline"],
                          {"MET2_BENCH_SHARE_GPU": "1", "MET2_DIST_BACKEND": "gloo", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     assert line["n_gpus"] == 2 and line["config"]["ranks_seen"] == 2 and line["config"]["gather_bytes_per_voxel"] == 792

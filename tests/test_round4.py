@@ -427,7 +427,7 @@ def test_bench_tv_workload_line():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ); env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "tv", "--dims", "40,36,32", "--nte", "6", "--steps", "2", "--warmup", "1",
-                        "--cpu-seconds", "2"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--cpu-seconds", "2", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline",
