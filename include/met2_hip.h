@@ -59,7 +59,8 @@ enum met2_status {
     MET2_ST_CHOLFAIL = 8,      /* BayesReg: Cholesky of beta(B + lambda K) failed (reference: LinAlgError) */
     MET2_ST_BRENT_MAXFUN = 16, /* lambda search stopped on maxfun                                  */
     MET2_ST_KOVERFLOW = 32     /* passive set outgrew the wave's LDS region: set only transiently -- the fit kernel queues such a voxel and
-                                  the spill-over kernel behind it solves it again, so no voxel returned by met2_fit carries it */
+                                  the spill-over kernel launched behind it (in every fit that runs at a reduced capacity) solves it again,
+                                  so no voxel returned by met2_fit carries it */
 };
 
 enum met2_error {
@@ -334,12 +335,14 @@ int met2_metrics(met2_plan *plan, int64_t nvox, const double *fsol, const uint8_
 int met2_plan_last_kernel_ms(met2_plan *plan, double *ms);
 /* NNLS/T2SPARC/X2/L-curve/GCV fits (and BayesReg at n_t2 > 64) give every wave an LDS region for a Cholesky factor of a reduced
  * passive-set capacity (the largest that lets 16 waves share a CU's LDS, never below 0.6 n_t2: 50 at n_t2 = 60; at two bins per
- * lane the largest that lets the 8 waves those kernels are compiled for share it: 71 at n_t2 = 120).  A voxel whose set outgrows
- * it (~1 % at 32 x 60, 5-10 % at 48 x 120) goes on in place with the factor's columns beyond the capacity in a per-wave slot in
- * device memory (allocated by the first such fit on the plan: 18 MB at n_t2 = 60, 77 MB at 120): ONE solver launch per fit.
- * met2_plan_last_spill_count: how many voxels of the most recent finished fit took that route (for reports and tests).
- * met2_plan_last_second_pass_ms: rounds 1-4 solved those voxels again in a second launch at full capacity; that ladder runs
- * only with MET2_TWO_PASS=1 in the environment (A/B test switch), otherwise this returns 0. */
+ * lane the largest that lets the 8 waves those kernels are compiled for share it: 71 at n_t2 = 120).  Such a fit runs two solver
+ * kernels: the fit kernel queues a voxel whose set outgrows the capacity (~1 % at 32 x 60, 5-10 % at 48 x 120), and the spill-over
+ * kernel launched behind it, with the same geometry, solves the queued voxels with the factor's columns beyond the capacity in a
+ * per-wave slot in device memory (allocated by the first such fit on the plan: 18 MB at n_t2 = 60, 77 MB at 120).  A plan whose
+ * options name non-default lambda-search intervals runs every voxel through the spill-over kernel.
+ * met2_plan_last_spill_count: how many voxels of the most recent finished fit were queued (for reports and tests).
+ * met2_plan_last_second_pass_ms: the spill-over kernel's duration in the most recent fit (0 if the fit ran none);
+ * met2_plan_last_kernel_ms is then the fit kernel's alone, about 0 under non-default lambda-search intervals. */
 int met2_plan_last_spill_count(met2_plan *plan, int64_t *count);
 int met2_plan_last_second_pass_ms(met2_plan *plan, double *ms);
 

@@ -1,7 +1,8 @@
-// abi_common.hpp -- error plumbing shared by the translation units of libmet2_hip.so.
+// abi_common.hpp -- error plumbing and the environment switches shared by the translation units of libmet2_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <string>
 
 namespace met2 {
@@ -10,6 +11,27 @@ __attribute__((visibility("hidden"))) int abi_fail(int code, const std::string &
 }  // namespace met2
 
 static inline int fail(int code, const std::string &msg) { return met2::abi_fail(code, msg); }
+
+// The switches the shipped library reads from the environment, at every call (the tests flip them between fits on one plan); set means on:
+//   MET2_NO_SEED      every voxel grows its first passive set from the lambda = 0 solution, not from the plan's seed (test_gpu_round2.py)
+//   MET2_GCV_FULL     GCV's trace from the (m + 1) x (m + 1) form, never the low-rank one (test_round4.py)
+//   MET2_FA_NOPRUNE   the brute-force FA walk visits every flip angle, no lower bounds (test_round4.py)
+//   MET2_LC_RESTART   queued L-curve voxels start their sweep over in the spill-over kernel (test_round5.py)
+//   MET2_HOST_BLOCKS  met2_fit_host gives its plans whole blocks, not runs of 4 096 voxels (test_round5.py)
+//   MET2_DEBUG        synchronous launches with progress lines on stderr
+static inline bool test_switch(const char *name) { return getenv(name) != nullptr; }
+
+// Development knobs (first-pass capacity, waves per CU, queue granularity, ...): read only by libraries built with -DMET2_TUNING, which take a
+// value in [lo, hi]; every other build uses dflt.
+static inline int tuning_env(const char *name, int lo, int hi, int dflt)
+{
+#ifdef MET2_TUNING
+    if (const char *e = getenv(name)) { const int v = atoi(e); if (v >= lo && v <= hi) return v; }
+#else
+    (void)name; (void)lo; (void)hi;
+#endif
+    return dflt;
+}
 
 // makes `dev` current for the duration of a C-ABI call and puts the caller's device back afterwards
 struct DevGuard {

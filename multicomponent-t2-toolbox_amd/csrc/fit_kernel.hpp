@@ -75,7 +75,6 @@ struct FitArgs {
     double *big;                          // [grid * waves][big_stride]: every wave's spill-over slot for factor columns >= kmax (nnls_big.hpp), or NULL
     int big_stride;
     double *lc_save;                      // L-curve at two bins per lane: [lc_cap][LC_SAVE_DOUBLES][64] sweep states of queued voxels (fit_voxel), or NULL
-    int spill_w2;                         // dev: the spill-over kernel's waves per workgroup (0: its own choice)
     int *lc_at;                           // [lc_cap]: the grid point the sweep goes on from (nlam: the solve at the corner)
     int lc_cap;
     double blam[MET2_BAYES_TABLE];        // the shared Brent abscissae lambda_j
@@ -577,8 +576,7 @@ __device__ __forceinline__ void refine(const WaveShared &S, NnlsState<NB> &st, d
 
 // One voxel (motor:129-155 + motor:448-468): load, normalise, the method's lambda search, epilogue.  BIG = false: the instance in the kernel's own
 // voxel loop; a passive set that wants to outgrow the LDS capacity makes it return true, the voxel's outputs carrying MET2_ST_KOVERFLOW until the
-// spill-over kernel (or, without slots, the caller's second launch) has written them again.  BIG = true: the instance inside fit_voxel_spill, which goes on in the wave's
-// global slot (nnls_big.hpp).
+// spill-over kernel has written them again.  BIG = true: the instance inside fit_voxel_spill, which goes on in the wave's global slot (nnls_big.hpp).
 template <int METHOD, int NB, bool BIG>
 __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S, const Band<NB> &bd, const MetricLanes<NB> &ml, int64_t v, int fa,
                                           int seed_k, bool have_seed, int lane, int wslot, int qslot)
@@ -923,7 +921,7 @@ __device__ __attribute__((noinline)) void fit_voxel_spill(const FitArgs *Ap, big
 // (capacity A.kmax: as many resident waves as the registers allow) is put on the spill-over queue, nothing written.
 // SECOND = true: the spill-over kernel, launched behind it with the same geometry: the same voxel routine with BIG = true -- the solver with the
 // spill-over legs compiled in (nnls_big.hpp), one not-inlined instance -- on the queued voxels, at the first kernel's occupancy (8 waves per CU at
-// nT2 = 120 where the full-size factor of rounds 1-4's clean-up pass allowed 2) and without the re-sort (five small kernels) that pass needed.
+// nT2 = 120 where the full-size factor of the clean-up launch of rounds 1-4 allowed 2) and without the re-sort (five small kernels) it needed.
 // Why a second kernel and not a call behind (or inside) the first one's voxel loop: a kernel that contains a call keeps registers for the calling
 // convention throughout -- fit_kernel<X2, 1> went from 29 spill stores / 47 reloads to 52 / 160 and configs[1] from 150.4 to 157.5 ms with the
 // call BEHIND the loop (inside it: 7 000 reloads); and with the spill-over legs inlined into the nine copies of the solver the X2 kernel holds,
@@ -999,7 +997,6 @@ __global__ __launch_bounds__(64 * method_max_waves(METHOD, NB)) void fit_kernel(
         const int total = A.waves * A.wave_doubles, wgs = (int)gridDim.x;
         int w2 = A.waves;
         while (w2 > 1 && (int64_t)(w2 - 1) * wgs >= ntail) --w2;
-        if (A.spill_w2 > 0 && A.spill_w2 <= A.waves) w2 = A.spill_w2;
         const int per = (total / w2) & ~1;
         int k2 = A.kmax;
         while (k2 < n && col_base(k2 + 1) <= per) ++k2;

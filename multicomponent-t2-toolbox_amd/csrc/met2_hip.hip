@@ -313,27 +313,6 @@ __global__ __launch_bounds__(MET2_SORT_BLOCK) void scatter_kernel(int64_t nvox, 
     if (key >= 0) sb.perm[sb.bucket_start[key] + sort_lds[nfa + key] + off] = (int)v;
 }
 
-// second pass of the capacity scheme: voxels whose passive set hit the fast path's kmax are queued again
-__global__ __launch_bounds__(256) void requeue_overflow_kernel(int64_t nvox, const double *__restrict__ fa_index,
-                                                               const int32_t *__restrict__ status, SortBufs sb)
-{
-    const int lane = lane_id();
-    int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    int key = -1;
-    if (v < nvox) {
-        if (status[v] & MET2_ST_KOVERFLOW) key = fa_index ? (int)fa_index[v] : 0;
-        sb.key[v] = key;
-    }
-    u64 todo = ballot(key >= 0);
-    while (todo) {
-        int leader = first_lane(todo);
-        int k0 = bcast_i(key, leader);
-        u64 same = ballot(key == k0) & todo;
-        if (lane == leader) atomicAdd(&sb.hist[k0], __popcll(same));
-        todo &= ~same;
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // brute-force flip-angle estimation (flip_angle_algorithms/fa_estimation.py:74-111):
 // for every flip angle of the dictionary one plain NNLS per voxel, argmin of the residual norm.
@@ -1016,7 +995,7 @@ struct met2_plan {
     double log_detL = 0.0;      // log(det(L)) as bayesian_interpolation.py:100,123 uses it (-inf for L2)
     // sort buffers (grown on demand)
     int64_t cap_vox = 0;
-    int *dKey = nullptr, *dPerm = nullptr, *dSmall = nullptr, *dOvf = nullptr;
+    int *dKey = nullptr, *dPerm = nullptr, *dSmall = nullptr, *dOvf = nullptr;      // dSmall: hist|cursor|bucket_start|chunk_start|queue|err
     char *dSeed = nullptr;                                // seed_kernel's output: [4][nfa] SeedRec
     bool seeds_valid = false; double seeds_key[7] = {0};  // (t2sparc_lambda and the six interval ends the seeds and tables were built for)
     bool seeds_ok = false;                                // B + lambda K is positive definite at the seed lambdas (checked on the host for
@@ -1035,7 +1014,6 @@ struct met2_plan {
     int *hErr = nullptr;                                  // pinned [4]: the FA-range error word of an enqueued fit lands here, and its spill-over queue's tail (= count) and head
     bool err_pending = false;
     hipStream_t err_stream = nullptr;                     // the stream the fits since the last finish were enqueued on (one plan serves one stream at a time)
-    int32_t *dStatus = nullptr; int64_t cap_status = 0;   // internal status words when the caller passes none   // dSmall: hist|cursor|bucket_start|chunk_start|queue|err
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     bool timed = false, timed2 = false;
 };
@@ -1100,16 +1078,11 @@ static SortBufs sort_bufs(met2_plan *p)
 }
 
 
-// Development knobs (first-pass capacity, waves per CU, queue granularity) exist only in builds with -DMET2_TUNING; the shipped
-// library reads two environment variables: MET2_NO_SEED (A/B test of the plan-level seeds) and MET2_DEBUG (synchronous progress lines).
-static int tuning_env(const char *name, int lo, int hi, int dflt)
+// GCV's kernel variant: the trace from the 17 x 17 low-rank form when the plan's dictionary allows it, unless MET2_GCV_FULL is set (the one
+// place fit_impl, met2_plan_gcv_form and met2_plan_launch_info take it from)
+static int kernel_method(const met2_plan *p, int method)
 {
-#ifdef MET2_TUNING
-    if (const char *e = getenv(name)) { const int v = atoi(e); if (v >= lo && v <= hi) return v; }
-#else
-    (void)name; (void)lo; (void)hi;
-#endif
-    return dflt;
+    return (method == MET2_GCV && p->gcv_lr && !test_switch("MET2_GCV_FULL")) ? MET2_GCV_LR : method;
 }
 
 // kmax_cap > 0: capacity of the passive set for this launch (fast path); 0: full capacity n.
@@ -1158,7 +1131,8 @@ static int fast_kmax(const met2_plan *p, int method)
 {
     if (method >= 10 || (method == MET2_BAYESREG && p->n_t2 <= 64)) return 0;     // (BayesReg at one bin per lane factorises n x n in the wave's region)
     { const int kk = tuning_env("MET2_KMAX", 8, p->n_t2 - 1, -1); if (kk > 0) return kk; }
-    // the largest capacity that still lets 16 waves share the LDS, but not below 0.6 n
+    // the largest capacity that still lets 16 waves share the LDS, but not below 0.6 n.  The figures below were measured with the
+    // capacity ladder of rounds 1-4, which solved the voxels that outgrew the capacity again in a clean-up launch at full capacity
     // (measured on X2/L2, nT2 = 60: kmax 48 -> 1.95 M voxels/s, 50 -> 2.10 M, 52 (14 waves) -> 2.03 M, 60 (11 waves) -> 1.84 M;
     //  nT2 = 120 with the per-wave queue, where the clean-up pass is cheap: kmax 56 / 64 / 72 / 80 / 96 ->
     //  320 / 464 / 583 / 534 / 391 k voxels/s at 12 / 9 / 7 / 6 / 4 waves per CU)
@@ -1168,7 +1142,7 @@ static int fast_kmax(const met2_plan *p, int method)
     if (k16 > k) k = k16;
     if (p->n_t2 > 64) {
         // two bins per lane: those kernels are compiled for 8 waves per CU (method_max_waves), so the capacity that still lets EIGHT
-        // regions share the LDS -- 71 at nT2 = 120, where 0.6 n = 72 gave 7 (round 3, X2/L2 at 48 x 120 on 32 768 voxels: first pass
+        // regions share the LDS -- 71 at nT2 = 120, where 0.6 n = 72 gave 7 (round 3, with the ladder, X2/L2 at 48 x 120 on 32 768 voxels: first pass
         // 26.1 -> 23.2 ms, clean-up 5.2 -> 6.4 ms; 64 -> 22.4 + 17.7 ms; 80 / 90 / 110 -> 29.0 / 41.4 / 53.3 ms with a clean-up pass
         // that stays at ~5 ms: a few voxels whose set at the first abscissae is nearly all of the grid.  A middle pass at capacity
         // 88 or 100 between the two made the clean-up slower, 6.7 -> 10 ms: those voxels outgrow it too and are solved three times) ...
@@ -1179,20 +1153,6 @@ static int fast_kmax(const met2_plan *p, int method)
         if (method == MET2_GCV) while (col_base(k + 1) <= gcv_lds_doubles(p->n_te, p->n_t2)) ++k;
     }
     return k < p->n_t2 ? k : 0;
-}
-
-// Middle rung of the capacity ladder, GCV at two bins per lane only (BayesReg's few clean-up voxels measure the same with and without): the full n x n factor of the clean-up pass (58 KB at nT2 = 120)
-// leaves a CU two waves; the largest capacity that gives it three is 116, and on the [1e-8, 10] interval of algorithms.py:279 the
-// sets that outgrow the first pass stay under it (131 072 voxels of configs[4] with a FIRST pass at capacity 116: 0.07 ms of clean-up
-// left).  X2's interval visits 6.18 for every voxel, where those sets are the whole grid (clean-up 4.96 ms after a first pass at
-// 118): for it a middle pass means solving them three times (measured: 6.7 -> 10 ms), so it gets none.  0: no middle pass.
-static int mid_kmax(const met2_plan *p, int method, int kfast)
-{
-    if (!kfast || p->n_t2 <= 64 || (method != MET2_GCV && method != MET2_GCV_LR)) return 0;
-    { const int kk = tuning_env("MET2_KMID", 0, p->n_t2 - 1, -1); if (kk >= 0) return kk > kfast ? kk : 0; }
-    int k3 = kfast;
-    while (k3 + 1 < p->n_t2 && 3 * sizeof(double) * (size_t)col_base(k3 + 1) <= 160 * 1024 - 64) ++k3;
-    return (k3 >= kfast + 8 && k3 < p->n_t2) ? k3 : 0;
 }
 
 template <int METHOD>
@@ -1620,7 +1580,7 @@ int met2_plan_destroy(met2_plan *p)
     if (!p) return MET2_OK;
     met2::host_release(p);           // what met2_fit_host keeps with the plan (met2_host.hip)
     DevGuard dev_guard_(p->opt.device);
-    void *bufs[] = {p->dQt, p->dAq, p->dAqRes, p->dD, p->dB, p->dDt, p->dKband, p->dLband, p->dKd, p->dLam, p->dT2, p->dKey, p->dPerm, p->dOvf, p->dSmall, p->dStatus, p->dSeed, p->dBtab, p->dH, p->dChol, p->dBig, p->dLcSave};
+    void *bufs[] = {p->dQt, p->dAq, p->dAqRes, p->dD, p->dB, p->dDt, p->dKband, p->dLband, p->dKd, p->dLam, p->dT2, p->dKey, p->dPerm, p->dOvf, p->dSmall, p->dSeed, p->dBtab, p->dH, p->dChol, p->dBig, p->dLcSave};
     for (void *b : bufs) (void)hipFree(b);
     if (p->hErr) (void)hipHostFree(p->hErr);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
@@ -1843,6 +1803,44 @@ int met2_plan_finish(met2_plan *p, void *stream)
     return MET2_OK;
 }
 
+// MET2_DEBUG: waits for the fit kernels; libraries built with -DMET2_CYCSTATS, -DMET2_BIGSTATS or -DMET2_LOOPSTATS print their counters too
+static int debug_counters(int method, hipStream_t s)
+{
+    (void)method;
+    HIPCHK(hipStreamSynchronize(s)); fprintf(stderr, "[met2] fit kernel done\n");
+#ifdef MET2_CYCSTATS
+    unsigned long long cy[16];
+    HIPCHK(hipMemcpyFromSymbol(cy, HIP_SYMBOL(met2::g_cyc), sizeof(cy)));
+    fprintf(stderr, "[met2] gcv trace: gram(mfma)=%llu tridiag=%llu bisect=%llu weights=%llu\n", cy[8], cy[9], cy[10], cy[11]);
+    fprintf(stderr, "[met2] calls: warm solves=%llu duals=%llu append rounds=%llu inner loops after an append=%llu\n", cy[12], cy[13], cy[14], cy[15]);
+    fprintf(stderr, "[met2] wave cycles: voxel=%llu refactor=%llu inner=%llu dual=%llu append=%llu | slots 5-7 (x2: sse, removals, removal cycles; bayes: chol, upper_times, erf/log; gcv small path: cycles, evaluations, sweeps; append slot += sum k)=%llu %llu %llu\n",
+            cy[0], cy[1], cy[2], cy[3], cy[4], cy[5], cy[6], cy[7]);
+    if (method == MET2_X2) {
+        static unsigned long long ev[40][12];
+        HIPCHK(hipMemcpyFromSymbol(ev, HIP_SYMBOL(met2::g_ev), sizeof(ev)));
+        fprintf(stderr, "[met2] X2 per Brent evaluation index: evals canonical | cycles per eval: refactor inner(incl. removal) dual append sse | removals/eval removal-cycles/eval | k start -> end\n");
+        for (int e = 0; e < 40; ++e) {
+            if (!ev[e][0]) continue;
+            const double c = (double)ev[e][0];
+            fprintf(stderr, "[met2]  ev %2d: %9llu %9llu | %8.0f %8.0f %8.0f %8.0f %8.0f | %5.2f %8.0f | %5.1f -> %5.1f\n", e, ev[e][0], ev[e][10], ev[e][1] / c, ev[e][2] / c,
+                    ev[e][3] / c, ev[e][4] / c, ev[e][5] / c, ev[e][6] / c, ev[e][7] / c, ev[e][8] / c, ev[e][9] / c);
+        }
+    }
+#endif
+#ifdef MET2_BIGSTATS
+    { unsigned long long bs[16]; HIPCHK(hipMemcpyFromSymbol(bs, HIP_SYMBOL(met2::g_bigstats), sizeof(bs)));
+      fprintf(stderr, "[met2] spill-over voxels: solver calls=%llu, with spill-over legs=%llu | cycles plain=%llu spill=%llu (refactor in slot %llu) | appends=%llu removals=%llu refactors=%llu | k start sum=%llu end sum=%llu\n",
+              bs[0], bs[1], bs[2], bs[3], bs[9], bs[4], bs[5], bs[6], bs[8], bs[7]); }
+#endif
+#ifdef MET2_LOOPSTATS
+    int ls[8];
+    HIPCHK(hipMemcpyFromSymbol(ls, HIP_SYMBOL(met2::g_loopstats), sizeof(ls)));
+    fprintf(stderr, "[met2] loop maxima: tries=%d sweeps=%d outer=%d iter=%d taken=%d round=%d jacobi_sweeps=%d last_sweep_rotations=%d\n", ls[0], ls[1], ls[2], ls[3], ls[4], ls[5], ls[6], ls[7]);
+#endif
+    fflush(stderr);
+    return MET2_OK;
+}
+
 static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *data, int64_t voxel_stride, int64_t echo_stride,
                     const double *fa_index, const uint8_t *mask, double *fsol, double *sig, double *reg, double *lam, double *maps,
                     int32_t *status, void *stream, bool sync)
@@ -1859,32 +1857,19 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
     if (objgrid) { method -= 10; if (method != MET2_X2 && method != MET2_GCV && method != MET2_BAYESREG) return fail(MET2_E_INVALID, "no objective for this method"); }
     if (method < 0 || method > MET2_BAYESREG) return fail(MET2_E_INVALID, "unknown method");
     if (objgrid && p->nlam > p->n_t2) return fail(MET2_E_UNSUPPORTED, "objective grid longer than n_t2");
-    if (nvox == 0) return MET2_OK;
     USE_DEVICE(p->opt.device);
     hipStream_t s = (hipStream_t)stream;
     if (p->err_pending && p->err_stream != s)
         return fail(MET2_E_STATE, "fits are pending on another stream of this plan: call met2_plan_finish on it first (one plan serves one stream at a time)");
     int rc = ensure_sort_bufs(p, nvox);
     if (rc) return rc;
-    // capacity scheme: pass 1 with a passive-set capacity kfast < n (more waves per CU), pass 2 with the full
-    // capacity for the voxels that hit it
-    // the kernel variant: GCV takes its trace from the 17 x 17 low-rank form when the plan's dictionary allows it (MET2_GCV_FULL=1: test
-    // switch, the (m + 1) x (m + 1) form always)
-    const int kmeth = (method == MET2_GCV && p->gcv_lr && !getenv("MET2_GCV_FULL")) ? MET2_GCV_LR : method;
+    // capacity scheme: the fit kernel runs at a passive-set capacity kfast < n (more waves per CU); the voxels whose set outgrows it
+    // go on in the spill-over kernel behind it
+    const int kmeth = kernel_method(p, method);
     const int kfast = objgrid ? 0 : fast_kmax(p, kmeth);
-    LaunchGeom g, g2;
+    LaunchGeom g;
     rc = fit_geometry(p, objgrid ? kmeth + 10 : kmeth, g, kfast, 0, nvox);
     if (rc) return rc;
-    if (kfast) { rc = fit_geometry(p, kmeth, g2, 0, 0, nvox); if (rc) return rc; }
-    const bool two_pass = getenv("MET2_TWO_PASS") != nullptr;      // test switch (A/B): the two-launch capacity ladder of rounds 1-4 instead of the spill-over slots
-    if (kfast && two_pass && !status) {        // the second pass is driven by the status words
-        if (p->cap_status < nvox) {
-            if (p->dStatus) HIPCHK(hipFree(p->dStatus));
-            HIPCHK(hipMalloc(&p->dStatus, sizeof(int32_t) * (size_t)nvox));
-            p->cap_status = nvox;
-        }
-        status = p->dStatus;
-    }
     if (!p->have_pen) {   // plain NNLS never touches the bands, but the kernel loads them
         HIPCHK(hipMemsetAsync(p->dKband, 0, sizeof(double) * 5 * 128, s));
         HIPCHK(hipMemsetAsync(p->dLband, 0, sizeof(double) * 5 * 128, s));
@@ -1894,7 +1879,6 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
     SortBufs sb = sort_bufs(p);
     // counters and cursors start at zero; the error word (index 4 (nfa + 1) + 1) keeps what earlier ENQUEUED fits may have set
     hipLaunchKernelGGL(reset_sort_kernel, dim3(1), dim3(256), 0, s, sb, p->n_fa, p->err_pending ? 1 : 0);
-    const int nb = (int)((nvox + 255) / 256);
     const int nbs = (int)((nvox + MET2_SORT_BLOCK - 1) / MET2_SORT_BLOCK);          // classify / scatter: one global atomic per (workgroup, flip angle)
     const size_t sort_lds = sizeof(int) * 2 * ((size_t)p->n_fa + 1);                // per-flip-angle tables of the sort kernels in LDS
     if (sort_lds > 48 * 1024) {
@@ -1910,7 +1894,7 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
     // T2SPARC, where one atomic per voxel on the queue word would cap the kernel at 23 M voxels/s (8 -> 82 M)
     int chunk = (method <= MET2_T2SPARC) ? 8 : 1;
     chunk = tuning_env("MET2_CHUNK", 1, 1024, chunk);
-    const bool dbg = getenv("MET2_DEBUG") != nullptr;
+    const bool dbg = test_switch("MET2_DEBUG");
     if (dbg) { HIPCHK(hipStreamSynchronize(s)); fprintf(stderr, "[met2] fit: nvox=%lld grid=%d block=%d lds=%d\n", (long long)nvox, g.grid, g.block, g.lds); fflush(stderr); }
     hipLaunchKernelGGL(classify_kernel, dim3(nbs), dim3(MET2_SORT_BLOCK), sort_lds, s, nvox, p->n_te, p->n_fa, data, voxel_stride, echo_stride, fa_index, mask, 1, sb, status);
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(256), sort_lds, s, p->n_fa, chunk, sb);
@@ -1937,8 +1921,7 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
     A.data = data; A.vs = voxel_stride; A.es = echo_stride; A.sb = sb; A.fsol = fsol; A.sig = sig; A.reg = reg; A.lam = lam; A.maps = maps; A.status = status; A.nvox = nvox;
 
     A.seed = nullptr;
-    const bool no_seed = getenv("MET2_NO_SEED") != nullptr;      // test switch: every voxel grows its first passive set from the lambda = 0 solution
-    if (!no_seed && !objgrid && p->have_pen && p->seeds_valid && p->seeds_ok && p->seeds_key[0] == p->opt.t2sparc_lambda &&
+    if (!test_switch("MET2_NO_SEED") && !objgrid && p->have_pen && p->seeds_valid && p->seeds_ok && p->seeds_key[0] == p->opt.t2sparc_lambda &&
         (method == MET2_X2 || method == MET2_GCV || method == MET2_BAYESREG || method == MET2_T2SPARC)) {
         const int slot = method == MET2_BAYESREG ? 1 : (method == MET2_T2SPARC ? 2 : (method == MET2_GCV ? 3 : 0));      // records built by ensure_seeds() when the plan was configured
         A.seed = p->dSeed + sizeof(SeedRec) * (size_t)slot * p->n_fa;
@@ -1946,9 +1929,9 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
     A.btab = nullptr; A.nbtab = 0; A.btab_stride = p->btab_stride;
     A.chol = nullptr; A.chol_stride = 0;
     if (method == MET2_BAYESREG && !objgrid && g.nb == 2) {
-        // chol_lean's scratch: one packed factor per wave of the widest launch (first pass; the clean-up pass has fewer waves)
+        // chol_lean's scratch: one packed factor per wave of the launch (the spill-over kernel runs with the same geometry)
         const int stride = (col_base(p->n_t2) + 15) & ~15;
-        const int64_t need = (int64_t)g.grid * (kfast ? std::max(g.waves, g2.waves) : g.waves) * stride;
+        const int64_t need = (int64_t)g.grid * g.waves * stride;
         if (p->cap_chol < need) {
             if (p->dChol) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(p->dChol)); p->dChol = nullptr; p->cap_chol = 0; }
             HIPCHK(hipMalloc(&p->dChol, sizeof(double) * (size_t)need));
@@ -1956,10 +1939,10 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
         }
         A.chol = p->dChol; A.chol_stride = stride;
     }
-    // spill-over slots (nnls_big.hpp): a set that outgrows the LDS capacity of the launch goes on in place, its columns beyond the capacity in
-    // the wave's slot -- one launch per fit.
-    A.big = nullptr; A.big_stride = 0; A.all_queued = 0;
-    if (kfast && !two_pass) {
+    // spill-over slots (nnls_big.hpp): a set that outgrows the LDS capacity of the launch goes on in the spill-over kernel, its columns beyond
+    // the capacity in the wave's slot
+    A.big = nullptr; A.big_stride = 0;
+    if (kfast) {
         const int stride = (col_base(p->n_t2) - col_base(g.kmax) + 15) & ~15;
         LaunchGeom gw;                                                      // sized for the widest launch of this shape (a short voxel list runs fewer waves):
         rc = fit_geometry(p, kmeth, gw, kfast, 0, -1);                      // the slots are allocated once, not per block of a host pipeline
@@ -1973,8 +1956,7 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
         A.big = p->dBig; A.big_stride = stride;
     }
     A.lc_save = nullptr; A.lc_at = nullptr; A.lc_cap = 0;
-    A.spill_w2 = getenv("MET2_SPILL_W2") ? atoi(getenv("MET2_SPILL_W2")) : 0;      // test switch (A/B)
-    if (A.big && method == MET2_LCURVE && g.nb == 2 && !objgrid && !getenv("MET2_LC_RESTART")) {
+    if (A.big && method == MET2_LCURVE && g.nb == 2 && !objgrid && !test_switch("MET2_LC_RESTART")) {
         // records for a sixteenth of the voxels (5 % of them overflow on measured spectra), between 4 096 and 262 144 (2.4 GB): entries beyond start over
         const int64_t cap = std::min<int64_t>(nvox, std::min<int64_t>(262144, std::max<int64_t>(4096, nvox / 16)));
         const int64_t need = cap * (LC_SAVE_DOUBLES * 64) + (cap + 1) / 2;
@@ -1985,7 +1967,6 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
         }
         A.lc_save = p->dLcSave; A.lc_at = (int *)(p->dLcSave + cap * (LC_SAVE_DOUBLES * 64)); A.lc_cap = (int)cap;
     }
-    const bool ladder = kfast && !A.big;
     for (int j = 0; j < (MET2_BAYES_TABLE > 0 ? MET2_BAYES_TABLE : 1); ++j) A.blam[j] = p->blam[j];
     if (MET2_BAYES_TABLE > 0 && method == MET2_BAYESREG && !objgrid && p->dBtab && p->seeds_valid && p->seeds_ok && !tuning_env("MET2_NO_BAYES_TABLE", 0, 1, 0)) {
         A.btab = p->dBtab; A.nbtab = MET2_BAYES_TABLE;
@@ -1995,98 +1976,28 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
     // a function call there).
     const bool custom_iv = !objgrid && ((method == MET2_X2 && (p->opt.x2_lo != 0.0 || p->opt.x2_hi != 10.0)) || (method == MET2_GCV && (p->opt.gcv_lo != 1e-8 || p->opt.gcv_hi != 10.0)) ||
                                         (method == MET2_BAYESREG && (p->opt.bayes_lo != 1e-8 || p->opt.bayes_hi != 2.0)));
+    A.all_queued = custom_iv ? 1 : 0;
     HIPCHK(hipEventRecord(p->ev0, s));
     if (objgrid) { A.sig = nullptr; A.maps = nullptr; A.lam = nullptr; }
-    if (custom_iv) {
-        if (two_pass) return fail(MET2_E_UNSUPPORTED, "MET2_TWO_PASS (A/B switch) does not go with non-default lambda-search intervals");
-        A.all_queued = 1;
-        HIPCHK(hipEventRecord(p->ev1, s));
-        rc = launch_method(kmeth, A, g, s, true);
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(p->ev2, s));
-        p->timed2 = true;
-    } else {
+    if (!custom_iv) {
         rc = launch_method(objgrid ? kmeth + 10 : kmeth, A, g, s);
         if (rc) return rc;
-        HIPCHK(hipEventRecord(p->ev1, s));
     }
-    if (custom_iv) {
-    } else if (A.big) {
-        // the spill-over kernel: the voxels the first kernel queued (their passive set outgrew the LDS capacity), same geometry, the solver with its
-        // spill-over legs -- no re-sort, no second capacity; it finds an empty queue in most launches at one bin per lane
+    HIPCHK(hipEventRecord(p->ev1, s));
+    // the spill-over kernel: the voxels the first kernel queued (their passive set outgrew the LDS capacity; under custom intervals every fitted
+    // voxel), same geometry, the solver with its spill-over legs -- no re-sort, no second capacity; it finds an empty queue in most launches at
+    // one bin per lane
+    const bool spill = A.big || custom_iv;
+    if (spill) {
         rc = launch_method(kmeth, A, g, s, true);
         if (rc) return rc;
         HIPCHK(hipEventRecord(p->ev2, s));
-        p->timed2 = true;
-    } else if (ladder) {
-        // gated-out voxels are finalised from the first pass's keys, then the key/perm buffers are reused
-        hipLaunchKernelGGL(finalize_unfitted_kernel, dim3(p->cus * 4), dim3(256), 0, s, nvox, p->n_t2, p->n_te, p->dKey, mask, fsol,
-                           sig, reg, lam, maps);
-        hipLaunchKernelGGL(reset_sort_kernel, dim3(1), dim3(256), 0, s, sb, p->n_fa, 1);              // all but the error word
-        hipLaunchKernelGGL(requeue_overflow_kernel, dim3(nb), dim3(256), 0, s, nvox, fa_index, status, sb);
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(256), sort_lds, s, p->n_fa, chunk, sb);
-        hipLaunchKernelGGL(scatter_kernel, dim3(nbs), dim3(MET2_SORT_BLOCK), sort_lds, s, nvox, p->n_fa, sb);
-        HIPCHK(hipGetLastError());
-        FitArgs A2 = A;
-        const int kmid = mid_kmax(p, kmeth, kfast);
-        if (kmid) {                                         // middle rung: same kernel at capacity kmid; what still overflows is queued once more
-            LaunchGeom gm;
-            rc = fit_geometry(p, kmeth, gm, kmid, 0, -1);
-            if (rc) return rc;
-            A2.kmax = gm.kmax; A2.waves = gm.waves; A2.wave_doubles = gm.wave_doubles;
-            rc = launch_method(kmeth, A2, gm, s);
-            if (rc) return rc;
-            hipLaunchKernelGGL(reset_sort_kernel, dim3(1), dim3(256), 0, s, sb, p->n_fa, 1);
-            hipLaunchKernelGGL(requeue_overflow_kernel, dim3(nb), dim3(256), 0, s, nvox, fa_index, status, sb);
-            hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(256), sort_lds, s, p->n_fa, chunk, sb);
-            hipLaunchKernelGGL(scatter_kernel, dim3(nbs), dim3(MET2_SORT_BLOCK), sort_lds, s, nvox, p->n_fa, sb);
-            HIPCHK(hipGetLastError());
-        }
-        A2.kmax = g2.kmax; A2.waves = g2.waves; A2.wave_doubles = g2.wave_doubles;
-        rc = launch_method(kmeth, A2, g2, s);
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(p->ev2, s));
-        p->timed2 = true;
-    } else p->timed2 = false;
-    p->timed = true;
-    if (dbg) {
-        HIPCHK(hipStreamSynchronize(s)); fprintf(stderr, "[met2] fit kernel done\n");
-#ifdef MET2_CYCSTATS
-        unsigned long long cy[16];
-        HIPCHK(hipMemcpyFromSymbol(cy, HIP_SYMBOL(met2::g_cyc), sizeof(cy)));
-        fprintf(stderr, "[met2] gcv trace: gram(mfma)=%llu tridiag=%llu bisect=%llu weights=%llu\n", cy[8], cy[9], cy[10], cy[11]);
-        fprintf(stderr, "[met2] calls: warm solves=%llu duals=%llu append rounds=%llu inner loops after an append=%llu\n", cy[12], cy[13], cy[14], cy[15]);
-        fprintf(stderr, "[met2] wave cycles: voxel=%llu refactor=%llu inner=%llu dual=%llu append=%llu | slots 5-7 (x2: sse, removals, removal cycles; bayes: chol, upper_times, erf/log; gcv small path: cycles, evaluations, sweeps; append slot += sum k)=%llu %llu %llu\n",
-                cy[0], cy[1], cy[2], cy[3], cy[4], cy[5], cy[6], cy[7]);
-        if (method == MET2_X2) {
-            static unsigned long long ev[40][12];
-            HIPCHK(hipMemcpyFromSymbol(ev, HIP_SYMBOL(met2::g_ev), sizeof(ev)));
-            fprintf(stderr, "[met2] X2 per Brent evaluation index: evals canonical | cycles per eval: refactor inner(incl. removal) dual append sse | removals/eval removal-cycles/eval | k start -> end\n");
-            for (int e = 0; e < 40; ++e) {
-                if (!ev[e][0]) continue;
-                const double c = (double)ev[e][0];
-                fprintf(stderr, "[met2]  ev %2d: %9llu %9llu | %8.0f %8.0f %8.0f %8.0f %8.0f | %5.2f %8.0f | %5.1f -> %5.1f\n", e, ev[e][0], ev[e][10], ev[e][1] / c, ev[e][2] / c,
-                        ev[e][3] / c, ev[e][4] / c, ev[e][5] / c, ev[e][6] / c, ev[e][7] / c, ev[e][8] / c, ev[e][9] / c);
-            }
-        }
-#endif
-#ifdef MET2_BIGSTATS
-        { unsigned long long bs[16]; HIPCHK(hipMemcpyFromSymbol(bs, HIP_SYMBOL(met2::g_bigstats), sizeof(bs)));
-          fprintf(stderr, "[met2] spill-over voxels: solver calls=%llu, with spill-over legs=%llu | cycles plain=%llu spill=%llu (refactor in slot %llu) | appends=%llu removals=%llu refactors=%llu | k start sum=%llu end sum=%llu\n",
-                  bs[0], bs[1], bs[2], bs[3], bs[9], bs[4], bs[5], bs[6], bs[8], bs[7]); }
-#endif
-#ifdef MET2_LOOPSTATS
-        int ls[8];
-        HIPCHK(hipMemcpyFromSymbol(ls, HIP_SYMBOL(met2::g_loopstats), sizeof(ls)));
-        fprintf(stderr, "[met2] loop maxima: tries=%d sweeps=%d outer=%d iter=%d taken=%d round=%d jacobi_sweeps=%d last_sweep_rotations=%d\n", ls[0], ls[1], ls[2], ls[3], ls[4], ls[5], ls[6], ls[7]);
-#endif
-        fflush(stderr);
     }
-    if (!ladder) {
-        hipLaunchKernelGGL(finalize_unfitted_kernel, dim3(p->cus * 4), dim3(256), 0, s, nvox, p->n_t2, p->n_te, p->dKey, mask, fsol,
-                           objgrid ? nullptr : sig, reg, objgrid ? nullptr : lam, objgrid ? nullptr : maps);
-        HIPCHK(hipGetLastError());
-    }
+    p->timed = true; p->timed2 = spill;
+    if (dbg) { rc = debug_counters(method, s); if (rc) return rc; }
+    hipLaunchKernelGGL(finalize_unfitted_kernel, dim3(p->cus * 4), dim3(256), 0, s, nvox, p->n_t2, p->n_te, p->dKey, mask, fsol,
+                       objgrid ? nullptr : sig, reg, objgrid ? nullptr : lam, objgrid ? nullptr : maps);
+    HIPCHK(hipGetLastError());
     // FA index range errors (IndexError in the reference): the error word lands in the plan's pinned host word; the blocking entries
     // wait for it here, an enqueued fit leaves it to met2_plan_finish (errors of several enqueued fits accumulate: the kernel ORs)
     HIPCHK(hipMemcpyAsync(p->hErr, sb.err, 4 * sizeof(int), hipMemcpyDeviceToHost, s));      // the error word and the spill-over queue.s tail and head
@@ -2133,7 +2044,7 @@ int met2_fa_bruteforce_strided(met2_plan *p, int64_t nvox, const double *data, i
     // Mh: doubles of H per voxel -- h of every flip angle, and behind it (when the walk prunes) the 16 coefficients of the voxel in every
     // flip angle's low-rank basis.  Pruning needs the basis to span the dictionary (p->gcv_lr), all residuals NOT to be asked for, and the
     // bounds of all angles to fit two per lane; MET2_FA_NOPRUNE=1: test switch.
-    const bool prune = p->gcv_lr && !resid && p->n_fa >= 8 && p->n_fa <= 128 && !getenv("MET2_FA_NOPRUNE");      // (<= 128: the bounds are formed two per lane)
+    const bool prune = p->gcv_lr && !resid && p->n_fa >= 8 && p->n_fa <= 128 && !test_switch("MET2_FA_NOPRUNE");      // (<= 128: the bounds are formed two per lane)
     // round 5: a pruning walk forms its h from the low-rank basis (fa_kernel), so its scratch is the 16 coefficients per angle and the bounds --
     // 12.4 KB per voxel at 91 angles where H took 87 KB more; the exhaustive walk (all residuals asked for; a dictionary the basis does not span) keeps H
     const int64_t Mh0 = prune ? 0 : (int64_t)p->n_fa * p->n_t2;
@@ -2199,7 +2110,7 @@ int met2_fa_bruteforce_strided(met2_plan *p, int64_t nvox, const double *data, i
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(p->ev1, s));
 #ifdef MET2_CYCSTATS
-    if (getenv("MET2_DEBUG")) {
+    if (test_switch("MET2_DEBUG")) {
         HIPCHK(hipStreamSynchronize(s));
         unsigned long long cy[8];
         HIPCHK(hipMemcpyFromSymbol(cy, HIP_SYMBOL(met2::g_cyc), sizeof(cy)));
@@ -2300,7 +2211,7 @@ int met2_plan_gcv_form(met2_plan *p, int32_t *low_rank, double *residual)
 {
     if (!p) return fail(MET2_E_INVALID, "NULL plan");
     if (!p->have_dict) return fail(MET2_E_STATE, "no dictionary in the plan");
-    if (low_rank) *low_rank = (p->gcv_lr && !getenv("MET2_GCV_FULL")) ? 1 : 0;
+    if (low_rank) *low_rank = kernel_method(p, MET2_GCV) == MET2_GCV_LR ? 1 : 0;
     if (residual) *residual = p->gcv_res;
     return MET2_OK;
 }
@@ -2309,7 +2220,7 @@ int met2_plan_launch_info(met2_plan *p, int32_t method, int32_t *grid, int32_t *
 {
     if (!p) return fail(MET2_E_INVALID, "NULL plan");
     LaunchGeom g;
-    if (method == MET2_GCV && p->gcv_lr && !getenv("MET2_GCV_FULL")) method = MET2_GCV_LR;      // the variant fit_impl launches
+    method = kernel_method(p, method);      // the variant fit_impl launches
     const int kf = fast_kmax(p, method);
     int rc = fit_geometry(p, method, g, kf);
     if (rc) return rc;

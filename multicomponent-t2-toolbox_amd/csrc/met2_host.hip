@@ -668,7 +668,7 @@ static int fit_host_impl(met2_plan *const *plans, int32_t n_plans, int32_t metho
     if (chunk > 0x7fffffff) return fail(MET2_E_INVALID, "chunk out of range");
     // several plans: the list is dealt in runs of 4 096 voxels (pipeline()); the layouts whose blocks are moved by pitched copies already (rows
     // with a pitch, general strides) keep whole blocks.  MET2_HOST_BLOCKS=1: whole blocks always (A/B switch).
-    const bool interleave = n_plans > 1 && (voxel_stride == 1 || (echo_stride == 1 && voxel_stride == nte)) && getenv("MET2_HOST_BLOCKS") == nullptr;
+    const bool interleave = n_plans > 1 && (voxel_stride == 1 || (echo_stride == 1 && voxel_stride == nte)) && !test_switch("MET2_HOST_BLOCKS");
     if (interleave) chunk = (chunk + 4095) / 4096 * 4096;
 
     Job J;
@@ -676,7 +676,7 @@ static int fit_host_impl(met2_plan *const *plans, int32_t n_plans, int32_t metho
     J.fa_index = fa_index; J.mask = mask; J.estimate_fa = estimate_fa; J.fsol = fsol; J.sig = sig; J.reg = reg; J.lam = lam; J.maps = maps;
     J.status = status; J.fa_out = fa_out; J.fa_gate = fa_gate; J.mask_values = mask_values; J.chunk = chunk; J.nte = nte; J.nt2 = nt2;
     J.run = interleave ? 4096 : 0;
-    J.split = getenv("MET2_HOST_NOSPLIT") == nullptr;            // test / A-B switch: whole blocks only
+    J.split = tuning_env("MET2_HOST_NOSPLIT", 0, 1, 0) == 0;     // MET2_HOST_NOSPLIT=1 (tuning builds): whole blocks only
     J.in_case = echo_stride == 1 ? 0 : (voxel_stride == 1 ? 1 : 2);
     if (J.in_case == 0 && voxel_stride < nte) return fail(MET2_E_INVALID, "met2_fit_host: voxel_stride < n_te with echo_stride 1 (overlapping voxels)");
     {   // data and fa_data may also lie in DEVICE memory (the volume as a whole-volume filter left it): copied block by block like pinned memory

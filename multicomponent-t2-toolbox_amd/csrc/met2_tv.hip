@@ -531,23 +531,17 @@ struct TvLayout {
     size_t off_F, off_P0, off_P1, off_coef, off_partial, off_state, off_weight, bytes;
 };
 
-int tv_env(const char *name, int dflt)
-{
-    const char *v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-
 void tv_layout(int n0, int n1, int n2, int nt, TvLayout &L)
 {
     L.vol = (int64_t)n0 * n1 * n2; L.elems = L.vol * nt;
     L.c0 = (n0 + 3) / 2; L.c1 = (n1 + 3) / 2; L.c2 = (n2 + 3) / 2;
     L.nc = (int64_t)L.c0 * L.c1 * L.c2;
-    L.oy = tv_env("MET2_TV_OY", 8);                                  // rows of a tile = waves of a workgroup; measured 4 / 8 / 16: 0.387 / 0.381 / 0.428 ms per iteration
+    L.oy = tuning_env("MET2_TV_OY", 4, 16, 8);                       // rows of a tile = waves of a workgroup; measured 4 / 8 / 16: 0.387 / 0.381 / 0.428 ms per iteration
     if (L.oy != 4 && L.oy != 8 && L.oy != 16) L.oy = 8;
     L.step1 = n1 <= L.oy ? L.oy : L.oy - 1;                          // a tile that spans the axis needs no halo row
     L.step2 = 64;                                                    // no overlap along the contiguous axis (tv_iter_kernel: EDGE)
     L.nt1 = (n1 + L.step1 - 1) / L.step1; L.nt2 = (n2 + L.step2 - 1) / L.step2;
-    L.xlen = std::max(1, std::min(n0, tv_env("MET2_TV_XLEN", 16)));
+    L.xlen = std::max(1, std::min(n0, tuning_env("MET2_TV_XLEN", 1, 1 << 30, 16)));
     L.nseg = (n0 + L.xlen - 1) / L.xlen;
     L.ntiles = L.nt1 * L.nt2 * L.nseg;
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };

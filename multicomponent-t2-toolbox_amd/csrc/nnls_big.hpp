@@ -3,7 +3,7 @@
 // The fit kernels give every wave an LDS region for a factor of capacity S.kmax < n (as many resident waves as the registers allow:
 // 16 per CU at one bin per lane, 8 at two).  Until round 4 a voxel whose set wanted to grow past that capacity was dropped, re-queued and
 // solved again from scratch by a second launch at full capacity (2 waves per CU at nT2 = 120) -- a serial tail behind every fit.  Now the
-// voxel goes on IN PLACE: columns c >= S.kmax of the factor live in a per-wave slot in global memory (S.Rg, L2-resident: written and read
+// voxel is solved again at the SAME capacity and occupancy: columns c >= S.kmax of the factor live in a per-wave slot in global memory (S.Rg, L2-resident: written and read
 // by this wave only), columns below stay in LDS, and the routines below address an entry through a generic pointer whose aperture decides
 // (flat loads and stores).  Where a column lives is a function of its index alone, so the fast routines of nnls_wave.hpp are valid again
 // as soon as a later solve starts with k <= S.kmax; only the evaluations that really hold a large set pay the global round trips
@@ -11,11 +11,11 @@
 //
 // The arithmetic is that of the fast routines (same sums in the same order); the code is the plain form of each -- no one-slot legs,
 // no pairing of LDS reads -- because it runs for a few evaluations of a few voxels.  None of it is compiled into the fit kernels' own
-// voxel loop (template argument BIG = false there: the round-4 code token for token, a set at the capacity flags the voxel); the voxel
-// is then solved again, at once and by the same wave, by a NOT-inlined instance of the voxel routine with BIG = true (fit_kernel.hpp:
-// fit_voxel_spill) -- one call site per kernel, so the hot loop's register allocation does not see this code.  Stores to the factor are followed by a
-// workgroup-scope fence before other lanes read them (big_sync): the slot is private to the wave, the fence orders the wave's own
-// stores and loads.
+// voxel loop (template argument BIG = false there: the round-4 code token for token, a set at the capacity puts the voxel on the spill-over
+// queue); the spill-over kernel launched behind the fit kernel, with the same geometry, solves the queued voxels again by a NOT-inlined
+// instance of the voxel routine with BIG = true (fit_kernel.hpp: fit_voxel_spill) -- one call site per kernel, so the hot loop's register
+// allocation does not see this code.  Stores to the factor are followed by a workgroup-scope fence before other lanes read them (big_sync):
+// the slot is private to the wave, the fence orders the wave's own stores and loads.
 #pragma once
 
 namespace met2 {

@@ -53,6 +53,18 @@ def find(d, suffix):
     return hits[0]
 
 
+def kernel_filter(name):
+    """the kernel's name without the return type and the argument list: 'void fit_kernel<2, 1, false>(FitArgs)' -> 'fit_kernel<2, 1, false>',
+    'void (anonymous namespace)::tv_iter_kernel<8, false, false>((anonymous namespace)::TvIterArgs)' -> '(anonymous namespace)::tv_iter_kernel<8, false, false>'"""
+    s = name[len("void "):] if name.startswith("void ") else name
+    depth = 0
+    for i in range(len(s) - 1, 0, -1) if s.endswith(")") else ():      # the argument list is the last parenthesised group
+        depth += (s[i] == ")") - (s[i] == "(")
+        if depth == 0:
+            return s[:i]
+    return s
+
+
 def counters(d, kernel_substr, steps=2, sum_step=False):
     """{counter: value} of the dominant dispatch of the last step of the kernel whose name contains kernel_substr.  A method
     with a clean-up pass launches the same kernel symbol twice per step (first pass, then the few voxels that hit the capacity):
@@ -97,7 +109,7 @@ def main():
     krows = [r for r in stats if a.kernel in r["Name"]]
     krows.sort(key=lambda r: -float(r["TotalDurationNs"]))
     dominant = krows[0]["Name"] if krows else a.kernel
-    sub = dominant.split("(")[0].replace("void ", "")
+    sub = kernel_filter(dominant)
     groups = [("fetch", ["FETCH_SIZE"]), ("write", ["WRITE_SIZE"]),
               ("sq1", ["SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_INSTS_SMEM", "SQ_INSTS_VMEM_RD", "SQ_INSTS_VMEM_WR"]),
               ("sq2", ["SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_VALU", "SQ_ACTIVE_INST_ANY", "SQ_BUSY_CYCLES"]),

@@ -1,5 +1,6 @@
 """met2_fit_host on configs[1]'s volume (128x128x64, 32x60, X2/L2): 1, 2 and 4 plans sharing the one device of the test box, pinned and
-pageable arrays, default and explicit block sizes.  Prints one JSON line per case (-> profiles/r04_host_entry.jsonl)."""
+pageable arrays, default and explicit block sizes.  Prints one JSON line per case (-> profiles/r04_host_entry.jsonl).
+The whole-block cases set MET2_HOST_NOSPLIT=1, which only a library built with MET2_BUILD_DEFINES=-DMET2_TUNING reads."""
 import importlib
 import json
 import os

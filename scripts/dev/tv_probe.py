@@ -1,6 +1,7 @@
 """GPU probe of the TV denoiser (met2_tv_chambolle): wall time of the whole step on a 128 x 128 x 64 x 32 phantom, iteration counts per
 echo, time per Chambolle iteration and the HBM rate its 56 algorithmic bytes per (voxel, echo) amount to.
-    python3 scripts/dev/tv_probe.py [nx ny nz nt] [--fortran]"""
+    python3 scripts/dev/tv_probe.py [nx ny nz nt] [--fortran]
+MET2_TV_OY / MET2_TV_XLEN (tile rows, segment length) are read only by a library built with MET2_BUILD_DEFINES=-DMET2_TUNING."""
 import importlib
 import json
 import os
