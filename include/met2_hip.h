@@ -235,6 +235,39 @@ int met2_plan_attach_fa_spline(met2_plan *plan, met2_plan *plan_lr, int32_t n_lr
  * wait; a driver that builds its plans per call then allocates and pins nothing per call); this frees the waiting ones. */
 int met2_host_trim(void);
 
+/* ---- bootstrap uncertainty maps (an extension: the reference has no counterpart) ----------
+ * Monte-Carlo noise propagation per voxel.  The point fit is met2_fit_strided's, bit for bit (fsol, sig, reg, lam, maps, status as there; let
+ * s_hat = sig[v]).  Then every voxel is refitted on n_rep = B Rician replicates of its fitted signal with the same method, plan, flip angle and
+ * mask, and the statistics of the metrics over the replicates are returned.  The ingredients are the reference's:
+ *   noise model   Rician at sigma around the signal, scripts_synthetic_data_evaluation/Paper_Comparison/
+ *                 evaluate_all_methods_two_lobes_SNR50_150.py:387-391:  M_b[e] = sqrt((s_hat_e + sigma_v z1)^2 + (sigma_v z2)^2)
+ *   sigma_v       sigma[v] when `sigma` is given; otherwise the estimate of intravoxel_algorithms/bayesian_interpolation.py:88-93 on the raw
+ *                 echoes: a plain-NNLS pass (MET2_NNLS) at the voxel's flip angle gives fsol0, sig0 and
+ *                 sigma_v = sqrt(sum_e (M_e - sig0_e)^2 / max(n_te - #{fsol0 > 0}, 1)); returned in sigma_out
+ *   replicates    counter-based: (x0, x1, x2, x3) = Philox4x32-10(counter = (e, b, lo32(id_v), hi32(id_v)), key = (lo32(seed), hi32(seed))),
+ *                 id_v = voxel_id[v] (NULL: v), u1 = ((x0 >> 5) 2^26 + (x1 >> 6) + 1) 2^-53 in (0, 1], u2 = ((x2 >> 5) 2^26 + (x3 >> 6)) 2^-53,
+ *                 r = sqrt(-2 log u1), z1 = r cos(2 pi u2), z2 = r sin(2 pi u2).  A voxel's replicates depend on (seed, id_v, b, e) alone: not
+ *                 on chunking, call splitting, voxel order or device.  Any 64-bit seed (its bits are taken as they are)
+ *   fits          each replicate as met2_fit fits its echoes, at the voxel's FA index and mask; replicates of a voxel whose point status lacks
+ *                 MET2_ST_FITTED are not fitted.  FA is not re-estimated per replicate
+ * DEVICE pointers: data (echo e of voxel v at data[v * voxel_stride + e * echo_stride], strides > 0), fa_index, mask, fsol, sig, reg, lam,
+ * maps, status as for met2_fit_strided; voxel_id [nvox] int64 or NULL; sigma [nvox] (>= 0) or NULL; sigma_out [nvox]; out:
+ *   stats       [7][5][nvox]  quantities MWF, IEWF, FWF, T2_M, T2_IE, TWC (the maps' order) and reg; statistics mean, std (ddof = 1; both in
+ *                             two deterministic passes) and the 0.025, 0.5, 0.975 quantiles, bit-equal to np.quantile (method 'linear').
+ *                             Zeros where the point status lacks MET2_ST_FITTED
+ *   rep_status  [nvox]        OR of the replicates' status bits (0 where not fitted)
+ * sig, lam, maps, status, sigma_out and rep_status may be NULL.  2 <= n_rep <= 1024.  The replicates are fitted in chunks of whole voxels
+ * (262 144 rows; 4 096 for L-curve at n_t2 > 64) through met2_fit_enqueue_strided on scratch kept with the plan until met2_plan_destroy.
+ * Blocking (one wait after the point fit, which reports an FA index outside the dictionary, and one at the end). */
+int met2_fit_bootstrap(met2_plan *plan, int32_t method, int64_t nvox, const double *data, int64_t voxel_stride, int64_t echo_stride,
+                       const double *fa_index, const uint8_t *mask, const int64_t *voxel_id, const double *sigma, int32_t n_rep,
+                       int64_t seed, double *fsol, double *sig, double *reg, double *lam, double *maps, int32_t *status,
+                       double *sigma_out, double *stats, int32_t *rep_status, void *stream);
+/* Test/diagnostic entry: the replicates of met2_fit_bootstrap for given centres.  DEVICE pointers: center [nvox][n_te] (the s_hat), sigma
+ * [nvox], voxel_id [nvox] or NULL; out [nvox][n_rep][n_te].  Every voxel gets replicates (no gating).  Asynchronous on `stream`. */
+int met2_bootstrap_replicates(met2_plan *plan, int64_t nvox, const double *center, const double *sigma, const int64_t *voxel_id,
+                              int32_t n_rep, int64_t seed, double *out, void *stream);
+
 /* Test/diagnostic entry: `method` = 10 + MET2_X2 / MET2_GCV / MET2_BAYESREG passed to met2_fit
  * evaluates that method's lambda-selection objective (algorithms.py:226-233, :285-296,
  * bayesian_interpolation.py:107-126) on the plan's lambda grid (n <= n_t2 points) and stores the

@@ -78,6 +78,7 @@ extern template int launch_fit_nb<6, 2, true>(const FitArgs &, const LaunchGeom 
 // error plumbing
 // ------------------------------------------------------------------------------------------
 namespace met2 { __attribute__((visibility("hidden"))) void host_release(met2_plan *plan); }
+namespace met2 { __attribute__((visibility("hidden"))) void bootstrap_release(met2_plan *plan); }
 static thread_local std::string g_err;
 int met2::abi_fail(int code, const std::string &msg) { g_err = msg; return code; }
 
@@ -1579,6 +1580,7 @@ int met2_plan_destroy(met2_plan *p)
 {
     if (!p) return MET2_OK;
     met2::host_release(p);           // what met2_fit_host keeps with the plan (met2_host.hip)
+    met2::bootstrap_release(p);      // what met2_fit_bootstrap keeps with the plan (met2_bootstrap.hip)
     DevGuard dev_guard_(p->opt.device);
     void *bufs[] = {p->dQt, p->dAq, p->dAqRes, p->dD, p->dB, p->dDt, p->dKband, p->dLband, p->dKd, p->dLam, p->dT2, p->dKey, p->dPerm, p->dOvf, p->dSmall, p->dSeed, p->dBtab, p->dH, p->dChol, p->dBig, p->dLcSave};
     for (void *b : bufs) (void)hipFree(b);

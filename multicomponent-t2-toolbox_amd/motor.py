@@ -150,7 +150,7 @@ def _estimate_fa(plan, dd_fa, mm, FA_method, fa_index, T2s, T1s, tau, TR, alpha_
 
 def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2", FA_method="brute-force", myelin_T2=40.0,
                       fa_index=None, device=0, plan=None, denoise="None", prepared=False, FA_smooth="no", distributed=False,
-                      return_prepared=False, devices=None):
+                      return_prepared=False, devices=None, bootstrap=None):
     """Steps 1-4 of motor_recon_met2 (motor:293-373, 427-472) on arrays: data [nx,ny,nz,nt] (or
     [nvox, nt]), mask [nx,ny,nz].  Mirrors the driver's preparation: data *= mask (motor:180-182),
     negative values clipped to 0 (motor:279), optional NESMA / TV filter (motor:293-333, needs a 3-D volume),
@@ -165,7 +165,14 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     devices=[d0, d1, ...]: ONE process drives several GPUs through the C ABI's host entry (met2_fit_host: one plan and one host thread per
     device inside the call, blocks of voxels dealt round-robin, outputs copied by every device into the same host arrays -- no
     torch.distributed); the whole-volume filters (TV / NESMA / FA smoothing) run on devices[0] first.  Same outputs bit for bit.
+    bootstrap=dict(n_rep=100, seed=0): per-voxel bootstrap uncertainty of the metrics (Met2Plan.fit_bootstrap; an extension with no
+    counterpart in the reference), on one device (devices[0]) with the pipeline's prepared data and FA indices; voxel_id is the voxel's flat
+    index in the volume's C order, whatever the memory order.  Adds '<Q>_bootstrap' [vol..., 5] for Q in BOOT_QUANTITIES (BOOT_STATS along
+    the last axis), 'sigma' and 'rep_status'; the ten outputs are those of the same run without it.
     Returns a dict with the driver's ten outputs."""
+    boot = _bootstrap_args(bootstrap)
+    if boot is not None and distributed:
+        raise ValueError("bootstrap runs on one device and does not go with distributed=True")
     if FA_method not in ("brute-force", "spline"):
         raise ValueError("FA_method must be 'spline' or 'brute-force'")
     if denoise not in ("None", None, "none", "NESMA", "TV"):
@@ -180,8 +187,20 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     if devices is not None:
         if plan is not None or distributed:
             raise ValueError("devices=[...] builds its own plans and does not go with distributed=True")
-        return _recon_multi_device(data, mask, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, fa_index, list(devices), prepared,
-                                   denoise, FA_smooth, return_prepared)
+        res = _recon_multi_device(data, mask, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, fa_index, list(devices), prepared,
+                                  denoise, FA_smooth, return_prepared or boot is not None)
+        if boot is not None:
+            dd = res["data_prepared"] if return_prepared else res.pop("data_prepared")
+            TE_array = np.asarray(TE_array, dtype=np.float64)
+            plan = Met2Plan(nt, res["T2s"].shape[0], 91 * 3 if FA_method == "spline" else 91, device=devices[0], myelin_T2=myelin_T2)
+            try:
+                plan.build_dictionary_epg(res["T2s"], 1000.0 * np.ones_like(res["T2s"]), float(TE_array[1] - TE_array[0]),
+                                          np.linspace(90.0, 180.0, plan.n_fa), TR)
+                plan.set_penalty("InvT2" if reg_method == "T2SPARC" else reg_matrix, res["T2s"])
+                _bootstrap_into(res, plan, reg_method, torch.as_tensor(dd).to(plan.device), res["FA_index"], mask > 0, boot)
+            finally:
+                plan.close()
+        return res
     dev = plan.device if plan is not None else torch.device("cuda", device)
     # a caller's own plan, a distributed run, or a bare voxel list: the volume on the device in one piece
     dd, mk = _prepare_volume(data, mask, dev, prepared, denoise)
@@ -218,10 +237,36 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
         res["T2s"] = T2s
         if return_prepared:
             res["data_prepared"] = dd.cpu().numpy()
+        if boot is not None:
+            _bootstrap_into(res, plan, reg_method, dd, fa_vol, mm, boot)
         return res
     finally:
         if own:
             plan.close()
+
+
+def _bootstrap_args(bootstrap):
+    if bootstrap is None:
+        return None
+    extra = set(bootstrap) - {"n_rep", "seed"}
+    if extra:
+        raise ValueError("bootstrap takes n_rep and seed, not %s" % sorted(extra))
+    return {"n_rep": int(bootstrap.get("n_rep", 100)), "seed": int(bootstrap.get("seed", 0))}
+
+
+def _bootstrap_into(res, plan, reg_method, dd, fa_vol, mask, boot):
+    """recon_met2_arrays(bootstrap=...): Met2Plan.fit_bootstrap on the prepared volume dd [vol..., nt] (a device tensor) with the run's FA
+    indices and mask; the statistics go into res beside the ten outputs, which stay as the run made them."""
+    from .plan import BOOT_QUANTITIES
+    vol = tuple(dd.shape[:-1])
+    vid = np.arange(int(np.prod(vol)), dtype=np.int64).reshape(vol)       # the C-order flat index: independent of the memory order
+    out = plan.fit_bootstrap(reg_method, dd, n_rep=boot["n_rep"], seed=boot["seed"], fa_index=fa_vol, mask=mask, voxel_id=vid,
+                             want_sig=True, want_status=False)
+    stats = out["stats"].cpu().numpy()                                    # [7, 5, vol...]
+    for i, q in enumerate(BOOT_QUANTITIES):
+        res[q + "_bootstrap"] = np.moveaxis(stats[i], 0, -1)
+    res["sigma"] = out["sigma"].cpu().numpy()
+    res["rep_status"] = out["rep_status"].cpu().numpy()
 
 
 PIPELINE_CHUNK = 262144       # voxels per DMA block the driver asks met2_fit_host for (262 144: the library's own default; a test sets others)
@@ -366,12 +411,14 @@ def _recon_sharded(plan, dd, dd_fa, mm, reg_method, FA_method, fa_index, T2s, T1
 
 
 def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR, reg_method, reg_matrix, denoise, FA_method,
-                     FA_smooth, myelin_T2, num_cores=-1, device=0, devices=None):
+                     FA_smooth, myelin_T2, num_cores=-1, device=0, devices=None, bootstrap=None):
     """Drop-in for motor_recon_met2 (motor:165-506) with the reference's on-disk contract: NIfTI in
     (data [nx,ny,nz,nt], mask [nx,ny,nz]), ten NIfTI volumes out (MWF, IEWF, FWF, T2_M, T2_IE, TWC, FA, fsol_4D,
     Est_Signal, reg_param .nii.gz at path_to_save_data, motor:475-503).  `num_cores` is accepted and ignored (one
     process drives the GPU; devices=[0, 1, ...]: that one process drives all the listed GPUs through met2_fit_host).  denoise: 'None',
-    'NESMA' (motor:305-333) or 'TV' (motor:293-304).  Not reproduced: the mean-spectrum PNG of motor:377-424."""
+    'NESMA' (motor:305-333) or 'TV' (motor:293-304).  Not reproduced: the mean-spectrum PNG of motor:377-424.
+    bootstrap=dict(n_rep=..., seed=...) (an extension, see recon_met2_arrays) also writes <Q>_bootstrap.nii.gz [nx,ny,nz,5] for Q in
+    BOOT_QUANTITIES (BOOT_STATS along the last axis) and sigma.nii.gz."""
     from . import nifti
     img = nifti.load(path_to_data)
     data = img.get_fdata().astype(np.float64, copy=False)           # Fortran-ordered, like nibabel's: read in place by the solver
@@ -379,11 +426,16 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     if data.ndim != 4 or mask.shape != data.shape[:3]:
         raise ValueError("data must be 4-D and mask must match its first three dimensions")
     res = recon_met2_arrays(data, mask, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, device=device, denoise=denoise,
-                            FA_smooth=FA_smooth, return_prepared=(denoise == "TV"), devices=devices)
+                            FA_smooth=FA_smooth, return_prepared=(denoise == "TV"), devices=devices, bootstrap=bootstrap)
     if denoise == "TV":                                             # motor:302-303
         nifti.save(nifti.NiftiImage(res.pop("data_prepared"), img.affine), path_to_save_data + "Data_denoised.nii.gz")
     for name in ("MWF", "IEWF", "FWF", "T2_M", "T2_IE", "TWC", "FA", "fsol_4D", "Est_Signal", "reg_param"):
         nifti.save(nifti.NiftiImage(res[name], img.affine), path_to_save_data + name + ".nii.gz")
+    if bootstrap is not None:
+        from .plan import BOOT_QUANTITIES
+        for q in BOOT_QUANTITIES:
+            nifti.save(nifti.NiftiImage(res[q + "_bootstrap"], img.affine), path_to_save_data + q + "_bootstrap.nii.gz")
+        nifti.save(nifti.NiftiImage(res["sigma"], img.affine), path_to_save_data + "sigma.nii.gz")
     return res
 
 

@@ -11,6 +11,8 @@ from ._lib import Options, check, lib
 METHODS = {"NNLS": 0, "T2SPARC": 1, "X2": 2, "L_curve": 3, "GCV": 4, "BayesReg": 5}
 PENALTIES = {"I": 0, "L1": 1, "L2": 2, "InvT2": 3}
 MAP_NAMES = ("MWF", "IEWF", "FWF", "T2_M", "T2_IE", "TWC")
+BOOT_QUANTITIES = MAP_NAMES + ("reg",)              # fit_bootstrap's stats [7][5][...]: the six maps and reg_param
+BOOT_STATS = ("mean", "std", "q025", "q500", "q975")
 
 _dp = C.POINTER(C.c_double)
 
@@ -225,6 +227,86 @@ class Met2Plan:
         if len(vol) > 1:
             res = {k: (None if t is None else unflatten(t, vol, order, lead=1 if k == "maps" else 0)) for k, t in res.items()}
         return res
+
+    def fit_bootstrap(self, method, data, n_rep=100, seed=0, fa_index=None, mask=None, sigma=None, voxel_id=None, want_sig=True,
+                      want_status=True, want_lambda=False):
+        """Per-voxel bootstrap uncertainty (met2_fit_bootstrap; an extension with no counterpart in the reference).  The point fit is
+        fit()'s, bit for bit; then every fitted voxel is refitted on n_rep Rician replicates of its fitted signal at its noise level
+        (`sigma`, one entry per voxel, or the plain-NNLS estimate of bayesian_interpolation.py:88-93) and the statistics of the metrics
+        are returned.  data, fa_index, mask as for fit(); voxel_id: int64 per voxel (default: the voxel's flat index in the data's
+        voxel order) -- a voxel's replicates depend on (seed, voxel_id, replicate, echo) alone.  Returns fit()'s dict plus
+        stats [7, 5, vol...] (BOOT_QUANTITIES x BOOT_STATS), sigma [vol...] and rep_status [vol...] (OR of the replicates' status bits)."""
+        if method not in METHODS:
+            raise ValueError("unknown reg_method %r" % (method,))
+        if not torch.is_tensor(data):
+            raise ValueError("data must be a CUDA tensor (the hot path has no host fallback)")
+        if data.dtype != torch.float64:
+            raise ValueError("data must be float64, got %s" % (data.dtype,))
+        if data.dim() < 2 or data.shape[-1] != self.n_te:
+            raise ValueError("data must be [..., n_te=%d], got %s" % (self.n_te, tuple(data.shape)))
+        n_rep = int(n_rep)
+        if not 2 <= n_rep <= 1024:
+            raise ValueError("n_rep must lie in [2, 1024], got %d" % n_rep)
+        seed = int(seed)
+        if not -2 ** 63 <= seed < 2 ** 64:
+            raise ValueError("seed must fit in 64 bits")
+        if seed >= 2 ** 63:
+            seed -= 2 ** 64                                  # the C entry takes the bits as int64_t
+        nvox = 1
+        for d in data.shape[:-1]:
+            nvox *= int(d)
+        if sigma is not None:
+            sg = sigma if torch.is_tensor(sigma) else torch.as_tensor(np.asarray(sigma, dtype=np.float64))
+            if sg.numel() != nvox:
+                raise ValueError("sigma has %d entries for %d voxels" % (sg.numel(), nvox))
+            if bool((sg < 0).any()) or bool(torch.isnan(sg).any()):
+                raise ValueError("sigma must be >= 0")
+        if voxel_id is not None:
+            vid_n = voxel_id.numel() if torch.is_tensor(voxel_id) else np.asarray(voxel_id).size
+            if vid_n != nvox:
+                raise ValueError("voxel_id has %d entries for %d voxels" % (vid_n, nvox))
+        self._check_data(data)
+        data, nvox, vs, es, vol, order = voxel_layout(data, self.n_te)
+        dev = self.device
+        fa_index = self._per_voxel(fa_index, nvox, torch.float64, "fa_index", order)
+        mask = self._per_voxel(mask, nvox, torch.uint8, "mask", order)
+        sigma = self._per_voxel(sigma, nvox, torch.float64, "sigma", order)
+        vid = self._per_voxel(voxel_id, nvox, torch.int64, "voxel_id", order)
+        e = lambda shape, dt=torch.float64: torch.empty(shape, dtype=dt, device=dev)
+        fsol, reg, maps = e((nvox, self.n_t2)), e((nvox,)), e((6, nvox))
+        sig = e((nvox, self.n_te)) if want_sig else None
+        lam = e((nvox,)) if want_lambda else None
+        status = e((nvox,), torch.int32) if want_status else None
+        sigma_out, stats, rep_status = e((nvox,)), e((7, 5, nvox)), e((nvox,), torch.int32)
+        with torch.cuda.device(dev):
+            check(lib().met2_fit_bootstrap(self._h, METHODS[method], nvox, _ptr(data), vs, es, _ptr(fa_index), _ptr(mask), _ptr(vid), _ptr(sigma),
+                                           n_rep, seed, _ptr(fsol), _ptr(sig), _ptr(reg), _ptr(lam), _ptr(maps), _ptr(status), _ptr(sigma_out),
+                                           _ptr(stats), _ptr(rep_status), self._stream()))
+        res = {"fsol": fsol, "sig": sig, "reg": reg, "lam": lam, "maps": maps, "status": status, "sigma": sigma_out, "stats": stats,
+               "rep_status": rep_status}
+        if len(vol) > 1:
+            lead = {"maps": 1, "stats": 2}
+            res = {k: (None if t is None else unflatten(t, vol, order, lead=lead.get(k, 0))) for k, t in res.items()}
+        return res
+
+    def bootstrap_replicates(self, center, sigma, n_rep, seed=0, voxel_id=None):
+        """The replicates fit_bootstrap fits (met2_bootstrap_replicates): center [nvox, n_te] and sigma [nvox] float64 CUDA tensors,
+        voxel_id [nvox] int64 (default 0..nvox-1) -> [nvox, n_rep, n_te].  No gating: every voxel gets replicates."""
+        self._check_data(center, "center")
+        self._check_data(sigma, "sigma")
+        center = center.contiguous()
+        if center.dim() != 2 or center.shape[1] != self.n_te:
+            raise ValueError("center must be [nvox, n_te=%d]" % self.n_te)
+        nvox = center.shape[0]
+        sigma = self._per_voxel(sigma, nvox, torch.float64, "sigma")
+        vid = None if voxel_id is None else self._per_voxel(voxel_id, nvox, torch.int64, "voxel_id")
+        seed = int(seed)
+        if seed >= 2 ** 63:
+            seed -= 2 ** 64
+        out = torch.empty((nvox, int(n_rep), self.n_te), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().met2_bootstrap_replicates(self._h, nvox, _ptr(center), _ptr(sigma), _ptr(vid), int(n_rep), seed, _ptr(out), self._stream()))
+        return out
 
     def finish(self):
         """Wait for the current stream and report what fits enqueued with sync=False deferred (met2_plan_finish)."""

@@ -1,0 +1,140 @@
+"""CPU-only tests of the bootstrap mode (met2_fit_bootstrap): a numpy restatement of the counter-based generator's Philox4x32-10
+against Random123's known-answer vectors (the GPU tests compare the device's replicates with this restatement), and the argument
+checks of the C entries and of Met2Plan.fit_bootstrap, which run before anything touches a device."""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+PKG = "multicomponent-t2-toolbox_amd"
+
+M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+W0, W1 = np.uint32(0x9E3779B9), np.uint32(0xBB67AE85)
+
+
+def philox4x32_10(ctr, key):
+    """ctr: 4 uint32 arrays (broadcastable), key: 2 uint32 arrays -> the 4 output words (uint32 arrays)."""
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint32) for c in ctr)
+    k0, k1 = (np.asarray(k, dtype=np.uint32) for k in key)
+    with np.errstate(over="ignore"):
+        for r in range(10):
+            if r:
+                k0 = (k0 + W0).astype(np.uint32)
+                k1 = (k1 + W1).astype(np.uint32)
+            p0 = M0 * c0.astype(np.uint64)
+            p1 = M1 * c2.astype(np.uint64)
+            n0 = (p1 >> np.uint64(32)).astype(np.uint32) ^ c1 ^ k0
+            n2 = (p0 >> np.uint64(32)).astype(np.uint32) ^ c3 ^ k1
+            c0, c1, c2, c3 = n0, p1.astype(np.uint32), n2, p0.astype(np.uint32)
+    return c0, c1, c2, c3
+
+
+def replicates_np(center, sigma, vid, n_rep, seed):
+    """Definition 3 of met2_fit_bootstrap (include/met2_hip.h) in numpy: center [nv, n_te], sigma [nv], vid [nv] int64 -> [nv, n_rep, n_te]."""
+    center = np.asarray(center, dtype=np.float64)
+    nv, nte = center.shape
+    vid = np.asarray(vid, dtype=np.int64).view(np.uint64)
+    s = np.array([seed], dtype=np.int64).view(np.uint64)[0]
+    key = (np.uint32(s & np.uint64(0xFFFFFFFF)), np.uint32(s >> np.uint64(32)))
+    e = np.arange(nte, dtype=np.uint32)[None, None, :]
+    b = np.arange(n_rep, dtype=np.uint32)[None, :, None]
+    lo = (vid & np.uint64(0xFFFFFFFF)).astype(np.uint32)[:, None, None]
+    hi = (vid >> np.uint64(32)).astype(np.uint32)[:, None, None]
+    shape = (nv, n_rep, nte)
+    x0, x1, x2, x3 = philox4x32_10([np.broadcast_to(e, shape), np.broadcast_to(b, shape), np.broadcast_to(lo, shape), np.broadcast_to(hi, shape)], key)
+    u1 = ((x0 >> 5).astype(np.float64) * 2.0 ** 26 + (x1 >> 6).astype(np.float64) + 1.0) * 2.0 ** -53
+    u2 = ((x2 >> 5).astype(np.float64) * 2.0 ** 26 + (x3 >> 6).astype(np.float64)) * 2.0 ** -53
+    r = np.sqrt(-2.0 * np.log(u1))
+    z1, z2 = r * np.cos((2.0 * np.pi) * u2), r * np.sin((2.0 * np.pi) * u2)
+    sg = np.asarray(sigma, dtype=np.float64)[:, None, None]
+    return np.sqrt((center[:, None, :] + sg * z1) ** 2 + (sg * z2) ** 2)
+
+
+def _words(*xs):
+    return ["%08x" % int(x) for x in xs]
+
+
+def test_philox_known_answers():
+    # Random123's kat_vectors for philox4x32_10
+    assert _words(*philox4x32_10([0, 0, 0, 0], [0, 0])) == ["6627e8d5", "e169c58d", "bc57ac4c", "9b00dbd8"]
+    f = 0xFFFFFFFF
+    assert _words(*philox4x32_10([f, f, f, f], [f, f])) == ["408f276d", "41c83b0e", "a20bc7c6", "6d5451fd"]
+    assert _words(*philox4x32_10([0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344], [0xA4093822, 0x299F31D0])) == \
+        ["d16cfe09", "94fdcceb", "5001e420", "24126ea1"]
+
+
+def test_replicates_np_uniforms_and_zero_sigma():
+    # u1 in (0, 1] keeps log finite; sigma = 0 gives the centre back exactly
+    c = np.abs(np.random.default_rng(1).normal(size=(5, 8))) * 100.0
+    r = replicates_np(c, np.zeros(5), np.arange(5) + 2 ** 40, 7, -1)
+    assert np.array_equal(r, np.broadcast_to(c[:, None, :], r.shape))
+    r = replicates_np(c, np.full(5, 3.0), np.arange(5), 7, 0)
+    assert np.all(np.isfinite(r)) and np.all(r >= 0.0)
+    assert not np.array_equal(r[:, 0], r[:, 1])
+
+
+def _lib():
+    b = importlib.import_module(PKG + "._build")
+    b.build()
+    lib = importlib.import_module(PKG + "._lib")
+    return lib.lib()
+
+
+def _boot(L, plan=None, n_rep=16, nvox=4, vs=32, es=1, seed=0):
+    nul = C.c_void_p(0)
+    return L.met2_fit_bootstrap(plan, 2, nvox, nul, vs, es, nul, nul, nul, nul, n_rep, seed, *([nul] * 10))
+
+
+@pytest.mark.parametrize("kw,msg", [({"n_rep": 1}, "n_rep"), ({"n_rep": 1025}, "n_rep"), ({}, "NULL plan"), ({"nvox": -1}, "nvox"),
+                                    ({"vs": 0}, "stride"), ({"es": -32}, "stride")])
+def test_fit_bootstrap_argument_checks_need_no_gpu(kw, msg):
+    L = _lib()
+    assert _boot(L, **kw) == -1           # MET2_E_INVALID
+    assert msg in L.met2_last_error().decode()
+
+
+def test_bootstrap_replicates_argument_checks_need_no_gpu():
+    L = _lib()
+    nul = C.c_void_p(0)
+    for n_rep, nvox, msg in ((1, 4, "n_rep"), (1025, 4, "n_rep"), (8, -1, "nvox"), (8, 4, "NULL plan")):
+        assert L.met2_bootstrap_replicates(nul, nvox, nul, nul, nul, n_rep, 0, nul, nul) == -1
+        assert msg in L.met2_last_error().decode()
+
+
+def test_any_64bit_seed_passes_the_checks():
+    L = _lib()
+    for seed in (0, -1, 2 ** 63 - 1, -2 ** 63):
+        assert _boot(L, seed=seed) == -1 and "NULL plan" in L.met2_last_error().decode()
+
+
+def test_fit_bootstrap_rejects_malformed_calls_before_the_device():
+    plan_mod = importlib.import_module(PKG + ".plan")
+    p = plan_mod.Met2Plan.__new__(plan_mod.Met2Plan)          # shape only: every check below fails before the handle or a device is used
+    p.n_te, p.n_t2, p.n_fa, p._h, p.device = 32, 60, 1, C.c_void_p(0), torch.device("cuda", 0)
+    d = torch.zeros((4, 32), dtype=torch.float64)
+    with pytest.raises(ValueError, match="unknown reg_method"):
+        p.fit_bootstrap("X3", d)
+    with pytest.raises(ValueError, match="float64"):
+        p.fit_bootstrap("X2", d.to(torch.float32))
+    with pytest.raises(ValueError, match="n_te"):
+        p.fit_bootstrap("X2", torch.zeros((4, 31), dtype=torch.float64))
+    with pytest.raises(ValueError, match="n_te"):
+        p.fit_bootstrap("X2", torch.zeros((32,), dtype=torch.float64))
+    with pytest.raises(ValueError, match="n_rep"):
+        p.fit_bootstrap("X2", d, n_rep=1)
+    with pytest.raises(ValueError, match="n_rep"):
+        p.fit_bootstrap("X2", d, n_rep=1025)
+    with pytest.raises(ValueError, match="sigma"):
+        p.fit_bootstrap("X2", d, sigma=np.array([1.0, -1.0, 1.0, 1.0]))
+    with pytest.raises(ValueError, match="sigma"):
+        p.fit_bootstrap("X2", d, sigma=np.ones(3))
+    with pytest.raises(ValueError, match="voxel_id"):
+        p.fit_bootstrap("X2", d, voxel_id=np.arange(5))
+
+
+def test_boot_names_exported():
+    pkg = importlib.import_module(PKG)
+    assert pkg.BOOT_QUANTITIES == pkg.MAP_NAMES + ("reg",)
+    assert len(pkg.BOOT_STATS) == 5 and pkg.BOOT_STATS[:2] == ("mean", "std")
