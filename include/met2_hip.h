@@ -268,6 +268,48 @@ int met2_fit_bootstrap(met2_plan *plan, int32_t method, int64_t nvox, const doub
 int met2_bootstrap_replicates(met2_plan *plan, int64_t nvox, const double *center, const double *sigma, const int64_t *voxel_id,
                               int32_t n_rep, int64_t seed, double *out, void *stream);
 
+/* ---- Monte-Carlo accuracy study (scripts_synthetic_data_evaluation/Paper_Comparison/evaluate_all_methods_two_lobes_SNR*.py) -------
+ * met2_synth_two_lobe draws n two-lobe voxels by the reference's recipe (:156-190, :376-428).  Per voxel, from counter-based Philox4x32-10
+ * (philox.hpp) with key (lo32(seed), hi32(seed)) and counter (c0, stream, lo32(id), hi32(id)), id = voxel_offset + v:
+ *   stream 1, c0 = 0..3   eight 53-bit uniforms u = ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53 in [0, 1), taken in the order MWF, T2m, T2ie, FA |
+ *                         SNR, sigma_m, sigma_ie; each value lo + (hi - lo) u.  FA is continuous (not snapped to a dictionary grid)
+ *   pdf on linspace(1, 300, 1000): MWF N(T2m, sigma_m) + (1 - MWF) N(T2ie, sigma_ie), normalised to sum 1 (f_csf = 0)
+ *   signal_e = km (1 - exp(-TR/T1)) sum_j EPG_e(T2_j; FA, FA/2, te, T1) pdf_j
+ *   stream 2, c0 = e      Rician noise at sigma = signal_0 / SNR, Box-Muller as met2_bootstrap_replicates; none when snr_lo = +inf
+ * DEVICE outputs: data [n][n_te]; true_dist [n][n_t2] the pdf re-binned onto the plan's T2 grid by the midpoint rule of :404-426
+ * (normalised); truth [MET2_EVAL_NTRUTH][n] = MWF (sum of true_dist at T2 <= t2_myelin_cut), T2m, T2ie, km, FA, SNR (inf when noise-free),
+ * the drawn MWF, sigma_m, sigma_ie.  n_te <= 64, n_t2 <= 128.  Asynchronous on `stream`. */
+#define MET2_EVAL_NTRUTH 9
+typedef struct met2_synth_params {
+    int32_t struct_size;      /* sizeof(met2_synth_params)                                       */
+    int32_t reserved0;
+    double te, TR, T1;        /* echo spacing (ms), :186-189 10; TR :209 3000; T1 :181 1000     */
+    double mwf_lo, mwf_hi;    /* :156  0.05, 0.25                                                */
+    double t2m_lo, t2m_hi;    /* :158  15, 35                                                    */
+    double t2ie_lo, t2ie_hi;  /* :160  60, 90                                                    */
+    double fa_lo, fa_hi;      /* :162  90, 180 (degrees)                                         */
+    double snr_lo, snr_hi;    /* :164  50, 150; snr_lo = +inf: no noise (the SNR_Inf script)     */
+    double sm_lo, sm_hi;      /* :168  1, 3                                                      */
+    double sie_lo, sie_hi;    /* :170  6, 12                                                     */
+    double km;                /* :166  1000                                                      */
+} met2_synth_params;
+int met2_synth_two_lobe(met2_plan *plan, const met2_synth_params *params, int64_t n, int64_t seed, int64_t voxel_offset, double *data,
+                        double *true_dist, double *truth, void *stream);
+/* estimate_error_metrics (:59-74) per voxel from a fit's fsol [n][n_t2] (already multiplied by the first echo) and true_dist [n][n_t2]
+ * (DEVICE).  km = sum fsol, x = fsol / km; out [MET2_EVAL_NFIELD][n] = fM (x at T2 <= t2_myelin_cut), fIE (t2_myelin_cut < T2 <= t2_ie_cut),
+ * arithmetic-mean T2 of both (epsilon 1e-50), km, the number of scipy.signal.find_peaks(x, height = 1e-5 max x), mean |true_dist - x|,
+ * scipy.spatial.distance.jensenshannon(true_dist, x) and scipy.stats.wasserstein_distance(true_dist, x) (the bin values as samples).
+ * 3 <= n_t2 <= 128.  One wave per voxel; asynchronous on `stream`. */
+#define MET2_EVAL_NFIELD 9
+int met2_eval_voxel_metrics(met2_plan *plan, int64_t n, const double *fsol, const double *true_dist, double *out, void *stream);
+/* compute_multi_metrics (:77-123) of one method over n voxels, and the lambda statistics.  DEVICE: per_voxel [MET2_EVAL_NFIELD][n] (of
+ * met2_eval_voxel_metrics), truth [MET2_EVAL_NTRUTH][n] (of met2_synth_two_lobe), lam [n] or NULL (zeros), fie [n] or NULL: the fIE array
+ * GMARE's second term reads (NULL: per_voxel's own; the reference reads its NNLS array for every method, :107).  out [MET2_EVAL_NAGG] = MAE,
+ * MARE, RMSE, cRMSE, RMSRE, U95, MBE, R, GMARE, MAE-k, MAE-S, MJSD-S, MWD-S (the columns of table_errors.txt), mean and std (ddof 0) of
+ * lambda.  One workgroup in a fixed reduction order: the same inputs give the same bits.  Runs on the current device; asynchronous. */
+#define MET2_EVAL_NAGG 15
+int met2_eval_reduce(int64_t n, const double *per_voxel, const double *truth, const double *lam, const double *fie, double *out, void *stream);
+
 /* Test/diagnostic entry: `method` = 10 + MET2_X2 / MET2_GCV / MET2_BAYESREG passed to met2_fit
  * evaluates that method's lambda-selection objective (algorithms.py:226-233, :285-296,
  * bayesian_interpolation.py:107-126) on the plan's lambda grid (n <= n_t2 points) and stores the

@@ -21,6 +21,7 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "philox.hpp"
 #include "wave_ops.hpp"
 
 namespace met2 {
@@ -32,18 +33,6 @@ namespace {
 #define MET2_BOOT_MAX_REP 1024
 #define MET2_BOOT_QUANT 7          // MWF, IEWF, FWF, T2_M, T2_IE, TWC, reg
 #define MET2_BOOT_STATS 5          // mean, std (ddof 1), quantiles 0.025, 0.5, 0.975
-
-// Philox4x32-10 (Salmon et al., SC'11; the constants of Random123): 10 rounds, the key bumped by the Weyl constants between rounds
-__device__ __forceinline__ void philox4x32_10(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-    }
-}
 
 struct GenArgs {
     int64_t nv, v0;                 // voxels of this launch, global index of the first
@@ -74,9 +63,8 @@ __global__ __launch_bounds__(256) void bootstrap_gen_kernel(GenArgs A)
         if (live) {
             const uint64_t id = A.vid ? (uint64_t)A.vid[v] : (uint64_t)v;
             uint32_t c0 = (uint32_t)e, c1 = (uint32_t)b, c2 = (uint32_t)id, c3 = (uint32_t)(id >> 32);
-            philox4x32_10(c0, c1, c2, c3, A.k0, A.k1);
-            const double u1 = ((double)(c0 >> 5) * 67108864.0 + (double)(c1 >> 6) + 1.0) * 0x1p-53;
-            const double u2 = ((double)(c2 >> 5) * 67108864.0 + (double)(c3 >> 6)) * 0x1p-53;
+            met2::philox4x32_10(c0, c1, c2, c3, A.k0, A.k1);
+            const double u1 = met2::u01_oc(c0, c1), u2 = met2::u01_co(c2, c3);
             const double r = sqrt(-2.0 * log(u1)), t = 6.283185307179586 * u2;
             const double sg = A.sigma[v];
             const double re = A.center[v * A.nte + e] + sg * (r * cos(t)), im = sg * (r * sin(t));

@@ -1068,6 +1068,9 @@ namespace met2 { __attribute__((visibility("hidden"))) int plan_reserve(met2_pla
     return ensure_sort_bufs(p, nvox);
 } }
 
+// the plan's T2 grid (a device array of n_t2) for met2_eval.hip; NULL before one is set
+namespace met2 { __attribute__((visibility("hidden"))) const double *plan_t2_grid(met2_plan *p) { return p && p->have_t2 ? p->dT2 : nullptr; } }
+
 static SortBufs sort_bufs(met2_plan *p)
 {
     SortBufs sb;
