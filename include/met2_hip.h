@@ -219,7 +219,7 @@ int met2_plan_finish(met2_plan *plan, void *stream);
  *                     4 096, at most 262 144 and (unless the share itself is smaller) at least 65 536
  *   plan_ms [n_plans] out, may be NULL: wall-clock ms every plan's thread spent in the call
  * Blocking.  Every voxel is solved on its own, so the outputs are bit for bit those of one met2_fit over the whole list, whatever
- * n_plans, chunk and the devices.  Returns the first failing plan's code (an FA index outside the dictionary: MET2_E_INVALID) after
+ * n_plans, chunk and the devices (a voxel queued for the spill-over kernel gets the same bits in a short queue and a long one).  Returns the first failing plan's code (an FA index outside the dictionary: MET2_E_INVALID) after
  * ALL plans' streams have drained -- nothing writes to the caller's arrays after the return.  The block buffers (two slots of
  * chunk x ~8 (2 n_te + n_t2 + 10) bytes on the device, the same pinned when a pageable array takes part), three streams and six
  * events stay with each plan until met2_plan_destroy (and then wait for the next plan on that device: met2_host_trim). */
@@ -415,7 +415,8 @@ int met2_plan_last_kernel_ms(met2_plan *plan, double *ms);
  * kernel launched behind it, with the same geometry, solves the queued voxels with the factor's columns beyond the capacity in a
  * per-wave slot in device memory (allocated by the first such fit on the plan: 18 MB at n_t2 = 60, 77 MB at 120).  A plan whose
  * options name non-default lambda-search intervals runs every voxel through the spill-over kernel.
- * met2_plan_last_spill_count: how many voxels of the most recent finished fit were queued (for reports and tests).
+ * met2_plan_last_spill_count: how many voxels of the most recent finished fit were queued (for reports and tests); under non-default
+ * lambda-search intervals every fitted voxel goes through the spill-over kernel, and the count is theirs.
  * met2_plan_last_second_pass_ms: the spill-over kernel's duration in the most recent fit (0 if the fit ran none);
  * met2_plan_last_kernel_ms is then the fit kernel's alone, about 0 under non-default lambda-search intervals. */
 int met2_plan_last_spill_count(met2_plan *plan, int64_t *count);

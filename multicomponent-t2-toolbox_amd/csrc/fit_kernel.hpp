@@ -446,7 +446,10 @@ __host__ __device__ constexpr int method_max_waves(int method, int nb = 1)
 // changes; every voxel's first evaluation starts from that passive set and iterate: one refactorisation and a few exchanges.
 // Any x >= 0 is a feasible start for Lawson-Hanson and the regularised problem is strictly convex, so the solution is the
 // cold-start one up to rounding, and because the seed depends on the plan only, a voxel's result stays independent of its
-// neighbours and of the order of the voxel list.  T2SPARC's single solve at its fixed lambda is seeded the same way.  The lambda = 0 solves keep the cold path: x(0) need not be unique and NNLS,
+// neighbours and of the order of the voxel list.  Which voxels start from it depends on the plan and the flip angle alone: a seed whose set
+// has more bins than the plan's LDS capacity (fast_kmax: 71 at nT2 = 120, where the seeds of X2 under the identity penalty have 74-85 bins) is not used, by the fit kernel
+// and by the spill-over kernel alike -- the latter carves capacities up to nT2 for a short queue, and gating on those would warm-start a
+// queued voxel in a short queue and cold-start it in a long one.  T2SPARC's single solve at its fixed lambda is seeded the same way.  The lambda = 0 solves keep the cold path: x(0) need not be unique and NNLS,
 // the L-curve and BayesReg's degrees of freedom use x(0) itself.
 struct SeedArgs {
     int n, m, nfa;
@@ -892,7 +895,7 @@ __device__ __forceinline__ void fit_shared_fa(const FitArgs &A, WaveShared &S, i
 // voxel -- every wave faulted on its second one (round 5: 3 020 queued voxels on 2 048 waves; 1 549 ran clean).  The arguments arrive in
 // vector registers and the plan's arguments through a private copy: everything wave-uniform is made scalar again (readfirstlane).
 template <int METHOD, int NB>
-__device__ __attribute__((noinline)) void fit_voxel_spill(const FitArgs *Ap, big_lds_dp sRl, int64_t v, int fa, int wslot, int qslot)
+__device__ __attribute__((noinline)) void fit_voxel_spill(const FitArgs *Ap, big_lds_dp sRl, int64_t v, int fa, int wslot, int qslot, int seed_cap)
 {
     const int lane = big_lane();
     double *sR = (double *)sRl;
@@ -904,7 +907,7 @@ __device__ __attribute__((noinline)) void fit_voxel_spill(const FitArgs *Ap, big
 #pragma unroll
         for (int i = 0; i < (int)(sizeof(FitArgs) / 4); ++i) dst[i] = big_rfl(src[i]);
     }
-    v = (int64_t)big_rfl((u64)v); fa = big_rfl(fa); wslot = big_rfl(wslot); qslot = big_rfl(qslot);
+    v = (int64_t)big_rfl((u64)v); fa = big_rfl(fa); wslot = big_rfl(wslot); qslot = big_rfl(qslot); seed_cap = big_rfl(seed_cap);
     WaveShared S;
     fit_shared(A, S, sR, wslot);
     fit_shared_fa<METHOD>(A, S, fa);
@@ -913,7 +916,7 @@ __device__ __attribute__((noinline)) void fit_voxel_spill(const FitArgs *Ap, big
     MetricLanes<NB> ml;
     metric_lanes<NB>(ml, A.t2s, A.n, A.cut_m, A.cut_ie, lane);
     const int seed_k = (MET2_SEED && A.seed) ? ((const SeedRec *)A.seed)[fa].k : 0;
-    const bool have_seed = seed_k > 0 && seed_k <= A.kmax;
+    const bool have_seed = seed_k > 0 && seed_k <= seed_cap;        // the first kernel's rule at the plan's capacity, not at the carved A.kmax
     (void)fit_voxel<METHOD, NB, true>(A, S, bd, ml, v, fa, seed_k, have_seed, lane, wslot, qslot);
 }
 
@@ -989,6 +992,7 @@ __global__ __launch_bounds__(64 * method_max_waves(METHOD, NB)) void fit_kernel(
     const int ntail = A.all_queued ? A.sb.bucket_start[A.nfa] : A.sb.err[1];      // (all_queued: every fitted voxel, in the sorted list's order)
     const int *queue = A.all_queued ? A.sb.perm : A.sb.ovf;
     FitArgs Ac = A;                                       // (a private copy for the not-inlined voxel routine)
+    if (A.all_queued && blockIdx.x == 0 && threadIdx.x == 0) A.sb.err[1] = ntail;       // the spill count the host reads back: every fitted voxel
     // The workgroup's LDS is carved for as few waves as give every queued voxel a wave of its own (this kernel's duration is the latency of its
     // slowest voxel when the queue is short, its throughput when it is long): w2 waves, each with the largest factor capacity its share holds --
     // at nT2 = 120: 8 waves at capacity 71 (the first kernel's), 7 / 75, 6 / 81, 5 / 89, 4 / 100, 3 / 116, 2 and 1 at 120 (no spill-over leg runs);
@@ -1010,7 +1014,7 @@ __global__ __launch_bounds__(64 * method_max_waves(METHOD, NB)) void fit_kernel(
         i = __builtin_amdgcn_readfirstlane(i);
         if (i >= ntail) break;
         const int64_t v = queue[i];
-        fit_voxel_spill<METHOD, NB>(&Ac, (big_lds_dp)sR, v, A.sb.key[v], wslot, A.all_queued ? -1 : i);
+        fit_voxel_spill<METHOD, NB>(&Ac, (big_lds_dp)sR, v, A.sb.key[v], wslot, A.all_queued ? -1 : i, kmax);
     }
     }
     }

@@ -360,6 +360,9 @@ __device__ __forceinline__ bool refactor_rowwise_big(const WaveShared &S, const 
             for (int b = 0; b < NB; ++b) { a[b] = gatherN<NB>(t0, st.ord[b]); a2[b] = 0.0; }
         }
         const double *ci = big_col(S, i);
+        // the sums of refactor_rowwise: there rows go in pairs, each row's sum one chain in row order; only the last row of an odd k
+        // alternates between two chains (even / odd rows of every step of four) that are added at the end
+        const bool two = (k & 1) && i == k - 1;
         int j = 0;
 #pragma clang loop unroll(disable)
         for (; j + 4 <= i; j += 4) {
@@ -369,8 +372,13 @@ __device__ __forceinline__ bool refactor_rowwise_big(const WaveShared &S, const 
                 const int pl = lane + 64 * b;
                 double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
                 if (pl >= i && pl < k) { q0 = cpl[b][j]; q1 = cpl[b][j + 1]; q2 = cpl[b][j + 2]; q3 = cpl[b][j + 3]; }
-                a[b] = fma(-s0, q0, a[b]); a2[b] = fma(-s1, q1, a2[b]);
-                a[b] = fma(-s2, q2, a[b]); a2[b] = fma(-s3, q3, a2[b]);
+                if (two) {
+                    a[b] = fma(-s0, q0, a[b]); a2[b] = fma(-s1, q1, a2[b]);
+                    a[b] = fma(-s2, q2, a[b]); a2[b] = fma(-s3, q3, a2[b]);
+                } else {
+                    a[b] = fma(-s0, q0, a[b]); a[b] = fma(-s1, q1, a[b]);
+                    a[b] = fma(-s2, q2, a[b]); a[b] = fma(-s3, q3, a[b]);
+                }
             }
         }
         for (; j < i; ++j) {
@@ -378,8 +386,10 @@ __device__ __forceinline__ bool refactor_rowwise_big(const WaveShared &S, const 
 #pragma unroll
             for (int b = 0; b < NB; ++b) { const int pl = lane + 64 * b; const double q0 = (pl >= i && pl < k) ? cpl[b][j] : 0.0; a[b] = fma(-s0, q0, a[b]); }
         }
+        if (two) {
 #pragma unroll
-        for (int b = 0; b < NB; ++b) a[b] += a2[b];
+            for (int b = 0; b < NB; ++b) a[b] += a2[b];
+        }
         const double d = bcastN<NB>(a, i);
         const double rinv = rsqrt_nr(d);
         const double yi = bcastN<NB>(g, i) * rinv;

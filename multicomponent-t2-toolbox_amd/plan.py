@@ -399,7 +399,8 @@ class Met2Plan:
         return ms.value
 
     def last_spill_count(self):
-        """Voxels of the most recent fit whose passive set outgrew the wave's LDS region and went on in the spill-over slot."""
+        """Voxels of the most recent fit whose passive set outgrew the wave's LDS region and went on in the spill-over slot (under non-default
+        lambda-search intervals: every fitted voxel, all of them solved by the spill-over kernel)."""
         n = C.c_int64(0)
         check(lib().met2_plan_last_spill_count(self._h, C.byref(n)))
         return n.value
