@@ -422,6 +422,10 @@ int met2_plan_last_kernel_ms(met2_plan *plan, double *ms);
 int met2_plan_last_spill_count(met2_plan *plan, int64_t *count);
 int met2_plan_last_second_pass_ms(met2_plan *plan, double *ms);
 
+/* For tests: the number of warm re-factorisations that took the packed four-rows-per-step leg (one bin per lane, 4 <= k <= 32) in the fits
+ * on the plan's device that ran with MET2_REFAC_COUNT set in the environment, since the last reset.  Waits for the device. */
+int met2_refac_packed_calls(met2_plan *plan, uint64_t *calls, int32_t reset);
+
 /* Launch geometry of the solver kernel (for reports): workgroups, threads per workgroup,
  * dynamic LDS bytes per workgroup. */
 int met2_plan_launch_info(met2_plan *plan, int32_t method, int32_t *grid, int32_t *block, int32_t *lds_bytes);

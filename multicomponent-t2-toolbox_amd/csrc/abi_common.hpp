@@ -18,6 +18,8 @@ static inline int fail(int code, const std::string &msg) { return met2::abi_fail
 //   MET2_FA_NOPRUNE   the brute-force FA walk visits every flip angle, no lower bounds (test_round4.py)
 //   MET2_LC_RESTART   queued L-curve voxels start their sweep over in the spill-over kernel (test_round5.py)
 //   MET2_HOST_BLOCKS  met2_fit_host gives its plans whole blocks, not runs of 4 096 voxels (test_round5.py)
+//   MET2_REFAC_PAIR   the warm re-factorisation keeps to its pair loop, no packed leg (test_gpu_refactor_packed.py)
+//   MET2_REFAC_COUNT  the fit kernels count the re-factorisations that took the packed leg (met2_refac_packed_calls; slow: one atomic per call)
 //   MET2_DEBUG        synchronous launches with progress lines on stderr
 static inline bool test_switch(const char *name) { return getenv(name) != nullptr; }
 

@@ -978,6 +978,9 @@ __global__ __launch_bounds__(256) void roi_finish_kernel(RoiArgs A)
 // ------------------------------------------------------------------------------------------
 // plan
 // ------------------------------------------------------------------------------------------
+// re-factorisations that took the packed leg of refactor_rowwise, counted by fits under the test switch MET2_REFAC_COUNT (met2_refac_packed_calls)
+__device__ unsigned long long g_refac_packed_calls;
+
 struct met2_plan {
     int n_te, n_t2, n_fa;
     met2_options opt;
@@ -1925,6 +1928,9 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
     A.Dfa = p->dD; A.Bfa = p->dB; A.Dtfa = p->dDt; A.Aq = p->dAq; A.kband = p->dKband; A.lband = p->dLband; A.Kd = p->dKd; A.lam_grid = p->dLam; A.t2s = p->dT2;
     A.data = data; A.vs = voxel_stride; A.es = echo_stride; A.sb = sb; A.fsol = fsol; A.sig = sig; A.reg = reg; A.lam = lam; A.maps = maps; A.status = status; A.nvox = nvox;
 
+    A.refac_pair = test_switch("MET2_REFAC_PAIR") ? 1 : 0;
+    A.refac_count = nullptr;
+    if (test_switch("MET2_REFAC_COUNT")) HIPCHK(hipGetSymbolAddress((void **)&A.refac_count, HIP_SYMBOL(g_refac_packed_calls)));
     A.seed = nullptr;
     if (!test_switch("MET2_NO_SEED") && !objgrid && p->have_pen && p->seeds_valid && p->seeds_ok && p->seeds_key[0] == p->opt.t2sparc_lambda &&
         (method == MET2_X2 || method == MET2_GCV || method == MET2_BAYESREG || method == MET2_T2SPARC)) {
@@ -2218,6 +2224,18 @@ int met2_plan_gcv_form(met2_plan *p, int32_t *low_rank, double *residual)
     if (!p->have_dict) return fail(MET2_E_STATE, "no dictionary in the plan");
     if (low_rank) *low_rank = kernel_method(p, MET2_GCV) == MET2_GCV_LR ? 1 : 0;
     if (residual) *residual = p->gcv_res;
+    return MET2_OK;
+}
+
+int met2_refac_packed_calls(met2_plan *p, uint64_t *calls, int32_t reset)
+{
+    if (!p) return fail(MET2_E_INVALID, "NULL plan");
+    USE_DEVICE(p->opt.device);
+    HIPCHK(hipDeviceSynchronize());
+    unsigned long long v = 0;
+    HIPCHK(hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_refac_packed_calls), sizeof(v)));
+    if (calls) *calls = (uint64_t)v;
+    if (reset) { v = 0; HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_refac_packed_calls), &v, sizeof(v))); }
     return MET2_OK;
 }
 

@@ -79,6 +79,8 @@ struct WaveShared {
                         // 19 MB of dictionaries at 48 x 120 missed L2 1.7x more often through the buffer path: 57 -> 66 ms per 131 k voxels)
     double *Rg = nullptr; // this wave's spill-over slot in global memory: columns c >= kmax of the factor, entry (r, c) at col_base(c) - gbase + r
     int gbase = 0;        // col_base(kmax)   (nnls_big.hpp; used by the BIG = true instances of the routines below only)
+    bool refac_pair = false;                     // the packed leg of refactor_rowwise is not taken (the test switch MET2_REFAC_PAIR)
+    unsigned long long *refac_count = nullptr;   // calls of refactor_rowwise that took the packed leg are counted here (MET2_REFAC_COUNT), or NULL
 };
 
 // L as 5 diagonals per owned bin: lb[b][d] = L[j][j+d-2].  (K = L^T L is not held in registers: its rows come from the
@@ -259,6 +261,12 @@ __device__ __forceinline__ double ld_row(const double *array_base, int row_off_e
 __device__ __forceinline__ double ld_row_sel(bool buffer, const double *array_base, int row_off_elems, unsigned lane_elem)
 {
     return buffer ? ld_row(array_base, row_off_elems, 8u * lane_elem) : array_base[row_off_elems + (int)lane_elem];
+}
+
+// element `elem` of the array, the whole index per lane (the packed leg of refactor_rowwise, whose two half waves load different rows)
+__device__ __forceinline__ double ld_elem_sel(bool buffer, const double *array_base, unsigned elem)
+{
+    return buffer ? ld_row(array_base, 0, 8u * elem) : array_base[elem];
 }
 
 // 1/sqrt(d) to fp64 accuracy from v_rsq_f64 (relative error 5.2e-8, measured: scripts/probes/rsq_precision.hip) and ONE
@@ -823,9 +831,20 @@ __device__ __forceinline__ void nnls_reset(NnlsState<NB> &st)
 // y comes out of the same sweep (one elimination step per finished row).
 // Returns false -- R is then unusable, ord/pos/P/k/x are untouched -- when a pivot falls under the independence
 // threshold of try_append; the caller re-appends column by column, which drops such columns.
-template <int NB, int NP = NB>
+//
+// PACK (one bin per lane, kernels built with MET2_REFAC_PACKED): while k <= 32 two thirds of the lanes own no column and execute the
+// fp64 FMAs of the sums for nothing.  The packed leg gives the upper half wave two MORE ROWS of the same factor: per step of four rows
+// lane l holds column l & 31 of rows i, i + 1 (lanes 0-31: today's pair) or of rows i + 2, i + 3 (lanes 32-63), so the terms j < i of
+// all four sums cost two FMAs per j instead of four.  The upper half then takes the terms j = i, i + 1 from the two rows the lower half
+// has just stored, and finishes its pair the same way; y's elimination stays in the lower half (lane = position), which reads the upper
+// half's two rows back from their columns.  The summation rule: every row's sum is G[i][c], then the terms j = 0, 1, ... in ascending order,
+// one FMA each, on the stored doubles -- exactly the pair loop's sums, so the factor, 1/diag and y are the same BITS on either leg.  The rows
+// of G arrive in position order (the lane's own pivot bin as the column of the load), not by bin and through gatherN.  Fewer than four rows
+// left: the pair loop and the odd tail below, unchanged.
+template <int NB, int NP = NB, bool PACK = false>
 __device__ __forceinline__ bool refactor_rowwise(const WaveShared &S, const Band<NB> &bd, NnlsState<NB> &st, double lam, int lane)
 {
+    static_assert(!PACK || (NB == 1 && NP == 1), "the packed leg is written for one bin per lane");
     const int k = st.k, n = S.n;
     int cbl[NB], cbc[NB];
     unsigned jc[NB];
@@ -877,11 +896,92 @@ __device__ __forceinline__ bool refactor_rowwise(const WaveShared &S, const Band
 #pragma unroll
         for (int b = 0; b < NP; ++b) gdp[b] = gatherN<NB>(gdb, st.ord[b]);
     }
-    fetch(0, gb0, gk0);
-    fetch(1, gb1, gk1);
     int cbi = 0;                                                        // col_base(i)
     bool bad = false;
     int i = 0;
+    bool packed = false;
+    if constexpr (PACK) {
+    packed = k >= 4 && k <= 32 && !S.refac_pair;                        // (wave-uniform)
+    if (packed) {
+        if (S.refac_count && lane == 0) atomicAdd(S.refac_count, 1ull);
+        const int lo_ = lane_opaque(lane), hi2 = (lo_ >> 5) << 1, cp = lo_ & 31;               // the lane's rows of a block start at i + hi2, its column is cp
+        const int cbq = col_base(min(cp, k - 1));                       // (an existing column, as cbc)
+        // G's entries (ord_p, ord_cp) for the lane's two rows p of the block that starts at row p0, as B and K
+        auto fetch_packed = [&](int p0) {
+            const unsigned oc = (unsigned)gather_i(st.ord[0], min(lane_opaque(lane) & 31, k - 1));      // the pivot bin of the lane's column
+            const unsigned ta = (unsigned)gather_i(st.ord[0], min(p0 + hi2, k - 1)), tb = (unsigned)gather_i(st.ord[0], min(p0 + hi2 + 1, k - 1));
+            gb0[0] = ld_elem_sel(S.buffer_rows, S.B, ta * (unsigned)S.bstride + oc);
+            gk0[0] = ld_elem_sel(S.buffer_rows, S.K, ta * (unsigned)n + oc);
+            gb1[0] = ld_elem_sel(S.buffer_rows, S.B, tb * (unsigned)S.bstride + oc);
+            gk1[0] = ld_elem_sel(S.buffer_rows, S.K, tb * (unsigned)n + oc);
+        };
+        fetch_packed(0);
+        for (; i + 3 < k; i += 4) {                                     // (i is a multiple of four: the sums over j < i are whole quads)
+            double a[NB], c[NB];
+            a[0] = fma(lam, gk0[0], gb0[0]); c[0] = fma(lam, gk1[0], gb1[0]);
+            const int ih = i + hi2;
+            const double *ci = S.R + col_base(ih), *cj = ci + col_len(ih), *cq = S.R + cbq;     // columns of the lane's two rows, and its own
+#pragma clang loop unroll(disable)
+            for (int j = 0; j < i; j += 2) {
+                double s0, s1, u0, u1, q0, q1;
+                lds_pair(ci + j, s0, s1);
+                lds_pair(cj + j, u0, u1);
+                lds_pair(cq + j, q0, q1);
+                a[0] = fma(-s0, q0, a[0]); c[0] = fma(-u0, q0, c[0]);
+                a[0] = fma(-s1, q1, a[0]); c[0] = fma(-u1, q1, c[0]);
+            }
+            // the next block's (or the pair loop's) entries of G are fetched HERE, behind the long sums: eight registers less across them
+            if (i + 7 < k) fetch_packed(i + 4);
+            else { fetch(i + 4, gb0, gk0); fetch(i + 5, gb1, gk1); }    // what the pair loop and the odd tail expect: by bin
+            // (both halves execute both finishing blocks: a half-wave branch would cost two EXEC switches per block and save nothing -- a vector
+            //  instruction issues in the same cycles for 32 lanes as for 64)
+            {   // rows i, i + 1: the lower half, as in the pair loop (what the upper half computes here is dropped: k <= 32 keeps it from storing)
+                double r[NB], r1[NB];
+                finish(i, a, r);
+                const double sr = bcast(r[0], i + 1);
+                double cl[NB];
+                cl[0] = fma(-sr, r[0], c[0]);                             // (c itself stays: in the upper half it is row i + 3's sum)
+                finish(i + 1, cl, r1);
+            }
+            __builtin_amdgcn_wave_barrier();
+            {   // rows i + 2, i + 3: the terms j = i, i + 1 on the entries just stored (the lower half's sums are finished: its results here are dropped)
+                double s0, s1, u0, u1, q0, q1;
+                lds_pair(ci + i, s0, s1);
+                lds_pair(cj + i, u0, u1);
+                lds_pair(cq + i, q0, q1);
+                a[0] = fma(-s0, q0, a[0]); c[0] = fma(-u0, q0, c[0]);
+                a[0] = fma(-s1, q1, a[0]); c[0] = fma(-u1, q1, c[0]);
+            }
+            const int iu = i + 2;
+            double y2, y3;
+            {   // finish them in the upper half: finish() with the diagonal in lane 32 + row; y's two steps wait for the read-back below
+                const double rinv2 = rsqrt_nr(bcast(a[0], 32 + iu));
+                y2 = bcast(g[0], iu) * rinv2;
+                const double r2 = a[0] * rinv2;
+                if (lane >= 32 + iu && lane < 32 + k) S.R[cbq + iu] = r2;
+                const double sr = bcast(r2, 32 + iu + 1);                     // R[i+2][i+3]
+                c[0] = fma(-sr, r2, c[0]);
+                const double rinv3 = rsqrt_nr(bcast(c[0], 32 + iu + 1));
+                y3 = fma(-sr, y2, bcast(g[0], iu + 1)) * rinv3;          // g[i+3] after row i + 2's step, as the lower lane i + 3 computes it below
+                const double r3 = c[0] * rinv3;
+                if (lane >= 32 + iu + 1 && lane < 32 + k) S.R[cbq + iu + 1] = r3;
+            }
+            __builtin_amdgcn_wave_barrier();
+            {   // y's elimination steps of rows i + 2, i + 3, in row order, lane = position: the two rows from the lane's own column
+                double e2, e3;
+                lds_pair(cq + iu, e2, e3);
+                g[0] = (lane > iu) ? fma(-e2, y2, g[0]) : g[0];
+                g[0] = (lane > iu + 1) ? fma(-e3, y3, g[0]) : g[0];
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        cbi = col_base(i);
+    }
+    }
+    if (!packed) {
+        fetch(0, gb0, gk0);
+        fetch(1, gb1, gk1);
+    }
     // two rows per step: rows i and i + 1 share the reads of the rows above them, and row i + 1 takes row i's
     // contribution from registers, so the pair costs one LDS round trip instead of two
     for (; i + 1 < k; i += 2) {
@@ -1215,6 +1315,12 @@ __device__ __forceinline__ bool refactor_blocked(const WaveShared &S, const Band
 #ifndef MET2_ONE_SLOT_REFACTOR
 #define MET2_ONE_SLOT_REFACTOR 1    // 1: with k <= 64 at two bins per lane the warm re-factorisation is the row-by-row form on one slot (0: the blocked MFMA form)
 #endif
+#if !defined(MET2_REFAC_PACKED) && !defined(MET2_SPLIT_TU)
+#define MET2_REFAC_PACKED 1                 // development builds (one translation unit, -DMET2_CYCSTATS, -DMET2_LOOPSTATS ...): EVERY one-bin-per-lane kernel takes the leg, so
+#endif                                      // that the instruments see the shipped X2 / L-curve / T2SPARC path (GCV and BayesReg differ from the shipped build there)
+#ifndef MET2_REFAC_PACKED
+#define MET2_REFAC_PACKED 0                 // 1: the kernels of this translation unit take the packed leg of refactor_rowwise (one bin per lane, 4 <= k <= 32);
+#endif                                      //    set by the translation units whose kernels have the registers for it (met2_fit_x2_nb1.hip, met2_fit_nnls_lcurve.hip)
 #ifndef MET2_REFACTOR_BLOCKED_FROM
 #define MET2_REFACTOR_BLOCKED_FROM 2        // bins per lane from which the blocked form is used
 #endif
@@ -1224,8 +1330,9 @@ __device__ __forceinline__ bool refactor(const WaveShared &S, const Band<NB> &bd
     if constexpr (BIG) if (st.k > S.kmax) return refactor_big<NB>(S, bd, st, lam, lane);   // beyond the LDS capacity: columns >= kmax in the wave's global slot
     if (NB == 2 && ONE && MET2_ONE_SLOT && MET2_ONE_SLOT_REFACTOR && st.k <= 64) return refactor_rowwise<NB, 1>(S, bd, st, lam, lane);   // k <= 64: one position slot, row by row
     if (NB >= MET2_REFACTOR_BLOCKED_FROM) return refactor_blocked<NB>(S, bd, st, lam, lane);
-    if (MET2_DOUBLE == 1) { (void)refactor_rowwise<NB>(S, bd, st, lam, lane); __builtin_amdgcn_wave_barrier(); }
-    return refactor_rowwise<NB>(S, bd, st, lam, lane);
+    constexpr bool PACK = MET2_REFAC_PACKED && NB == 1 && !BIG;
+    if (MET2_DOUBLE == 1) { (void)refactor_rowwise<NB, NB, PACK>(S, bd, st, lam, lane); __builtin_amdgcn_wave_barrier(); }
+    return refactor_rowwise<NB, NB, PACK>(S, bd, st, lam, lane);
 }
 
 // cold-start solve; on return st.x is the solution
