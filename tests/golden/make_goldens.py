@@ -679,9 +679,41 @@ def gen_x2_failset(path):
     print("wrote golden_x2_failset.npz (%d voxels)" % data.shape[0])
 
 
+EPG_EDGE_CASES = [
+    # (n_te, n_t2, tau, TR, alpha_values in degrees): the corners of what met2_plan_create accepts (2 <= n_te <= 63, 2 <= n_t2 <= 128),
+    # tau and TR away from 10 / 3000, and angles outside the driver's 90...180 (0: no signal at all; > 180; just below 180)
+    (63, 128, 10.0, 3000.0, [90.0, 123.4, 180.0]),
+    (2, 3, 7.3, 1500.0, [30.0, 60.0, 180.0]),
+    (47, 65, 5.0, 800.0, [100.0, 179.999, 180.0, 200.0]),
+    (32, 60, 10.0, 3000.0, [0.0, 1e-3, 45.0]),
+    (63, 7, 12.5, 3000.0, [180.0]),
+    (31, 2, 9.0, 2500.0, [135.0, 180.0]),
+    (33, 64, 10.0, 1000.0, [150.0]),
+]
+
+
+def gen_epg_edges():
+    """Inputs and outputs of the reference's create_Dic_3D (epg/epg.py:155-162) at EPG_EDGE_CASES.  Every case has T2s log-spaced over
+    0.5 ... 2000 ms (T2 << tau at the short end: entries down to 1e-280) and a different T1 per bin (300 ... 4000 ms, linear)."""
+    from epg.epg import create_Dic_3D
+    out = {"ncases": len(EPG_EDGE_CASES)}
+    for i, (nte, npc, tau, TR, alphas) in enumerate(EPG_EDGE_CASES):
+        T2s = np.logspace(math.log10(0.5), math.log10(2000.0), num=npc, endpoint=True, base=10.0)
+        T1s = np.linspace(300.0, 4000.0, npc)
+        alphas = np.array(alphas, dtype=np.float64)
+        Dic = create_Dic_3D(npc, T2s, T1s, nte, tau, alphas, TR)
+        assert Dic.shape == (nte, npc, alphas.shape[0]) and np.isfinite(Dic).all()
+        p = "c%d_" % i
+        out.update({p + "T2s": T2s, p + "T1s": T1s, p + "tau": tau, p + "TR": TR, p + "alpha_values": alphas, p + "Dic": Dic})
+    np.savez_compressed(os.path.join(HERE, "golden_epg_edges.npz"), **out)
+    print("wrote golden_epg_edges.npz (%d cases)" % len(EPG_EDGE_CASES))
+
+
 def main():
     install_shims()
-    which = sys.argv[1:] or ["S1", "S2", "motor", "nesma", "smooth", "roi"]
+    which = sys.argv[1:] or ["S1", "S2", "motor", "nesma", "smooth", "roi", "epg_edges"]
+    if "epg_edges" in which:     # a file of its own: the other fixtures are not touched when only this one is asked for
+        gen_epg_edges()
     if "S1" in which:
         gen_shape("S1", 32, 60, nvox=32, nvox_slow=32, seed=20260101, with_fa_full=True)
     if "S2" in which:

@@ -360,6 +360,24 @@ def test_gaussian_smooth_and_default_pipeline_golden(pkg, tmp_path):
         motor.gaussian_smooth(np.zeros((2, 2, 2, 2)), sigma=9.0)        # radius 36 > 32
 
 
+@pytest.mark.parametrize("sigma,radius", [(0.5, 2), (1.0, 4), (3.3, 13), (8.0, 32)])
+def test_gaussian_smooth_other_radii(pkg, sigma, radius):
+    # the bit identity with scipy.ndimage.gaussian_filter at radii other than the driver's 8, up to the entry's cap of 32, on axes far
+    # shorter than the radius ('reflect' folds several times: length 1, 2, 3, 5), just longer than it (33) and long (70); 1 and 63 echoes
+    import torch
+    import scipy.ndimage as filt
+    from oracle import oracle
+    motor = importlib.import_module(PKG + ".motor")
+    assert oracle.gaussian_kernel1d(sigma)[0] == radius
+    rng = np.random.default_rng(int(sigma * 10))
+    for shp in [(1, 2, 3, 1), (5, 1, 2, 63), (3, 5, 33, 1), (33, 3, 5, 63), (2, 70, 1, 1), (70, 5, 3, 63), (5, 33, 70, 1)]:
+        d = rng.standard_normal(shp)
+        ref = np.stack([filt.gaussian_filter(d[..., c], sigma, 0) for c in range(shp[-1])], axis=-1)
+        got = motor.gaussian_smooth(torch.as_tensor(d, device="cuda"), sigma)
+        assert np.array_equal(got.cpu().numpy(), ref), (sigma, shp)
+        assert np.array_equal(motor.gaussian_smooth(d, sigma), ref), (sigma, shp)            # numpy in, numpy out
+
+
 def test_roi_mode_x2(pkg):
     # ROI-mode fits (motor_recon_met2_real_data_ROI.py:405-443): mean signal, mean kernel, X2 with factor 1.01
     from oracle import oracle
