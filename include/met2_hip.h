@@ -249,7 +249,7 @@ int met2_host_trim(void);
  *                 r = sqrt(-2 log u1), z1 = r cos(2 pi u2), z2 = r sin(2 pi u2).  A voxel's replicates depend on (seed, id_v, b, e) alone: not
  *                 on chunking, call splitting, voxel order or device.  Any 64-bit seed (its bits are taken as they are)
  *   fits          each replicate as met2_fit fits its echoes, at the voxel's FA index and mask; replicates of a voxel whose point status lacks
- *                 MET2_ST_FITTED are not fitted.  FA is not re-estimated per replicate
+ *                 MET2_ST_FITTED are not fitted.  FA is not re-estimated per replicate (met2_fit_bootstrap_fa can)
  * DEVICE pointers: data (echo e of voxel v at data[v * voxel_stride + e * echo_stride], strides > 0), fa_index, mask, fsol, sig, reg, lam,
  * maps, status as for met2_fit_strided; voxel_id [nvox] int64 or NULL; sigma [nvox] (>= 0) or NULL; sigma_out [nvox]; out:
  *   stats       [7][5][nvox]  quantities MWF, IEWF, FWF, T2_M, T2_IE, TWC (the maps' order) and reg; statistics mean, std (ddof = 1; both in
@@ -263,6 +263,34 @@ int met2_fit_bootstrap(met2_plan *plan, int32_t method, int64_t nvox, const doub
                        const double *fa_index, const uint8_t *mask, const int64_t *voxel_id, const double *sigma, int32_t n_rep,
                        int64_t seed, double *fsol, double *sig, double *reg, double *lam, double *maps, int32_t *status,
                        double *sigma_out, double *stats, int32_t *rep_status, void *stream);
+/* The same with the flip angle re-estimated on every replicate, and with statistics of the replicates' spectra (additive; ABI stays 6).
+ * met2_fit_bootstrap refits every replicate at the point fit's FA, so its spread holds only the noise that reaches the spectrum at a fixed
+ * dictionary slice; a pipeline that estimates the FA per voxel (motor:349-373; evaluate_all_methods_two_lobes_SNR50_150.py:398 does so for
+ * every noisy voxel) has a second estimation step, whose error this entry can put into the spread.  Everything not named here is as in
+ * met2_fit_bootstrap: the point fit, sigma_v, the replicate generator (a replicate row is bit for bit met2_bootstrap_replicates') and the gating.
+ *   fa_mode  MET2_BOOT_FA_FIXED       the replicates are fitted at the point fit's FA: rows 0..6 of stats, rep_status, sigma_out and all point
+ *                                     outputs are bit for bit met2_fit_bootstrap's; row 7 holds the point FA index (mean and quantiles, std 0)
+ *            MET2_BOOT_FA_BRUTEFORCE  every replicate row goes through the plan's brute-force walk exactly as met2_fa_bruteforce treats a row
+ *                                     (un-normalised echoes, gate of fa_estimation.py:45) and is fitted at THAT index; the row's mask is the
+ *                                     voxel's point-fit MET2_ST_FITTED bit
+ *            MET2_BOOT_FA_SPLINE      the same with the coarse walk on the plan attached by met2_plan_attach_fa_spline followed by the
+ *                                     spline selection (met2_fa_spline_select); MET2_E_STATE if nothing is attached
+ *   fa_index still gives the POINT fit's FA: the caller estimated it, possibly on a smoothed volume.  A replicate's FA is estimated on the
+ *            replicate row alone: the Gaussian pre-smoothing of motor:337-343 is spatial, and replicates of different voxels are independent
+ *            draws, so it does not apply.  (With a point FA from a smoothed volume the spread would then measure the difference between two
+ *            estimators; the Python drivers refuse that combination.)
+ *   stats       [8][5][nvox]        the 7 quantities of met2_fit_bootstrap, then the FA index the replicates were fitted with
+ *   spec_stats  [5][nvox][n_t2]     or NULL: mean, std (ddof = 1), q0.025, q0.5, q0.975 over the replicates of fsol[row][j] as the fit writes it
+ *                                   (x * km, not normalised), per T2 bin, with the definitions of stats (two deterministic passes; quantiles
+ *                                   bit-equal to np.quantile, method 'linear'); zeros where the point status lacks MET2_ST_FITTED.  Taken from
+ *                                   the replicate spectra the fits have just written: no additional fits
+ * The FA walk is enqueued per chunk in front of the chunk's fit on the caller's stream; its scratch stays with the plans.  Blocking like
+ * met2_fit_bootstrap (the same two waits). */
+enum met2_boot_fa { MET2_BOOT_FA_FIXED = 0, MET2_BOOT_FA_BRUTEFORCE = 1, MET2_BOOT_FA_SPLINE = 2 };
+int met2_fit_bootstrap_fa(met2_plan *plan, int32_t method, int32_t fa_mode, int64_t nvox, const double *data, int64_t voxel_stride,
+                          int64_t echo_stride, const double *fa_index, const uint8_t *mask, const int64_t *voxel_id, const double *sigma,
+                          int32_t n_rep, int64_t seed, double *fsol, double *sig, double *reg, double *lam, double *maps, int32_t *status,
+                          double *sigma_out, double *stats, double *spec_stats, int32_t *rep_status, void *stream);
 /* Test/diagnostic entry: the replicates of met2_fit_bootstrap for given centres.  DEVICE pointers: center [nvox][n_te] (the s_hat), sigma
  * [nvox], voxel_id [nvox] or NULL; out [nvox][n_rep][n_te].  Every voxel gets replicates (no gating).  Asynchronous on `stream`. */
 int met2_bootstrap_replicates(met2_plan *plan, int64_t nvox, const double *center, const double *sigma, const int64_t *voxel_id,

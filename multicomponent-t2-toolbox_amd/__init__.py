@@ -14,4 +14,4 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
 
 There is no CPU fallback: without the built HIP library and a visible GPU every call raises."""
 from ._lib import Met2Error  # noqa: F401
-from .plan import BOOT_QUANTITIES, BOOT_STATS, MAP_NAMES, METHODS, PENALTIES, Met2Plan  # noqa: F401
+from .plan import BOOT_QUANTITIES, BOOT_QUANTITIES_FA, BOOT_STATS, MAP_NAMES, METHODS, PENALTIES, Met2Plan  # noqa: F401

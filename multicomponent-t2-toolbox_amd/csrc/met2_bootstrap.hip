@@ -5,10 +5,15 @@
 // estimate of BayesReg_nnls (intravoxel_algorithms/bayesian_interpolation.py:88-93: sigma from a plain NNLS fit with m - nnz degrees of
 // freedom) and the library's fits.  Every voxel is refitted on B replicates M_b = |s_hat + sigma (z1 + i z2)| of its fitted signal; the
 // replicate fits go through met2_fit_enqueue_strided on per-plan scratch, chunk after chunk on the caller's stream, and the statistics of every
-// chunk's voxels are taken behind its fit.  Three kernels of this file:
-//   bootstrap_sigma_kernel   sigma_v from the plain-NNLS pass (one thread per voxel)
-//   bootstrap_gen_kernel     the replicate rows of a chunk (one thread per echo; counter-based Philox4x32-10, HBM-write-bound)
-//   bootstrap_stats_kernel   mean, std and three quantiles of 7 quantities per voxel (one wave per voxel, bitonic sort in LDS)
+// chunk's voxels are taken behind its fit.  met2_fit_bootstrap_fa re-estimates the flip angle of every replicate row before its fit (the
+// plan's brute-force walk, or the coarse walk and the spline selection) and can return the statistics of the replicates' spectra per T2 bin.
+// Four kernels of this file:
+//   bootstrap_sigma_kernel        sigma_v from the plain-NNLS pass (one thread per voxel)
+//   bootstrap_gen_kernel          the replicate rows of a chunk (one thread per echo; counter-based Philox4x32-10, HBM-write-bound)
+//   bootstrap_stats_kernel        mean, std and three quantiles of 7 (8 with the FA index) quantities per voxel (one wave per voxel)
+//   bootstrap_spec_stats_kernel   the same statistics of every T2 bin of the replicates' spectra (one workgroup per voxel, tiles of bins
+//                                 transposed through LDS, one series per wave at a time)
+// Both statistics kernels reduce and sort a series with series_stats: the bit-level contract has one implementation.
 // The replicates of a voxel depend on (seed, voxel_id, b, e) alone and every replicate is solved on its own, so the outputs do not depend on
 // chunking, call splitting, voxel order or device.
 #include <hip/hip_runtime.h>
@@ -18,6 +23,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
@@ -26,12 +32,15 @@
 
 namespace met2 {
 __attribute__((visibility("hidden"))) int plan_reserve(met2_plan *plan, int64_t nvox);      // the plan's per-voxel scratch (met2_hip.hip)
+__attribute__((visibility("hidden"))) bool fa_spline_attachment(met2_plan *plan, met2_plan **plan_lr, std::vector<double> *alpha_lr,
+                                                                std::vector<double> *alpha_hr);   // met2_host.hip
 }
 
 namespace {
 
 #define MET2_BOOT_MAX_REP 1024
 #define MET2_BOOT_QUANT 7          // MWF, IEWF, FWF, T2_M, T2_IE, TWC, reg
+#define MET2_BOOT_QUANT_FA 8       // ... and the FA index (met2_fit_bootstrap_fa)
 #define MET2_BOOT_STATS 5          // mean, std (ddof 1), quantiles 0.025, 0.5, 0.975
 
 struct GenArgs {
@@ -93,12 +102,13 @@ __global__ __launch_bounds__(256) void bootstrap_sigma_kernel(int64_t nvox, int 
 
 struct StatArgs {
     int64_t v0, nvox, rows;         // first voxel of the chunk, voxels of the call (stride of stats), replicate rows of the chunk
-    int nrep, npow2;
+    int nrep, npow2, nquant;        // nquant: 7, or 8 with the FA index
     const double *maps_r;           // [6][rows]
     const double *reg_r;            // [rows]
+    const double *fa_r;             // [rows] (nquant = 8)
     const int32_t *st_r;            // [rows]
     const int32_t *pstatus;         // [nvox]
-    double *stats;                  // [7][5][nvox]
+    double *stats;                  // [nquant][5][nvox]
     int32_t *rep_status;            // [nvox] or NULL
 };
 
@@ -121,8 +131,56 @@ __device__ double quantile_sorted(const double *s, int n, double p)
     return g >= 0.5 ? b - d * (1.0 - g) : a + d * g;
 }
 
-// one wave (one workgroup) per voxel: for each quantity the B values go to LDS; mean and std in two passes in a fixed order (lane-strided
-// partial sums, then wave_sum); then a bitonic sort over the next power of two (nan padding sorts last) and the three quantiles
+// The lanes of ONE wave exchange values through LDS: a wave's LDS accesses complete in program order, so what is needed is that the compiler
+// keeps them in it (the fences) and that the wave is converged (the barrier, which emits no instruction).  A workgroup barrier would tie the
+// waves of bootstrap_spec_stats_kernel, which sort series of their own, to each other.
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The statistics of one series, by one wave: buf[0..B) holds the values and buf[B..P) nan (P = the next power of two), written by anyone
+// and made visible to this wave before the call.  Mean and std in two passes in a fixed order (lane-strided partial sums, then wave_sum);
+// then a bitonic sort over P (the nan padding sorts last) and the three quantiles.  Lane s < 5 returns statistic s; buf is left sorted.
+// SKIP_EQUAL: a series of B identical finite values (bit patterns; not -0.0, whose sums and lerps give +0.0) needs no sort -- the long way
+// gives mean = c + 0 / B = c, std = sqrt(0 / (B - 1)) = 0 and quantiles a + 0 g = b - 0 (1 - g) = c, the same bits.
+template <bool SKIP_EQUAL>
+__device__ __forceinline__ double series_stats(double *buf, int B, int P, int lane)
+{
+    const double qp[3] = {0.025, 0.5, 0.975};
+    const double c = buf[0];                                   // shifted sums: identical values give a mean equal to them and std 0
+    if (SKIP_EQUAL) {
+        const long long cb = __double_as_longlong(c);
+        bool same = cb != (long long)0x8000000000000000ull && c - c == 0.0;
+        for (int b = lane; b < B; b += 64) same = same && __double_as_longlong(buf[b]) == cb;
+        if (__all(same)) return lane == 1 ? 0.0 : c;
+    }
+    double s = 0.0;
+    for (int b = lane; b < B; b += 64) s += buf[b] - c;
+    const double mean = c + met2::wave_sum(s) / (double)B;
+    double ss = 0.0;
+    for (int b = lane; b < B; b += 64) { const double d = buf[b] - mean; ss += d * d; }
+    const double sd = sqrt(met2::wave_sum(ss) / (double)(B - 1));
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = lane; i < P; i += 64) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const double x = buf[i], y = buf[l];
+                    if ((i & k) == 0 ? nan_last_gt(x, y) : nan_last_gt(y, x)) { buf[i] = y; buf[l] = x; }
+                }
+            }
+            wave_lds_sync();
+        }
+    double r = 0.0;
+    if (lane < MET2_BOOT_STATS) r = lane == 0 ? mean : (lane == 1 ? sd : quantile_sorted(buf, B, qp[lane - 2]));
+    return r;
+}
+
+// one wave (one workgroup) per voxel: for each quantity the B values go to LDS (read with unit stride from the [q][rows] arrays) and
+// through series_stats
 __global__ __launch_bounds__(64) void bootstrap_stats_kernel(StatArgs A)
 {
     __shared__ double buf[MET2_BOOT_MAX_REP];
@@ -130,7 +188,7 @@ __global__ __launch_bounds__(64) void bootstrap_stats_kernel(StatArgs A)
     const int64_t lv = blockIdx.x, v = A.v0 + lv;
     const int B = A.nrep, P = A.npow2;
     if (!(A.pstatus[v] & MET2_ST_FITTED)) {
-        for (int i = lane; i < MET2_BOOT_QUANT * MET2_BOOT_STATS; i += 64) A.stats[i * A.nvox + v] = 0.0;
+        for (int i = lane; i < A.nquant * MET2_BOOT_STATS; i += 64) A.stats[i * A.nvox + v] = 0.0;
         if (lane == 0 && A.rep_status) A.rep_status[v] = 0;
         return;
     }
@@ -141,34 +199,76 @@ __global__ __launch_bounds__(64) void bootstrap_stats_kernel(StatArgs A)
         for (int off = 32; off > 0; off >>= 1) st |= __shfl_xor(st, off);
         if (lane == 0) A.rep_status[v] = st;
     }
-    const double qp[3] = {0.025, 0.5, 0.975};
-    for (int q = 0; q < MET2_BOOT_QUANT; ++q) {
-        const double *src = (q < 6 ? A.maps_r + q * A.rows : A.reg_r) + base;
+    for (int q = 0; q < A.nquant; ++q) {
+        const double *src = (q < 6 ? A.maps_r + q * A.rows : (q == 6 ? A.reg_r : A.fa_r)) + base;
         for (int i = lane; i < P; i += 64) buf[i] = i < B ? src[i] : __builtin_nan("");
         __syncthreads();
-        const double c = buf[0];                                   // shifted sums: identical values give a mean equal to them and std 0
-        double s = 0.0;
-        for (int b = lane; b < B; b += 64) s += buf[b] - c;
-        const double mean = c + met2::wave_sum(s) / (double)B;
-        double ss = 0.0;
-        for (int b = lane; b < B; b += 64) { const double d = buf[b] - mean; ss += d * d; }
-        const double sd = sqrt(met2::wave_sum(ss) / (double)(B - 1));
-        for (int k = 2; k <= P; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = lane; i < P; i += 64) {
-                    const int l = i ^ j;
-                    if (l > i) {
-                        const double x = buf[i], y = buf[l];
-                        if ((i & k) == 0 ? nan_last_gt(x, y) : nan_last_gt(y, x)) { buf[i] = y; buf[l] = x; }
-                    }
-                }
-                __syncthreads();
-            }
-        if (lane < MET2_BOOT_STATS) {
-            const double r = lane == 0 ? mean : (lane == 1 ? sd : quantile_sorted(buf, B, qp[lane - 2]));
-            A.stats[(q * MET2_BOOT_STATS + lane) * A.nvox + v] = r;
+        const double r = series_stats<false>(buf, B, P, lane);
+        if (lane < MET2_BOOT_STATS) A.stats[(q * MET2_BOOT_STATS + lane) * A.nvox + v] = r;
+        __syncthreads();
+    }
+}
+
+struct SpecArgs {
+    int64_t v0, nvox;               // first voxel of the chunk, voxels of the call
+    int nrep, npow2, nt2;
+    int w, lw, S;                   // bins per tile (a power of two, 2^lw), doubles between two series of the tile
+    const double *fsol_r;           // [rows][nt2] the chunk's replicate spectra
+    const int32_t *pstatus;         // [nvox]
+    double *spec;                   // [5][nvox][nt2]
+};
+
+#define MET2_SPEC_WAVES 4
+#ifndef MET2_BOOT_SPEC_SKIP_EQUAL
+#define MET2_BOOT_SPEC_SKIP_EQUAL true     // series_stats' shortcut for constant series in the spectrum kernel (false: for measuring it)
+#endif
+// bins per tile for series of P sort slots: w P = 4 096 doubles (32 KiB) from P = 64 on, 64 bins below.  With the padding and the [5][w]
+// staging of the results a workgroup takes 33 .. 36 KiB of LDS, so four workgroups (16 waves) share a CU's 160 KiB.
+inline int spec_tile_bins(int P) { return P <= 64 ? 64 : 4096 / P; }
+// A series is a row of the tile, S = P + pad doubles long.  The transposing store puts lane (j, b) at double j S + b with the bin j running
+// fastest over min(w, 16) lanes; ds_write_b64 is served in groups of 16 consecutive lanes over 32 banks of 4 bytes = 16 doubles.  S odd
+// spreads 16 bins over the 16 double-banks; with w < 16 a group holds 16 / w replicates of each bin, and S = 16 / w (mod 16) keeps
+// (j S + b) mod 16 distinct.  The sort then reads and writes a series with unit stride, which is conflict-free at any S.
+inline int spec_tile_pad(int w) { return w >= 16 ? 1 : 16 / w; }
+
+// One workgroup of four waves per voxel.  The voxel's [B][nt2] block of the chunk's fsol is taken in tiles of w bins: loaded with the lanes
+// along the bin axis (w consecutive doubles of a row; reading one bin's B values directly would fetch a 64-byte line for every 8 bytes),
+// stored transposed, and then every wave takes whole series through series_stats.  The results of a tile are staged in LDS and written with
+// the lanes along the bin axis again.
+template <bool SKIP_EQUAL>
+__global__ __launch_bounds__(64 * MET2_SPEC_WAVES) void bootstrap_spec_stats_kernel(SpecArgs A)
+{
+    extern __shared__ double spec_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t lv = blockIdx.x, v = A.v0 + lv;
+    const int B = A.nrep, P = A.npow2, n = A.nt2, w = A.w, S = A.S;
+    double *tile = spec_lds, *res = spec_lds + w * S;          // [w][S], [5][w]
+    if (!(A.pstatus[v] & MET2_ST_FITTED)) {
+        for (int i = tid; i < MET2_BOOT_STATS * n; i += 64 * MET2_SPEC_WAVES) {
+            const int s = i / n, j = i - s * n;
+            A.spec[((int64_t)s * A.nvox + v) * n + j] = 0.0;
+        }
+        return;
+    }
+    const double *src = A.fsol_r + lv * B * n;
+    for (int j0 = 0; j0 < n; j0 += w) {
+        const int wj = min(w, n - j0);
+        for (int i = tid; i < P * w; i += 64 * MET2_SPEC_WAVES) {
+            const int j = i & (w - 1), b = i >> A.lw;
+            if (j < wj) tile[j * S + b] = b < B ? src[(int64_t)b * n + j0 + j] : __builtin_nan("");
         }
         __syncthreads();
+        for (int j = wave; j < wj; j += MET2_SPEC_WAVES) {
+            const double r = series_stats<SKIP_EQUAL>(tile + j * S, B, P, lane);
+            if (lane < MET2_BOOT_STATS) res[lane * w + j] = r;
+        }
+        __syncthreads();
+        for (int i = tid; i < MET2_BOOT_STATS * wj; i += 64 * MET2_SPEC_WAVES) {
+            const int s = i / wj, j = i - s * wj;
+            A.spec[((int64_t)s * A.nvox + v) * n + j0 + j] = res[s * w + j];
+        }
+        // the next tile's loads overwrite `tile`, which every wave has left behind the barrier above; `res` is written again only behind the
+        // next tile's first barrier, which these reads precede
     }
 }
 
@@ -179,6 +279,8 @@ struct BootWork {
     int64_t cap_vox = 0, cap_rows = 0;
     char *vox = nullptr;            // sig | sig0 | fsol0 | sigma | reg0 | status
     char *rows = nullptr;           // data | fsol | maps | reg | fa | status | mask
+    int64_t cap_aux = 0;            // bytes
+    char *aux = nullptr;            // spline mode: the coarse walk's residuals [rows][n_lr]
 };
 std::mutex g_boot_mutex;
 std::map<met2_plan *, BootWork> g_boot;
@@ -189,6 +291,7 @@ void free_boot(BootWork &w)
     DevGuard dg(w.device);
     if (w.vox) (void)hipFree(w.vox);
     if (w.rows) (void)hipFree(w.rows);
+    if (w.aux) (void)hipFree(w.aux);
     w = BootWork();
 }
 
@@ -257,10 +360,13 @@ extern "C" int met2_bootstrap_replicates(met2_plan *plan, int64_t nvox, const do
     return MET2_OK;
 }
 
-extern "C" int met2_fit_bootstrap(met2_plan *plan, int32_t method, int64_t nvox, const double *data, int64_t voxel_stride, int64_t echo_stride,
-                                  const double *fa_index, const uint8_t *mask, const int64_t *voxel_id, const double *sigma, int32_t n_rep,
-                                  int64_t seed, double *fsol, double *sig, double *reg, double *lam, double *maps, int32_t *status,
-                                  double *sigma_out, double *stats, int32_t *rep_status, void *stream)
+namespace {
+
+// met2_fit_bootstrap (fa_mode FIXED, nquant 7, no spec_stats) and met2_fit_bootstrap_fa (nquant 8)
+int boot_impl(met2_plan *plan, int32_t method, int32_t fa_mode, int nquant, int64_t nvox, const double *data, int64_t voxel_stride, int64_t echo_stride,
+              const double *fa_index, const uint8_t *mask, const int64_t *voxel_id, const double *sigma, int32_t n_rep, int64_t seed, double *fsol,
+              double *sig, double *reg, double *lam, double *maps, int32_t *status, double *sigma_out, double *stats, double *spec_stats,
+              int32_t *rep_status, void *stream)
 {
     // argument checks first: nothing here touches a device
     if (n_rep < 2 || n_rep > MET2_BOOT_MAX_REP) return fail(MET2_E_INVALID, "n_rep must lie in [2, 1024]");
@@ -268,6 +374,11 @@ extern "C" int met2_fit_bootstrap(met2_plan *plan, int32_t method, int64_t nvox,
     if (voxel_stride <= 0 || echo_stride <= 0) return fail(MET2_E_INVALID, "strides must be positive");
     if (!plan) return fail(MET2_E_INVALID, "NULL plan");
     if (method < MET2_NNLS || method > MET2_BAYESREG) return fail(MET2_E_INVALID, "unknown method");
+    if (fa_mode < MET2_BOOT_FA_FIXED || fa_mode > MET2_BOOT_FA_SPLINE) return fail(MET2_E_INVALID, "unknown fa_mode");
+    met2_plan *plan_lr = nullptr;
+    std::vector<double> alpha_lr, alpha_hr;
+    if (fa_mode == MET2_BOOT_FA_SPLINE && !met2::fa_spline_attachment(plan, &plan_lr, &alpha_lr, &alpha_hr))
+        return fail(MET2_E_STATE, "fa_mode = MET2_BOOT_FA_SPLINE needs met2_plan_attach_fa_spline on the plan first");
     if (nvox == 0) return MET2_OK;
     if (!data || !fsol || !reg || !stats) return fail(MET2_E_INVALID, "NULL argument");
     int nte, nt2, dev;
@@ -297,12 +408,20 @@ extern "C" int met2_fit_bootstrap(met2_plan *plan, int32_t method, int64_t nvox,
     if (rc) return rc;
     rc = met2::plan_reserve(plan, std::max(nvox, rcap));       // the sort scratch is sized once, before anything is enqueued
     if (rc) return rc;
+    const int n_lr = (int)alpha_lr.size();
+    if (plan_lr) {                                             // the coarse walk's residuals, and the coarse plan's own scratch
+        rc = grow(w->aux, w->cap_aux, (int64_t)sizeof(double) * rcap * n_lr, 1);
+        if (rc) return rc;
+        rc = met2::plan_reserve(plan_lr, rcap);
+        if (rc) return rc;
+    }
     double *v_sig = (double *)w->vox, *v_sig0 = v_sig + nvox * nte, *v_fsol0 = v_sig0 + nvox * nte, *v_sigma = v_fsol0 + nvox * nt2;
     double *v_reg0 = v_sigma + nvox;
     int32_t *v_st = (int32_t *)(v_reg0 + nvox);
     double *r_data = (double *)w->rows, *r_fsol = r_data + rcap * nte, *r_maps = r_fsol + rcap * nt2, *r_reg = r_maps + 6 * rcap, *r_fa = r_reg + rcap;
     int32_t *r_st = (int32_t *)(r_fa + rcap);
     uint8_t *r_mask = (uint8_t *)(r_st + rcap);
+    double *r_res = (double *)w->aux;
 
     // 1. the point fit, exactly met2_fit's
     double *psig = sig ? sig : v_sig;
@@ -325,23 +444,67 @@ extern "C" int met2_fit_bootstrap(met2_plan *plan, int32_t method, int64_t nvox,
     // one wait: an FA index outside the dictionary is reported before any replicate is fitted
     rc = met2_plan_finish(plan, stream);
     if (rc) return rc;
-    // 3.-5. chunk after chunk: replicate rows, their fits (enqueued, no wait), the statistics of the chunk's voxels
+    // 3.-5. chunk after chunk: replicate rows, [their flip angles,] their fits (enqueued, no wait), the statistics of the chunk's voxels
     GenArgs G;
     G.nrep = n_rep; G.nte = nte; G.k0 = (uint32_t)(uint64_t)seed; G.k1 = (uint32_t)((uint64_t)seed >> 32);
     G.center = psig; G.sigma = sg; G.vid = voxel_id; G.pstatus = pst; G.fa = fa_index;
     G.out = r_data; G.fa_rows = r_fa; G.mask_rows = r_mask;
     StatArgs S;
-    S.nvox = nvox; S.nrep = n_rep; S.npow2 = npow2; S.maps_r = r_maps; S.reg_r = r_reg; S.st_r = r_st; S.pstatus = pst; S.stats = stats; S.rep_status = rep_status;
+    S.nvox = nvox; S.nrep = n_rep; S.npow2 = npow2; S.nquant = nquant; S.maps_r = r_maps; S.reg_r = r_reg; S.fa_r = r_fa; S.st_r = r_st; S.pstatus = pst;
+    S.stats = stats; S.rep_status = rep_status;
+    SpecArgs Q;
+    Q.nvox = nvox; Q.nrep = n_rep; Q.npow2 = npow2; Q.nt2 = nt2; Q.fsol_r = r_fsol; Q.pstatus = pst; Q.spec = spec_stats;
+    Q.w = spec_tile_bins(npow2); Q.S = npow2 + spec_tile_pad(Q.w);
+    Q.lw = 0;
+    while ((1 << Q.lw) < Q.w) ++Q.lw;
+    const size_t spec_lds = sizeof(double) * ((size_t)Q.w * Q.S + MET2_BOOT_STATS * Q.w);
     for (int64_t v0 = 0; v0 < nvox; v0 += vpc) {
         const int64_t nv = std::min(vpc, nvox - v0), rows = nv * n_rep;
         G.nv = nv; G.v0 = v0;
         hipLaunchKernelGGL(bootstrap_gen_kernel, dim3(gen_grid(rows * nte)), dim3(256), 0, s, G);
         HIPCHK(hipGetLastError());
+        // the rows' flip angles, as met2_fa_bruteforce / the spline method treat a row; the walks keep their scratch with their plans, sized by
+        // the first (largest) chunk.  A row of a voxel without a point fit is masked out and keeps index 0
+        if (fa_mode == MET2_BOOT_FA_BRUTEFORCE) {
+            rc = met2_fa_bruteforce_strided(plan, rows, r_data, nte, 1, r_mask, r_fa, nullptr, nullptr, stream);
+            if (rc) return rc;
+        } else if (fa_mode == MET2_BOOT_FA_SPLINE) {
+            rc = met2_fa_bruteforce_strided(plan_lr, rows, r_data, nte, 1, r_mask, r_fa, nullptr, r_res, stream);
+            if (rc) return rc;
+            rc = met2_fa_spline_select_strided(dev, rows, n_lr, alpha_lr.data(), r_res, (int32_t)alpha_hr.size(), alpha_hr.data(), nte, r_data, nte, 1,
+                                               r_mask, r_fa, nullptr, stream);
+            if (rc) return rc;
+        }
         rc = met2_fit_enqueue_strided(plan, method, rows, r_data, nte, 1, r_fa, r_mask, r_fsol, nullptr, r_reg, nullptr, r_maps, r_st, stream);
         if (rc) return rc;
         S.v0 = v0; S.rows = rows;
         hipLaunchKernelGGL(bootstrap_stats_kernel, dim3((unsigned)nv), dim3(64), 0, s, S);
         HIPCHK(hipGetLastError());
+        if (spec_stats) {
+            Q.v0 = v0;
+            hipLaunchKernelGGL(bootstrap_spec_stats_kernel<MET2_BOOT_SPEC_SKIP_EQUAL>, dim3((unsigned)nv), dim3(64 * MET2_SPEC_WAVES), spec_lds, s, Q);
+            HIPCHK(hipGetLastError());
+        }
     }
     return met2_plan_finish(plan, stream);
+}
+
+}  // namespace
+
+extern "C" int met2_fit_bootstrap(met2_plan *plan, int32_t method, int64_t nvox, const double *data, int64_t voxel_stride, int64_t echo_stride,
+                                  const double *fa_index, const uint8_t *mask, const int64_t *voxel_id, const double *sigma, int32_t n_rep,
+                                  int64_t seed, double *fsol, double *sig, double *reg, double *lam, double *maps, int32_t *status,
+                                  double *sigma_out, double *stats, int32_t *rep_status, void *stream)
+{
+    return boot_impl(plan, method, MET2_BOOT_FA_FIXED, MET2_BOOT_QUANT, nvox, data, voxel_stride, echo_stride, fa_index, mask, voxel_id, sigma, n_rep,
+                     seed, fsol, sig, reg, lam, maps, status, sigma_out, stats, nullptr, rep_status, stream);
+}
+
+extern "C" int met2_fit_bootstrap_fa(met2_plan *plan, int32_t method, int32_t fa_mode, int64_t nvox, const double *data, int64_t voxel_stride,
+                                     int64_t echo_stride, const double *fa_index, const uint8_t *mask, const int64_t *voxel_id, const double *sigma,
+                                     int32_t n_rep, int64_t seed, double *fsol, double *sig, double *reg, double *lam, double *maps, int32_t *status,
+                                     double *sigma_out, double *stats, double *spec_stats, int32_t *rep_status, void *stream)
+{
+    return boot_impl(plan, method, fa_mode, MET2_BOOT_QUANT_FA, nvox, data, voxel_stride, echo_stride, fa_index, mask, voxel_id, sigma, n_rep, seed,
+                     fsol, sig, reg, lam, maps, status, sigma_out, stats, spec_stats, rep_status, stream);
 }

@@ -592,6 +592,17 @@ extern "C" int met2_host_trim(void)
 }
 
 namespace met2 {
+// for met2_fit_bootstrap_fa (met2_bootstrap.hip): a copy of what met2_plan_attach_fa_spline left with the plan; false if nothing is attached
+__attribute__((visibility("hidden"))) bool fa_spline_attachment(met2_plan *plan, met2_plan **plan_lr, std::vector<double> *alpha_lr,
+                                                                std::vector<double> *alpha_hr)
+{
+    std::lock_guard<std::mutex> lock(g_work_mutex);
+    auto it = g_attach.find(plan);
+    if (it == g_attach.end() || !it->second.plan_lr) return false;
+    *plan_lr = it->second.plan_lr; *alpha_lr = it->second.alpha_lr; *alpha_hr = it->second.alpha_hr;
+    return true;
+}
+
 // called by met2_plan_destroy: the block buffers, streams and events this entry keeps with a plan
 __attribute__((visibility("hidden"))) void host_release(met2_plan *plan)
 {

@@ -168,11 +168,15 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     bootstrap=dict(n_rep=100, seed=0): per-voxel bootstrap uncertainty of the metrics (Met2Plan.fit_bootstrap; an extension with no
     counterpart in the reference), on one device (devices[0]) with the pipeline's prepared data and FA indices; voxel_id is the voxel's flat
     index in the volume's C order, whatever the memory order.  Adds '<Q>_bootstrap' [vol..., 5] for Q in BOOT_QUANTITIES (BOOT_STATS along
-    the last axis), 'sigma' and 'rep_status'; the ten outputs are those of the same run without it.
+    the last axis), 'sigma' and 'rep_status'; the ten outputs are those of the same run without it.  Two more keys (Met2Plan.fit_bootstrap's
+    fa and want_spectrum): fa='fixed' (default) | 'brute-force' | 'spline' -- other than 'fixed' it must be the run's FA_method, every
+    replicate then gets its own flip angle and 'FA_bootstrap' [vol..., 5] (degrees) is added; it does not go with FA_smooth='yes' (see
+    _bootstrap_check).  spectrum=True adds 'fsol_bootstrap' [vol..., n_t2, 5], the per-bin band of the T2 spectrum.
     Returns a dict with the driver's ten outputs."""
     boot = _bootstrap_args(bootstrap)
     if boot is not None and distributed:
         raise ValueError("bootstrap runs on one device and does not go with distributed=True")
+    _bootstrap_check(boot, FA_method, FA_smooth)
     if FA_method not in ("brute-force", "spline"):
         raise ValueError("FA_method must be 'spline' or 'brute-force'")
     if denoise not in ("None", None, "none", "NESMA", "TV"):
@@ -197,7 +201,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
                 plan.build_dictionary_epg(res["T2s"], 1000.0 * np.ones_like(res["T2s"]), float(TE_array[1] - TE_array[0]),
                                           np.linspace(90.0, 180.0, plan.n_fa), TR)
                 plan.set_penalty("InvT2" if reg_method == "T2SPARC" else reg_matrix, res["T2s"])
-                _bootstrap_into(res, plan, reg_method, torch.as_tensor(dd).to(plan.device), res["FA_index"], mask > 0, boot)
+                _bootstrap_into(res, plan, reg_method, torch.as_tensor(dd).to(plan.device), res["FA_index"], mask > 0, boot,
+                                (res["T2s"], 1000.0 * np.ones_like(res["T2s"]), float(TE_array[1] - TE_array[0]), TR))
             finally:
                 plan.close()
         return res
@@ -238,7 +243,7 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
         if return_prepared:
             res["data_prepared"] = dd.cpu().numpy()
         if boot is not None:
-            _bootstrap_into(res, plan, reg_method, dd, fa_vol, mm, boot)
+            _bootstrap_into(res, plan, reg_method, dd, fa_vol, mm, boot, (T2s, T1s, tau, TR))
         return res
     finally:
         if own:
@@ -248,25 +253,58 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
 def _bootstrap_args(bootstrap):
     if bootstrap is None:
         return None
-    extra = set(bootstrap) - {"n_rep", "seed"}
+    extra = set(bootstrap) - {"n_rep", "seed", "fa", "spectrum"}
     if extra:
-        raise ValueError("bootstrap takes n_rep and seed, not %s" % sorted(extra))
-    return {"n_rep": int(bootstrap.get("n_rep", 100)), "seed": int(bootstrap.get("seed", 0))}
+        raise ValueError("bootstrap takes n_rep, seed, fa and spectrum, not %s" % sorted(extra))
+    fa = bootstrap.get("fa", "fixed")
+    if fa not in ("fixed", "brute-force", "spline"):
+        raise ValueError("bootstrap fa must be 'fixed', 'brute-force' or 'spline', got %r" % (fa,))
+    return {"n_rep": int(bootstrap.get("n_rep", 100)), "seed": int(bootstrap.get("seed", 0)), "fa": fa, "spectrum": bool(bootstrap.get("spectrum", False))}
 
 
-def _bootstrap_into(res, plan, reg_method, dd, fa_vol, mask, boot):
+def _bootstrap_check(boot, FA_method, FA_smooth):
+    """What a bootstrap with per-replicate flip angles cannot be combined with; raised before any device work."""
+    if boot is None or boot["fa"] == "fixed":
+        return
+    if FA_smooth == "yes":
+        raise ValueError("bootstrap fa=%r does not go with FA_smooth='yes': the point fit's flip angle would come from the Gaussian-smoothed "
+                         "volume and every replicate's from its own unsmoothed row (replicates of different voxels are independent draws, "
+                         "there is nothing to smooth over), so the spread would measure the difference between two estimators; "
+                         "use FA_smooth='no' or fa='fixed'" % (boot["fa"],))
+    if boot["fa"] != FA_method:
+        raise ValueError("bootstrap fa=%r must be the run's FA_method (%r): the replicates are re-estimated the way the point fit was"
+                         % (boot["fa"], FA_method))
+
+
+def _bootstrap_into(res, plan, reg_method, dd, fa_vol, mask, boot, epg=None):
     """recon_met2_arrays(bootstrap=...): Met2Plan.fit_bootstrap on the prepared volume dd [vol..., nt] (a device tensor) with the run's FA
-    indices and mask; the statistics go into res beside the ten outputs, which stay as the run made them."""
+    indices and mask; the statistics go into res beside the ten outputs, which stay as the run made them.  epg = (T2s, T1s, tau, TR): what
+    the coarse plan of fa='spline' is built from."""
     from .plan import BOOT_QUANTITIES
     vol = tuple(dd.shape[:-1])
     vid = np.arange(int(np.prod(vol)), dtype=np.int64).reshape(vol)       # the C-order flat index: independent of the memory order
-    out = plan.fit_bootstrap(reg_method, dd, n_rep=boot["n_rep"], seed=boot["seed"], fa_index=fa_vol, mask=mask, voxel_id=vid,
-                             want_sig=True, want_status=False)
+    plan_lr = None
+    try:
+        if boot["fa"] == "spline":
+            alpha_lr = np.linspace(90.0, 180.0, 15)                          # motor:237
+            plan_lr = Met2Plan(plan.n_te, plan.n_t2, 15, device=plan.device.index or 0)
+            plan_lr.build_dictionary_epg(epg[0], epg[1], epg[2], alpha_lr, epg[3])
+            plan.attach_fa_spline(plan_lr, alpha_lr)
+        out = plan.fit_bootstrap(reg_method, dd, n_rep=boot["n_rep"], seed=boot["seed"], fa_index=fa_vol, mask=mask, voxel_id=vid,
+                                 want_sig=True, want_status=False, fa=boot["fa"], want_spectrum=boot["spectrum"])
+    finally:
+        if plan_lr is not None:
+            plan.attach_fa_spline(None, None)
+            plan_lr.close()
     stats = out["stats"].cpu().numpy()                                    # [7, 5, vol...]
     for i, q in enumerate(BOOT_QUANTITIES):
         res[q + "_bootstrap"] = np.moveaxis(stats[i], 0, -1)
     res["sigma"] = out["sigma"].cpu().numpy()
     res["rep_status"] = out["rep_status"].cpu().numpy()
+    if boot["fa"] != "fixed":
+        res["FA_bootstrap"] = np.where((res["rep_status"] != 0)[..., None], np.moveaxis(out["fa_stats_deg"], 0, -1), 0.0)   # degrees; 0 where not fitted, like 'FA'
+    if boot["spectrum"]:
+        res["fsol_bootstrap"] = np.moveaxis(out["spec_stats"].cpu().numpy(), 0, -1)       # [vol..., n_t2, 5]
 
 
 PIPELINE_CHUNK = 262144       # voxels per DMA block the driver asks met2_fit_host for (262 144: the library's own default; a test sets others)
@@ -418,7 +456,8 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     process drives the GPU; devices=[0, 1, ...]: that one process drives all the listed GPUs through met2_fit_host).  denoise: 'None',
     'NESMA' (motor:305-333) or 'TV' (motor:293-304).  Not reproduced: the mean-spectrum PNG of motor:377-424.
     bootstrap=dict(n_rep=..., seed=...) (an extension, see recon_met2_arrays) also writes <Q>_bootstrap.nii.gz [nx,ny,nz,5] for Q in
-    BOOT_QUANTITIES (BOOT_STATS along the last axis) and sigma.nii.gz."""
+    BOOT_QUANTITIES (BOOT_STATS along the last axis) and sigma.nii.gz; with fa='brute-force' / 'spline' also FA_bootstrap.nii.gz [nx,ny,nz,5]
+    (degrees), with spectrum=True also fsol_bootstrap_{mean,std,q025,q500,q975}.nii.gz [nx,ny,nz,n_t2] each."""
     from . import nifti
     img = nifti.load(path_to_data)
     data = img.get_fdata().astype(np.float64, copy=False)           # Fortran-ordered, like nibabel's: read in place by the solver
@@ -436,6 +475,13 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
         for q in BOOT_QUANTITIES:
             nifti.save(nifti.NiftiImage(res[q + "_bootstrap"], img.affine), path_to_save_data + q + "_bootstrap.nii.gz")
         nifti.save(nifti.NiftiImage(res["sigma"], img.affine), path_to_save_data + "sigma.nii.gz")
+        if "FA_bootstrap" in res:
+            nifti.save(nifti.NiftiImage(res["FA_bootstrap"], img.affine), path_to_save_data + "FA_bootstrap.nii.gz")
+        if "fsol_bootstrap" in res:
+            from .plan import BOOT_STATS
+            for i, st in enumerate(BOOT_STATS):
+                nifti.save(nifti.NiftiImage(np.ascontiguousarray(res["fsol_bootstrap"][..., i]), img.affine),
+                           path_to_save_data + "fsol_bootstrap_" + st + ".nii.gz")
     return res
 
 

@@ -12,7 +12,9 @@ METHODS = {"NNLS": 0, "T2SPARC": 1, "X2": 2, "L_curve": 3, "GCV": 4, "BayesReg":
 PENALTIES = {"I": 0, "L1": 1, "L2": 2, "InvT2": 3}
 MAP_NAMES = ("MWF", "IEWF", "FWF", "T2_M", "T2_IE", "TWC")
 BOOT_QUANTITIES = MAP_NAMES + ("reg",)              # fit_bootstrap's stats [7][5][...]: the six maps and reg_param
+BOOT_QUANTITIES_FA = BOOT_QUANTITIES + ("FA",)        # with fa != "fixed" or want_spectrum: met2_fit_bootstrap_fa's stats [8][5][...]
 BOOT_STATS = ("mean", "std", "q025", "q500", "q975")
+BOOT_FA_MODES = {"fixed": 0, "brute-force": 1, "spline": 2}
 
 _dp = C.POINTER(C.c_double)
 
@@ -88,6 +90,7 @@ class Met2Plan:
         lam = np.zeros(50)
         lam[1:] = np.logspace(np.log10(1e-8), np.log10(10.0), num=49, endpoint=True, base=10.0)
         self._lam_grid = None
+        self.alpha_values = None                  # the flip angles in degrees, once build_dictionary_epg has set them
         self.set_lambda_grid(lam)
 
     def close(self):
@@ -124,6 +127,7 @@ class Met2Plan:
         (_, p2), (_, p1), (_, pa) = _h(T2s), _h(T1s), _h(alpha_values)
         keep = (_h(T2s), _h(T1s), _h(alpha_values))
         check(lib().met2_plan_build_dictionary_epg(self._h, keep[0][1], keep[1][1], float(tau), keep[2][1], float(TR), self._stream()))
+        self.alpha_values = keep[2][0].copy()
         return self
 
     def set_dictionary(self, Dic_3D):
@@ -131,6 +135,7 @@ class Met2Plan:
         if a.shape != (self.n_te, self.n_t2, self.n_fa):
             raise ValueError("Dic_3D must be [n_te, n_t2, n_fa] = %s, got %s" % ((self.n_te, self.n_t2, self.n_fa), a.shape))
         check(lib().met2_plan_set_dictionary(self._h, p))
+        self.alpha_values = None
         return self
 
     def get_dictionary(self):
@@ -228,16 +233,55 @@ class Met2Plan:
             res = {k: (None if t is None else unflatten(t, vol, order, lead=1 if k == "maps" else 0)) for k, t in res.items()}
         return res
 
+    def attach_fa_spline(self, plan_lr, alpha_lr, alpha_hr=None):
+        """met2_plan_attach_fa_spline: `plan_lr` holds the coarse-grid dictionary of the spline FA method (motor:237-238) on this plan's
+        device, alpha_lr its angles in degrees, alpha_hr this plan's (default: those build_dictionary_epg was given).  plan_lr=None
+        detaches.  Needed by fit_bootstrap(fa="spline"); the coarse plan must outlive the attachment."""
+        if plan_lr is None:
+            check(lib().met2_plan_attach_fa_spline(self._h, None, 0, None, 0, None))
+            return self
+        if alpha_hr is None:
+            alpha_hr = self.alpha_values
+        if alpha_hr is None:
+            raise ValueError("alpha_hr is needed: the plan's dictionary was not built by build_dictionary_epg")
+        (al, pal), (ah, pah) = _h(alpha_lr), _h(alpha_hr)
+        check(lib().met2_plan_attach_fa_spline(self._h, plan_lr._h, al.shape[0], pal, ah.shape[0], pah))
+        return self
+
+    def fa_stats_degrees(self, fa_stats):
+        """fit_bootstrap's fa_stats [5, ...] (index units) -> degrees on the plan's flip-angle grid: mean and quantiles by linear interpolation
+        in the index; std times the grid step if the grid is uniform, else nan (a std has no image under a non-linear map).  None when the
+        plan does not know its angles."""
+        a = self.alpha_values
+        if a is None:
+            return None
+        x = fa_stats.detach().cpu().numpy() if torch.is_tensor(fa_stats) else np.asarray(fa_stats, dtype=np.float64)
+        out = np.interp(x, np.arange(a.shape[0], dtype=np.float64), a)
+        d = np.diff(a)
+        uniform = d.size > 0 and np.allclose(d, d[0], rtol=1e-9, atol=0.0)
+        out[1] = x[1] * abs(d[0]) if uniform else np.nan
+        return out
+
     def fit_bootstrap(self, method, data, n_rep=100, seed=0, fa_index=None, mask=None, sigma=None, voxel_id=None, want_sig=True,
-                      want_status=True, want_lambda=False):
+                      want_status=True, want_lambda=False, fa="fixed", want_spectrum=False):
         """Per-voxel bootstrap uncertainty (met2_fit_bootstrap; an extension with no counterpart in the reference).  The point fit is
         fit()'s, bit for bit; then every fitted voxel is refitted on n_rep Rician replicates of its fitted signal at its noise level
         (`sigma`, one entry per voxel, or the plain-NNLS estimate of bayesian_interpolation.py:88-93) and the statistics of the metrics
         are returned.  data, fa_index, mask as for fit(); voxel_id: int64 per voxel (default: the voxel's flat index in the data's
         voxel order) -- a voxel's replicates depend on (seed, voxel_id, replicate, echo) alone.  Returns fit()'s dict plus
-        stats [7, 5, vol...] (BOOT_QUANTITIES x BOOT_STATS), sigma [vol...] and rep_status [vol...] (OR of the replicates' status bits)."""
+        stats [7, 5, vol...] (BOOT_QUANTITIES x BOOT_STATS), sigma [vol...] and rep_status [vol...] (OR of the replicates' status bits).
+        fa: "fixed" (the default) refits every replicate at the voxel's fa_index, so the spread holds the noise that reaches the spectrum at a
+        fixed dictionary slice; "brute-force" / "spline" re-estimate the flip angle on every replicate row (fa_bruteforce; the spline method
+        on the coarse plan of attach_fa_spline) and fit it at that index, so the spread also holds the FA step's error -- use it when the
+        pipeline estimates the FA per voxel on the unsmoothed data (fa_index still gives the point fit's FA).  want_spectrum: statistics of the
+        replicates' spectra per T2 bin.  With fa != "fixed" or want_spectrum the call goes to met2_fit_bootstrap_fa and the result also has
+        fa_stats [5, vol...] (the FA index the replicates were fitted with; BOOT_STATS), fa_stats_deg (numpy, degrees; only when the plan
+        knows its angles, see fa_stats_degrees) and, with want_spectrum, spec_stats [5, vol..., n_t2]; stats stays [7, 5, vol...]."""
         if method not in METHODS:
             raise ValueError("unknown reg_method %r" % (method,))
+        if fa not in BOOT_FA_MODES:
+            raise ValueError("fa must be 'fixed', 'brute-force' or 'spline', got %r" % (fa,))
+        extended = fa != "fixed" or bool(want_spectrum)
         if not torch.is_tensor(data):
             raise ValueError("data must be a CUDA tensor (the hot path has no host fallback)")
         if data.dtype != torch.float64:
@@ -277,16 +321,29 @@ class Met2Plan:
         sig = e((nvox, self.n_te)) if want_sig else None
         lam = e((nvox,)) if want_lambda else None
         status = e((nvox,), torch.int32) if want_status else None
-        sigma_out, stats, rep_status = e((nvox,)), e((7, 5, nvox)), e((nvox,), torch.int32)
+        sigma_out, stats, rep_status = e((nvox,)), e((8 if extended else 7, 5, nvox)), e((nvox,), torch.int32)
+        spec = e((5, nvox, self.n_t2)) if want_spectrum else None
         with torch.cuda.device(dev):
-            check(lib().met2_fit_bootstrap(self._h, METHODS[method], nvox, _ptr(data), vs, es, _ptr(fa_index), _ptr(mask), _ptr(vid), _ptr(sigma),
-                                           n_rep, seed, _ptr(fsol), _ptr(sig), _ptr(reg), _ptr(lam), _ptr(maps), _ptr(status), _ptr(sigma_out),
-                                           _ptr(stats), _ptr(rep_status), self._stream()))
-        res = {"fsol": fsol, "sig": sig, "reg": reg, "lam": lam, "maps": maps, "status": status, "sigma": sigma_out, "stats": stats,
+            if extended:
+                check(lib().met2_fit_bootstrap_fa(self._h, METHODS[method], BOOT_FA_MODES[fa], nvox, _ptr(data), vs, es, _ptr(fa_index), _ptr(mask),
+                                                  _ptr(vid), _ptr(sigma), n_rep, seed, _ptr(fsol), _ptr(sig), _ptr(reg), _ptr(lam), _ptr(maps),
+                                                  _ptr(status), _ptr(sigma_out), _ptr(stats), _ptr(spec), _ptr(rep_status), self._stream()))
+            else:
+                check(lib().met2_fit_bootstrap(self._h, METHODS[method], nvox, _ptr(data), vs, es, _ptr(fa_index), _ptr(mask), _ptr(vid), _ptr(sigma),
+                                               n_rep, seed, _ptr(fsol), _ptr(sig), _ptr(reg), _ptr(lam), _ptr(maps), _ptr(status), _ptr(sigma_out),
+                                               _ptr(stats), _ptr(rep_status), self._stream()))
+        res = {"fsol": fsol, "sig": sig, "reg": reg, "lam": lam, "maps": maps, "status": status, "sigma": sigma_out,
+               "stats": stats[:7] if extended else stats,
                "rep_status": rep_status}
+        if extended:
+            res["fa_stats"] = stats[7]
+            if want_spectrum:
+                res["spec_stats"] = spec
         if len(vol) > 1:
-            lead = {"maps": 1, "stats": 2}
+            lead = {"maps": 1, "stats": 2, "fa_stats": 1, "spec_stats": 1}
             res = {k: (None if t is None else unflatten(t, vol, order, lead=lead.get(k, 0))) for k, t in res.items()}
+        if extended and self.alpha_values is not None:
+            res["fa_stats_deg"] = self.fa_stats_degrees(res["fa_stats"])
         return res
 
     def bootstrap_replicates(self, center, sigma, n_rep, seed=0, voxel_id=None):
