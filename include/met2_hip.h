@@ -295,6 +295,27 @@ int met2_fit_bootstrap_fa(met2_plan *plan, int32_t method, int32_t fa_mode, int6
  * [nvox], voxel_id [nvox] or NULL; out [nvox][n_rep][n_te].  Every voxel gets replicates (no gating).  Asynchronous on `stream`. */
 int met2_bootstrap_replicates(met2_plan *plan, int64_t nvox, const double *center, const double *sigma, const int64_t *voxel_id,
                               int32_t n_rep, int64_t seed, double *out, void *stream);
+/* The statistics kernels of met2_fit_bootstrap and met2_fit_bootstrap_fa on values the caller supplies (additive; ABI stays 6): what summarises a quantity derived
+ * from replicates, and what lets a test hand the kernels any series.  No plan: `device` and `stream` only.  DEVICE pointers.
+ * A series is the n_rep consecutive values of one voxel; its statistics are those of stats above (mean, std with ddof = 1, the 0.025, 0.5
+ * and 0.975 quantiles bit-equal to np.quantile, method 'linear').  status [nvox] or NULL: a voxel whose status lacks MET2_ST_FITTED gets
+ * zeros and its values are not read; NULL counts every voxel (the call then allocates a status of its own and waits for `stream` before it
+ * returns; with a status it is asynchronous on `stream`).  2 <= n_rep <= 1024.
+ *   met2_bootstrap_series_stats     values [n_quant][nvox * n_rep], 1 <= n_quant <= 8  ->  stats [n_quant][5][nvox]   (bootstrap_stats_kernel)
+ *   met2_bootstrap_spectrum_stats   fsol_r [nvox * n_rep][n_t2], 1 <= n_t2 <= 65536    ->  spec [5][nvox][n_t2]      (bootstrap_spec_stats_kernel,
+ *                                   with the tile geometry and LDS size the fused entry launches it with).  Bin j of voxel v is the series
+ *                                   fsol_r[(v n_rep + b) n_t2 + j], b = 0 .. n_rep - 1
+ * Both give the same bits for the same series.  Input domain: finite values and NaN.  A series with a NaN gives five NaNs, as numpy does.
+ * +-inf is outside the contract: the mean is taken from sums shifted by the series' first value, which turn an inf into NaN where numpy
+ * gives inf.  The accuracy of mean and std against exact arithmetic (|mean error| <= 1e-14 max|v|, |std error| <= 1e-12 std + 1e-14 max|v|)
+ * holds for nonzero magnitudes within [1e-150, 1e150]: outside, squares under- or overflow in float64, for numpy's std as well. */
+int met2_bootstrap_series_stats(int32_t device, int64_t nvox, int32_t n_rep, int32_t n_quant, const double *values, const int32_t *status,
+                                double *stats, void *stream);
+int met2_bootstrap_spectrum_stats(int32_t device, int64_t nvox, int32_t n_rep, int32_t n_t2, const double *fsol_r, const int32_t *status,
+                                  double *spec, void *stream);
+/* Host only: how bootstrap_spec_stats_kernel is launched for series of n_rep values, by every entry that launches it -- T2 bins per tile,
+ * doubles between two series of a tile, dynamic LDS in bytes (at most 65 536).  Any output may be NULL. */
+int met2_bootstrap_spec_launch_info(int32_t n_rep, int32_t *tile_bins, int32_t *tile_stride, int64_t *lds_bytes);
 
 /* ---- Monte-Carlo accuracy study (scripts_synthetic_data_evaluation/Paper_Comparison/evaluate_all_methods_two_lobes_SNR*.py) -------
  * met2_synth_two_lobe draws n two-lobe voxels by the reference's recipe (:156-190, :376-428).  Per voxel, from counter-based Philox4x32-10

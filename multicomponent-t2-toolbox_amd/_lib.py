@@ -34,7 +34,8 @@ SYMBOLS = ["met2_default_options", "met2_abi_version", "met2_device_count", "met
            "met2_plan_set_t2_grid", "met2_fit", "met2_fit_strided", "met2_fit_enqueue_strided", "met2_plan_finish", "met2_fa_bruteforce", "met2_fa_bruteforce_strided", "met2_fa_spline_select",
            "met2_fa_spline_select_strided", "met2_roi_reduce", "met2_nesma", "met2_tv_work_bytes", "met2_tv_chambolle", "met2_tv_last_timing", "met2_smooth_separable", "met2_metrics", "met2_plan_last_kernel_ms", "met2_plan_last_second_pass_ms", "met2_plan_last_spill_count",
            "met2_plan_launch_info", "met2_plan_gcv_form", "met2_plan_get_shape", "met2_fit_host", "met2_plan_attach_fa_spline", "met2_host_trim",
-           "met2_fit_bootstrap", "met2_fit_bootstrap_fa", "met2_bootstrap_replicates", "met2_synth_two_lobe", "met2_eval_voxel_metrics", "met2_eval_reduce", "met2_refac_packed_calls"]
+           "met2_fit_bootstrap", "met2_fit_bootstrap_fa", "met2_bootstrap_replicates", "met2_bootstrap_series_stats", "met2_bootstrap_spectrum_stats",
+           "met2_bootstrap_spec_launch_info", "met2_synth_two_lobe", "met2_eval_voxel_metrics", "met2_eval_reduce", "met2_refac_packed_calls"]
 
 
 def lib():
@@ -88,6 +89,9 @@ def lib():
         L.met2_fit_bootstrap.argtypes = [vp, C.c_int32, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int32, C.c_int64] + [vp] * 10
         L.met2_fit_bootstrap_fa.argtypes = [vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int32, C.c_int64] + [vp] * 11
         L.met2_bootstrap_replicates.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_int32, C.c_int64, vp, vp]
+        L.met2_bootstrap_series_stats.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        L.met2_bootstrap_spectrum_stats.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        L.met2_bootstrap_spec_launch_info.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.met2_synth_two_lobe.argtypes = [vp, C.POINTER(SynthParams), C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp]
         L.met2_eval_voxel_metrics.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
         L.met2_eval_reduce.argtypes = [C.c_int64, vp, vp, vp, vp, vp, vp]

@@ -14,6 +14,7 @@
 //   bootstrap_spec_stats_kernel   the same statistics of every T2 bin of the replicates' spectra (one workgroup per voxel, tiles of bins
 //                                 transposed through LDS, one series per wave at a time)
 // Both statistics kernels reduce and sort a series with series_stats: the bit-level contract has one implementation.
+// met2_bootstrap_series_stats / met2_bootstrap_spectrum_stats launch the two on values of the caller's (no plan, no fit).
 // The replicates of a voxel depend on (seed, voxel_id, b, e) alone and every replicate is solved on its own, so the outputs do not depend on
 // chunking, call splitting, voxel order or device.
 #include <hip/hip_runtime.h>
@@ -230,6 +231,22 @@ inline int spec_tile_bins(int P) { return P <= 64 ? 64 : 4096 / P; }
 // spreads 16 bins over the 16 double-banks; with w < 16 a group holds 16 / w replicates of each bin, and S = 16 / w (mod 16) keeps
 // (j S + b) mod 16 distinct.  The sort then reads and writes a series with unit stride, which is conflict-free at any S.
 inline int spec_tile_pad(int w) { return w >= 16 ? 1 : 16 / w; }
+// The launch geometry of bootstrap_spec_stats_kernel for series of n_rep values, the one copy every launch site and
+// met2_bootstrap_spec_launch_info take it from: sort slots, tile shape and the dynamic LDS ([w][S] tile and [5][w] results) in bytes.
+struct SpecGeom { int P, w, lw, S; size_t lds; };
+inline int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+inline SpecGeom spec_geometry(int n_rep)
+{
+    SpecGeom g;
+    g.P = next_pow2(n_rep);
+    g.w = spec_tile_bins(g.P);
+    g.S = g.P + spec_tile_pad(g.w);
+    g.lw = 0;
+    while ((1 << g.lw) < g.w) ++g.lw;
+    g.lds = sizeof(double) * ((size_t)g.w * g.S + MET2_BOOT_STATS * g.w);
+    return g;
+}
+#define MET2_SPEC_LDS_MAX 65536     // the dynamic LDS a kernel gets without asking for more
 
 // One workgroup of four waves per voxel.  The voxel's [B][nt2] block of the chunk's fsol is taken in tiles of w bins: loaded with the lanes
 // along the bin axis (w consecutive doubles of a row; reading one bin's B values directly would fetch a 64-byte line for every 8 bytes),
@@ -392,8 +409,8 @@ int boot_impl(met2_plan *plan, int32_t method, int32_t fa_mode, int nquant, int6
     const int64_t rmax = (method == MET2_LCURVE && nt2 > 64) ? 4096 : 262144;
     const int64_t vpc = std::min<int64_t>(nvox, std::max<int64_t>(1, rmax / n_rep));
     const int64_t rcap = vpc * n_rep;
-    int npow2 = 1;
-    while (npow2 < n_rep) npow2 <<= 1;
+    const SpecGeom geo = spec_geometry(n_rep);
+    const int npow2 = geo.P;
     BootWork *w;
     {
         std::lock_guard<std::mutex> lock(g_boot_mutex);
@@ -454,10 +471,8 @@ int boot_impl(met2_plan *plan, int32_t method, int32_t fa_mode, int nquant, int6
     S.stats = stats; S.rep_status = rep_status;
     SpecArgs Q;
     Q.nvox = nvox; Q.nrep = n_rep; Q.npow2 = npow2; Q.nt2 = nt2; Q.fsol_r = r_fsol; Q.pstatus = pst; Q.spec = spec_stats;
-    Q.w = spec_tile_bins(npow2); Q.S = npow2 + spec_tile_pad(Q.w);
-    Q.lw = 0;
-    while ((1 << Q.lw) < Q.w) ++Q.lw;
-    const size_t spec_lds = sizeof(double) * ((size_t)Q.w * Q.S + MET2_BOOT_STATS * Q.w);
+    Q.w = geo.w; Q.lw = geo.lw; Q.S = geo.S;
+    const size_t spec_lds = geo.lds;
     for (int64_t v0 = 0; v0 < nvox; v0 += vpc) {
         const int64_t nv = std::min(vpc, nvox - v0), rows = nv * n_rep;
         G.nv = nv; G.v0 = v0;
@@ -507,4 +522,84 @@ extern "C" int met2_fit_bootstrap_fa(met2_plan *plan, int32_t method, int32_t fa
 {
     return boot_impl(plan, method, fa_mode, MET2_BOOT_QUANT_FA, nvox, data, voxel_stride, echo_stride, fa_index, mask, voxel_id, sigma, n_rep, seed,
                      fsol, sig, reg, lam, maps, status, sigma_out, stats, spec_stats, rep_status, stream);
+}
+
+namespace {
+
+// status = NULL of the two entries below: every series counts.  The kernels read a status per voxel, so the call makes one, waits for the
+// stream behind its launch and frees it.
+struct AllFitted {
+    int32_t *p = nullptr;
+    ~AllFitted() { if (p) (void)hipFree(p); }
+    int make(int64_t nvox, hipStream_t s)
+    {
+        HIPCHK(hipMalloc(&p, sizeof(int32_t) * (size_t)nvox));
+        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)p, MET2_ST_FITTED, (size_t)nvox, s));
+        return MET2_OK;
+    }
+};
+
+int stats_entry_checks(int64_t nvox, int32_t n_rep)
+{
+    if (n_rep < 2 || n_rep > MET2_BOOT_MAX_REP) return fail(MET2_E_INVALID, "n_rep must lie in [2, 1024]");
+    if (nvox < 0 || nvox > 0x7fffffff) return fail(MET2_E_INVALID, "nvox out of range");
+    return MET2_OK;
+}
+
+}  // namespace
+
+extern "C" int met2_bootstrap_series_stats(int32_t device, int64_t nvox, int32_t n_rep, int32_t n_quant, const double *values,
+                                           const int32_t *status, double *stats, void *stream)
+{
+    int rc = stats_entry_checks(nvox, n_rep);
+    if (rc) return rc;
+    if (n_quant < 1 || n_quant > MET2_BOOT_QUANT_FA) return fail(MET2_E_INVALID, "n_quant must lie in [1, 8]");
+    if (nvox == 0) return MET2_OK;
+    if (!values || !stats) return fail(MET2_E_INVALID, "NULL argument");
+    USE_DEVICE(device);
+    hipStream_t s = (hipStream_t)stream;
+    AllFitted all;
+    if (!status) { rc = all.make(nvox, s); if (rc) return rc; }
+    const int64_t rows = nvox * n_rep;
+    StatArgs S;
+    S.v0 = 0; S.nvox = nvox; S.rows = rows; S.nrep = n_rep; S.npow2 = next_pow2(n_rep); S.nquant = n_quant;
+    S.maps_r = values; S.reg_r = n_quant > 6 ? values + 6 * rows : nullptr; S.fa_r = n_quant > 7 ? values + 7 * rows : nullptr;
+    S.st_r = nullptr; S.pstatus = status ? status : all.p; S.stats = stats; S.rep_status = nullptr;
+    hipLaunchKernelGGL(bootstrap_stats_kernel, dim3((unsigned)nvox), dim3(64), 0, s, S);
+    HIPCHK(hipGetLastError());
+    if (all.p) HIPCHK(hipStreamSynchronize(s));
+    return MET2_OK;
+}
+
+extern "C" int met2_bootstrap_spectrum_stats(int32_t device, int64_t nvox, int32_t n_rep, int32_t n_t2, const double *fsol_r,
+                                             const int32_t *status, double *spec, void *stream)
+{
+    int rc = stats_entry_checks(nvox, n_rep);
+    if (rc) return rc;
+    if (n_t2 < 1 || n_t2 > 65536) return fail(MET2_E_INVALID, "n_t2 must lie in [1, 65536]");
+    if (nvox == 0) return MET2_OK;
+    if (!fsol_r || !spec) return fail(MET2_E_INVALID, "NULL argument");
+    const SpecGeom geo = spec_geometry(n_rep);
+    if (geo.lds > MET2_SPEC_LDS_MAX) return fail(MET2_E_UNSUPPORTED, "the tile of the spectrum statistics does not fit into LDS");
+    USE_DEVICE(device);
+    hipStream_t s = (hipStream_t)stream;
+    AllFitted all;
+    if (!status) { rc = all.make(nvox, s); if (rc) return rc; }
+    SpecArgs Q;
+    Q.v0 = 0; Q.nvox = nvox; Q.nrep = n_rep; Q.npow2 = geo.P; Q.nt2 = n_t2; Q.w = geo.w; Q.lw = geo.lw; Q.S = geo.S;
+    Q.fsol_r = fsol_r; Q.pstatus = status ? status : all.p; Q.spec = spec;
+    hipLaunchKernelGGL(bootstrap_spec_stats_kernel<MET2_BOOT_SPEC_SKIP_EQUAL>, dim3((unsigned)nvox), dim3(64 * MET2_SPEC_WAVES), geo.lds, s, Q);
+    HIPCHK(hipGetLastError());
+    if (all.p) HIPCHK(hipStreamSynchronize(s));
+    return MET2_OK;
+}
+
+extern "C" int met2_bootstrap_spec_launch_info(int32_t n_rep, int32_t *tile_bins, int32_t *tile_stride, int64_t *lds_bytes)
+{
+    if (n_rep < 2 || n_rep > MET2_BOOT_MAX_REP) return fail(MET2_E_INVALID, "n_rep must lie in [2, 1024]");
+    const SpecGeom geo = spec_geometry(n_rep);
+    if (tile_bins) *tile_bins = geo.w;
+    if (tile_stride) *tile_stride = geo.S;
+    if (lds_bytes) *lds_bytes = (int64_t)geo.lds;
+    return MET2_OK;
 }

@@ -365,6 +365,65 @@ class Met2Plan:
             check(lib().met2_bootstrap_replicates(self._h, nvox, _ptr(center), _ptr(sigma), _ptr(vid), int(n_rep), seed, _ptr(out), self._stream()))
         return out
 
+    @staticmethod
+    def _stats_args(t, what, status, nvox):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float64:
+            raise ValueError("%s must be a float64 CUDA tensor (the hot path has no host fallback)" % what)
+        if status is not None:
+            status = torch.as_tensor(status, device=t.device)
+            if status.numel() != nvox:
+                raise ValueError("status has %d entries for %d voxels" % (status.numel(), nvox))
+            status = status.reshape(-1).to(torch.int32).contiguous()
+        return t.contiguous(), status
+
+    @staticmethod
+    def bootstrap_series_stats(values, status=None):
+        """The bootstrap's statistics of any series (met2_bootstrap_series_stats; needs no plan): values [n_quant <= 8, nvox, n_rep] or
+        [nvox, n_rep] float64 CUDA tensor -> [n_quant, 5, nvox] or [5, nvox] (BOOT_STATS).  status: int per voxel (bit 1 = take it) or None = all;
+        the others get zeros.  Finite values and nan; a series with a nan gives five nans."""
+        lead = values.dim() == 3 if torch.is_tensor(values) else False
+        if not torch.is_tensor(values) or values.dim() not in (2, 3):
+            raise ValueError("values must be a [n_quant, nvox, n_rep] or [nvox, n_rep] tensor")
+        nq = int(values.shape[0]) if lead else 1
+        nvox, n_rep = int(values.shape[-2]), int(values.shape[-1])
+        if not 1 <= nq <= 8:
+            raise ValueError("n_quant must lie in [1, 8], got %d" % nq)
+        if not 2 <= n_rep <= 1024:
+            raise ValueError("n_rep must lie in [2, 1024], got %d" % n_rep)
+        values, status = Met2Plan._stats_args(values, "values", status, nvox)
+        out = torch.empty((nq, 5, nvox), dtype=torch.float64, device=values.device)
+        with torch.cuda.device(values.device):
+            check(lib().met2_bootstrap_series_stats(values.device.index, nvox, n_rep, nq, _ptr(values), _ptr(status), _ptr(out),
+                                                    C.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)))
+        return out if lead else out[0]
+
+    @staticmethod
+    def bootstrap_spectrum_stats(fsol_r, status=None):
+        """The bootstrap's statistics per T2 bin of any replicate spectra (met2_bootstrap_spectrum_stats; needs no plan): fsol_r
+        [nvox, n_rep, n_t2] float64 CUDA tensor -> [5, nvox, n_t2] (BOOT_STATS); the same bits as bootstrap_series_stats gives the series
+        fsol_r[v, :, j].  status as there."""
+        if not torch.is_tensor(fsol_r) or fsol_r.dim() != 3:
+            raise ValueError("fsol_r must be a [nvox, n_rep, n_t2] tensor")
+        nvox, n_rep, nt2 = (int(x) for x in fsol_r.shape)
+        if not 2 <= n_rep <= 1024:
+            raise ValueError("n_rep must lie in [2, 1024], got %d" % n_rep)
+        if nt2 < 1:
+            raise ValueError("n_t2 must be at least 1")
+        fsol_r, status = Met2Plan._stats_args(fsol_r, "fsol_r", status, nvox)
+        out = torch.empty((5, nvox, nt2), dtype=torch.float64, device=fsol_r.device)
+        with torch.cuda.device(fsol_r.device):
+            check(lib().met2_bootstrap_spectrum_stats(fsol_r.device.index, nvox, n_rep, nt2, _ptr(fsol_r), _ptr(status), _ptr(out),
+                                                      C.c_void_p(torch.cuda.current_stream(fsol_r.device).cuda_stream)))
+        return out
+
+    @staticmethod
+    def bootstrap_spec_launch_info(n_rep):
+        """(T2 bins per tile, doubles between two series of a tile, dynamic LDS in bytes) of the spectrum statistics kernel for n_rep
+        replicates (met2_bootstrap_spec_launch_info; host only)."""
+        w, S, lds = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        check(lib().met2_bootstrap_spec_launch_info(int(n_rep), C.byref(w), C.byref(S), C.byref(lds)))
+        return w.value, S.value, lds.value
+
     def finish(self):
         """Wait for the current stream and report what fits enqueued with sync=False deferred (met2_plan_finish)."""
         with torch.cuda.device(self.device):

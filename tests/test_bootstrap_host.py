@@ -103,6 +103,79 @@ def test_bootstrap_replicates_argument_checks_need_no_gpu():
         assert msg in L.met2_last_error().decode()
 
 
+def _series(L, n_rep=16, nvox=4, n_quant=7, values=1, stats=1):
+    # nonzero "pointers" are never dereferenced: every check below fails before a device is touched
+    return L.met2_bootstrap_series_stats(0, nvox, n_rep, n_quant, C.c_void_p(values * 256), C.c_void_p(0), C.c_void_p(stats * 256), C.c_void_p(0))
+
+
+def _spectrum(L, n_rep=16, nvox=4, nt2=60, fsol=1, spec=1):
+    return L.met2_bootstrap_spectrum_stats(0, nvox, n_rep, nt2, C.c_void_p(fsol * 256), C.c_void_p(0), C.c_void_p(spec * 256), C.c_void_p(0))
+
+
+@pytest.mark.parametrize("fn,kw,msg", [(_series, {"n_rep": 1}, "n_rep"), (_series, {"n_rep": 1025}, "n_rep"), (_series, {"n_quant": 0}, "n_quant"),
+                                       (_series, {"n_quant": 9}, "n_quant"), (_series, {"nvox": -1}, "nvox"), (_series, {"values": 0}, "NULL"),
+                                       (_series, {"stats": 0}, "NULL"), (_spectrum, {"n_rep": 1}, "n_rep"), (_spectrum, {"n_rep": 1025}, "n_rep"),
+                                       (_spectrum, {"nt2": 0}, "n_t2"), (_spectrum, {"nvox": -1}, "nvox"), (_spectrum, {"fsol": 0}, "NULL"),
+                                       (_spectrum, {"spec": 0}, "NULL")])
+def test_stats_entries_argument_checks_need_no_gpu(fn, kw, msg):
+    L = _lib()
+    assert fn(L, **kw) == -1              # MET2_E_INVALID
+    assert msg in L.met2_last_error().decode()
+
+
+def test_stats_entries_take_an_empty_call():
+    L = _lib()
+    assert _series(L, nvox=0, values=0, stats=0) == 0 and _spectrum(L, nvox=0, fsol=0, spec=0) == 0
+
+
+def _next_pow2(n):
+    p = 1
+    while p < n:
+        p *= 2
+    return p
+
+
+def test_spec_launch_info_is_the_documented_geometry():
+    """met2_bootstrap_spec_launch_info (host only) against the rule the kernel's comment states: 64 bins per tile up to 64 sort slots, then
+    4096 / P down to 4; one double of padding from 16 bins up, 16 / w below; LDS = the [w][S] tile and the [5][w] results, under 64 KiB."""
+    L = _lib()
+    w, S, lds = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    for bad in (1, 1025):
+        assert L.met2_bootstrap_spec_launch_info(bad, C.byref(w), C.byref(S), C.byref(lds)) == -1
+    seen = set()
+    for n_rep in range(2, 1025):
+        assert L.met2_bootstrap_spec_launch_info(n_rep, C.byref(w), C.byref(S), C.byref(lds)) == 0
+        P = _next_pow2(n_rep)
+        ww = 64 if P <= 64 else 4096 // P
+        assert w.value == ww and S.value == P + (1 if ww >= 16 else 16 // ww), n_rep
+        assert lds.value == 8 * (ww * S.value + 5 * ww) and lds.value <= 65536, n_rep
+        seen.add(ww)
+    assert seen == {64, 32, 16, 8, 4}
+    assert L.met2_bootstrap_spec_launch_info(64, None, None, None) == 0
+
+
+def test_stats_wrappers_reject_malformed_calls_before_the_device():
+    plan_mod = importlib.import_module(PKG + ".plan")
+    P = plan_mod.Met2Plan
+    with pytest.raises(ValueError, match="CUDA"):
+        P.bootstrap_series_stats(torch.zeros((3, 8), dtype=torch.float64))
+    with pytest.raises(ValueError, match="n_rep"):
+        P.bootstrap_series_stats(torch.zeros((3, 1), dtype=torch.float64))
+    with pytest.raises(ValueError, match="n_quant"):
+        P.bootstrap_series_stats(torch.zeros((9, 3, 8), dtype=torch.float64))
+    with pytest.raises(ValueError, match="tensor"):
+        P.bootstrap_series_stats(np.zeros((3, 8)))
+    with pytest.raises(ValueError, match="CUDA"):
+        P.bootstrap_spectrum_stats(torch.zeros((3, 8, 60), dtype=torch.float64))
+    with pytest.raises(ValueError, match="n_rep"):
+        P.bootstrap_spectrum_stats(torch.zeros((3, 1025, 2), dtype=torch.float64))
+    with pytest.raises(ValueError, match="n_t2"):
+        P.bootstrap_spectrum_stats(torch.zeros((3, 8, 0), dtype=torch.float64))
+    with pytest.raises(ValueError, match="n_rep, n_t2"):
+        P.bootstrap_spectrum_stats(torch.zeros((3, 8), dtype=torch.float64))
+    assert P.bootstrap_spec_launch_info(1024) == (4, 1028, 8 * (4 * 1028 + 20))
+
+
 def test_any_64bit_seed_passes_the_checks():
     L = _lib()
     for seed in (0, -1, 2 ** 63 - 1, -2 ** 63):

@@ -174,6 +174,94 @@ def test_gated_voxels_get_zero_stats(pkg, synth):
     P.close()
 
 
+def chunk_voxels(method, nt2, n_rep, nvox):
+    """voxels per internal chunk as include/met2_hip.h states them: whole voxels within 262 144 replicate rows, 4 096 for L-curve at n_t2 > 64"""
+    rmax = 4096 if method == "L_curve" and nt2 > 64 else 262144
+    return min(nvox, max(1, rmax // n_rep))
+
+
+BOOT_KEYS = ("stats", "fa_stats", "rep_status", "sigma")
+# method, penalty, nte, nt2, fa, nvox, B, the chunks the call is expected to make, where the split calls cut
+CHUNK_CASES = [("X2", "L2", 32, 60, "brute-force", 300, 1024, [256, 44], [0, 100, 256, 257, 300]),
+               ("X2", "L2", 32, 60, "spline", 300, 1000, [262, 38], [0, 261, 262, 300]),         # aux is sized by the first chunk, reused by a smaller one
+               ("L_curve", "L1", 48, 120, "brute-force", 400, 24, [170, 170, 60], [0, 90, 170, 341, 400])]
+
+
+@pytest.mark.parametrize("method,penalty,nte,nt2,fa,nvox,B,chunks,cuts", CHUNK_CASES)
+def test_chunk_edges_fused_equals_composed_and_split(pkg, synth, method, penalty, nte, nt2, fa, nvox, B, chunks, cuts):
+    """A call of several chunks with a partial last one: the chunk-local row index against the global voxel index in both statistics kernels,
+    the FA row, the spectrum and the spline mode's residual buffer.  Fused against composed with check_stats, and against the same voxels
+    fitted in calls cut inside chunks and at their boundaries, bit for bit."""
+    vpc = chunk_voxels(method, nt2, B, nvox)
+    assert [min(vpc, nvox - v0) for v0 in range(0, nvox, vpc)] == chunks and len(chunks) > 1 and chunks[-1] < vpc       # the premise
+    assert any(c % vpc == 0 for c in cuts[1:-1]) and any(c % vpc != 0 for c in cuts[1:-1])
+    P = Plans(pkg, synth, nte, nt2, penalty, fa)
+    plan = P.plan
+    data, _, _ = synth.make_voxels(nvox, nte=nte, seed=41, fa_values=P.alphas, device="cuda:0")
+    seed = 2 ** 33 + 5
+    fa_point = P.estimate(data)
+    kw = dict(n_rep=B, seed=seed, fa=fa, want_spectrum=True)
+    one = plan.fit_bootstrap(method, data, fa_index=fa_point, **kw)
+    assert bool(((one["status"] & 1) != 0).all())
+    # composed: the fits in runs of 4 096 rows, which are not the call's chunks (and which L-curve at two bins per lane needs: past them the
+    # spill-over kernel's outcome may depend on arrival order)
+    rows = plan.bootstrap_replicates(one["sig"], one["sigma"], B, seed).reshape(nvox * B, nte)
+    fa_rows = P.estimate(rows)
+    step = 4096 if method == "L_curve" else nvox * B
+    frs = [plan.fit(method, rows[a:a + step].contiguous(), fa_index=fa_rows[a:a + step]) for a in range(0, nvox * B, step)]
+    fr = {k: torch.cat([f[k] for f in frs], dim=-1 if k != "fsol" else 0) for k in ("maps", "reg", "fsol", "status")}
+    vals = torch.cat([fr["maps"], fr["reg"][None], fa_rows[None]], 0).reshape(8, nvox, B).cpu().numpy()
+    got = torch.cat([one["stats"], one["fa_stats"][None]], 0).cpu().numpy()                      # [8, 5, nvox]
+    check_stats(np.moveaxis(got, 0, 1), vals, "stats over %d chunks" % len(chunks))
+    spectra = fr["fsol"].reshape(nvox, B, nt2).permute(0, 2, 1).cpu().numpy()                     # [nvox, nt2, B]
+    check_stats(one["spec_stats"].cpu().numpy(), spectra, "spec_stats over %d chunks" % len(chunks))
+    st = fr["status"].reshape(nvox, B).cpu().numpy()
+    assert np.array_equal(one["rep_status"].cpu().numpy(), np.bitwise_or.reduce(st, axis=1))
+    assert len(np.unique(vals[7, vpc:])) > 1                                                      # the walk found different angles past the first chunk
+    del rows, frs, fr
+    # the same voxels in several calls
+    parts = [plan.fit_bootstrap(method, data[a:b].contiguous(), fa_index=fa_point[a:b], voxel_id=np.arange(a, b), **kw)
+             for a, b in zip(cuts[:-1], cuts[1:])]
+    for k in BOOT_KEYS:
+        assert torch.equal(one[k], torch.cat([p[k] for p in parts], dim=-1)), k
+    assert torch.equal(one["spec_stats"], torch.cat([p["spec_stats"] for p in parts], dim=1))
+    P.close()
+
+
+def test_gated_voxels_in_the_second_chunk(pkg, synth):
+    """A masked voxel, an all-zero voxel and a voxel with a nan echo past the first chunk: zeros for them (pstatus[v] is read at the global
+    index), and the rest of that chunk as a call of its own gives it."""
+    nvox, B, nt2 = 300, 1024, 60
+    vpc = chunk_voxels("X2", nt2, B, nvox)
+    gated = [vpc + 4, vpc + 14, nvox - 1]
+    assert vpc < min(gated) and nvox % vpc != 0                                                   # the premise: all three in a partial second chunk
+    P = Plans(pkg, synth)
+    data, _, _ = synth.make_voxels(nvox, nte=32, seed=42, fa_values=P.alphas, device="cuda:0")
+    mask = torch.ones(nvox, dtype=torch.uint8, device="cuda:0")
+    mask[gated[0]] = 0
+    data[gated[1]] = 0.0
+    data[gated[2], 5] = float("nan")
+    fa_point = P.estimate(torch.nan_to_num(data), mask)
+    kw = dict(n_rep=B, seed=4, fa="brute-force", want_spectrum=True)
+    out = P.plan.fit_bootstrap("X2", data, mask=mask, fa_index=fa_point, **kw)
+    ref = P.plan.fit("X2", data, mask=mask, fa_index=fa_point)
+    assert torch.equal(out["status"], ref["status"])
+    fitted = ((out["status"] & 1) != 0).cpu().numpy()
+    assert np.array_equal(np.where(~fitted)[0], gated)
+    st = torch.cat([out["stats"], out["fa_stats"][None]], 0).cpu().numpy()
+    sp = out["spec_stats"].cpu().numpy()
+    rs = out["rep_status"].cpu().numpy()
+    assert np.all(st[:, :, gated] == 0.0) and np.all(sp[:, gated] == 0.0) and np.all(rs[gated] == 0)
+    assert np.all(st[5, 1, fitted] > 0.0) and np.all((rs[fitted] & 1) == 1) and np.all(sp[0, fitted].sum(-1) > 0.0)
+    tail = P.plan.fit_bootstrap("X2", data[vpc:].contiguous(), mask=mask[vpc:], fa_index=fa_point[vpc:], voxel_id=np.arange(vpc, nvox), **kw)
+    for k in ("stats", "fa_stats", "rep_status"):
+        assert torch.equal(out[k][..., vpc:], tail[k]), k
+    ft = torch.as_tensor(fitted[vpc:], device="cuda:0")                                          # sigma of the voxel with a nan echo is nan
+    assert torch.equal(out["sigma"][vpc:][ft], tail["sigma"][ft])
+    assert torch.equal(out["spec_stats"][:, vpc:], tail["spec_stats"])
+    P.close()
+
+
 def test_spline_mode_needs_an_attached_coarse_plan(pkg, synth):
     lib = importlib.import_module(PKG + "._lib")
     P = Plans(pkg, synth, fa="spline", attach=False)
@@ -289,7 +377,7 @@ def test_drivers(pkg, synth, tmp_path):
 def test_what_the_spread_means(pkg, synth):
     """Not a tolerance test.  Empirical std of the MWF over R independent Rician draws, each with its flip angle re-estimated by the
     brute-force walk, against the bootstrap std of ONE draw in both modes; the two medians of bootstrap / empirical are printed (to be
-    recorded in profiles/boot_fa_spread.txt; no figure has been measured yet).  Asserted: only that the re-estimating mode did re-estimate."""
+    recorded in profiles/boot_fa_spread.txt; on an MI355X: 0.955 with the FA fixed, 1.012 with it re-estimated).  Asserted: only that the re-estimating mode did re-estimate."""
     P = Plans(pkg, synth)
     plan = P.plan
     n, snr, R = 2048, 100.0, 64
