@@ -20,6 +20,8 @@ static inline int fail(int code, const std::string &msg) { return met2::abi_fail
 //   MET2_HOST_BLOCKS  met2_fit_host gives its plans whole blocks, not runs of 4 096 voxels (test_round5.py)
 //   MET2_REFAC_PAIR   the warm re-factorisation keeps to its pair loop, no packed leg (test_gpu_refactor_packed.py)
 //   MET2_REFAC_COUNT  the fit kernels count the re-factorisations that took the packed leg (met2_refac_packed_calls; slow: one atomic per call)
+//   MET2_SUBST_REF    the fit kernels' triangular substitutions at one bin per lane run their reference loops, not the lean ones (test_gpu_subst_lean.py)
+//                     (fit_kernel and its spill-over kernels only: the plan's seed kernel, the Bayes table and the flip-angle walk keep the lean loops)
 //   MET2_DEBUG        synchronous launches with progress lines on stderr
 static inline bool test_switch(const char *name) { return getenv(name) != nullptr; }
 

@@ -1823,6 +1823,11 @@ static int debug_counters(int method, hipStream_t s)
     fprintf(stderr, "[met2] calls: warm solves=%llu duals=%llu append rounds=%llu inner loops after an append=%llu\n", cy[12], cy[13], cy[14], cy[15]);
     fprintf(stderr, "[met2] wave cycles: voxel=%llu refactor=%llu inner=%llu dual=%llu append=%llu | slots 5-7 (x2: sse, removals, removal cycles; bayes: chol, upper_times, erf/log; gcv small path: cycles, evaluations, sweeps; append slot += sum k)=%llu %llu %llu\n",
             cy[0], cy[1], cy[2], cy[3], cy[4], cy[5], cy[6], cy[7]);
+    {
+        unsigned long long rk[4];
+        HIPCHK(hipMemcpyFromSymbol(rk, HIP_SYMBOL(met2::g_refk), sizeof(rk)));
+        fprintf(stderr, "[met2] row-by-row re-factorisations: calls=%llu row-terms=%llu | with k > 32: calls=%llu row-terms=%llu\n", rk[0], rk[1], rk[2], rk[3]);
+    }
     if (method == MET2_X2) {
         static unsigned long long ev[40][12];
         HIPCHK(hipMemcpyFromSymbol(ev, HIP_SYMBOL(met2::g_ev), sizeof(ev)));
@@ -1928,7 +1933,7 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
     A.Dfa = p->dD; A.Bfa = p->dB; A.Dtfa = p->dDt; A.Aq = p->dAq; A.kband = p->dKband; A.lband = p->dLband; A.Kd = p->dKd; A.lam_grid = p->dLam; A.t2s = p->dT2;
     A.data = data; A.vs = voxel_stride; A.es = echo_stride; A.sb = sb; A.fsol = fsol; A.sig = sig; A.reg = reg; A.lam = lam; A.maps = maps; A.status = status; A.nvox = nvox;
 
-    A.refac_pair = test_switch("MET2_REFAC_PAIR") ? 1 : 0;
+    A.test_switches = (test_switch("MET2_REFAC_PAIR") ? FitArgs::TEST_REFAC_PAIR : 0) | (test_switch("MET2_SUBST_REF") ? FitArgs::TEST_SUBST_REF : 0);
     A.refac_count = nullptr;
     if (test_switch("MET2_REFAC_COUNT")) HIPCHK(hipGetSymbolAddress((void **)&A.refac_count, HIP_SYMBOL(g_refac_packed_calls)));
     A.seed = nullptr;

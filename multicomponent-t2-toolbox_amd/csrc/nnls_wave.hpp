@@ -47,6 +47,8 @@ __device__ unsigned long long g_cyc[16];
 // per Brent-evaluation index (X2 kernel): [0] evaluations, [1] refactor, [2] inner, [3] dual, [4] append, [5] sse cycles, [6] removals,
 // [7] removal cycles, [8] sum of k at the start, [9] sum of k at the end, [10] evaluations on the canonical (voxel-independent) abscissa
 __device__ unsigned long long g_ev[40][12];
+// calls of refactor_rowwise and their row-terms (row i sums i products per column: k (k - 1) / 2 per call): [0] calls, [1] row-terms, [2] [3] the same of the calls with k > 32
+__device__ unsigned long long g_refk[4];
 #define MET2_CYC_BEGIN(var) const unsigned long long var = __builtin_readcyclecounter()
 #define MET2_CYC_END(slot, var) st.cyc[slot] += __builtin_readcyclecounter() - var
 #define MET2_CYC_ADD(slot, v) st.cyc[slot] += (unsigned long long)(v)
@@ -80,6 +82,8 @@ struct WaveShared {
     double *Rg = nullptr; // this wave's spill-over slot in global memory: columns c >= kmax of the factor, entry (r, c) at col_base(c) - gbase + r
     int gbase = 0;        // col_base(kmax)   (nnls_big.hpp; used by the BIG = true instances of the routines below only)
     bool refac_pair = false;                     // the packed leg of refactor_rowwise is not taken (the test switch MET2_REFAC_PAIR)
+    bool subst_ref = false;                      // the substitutions run their zero-filling reference loops, not the lean ones (the test switch MET2_SUBST_REF;
+                                                 // set by the fit kernels only: the seed, Bayes-table and FA-walk kernels always run the lean loops)
     unsigned long long *refac_count = nullptr;   // calls of refactor_rowwise that took the packed leg are counted here (MET2_REFAC_COUNT), or NULL
 };
 
@@ -297,6 +301,41 @@ __device__ __forceinline__ void givens(double a, double b, double &c, double &s,
     else { sig = 0.0; c = 0.0; s = 1.0; rinv = INFINITY; }
 }
 
+// true in the lanes whose bit is set in the wave-uniform mask m.  The mask is made by the scalar unit and becomes EXEC as it is: a
+// test of the lane number against a wave-uniform bound costs no v_cmp this way.
+__device__ __forceinline__ bool lane_in(u64 m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+
+// The lean column loop of the back substitution (one bin per lane).  The reference loop below reads every column under a
+// per-lane predicate, fills the other lanes with zeros and runs the FMA on all 64 lanes: per column one v_cmp and one 64-bit
+// zero move on top of the arithmetic, and a register copy per pair of columns.  Here the lanes that column c updates (rows < c) are the
+// scalar mask m: the FMA and the read of the NEXT column (rows <= c - 1 of column c - 1: its own entries, diagonal included) run under
+// it and nobody else executes anything, so no zero is needed.  What an updated lane computes -- one FMA per column c > row, in
+// descending c, on the stored entries -- is what the reference computes there; the lanes it leaves out took fma(-0, s, y), which is y for a
+// finite s and a y other than -0.  Two degenerate cases are therefore NOT the reference's bits: behind a pivot with rinv = INFINITY (givens
+// with r2 == 0: a singular factor) s is infinite or NaN and the reference turns every lane into NaN through 0 * inf, where this loop leaves
+// the rows >= c as they are (the rows < c become NaN or inf in both); and a y of -0 in a row >= c becomes +0 in the reference (-0 + +0) and
+// stays -0 here.  The first is a failed solve either way, the second a zero either way; the equality tests compare values and cannot see
+// the sign of a zero.  The same holds for the forward loop of try_append.
+__device__ __forceinline__ void back_subst_lean(const WaveShared &S, const NnlsState<1> &st, int lane, double (&z)[1])
+{
+    const int k = st.k;
+    double y = st.y[0], ra = 0.0, rb = 0.0;
+    const double rinv = st.rinv[0];
+    const double *p = S.R + lane;
+    int cb = col_base(k - 1);
+    u64 m = k > 0 ? ~(~0ull << (k - 1)) : 0ull;                         // lanes < c, c = k - 1 <= 63
+    if (lane_in(m)) ra = p[cb];                                         // column k - 1
+    for (int c = k - 1; c >= 1; c -= 2) {
+        const int cb1 = cb - col_len(c - 1), cb2 = cb1 - col_len(c - 2);   // col_base(c-1), col_base(c-2)
+        double s = bcast(y * rinv, c);                                  // positions >= c are final
+        if (lane_in(m)) { y = fma(-ra, s, y); rb = p[cb1]; }
+        s = bcast(y * rinv, c - 1);
+        if (lane_in(m >> 1)) { y = fma(-rb, s, y); ra = p[cb2]; }       // (c == 1: no lane, nothing is read)
+        cb = cb2; m >>= 2;
+    }
+    z[0] = (lane < k) ? y * rinv : 0.0;
+}
+
 // back substitution R z = y ; z position-indexed.
 // The column loop is unrolled by two with two named prefetch registers: the LDS read issued in one step is
 // consumed a full step later, so the compiler can wait with lgkmcnt(1) instead of draining the read it has
@@ -304,6 +343,7 @@ __device__ __forceinline__ void givens(double a, double b, double &c, double &s,
 template <int NB, int NP = NB>
 __device__ __forceinline__ void back_subst(const WaveShared &S, const NnlsState<NB> &st, int lane, double (&z)[NB])
 {
+    if constexpr (NB == 1 && NP == 1) if (!S.subst_ref) { back_subst_lean(S, st, lane, z); return; }
     const int k = st.k;
     double y[NB], ra[NB], rb[NB];
     int cb = col_base(k - 1);                                           // column c of the loop below
@@ -460,7 +500,23 @@ __device__ __forceinline__ bool try_append(const WaveShared &S, const Band<NB> &
     }
     // forward substitution R^T r = g, unrolled by two with two prefetch registers (see back_subst); a lane walks
     // down its own column, so the row index is an immediate offset from a fixed per-lane address
-    {
+    bool lean = false;
+    if constexpr (NB == 1 && NP == 1) lean = !S.subst_ref;
+    if (lean) {
+        // the lean loop (back_subst_lean): row i updates the positions i < p < k, a scalar mask; the FMA and the read of the lane's entry of
+        // the next row (row i + 1 <= p: inside its own column) run under it, one FMA per row i < p in ascending i as in the reference loop
+        const u64 kmask = k >= 64 ? ~0ull : (1ull << k) - 1ull;
+        const double *col = S.R + cbl[0];
+        double gq = g[0], ru = rv[0], rw = 0.0;
+        const double rinv = st.rinv[0];
+        for (int i = 0; i + 1 < k; i += 2) {                                // (i <= 62)
+            double s = bcast(gq * rinv, i);                                 // positions <= i are final
+            if (lane_in(kmask & (~1ull << i))) { gq = fma(-ru, s, gq); rw = col[i + 1]; }
+            s = bcast(gq * rinv, i + 1);
+            if (lane_in(kmask & (~3ull << i))) { gq = fma(-rw, s, gq); ru = col[i + 2]; }
+        }
+        g[0] = gq;
+    } else {
         double rw[NB];
 #pragma unroll
         for (int b = 0; b < NP; ++b) rw[b] = 0.0;
@@ -846,6 +902,13 @@ __device__ __forceinline__ bool refactor_rowwise(const WaveShared &S, const Band
 {
     static_assert(!PACK || (NB == 1 && NP == 1), "the packed leg is written for one bin per lane");
     const int k = st.k, n = S.n;
+#ifdef MET2_CYCSTATS
+    if (lane == 0) {
+        const unsigned long long terms = (unsigned long long)(k * (k - 1) / 2);
+        atomicAdd(&g_refk[0], 1ull); atomicAdd(&g_refk[1], terms);
+        if (k > 32) { atomicAdd(&g_refk[2], 1ull); atomicAdd(&g_refk[3], terms); }
+    }
+#endif
     int cbl[NB], cbc[NB];
     unsigned jc[NB];
     double g[NB], gb0[NB], gk0[NB], gb1[NB], gk1[NB];
