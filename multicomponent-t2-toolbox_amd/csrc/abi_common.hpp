@@ -22,6 +22,8 @@ static inline int fail(int code, const std::string &msg) { return met2::abi_fail
 //   MET2_REFAC_COUNT  the fit kernels count the re-factorisations that took the packed leg (met2_refac_packed_calls; slow: one atomic per call)
 //   MET2_SUBST_REF    the fit kernels' triangular substitutions at one bin per lane run their reference loops, not the lean ones (test_gpu_subst_lean.py)
 //                     (fit_kernel and its spill-over kernels only: the plan's seed kernel, the Bayes table and the flip-angle walk keep the lean loops)
+//   MET2_ROWWALK_REF  the fit kernels' model signal at one bin per lane runs on the whole wave with one lane read per passive position, not on two
+//                     half waves (test_gpu_row_walk.py; same reach as MET2_SUBST_REF)
 //   MET2_DEBUG        synchronous launches with progress lines on stderr
 static inline bool test_switch(const char *name) { return getenv(name) != nullptr; }
 

@@ -82,6 +82,7 @@ struct FitArgs {
                                           // costs them 16-32 B per lane
     static constexpr int TEST_REFAC_PAIR = 1;   // MET2_REFAC_PAIR: the warm re-factorisation never takes its packed leg (refactor_rowwise)
     static constexpr int TEST_SUBST_REF = 2;    // MET2_SUBST_REF: the substitutions' reference loops (back_subst, try_append)
+    static constexpr int TEST_ROWWALK_REF = 4;  // MET2_ROWWALK_REF: model_signal on the whole wave, one lane read per position
     unsigned long long *refac_count = nullptr;   // test switch MET2_REFAC_COUNT: the calls that took it are counted here
 };
 
@@ -884,7 +885,8 @@ __device__ __forceinline__ void fit_shared(const FitArgs &A, WaveShared &S, doub
     S.R = sR; S.n = A.n; S.m = A.m; S.kmax = A.kmax; S.rcap = A.wave_doubles; S.K = A.Kd; S.kband = A.kband; S.Dt = nullptr; S.DtG = A.Dtfa; S.dtstride = A.m; S.buffer_rows = true; S.reorder = true; S.have_bdiag = false; S.bdiag[0] = S.bdiag[1] = 0.0;
     S.B = A.Bfa; S.D = A.Dfa; S.bstride = A.n; S.dstride = A.n;
     S.Rg = A.big ? A.big + (size_t)wslot * (size_t)A.big_stride : nullptr; S.gbase = col_base(A.kmax);
-    S.refac_pair = (A.test_switches & FitArgs::TEST_REFAC_PAIR) != 0; S.subst_ref = (A.test_switches & FitArgs::TEST_SUBST_REF) != 0; S.refac_count = A.refac_count;
+    S.refac_pair = (A.test_switches & FitArgs::TEST_REFAC_PAIR) != 0; S.subst_ref = (A.test_switches & FitArgs::TEST_SUBST_REF) != 0;
+    S.rowwalk_ref = (A.test_switches & FitArgs::TEST_ROWWALK_REF) != 0; S.refac_count = A.refac_count;
 }
 template <int METHOD>
 __device__ __forceinline__ void fit_shared_fa(const FitArgs &A, WaveShared &S, int fa)

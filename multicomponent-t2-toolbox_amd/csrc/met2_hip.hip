@@ -1933,7 +1933,8 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
     A.Dfa = p->dD; A.Bfa = p->dB; A.Dtfa = p->dDt; A.Aq = p->dAq; A.kband = p->dKband; A.lband = p->dLband; A.Kd = p->dKd; A.lam_grid = p->dLam; A.t2s = p->dT2;
     A.data = data; A.vs = voxel_stride; A.es = echo_stride; A.sb = sb; A.fsol = fsol; A.sig = sig; A.reg = reg; A.lam = lam; A.maps = maps; A.status = status; A.nvox = nvox;
 
-    A.test_switches = (test_switch("MET2_REFAC_PAIR") ? FitArgs::TEST_REFAC_PAIR : 0) | (test_switch("MET2_SUBST_REF") ? FitArgs::TEST_SUBST_REF : 0);
+    A.test_switches = (test_switch("MET2_REFAC_PAIR") ? FitArgs::TEST_REFAC_PAIR : 0) | (test_switch("MET2_SUBST_REF") ? FitArgs::TEST_SUBST_REF : 0) |
+                      (test_switch("MET2_ROWWALK_REF") ? FitArgs::TEST_ROWWALK_REF : 0);
     A.refac_count = nullptr;
     if (test_switch("MET2_REFAC_COUNT")) HIPCHK(hipGetSymbolAddress((void **)&A.refac_count, HIP_SYMBOL(g_refac_packed_calls)));
     A.seed = nullptr;

@@ -84,6 +84,8 @@ struct WaveShared {
     bool refac_pair = false;                     // the packed leg of refactor_rowwise is not taken (the test switch MET2_REFAC_PAIR)
     bool subst_ref = false;                      // the substitutions run their zero-filling reference loops, not the lean ones (the test switch MET2_SUBST_REF;
                                                  // set by the fit kernels only: the seed, Bayes-table and FA-walk kernels always run the lean loops)
+    bool rowwalk_ref = false;                    // model_signal() walks the passive set on the whole wave with one lane read per position, not on two half waves
+                                                 // (the test switch MET2_ROWWALK_REF; set by the fit kernels only, as subst_ref)
     unsigned long long *refac_count = nullptr;   // calls of refactor_rowwise that took the packed leg are counted here (MET2_REFAC_COUNT), or NULL
 };
 
@@ -1505,6 +1507,27 @@ __device__ __forceinline__ double model_signal(const WaveShared &S, const NnlsSt
     double acc = 0.0, acc2 = 0.0, xp[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) { const double t = gatherN<NB>(st.x, st.ord[b]); xp[b] = (lane + 64 * b < k) ? t : 0.0; }   // as in dual()
+    if constexpr (NB == 1 && MET2_ROWWALK_ON(2)) if (S.m <= 32 && S.buffer_rows && !S.rowwalk_ref) {
+        // The half-wave form (at most 32 echoes: the upper half wave carries none).  The loop below keeps two chains, acc over the positions
+        // p, p + 2, ... and acc2 over p + 1, p + 3, ...: here lane e < 32 runs acc of echo e and lane 32 + e runs acc2 of the same echo, each
+        // the same FMAs on the same operands in the same order, so a group of four positions costs two row loads and two FMAs, not four and
+        // four.  The two halves want different positions, so nothing here is wave-uniform: the bin and x of a lane's position come through
+        // ds_bpermute (no lane reads, no scalar row offset -- the row offset is a per-lane v_mad).  The closing acc + acc2 takes the upper
+        // half's chain across with one 64-bit lane exchange; lane 32 + e forms acc2 + acc, the same sum.  Lanes >= m hold the clamped
+        // echo's value, as before; every caller masks them.
+        const int lo_ = lane_opaque(lane), hi = lo_ >> 5;
+        const unsigned ecb = 8u * (unsigned)min(lo_ & 31, S.m - 1), rowb = 8u * (unsigned)S.dtstride;
+#pragma clang loop unroll(disable)
+        for (int p = 0; p < k; p += 4) {
+            const int pa = p + hi, pb = pa + 2;                          // <= 63 (p <= 60)
+            const unsigned ta = (unsigned)gather_i(st.ord[0], pa), tb = (unsigned)gather_i(st.ord[0], pb);
+            const double va = ld_row(S.Dt, 0, ta * rowb + ecb), vb = ld_row(S.Dt, 0, tb * rowb + ecb);
+            const double xa = gather(xp[0], pa), xb = gather(xp[0], pb);
+            acc = fma(va, xa, acc);
+            acc = fma(vb, xb, acc);
+        }
+        return acc + gather(acc, lo_ ^ 32);
+    }
     const unsigned ec = (unsigned)min(lane, S.m - 1);
 #pragma clang loop unroll(disable)
     for (int p = 0; p < k; p += 4) {
@@ -1616,6 +1639,7 @@ __device__ __forceinline__ void big_uniform(WaveShared &S)
     S.dtstride = big_rfl(S.dtstride); S.n = big_rfl(S.n); S.m = big_rfl(S.m); S.bstride = big_rfl(S.bstride); S.dstride = big_rfl(S.dstride);
     S.kmax = big_rfl(S.kmax); S.rcap = big_rfl(S.rcap); S.gbase = big_rfl(S.gbase);
     S.have_bdiag = big_rfl((int)S.have_bdiag) != 0; S.reorder = big_rfl((int)S.reorder) != 0; S.buffer_rows = big_rfl((int)S.buffer_rows) != 0;
+    S.rowwalk_ref = big_rfl((int)S.rowwalk_ref) != 0;
 }
 template <int NB>
 __device__ __forceinline__ void big_uniform(NnlsState<NB> &st)
