@@ -437,6 +437,37 @@ int met2_tv_chambolle(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_
 /* For reports: HIP-event time (ms) from the first to the last Chambolle launch of the calling thread's most recent
  * met2_tv_chambolle (blocks until they finished) and the number of iterations that were enqueued. */
 int met2_tv_last_timing(double *iter_ms, int32_t *launches);
+/* The noise estimate's kernels one by one, and the tile geometry of the iteration, for tests and diagnostics (additive; ABI stays 6).
+ * met2_tv_chambolle launches tv_gather_kernel, tv_detail_kernel and tv_sigma_kernel through the same host helpers as these entries.
+ *
+ * Host only: how met2_tv_chambolle lays a shape out.  (n0, n1, n2) is one echo volume in memory order, slowest axis first: (nx, ny, nz)
+ * for echo_major = 0, (nz, ny, nx) for echo_major = 1.  A workgroup of tv_iter_kernel has `oy` rows of 64 lanes and owns step1 rows
+ * along n1 (oy when n1 <= oy, else oy - 1: the last row is a halo) and step2 lanes along n2; it marches over xlen planes along n0.
+ * nt1, nt2, nseg = tiles along n1 and n2, segments along n0; ntiles = nt1 nt2 nseg per echo.  c0, c1, c2 = (n + 3) / 2 per memory axis:
+ * the shape of the 'ddd' sub-band; nc = c0 c1 c2.  sigma_cap: tv_sigma_kernel counts on the whole array while more than this many keys
+ * share the prefix found so far, and decides the remaining bits on a list in LDS after that.
+ * met2_tv_work_bytes = the sum, each term rounded up to a multiple of 256, of: 8 vol n_te (echo-major copy), 2 x 24 vol n_te (the two
+ * buffers of p), 8 nc n_te (coefficients), 16 ntiles n_te (energy partials), 56 n_te (per-echo state), 8 n_te (weights); vol = n0 n1 n2. */
+typedef struct met2_tv_geometry {
+    int32_t oy, step1, step2, xlen, nt1, nt2, nseg, ntiles, c0, c1, c2, sigma_cap;
+    int64_t nc;
+} met2_tv_geometry;
+int met2_tv_launch_info(int32_t nx, int32_t ny, int32_t nz, int32_t n_te, int32_t echo_major, met2_tv_geometry *geom);
+/* The finest all-detail ('ddd') db2 coefficients of every echo volume: the gather (echo_major = 0 only) and tv_detail_kernel.
+ * DEVICE pointers: data as for met2_tv_chambolle (n_te <= 127 for echo_major = 0); coef [n_te][c0][c1][c2] in the volume's MEMORY axis
+ * order: [n_te][(nx+3)/2][(ny+3)/2][(nz+3)/2] for echo_major = 0, [n_te][(nz+3)/2][(ny+3)/2][(nx+3)/2] for echo_major = 1.  The separable
+ * passes run x first, then y, then z in either layout, products and sums rounded separately and added in tap order, so both layouts
+ * give the same bits for the same volume.  Input domain: any float64, axis lengths >= 1 (inf and nan propagate as in IEEE arithmetic).
+ * Allocates its echo-major copy inside and blocks until the coefficients are written. */
+int met2_tv_detail(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, int32_t echo_major, double *coef,
+                   void *stream);
+/* tv_sigma_kernel on coefficients the caller supplies.  DEVICE: coef [n_te][nc], nc >= 1; out, each may be NULL: sigma [n_te] =
+ * median(|d|) / 0.6744897501960817 over the echo's non-zero d (-0.0 counts as zero), bit-equal to np.median -- the mean (a + b) / 2 of the
+ * two middle values for an even count; 0 when every d is zero; nan when any d is inf or nan.  weight_out [n_te] = weight[t] if given, else
+ * weight_factor x sigma; copy [n_te] int32 = 1 where that weight is not a positive finite number (met2_tv_chambolle copies such an echo
+ * through).  HOST: weight [n_te] or NULL.  Input domain: any float64, denormals included.  Blocking. */
+int met2_tv_sigma(int32_t device, int32_t n_te, int64_t nc, const double *coef, const double *weight, double weight_factor, double *sigma,
+                  double *weight_out, int32_t *copy, void *stream);
 
 /* motor/motor_recon_met2_real_data_ROI.py:405-420, the reduction of the ROI mode: for every ROI the mean signal over its
  * voxels and the mean EPG kernel, each voxel contributing the dictionary slice of its own flip angle

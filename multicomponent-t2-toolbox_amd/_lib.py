@@ -27,12 +27,16 @@ class SynthParams(C.Structure):
                                   "sie_lo", "sie_hi", "km")]
 
 
+class TvGeometry(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("oy", "step1", "step2", "xlen", "nt1", "nt2", "nseg", "ntiles", "c0", "c1", "c2", "sigma_cap")] + [("nc", C.c_int64)]
+
+
 # every symbol include/met2_hip.h declares
 SYMBOLS = ["met2_default_options", "met2_abi_version", "met2_device_count", "met2_last_error", "met2_plan_create",
            "met2_plan_destroy", "met2_plan_set_options", "met2_plan_get_options", "met2_plan_build_dictionary_epg", "met2_plan_set_dictionary", "met2_plan_get_dictionary",
            "met2_plan_set_penalty", "met2_plan_set_penalty_dense", "met2_plan_get_penalty", "met2_plan_set_lambda_grid",
            "met2_plan_set_t2_grid", "met2_fit", "met2_fit_strided", "met2_fit_enqueue_strided", "met2_plan_finish", "met2_fa_bruteforce", "met2_fa_bruteforce_strided", "met2_fa_spline_select",
-           "met2_fa_spline_select_strided", "met2_roi_reduce", "met2_nesma", "met2_tv_work_bytes", "met2_tv_chambolle", "met2_tv_last_timing", "met2_smooth_separable", "met2_metrics", "met2_plan_last_kernel_ms", "met2_plan_last_second_pass_ms", "met2_plan_last_spill_count",
+           "met2_fa_spline_select_strided", "met2_roi_reduce", "met2_nesma", "met2_tv_work_bytes", "met2_tv_chambolle", "met2_tv_last_timing", "met2_tv_launch_info", "met2_tv_detail", "met2_tv_sigma", "met2_smooth_separable", "met2_metrics", "met2_plan_last_kernel_ms", "met2_plan_last_second_pass_ms", "met2_plan_last_spill_count",
            "met2_plan_launch_info", "met2_plan_gcv_form", "met2_plan_get_shape", "met2_fit_host", "met2_plan_attach_fa_spline", "met2_host_trim",
            "met2_fit_bootstrap", "met2_fit_bootstrap_fa", "met2_bootstrap_replicates", "met2_bootstrap_series_stats", "met2_bootstrap_spectrum_stats",
            "met2_bootstrap_spec_launch_info", "met2_synth_two_lobe", "met2_eval_voxel_metrics", "met2_eval_reduce", "met2_refac_packed_calls"]
@@ -74,6 +78,9 @@ def lib():
         L.met2_tv_work_bytes.restype = C.c_int64
         L.met2_tv_chambolle.argtypes = [C.c_int32] * 5 + [vp, C.c_int32, _dp, C.c_double, C.c_double, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp]
         L.met2_tv_last_timing.argtypes = [_dp, C.POINTER(C.c_int32)]
+        L.met2_tv_launch_info.argtypes = [C.c_int32] * 5 + [C.POINTER(TvGeometry)]
+        L.met2_tv_detail.argtypes = [C.c_int32] * 5 + [vp, C.c_int32, vp, vp]
+        L.met2_tv_sigma.argtypes = [C.c_int32, C.c_int32, C.c_int64, vp, _dp, C.c_double, vp, vp, vp, vp]
         L.met2_smooth_separable.argtypes = [C.c_int32] * 6 + [_dp] + [vp] * 4
         L.met2_metrics.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
         L.met2_plan_last_kernel_ms.argtypes = [vp, _dp]

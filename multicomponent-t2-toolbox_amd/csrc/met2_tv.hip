@@ -583,6 +583,41 @@ void launch_iter(const TvIterArgs &A, int oy, int nt, hipStream_t s)
     }
 }
 
+// dynamic LDS of tv_gather_kernel / tv_scatter_kernel: a [64][nt + 1] tile of doubles
+size_t tv_gather_lds(int nt) { return sizeof(double) * 64 * ((size_t)nt + 1); }
+
+// The launches of the noise estimate.  met2_tv_chambolle and the test-facing entries (met2_tv_detail, met2_tv_sigma) all go through these.
+void launch_gather(const TvLayout &L, int nt, const double *data, double *F, hipStream_t s)
+{
+    hipLaunchKernelGGL(tv_gather_kernel, dim3((unsigned)((L.vol + 63) / 64)), dim3(256), tv_gather_lds(nt), s, L.vol, nt, data, F);
+}
+
+void launch_detail(bool rev, int n0, int n1, int n2, const TvLayout &L, int nt, const double *F, double *coef, hipStream_t s)
+{
+    TvDetailArgs D;
+    D.n0 = n0; D.n1 = n1; D.n2 = n2; D.c0 = L.c0; D.c1 = L.c1; D.c2 = L.c2; D.vol = L.vol; D.nc = L.nc; D.F = F; D.coef = coef;
+    const dim3 g((unsigned)((L.nc + 255) / 256), (unsigned)nt);
+    if (rev) hipLaunchKernelGGL(tv_detail_kernel<true>, g, dim3(256), 0, s, D);
+    else hipLaunchKernelGGL(tv_detail_kernel<false>, g, dim3(256), 0, s, D);
+}
+
+void launch_sigma(int nt, int64_t nc, const double *coef, TvState *state, double factor, const double *dweight, hipStream_t s)
+{
+    TvSigmaArgs S;
+    S.nc = nc; S.coef = coef; S.state = state; S.factor = factor; S.weight_in = dweight;
+    hipLaunchKernelGGL(tv_sigma_kernel, dim3((unsigned)nt), dim3(1024), 0, s, S);
+}
+
+// met2_tv_sigma: what tv_sigma_kernel left in the echoes' states
+__global__ void tv_sigma_report_kernel(int nt, const TvState *state, double *sigma, double *weight, int32_t *copy)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nt) return;
+    if (sigma) sigma[t] = state[t].sigma;
+    if (weight) weight[t] = state[t].weight;
+    if (copy) copy[t] = state[t].copy;
+}
+
 }  // namespace
 
 extern "C" int64_t met2_tv_work_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t n_te, int32_t echo_major)
@@ -591,6 +626,67 @@ extern "C" int64_t met2_tv_work_bytes(int32_t nx, int32_t ny, int32_t nz, int32_
     TvLayout L;
     tv_layout(echo_major ? nz : nx, ny, echo_major ? nx : nz, n_te, L);
     return (int64_t)L.bytes;
+}
+
+extern "C" int met2_tv_launch_info(int32_t nx, int32_t ny, int32_t nz, int32_t n_te, int32_t echo_major, met2_tv_geometry *geom)
+{
+    if (nx < 1 || ny < 1 || nz < 1 || n_te < 1) return fail(MET2_E_INVALID, "bad shape");
+    if (!geom) return fail(MET2_E_INVALID, "NULL argument");
+    TvLayout L;
+    tv_layout(echo_major ? nz : nx, ny, echo_major ? nx : nz, n_te, L);
+    geom->oy = L.oy; geom->step1 = L.step1; geom->step2 = L.step2; geom->xlen = L.xlen; geom->nt1 = L.nt1; geom->nt2 = L.nt2;
+    geom->nseg = L.nseg; geom->ntiles = L.ntiles; geom->c0 = L.c0; geom->c1 = L.c1; geom->c2 = L.c2; geom->sigma_cap = TV_SIGMA_CAP;
+    geom->nc = L.nc;
+    return MET2_OK;
+}
+
+extern "C" int met2_tv_detail(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, int32_t echo_major,
+                              double *coef, void *stream)
+{
+    if (nx < 1 || ny < 1 || nz < 1 || n_te < 1) return fail(MET2_E_INVALID, "bad shape");
+    if (n_te > 65535) return fail(MET2_E_UNSUPPORTED, "at most 65535 echo volumes");
+    if (!data || !coef) return fail(MET2_E_INVALID, "NULL argument");
+    const bool rev = echo_major != 0;
+    const int n0 = rev ? nz : nx, n1 = ny, n2 = rev ? nx : nz;
+    TvLayout L;
+    tv_layout(n0, n1, n2, n_te, L);
+    if ((L.vol + 63) / 64 > 0x7fffffffLL || (L.nc + 255) / 256 > 0x7fffffffLL) return fail(MET2_E_UNSUPPORTED, "volume too large for one launch");
+    if (!rev && tv_gather_lds(n_te) > 64 * 1024) return fail(MET2_E_UNSUPPORTED, "more than 127 echoes: pass the volume echo-major");
+    USE_DEVICE(device);
+    hipStream_t s = (hipStream_t)stream;
+    double *F = nullptr;
+    if (!rev) HIPCHK(hipMalloc((void **)&F, sizeof(double) * (size_t)L.elems));
+    struct Free { double *p; ~Free() { if (p) (void)hipFree(p); } } guard{F};
+    if (!rev) launch_gather(L, n_te, data, F, s);
+    launch_detail(rev, n0, n1, n2, L, n_te, rev ? data : F, coef, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    return MET2_OK;
+}
+
+extern "C" int met2_tv_sigma(int32_t device, int32_t n_te, int64_t nc, const double *coef, const double *weight, double weight_factor,
+                             double *sigma, double *weight_out, int32_t *copy, void *stream)
+{
+    if (n_te < 1 || nc < 1) return fail(MET2_E_INVALID, "bad shape");
+    if (n_te > 65535) return fail(MET2_E_UNSUPPORTED, "at most 65535 echo volumes");
+    if (!coef) return fail(MET2_E_INVALID, "NULL argument");
+    USE_DEVICE(device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t state_bytes = (sizeof(TvState) * (size_t)n_te + 255) & ~(size_t)255;
+    char *W = nullptr;
+    HIPCHK(hipMalloc((void **)&W, state_bytes + sizeof(double) * (size_t)n_te));
+    struct Free { char *p; ~Free() { if (p) (void)hipFree(p); } } guard{W};
+    TvState *state = (TvState *)W;
+    double *dweight = nullptr;
+    if (weight) {
+        dweight = (double *)(W + state_bytes);
+        HIPCHK(hipMemcpyAsync(dweight, weight, sizeof(double) * n_te, hipMemcpyHostToDevice, s));
+    }
+    launch_sigma(n_te, nc, coef, state, weight_factor, dweight, s);
+    hipLaunchKernelGGL(tv_sigma_report_kernel, dim3((unsigned)((n_te + 63) / 64)), dim3(64), 0, s, (int)n_te, (const TvState *)state, sigma, weight_out, copy);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    return MET2_OK;
 }
 
 extern "C" int met2_tv_chambolle(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, int32_t echo_major,
@@ -618,13 +714,13 @@ extern "C" int met2_tv_chambolle(int32_t device, int32_t nx, int32_t ny, int32_t
     double *F = (double *)(W + L.off_F), *P0 = (double *)(W + L.off_P0), *P1 = (double *)(W + L.off_P1);
     double *coef = (double *)(W + L.off_coef), *partial = (double *)(W + L.off_partial);
     TvState *state = (TvState *)(W + L.off_state);
-    const size_t lds_t = sizeof(double) * 64 * ((size_t)n_te + 1);
+    const size_t lds_t = tv_gather_lds(n_te);
     if (!rev && lds_t > 64 * 1024) return fail(MET2_E_UNSUPPORTED, "more than 127 echoes: pass the volume echo-major");
 
     // 1. echo-major working copy
     const double *Fsrc = F;
     if (rev) Fsrc = data;                                            // already [echo][z][y][x]
-    else hipLaunchKernelGGL(tv_gather_kernel, dim3((unsigned)((L.vol + 63) / 64)), dim3(256), lds_t, s, L.vol, (int)n_te, data, F);
+    else launch_gather(L, n_te, data, F, s);
     // 2. noise level and weight per echo
     double *dweight = nullptr;
     if (weight) {
@@ -632,14 +728,8 @@ extern "C" int met2_tv_chambolle(int32_t device, int32_t nx, int32_t ny, int32_t
         HIPCHK(hipMemcpyAsync(dweight, weight, sizeof(double) * n_te, hipMemcpyHostToDevice, s));
     }
     if (!weight || sigma) {
-        TvDetailArgs D;
-        D.n0 = n0; D.n1 = n1; D.n2 = n2; D.c0 = L.c0; D.c1 = L.c1; D.c2 = L.c2; D.vol = L.vol; D.nc = L.nc; D.F = Fsrc; D.coef = coef;
-        const dim3 g((unsigned)((L.nc + 255) / 256), (unsigned)n_te);
-        if (rev) hipLaunchKernelGGL(tv_detail_kernel<true>, g, dim3(256), 0, s, D);
-        else hipLaunchKernelGGL(tv_detail_kernel<false>, g, dim3(256), 0, s, D);
-        TvSigmaArgs S;
-        S.nc = L.nc; S.coef = coef; S.state = state; S.factor = weight_factor; S.weight_in = dweight;
-        hipLaunchKernelGGL(tv_sigma_kernel, dim3((unsigned)n_te), dim3(1024), 0, s, S);
+        launch_detail(rev, n0, n1, n2, L, n_te, Fsrc, coef, s);
+        launch_sigma(n_te, L.nc, coef, state, weight_factor, dweight, s);
     } else {
         hipLaunchKernelGGL(tv_state_init_kernel, dim3((unsigned)((n_te + 63) / 64)), dim3(64), 0, s, (int)n_te, (const double *)dweight, state);
     }

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import Met2Error, check, lib
+from ._lib import Met2Error, TvGeometry, check, lib
 
 
 def _layout(data):
@@ -55,6 +55,60 @@ def tv_chambolle(data, weight=None, weight_factor=2.0, eps=2.0e-4, max_num_iter=
     if return_info:
         return res, sig.cpu().numpy(), its.cpu().numpy()
     return res
+
+
+def tv_launch_info(nx, ny, nz, nt=1, echo_major=0):
+    """How met2_tv_chambolle lays a [nx,ny,nz,nt] volume out (met2_tv_launch_info; host only, no GPU): dict of oy, step1, step2, xlen,
+    nt1, nt2, nseg, ntiles, c0, c1, c2, sigma_cap, nc -- include/met2_hip.h explains them."""
+    g = TvGeometry()
+    check(lib().met2_tv_launch_info(int(nx), int(ny), int(nz), int(nt), int(echo_major), C.byref(g)))
+    return {k: int(getattr(g, k)) for k, _ in TvGeometry._fields_}
+
+
+def tv_detail_coefficients(data, device=0):
+    """The 'ddd' db2 coefficients estimate_sigma takes its median of, for every echo volume of data [nx,ny,nz,nt] (met2_tv_detail: the
+    gather and tv_detail_kernel as met2_tv_chambolle launches them) -> [(nx+3)//2, (ny+3)//2, (nz+3)//2, nt], numpy for numpy, tensor for
+    a CUDA tensor.  A Fortran-ordered input is read in place like tv_chambolle's."""
+    as_numpy = not torch.is_tensor(data)
+    dev = torch.device("cuda", device) if as_numpy else data.device
+    if dev.type != "cuda":
+        raise Met2Error("TV denoising runs on the GPU only; there is no CPU fallback")
+    dd, echo_major = _layout(torch.as_tensor(data, dtype=torch.float64, device=dev))
+    nx, ny, nz, nt = dd.shape
+    g = tv_launch_info(nx, ny, nz, nt, echo_major)
+    coef = torch.empty((nt, g["c0"], g["c1"], g["c2"]), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().met2_tv_detail(dev.index or 0, nx, ny, nz, nt, dd.data_ptr(), echo_major, coef.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    res = coef.permute(3, 2, 1, 0) if echo_major else coef.permute(1, 2, 3, 0)      # memory axis order -> [x, y, z, echo]
+    return res.cpu().numpy() if as_numpy else res
+
+
+def tv_sigma_from_coefficients(coef, weight=None, weight_factor=2.0, device=0):
+    """tv_sigma_kernel on coefficients coef [nt, nc] (or [nc]: one echo) supplied by the caller (met2_tv_sigma) -> numpy (sigma [nt],
+    weight [nt], copy [nt] int32): median(|d|) / 0.6744897501960817 over the non-zero d, the weight tv_chambolle would use (`weight` per echo if
+    given, else weight_factor x sigma) and whether the echo would be copied through."""
+    as_numpy = not torch.is_tensor(coef)
+    dev = torch.device("cuda", device) if as_numpy else coef.device
+    if dev.type != "cuda":
+        raise Met2Error("TV denoising runs on the GPU only; there is no CPU fallback")
+    cc = torch.as_tensor(coef, dtype=torch.float64, device=dev)
+    if cc.dim() == 1:
+        cc = cc[None]
+    if cc.dim() != 2 or cc.shape[1] < 1 or cc.shape[0] < 1:
+        raise ValueError("coef must be [nt, nc]")
+    cc = cc.contiguous()
+    nt, nc = cc.shape
+    sig = torch.empty(nt, dtype=torch.float64, device=dev)
+    wout = torch.empty(nt, dtype=torch.float64, device=dev)
+    cp = torch.empty(nt, dtype=torch.int32, device=dev)
+    wp = None
+    if weight is not None:
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(weight, dtype=np.float64), (nt,)))
+        wp = w.ctypes.data_as(C.POINTER(C.c_double))
+    with torch.cuda.device(dev):
+        check(lib().met2_tv_sigma(dev.index or 0, nt, nc, cc.data_ptr(), wp, float(weight_factor), sig.data_ptr(), wout.data_ptr(), cp.data_ptr(),
+                                  torch.cuda.current_stream(dev).cuda_stream))
+    return sig.cpu().numpy(), wout.cpu().numpy(), cp.cpu().numpy()
 
 
 def tv_denoise_volume(data, weight_factor=2.0, eps=2.0e-4, max_num_iter=200, return_info=False):

@@ -53,7 +53,8 @@ def estimate_sigma(vol):
     return float(np.median(np.abs(d)) / PHI_INV_075)
 
 
-def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, return_iters=False):
+def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, return_iters=False, return_energies=False):
+    """return_energies: the list of E, one per executed iteration, is appended to what is returned."""
     image = np.asarray(image, dtype=np.float64)
     ndim = image.ndim
     p = np.zeros((ndim,) + image.shape, dtype=image.dtype)
@@ -62,6 +63,7 @@ def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, return
     out = image
     i = 0
     n_done = 0
+    energies = []
     while i < max_num_iter:
         if i > 0:
             d = -p.sum(0)                                            # minus the divergence of p
@@ -92,6 +94,7 @@ def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, return
         p -= tau * g
         p /= norm
         E /= float(image.size)
+        energies.append(float(E))
         n_done = i + 1
         if i == 0:
             E_init = E
@@ -101,7 +104,8 @@ def denoise_tv_chambolle(image, weight=0.1, eps=2.0e-4, max_num_iter=200, return
                 break
             E_previous = E
         i += 1
-    return (out, n_done) if return_iters else out
+    res = (out,) + ((n_done,) if return_iters else ()) + ((energies,) if return_energies else ())
+    return res if len(res) > 1 else out
 
 
 def tv_denoise_volume(data, weight_factor=2.0, eps=2.0e-4, max_num_iter=200, return_info=False):

@@ -105,7 +105,8 @@ def test_product_tv_has_no_cpu_fallback():
 
 
 # ---- GPU: the kernels against the restatement ---------------------------------------------------------------------------------
-def _check(vol, got, sig, its, weight=None, tol=1e-12):
+def _want(vol, weight=None):
+    """The restatement's (volumes, sigma, iteration count) per echo of vol [nx,ny,nz,nt]."""
     want, wsig, wits = [], [], []
     for t in range(vol.shape[3]):
         v = np.ascontiguousarray(vol[..., t])
@@ -113,7 +114,12 @@ def _check(vol, got, sig, its, weight=None, tol=1e-12):
         w = 2.0 * s if weight is None else float(np.broadcast_to(weight, (vol.shape[3],))[t])
         o, n = tv_oracle.denoise_tv_chambolle(v, w, return_iters=True)
         want.append(o); wsig.append(s); wits.append(n)
-    want = np.stack(want, axis=3)
+    return np.stack(want, axis=3), wsig, wits
+
+
+def _check(vol, got, sig, its, weight=None, tol=1e-12, want=None):
+    """want: _want(vol, weight) where a caller has it already (several layouts of one volume)."""
+    want, wsig, wits = _want(vol, weight) if want is None else want
     assert np.array_equal(its, np.array(wits)), (its, wits)                        # the same iteration count for every echo
     if weight is None:
         assert np.max(np.abs(sig / np.array(wsig) - 1.0)) < 1e-14, (sig, wsig)
@@ -125,9 +131,12 @@ def _check(vol, got, sig, its, weight=None, tol=1e-12):
 @pytest.mark.parametrize("shape,nt", [((20, 18, 24), 3), ((9, 37, 70), 2), ((35, 16, 64), 4), ((17, 33, 130), 1), ((3, 2, 5), 2), ((14, 11, 1), 2), ((1, 12, 9), 1),
                                       ((16, 1, 20), 2)])
 def test_hip_tv_matches_the_numpy_restatement(shape, nt):
-    """C-ordered volumes: one tile, tiles with halo rows along axis 1 (33, 37 > 15), halo lanes along axis 2 (70, 130 > 63),
-    several segments along axis 0 (35 > 16), a volume smaller than any tile, volumes with a singleton axis (a 2-D slice kept as a 3-D array:
-    scikit-image still runs its three-axis iteration with tau = 1/6 on it)."""
+    """C-ordered volumes.  A tile is 8 rows of 64 lanes and marches over segments of 16 planes; it owns all 8 rows when axis 1 fits it,
+    else 7 (the eighth is a halo), and all 64 lanes (lane 63's neighbour in the next tile is rebuilt in the wave).  So: tiles with a halo
+    row along axis 1 (16, 18, 33, 37 > 8; 11 = 7 + 4), a neighbour tile along axis 2 (70, 130 > 64), several segments along axis 0 (17, 20,
+    35 > 16), volumes smaller than one tile, volumes with a singleton axis (a 2-D slice kept as a 3-D array: scikit-image still runs its
+    three-axis iteration with tau = 1/6 on it).  tests/test_gpu_tv_kernels.py sits on the seams themselves and asserts the geometry
+    with tv_launch_info."""
     tv = importlib.import_module(PKG + ".tv")
     vol = _phantom(shape, nt, seed=sum(shape) + nt)
     got, sig, its = tv.tv_denoise_volume(vol, return_info=True)
