@@ -411,6 +411,26 @@ int met2_smooth_separable(int32_t device, int32_t nx, int32_t ny, int32_t nz, in
 int met2_nesma(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data,
                const uint8_t *mask, double *out, void *stream);
 
+/* Marchenko-Pastur PCA denoising (denoise='MPPCA'; Veraart et al., NeuroImage 2016; an extension with no counterpart in the reference).
+ * DEVICE pointers: data [nx][ny][nz][n_te] fp64 in C order, mask [nx][ny][nz] uint8 (NULL = every voxel), out [nx][ny][nz][n_te], must
+ * not alias data; out, each may be NULL: sigma [nx][ny][nz] the estimated noise level, rank [nx][ny][nz] int32 the number of signal
+ * components kept.  window = w, odd and >= 3.  For every voxel v with mask != 0:
+ *   1. the patch is the cube of side w centred on v, clipped at the volume's faces and restricted to voxels with mask != 0; N = its
+ *      voxel count (v is one of them), X = the n_te x N matrix of their decay curves, not centred; M = n_te, r = min(M, N), q = max(M, N);
+ *   2. C = X X^T, eigenvalues ev ascending with orthonormal eigenvectors; lambda_p = max(ev[M - r + p], 0) / q for p = 0..r-1 (for N < M
+ *      the lowest M - N eigenvalues are zero up to rounding and are dropped with their eigenvectors);
+ *   3. clam = 0, cut = 0, sigma2 = 0; for p = 0..r-1: clam += lambda_p, gamma = (p + 1) / q, s1 = clam / (p + 1),
+ *      s2 = (lambda_p - lambda_0) / (4 sqrt(gamma)); if s2 < s1: sigma2 = s1, cut = p + 1.  k = r - cut signal components;
+ *   4. out[v] = U_s (U_s^T x_v) with U_s the eigenvectors of the k largest eigenvalues, sigma[v] = sqrt(sigma2), rank[v] = k.
+ * mask == 0: out = 0, sigma = 0, rank = 0.  N < 2: the voxel is copied through, sigma = 0, rank = 1.  A non-finite value anywhere in the
+ * patch: copied through, sigma = 0, rank = -1.  The eigen-solver (a cyclic Jacobi, stopped when every |c_ij| <= 2^-52 sqrt(c_ii c_jj))
+ * capped at its 30 sweeps: copied through, sigma = 0, rank = -2.  The output is not clipped: the projection can undershoot zero at late echoes.
+ * MET2_E_INVALID: window even or < 3, data or out NULL, out == data.  MET2_E_UNSUPPORTED: n_te < 2 or > 63; a window whose patch list
+ * (4 w^3 bytes) does not fit in the 64 KB of LDS beside the two n_te x n_te matrices (w <= 7 fits at every n_te); more than 2^26 - 1 voxels.
+ * An empty volume returns MET2_OK at once.  Deterministic; asynchronous on `stream`. */
+int met2_mppca(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, const uint8_t *mask, int32_t window,
+               double *out, double *sigma, int32_t *rank, void *stream);
+
 /* motor:293-304, TV denoising (denoise='TV'; the reference's example pipeline runs it, example_script_run_MET2_preproc_and_recon.sh:54):
  *     for every echo volume:  sigma_est = mean(estimate_sigma(vol));  vol <- denoise_tv_chambolle(vol, weight = 2 sigma_est, eps = 2e-4,
  *                                                                                                 max_num_iter = 200)

@@ -1,5 +1,5 @@
-"""Drop-ins for motor/motor_recon_met2_real_data.py: create_Laplacian_matrix, fitting_slice_T2, the NESMA filter,
-recon_met2_arrays (the driver's steps 1-4 on in-memory arrays), motor_recon_met2 (the same with the on-disk
+"""Drop-ins for motor/motor_recon_met2_real_data.py: create_Laplacian_matrix, fitting_slice_T2, the NESMA filter, the MP-PCA filter
+(mppca_filter: an extension), recon_met2_arrays (the driver's steps 1-4 on in-memory arrays), motor_recon_met2 (the same with the on-disk
 contract) and the ROI mode (recon_met2_rois, motor_recon_met2_ROIs).  Plots and the mean-spectrum PNG are not reproduced."""
 import math
 
@@ -83,6 +83,31 @@ def nesma_filter(data, mask, device=0):
     return out.cpu().numpy() if as_numpy else out
 
 
+def mppca_filter(data, mask, window=5, device=0, return_maps=False):
+    """Marchenko-Pastur PCA denoising (Veraart et al., NeuroImage 2016; met2_mppca in include/met2_hip.h states the algorithm) on the
+    device: `data` [nx,ny,nz,nt], 2 <= nt <= 63, `mask` [nx,ny,nz]; every voxel with mask != 0 is projected on the signal subspace of
+    the decay curves of its window^3 patch (masked voxels only), all others become zero.  The output is not clipped.
+    return_maps=True: (denoised, sigma [nx,ny,nz] the noise level, rank [nx,ny,nz] int32 the components kept; -1 where the patch holds
+    a non-finite value and -2 where the eigen-solver gave up, both copied through).  numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    as_numpy = not torch.is_tensor(data)
+    dev = torch.device("cuda", device) if as_numpy else data.device
+    dd = torch.as_tensor(data, dtype=torch.float64, device=dev).contiguous()
+    if dd.dim() != 4 or tuple(np.shape(mask)) != tuple(dd.shape[:3]):
+        raise ValueError("data must be [nx,ny,nz,nt] and mask [nx,ny,nz]")
+    mk = (torch.as_tensor(mask, device=dev) != 0).to(torch.uint8).contiguous()
+    out = torch.empty_like(dd)
+    nx, ny, nz, nt = dd.shape
+    sigma = torch.empty((nx, ny, nz), dtype=torch.float64, device=dev) if return_maps else None
+    rank = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev) if return_maps else None
+    with torch.cuda.device(dev):
+        check(lib().met2_mppca(dev.index or 0, nx, ny, nz, nt, dd.data_ptr(), mk.data_ptr(), int(window), out.data_ptr(),
+                               sigma.data_ptr() if return_maps else None, rank.data_ptr() if return_maps else None,
+                               torch.cuda.current_stream(dev).cuda_stream))
+    if not return_maps:
+        return out.cpu().numpy() if as_numpy else out
+    return tuple(t.cpu().numpy() for t in (out, sigma, rank)) if as_numpy else (out, sigma, rank)
+
+
 def gaussian_smooth(data, sigma=2.0, truncate=4.0, device=0):
     """The Gaussian pre-smoothing of the FA step (motor:337-343): every echo volume of data [nx,ny,nz,nt] through the
     equivalent of scipy.ndimage.gaussian_filter(volume, sigma) (mode 'reflect', truncate 4), on the device, bit-identical
@@ -107,9 +132,10 @@ def gaussian_smooth(data, sigma=2.0, truncate=4.0, device=0):
     return out.cpu().numpy() if as_numpy else out
 
 
-def _prepare_volume(data, mask, dev, prepared, denoise):
+def _prepare_volume(data, mask, dev, prepared, denoise, maps=None):
     """The driver's preparation (motor:180-182, :279, :293-333) on the device.  The volume keeps the memory order it
-    arrives in (nibabel arrays are Fortran-ordered; the solver reads either order in place)."""
+    arrives in (nibabel arrays are Fortran-ordered; the solver reads either order in place).  denoise='MPPCA' (an extension) leaves its
+    noise map in maps['MPPCA_sigma'] when the caller hands a dict in."""
     dd = torch.as_tensor(data, dtype=torch.float64, device=dev)
     mk = torch.as_tensor(mask, device=dev)
     if not prepared:
@@ -124,6 +150,13 @@ def _prepare_volume(data, mask, dev, prepared, denoise):
                 raise ValueError("TV denoising needs data [nx,ny,nz,nt]")
             from .tv import tv_denoise_volume
             dd = tv_denoise_volume(dd)
+        elif denoise == "MPPCA":
+            if dd.dim() != 4:
+                raise ValueError("MPPCA needs data [nx,ny,nz,nt]")
+            dd, sigma, _ = mppca_filter(dd, mk, return_maps=True)
+            dd = torch.where(dd < 0.0, torch.zeros((), dtype=torch.float64, device=dev), dd)   # the projection can undershoot at late echoes
+            if maps is not None:
+                maps["MPPCA_sigma"] = sigma
     return dd, mk
 
 
@@ -153,7 +186,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
                       return_prepared=False, devices=None, bootstrap=None):
     """Steps 1-4 of motor_recon_met2 (motor:293-373, 427-472) on arrays: data [nx,ny,nz,nt] (or
     [nvox, nt]), mask [nx,ny,nz].  Mirrors the driver's preparation: data *= mask (motor:180-182),
-    negative values clipped to 0 (motor:279), optional NESMA / TV filter (motor:293-333, needs a 3-D volume),
+    negative values clipped to 0 (motor:279), optional NESMA / TV filter (motor:293-333, needs a 3-D volume) or denoise='MPPCA'
+    (mppca_filter with window 5, an extension; what it leaves below zero is set to zero; return_prepared=True then adds 'MPPCA_sigma'),
     Npc = 60 (96 for T2SPARC, motor:207-213), T2 grid 10..2000 ms, T1 = 1000 ms, 91 flip angles for brute force.
     `prepared=True` says the caller already did that preparation (mask multiply, clip, denoise).
     FA_smooth='yes' (the CLI default, motor:337-343): the flip angles are estimated on the Gaussian-smoothed volume
@@ -164,7 +198,7 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     (dist.fit_sharded); ranks other than 0 return None.
     devices=[d0, d1, ...]: ONE process drives several GPUs through the C ABI's host entry (met2_fit_host: one plan and one host thread per
     device inside the call, blocks of voxels dealt round-robin, outputs copied by every device into the same host arrays -- no
-    torch.distributed); the whole-volume filters (TV / NESMA / FA smoothing) run on devices[0] first.  Same outputs bit for bit.
+    torch.distributed); the whole-volume filters (TV / NESMA / MPPCA / FA smoothing) run on devices[0] first.  Same outputs bit for bit.
     bootstrap=dict(n_rep=100, seed=0): per-voxel bootstrap uncertainty of the metrics (Met2Plan.fit_bootstrap; an extension with no
     counterpart in the reference), on one device (devices[0]) with the pipeline's prepared data and FA indices; voxel_id is the voxel's flat
     index in the volume's C order, whatever the memory order.  Adds '<Q>_bootstrap' [vol..., 5] for Q in BOOT_QUANTITIES (BOOT_STATS along
@@ -179,8 +213,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     _bootstrap_check(boot, FA_method, FA_smooth)
     if FA_method not in ("brute-force", "spline"):
         raise ValueError("FA_method must be 'spline' or 'brute-force'")
-    if denoise not in ("None", None, "none", "NESMA", "TV"):
-        raise ValueError("denoise must be 'None', 'NESMA' or 'TV'")
+    if denoise not in ("None", None, "none", "NESMA", "TV", "MPPCA"):
+        raise ValueError("denoise must be 'None', 'NESMA', 'TV' or 'MPPCA'")
     data = np.asarray(data, dtype=np.float64)
     vol_shape = data.shape[:-1]
     nt = data.shape[-1]
@@ -195,6 +229,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
                                   denoise, FA_smooth, return_prepared or boot is not None)
         if boot is not None:
             dd = res["data_prepared"] if return_prepared else res.pop("data_prepared")
+            if not return_prepared:
+                res.pop("MPPCA_sigma", None)
             TE_array = np.asarray(TE_array, dtype=np.float64)
             plan = Met2Plan(nt, res["T2s"].shape[0], 91 * 3 if FA_method == "spline" else 91, device=devices[0], myelin_T2=myelin_T2)
             try:
@@ -208,7 +244,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
         return res
     dev = plan.device if plan is not None else torch.device("cuda", device)
     # a caller's own plan, a distributed run, or a bare voxel list: the volume on the device in one piece
-    dd, mk = _prepare_volume(data, mask, dev, prepared, denoise)
+    extra = {}
+    dd, mk = _prepare_volume(data, mask, dev, prepared, denoise, extra)
     dd_fa = dd
     if FA_smooth == "yes" and fa_index is None:
         if len(vol_shape) != 3:
@@ -242,6 +279,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
         res["T2s"] = T2s
         if return_prepared:
             res["data_prepared"] = dd.cpu().numpy()
+            for name, t in extra.items():
+                res[name] = t.cpu().numpy()
         if boot is not None:
             _bootstrap_into(res, plan, reg_method, dd, fa_vol, mm, boot, (T2s, T1s, tau, TR))
         return res
@@ -337,9 +376,10 @@ def _recon_multi_device(data, mask, TE_array, TR, reg_method, reg_matrix, FA_met
         return h.numpy()
 
     keep_alive = None
+    extra = {}                                                   # what a filter leaves beside the volume (MPPCA: its noise map)
     if filtered:
         dev0 = torch.device("cuda", devices[0])
-        dd, _ = _prepare_volume(data, mask, dev0, prepared, denoise)
+        dd, _ = _prepare_volume(data, mask, dev0, prepared, denoise, extra)
         one_device = len(set(devices)) == 1                      # the filtered volume stays where it is: met2_fit_host copies its blocks device to device
         place = (lambda t: t) if one_device else to_pinned
         if FA_smooth == "yes" and fa_index is None:
@@ -411,6 +451,8 @@ def _recon_multi_device(data, mask, TE_array, TR, reg_method, reg_matrix, FA_met
         if mvals is not None:                                     # (plain runs prepare per block inside the library)
             vol = np.maximum(vol * mvals[..., None], 0.0)
         res["data_prepared"] = vol.cpu().numpy() if torch.is_tensor(vol) else vol
+        for name, t in extra.items():
+            res[name] = t.cpu().numpy()
     return res
 
 
@@ -454,7 +496,8 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     (data [nx,ny,nz,nt], mask [nx,ny,nz]), ten NIfTI volumes out (MWF, IEWF, FWF, T2_M, T2_IE, TWC, FA, fsol_4D,
     Est_Signal, reg_param .nii.gz at path_to_save_data, motor:475-503).  `num_cores` is accepted and ignored (one
     process drives the GPU; devices=[0, 1, ...]: that one process drives all the listed GPUs through met2_fit_host).  denoise: 'None',
-    'NESMA' (motor:305-333) or 'TV' (motor:293-304).  Not reproduced: the mean-spectrum PNG of motor:377-424.
+    'NESMA' (motor:305-333), 'TV' (motor:293-304) or 'MPPCA' (an extension: mppca_filter; Data_denoised.nii.gz as for TV, and the noise
+    map MPPCA_sigma.nii.gz).  Not reproduced: the mean-spectrum PNG of motor:377-424.
     bootstrap=dict(n_rep=..., seed=...) (an extension, see recon_met2_arrays) also writes <Q>_bootstrap.nii.gz [nx,ny,nz,5] for Q in
     BOOT_QUANTITIES (BOOT_STATS along the last axis) and sigma.nii.gz; with fa='brute-force' / 'spline' also FA_bootstrap.nii.gz [nx,ny,nz,5]
     (degrees), with spectrum=True also fsol_bootstrap_{mean,std,q025,q500,q975}.nii.gz [nx,ny,nz,n_t2] each."""
@@ -465,9 +508,11 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     if data.ndim != 4 or mask.shape != data.shape[:3]:
         raise ValueError("data must be 4-D and mask must match its first three dimensions")
     res = recon_met2_arrays(data, mask, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, device=device, denoise=denoise,
-                            FA_smooth=FA_smooth, return_prepared=(denoise == "TV"), devices=devices, bootstrap=bootstrap)
-    if denoise == "TV":                                             # motor:302-303
+                            FA_smooth=FA_smooth, return_prepared=(denoise in ("TV", "MPPCA")), devices=devices, bootstrap=bootstrap)
+    if denoise in ("TV", "MPPCA"):                                  # motor:302-303
         nifti.save(nifti.NiftiImage(res.pop("data_prepared"), img.affine), path_to_save_data + "Data_denoised.nii.gz")
+    if denoise == "MPPCA":
+        nifti.save(nifti.NiftiImage(res.pop("MPPCA_sigma"), img.affine), path_to_save_data + "MPPCA_sigma.nii.gz")
     for name in ("MWF", "IEWF", "FWF", "T2_M", "T2_IE", "TWC", "FA", "fsol_4D", "Est_Signal", "reg_param"):
         nifti.save(nifti.NiftiImage(res[name], img.affine), path_to_save_data + name + ".nii.gz")
     if bootstrap is not None:
