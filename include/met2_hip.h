@@ -431,6 +431,37 @@ int met2_nesma(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te,
 int met2_mppca(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, const uint8_t *mask, int32_t window,
                double *out, double *sigma, int32_t *rank, void *stream);
 
+/* Removal of Gibbs (truncation) ringing by local sub-voxel shifts (degibbs='yes'; Kellner, Dhital, Kiselev, Reisert, MRM 2016; step 2 of the
+ * reference's example pipeline, example_script_run_MET2_preproc_and_recon.sh, which runs MRtrix's mrdegibbs there; stated here from the
+ * paper, none of MRtrix's program text is used and parity with mrdegibbs itself is unpinned).
+ * DEVICE pointers: data [nx][ny][nz][n_te] fp64 in C order; out the same shape, must not alias data; out, each may be NULL: shift_x, shift_y
+ * [nx][ny][nz][n_te] int8, the signed shift sh[j*] chosen per sample along x and along y (a diagnostic).  nshifts = nsh (MRtrix: 20),
+ * min_w = minW (1), max_w = maxW (3).  The unringing axes are x and y; every (z, echo) slice S[nx][ny] is processed on its own, in real fp64:
+ *   2-D split.  F = DFT2(S); for the frequency indices (p, q): cx = 1 + cos(2 pi p / nx), cy = 1 + cos(2 pi q / ny), Gx = cy / (cx + cy),
+ *     Gy = cx / (cx + cy), both 0 where cx + cy == 0 (the corner Nyquist term of even nx and ny).  Ix = Re IDFT2(F Gx), Iy = Re IDFT2(F Gy)
+ *     (Ix + Iy = S less that corner term).  out = U(Ix along x) + U(Iy along y).
+ *   U on a line x[0..n), indices periodic:
+ *     1. sh = [0, 1, ..., nsh, -1, ..., -nsh] (2 nsh + 1 entries), delta_j = sh[j] / (2 nsh);
+ *     2. x_j[m] = x(m + delta_j) by Fourier interpolation: x_j = IDFT(X[k] exp(2 pi i k' delta_j / n)), k' the signed frequency,
+ *        |k'| <= (n - 1) / 2 (integer division); for even n the Nyquist bin is kept as it is for j = 0 and set to zero for every other j.
+ *        In real form a circular convolution: x_j[m] = sum_l c_j[(m - l) mod n] x[l], c_j[r] = (1 / n) sum_k' cos(2 pi k' (r + delta_j) / n),
+ *        plus (1 / n) cos(pi r) for j = 0 and even n;
+ *     3. d_j[m] = |x_j[m] - x_j[m - 1]|;  TVL_j[l] = sum_{t = minW..maxW} d_j[l - t],  TVR_j[l] = sum_{t = minW..maxW} d_j[l + t + 1], each
+ *        sum formed directly in increasing t (no running window);
+ *     4. per sample l the candidates are scanned in the order (j = 0, L), (j = 0, R), (j = 1, L), (j = 1, R), ...; the first strict minimum
+ *        gives j*;
+ *     5. with delta = delta_j*, a0 = x_j*[l - 1], a1 = x_j*[l], a2 = x_j*[l + 1]:  out[l] = a1 (1 - delta) + a0 delta if delta > 0,
+ *        a1 (1 + delta) - a2 delta otherwise.
+ * A slice that holds a non-finite value is copied through unchanged (its shifts are 0); the other slices are not affected.
+ * MET2_E_INVALID: a negative dimension, nshifts < 1, min_w < 1, min_w > max_w, data or out NULL, out == data.  MET2_E_UNSUPPORTED: nshifts > 32;
+ * nx or ny outside 8..256; 2 (max_w + 1) > min(nx, ny) (at the smallest axis, 8, the default windows reach round the line and overlap); 2^31 samples or more.  All of them before any launch.  A volume with a zero-sized
+ * dimension returns MET2_OK at once (after the checks of nshifts, min_w and max_w).  MRtrix accumulates the windows with running updates, so it
+ * may pick another shift where two candidates tie within rounding.
+ * Deterministic, slice by slice independent of the rest of the volume.  BLOCKING: the entry allocates its own work space (42 bytes per sample
+ * of a chunk of at most 2^22 samples, or of one slice; plus the two axes' tables), enqueues on `stream`, waits for it and frees the space. */
+int met2_degibbs(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, int32_t nshifts, int32_t min_w,
+                 int32_t max_w, double *out, int8_t *shift_x, int8_t *shift_y, void *stream);
+
 /* motor:293-304, TV denoising (denoise='TV'; the reference's example pipeline runs it, example_script_run_MET2_preproc_and_recon.sh:54):
  *     for every echo volume:  sigma_est = mean(estimate_sigma(vol));  vol <- denoise_tv_chambolle(vol, weight = 2 sigma_est, eps = 2e-4,
  *                                                                                                 max_num_iter = 200)

@@ -7,6 +7,7 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   epg.py                    create_Dic_3D, create_met2_design_matrix_epg
   flip_angle_algorithms.py  compute_optimal_FA, fitting_slice_FA_brute_force
   motor.py                  create_Laplacian_matrix, fitting_slice_T2, recon_met2_arrays (voxel loop), nesma_filter, mppca_filter (MP-PCA denoising: csrc/met2_mppca.hip),
+                            gibbs_filter (Gibbs-ringing removal, degibbs='yes': csrc/met2_gibbs.hip),
                             gaussian_smooth, ROI mode
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
   nifti.py                  NIfTI-1 reader / writer for the driver's on-disk contract
@@ -16,3 +17,10 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
 There is no CPU fallback: without the built HIP library and a visible GPU every call raises."""
 from ._lib import Met2Error  # noqa: F401
 from .plan import BOOT_QUANTITIES, BOOT_QUANTITIES_FA, BOOT_STATS, MAP_NAMES, METHODS, PENALTIES, Met2Plan  # noqa: F401
+
+
+def __getattr__(name):
+    if name == "gibbs_filter":                 # motor.gibbs_filter, imported on first use
+        from .motor import gibbs_filter
+        return gibbs_filter
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1,0 +1,427 @@
+// met2_gibbs.hip -- met2_degibbs: removal of Gibbs (truncation) ringing by local sub-voxel shifts (Kellner, Dhital, Kiselev, Reisert, MRM 2016;
+// degibbs='yes'; step 2 of the reference's example pipeline, which runs MRtrix's mrdegibbs on the CPU).  include/met2_hip.h states the
+// algorithm; no program text of MRtrix was used.  The volume is worked on in chunks of whole (z, echo) slices, slice-major [slice][nx][ny]:
+//   gibbs_tables_kernel   per axis of length n: the DFT matrix W[b][q] = exp(-2 pi i b q / n) and the 2 nsh + 1 circular-convolution kernels
+//                         c_j[r] of the sub-voxel shifts, laid out [r][j] (j padded to a multiple of GIBBS_JB with zeros) so that a wave reads
+//                         the GIBBS_JB coefficients of one r with scalar loads;
+//   gibbs_gather_kernel   caller's [nx][ny][slices] -> [slice][nx][ny] through a 32 x 32 LDS tile; flags the slices that hold a non-finite value;
+//   gibbs_dft_rows_kernel T = S W_y               (real -> complex; GIBBS_LB rows per workgroup in LDS, one thread per output frequency)
+//   gibbs_dft_cols_kernel T <- conj(W_x) ((W_x T) . Gx)   in place, GIBBS_LB columns per workgroup in LDS; keeps the corner Nyquist term of the slice
+//   gibbs_idft_rows_kernel Ix = Re(T conj(W_y)) / (nx ny),  Iy = S - corner term - Ix     (Gx + Gy = 1 except at the corner, where both are 0)
+//   gibbs_unring_kernel   the 1-D operator U on every line of one axis: the line twice over in LDS, each thread one sample; the shifted
+//                         lines GIBBS_JB at a time as circular convolutions in registers (one LDS read per GIBBS_JB FMAs), handed to the
+//                         neighbours through LDS for the windowed total variation; the running strict minimum with its three samples stays
+//                         in registers; the y-pass adds into the x-pass's result;
+//   gibbs_scatter_kernel  back to the caller's layout, non-finite slices copied through from the gathered input.
+// Every loop is bounded by a shape or a compile-time constant; fp64 throughout.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cmath>
+
+#include "../../include/met2_hip.h"
+#include "abi_common.hpp"
+
+namespace {
+
+#define GIBBS_MIN_N 8
+#define GIBBS_MAX_N 256
+#define GIBBS_MAX_NSH 32
+#define GIBBS_JB 7                        // shifted lines per pass of the convolution: 41 = 6 * 7 - 1 at the default nsh = 20
+#define GIBBS_LB 8                        // lines per workgroup of the DFT kernels
+#define GIBBS_CHUNK_ELEMS (1 << 22)       // samples per chunk of slices: 40 B of work space each
+
+__global__ __launch_bounds__(256) void gibbs_tables_kernel(int n, int nsh, int jp, double2 *W, double *ct)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n * n) {
+        const int b = i / n, q = i - b * n;
+        const int k = (b * q) % n;                                   // < 2^16
+        double s, c;
+        sincospi(2.0 * (double)k / (double)n, &s, &c);
+        W[i] = make_double2(c, -s);
+    }
+    if (i < n * jp) {
+        const int r = i / jp, j = i - r * jp;
+        double v = 0.0;
+        if (j < 2 * nsh + 1) {
+            const int sh = j <= nsh ? j : nsh - j;
+            const int64_t num = (int64_t)r * 2 * nsh + sh;           // (r + delta_j) 2 nsh;  2 pi k' (r + delta_j) / n = pi k' num / (nsh n)
+            const int64_t per = (int64_t)2 * nsh * n;                // the cosine's period in k' num
+            double sum = 0.0;
+            for (int k = 1; k <= (n - 1) / 2; ++k) {
+                int64_t a = ((int64_t)k * num) % per;
+                if (a < 0) a += per;
+                sum += cospi((double)a / (double)(nsh * n));
+            }
+            v = (1.0 + 2.0 * sum) / (double)n;
+            if (j == 0 && n % 2 == 0) v += ((r & 1) ? -1.0 : 1.0) / (double)n;
+        }
+        ct[i] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void gibbs_gather_kernel(const double *__restrict__ data, int64_t P, int64_t ns, int64_t s0, int sc,
+                                                           double *__restrict__ W, int32_t *flag)
+{
+    __shared__ double tile[32][33];
+    const int64_t p0 = (int64_t)blockIdx.x * 32;
+    const int sb = blockIdx.y * 32;
+    for (int i = threadIdx.y; i < 32; i += 8) {
+        const int64_t p = p0 + i;
+        const int s = sb + threadIdx.x;
+        if (p < P && s < sc) {
+            const double v = data[p * ns + s0 + s];
+            tile[i][threadIdx.x] = v;
+            if (!isfinite(v)) flag[s] = 1;                            // every writer writes the same value
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.y; i < 32; i += 8) {
+        const int s = sb + i;
+        const int64_t p = p0 + threadIdx.x;
+        if (s < sc && p < P) W[(int64_t)s * P + p] = tile[threadIdx.x][i];
+    }
+}
+
+__global__ __launch_bounds__(256) void gibbs_scatter_kernel(const double *__restrict__ R, const double *__restrict__ W, const int8_t *__restrict__ sx,
+                                                            const int8_t *__restrict__ sy, const int32_t *__restrict__ flag, int64_t P, int64_t ns,
+                                                            int64_t s0, int sc, double *__restrict__ out, int8_t *__restrict__ ox,
+                                                            int8_t *__restrict__ oy)
+{
+    __shared__ double tile[32][33];
+    __shared__ int8_t tx8[32][33], ty8[32][33];
+    const int64_t p0 = (int64_t)blockIdx.x * 32;
+    const int sb = blockIdx.y * 32;
+    for (int i = threadIdx.y; i < 32; i += 8) {
+        const int s = sb + i;
+        const int64_t p = p0 + threadIdx.x;
+        if (s < sc && p < P) {
+            const bool copy = flag[s] != 0;                           // a slice with a non-finite value goes through unchanged
+            const int64_t at = (int64_t)s * P + p;
+            tile[i][threadIdx.x] = copy ? W[at] : R[at];
+            if (ox) tx8[i][threadIdx.x] = copy ? (int8_t)0 : sx[at];
+            if (oy) ty8[i][threadIdx.x] = copy ? (int8_t)0 : sy[at];
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.y; i < 32; i += 8) {
+        const int64_t p = p0 + i;
+        const int s = sb + threadIdx.x;
+        if (p < P && s < sc) {
+            const int64_t at = p * ns + s0 + s;
+            out[at] = tile[threadIdx.x][i];
+            if (ox) ox[at] = tx8[threadIdx.x][i];
+            if (oy) oy[at] = ty8[threadIdx.x][i];
+        }
+    }
+}
+
+// T[g][q] = sum_b S[g][b] Wy[b][q] for the rows g of all slices of the chunk; blockDim.x >= ny
+__global__ __launch_bounds__(256) void gibbs_dft_rows_kernel(const double *__restrict__ S, const double2 *__restrict__ Wy, int ny, int nrows,
+                                                             double2 *__restrict__ T)
+{
+    __shared__ double xr[GIBBS_LB][GIBBS_MAX_N];
+    const int g0 = blockIdx.x * GIBBS_LB;
+    for (int i = threadIdx.x; i < GIBBS_LB * ny; i += blockDim.x) {
+        const int l = i / ny, b = i - l * ny;
+        xr[l][b] = g0 + l < nrows ? S[(int64_t)(g0 + l) * ny + b] : 0.0;
+    }
+    __syncthreads();
+    const int q = threadIdx.x;
+    if (q >= ny) return;
+    double re[GIBBS_LB], im[GIBBS_LB];
+#pragma unroll
+    for (int l = 0; l < GIBBS_LB; ++l) { re[l] = 0.0; im[l] = 0.0; }
+    for (int b = 0; b < ny; ++b) {
+        const double2 w = Wy[b * ny + q];
+#pragma unroll
+        for (int l = 0; l < GIBBS_LB; ++l) {
+            const double v = xr[l][b];
+            re[l] = fma(v, w.x, re[l]);
+            im[l] = fma(v, w.y, im[l]);
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < GIBBS_LB; ++l)
+        if (g0 + l < nrows) T[(int64_t)(g0 + l) * ny + q] = make_double2(re[l], im[l]);
+}
+
+// per slice and GIBBS_LB columns: F = W_x T, F *= Gx, T <- conj(W_x) F; blockDim.x >= nx; grid (ceil(ny / LB), slices)
+__global__ __launch_bounds__(256) void gibbs_dft_cols_kernel(double2 *__restrict__ T, const double2 *__restrict__ Wx, const double2 *__restrict__ Wy,
+                                                             int nx, int ny, double *__restrict__ corner)
+{
+    __shared__ double2 tc[GIBBS_LB][GIBBS_MAX_N];
+    const int q0 = blockIdx.x * GIBBS_LB;
+    const int s = blockIdx.y;
+    double2 *Ts = T + (int64_t)s * nx * ny;
+    for (int i = threadIdx.x; i < GIBBS_LB * nx; i += blockDim.x) {
+        const int a = i / GIBBS_LB, l = i - a * GIBBS_LB;
+        tc[l][a] = q0 + l < ny ? Ts[a * ny + q0 + l] : make_double2(0.0, 0.0);
+    }
+    __syncthreads();
+    const int p = threadIdx.x;
+    const bool mine = p < nx;
+    double re[GIBBS_LB], im[GIBBS_LB];
+#pragma unroll
+    for (int l = 0; l < GIBBS_LB; ++l) { re[l] = 0.0; im[l] = 0.0; }
+    if (mine) {
+        for (int a = 0; a < nx; ++a) {
+            const double2 w = Wx[a * nx + p];
+#pragma unroll
+            for (int l = 0; l < GIBBS_LB; ++l) {
+                const double2 t = tc[l][a];
+                re[l] = fma(t.x, w.x, fma(-t.y, w.y, re[l]));
+                im[l] = fma(t.x, w.y, fma(t.y, w.x, im[l]));
+            }
+        }
+        const double cx = 1.0 + Wx[nx + p].x;                          // 1 + cos(2 pi p / nx); exactly 0 at p = nx / 2
+#pragma unroll
+        for (int l = 0; l < GIBBS_LB; ++l) {
+            const int q = q0 + l;
+            if (q < ny) {
+                const double cy = 1.0 + Wy[ny + q].x;
+                const double den = cx + cy;
+                const double gx = den == 0.0 ? 0.0 : cy / den;
+                if (2 * p == nx && 2 * q == ny) corner[s] = re[l];
+                re[l] *= gx;
+                im[l] *= gx;
+            }
+        }
+    }
+    __syncthreads();
+    if (mine) {
+#pragma unroll
+        for (int l = 0; l < GIBBS_LB; ++l) tc[l][p] = make_double2(re[l], im[l]);
+    }
+    __syncthreads();
+    if (!mine) return;
+    const int a = p;
+#pragma unroll
+    for (int l = 0; l < GIBBS_LB; ++l) { re[l] = 0.0; im[l] = 0.0; }
+    for (int pp = 0; pp < nx; ++pp) {
+        const double2 w = Wx[pp * nx + a];                            // conjugated below
+#pragma unroll
+        for (int l = 0; l < GIBBS_LB; ++l) {
+            const double2 t = tc[l][pp];
+            re[l] = fma(t.x, w.x, fma(t.y, w.y, re[l]));
+            im[l] = fma(t.y, w.x, fma(-t.x, w.y, im[l]));
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < GIBBS_LB; ++l)
+        if (q0 + l < ny) Ts[a * ny + q0 + l] = make_double2(re[l], im[l]);
+}
+
+// Ix[g][b] = Re sum_q T[g][q] conj(Wy[q][b]) / (nx ny);  Iy = S - corner / (nx ny) (-1)^(a + b) - Ix
+__global__ __launch_bounds__(256) void gibbs_idft_rows_kernel(const double2 *__restrict__ T, const double2 *__restrict__ Wy, const double *__restrict__ S,
+                                                              const double *__restrict__ corner, int nx, int ny, int nrows, double *__restrict__ Ix,
+                                                              double *__restrict__ Iy)
+{
+    __shared__ double2 vr[GIBBS_LB][GIBBS_MAX_N];
+    const int g0 = blockIdx.x * GIBBS_LB;
+    for (int i = threadIdx.x; i < GIBBS_LB * ny; i += blockDim.x) {
+        const int l = i / ny, q = i - l * ny;
+        vr[l][q] = g0 + l < nrows ? T[(int64_t)(g0 + l) * ny + q] : make_double2(0.0, 0.0);
+    }
+    __syncthreads();
+    const int b = threadIdx.x;
+    if (b >= ny) return;
+    double re[GIBBS_LB];
+#pragma unroll
+    for (int l = 0; l < GIBBS_LB; ++l) re[l] = 0.0;
+    for (int q = 0; q < ny; ++q) {
+        const double2 w = Wy[q * ny + b];
+#pragma unroll
+        for (int l = 0; l < GIBBS_LB; ++l) {
+            const double2 t = vr[l][q];
+            re[l] = fma(t.x, w.x, fma(t.y, w.y, re[l]));
+        }
+    }
+    const double scale = 1.0 / ((double)nx * (double)ny);
+#pragma unroll
+    for (int l = 0; l < GIBBS_LB; ++l) {
+        const int g = g0 + l;
+        if (g < nrows) {
+            const int s = g / nx, a = g - s * nx;
+            const int64_t at = (int64_t)g * ny + b;
+            const double ix = re[l] * scale;
+            const double cn = corner[s] * scale;
+            Ix[at] = ix;
+            Iy[at] = S[at] - (((a + b) & 1) ? -cn : cn) - ix;
+        }
+    }
+}
+
+struct UnringArgs {
+    const double *src;        // [slices][nx][ny]
+    const double *ct;         // [n][jp]
+    double *dst;              // [slices][nx][ny]
+    int8_t *shift;            // [slices][nx][ny] or NULL
+    int n;                    // the line's length
+    int nlines;               // lines in the chunk
+    int per_slice;            // lines per slice
+    int64_t slice_stride;     // nx ny
+    int line_stride;          // between the first samples of a slice's consecutive lines
+    int stride;               // between a line's samples
+    int nsh, jp, min_w, max_w;
+    int accumulate;           // dst += U(src) instead of dst = U(src)
+};
+
+// one sample per thread, 256 / n lines per workgroup (one at n > 128)
+__global__ __launch_bounds__(256) void gibbs_unring_kernel(UnringArgs A)
+{
+    __shared__ double xl[2 * GIBBS_MAX_N];                              // every line twice over: x[(m - r) mod n] = xl[base + m + n - r]
+    __shared__ double xs[GIBBS_JB][GIBBS_MAX_N];                         // the pass's shifted lines, by thread
+    const int n = A.n;
+    const int lpb = 256 / n;
+    const int t = threadIdx.x;
+    const int li = t / n, m = t - li * n;
+    const int line = blockIdx.x * lpb + li;
+    const bool active = li < lpb && line < A.nlines;
+    int64_t base = 0;
+    if (active) {
+        const int s = line / A.per_slice, o = line - s * A.per_slice;
+        base = (int64_t)s * A.slice_stride + (int64_t)o * A.line_stride + (int64_t)m * A.stride;
+    }
+    const int lb = active ? li * 2 * n : 0;                             // an idle thread walks line 0's copy and writes nothing
+    const int tb = active ? li * n : 0;
+    if (active) {
+        const double v = A.src[base];
+        xl[lb + m] = v;
+        xl[lb + n + m] = v;
+    }
+    __syncthreads();
+
+    const int nj = 2 * A.nsh + 1;
+    double best = INFINITY, a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    int jbest = 0;
+    const int mm = active ? m : 0;
+    const int ml = mm == 0 ? n - 1 : mm - 1, mr = mm == n - 1 ? 0 : mm + 1;
+    const double *xp = xl + lb + mm + n;
+    for (int j0 = 0; j0 < nj; j0 += GIBBS_JB) {
+        double acc[GIBBS_JB];
+#pragma unroll
+        for (int jj = 0; jj < GIBBS_JB; ++jj) acc[jj] = 0.0;
+        const double *__restrict__ cr = A.ct + j0;
+#pragma unroll 4
+        for (int r = 0; r < n; ++r) {
+            const double xv = xp[-r];
+#pragma unroll
+            for (int jj = 0; jj < GIBBS_JB; ++jj) acc[jj] = fma(cr[r * A.jp + jj], xv, acc[jj]);
+        }
+        __syncthreads();                                              // the previous pass's readers are done
+#pragma unroll
+        for (int jj = 0; jj < GIBBS_JB; ++jj) xs[jj][t] = acc[jj];
+        __syncthreads();
+#pragma unroll
+        for (int jj = 0; jj < GIBBS_JB; ++jj) {
+            if (j0 + jj < nj) {                                        // uniform
+                const double *xj = xs[jj] + tb;
+                double tvl = 0.0, tvr = 0.0;
+                for (int w = A.min_w; w <= A.max_w; ++w) {             // 2 (max_w + 1) <= n: one wrap at most
+                    int i1 = mm - w, i0 = mm - w - 1, k0 = mm + w, k1 = mm + w + 1;
+                    if (i1 < 0) i1 += n;
+                    if (i0 < 0) i0 += n;
+                    if (k0 >= n) k0 -= n;
+                    if (k1 >= n) k1 -= n;
+                    tvl += fabs(xj[i1] - xj[i0]);
+                    tvr += fabs(xj[k1] - xj[k0]);
+                }
+                if (tvl < best) { best = tvl; jbest = j0 + jj; a0 = xj[ml]; a1 = acc[jj]; a2 = xj[mr]; }
+                if (tvr < best) { best = tvr; jbest = j0 + jj; a0 = xj[ml]; a1 = acc[jj]; a2 = xj[mr]; }
+            }
+        }
+    }
+    if (!active) return;
+    const int sh = jbest <= A.nsh ? jbest : A.nsh - jbest;
+    const double d = (double)sh / (double)(2 * A.nsh);
+    const double o = d > 0.0 ? a1 * (1.0 - d) + a0 * d : a1 * (1.0 + d) - a2 * d;
+    A.dst[base] = A.accumulate ? A.dst[base] + o : o;
+    if (A.shift) A.shift[base] = (int8_t)sh;
+}
+
+inline int round64(int n) { return (n + 63) / 64 * 64; }
+
+}  // namespace
+
+extern "C" int met2_degibbs(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, const double *data, int32_t nshifts, int32_t min_w,
+                            int32_t max_w, double *out, int8_t *shift_x, int8_t *shift_y, void *stream)
+{
+    if (nx < 0 || ny < 0 || nz < 0 || nt < 0) return fail(MET2_E_INVALID, "bad shape");
+    if (nshifts < 1) return fail(MET2_E_INVALID, "degibbs needs at least one sub-voxel shift");
+    if (min_w < 1 || min_w > max_w) return fail(MET2_E_INVALID, "degibbs needs 1 <= minW <= maxW");
+    if (nshifts > GIBBS_MAX_NSH) return fail(MET2_E_UNSUPPORTED, "degibbs supports at most 32 sub-voxel shifts to a side");
+    const int64_t ns = (int64_t)nz * nt;
+    if (nx == 0 || ny == 0 || ns == 0) return MET2_OK;
+    if (nx < GIBBS_MIN_N || nx > GIBBS_MAX_N || ny < GIBBS_MIN_N || ny > GIBBS_MAX_N)
+        return fail(MET2_E_UNSUPPORTED, "degibbs supports 8 to 256 samples along x and y");
+    if (2 * ((int64_t)max_w + 1) > (nx < ny ? nx : ny)) return fail(MET2_E_UNSUPPORTED, "the total-variation window is too wide for the axis");
+    if (!data || !out) return fail(MET2_E_INVALID, "NULL argument");
+    if (data == out) return fail(MET2_E_INVALID, "degibbs cannot run in place");
+    if (ns > 0x7fffffffLL / ((int64_t)nx * ny)) return fail(MET2_E_UNSUPPORTED, "volume too large");
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+
+    const int64_t P = (int64_t)nx * ny;
+    int64_t scl = GIBBS_CHUNK_ELEMS / P;
+    if (scl < 1) scl = 1;
+    if (scl > ns) scl = ns;
+    if (scl > 65535) scl = 65535;                                      // the column kernel's grid.y
+    const int sc_max = (int)scl;
+    const int jp = (2 * nshifts + 1 + GIBBS_JB - 1) / GIBBS_JB * GIBBS_JB;
+    const size_t ce = (size_t)sc_max * (size_t)P;                      // samples of a chunk
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t b_W = up(ce * 8), b_T = up(ce * 16), b_I = up(ce * 8), b_sh = up(ce), b_small = up((size_t)sc_max * 8);
+    const size_t b_Wx = up((size_t)nx * nx * 16), b_Wy = up((size_t)ny * ny * 16), b_cx = up((size_t)nx * jp * 8), b_cy = up((size_t)ny * jp * 8);
+    const size_t total = b_W + b_T + 2 * b_I + 2 * b_sh + 2 * b_small + b_Wx + b_Wy + b_cx + b_cy;
+    char *work = nullptr;
+    HIPCHK(hipMalloc(&work, total));
+    char *at = work;
+    auto take = [&at](size_t b) { char *p = at; at += b; return p; };
+    double *W = (double *)take(b_W);
+    double2 *T = (double2 *)take(b_T);
+    double *Ix = (double *)take(b_I), *Iy = (double *)take(b_I);
+    int8_t *sx = (int8_t *)take(b_sh), *sy = (int8_t *)take(b_sh);
+    double *corner = (double *)take(b_small);
+    int32_t *flag = (int32_t *)take(b_small);
+    double2 *Wx = (double2 *)take(b_Wx), *Wy = (double2 *)take(b_Wy);
+    double *cx = (double *)take(b_cx), *cy = (double *)take(b_cy);
+
+    int rc = MET2_OK;
+    hipError_t err = hipSuccess;
+    auto ok = [&](hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; return err == hipSuccess; };
+    {
+        const int big_x = nx * (nx > jp ? nx : jp), big_y = ny * (ny > jp ? ny : jp);
+        hipLaunchKernelGGL(gibbs_tables_kernel, dim3((big_x + 255) / 256), dim3(256), 0, st, nx, nshifts, jp, Wx, cx);
+        hipLaunchKernelGGL(gibbs_tables_kernel, dim3((big_y + 255) / 256), dim3(256), 0, st, ny, nshifts, jp, Wy, cy);
+        ok(hipGetLastError());
+    }
+    for (int64_t s0 = 0; s0 < ns && err == hipSuccess; s0 += sc_max) {
+        const int sc = (int)(ns - s0 < sc_max ? ns - s0 : sc_max);
+        const int nrows = sc * nx;
+        if (!ok(hipMemsetAsync(corner, 0, 2 * b_small, st))) break;     // the corner terms and the flags lie side by side
+        const dim3 tg((unsigned)((P + 31) / 32), (unsigned)((sc + 31) / 32));
+        hipLaunchKernelGGL(gibbs_gather_kernel, tg, dim3(32, 8), 0, st, data, P, ns, s0, sc, W, flag);
+        hipLaunchKernelGGL(gibbs_dft_rows_kernel, dim3((nrows + GIBBS_LB - 1) / GIBBS_LB), dim3(round64(ny)), 0, st, W, Wy, ny, nrows, T);
+        hipLaunchKernelGGL(gibbs_dft_cols_kernel, dim3((ny + GIBBS_LB - 1) / GIBBS_LB, sc), dim3(round64(nx)), 0, st, T, Wx, Wy, nx, ny, corner);
+        hipLaunchKernelGGL(gibbs_idft_rows_kernel, dim3((nrows + GIBBS_LB - 1) / GIBBS_LB), dim3(round64(ny)), 0, st, T, Wy, W, corner, nx, ny,
+                           nrows, Ix, Iy);
+        UnringArgs A;
+        A.nsh = nshifts; A.jp = jp; A.min_w = min_w; A.max_w = max_w; A.slice_stride = P;
+        // along x: the lines are a slice's columns; the result overwrites Ix
+        A.src = Ix; A.dst = Ix; A.ct = cx; A.shift = shift_x ? sx : nullptr; A.n = nx; A.nlines = sc * ny; A.per_slice = ny; A.line_stride = 1;
+        A.stride = ny; A.accumulate = 0;
+        hipLaunchKernelGGL(gibbs_unring_kernel, dim3((A.nlines + 256 / nx - 1) / (256 / nx)), dim3(256), 0, st, A);
+        // along y: the rows; added to the x-pass's result
+        A.src = Iy; A.dst = Ix; A.ct = cy; A.shift = shift_y ? sy : nullptr; A.n = ny; A.nlines = nrows; A.per_slice = nx; A.line_stride = ny;
+        A.stride = 1; A.accumulate = 1;
+        hipLaunchKernelGGL(gibbs_unring_kernel, dim3((A.nlines + 256 / ny - 1) / (256 / ny)), dim3(256), 0, st, A);
+        hipLaunchKernelGGL(gibbs_scatter_kernel, tg, dim3(32, 8), 0, st, Ix, W, sx, sy, flag, P, ns, s0, sc, out, shift_x, shift_y);
+        ok(hipGetLastError());
+    }
+    ok(hipStreamSynchronize(st));                                       // the work space goes back before the call returns
+    if (err != hipSuccess) rc = fail(MET2_E_HIP, std::string("met2_degibbs: ") + hipGetErrorString(err));
+    (void)hipFree(work);
+    return rc;
+}

@@ -1,5 +1,5 @@
 """Drop-ins for motor/motor_recon_met2_real_data.py: create_Laplacian_matrix, fitting_slice_T2, the NESMA filter, the MP-PCA filter
-(mppca_filter: an extension), recon_met2_arrays (the driver's steps 1-4 on in-memory arrays), motor_recon_met2 (the same with the on-disk
+(mppca_filter: an extension), the Gibbs-ringing filter (gibbs_filter: the mrdegibbs step of the reference's example script), recon_met2_arrays (the driver's steps 1-4 on in-memory arrays), motor_recon_met2 (the same with the on-disk
 contract) and the ROI mode (recon_met2_rois, motor_recon_met2_ROIs).  Plots and the mean-spectrum PNG are not reproduced."""
 import math
 
@@ -108,6 +108,44 @@ def mppca_filter(data, mask, window=5, device=0, return_maps=False):
     return tuple(t.cpu().numpy() for t in (out, sigma, rank)) if as_numpy else (out, sigma, rank)
 
 
+def gibbs_filter(data, nshifts=20, minW=1, maxW=3, device=0, return_shifts=False):
+    """Removal of Gibbs (truncation) ringing by local sub-voxel shifts (Kellner et al., MRM 2016; met2_degibbs in include/met2_hip.h states
+    the algorithm) on the device: every (z, echo) slice of `data` [nx,ny,nz,nt] is unrung along x and y, 8 <= nx, ny <= 256.  The defaults
+    are those of MRtrix's mrdegibbs, which the reference's example script runs at this place; parity with mrdegibbs itself is unpinned.  A
+    slice that holds a non-finite value is copied through.  The output is not clipped: it can undershoot zero next to an edge.
+    return_shifts=True: (unrung, shift_x, shift_y), the int8 shifts (in units of 1 / (2 nshifts) voxel) chosen per sample along each axis.
+    numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    as_numpy = not torch.is_tensor(data)
+    dev = torch.device("cuda", device) if as_numpy else data.device
+    dd = torch.as_tensor(data, dtype=torch.float64, device=dev).contiguous()
+    if dd.dim() != 4:
+        raise ValueError("data must be [nx,ny,nz,nt]")
+    out = torch.empty_like(dd)
+    nx, ny, nz, nt = dd.shape
+    sx = torch.empty(dd.shape, dtype=torch.int8, device=dev) if return_shifts else None
+    sy = torch.empty(dd.shape, dtype=torch.int8, device=dev) if return_shifts else None
+    with torch.cuda.device(dev):
+        check(lib().met2_degibbs(dev.index or 0, nx, ny, nz, nt, dd.data_ptr(), int(nshifts), int(minW), int(maxW), out.data_ptr(),
+                                 sx.data_ptr() if return_shifts else None, sy.data_ptr() if return_shifts else None,
+                                 torch.cuda.current_stream(dev).cuda_stream))
+    if not return_shifts:
+        return out.cpu().numpy() if as_numpy else out
+    return tuple(t.cpu().numpy() for t in (out, sx, sy)) if as_numpy else (out, sx, sy)
+
+
+def _degibbs_first(data, degibbs, prepared, device):
+    """degibbs='yes' of the drivers: the raw volume through gibbs_filter, before anything else -> the volume to go on with"""
+    if degibbs not in ("no", "yes"):
+        raise ValueError("degibbs must be 'no' or 'yes'")
+    if degibbs == "no":
+        return data
+    if prepared:
+        raise ValueError("degibbs='yes' works on the raw volume and does not go with prepared=True")
+    if np.ndim(data) != 4:
+        raise ValueError("degibbs='yes' needs data [nx,ny,nz,nt]")
+    return gibbs_filter(np.asarray(data, dtype=np.float64), device=device)
+
+
 def gaussian_smooth(data, sigma=2.0, truncate=4.0, device=0):
     """The Gaussian pre-smoothing of the FA step (motor:337-343): every echo volume of data [nx,ny,nz,nt] through the
     equivalent of scipy.ndimage.gaussian_filter(volume, sigma) (mode 'reflect', truncate 4), on the device, bit-identical
@@ -183,13 +221,18 @@ def _estimate_fa(plan, dd_fa, mm, FA_method, fa_index, T2s, T1s, tau, TR, alpha_
 
 def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2", FA_method="brute-force", myelin_T2=40.0,
                       fa_index=None, device=0, plan=None, denoise="None", prepared=False, FA_smooth="no", distributed=False,
-                      return_prepared=False, devices=None, bootstrap=None):
+                      return_prepared=False, devices=None, bootstrap=None, degibbs="no"):
     """Steps 1-4 of motor_recon_met2 (motor:293-373, 427-472) on arrays: data [nx,ny,nz,nt] (or
     [nvox, nt]), mask [nx,ny,nz].  Mirrors the driver's preparation: data *= mask (motor:180-182),
     negative values clipped to 0 (motor:279), optional NESMA / TV filter (motor:293-333, needs a 3-D volume) or denoise='MPPCA'
     (mppca_filter with window 5, an extension; what it leaves below zero is set to zero; return_prepared=True then adds 'MPPCA_sigma'),
     Npc = 60 (96 for T2SPARC, motor:207-213), T2 grid 10..2000 ms, T1 = 1000 ms, 91 flip angles for brute force.
     `prepared=True` says the caller already did that preparation (mask multiply, clip, denoise).
+    degibbs='yes' (step 2 of the reference's example script, which runs MRtrix's mrdegibbs there): the raw volume goes through gibbs_filter
+    first -- before the mask multiply, the clip and any denoise, so the clip also removes what the unringing leaves below zero; needs data
+    [nx,ny,nz,nt]; ValueError with prepared=True; on the devices=[...] path it runs on devices[0], under distributed=True on every rank's own
+    copy (it is deterministic).  MRtrix recommends MP-PCA denoising BEFORE unringing: a caller who wants that order calls mppca_filter and
+    gibbs_filter themselves and passes prepared=True.  degibbs='no' (default) changes nothing.
     FA_smooth='yes' (the CLI default, motor:337-343): the flip angles are estimated on the Gaussian-smoothed volume
     (sigma = 2 voxels, every echo), the spectra on the unsmoothed one; needs a 3-D volume.
     C- and Fortran-ordered volumes (nibabel's) are both read in place.
@@ -215,6 +258,7 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
         raise ValueError("FA_method must be 'spline' or 'brute-force'")
     if denoise not in ("None", None, "none", "NESMA", "TV", "MPPCA"):
         raise ValueError("denoise must be 'None', 'NESMA', 'TV' or 'MPPCA'")
+    data = _degibbs_first(data, degibbs, prepared, devices[0] if devices else plan.device.index or 0 if plan is not None else device)
     data = np.asarray(data, dtype=np.float64)
     vol_shape = data.shape[:-1]
     nt = data.shape[-1]
@@ -491,13 +535,14 @@ def _recon_sharded(plan, dd, dd_fa, mm, reg_method, FA_method, fa_index, T2s, T1
 
 
 def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR, reg_method, reg_matrix, denoise, FA_method,
-                     FA_smooth, myelin_T2, num_cores=-1, device=0, devices=None, bootstrap=None):
+                     FA_smooth, myelin_T2, num_cores=-1, device=0, devices=None, bootstrap=None, degibbs="no"):
     """Drop-in for motor_recon_met2 (motor:165-506) with the reference's on-disk contract: NIfTI in
     (data [nx,ny,nz,nt], mask [nx,ny,nz]), ten NIfTI volumes out (MWF, IEWF, FWF, T2_M, T2_IE, TWC, FA, fsol_4D,
     Est_Signal, reg_param .nii.gz at path_to_save_data, motor:475-503).  `num_cores` is accepted and ignored (one
     process drives the GPU; devices=[0, 1, ...]: that one process drives all the listed GPUs through met2_fit_host).  denoise: 'None',
     'NESMA' (motor:305-333), 'TV' (motor:293-304) or 'MPPCA' (an extension: mppca_filter; Data_denoised.nii.gz as for TV, and the noise
-    map MPPCA_sigma.nii.gz).  Not reproduced: the mean-spectrum PNG of motor:377-424.
+    map MPPCA_sigma.nii.gz).  degibbs='yes' (see recon_met2_arrays): the raw volume is unrung first (gibbs_filter) and written as
+    Data_degibbs.nii.gz.  Not reproduced: the mean-spectrum PNG of motor:377-424.
     bootstrap=dict(n_rep=..., seed=...) (an extension, see recon_met2_arrays) also writes <Q>_bootstrap.nii.gz [nx,ny,nz,5] for Q in
     BOOT_QUANTITIES (BOOT_STATS along the last axis) and sigma.nii.gz; with fa='brute-force' / 'spline' also FA_bootstrap.nii.gz [nx,ny,nz,5]
     (degrees), with spectrum=True also fsol_bootstrap_{mean,std,q025,q500,q975}.nii.gz [nx,ny,nz,n_t2] each."""
@@ -507,6 +552,9 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     mask = nifti.load(path_to_mask).get_fdata().astype(np.int64)
     if data.ndim != 4 or mask.shape != data.shape[:3]:
         raise ValueError("data must be 4-D and mask must match its first three dimensions")
+    if degibbs != "no":
+        data = _degibbs_first(data, degibbs, False, devices[0] if devices else device)
+        nifti.save(nifti.NiftiImage(data, img.affine), path_to_save_data + "Data_degibbs.nii.gz")
     res = recon_met2_arrays(data, mask, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, device=device, denoise=denoise,
                             FA_smooth=FA_smooth, return_prepared=(denoise in ("TV", "MPPCA")), devices=devices, bootstrap=bootstrap)
     if denoise in ("TV", "MPPCA"):                                  # motor:302-303
@@ -573,13 +621,14 @@ def recon_met2_rois(data, rois, fa_index, Dic_3D, T2s, Laplac, factor=1.01, myel
 
 
 def motor_recon_met2_ROIs(TE_array, path_to_data, path_to_mask, path_to_ROIs, path_to_save_data, TR, reg_matrix, denoise, FA_method,
-                          FA_smooth, myelin_T2, num_cores=-1, device=0):
+                          FA_smooth, myelin_T2, num_cores=-1, device=0, degibbs="no"):
     """Drop-in for motor_recon_met2_ROIs (motor/motor_recon_met2_real_data_ROI.py:152-498): NIfTI data, mask and ROI labels in;
     flip angles per voxel (step 2), then one X2 fit (factor 1.01, :417) per ROI on the ROI's mean signal and mean kernel.
     Writes the reference's tables: table_MWF.csv, table_Spectra.csv, ROI_labels.csv at path_to_save_data and
     ROI_<label>/table_values.csv per ROI (:476-498; the PNG plots and the tabulate text table are not reproduced).
     Labels are taken from the ROI volume before the mask is applied, as the reference does (:175-178); a label that lies
-    entirely outside the mask has no voxels and the reference's nnls_x2 raises ValueError on its nan kernel -- so does this."""
+    entirely outside the mask has no voxels and the reference's nnls_x2 raises ValueError on its nan kernel -- so does this.
+    degibbs='yes': the raw volume is unrung first (gibbs_filter; see recon_met2_arrays)."""
     import os
     from . import nifti
     img = nifti.load(path_to_data)
@@ -595,6 +644,7 @@ def motor_recon_met2_ROIs(TE_array, path_to_data, path_to_mask, path_to_ROIs, pa
     labels_all = labels_all[labels_all != 0]
     rois = rois * mask                                              # :191
     dev = torch.device("cuda", device)
+    data = _degibbs_first(data, degibbs, False, device)
     dd, mk = _prepare_volume(data, mask, dev, False, denoise)
     dd_fa = gaussian_smooth(dd, 2.0) if FA_smooth == "yes" else dd
     TE_array = np.asarray(TE_array, dtype=np.float64)
