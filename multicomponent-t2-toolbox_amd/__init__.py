@@ -8,6 +8,7 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   flip_angle_algorithms.py  compute_optimal_FA, fitting_slice_FA_brute_force
   motor.py                  create_Laplacian_matrix, fitting_slice_T2, recon_met2_arrays (voxel loop), nesma_filter, mppca_filter (MP-PCA denoising: csrc/met2_mppca.hip),
                             gibbs_filter (Gibbs-ringing removal, degibbs='yes': csrc/met2_gibbs.hip),
+                            bias_field_filter (bias-field correction of the TWC map, bias_correct='yes': csrc/met2_bias.hip),
                             gaussian_smooth, ROI mode
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
   nifti.py                  NIfTI-1 reader / writer for the driver's on-disk contract
@@ -23,4 +24,7 @@ def __getattr__(name):
     if name == "gibbs_filter":                 # motor.gibbs_filter, imported on first use
         from .motor import gibbs_filter
         return gibbs_filter
+    if name == "bias_field_filter":            # motor.bias_field_filter, likewise
+        from .motor import bias_field_filter
+        return bias_field_filter
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1,0 +1,562 @@
+// met2_bias.hip -- met2_bias_field: bias-field correction of a 3-D map (bias_correct='yes'; step 5 of the reference's example pipeline, which
+// runs FSL's fast on the total water content map on the CPU).  The EM estimator of Wells et al. (IEEE TMI 1996) and Guillemaud & Brady
+// (1997), the one FAST iterates, without FAST's Markov random field term; include/met2_hip.h states the algorithm; no program text of FSL was
+// used.  The host reads nothing back: every launch of the call is enqueued up front, and the domain's size, the histogram, the class
+// parameters and the mean of b stay in a small device record (BiasStats) that the kernels read.
+//   bias_log_kernel       y = log v on the domain, the domain flags, the number of domain voxels per chunk of 1024 voxels
+//   bias_scan_kernel      exclusive scan of those counts (one workgroup) -> N
+//   bias_compact_kernel   the domain's voxel indices in memory order: idx[0..N)
+// Every fp64 sum over the domain runs over that compacted list, BIAS_CHUNK entries per workgroup in a fixed order (a thread's four entries,
+// a butterfly over the wave, the four waves), one partial per chunk; a one-workgroup second stage adds the partials in a fixed order.  So a
+// sum depends on the domain's values in memory order alone: not on the grid, and not on where the domain lies in the volume.
+//   bias_stat1_kernel / bias_stat1_final    lo, hi, mean of y
+//   bias_stat2_kernel / bias_init_kernel    256-bin histogram (integer atomics, LDS then global), variance -> the initial classes
+//   bias_estep_kernel<false> / bias_mstep_kernel   posteriors and the 3 K sums of the M-step (s, sum p u, sum p (u - mu)^2 about the OLD mean;
+//                         the second stage moves it to the new one: sum p (u - mu')^2 = sum p (u - mu)^2 - s (mu' - mu)^2)
+//   bias_estep_kernel<true>   the posteriors once more, R and W written as one (R, W) pair per voxel
+//   bias_smooth_kernel    one axis of the separable Gaussian on both channels: a tile of 64 samples along the axis by 16 lines with its halo
+//                         of r samples either side in LDS, zeros outside the volume, taps in ascending order, weights from scalar loads
+//   bias_update_kernel, bias_bmean_kernel / bias_bmean_final, bias_recentre_kernel, bias_apply_kernel
+// Every loop is bounded by a shape or a compile-time constant; fp64 throughout.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cmath>
+#include <vector>
+
+#include "../../include/met2_hip.h"
+#include "abi_common.hpp"
+
+namespace {
+
+#define BIAS_MAX_K 8
+#define BIAS_MAX_R 64
+#define BIAS_NBINS 256
+#define BIAS_CHUNK 1024                   // entries per partial sum: 256 threads x 4
+#define BIAS_TA 64                        // samples of a smoothing tile along the axis
+#define BIAS_TC 16                        // lines of a smoothing tile
+#define BIAS_VAR_FLOOR 1e-6
+
+struct BiasStats {
+    int32_t N, degenerate;                // |domain|; N == 0 or hi == lo
+    double lo, hi, mean, bmean;
+    double mu[BIAS_MAX_K], var[BIAS_MAX_K], pi[BIAS_MAX_K], lc[BIAS_MAX_K];     // lc = log pi - log(var) / 2
+    uint32_t hist[BIAS_NBINS];
+};
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);          // every lane adds the same two numbers: the same bits in all lanes
+    return v;
+}
+
+// the sum over a workgroup of 256 threads in a fixed order, returned to every thread; red: 4 doubles of LDS
+__device__ __forceinline__ double block_sum(double v, double *red)
+{
+    v = wave_sum(v);
+    __syncthreads();                                                  // the previous call's readers are done
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// inclusive scan over the 256 threads; sc: 256 ints of LDS
+__device__ __forceinline__ int block_scan(int x, int *sc)
+{
+    const int t = threadIdx.x;
+    __syncthreads();
+    sc[t] = x;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const int a = t >= d ? sc[t - d] : 0;
+        __syncthreads();
+        sc[t] += a;
+        __syncthreads();
+    }
+    return sc[t];
+}
+
+// the second stage's fixed-order sum of np partials (stride 1), by one workgroup
+__device__ __forceinline__ double partial_sum(const double *part, int np, double *red)
+{
+    double a = 0.0;
+    for (int p = threadIdx.x; p < np; p += 256) a += part[p];
+    return block_sum(a, red);
+}
+
+__global__ __launch_bounds__(256) void bias_log_kernel(const double *__restrict__ v, const uint8_t *__restrict__ mask, int64_t n,
+                                                       double *__restrict__ y, uint8_t *__restrict__ dom, int32_t *__restrict__ cnt)
+{
+    __shared__ int sc[256];
+    const int64_t base = (int64_t)blockIdx.x * BIAS_CHUNK + threadIdx.x * 4;
+    int c = 0;
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i = base + j;
+        if (i < n) {
+            const double val = v[i];
+            const bool ok = (!mask || mask[i] != 0) && isfinite(val) && val > 0.0;
+            y[i] = ok ? log(val) : 0.0;
+            dom[i] = ok ? 1 : 0;
+            c += ok ? 1 : 0;
+        }
+    }
+    const int tot = block_scan(c, sc);
+    if (threadIdx.x == 255) cnt[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(256) void bias_scan_kernel(const int32_t *__restrict__ cnt, int nchunks, int32_t *__restrict__ off, BiasStats *st)
+{
+    __shared__ int sc[256];
+    int running = 0;
+    for (int b0 = 0; b0 < nchunks; b0 += 256) {
+        const int p = b0 + threadIdx.x;
+        const int x = p < nchunks ? cnt[p] : 0;
+        const int inc = block_scan(x, sc);
+        if (p < nchunks) off[p] = running + inc - x;
+        running += sc[255];
+    }
+    if (threadIdx.x == 0) st->N = running;
+}
+
+__global__ __launch_bounds__(256) void bias_compact_kernel(const uint8_t *__restrict__ dom, int64_t n, const int32_t *__restrict__ off,
+                                                           int32_t *__restrict__ idx)
+{
+    __shared__ int sc[256];
+    const int64_t base = (int64_t)blockIdx.x * BIAS_CHUNK + threadIdx.x * 4;
+    bool f[4];
+    int c = 0;
+    for (int j = 0; j < 4; ++j) {
+        f[j] = base + j < n && dom[base + j] != 0;
+        c += f[j] ? 1 : 0;
+    }
+    int pos = off[blockIdx.x] + block_scan(c, sc) - c;               // < N <= n: the counts are those bias_log_kernel made from the same flags
+    for (int j = 0; j < 4; ++j)
+        if (f[j]) idx[pos++] = (int32_t)(base + j);
+}
+
+// partials of chunk c of the compacted list: min, max and sum of y
+__global__ __launch_bounds__(256) void bias_stat1_kernel(const double *__restrict__ y, const int32_t *__restrict__ idx, const BiasStats *st,
+                                                         int pstride, double *__restrict__ part)
+{
+    __shared__ double red[4];
+    const int N = st->N;
+    const int64_t c0 = (int64_t)blockIdx.x * BIAS_CHUNK;
+    if (c0 >= N) return;
+    double mn = INFINITY, mx = -INFINITY, s = 0.0;
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i = c0 + j * 256 + threadIdx.x;
+        if (i < N) {
+            const double val = y[idx[i]];
+            mn = fmin(mn, val);
+            mx = fmax(mx, val);
+            s += val;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        mn = fmin(mn, __shfl_xor(mn, o));
+        mx = fmax(mx, __shfl_xor(mx, o));
+    }
+    __shared__ double rmn[4], rmx[4];
+    if ((threadIdx.x & 63) == 0) { rmn[threadIdx.x >> 6] = mn; rmx[threadIdx.x >> 6] = mx; }
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = fmin(fmin(rmn[0], rmn[1]), fmin(rmn[2], rmn[3]));
+        part[pstride + blockIdx.x] = fmax(fmax(rmx[0], rmx[1]), fmax(rmx[2], rmx[3]));
+        part[2 * pstride + blockIdx.x] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void bias_stat1_final(const double *__restrict__ part, int pstride, BiasStats *st)
+{
+    __shared__ double red[4];
+    __shared__ double rmn[256], rmx[256];
+    const int N = st->N;
+    const int np = (int)(((int64_t)N + BIAS_CHUNK - 1) / BIAS_CHUNK);
+    double mn = INFINITY, mx = -INFINITY;
+    for (int p = threadIdx.x; p < np; p += 256) {
+        mn = fmin(mn, part[p]);
+        mx = fmax(mx, part[pstride + p]);
+    }
+    rmn[threadIdx.x] = mn;
+    rmx[threadIdx.x] = mx;
+    const double s = partial_sum(part + 2 * pstride, np, red);
+    if (threadIdx.x == 0) {
+        for (int t = 1; t < 256; ++t) { mn = fmin(mn, rmn[t]); mx = fmax(mx, rmx[t]); }
+        const bool deg = N == 0 || mx == mn;
+        st->lo = N == 0 ? 0.0 : mn;
+        st->hi = N == 0 ? 0.0 : mx;
+        st->mean = N == 0 ? 0.0 : s / (double)N;
+        st->bmean = 0.0;
+        st->degenerate = deg ? 1 : 0;
+    }
+}
+
+// the histogram of y over [lo, hi] and the partials of sum (y - mean)^2
+__global__ __launch_bounds__(256) void bias_stat2_kernel(const double *__restrict__ y, const int32_t *__restrict__ idx, BiasStats *st,
+                                                         double *__restrict__ part)
+{
+    __shared__ double red[4];
+    __shared__ uint32_t lh[BIAS_NBINS];
+    const int N = st->N;
+    const int64_t c0 = (int64_t)blockIdx.x * BIAS_CHUNK;
+    if (st->degenerate || c0 >= N) return;
+    const double lo = st->lo, hi = st->hi, mean = st->mean;
+    lh[threadIdx.x] = 0;
+    __syncthreads();
+    double ss = 0.0;
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i = c0 + j * 256 + threadIdx.x;
+        if (i < N) {
+            const double val = y[idx[i]];
+            int bin = (int)floor((val - lo) / (hi - lo) * (double)BIAS_NBINS);
+            bin = bin < 0 ? 0 : bin > BIAS_NBINS - 1 ? BIAS_NBINS - 1 : bin;
+            atomicAdd(&lh[bin], 1u);
+            const double d = val - mean;
+            ss += d * d;
+        }
+    }
+    ss = block_sum(ss, red);                                          // its barriers also close the LDS histogram
+    if (threadIdx.x == 0) part[blockIdx.x] = ss;
+    if (lh[threadIdx.x]) atomicAdd(&st->hist[threadIdx.x], lh[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(256) void bias_init_kernel(const double *__restrict__ part, BiasStats *st, int K)
+{
+    __shared__ double red[4];
+    const int N = st->N;
+    const int np = (int)(((int64_t)N + BIAS_CHUNK - 1) / BIAS_CHUNK);
+    const bool deg = st->degenerate != 0;
+    const double ss = deg ? 0.0 : partial_sum(part, np, red);        // deg is uniform
+    if (threadIdx.x != 0) return;
+    const double lo = st->lo, hi = st->hi;
+    if (deg) {
+        for (int k = 0; k < K; ++k) { st->mu[k] = lo; st->var[k] = 0.0; st->pi[k] = 1.0 / (double)K; st->lc[k] = 0.0; }
+        return;
+    }
+    const double var = ss / (double)N / (double)(K * K);
+    const double pi = 1.0 / (double)K;
+    uint32_t c = 0;
+    int k = 0;
+    for (int j = 0; j < BIAS_NBINS && k < K; ++j) {
+        c += st->hist[j];
+        while (k < K && (double)c >= (double)(2 * k + 1) / (2.0 * (double)K) * (double)N) {
+            st->mu[k] = lo + ((double)j + 0.5) * (hi - lo) / (double)BIAS_NBINS;
+            st->var[k] = var;
+            st->pi[k] = pi;
+            st->lc[k] = log(pi) - 0.5 * log(var);
+            ++k;
+        }
+    }
+}
+
+// E-step over chunk c of the compacted list.  FINAL = false: the partials of the M-step's 3 K sums, slot k, 8 + k, 16 + k at stride pstride.
+// FINAL = true: R and W of the voxel instead.
+template <bool FINAL>
+__global__ __launch_bounds__(256) void bias_estep_kernel(const double *__restrict__ y, const double *__restrict__ b, const int32_t *__restrict__ idx,
+                                                         const BiasStats *__restrict__ st, int K, int pstride, double *__restrict__ part,
+                                                         double2 *__restrict__ RW)
+{
+    __shared__ double red[4];
+    const int N = st->N;
+    const int64_t c0 = (int64_t)blockIdx.x * BIAS_CHUNK;
+    if (st->degenerate || c0 >= N) return;
+    double mu[BIAS_MAX_K], var[BIAS_MAX_K], lc[BIAS_MAX_K];
+#pragma unroll
+    for (int k = 0; k < BIAS_MAX_K; ++k) {
+        mu[k] = k < K ? st->mu[k] : 0.0;
+        var[k] = k < K ? st->var[k] : 1.0;
+        lc[k] = k < K ? st->lc[k] : -INFINITY;
+    }
+    double s0[BIAS_MAX_K], s1[BIAS_MAX_K], s2[BIAS_MAX_K];
+#pragma unroll
+    for (int k = 0; k < BIAS_MAX_K; ++k) { s0[k] = 0.0; s1[k] = 0.0; s2[k] = 0.0; }
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i = c0 + j * 256 + threadIdx.x;
+        if (i < N) {
+            const int32_t at = idx[i];
+            const double u = y[at] - b[at];
+            double l[BIAS_MAX_K], m = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < BIAS_MAX_K; ++k) {
+                const double d = u - mu[k];
+                l[k] = lc[k] - d * d / (2.0 * var[k]);                // -inf for a class that is not there or has pi = 0
+                m = fmax(m, l[k]);
+            }
+            double se = 0.0;
+#pragma unroll
+            for (int k = 0; k < BIAS_MAX_K; ++k) {
+                l[k] = k < K ? exp(l[k] - m) : 0.0;
+                se += l[k];
+            }
+            double r = 0.0, w = 0.0;
+#pragma unroll
+            for (int k = 0; k < BIAS_MAX_K; ++k) {
+                if (k < K) {
+                    const double p = l[k] / se, d = u - mu[k];
+                    if (FINAL) {
+                        r += p * d / var[k];
+                        w += p / var[k];
+                    } else {
+                        s0[k] += p;
+                        s1[k] += p * u;
+                        s2[k] += p * d * d;
+                    }
+                }
+            }
+            if (FINAL) RW[at] = make_double2(r, w);
+        }
+    }
+    if (FINAL) return;
+#pragma unroll
+    for (int k = 0; k < BIAS_MAX_K; ++k) {
+        if (k < K) {                                                  // uniform
+            const double a0 = block_sum(s0[k], red), a1 = block_sum(s1[k], red), a2 = block_sum(s2[k], red);
+            if (threadIdx.x == 0) {
+                part[(int64_t)k * pstride + blockIdx.x] = a0;
+                part[(int64_t)(BIAS_MAX_K + k) * pstride + blockIdx.x] = a1;
+                part[(int64_t)(2 * BIAS_MAX_K + k) * pstride + blockIdx.x] = a2;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void bias_mstep_kernel(const double *__restrict__ part, int pstride, BiasStats *st, int K)
+{
+    __shared__ double red[4];
+    if (st->degenerate) return;
+    const int N = st->N;
+    const int np = (int)(((int64_t)N + BIAS_CHUNK - 1) / BIAS_CHUNK);
+    for (int k = 0; k < K; ++k) {
+        const double s = partial_sum(part + (int64_t)k * pstride, np, red);
+        const double a = partial_sum(part + (int64_t)(BIAS_MAX_K + k) * pstride, np, red);
+        const double q = partial_sum(part + (int64_t)(2 * BIAS_MAX_K + k) * pstride, np, red);
+        if (threadIdx.x == 0) {
+            if (s == 0.0) {                                           // the class keeps its mean and variance and is never seen again
+                st->pi[k] = 0.0;
+                st->lc[k] = -INFINITY;
+            } else {
+                const double mo = st->mu[k], mn = a / s, dm = mn - mo;
+                const double var = fmax(q / s - dm * dm, BIAS_VAR_FLOOR);
+                const double pi = s / (double)N;
+                st->mu[k] = mn;
+                st->var[k] = var;
+                st->pi[k] = pi;
+                st->lc[k] = log(pi) - 0.5 * log(var);
+            }
+        }
+    }
+}
+
+struct SmoothArgs {
+    const double2 *src;
+    double2 *dst;
+    const double *w;                      // [2 r + 1]
+    int r;
+    int A, C, O;                          // the axis' length, the lines of one slab, the slabs
+    int64_t sa, sc, so;                   // their strides
+};
+
+// AXIS_FAST: the axis is the contiguous one (z); the tile then lies in LDS line by line, otherwise sample by sample, so that a wave's lanes
+// read and write consecutive addresses in both memories either way.  Tiles are numbered along blockIdx.x: at most one per voxel.
+template <bool AXIS_FAST>
+__global__ __launch_bounds__(256) void bias_smooth_kernel(SmoothArgs P)
+{
+    __shared__ double2 tile[(BIAS_TA + 2 * BIAS_MAX_R) * BIAS_TC];
+    const int nta = (P.A + BIAS_TA - 1) / BIAS_TA, ntc = (P.C + BIAS_TC - 1) / BIAS_TC;
+    int bid = blockIdx.x;
+    const int ta = bid % nta;
+    bid /= nta;
+    const int tc = bid % ntc, o = bid / ntc;
+    const int a0 = ta * BIAS_TA, c0 = tc * BIAS_TC;
+    const int rows = BIAS_TA + 2 * P.r;                               // <= BIAS_TA + 2 BIAS_MAX_R: r is checked by the entry
+    const double2 *src = P.src + (int64_t)o * P.so;
+    double2 *dst = P.dst + (int64_t)o * P.so;
+    for (int e = threadIdx.x; e < rows * BIAS_TC; e += 256) {
+        const int ia = AXIS_FAST ? e % rows : e / BIAS_TC, ic = AXIS_FAST ? e / rows : e % BIAS_TC;
+        const int a = a0 - P.r + ia, c = c0 + ic;
+        tile[e] = a >= 0 && a < P.A && c < P.C ? src[(int64_t)a * P.sa + (int64_t)c * P.sc] : make_double2(0.0, 0.0);
+    }
+    __syncthreads();
+    const int step = AXIS_FAST ? 1 : BIAS_TC;
+    for (int e = threadIdx.x; e < BIAS_TA * BIAS_TC; e += 256) {
+        const int ia = AXIS_FAST ? e % BIAS_TA : e / BIAS_TC, ic = AXIS_FAST ? e / BIAS_TA : e % BIAS_TC;
+        const int a = a0 + ia, c = c0 + ic;
+        if (a < P.A && c < P.C) {
+            const double2 *tp = tile + (AXIS_FAST ? ic * rows + ia : ia * BIAS_TC + ic);
+            double sr = 0.0, sw = 0.0;
+            for (int t = 0; t <= 2 * P.r; ++t) {
+                const double w = P.w[t];
+                const double2 x = tp[t * step];
+                sr = fma(w, x.x, sr);
+                sw = fma(w, x.y, sw);
+            }
+            dst[(int64_t)a * P.sa + (int64_t)c * P.sc] = make_double2(sr, sw);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void bias_update_kernel(const double2 *__restrict__ S, int64_t n, double *__restrict__ b)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        const double2 s = S[i];
+        if (s.y > 0.0) b[i] += s.x / s.y;
+    }
+}
+
+__global__ __launch_bounds__(256) void bias_bmean_kernel(const double *__restrict__ b, const int32_t *__restrict__ idx, const BiasStats *st,
+                                                         double *__restrict__ part)
+{
+    __shared__ double red[4];
+    const int N = st->N;
+    const int64_t c0 = (int64_t)blockIdx.x * BIAS_CHUNK;
+    if (st->degenerate || c0 >= N) return;
+    double s = 0.0;
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i = c0 + j * 256 + threadIdx.x;
+        if (i < N) s += b[idx[i]];
+    }
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void bias_bmean_final(const double *__restrict__ part, BiasStats *st)
+{
+    __shared__ double red[4];
+    if (st->degenerate) return;
+    const int N = st->N;
+    const double s = partial_sum(part, (int)(((int64_t)N + BIAS_CHUNK - 1) / BIAS_CHUNK), red);
+    if (threadIdx.x == 0) st->bmean = s / (double)N;
+}
+
+__global__ __launch_bounds__(256) void bias_recentre_kernel(const double2 *__restrict__ S, int64_t n, const BiasStats *st, double *__restrict__ b)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && S[i].y > 0.0) b[i] -= st->bmean;
+}
+
+__global__ __launch_bounds__(256) void bias_apply_kernel(const double *__restrict__ v, const double *__restrict__ b, int64_t n, const BiasStats *st,
+                                                         int K, double *__restrict__ out, double *__restrict__ field, double *__restrict__ classes)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        const double f = exp(b[i]);                                   // exp(0) = 1 off the support
+        const double val = v[i];
+        if (field) field[i] = f;
+        out[i] = isfinite(val) ? val / f : val;
+    }
+    if (classes && blockIdx.x == 0 && threadIdx.x < K) {
+        classes[threadIdx.x] = st->mu[threadIdx.x];
+        classes[K + threadIdx.x] = st->var[threadIdx.x];
+        classes[2 * K + threadIdx.x] = st->pi[threadIdx.x];
+    }
+}
+
+}  // namespace
+
+extern "C" int met2_bias_field(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double *v, const uint8_t *mask, const double voxel_mm[3],
+                               int32_t n_class, int32_t n_outer, int32_t n_em, double fwhm_mm, double *out, double *field, double *classes,
+                               void *stream)
+{
+    if (nx < 0 || ny < 0 || nz < 0) return fail(MET2_E_INVALID, "bad shape");
+    if (n_class < 1) return fail(MET2_E_INVALID, "bias field needs at least one class");
+    if (n_outer < 0 || n_em < 1) return fail(MET2_E_INVALID, "bias field needs n_outer >= 0 and n_em >= 1");
+    if (!voxel_mm) return fail(MET2_E_INVALID, "NULL voxel size");
+    if (!(fwhm_mm > 0.0) || !std::isfinite(fwhm_mm)) return fail(MET2_E_INVALID, "the smoothing width must be positive and finite");
+    for (int a = 0; a < 3; ++a)
+        if (!(voxel_mm[a] > 0.0) || !std::isfinite(voxel_mm[a])) return fail(MET2_E_INVALID, "the voxel size must be positive and finite");
+    const int64_t n = (int64_t)nx * ny * nz;
+    if (n == 0) return MET2_OK;
+    if (!v || !out) return fail(MET2_E_INVALID, "NULL argument");
+    if (v == out) return fail(MET2_E_INVALID, "the bias field cannot be removed in place");
+    if (n_class > BIAS_MAX_K) return fail(MET2_E_UNSUPPORTED, "bias field supports at most 8 classes");
+    if (n > 0x7fffffffLL) return fail(MET2_E_UNSUPPORTED, "volume too large");
+    int rad[3];
+    std::vector<double> hw(3 * (2 * BIAS_MAX_R + 1), 0.0);
+    for (int a = 0; a < 3; ++a) {
+        const double sigma = fwhm_mm / (2.0 * std::sqrt(2.0 * std::log(2.0))) / voxel_mm[a];
+        if (4.0 * sigma + 0.5 >= (double)(BIAS_MAX_R + 1)) return fail(MET2_E_UNSUPPORTED, "the smoothing kernel reaches further than 64 voxels");
+        rad[a] = (int)(4.0 * sigma + 0.5);
+        double *w = hw.data() + a * (2 * BIAS_MAX_R + 1), sum = 0.0;
+        for (int t = -rad[a]; t <= rad[a]; ++t) {
+            w[t + rad[a]] = rad[a] == 0 ? 1.0 : std::exp(-((double)t * (double)t) / (2.0 * sigma * sigma));
+            sum += w[t + rad[a]];
+        }
+        for (int t = 0; t <= 2 * rad[a]; ++t) w[t] /= sum;
+    }
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+
+    const int nch = (int)((n + BIAS_CHUNK - 1) / BIAS_CHUNK);           // chunks of the volume; of the compacted list at most as many
+    const unsigned nel = (unsigned)((n + 255) / 256);
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t b_d = up((size_t)n * 8), b_rw = up((size_t)n * 16), b_idx = up((size_t)n * 4), b_dom = up((size_t)n), b_cnt = up((size_t)nch * 4);
+    const size_t b_part = up((size_t)nch * 3 * BIAS_MAX_K * 8), b_st = up(sizeof(BiasStats)), b_w = up(hw.size() * 8);
+    char *work = nullptr;
+    HIPCHK(hipMalloc(&work, 2 * b_d + 2 * b_rw + b_idx + b_dom + 2 * b_cnt + b_part + b_st + b_w));
+    char *at = work;
+    auto take = [&at](size_t b) { char *p = at; at += b; return p; };
+    double *y = (double *)take(b_d), *b = (double *)take(b_d);
+    double2 *RA = (double2 *)take(b_rw), *RB = (double2 *)take(b_rw);
+    int32_t *idx = (int32_t *)take(b_idx);
+    uint8_t *dom = (uint8_t *)take(b_dom);
+    int32_t *cnt = (int32_t *)take(b_cnt), *off = (int32_t *)take(b_cnt);
+    double *part = (double *)take(b_part);
+    BiasStats *S = (BiasStats *)take(b_st);
+    double *wd = (double *)take(b_w);
+
+    int rc = MET2_OK;
+    hipError_t err = hipSuccess;
+    auto ok = [&](hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; return err == hipSuccess; };
+    const dim3 T(256), GC(nch), GE(nel), G1(1);
+    ok(hipMemsetAsync(S, 0, b_st, st));
+    ok(hipMemsetAsync(b, 0, b_d, st));
+    ok(hipMemcpyAsync(wd, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, st));      // hw lives until the wait below
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(bias_log_kernel, GC, T, 0, st, v, mask, n, y, dom, cnt);
+        hipLaunchKernelGGL(bias_scan_kernel, G1, T, 0, st, cnt, nch, off, S);
+        hipLaunchKernelGGL(bias_compact_kernel, GC, T, 0, st, dom, n, off, idx);
+        hipLaunchKernelGGL(bias_stat1_kernel, GC, T, 0, st, y, idx, S, nch, part);
+        hipLaunchKernelGGL(bias_stat1_final, G1, T, 0, st, part, nch, S);
+        hipLaunchKernelGGL(bias_stat2_kernel, GC, T, 0, st, y, idx, S, part);
+        hipLaunchKernelGGL(bias_init_kernel, G1, T, 0, st, part, S, n_class);
+        ok(hipGetLastError());
+    }
+    SmoothArgs P[3];
+    for (int a = 0; a < 3; ++a) {
+        P[a].w = wd + a * (2 * BIAS_MAX_R + 1);
+        P[a].r = rad[a];
+    }
+    // x: nx samples at stride ny nz, the lines are the ny nz contiguous voxels; y: per x a slab of nz lines; z: contiguous, one line per (x, y)
+    P[0].src = RA; P[0].dst = RB; P[0].A = nx; P[0].C = (int)((int64_t)ny * nz); P[0].O = 1; P[0].sa = (int64_t)ny * nz; P[0].sc = 1; P[0].so = 0;
+    P[1].src = RB; P[1].dst = RA; P[1].A = ny; P[1].C = nz; P[1].O = nx; P[1].sa = nz; P[1].sc = 1; P[1].so = (int64_t)ny * nz;
+    P[2].src = RA; P[2].dst = RB; P[2].A = nz; P[2].C = (int)((int64_t)nx * ny); P[2].O = 1; P[2].sa = 1; P[2].sc = nz; P[2].so = 0;
+    for (int it = 0; it < n_outer && err == hipSuccess; ++it) {
+        for (int em = 0; em < n_em; ++em) {
+            hipLaunchKernelGGL(bias_estep_kernel<false>, GC, T, 0, st, y, b, idx, S, n_class, nch, part, (double2 *)nullptr);
+            hipLaunchKernelGGL(bias_mstep_kernel, G1, T, 0, st, part, nch, S, n_class);
+        }
+        if (!ok(hipMemsetAsync(RA, 0, b_rw, st))) break;               // R = W = 0 off the domain; the y pass of the last round wrote here
+        hipLaunchKernelGGL(bias_estep_kernel<true>, GC, T, 0, st, y, b, idx, S, n_class, nch, (double *)nullptr, RA);
+        for (int a = 0; a < 3; ++a) {
+            const int64_t tiles = (int64_t)((P[a].A + BIAS_TA - 1) / BIAS_TA) * ((P[a].C + BIAS_TC - 1) / BIAS_TC) * P[a].O;      // <= n
+            if (a == 2)
+                hipLaunchKernelGGL(bias_smooth_kernel<true>, dim3((unsigned)tiles), T, 0, st, P[a]);
+            else
+                hipLaunchKernelGGL(bias_smooth_kernel<false>, dim3((unsigned)tiles), T, 0, st, P[a]);
+        }
+        hipLaunchKernelGGL(bias_update_kernel, GE, T, 0, st, RB, n, b);
+        hipLaunchKernelGGL(bias_bmean_kernel, GC, T, 0, st, b, idx, S, part);
+        hipLaunchKernelGGL(bias_bmean_final, G1, T, 0, st, part, S);
+        hipLaunchKernelGGL(bias_recentre_kernel, GE, T, 0, st, RB, n, S, b);
+        ok(hipGetLastError());
+    }
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(bias_apply_kernel, GE, T, 0, st, v, b, n, S, n_class, out, field, classes);
+        ok(hipGetLastError());
+    }
+    ok(hipStreamSynchronize(st));                                       // the work space goes back before the call returns
+    if (err != hipSuccess) rc = fail(MET2_E_HIP, std::string("met2_bias_field: ") + hipGetErrorString(err));
+    (void)hipFree(work);
+    return rc;
+}

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from ._cache import plan_for
-from ._lib import check, lib
+from ._lib import _dp, check, lib
 from .plan import MAP_NAMES, Met2Plan
 
 
@@ -146,6 +146,60 @@ def _degibbs_first(data, degibbs, prepared, device):
     return gibbs_filter(np.asarray(data, dtype=np.float64), device=device)
 
 
+def bias_field_filter(vol, mask=None, voxel_size=(1, 1, 1), n_class=3, n_outer=4, n_em=10, fwhm=20.0, device=0, return_field=False):
+    """Bias-field correction of a 3-D map (met2_bias_field in include/met2_hip.h states the algorithm: the EM estimator of Wells et al. 1996
+    and Guillemaud & Brady 1997, which FSL's fast iterates, without fast's Markov random field term) on the device: `vol` [nx,ny,nz], `mask`
+    [nx,ny,nz] or None (every voxel), `voxel_size` (dx, dy, dz) in mm.  The defaults are those of the reference's example script
+    (fast -n 3 -I 4 -l 20.0); parity with fast itself is unpinned.  The field is estimated on the masked voxels that are finite and positive
+    and divided out wherever it is defined; non-finite voxels are copied through.
+    return_field=True: (corrected, field, classes [3 n_class] = the final class means and variances of log(vol) and the class weights).
+    numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    as_numpy = not torch.is_tensor(vol)
+    dev = torch.device("cuda", device) if as_numpy else vol.device
+    dd = torch.as_tensor(vol, dtype=torch.float64, device=dev).contiguous()
+    if dd.dim() != 3 or (mask is not None and tuple(np.shape(mask)) != tuple(dd.shape)):
+        raise ValueError("vol must be [nx,ny,nz] and mask the same shape")
+    vox = np.asarray(voxel_size, dtype=np.float64).reshape(-1)
+    if vox.shape != (3,):
+        raise ValueError("voxel_size must be (dx, dy, dz)")
+    mk = None if mask is None else (torch.as_tensor(mask, device=dev) != 0).to(torch.uint8).contiguous()
+    out = torch.empty_like(dd)
+    nx, ny, nz = dd.shape
+    field = torch.empty_like(dd) if return_field else None
+    classes = torch.empty(3 * max(int(n_class), 0), dtype=torch.float64, device=dev) if return_field else None
+    with torch.cuda.device(dev):
+        check(lib().met2_bias_field(dev.index or 0, nx, ny, nz, dd.data_ptr(), None if mk is None else mk.data_ptr(),
+                                    vox.ctypes.data_as(_dp), int(n_class), int(n_outer), int(n_em), float(fwhm), out.data_ptr(),
+                                    field.data_ptr() if return_field else None, classes.data_ptr() if return_field else None,
+                                    torch.cuda.current_stream(dev).cuda_stream))
+    if not return_field:
+        return out.cpu().numpy() if as_numpy else out
+    return tuple(t.cpu().numpy() for t in (out, field, classes)) if as_numpy else (out, field, classes)
+
+
+def _bias_check(bias_correct, vol_shape, voxel_size, distributed):
+    """bias_correct of the drivers, checked before any device work -> True when the step is to run"""
+    if bias_correct not in ("no", "yes"):
+        raise ValueError("bias_correct must be 'no' or 'yes'")
+    if bias_correct == "no":
+        return False
+    if distributed:
+        raise ValueError("bias_correct='yes' does not go with distributed=True: the map is complete only after the gather")
+    if len(vol_shape) != 3:
+        raise ValueError("bias_correct='yes' needs data [nx,ny,nz,nt]")
+    if voxel_size is None or np.shape(voxel_size) != (3,):
+        raise ValueError("bias_correct='yes' needs voxel_size=(dx, dy, dz) in mm")
+    return True
+
+
+def _bias_last(res, mask, voxel_size, device):
+    """bias_correct='yes' of the drivers: res['TWC'] through bias_field_filter with the driver's mask -> the corrected map, and 'TWC_bias'"""
+    twc, field, _ = bias_field_filter(np.ascontiguousarray(res["TWC"], dtype=np.float64), np.asarray(mask) != 0, voxel_size, device=device,
+                                      return_field=True)
+    res["TWC"] = twc
+    res["TWC_bias"] = field
+
+
 def gaussian_smooth(data, sigma=2.0, truncate=4.0, device=0):
     """The Gaussian pre-smoothing of the FA step (motor:337-343): every echo volume of data [nx,ny,nz,nt] through the
     equivalent of scipy.ndimage.gaussian_filter(volume, sigma) (mode 'reflect', truncate 4), on the device, bit-identical
@@ -221,7 +275,7 @@ def _estimate_fa(plan, dd_fa, mm, FA_method, fa_index, T2s, T1s, tau, TR, alpha_
 
 def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2", FA_method="brute-force", myelin_T2=40.0,
                       fa_index=None, device=0, plan=None, denoise="None", prepared=False, FA_smooth="no", distributed=False,
-                      return_prepared=False, devices=None, bootstrap=None, degibbs="no"):
+                      return_prepared=False, devices=None, bootstrap=None, degibbs="no", bias_correct="no", voxel_size=None):
     """Steps 1-4 of motor_recon_met2 (motor:293-373, 427-472) on arrays: data [nx,ny,nz,nt] (or
     [nvox, nt]), mask [nx,ny,nz].  Mirrors the driver's preparation: data *= mask (motor:180-182),
     negative values clipped to 0 (motor:279), optional NESMA / TV filter (motor:293-333, needs a 3-D volume) or denoise='MPPCA'
@@ -233,6 +287,11 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     [nx,ny,nz,nt]; ValueError with prepared=True; on the devices=[...] path it runs on devices[0], under distributed=True on every rank's own
     copy (it is deterministic).  MRtrix recommends MP-PCA denoising BEFORE unringing: a caller who wants that order calls mppca_filter and
     gibbs_filter themselves and passes prepared=True.  degibbs='no' (default) changes nothing.
+    bias_correct='yes' (step 5 of the reference's example script, which runs FSL's fast on the TWC map there): after everything else the
+    total water content map goes through bias_field_filter with the driver's mask and voxel_size=(dx, dy, dz) in mm; 'TWC' becomes the
+    corrected map and 'TWC_bias' the estimated field; the other outputs, the bootstrap's included, are not touched.  Needs data [nx,ny,nz,nt]
+    and voxel_size; ValueError otherwise and with distributed=True; on the devices=[...] path it runs on devices[0], on the assembled map.
+    Parity with fast itself is unpinned (no Markov random field term).  bias_correct='no' (default) changes nothing.
     FA_smooth='yes' (the CLI default, motor:337-343): the flip angles are estimated on the Gaussian-smoothed volume
     (sigma = 2 voxels, every echo), the spectra on the unsmoothed one; needs a 3-D volume.
     C- and Fortran-ordered volumes (nibabel's) are both read in place.
@@ -261,6 +320,7 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     data = _degibbs_first(data, degibbs, prepared, devices[0] if devices else plan.device.index or 0 if plan is not None else device)
     data = np.asarray(data, dtype=np.float64)
     vol_shape = data.shape[:-1]
+    bias = _bias_check(bias_correct, vol_shape, voxel_size, distributed)
     nt = data.shape[-1]
     mask = np.asarray(mask).reshape(vol_shape)
     if devices is None and plan is None and not distributed and data.ndim >= 2:
@@ -285,6 +345,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
                                 (res["T2s"], 1000.0 * np.ones_like(res["T2s"]), float(TE_array[1] - TE_array[0]), TR))
             finally:
                 plan.close()
+        if bias:
+            _bias_last(res, mask, voxel_size, devices[0])
         return res
     dev = plan.device if plan is not None else torch.device("cuda", device)
     # a caller's own plan, a distributed run, or a bare voxel list: the volume on the device in one piece
@@ -327,6 +389,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
                 res[name] = t.cpu().numpy()
         if boot is not None:
             _bootstrap_into(res, plan, reg_method, dd, fa_vol, mm, boot, (T2s, T1s, tau, TR))
+        if bias:
+            _bias_last(res, mask, voxel_size, dev.index or 0)
         return res
     finally:
         if own:
@@ -535,14 +599,16 @@ def _recon_sharded(plan, dd, dd_fa, mm, reg_method, FA_method, fa_index, T2s, T1
 
 
 def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR, reg_method, reg_matrix, denoise, FA_method,
-                     FA_smooth, myelin_T2, num_cores=-1, device=0, devices=None, bootstrap=None, degibbs="no"):
+                     FA_smooth, myelin_T2, num_cores=-1, device=0, devices=None, bootstrap=None, degibbs="no", bias_correct="no"):
     """Drop-in for motor_recon_met2 (motor:165-506) with the reference's on-disk contract: NIfTI in
     (data [nx,ny,nz,nt], mask [nx,ny,nz]), ten NIfTI volumes out (MWF, IEWF, FWF, T2_M, T2_IE, TWC, FA, fsol_4D,
     Est_Signal, reg_param .nii.gz at path_to_save_data, motor:475-503).  `num_cores` is accepted and ignored (one
     process drives the GPU; devices=[0, 1, ...]: that one process drives all the listed GPUs through met2_fit_host).  denoise: 'None',
     'NESMA' (motor:305-333), 'TV' (motor:293-304) or 'MPPCA' (an extension: mppca_filter; Data_denoised.nii.gz as for TV, and the noise
     map MPPCA_sigma.nii.gz).  degibbs='yes' (see recon_met2_arrays): the raw volume is unrung first (gibbs_filter) and written as
-    Data_degibbs.nii.gz.  Not reproduced: the mean-spectrum PNG of motor:377-424.
+    Data_degibbs.nii.gz.  bias_correct='yes' (see recon_met2_arrays): TWC.nii.gz is the bias-corrected map and TWC_bias.nii.gz the
+    estimated field, as the example script leaves them; the voxel size is the data header's pixdim[1:4] (absolute values, 0 read as 1).
+    Not reproduced: the mean-spectrum PNG of motor:377-424.
     bootstrap=dict(n_rep=..., seed=...) (an extension, see recon_met2_arrays) also writes <Q>_bootstrap.nii.gz [nx,ny,nz,5] for Q in
     BOOT_QUANTITIES (BOOT_STATS along the last axis) and sigma.nii.gz; with fa='brute-force' / 'spline' also FA_bootstrap.nii.gz [nx,ny,nz,5]
     (degrees), with spectrum=True also fsol_bootstrap_{mean,std,q025,q500,q975}.nii.gz [nx,ny,nz,n_t2] each."""
@@ -552,11 +618,18 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     mask = nifti.load(path_to_mask).get_fdata().astype(np.int64)
     if data.ndim != 4 or mask.shape != data.shape[:3]:
         raise ValueError("data must be 4-D and mask must match its first three dimensions")
+    bias_kw = {}
+    if bias_correct != "no":
+        pixdim = img.header.get("pixdim", (1.0,) * 8)
+        bias_kw = {"bias_correct": bias_correct, "voxel_size": tuple(abs(float(p)) or 1.0 for p in pixdim[1:4])}
     if degibbs != "no":
         data = _degibbs_first(data, degibbs, False, devices[0] if devices else device)
         nifti.save(nifti.NiftiImage(data, img.affine), path_to_save_data + "Data_degibbs.nii.gz")
     res = recon_met2_arrays(data, mask, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, device=device, denoise=denoise,
-                            FA_smooth=FA_smooth, return_prepared=(denoise in ("TV", "MPPCA")), devices=devices, bootstrap=bootstrap)
+                            FA_smooth=FA_smooth, return_prepared=(denoise in ("TV", "MPPCA")), devices=devices, bootstrap=bootstrap,
+                            **bias_kw)
+    if bias_kw:
+        nifti.save(nifti.NiftiImage(res["TWC_bias"], img.affine), path_to_save_data + "TWC_bias.nii.gz")
     if denoise in ("TV", "MPPCA"):                                  # motor:302-303
         nifti.save(nifti.NiftiImage(res.pop("data_prepared"), img.affine), path_to_save_data + "Data_denoised.nii.gz")
     if denoise == "MPPCA":
