@@ -462,6 +462,27 @@ int met2_mppca(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te,
 int met2_degibbs(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, int32_t nshifts, int32_t min_w,
                  int32_t max_w, double *out, int8_t *shift_x, int8_t *shift_y, void *stream);
 
+/* The stages of met2_degibbs one by one, for tests and diagnostics.  Each launches the kernels of met2_degibbs through the host code that
+ * met2_degibbs itself runs; the argument checks and return codes are those of met2_degibbs where they apply.
+ *
+ * met2_gibbs_table_cols: the row length jp of the shift-kernel table at nshifts (2 nshifts + 1 rounded up to the kernel's pass width), or
+ *   MET2_E_INVALID (nshifts < 1) / MET2_E_UNSUPPORTED (nshifts > 32).
+ * met2_gibbs_tables: the two tables of one axis of length n, as the kernels read them.  DEVICE pointers: W [n][n][2], the DFT matrix
+ *   W[b][q] = exp(-2 pi i b q / n) as (re, im) pairs; c [n][jp], c[r][j] = c_j[r] of step 2 of U for j < 2 nshifts + 1 and exactly 0 in the
+ *   padding columns j >= 2 nshifts + 1.  8 <= n <= 256.  Asynchronous on `stream`.
+ * met2_gibbs_split: the 2-D split alone.  DEVICE pointers: data [nx][ny][nz][n_te]; ix, iy the same shape, distinct from data and from each
+ *   other: Ix and Iy of every (z, echo) slice.  A slice that holds a non-finite value gets what the arithmetic gives (not a copy).  The
+ *   volume goes through the chunk loop of met2_degibbs.  BLOCKING.
+ * met2_gibbs_lines: the operator U on nlines lines of n samples.  DEVICE pointers: lines [nlines][n]; out [nlines][n], must not alias lines;
+ *   each may be NULL: shift [nlines][n] int8, the chosen sh[j*]; best [nlines][n], the winning candidate's total variation
+ *   min(TVL_j*[l], TVR_j*[l]).  8 <= n <= 256, 2 (max_w + 1) <= n, nlines n < 2^31.  nlines == 0 or n == 0 returns MET2_OK at once (after
+ *   the checks of nshifts, min_w and max_w).  A non-finite line is not treated specially here.  BLOCKING. */
+int met2_gibbs_table_cols(int32_t nshifts);
+int met2_gibbs_tables(int32_t device, int32_t n, int32_t nshifts, double *W, double *c, void *stream);
+int met2_gibbs_split(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, double *ix, double *iy, void *stream);
+int met2_gibbs_lines(int32_t device, int32_t n, int32_t nlines, const double *lines, int32_t nshifts, int32_t min_w, int32_t max_w, double *out,
+                     int8_t *shift, double *best, void *stream);
+
 /* Bias-field correction of a 3-D map (bias_correct='yes'; step 5 of the reference's example pipeline,
  * example_script_run_MET2_preproc_and_recon.sh, which runs FSL's `fast -t 3 -n 3 -H 0.1 -I 4 -l 20.0 -b` on the total water content map and
  * divides the estimated field out).  The EM bias-field estimation of Wells et al. (IEEE TMI 1996) and Guillemaud & Brady (IEEE TMI 1997): the

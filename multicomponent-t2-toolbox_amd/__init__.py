@@ -11,6 +11,7 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
                             bias_field_filter (bias-field correction of the TWC map, bias_correct='yes': csrc/met2_bias.hip),
                             gaussian_smooth, ROI mode
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
+  gibbs.py                  gibbs_tables / gibbs_split / gibbs_lines: the stages of the Gibbs-ringing filter one by one (tests and diagnostics)
   nifti.py                  NIfTI-1 reader / writer for the driver's on-disk contract
   dist.py                   one-process-per-GPU voxel sharding + the single gather of output maps
   synth.py                  seeded synthetic volumes (the reference's Monte-Carlo recipe)

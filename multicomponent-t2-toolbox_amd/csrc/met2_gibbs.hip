@@ -266,6 +266,7 @@ struct UnringArgs {
     int stride;               // between a line's samples
     int nsh, jp, min_w, max_w;
     int accumulate;           // dst += U(src) instead of dst = U(src)
+    double *best;             // [slices][nx][ny] or NULL: the winning candidate's total variation (met2_gibbs_lines)
 };
 
 // one sample per thread, 256 / n lines per workgroup (one at n > 128)
@@ -339,27 +340,43 @@ __global__ __launch_bounds__(256) void gibbs_unring_kernel(UnringArgs A)
     const double o = d > 0.0 ? a1 * (1.0 - d) + a0 * d : a1 * (1.0 + d) - a2 * d;
     A.dst[base] = A.accumulate ? A.dst[base] + o : o;
     if (A.shift) A.shift[base] = (int8_t)sh;
+    if (A.best) A.best[base] = best;                                    // uniform
 }
 
 inline int round64(int n) { return (n + 63) / 64 * 64; }
 
-}  // namespace
+inline int table_cols(int nshifts) { return (2 * nshifts + 1 + GIBBS_JB - 1) / GIBBS_JB * GIBBS_JB; }
 
-extern "C" int met2_degibbs(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, const double *data, int32_t nshifts, int32_t min_w,
-                            int32_t max_w, double *out, int8_t *shift_x, int8_t *shift_y, void *stream)
+// the checks on an axis' tables and on the operator U that every entry shares; MET2_OK or the code already recorded by fail()
+int check_shifts(int32_t nshifts)
 {
-    if (nx < 0 || ny < 0 || nz < 0 || nt < 0) return fail(MET2_E_INVALID, "bad shape");
     if (nshifts < 1) return fail(MET2_E_INVALID, "degibbs needs at least one sub-voxel shift");
-    if (min_w < 1 || min_w > max_w) return fail(MET2_E_INVALID, "degibbs needs 1 <= minW <= maxW");
     if (nshifts > GIBBS_MAX_NSH) return fail(MET2_E_UNSUPPORTED, "degibbs supports at most 32 sub-voxel shifts to a side");
-    const int64_t ns = (int64_t)nz * nt;
-    if (nx == 0 || ny == 0 || ns == 0) return MET2_OK;
-    if (nx < GIBBS_MIN_N || nx > GIBBS_MAX_N || ny < GIBBS_MIN_N || ny > GIBBS_MAX_N)
-        return fail(MET2_E_UNSUPPORTED, "degibbs supports 8 to 256 samples along x and y");
-    if (2 * ((int64_t)max_w + 1) > (nx < ny ? nx : ny)) return fail(MET2_E_UNSUPPORTED, "the total-variation window is too wide for the axis");
-    if (!data || !out) return fail(MET2_E_INVALID, "NULL argument");
-    if (data == out) return fail(MET2_E_INVALID, "degibbs cannot run in place");
-    if (ns > 0x7fffffffLL / ((int64_t)nx * ny)) return fail(MET2_E_UNSUPPORTED, "volume too large");
+    return MET2_OK;
+}
+
+int check_windows(int32_t min_w, int32_t max_w)
+{
+    if (min_w < 1 || min_w > max_w) return fail(MET2_E_INVALID, "degibbs needs 1 <= minW <= maxW");
+    return MET2_OK;
+}
+
+void launch_tables(hipStream_t st, int n, int nshifts, int jp, double2 *W, double *ct)
+{
+    const int big = n * (n > jp ? n : jp);
+    hipLaunchKernelGGL(gibbs_tables_kernel, dim3((big + 255) / 256), dim3(256), 0, st, n, nshifts, jp, W, ct);
+}
+
+void launch_unring(hipStream_t st, const UnringArgs &A)
+{
+    hipLaunchKernelGGL(gibbs_unring_kernel, dim3((A.nlines + 256 / A.n - 1) / (256 / A.n)), dim3(256), 0, st, A);
+}
+
+// The volume in chunks of whole slices.  split_x == NULL: the filter (out, shift_x, shift_y as met2_degibbs takes them).  Otherwise the 2-D
+// split alone: Ix and Iy of every slice go to split_x and split_y, whatever the slice holds.  The shapes and parameters have been checked.
+int run_volume(int32_t device, int32_t nx, int32_t ny, int64_t ns, const double *data, int32_t nshifts, int32_t min_w, int32_t max_w, double *out,
+               int8_t *shift_x, int8_t *shift_y, double *split_x, double *split_y, void *stream, const char *who)
+{
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
 
@@ -369,7 +386,7 @@ extern "C" int met2_degibbs(int32_t device, int32_t nx, int32_t ny, int32_t nz, 
     if (scl > ns) scl = ns;
     if (scl > 65535) scl = 65535;                                      // the column kernel's grid.y
     const int sc_max = (int)scl;
-    const int jp = (2 * nshifts + 1 + GIBBS_JB - 1) / GIBBS_JB * GIBBS_JB;
+    const int jp = table_cols(nshifts);
     const size_t ce = (size_t)sc_max * (size_t)P;                      // samples of a chunk
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t b_W = up(ce * 8), b_T = up(ce * 16), b_I = up(ce * 8), b_sh = up(ce), b_small = up((size_t)sc_max * 8);
@@ -391,12 +408,9 @@ extern "C" int met2_degibbs(int32_t device, int32_t nx, int32_t ny, int32_t nz, 
     int rc = MET2_OK;
     hipError_t err = hipSuccess;
     auto ok = [&](hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; return err == hipSuccess; };
-    {
-        const int big_x = nx * (nx > jp ? nx : jp), big_y = ny * (ny > jp ? ny : jp);
-        hipLaunchKernelGGL(gibbs_tables_kernel, dim3((big_x + 255) / 256), dim3(256), 0, st, nx, nshifts, jp, Wx, cx);
-        hipLaunchKernelGGL(gibbs_tables_kernel, dim3((big_y + 255) / 256), dim3(256), 0, st, ny, nshifts, jp, Wy, cy);
-        ok(hipGetLastError());
-    }
+    launch_tables(st, nx, nshifts, jp, Wx, cx);
+    launch_tables(st, ny, nshifts, jp, Wy, cy);
+    ok(hipGetLastError());
     for (int64_t s0 = 0; s0 < ns && err == hipSuccess; s0 += sc_max) {
         const int sc = (int)(ns - s0 < sc_max ? ns - s0 : sc_max);
         const int nrows = sc * nx;
@@ -407,21 +421,126 @@ extern "C" int met2_degibbs(int32_t device, int32_t nx, int32_t ny, int32_t nz, 
         hipLaunchKernelGGL(gibbs_dft_cols_kernel, dim3((ny + GIBBS_LB - 1) / GIBBS_LB, sc), dim3(round64(nx)), 0, st, T, Wx, Wy, nx, ny, corner);
         hipLaunchKernelGGL(gibbs_idft_rows_kernel, dim3((nrows + GIBBS_LB - 1) / GIBBS_LB), dim3(round64(ny)), 0, st, T, Wy, W, corner, nx, ny,
                            nrows, Ix, Iy);
+        if (split_x) {                                                  // source and copy-through source the same: the flags change nothing
+            hipLaunchKernelGGL(gibbs_scatter_kernel, tg, dim3(32, 8), 0, st, Ix, Ix, sx, sy, flag, P, ns, s0, sc, split_x, (int8_t *)nullptr,
+                               (int8_t *)nullptr);
+            hipLaunchKernelGGL(gibbs_scatter_kernel, tg, dim3(32, 8), 0, st, Iy, Iy, sx, sy, flag, P, ns, s0, sc, split_y, (int8_t *)nullptr,
+                               (int8_t *)nullptr);
+            ok(hipGetLastError());
+            continue;
+        }
         UnringArgs A;
-        A.nsh = nshifts; A.jp = jp; A.min_w = min_w; A.max_w = max_w; A.slice_stride = P;
+        A.nsh = nshifts; A.jp = jp; A.min_w = min_w; A.max_w = max_w; A.slice_stride = P; A.best = nullptr;
         // along x: the lines are a slice's columns; the result overwrites Ix
         A.src = Ix; A.dst = Ix; A.ct = cx; A.shift = shift_x ? sx : nullptr; A.n = nx; A.nlines = sc * ny; A.per_slice = ny; A.line_stride = 1;
         A.stride = ny; A.accumulate = 0;
-        hipLaunchKernelGGL(gibbs_unring_kernel, dim3((A.nlines + 256 / nx - 1) / (256 / nx)), dim3(256), 0, st, A);
+        launch_unring(st, A);
         // along y: the rows; added to the x-pass's result
         A.src = Iy; A.dst = Ix; A.ct = cy; A.shift = shift_y ? sy : nullptr; A.n = ny; A.nlines = nrows; A.per_slice = nx; A.line_stride = ny;
         A.stride = 1; A.accumulate = 1;
-        hipLaunchKernelGGL(gibbs_unring_kernel, dim3((A.nlines + 256 / ny - 1) / (256 / ny)), dim3(256), 0, st, A);
+        launch_unring(st, A);
         hipLaunchKernelGGL(gibbs_scatter_kernel, tg, dim3(32, 8), 0, st, Ix, W, sx, sy, flag, P, ns, s0, sc, out, shift_x, shift_y);
         ok(hipGetLastError());
     }
     ok(hipStreamSynchronize(st));                                       // the work space goes back before the call returns
-    if (err != hipSuccess) rc = fail(MET2_E_HIP, std::string("met2_degibbs: ") + hipGetErrorString(err));
+    if (err != hipSuccess) rc = fail(MET2_E_HIP, std::string(who) + ": " + hipGetErrorString(err));
     (void)hipFree(work);
     return rc;
+}
+
+// the checks on the volume's shape that met2_degibbs and met2_gibbs_split share, after those of the parameters; *empty: nothing to do
+int check_volume(int32_t nx, int32_t ny, int32_t nz, int32_t nt, int64_t min_axis, bool *empty)
+{
+    const int64_t ns = (int64_t)nz * nt;
+    *empty = nx == 0 || ny == 0 || ns == 0;
+    if (*empty) return MET2_OK;
+    if (nx < GIBBS_MIN_N || nx > GIBBS_MAX_N || ny < GIBBS_MIN_N || ny > GIBBS_MAX_N)
+        return fail(MET2_E_UNSUPPORTED, "degibbs supports 8 to 256 samples along x and y");
+    if (min_axis > (nx < ny ? nx : ny)) return fail(MET2_E_UNSUPPORTED, "the total-variation window is too wide for the axis");
+    return MET2_OK;
+}
+
+}  // namespace
+
+extern "C" int met2_degibbs(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, const double *data, int32_t nshifts, int32_t min_w,
+                            int32_t max_w, double *out, int8_t *shift_x, int8_t *shift_y, void *stream)
+{
+    if (nx < 0 || ny < 0 || nz < 0 || nt < 0) return fail(MET2_E_INVALID, "bad shape");
+    if (nshifts < 1) return fail(MET2_E_INVALID, "degibbs needs at least one sub-voxel shift");
+    if (int rc = check_windows(min_w, max_w)) return rc;
+    if (int rc = check_shifts(nshifts)) return rc;
+    bool empty;
+    if (int rc = check_volume(nx, ny, nz, nt, 2 * ((int64_t)max_w + 1), &empty)) return rc;
+    if (empty) return MET2_OK;
+    if (!data || !out) return fail(MET2_E_INVALID, "NULL argument");
+    if (data == out) return fail(MET2_E_INVALID, "degibbs cannot run in place");
+    const int64_t ns = (int64_t)nz * nt;
+    if (ns > 0x7fffffffLL / ((int64_t)nx * ny)) return fail(MET2_E_UNSUPPORTED, "volume too large");
+    return run_volume(device, nx, ny, ns, data, nshifts, min_w, max_w, out, shift_x, shift_y, nullptr, nullptr, stream, "met2_degibbs");
+}
+
+extern "C" int met2_gibbs_table_cols(int32_t nshifts)
+{
+    if (int rc = check_shifts(nshifts)) return rc;
+    return table_cols(nshifts);
+}
+
+extern "C" int met2_gibbs_tables(int32_t device, int32_t n, int32_t nshifts, double *W, double *c, void *stream)
+{
+    if (int rc = check_shifts(nshifts)) return rc;
+    if (n < GIBBS_MIN_N || n > GIBBS_MAX_N) return fail(MET2_E_UNSUPPORTED, "degibbs supports 8 to 256 samples along x and y");
+    if (!W || !c) return fail(MET2_E_INVALID, "NULL argument");
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    launch_tables(st, n, nshifts, table_cols(nshifts), (double2 *)W, c);
+    HIPCHK(hipGetLastError());
+    return MET2_OK;
+}
+
+extern "C" int met2_gibbs_split(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, const double *data, double *ix, double *iy,
+                                void *stream)
+{
+    if (nx < 0 || ny < 0 || nz < 0 || nt < 0) return fail(MET2_E_INVALID, "bad shape");
+    bool empty;
+    if (int rc = check_volume(nx, ny, nz, nt, GIBBS_MIN_N, &empty)) return rc;
+    if (empty) return MET2_OK;
+    if (!data || !ix || !iy) return fail(MET2_E_INVALID, "NULL argument");
+    if (data == ix || data == iy || ix == iy) return fail(MET2_E_INVALID, "the split cannot run in place");
+    const int64_t ns = (int64_t)nz * nt;
+    if (ns > 0x7fffffffLL / ((int64_t)nx * ny)) return fail(MET2_E_UNSUPPORTED, "volume too large");
+    return run_volume(device, nx, ny, ns, data, 1, 1, 1, nullptr, nullptr, nullptr, ix, iy, stream, "met2_gibbs_split");
+}
+
+extern "C" int met2_gibbs_lines(int32_t device, int32_t n, int32_t nlines, const double *lines, int32_t nshifts, int32_t min_w, int32_t max_w,
+                                double *out, int8_t *shift, double *best, void *stream)
+{
+    if (n < 0 || nlines < 0) return fail(MET2_E_INVALID, "bad shape");
+    if (int rc = check_shifts(nshifts)) return rc;
+    if (int rc = check_windows(min_w, max_w)) return rc;
+    if (n == 0 || nlines == 0) return MET2_OK;
+    if (n < GIBBS_MIN_N || n > GIBBS_MAX_N) return fail(MET2_E_UNSUPPORTED, "degibbs supports 8 to 256 samples along x and y");
+    if (2 * ((int64_t)max_w + 1) > n) return fail(MET2_E_UNSUPPORTED, "the total-variation window is too wide for the axis");
+    if (!lines || !out) return fail(MET2_E_INVALID, "NULL argument");
+    if (lines == out) return fail(MET2_E_INVALID, "degibbs cannot run in place");
+    if (nlines > 0x7fffffffLL / n) return fail(MET2_E_UNSUPPORTED, "volume too large");
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    const int jp = table_cols(nshifts);
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t b_W = up((size_t)n * n * 16), b_c = up((size_t)n * jp * 8);
+    char *work = nullptr;
+    HIPCHK(hipMalloc(&work, b_W + b_c));
+    double *ct = (double *)(work + b_W);
+    launch_tables(st, n, nshifts, jp, (double2 *)work, ct);
+    UnringArgs A;
+    A.nsh = nshifts; A.jp = jp; A.min_w = min_w; A.max_w = max_w; A.slice_stride = 0; A.best = best;
+    A.src = lines; A.dst = out; A.ct = ct; A.shift = shift; A.n = n; A.nlines = nlines; A.per_slice = nlines; A.line_stride = n;
+    A.stride = 1; A.accumulate = 0;
+    launch_unring(st, A);
+    hipError_t err = hipGetLastError();
+    const hipError_t e2 = hipStreamSynchronize(st);                     // the work space goes back before the call returns
+    if (err == hipSuccess) err = e2;
+    (void)hipFree(work);
+    if (err != hipSuccess) return fail(MET2_E_HIP, std::string("met2_gibbs_lines: ") + hipGetErrorString(err));
+    return MET2_OK;
 }

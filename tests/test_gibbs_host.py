@@ -107,6 +107,47 @@ def test_committed_volumes_hold_no_ties(name):
     assert not gn.ties(res).any(), m
 
 
+@pytest.mark.parametrize("name", gn.IMAGES)
+def test_committed_images_hold_no_ties(name):
+    data = gn.image_volume(name)
+    res = gn.degibbs(data)
+    m = min(res["margin_x"].min(), res["margin_y"].min())
+    print("%s %s: smallest margin %.2e" % (name, data.shape, m))
+    assert not gn.ties(res).any(), m
+    if name == "box":
+        assert (data == 0.0).sum() > data.size // 2
+    if name == "scales":
+        assert data.shape[3] == 3 and np.array_equal(data[:, :, 0, 2], data[:, :, 0, 1] * 1e7)
+
+
+@pytest.mark.parametrize("n,params", gn.line_cases())
+def test_committed_lines_hold_few_ties(n, params):
+    """the line sets of tests/test_gpu_gibbs_kernels.py, in the extended-precision restatement alone: no sample of the noise lines is a tie,
+    at most 2 % of the samples of the designed lines are (their all-zero line is one all along)"""
+    noise = gn.line_reference(n, params, "noise")
+    assert (noise["margin"] >= gn.TIE).all(), noise["margin"].min()
+    des = gn.line_reference(n, params, "designed")
+    share = float((des["margin"] < gn.TIE).mean())
+    z = des["zero_at"]
+    print("n = %d %s: noise lines' smallest margin %.2e; designed lines: %d, %.2f %% of the samples are ties (%d outside the zero line)"
+          % (n, params, noise["margin"].min(), des["lines"].shape[0], 100 * share, int((np.delete(des["margin"], z, axis=0) < gn.TIE).sum())))
+    assert share <= 0.02
+    assert not des["shift"][z].any() and not des["out"][z].any() and not des["best"][z].any()
+    assert 2 * (params[2] + 1) <= n
+
+
+def test_extended_precision_routes_agree_with_the_float64_ones():
+    x = gn.noise_lines(16)
+    o, s, g, b = gn.ld_unring_lines(x)
+    o2, s2, g2 = gn.unring_lines(x)
+    assert np.array_equal(s, s2) and np.abs(o - o2).max() <= 1e-12 * np.abs(x).max()
+    S = 100.0 + 5.0 * np.random.default_rng(3).standard_normal((16, 12))
+    ix, iy, corner = gn.ld_split2d(S)
+    a, c = gn.split2d(S)
+    assert max(np.abs(ix - a).max(), np.abs(iy - c).max()) <= 1e-12 * np.abs(S).max()
+    assert np.abs(gn.ld_shift_kernels(9, 20) - gn.shift_kernels(9, 20)).max() <= 1e-12
+
+
 def test_known_answer_disc():
     img, dist = gn.disc_phantom()
     assert img.shape == (64, 64)
