@@ -523,6 +523,78 @@ int met2_gibbs_lines(int32_t device, int32_t n, int32_t nlines, const double *li
 int met2_bias_field(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double *v, const uint8_t *mask, const double voxel_mm[3],
                     int32_t n_class, int32_t n_outer, int32_t n_em, double fwhm_mm, double *out, double *field, double *classes, void *stream);
 
+/* Brain extraction (brain_mask='yes'; an extension: the reference's example pipeline makes the mask on the CPU, with FSL's
+ * `fslmaths -Tmean` and `bet -m -f 0.4`, example_script_run_MET2_preproc_and_recon.sh step 3).  The surface model of Smith, Fast robust
+ * automated brain extraction, HBM 17:143-155, 2002 -- the model bet runs -- WITHOUT bet's self-intersection retry pass, its skull and
+ * scalp surfaces and its -R / -S / -B variants; parity with bet itself is unpinned.  All arithmetic is fp64 and no product is fused into a
+ * sum: every expression below rounds operation by operation as written, products before sums, left to right.  v [nx][ny][nz] (z fastest);
+ * voxel (ix, iy, iz) has its centre at (ix dx, iy dy, iz dz) mm, (dx, dy, dz) = voxel_mm.
+ *  0 echo mean (met2_bet_mean): v = (((d_0 + d_1) + d_2) + ... + d_{n_te-1}) / n_te per voxel; a non-finite echo leaves a non-finite v.
+ *  1 robust statistics over the FINITE voxels of v, N of them (met2_bet_stats):
+ *      lo, hi = their min and max; bin(x) = min(999, floor((x - lo) / (hi - lo) * 1000)); C_j = the number of voxels in bins 0 .. j;
+ *      j2 = the first j with 100 C_j >= 2 N, j98 = the first with 100 C_j >= 98 N (integers); w = (hi - lo) / 1000;
+ *      t2 = lo + j2 w (the bin's lower edge), t98 = lo + (j98 + 1) w (the bin's upper edge), t = t2 + 0.1 (t98 - t2);
+ *      S = the finite voxels with v > t, `count` of them; weight q = min(v, t98) - t2; COG_a = (sum_S q p_a) / (sum_S q), p_a = i_a d_a;
+ *      r = cbrt(3 count ((dx dy) dz) / (4 pi));
+ *      tm = the median (np.median's: the mean (a + b) / 2 of the two middle values for an even number) of the voxels with t2 < v < t98 and
+ *      ((p_x - COG_x)^2 + (p_y - COG_y)^2) + (p_z - COG_z)^2 <= r r; tm = t when there is none.
+ *      The histogram and the median's radix selection are integer atomics.  The four sums run over chunks of 1024 consecutive voxels in
+ *      memory order: in a chunk thread h of 256 adds voxels h, 256 + h, 512 + h, 768 + h in that order, a butterfly (xor 32, 16, .. 1) adds the
+ *      64 lanes of a wave, the four waves add as (0 + 1) + (2 + 3); the host adds the chunks' partials in ascending order.  No float atomics:
+ *      a call gives the same bits every time.  MET2_E_INVALID when S is empty (no finite voxel, hi = lo, no voxel at all).
+ *  2 mesh (met2_bet_mesh, built on the host): the icosahedron, phi = (1 + sqrt 5) / 2, every vertex divided by sqrt((x^2 + y^2) + z^2):
+ *      vertices (-1,phi,0) (1,phi,0) (-1,-phi,0) (1,-phi,0) (0,-1,phi) (0,1,phi) (0,-1,-phi) (0,1,-phi) (phi,0,-1) (phi,0,1) (-phi,0,-1) (-phi,0,1);
+ *      faces, counter-clockwise seen from outside: 0 11 5, 0 5 1, 0 1 7, 0 7 10, 0 10 11, 1 5 9, 5 11 4, 11 10 2, 10 7 6, 7 1 8, 3 9 4, 3 4 2,
+ *      3 2 6, 3 6 8, 3 8 9, 4 9 5, 2 4 11, 6 2 10, 8 6 7, 9 8 1;  subdivided `level` times: every triangle (a, b, c), in
+ *      order, becomes (a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca); a midpoint is ((p + q) 0.5) / |.| and gets the next free index the
+ *      first time its edge is met (edges ab, bc, ca in that order).  10 4^level + 2 vertices, 20 4^level triangles: 2562 and 5120 at level 4,
+ *      bet's mesh.  ring[i][0 .. deg_i) = the neighbours of vertex i counter-clockwise seen from outside, starting at the one of the smallest
+ *      index; deg is 5 at the twelve original vertices and 6 elsewhere.  Start: vertex = COG + unit vertex x (r / 2).
+ *  3 surface evolution (met2_bet_evolve), n_iter Jacobi steps: every vertex x is computed from the previous step's positions.  With D_k =
+ *      ring_k - x, k in ring order, sums started at 0 and added in that order:
+ *      N = sum_k D_k x D_{k+1} (cyclic; (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x)), n = N / sqrt((N_x^2 + N_y^2) + N_z^2), 0 if N = 0;
+ *      s = (sum_k ring_k) / deg - x;  sd = (s_x n_x + s_y n_y) + s_z n_z;  sn = sd n;  st = s - sn;
+ *      u1 = 0.5 st;  u2 = f2 sn, f2 = (1 + tanh(F (2 |sd| / (l l) - E))) 0.5   [1 / rho = 2 |sn| / l^2],
+ *      E = (1 / rmin + 1 / rmax) / 2, F = 6 / (1 / rmin - 1 / rmax), rmin = 3.33 mm, rmax = 10 mm;
+ *      I(d) = v at voxel i_a = floor((x_a - d n_a) g_a + 0.5), g_a = 1 / d_a rounded to fp64, d = 1, 2, .. mm; 0 outside the volume and where v
+ *      is not finite;  Imin = max(t2, min(tm, min_{d = 1..20} I(d)));  Imax = min(tm, max(t, max_{d = 1..10} I(d)));
+ *      tl = (Imax - t2) b + t2, b = pow(f, 0.275);  f3 = 2 (Imin - tl) / (Imax - t2), 0 where Imax - t2 is not positive;
+ *      u3 = ((0.05 f3) l) n;  x' = ((x + u1) + u2) + u3.
+ *      l = the mean vertex-to-neighbour distance of the mesh, (sum_i sum_k |D_k|) / (sum_i deg_i), taken from the positions at the start of
+ *      iterations 0, 50, 100, ..: per vertex the ring in order, per thread h of 1024 its vertices h, 1024 + h, 2048 + h in order, the
+ *      butterfly over a wave, the 16 waves in ascending order.  tanh is the device library's (about an ulp).
+ *      ONE workgroup of 1024 threads runs all n_iter steps in one launch: both position buffers and the rings in LDS (60 nv bytes: 153 720
+ *      of the CU's 163 840 at level 4), one barrier per step.  level > 4 does not fit: MET2_E_UNSUPPORTED.  The volume needs one voxel at least.
+ *  4 fill (met2_bet_fill): voxel (ix, iy, iz) is inside when the ray from its centre along +z crosses the surface an odd number of times.
+ *      Per triangle, with (px, py) = (ix dx, iy dy): an edge (p, q) -- p the end of the SMALLER vertex index, so that both triangles of an
+ *      edge compute the same bits -- meets the line y = py when (p_y <= py) != (q_y <= py) (half-open: an end on the line belongs to the
+ *      side below), at x_e = p_x + ((py - p_y) (q_x - p_x)) / (q_y - p_y), z_e likewise.  None or two of a triangle's edges do; the ray crosses
+ *      the triangle when exactly one of the two has x_e > px (half-open again).  With (xl, zl) the one with x_e <= px and (xr, zr) the other:
+ *      zc = zl + ((px - xl) (zr - zl)) / (xr - xl), m = ceil(zc / dz): the crossing lies above the voxels iz < m (a voxel whose centre is on
+ *      the surface counts as above it).  A voxel is inside when an odd number of crossings has m > iz.  Every edge is decided once for
+ *      both of its triangles, so on a closed mesh every column has an even number of crossings and a ray through an edge or a vertex is
+ *      counted once.  One thread per column, integers only.  A triangle with an index outside [0, n_vertices) is skipped; a crossing whose
+ *      zc is NaN (non-finite vertices) is dropped.
+ * DEVICE pointers: v, data, mask_out [nx][ny][nz] uint8 (1 inside), vertices [nv][3] (x, y, z in mm), triangles [nt][3] int32.
+ * HOST: voxel_mm, stats and stats_out [8] = (t2, t, t98, tm, COG_x, COG_y, COG_z, r), count_out (may be NULL), met2_bet_mesh's outputs (each may be NULL):
+ * unit_vertices [nv][3], triangles [nt][3], ring [nv][6] (-1 beyond deg), deg [nv].
+ * met2_brain_mask runs 1-4 through the host code of the stage entries (which exist for tests and diagnostics); vertices_out (device,
+ * [nv][3], the final surface) and stats_out (host, 8 doubles) may be NULL.  met2_bet_evolve takes the statistics and the start vertices
+ * from the caller (vertices_out may be vertices_in), met2_bet_fill any mesh.  All but met2_bet_mean and met2_bet_fill BLOCK: the host reads
+ * the statistics back between the stages, and the evolution waits for its kernel.  Additive: MET2_ABI_VERSION stays 6.
+ * Limits: 0 < f < 1, n_iter >= 0, positive finite voxel sizes, level >= 0 (MET2_E_INVALID); level <= 4, fewer than 2^31 voxels
+ * (MET2_E_UNSUPPORTED). */
+int met2_brain_mask(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double *v, const double voxel_mm[3], double f, int32_t level,
+                    int32_t n_iter, uint8_t *mask_out, double *vertices_out, double *stats_out, void *stream);
+int met2_bet_mean(int32_t device, int64_t nvox, int32_t n_te, const double *data, double *out, void *stream);
+int met2_bet_stats(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double *v, const double voxel_mm[3], double *stats_out,
+                   int64_t *count_out, void *stream);
+int met2_bet_mesh(int32_t level, double *unit_vertices, int32_t *triangles, int32_t *ring, int32_t *deg);
+int met2_bet_evolve(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double *v, const double voxel_mm[3], const double stats[8], double f,
+                    int32_t level, int32_t n_iter, const double *vertices_in, double *vertices_out, void *stream);
+int met2_bet_fill(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double voxel_mm[3], int32_t n_vertices, const double *vertices,
+                  int32_t n_triangles, const int32_t *triangles, uint8_t *mask_out, void *stream);
+
 /* motor:293-304, TV denoising (denoise='TV'; the reference's example pipeline runs it, example_script_run_MET2_preproc_and_recon.sh:54):
  *     for every echo volume:  sigma_est = mean(estimate_sigma(vol));  vol <- denoise_tv_chambolle(vol, weight = 2 sigma_est, eps = 2e-4,
  *                                                                                                 max_num_iter = 200)

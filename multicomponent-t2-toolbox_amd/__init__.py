@@ -9,9 +9,11 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   motor.py                  create_Laplacian_matrix, fitting_slice_T2, recon_met2_arrays (voxel loop), nesma_filter, mppca_filter (MP-PCA denoising: csrc/met2_mppca.hip),
                             gibbs_filter (Gibbs-ringing removal, degibbs='yes': csrc/met2_gibbs.hip),
                             bias_field_filter (bias-field correction of the TWC map, bias_correct='yes': csrc/met2_bias.hip),
+                            brain_mask_filter (brain extraction, brain_mask='yes': csrc/met2_bet.hip),
                             gaussian_smooth, ROI mode
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
   gibbs.py                  gibbs_tables / gibbs_split / gibbs_lines: the stages of the Gibbs-ringing filter one by one (tests and diagnostics)
+  bet.py                    bet_mean / bet_stats / bet_mesh / bet_evolve / bet_fill: the stages of the brain extraction one by one (tests and diagnostics)
   nifti.py                  NIfTI-1 reader / writer for the driver's on-disk contract
   dist.py                   one-process-per-GPU voxel sharding + the single gather of output maps
   synth.py                  seeded synthetic volumes (the reference's Monte-Carlo recipe)
@@ -28,4 +30,7 @@ def __getattr__(name):
     if name == "bias_field_filter":            # motor.bias_field_filter, likewise
         from .motor import bias_field_filter
         return bias_field_filter
+    if name == "brain_mask_filter":            # motor.brain_mask_filter, likewise
+        from .motor import brain_mask_filter
+        return brain_mask_filter
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -146,6 +146,58 @@ def _degibbs_first(data, degibbs, prepared, device):
     return gibbs_filter(np.asarray(data, dtype=np.float64), device=device)
 
 
+def brain_mask_filter(data, voxel_size, f=0.4, level=4, n_iter=1000, device=0, return_surface=False):
+    """Brain extraction (met2_brain_mask in include/met2_hip.h states the algorithm: the surface model of Smith, HBM 2002, which FSL's bet
+    runs, without bet's self-intersection retry pass and its -R / -S / -B variants) on the device: `data` [nx,ny,nz], or [nx,ny,nz,nt], which
+    is averaged over the echoes first; `voxel_size` (dx, dy, dz) in mm.  The defaults are those of the reference's example script
+    (bet -m -f 0.4; level 4 is bet's mesh of 2562 vertices); parity with bet itself is unpinned.  -> uint8 mask [nx,ny,nz], 1 inside the
+    surface.  return_surface=True: (mask, vertices [nv, 3] in mm, triangles [nt, 3] int32, statistics: a dict of t2, t, t98, tm, cx, cy, cz,
+    r).  numpy in -> numpy out, CUDA tensor in -> tensors out (the triangles and the statistics are host objects either way)."""
+    from . import bet
+    as_numpy = not torch.is_tensor(data)
+    if (np.ndim(data) if as_numpy else data.dim()) not in (3, 4):
+        raise ValueError("data must be [nx,ny,nz] or [nx,ny,nz,nt]")
+    vox = np.ascontiguousarray(np.asarray(voxel_size, dtype=np.float64).reshape(-1))
+    if vox.shape != (3,):
+        raise ValueError("voxel_size must be (dx, dy, dz)")
+    dev = torch.device("cuda", device) if as_numpy else data.device
+    dd = torch.as_tensor(data, dtype=torch.float64, device=dev).contiguous()
+    if dd.dim() == 4:
+        dd = bet.bet_mean(dd)
+    nx, ny, nz = dd.shape
+    mask = torch.empty(dd.shape, dtype=torch.uint8, device=dev)
+    n = 4 ** min(max(int(level), 0), 4)
+    verts = torch.empty((10 * n + 2, 3), dtype=torch.float64, device=dev) if return_surface else None
+    st = np.zeros(8, dtype=np.float64)
+    with torch.cuda.device(dev):
+        check(lib().met2_brain_mask(dev.index or 0, nx, ny, nz, dd.data_ptr(), vox.ctypes.data_as(_dp), float(f), int(level), int(n_iter),
+                                    mask.data_ptr(), verts.data_ptr() if return_surface else None, st.ctypes.data_as(_dp),
+                                    torch.cuda.current_stream(dev).cuda_stream))
+    if not return_surface:
+        return mask.cpu().numpy() if as_numpy else mask
+    stats = {k: float(x) for k, x in zip(bet.STAT_KEYS, st)}
+    return (mask.cpu().numpy() if as_numpy else mask, verts.cpu().numpy() if as_numpy else verts, bet.bet_mesh(level)[1], stats)
+
+
+def _brain_mask_check(brain_mask, mask, data, voxel_size, prepared, distributed):
+    """brain_mask of the drivers, checked before any device work -> True when the step is to run"""
+    if brain_mask not in ("no", "yes"):
+        raise ValueError("brain_mask must be 'no' or 'yes'")
+    if brain_mask == "no":
+        return False
+    if mask is not None:
+        raise ValueError("brain_mask='yes' makes the mask itself and does not go with a mask")
+    if prepared:
+        raise ValueError("brain_mask='yes' works on the raw volume and does not go with prepared=True")
+    if distributed:
+        raise ValueError("brain_mask='yes' does not go with distributed=True")
+    if np.ndim(data) != 4:
+        raise ValueError("brain_mask='yes' needs data [nx,ny,nz,nt]")
+    if voxel_size is None or np.shape(voxel_size) != (3,):
+        raise ValueError("brain_mask='yes' needs voxel_size=(dx, dy, dz) in mm")
+    return True
+
+
 def bias_field_filter(vol, mask=None, voxel_size=(1, 1, 1), n_class=3, n_outer=4, n_em=10, fwhm=20.0, device=0, return_field=False):
     """Bias-field correction of a 3-D map (met2_bias_field in include/met2_hip.h states the algorithm: the EM estimator of Wells et al. 1996
     and Guillemaud & Brady 1997, which FSL's fast iterates, without fast's Markov random field term) on the device: `vol` [nx,ny,nz], `mask`
@@ -275,7 +327,8 @@ def _estimate_fa(plan, dd_fa, mm, FA_method, fa_index, T2s, T1s, tau, TR, alpha_
 
 def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2", FA_method="brute-force", myelin_T2=40.0,
                       fa_index=None, device=0, plan=None, denoise="None", prepared=False, FA_smooth="no", distributed=False,
-                      return_prepared=False, devices=None, bootstrap=None, degibbs="no", bias_correct="no", voxel_size=None):
+                      return_prepared=False, devices=None, bootstrap=None, degibbs="no", bias_correct="no", voxel_size=None,
+                      brain_mask="no"):
     """Steps 1-4 of motor_recon_met2 (motor:293-373, 427-472) on arrays: data [nx,ny,nz,nt] (or
     [nvox, nt]), mask [nx,ny,nz].  Mirrors the driver's preparation: data *= mask (motor:180-182),
     negative values clipped to 0 (motor:279), optional NESMA / TV filter (motor:293-333, needs a 3-D volume) or denoise='MPPCA'
@@ -292,6 +345,12 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     corrected map and 'TWC_bias' the estimated field; the other outputs, the bootstrap's included, are not touched.  Needs data [nx,ny,nz,nt]
     and voxel_size; ValueError otherwise and with distributed=True; on the devices=[...] path it runs on devices[0], on the assembled map.
     Parity with fast itself is unpinned (no Markov random field term).  bias_correct='no' (default) changes nothing.
+    brain_mask='yes' (step 3 of the reference's example script, which runs FSL's fslmaths -Tmean and bet -m -f 0.4 there): `mask` is None
+    and the mask is made by brain_mask_filter from the echo mean of the raw volume -- of the unrung one with degibbs='yes' -- with
+    voxel_size=(dx, dy, dz) in mm, after degibbs and before the mask multiply; the result carries it as 'mask' (uint8).  Needs data
+    [nx,ny,nz,nt] and voxel_size; ValueError otherwise, with a mask given, with prepared=True and with distributed=True, before any device
+    work; on the devices=[...] path it runs on devices[0].  Parity with bet itself is unpinned (no self-intersection retry).
+    brain_mask='no' (default) changes nothing.
     FA_smooth='yes' (the CLI default, motor:337-343): the flip angles are estimated on the Gaussian-smoothed volume
     (sigma = 2 voxels, every echo), the spectra on the unsmoothed one; needs a 3-D volume.
     C- and Fortran-ordered volumes (nibabel's) are both read in place.
@@ -317,9 +376,17 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
         raise ValueError("FA_method must be 'spline' or 'brute-force'")
     if denoise not in ("None", None, "none", "NESMA", "TV", "MPPCA"):
         raise ValueError("denoise must be 'None', 'NESMA', 'TV' or 'MPPCA'")
-    data = _degibbs_first(data, degibbs, prepared, devices[0] if devices else plan.device.index or 0 if plan is not None else device)
+    bet = _brain_mask_check(brain_mask, mask, data, voxel_size, prepared, distributed)
+    first_dev = devices[0] if devices else plan.device.index or 0 if plan is not None else device
+    data = _degibbs_first(data, degibbs, prepared, first_dev)
     data = np.asarray(data, dtype=np.float64)
     vol_shape = data.shape[:-1]
+    if bet:
+        made = brain_mask_filter(np.ascontiguousarray(data), voxel_size, device=first_dev)
+        res = recon_met2_arrays(data, made, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, fa_index, device, plan, denoise, False,
+                                FA_smooth, False, return_prepared, devices, bootstrap, "no", bias_correct, voxel_size)
+        res["mask"] = made
+        return res
     bias = _bias_check(bias_correct, vol_shape, voxel_size, distributed)
     nt = data.shape[-1]
     mask = np.asarray(mask).reshape(vol_shape)
@@ -599,7 +666,8 @@ def _recon_sharded(plan, dd, dd_fa, mm, reg_method, FA_method, fa_index, T2s, T1
 
 
 def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR, reg_method, reg_matrix, denoise, FA_method,
-                     FA_smooth, myelin_T2, num_cores=-1, device=0, devices=None, bootstrap=None, degibbs="no", bias_correct="no"):
+                     FA_smooth, myelin_T2, num_cores=-1, device=0, devices=None, bootstrap=None, degibbs="no", bias_correct="no",
+                     brain_mask="no"):
     """Drop-in for motor_recon_met2 (motor:165-506) with the reference's on-disk contract: NIfTI in
     (data [nx,ny,nz,nt], mask [nx,ny,nz]), ten NIfTI volumes out (MWF, IEWF, FWF, T2_M, T2_IE, TWC, FA, fsol_4D,
     Est_Signal, reg_param .nii.gz at path_to_save_data, motor:475-503).  `num_cores` is accepted and ignored (one
@@ -608,6 +676,9 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     map MPPCA_sigma.nii.gz).  degibbs='yes' (see recon_met2_arrays): the raw volume is unrung first (gibbs_filter) and written as
     Data_degibbs.nii.gz.  bias_correct='yes' (see recon_met2_arrays): TWC.nii.gz is the bias-corrected map and TWC_bias.nii.gz the
     estimated field, as the example script leaves them; the voxel size is the data header's pixdim[1:4] (absolute values, 0 read as 1).
+    brain_mask='yes' (see recon_met2_arrays): path_to_mask is None, the mask is made by brain_mask_filter from the echo mean (of the unrung
+    volume with degibbs='yes') with the header's voxel size, and Data_avg.nii.gz (the echo mean) and mask.nii.gz are written beside the
+    outputs, as the example script's step 3 leaves Data_avg and Data_mask.
     Not reproduced: the mean-spectrum PNG of motor:377-424.
     bootstrap=dict(n_rep=..., seed=...) (an extension, see recon_met2_arrays) also writes <Q>_bootstrap.nii.gz [nx,ny,nz,5] for Q in
     BOOT_QUANTITIES (BOOT_STATS along the last axis) and sigma.nii.gz; with fa='brute-force' / 'spline' also FA_bootstrap.nii.gz [nx,ny,nz,5]
@@ -615,19 +686,33 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     from . import nifti
     img = nifti.load(path_to_data)
     data = img.get_fdata().astype(np.float64, copy=False)           # Fortran-ordered, like nibabel's: read in place by the solver
-    mask = nifti.load(path_to_mask).get_fdata().astype(np.int64)
-    if data.ndim != 4 or mask.shape != data.shape[:3]:
+    if brain_mask not in ("no", "yes"):
+        raise ValueError("brain_mask must be 'no' or 'yes'")
+    if brain_mask == "yes" and path_to_mask is not None:
+        raise ValueError("brain_mask='yes' makes the mask itself and does not go with path_to_mask")
+    mask = None if brain_mask == "yes" else nifti.load(path_to_mask).get_fdata().astype(np.int64)
+    if data.ndim != 4 or (mask is not None and mask.shape != data.shape[:3]):
         raise ValueError("data must be 4-D and mask must match its first three dimensions")
     bias_kw = {}
-    if bias_correct != "no":
+    if bias_correct != "no" or brain_mask == "yes":
         pixdim = img.header.get("pixdim", (1.0,) * 8)
-        bias_kw = {"bias_correct": bias_correct, "voxel_size": tuple(abs(float(p)) or 1.0 for p in pixdim[1:4])}
+        voxel_size = tuple(abs(float(p)) or 1.0 for p in pixdim[1:4])
+    if bias_correct != "no":
+        bias_kw = {"bias_correct": bias_correct, "voxel_size": voxel_size}
     if degibbs != "no":
         data = _degibbs_first(data, degibbs, False, devices[0] if devices else device)
         nifti.save(nifti.NiftiImage(data, img.affine), path_to_save_data + "Data_degibbs.nii.gz")
+    if brain_mask == "yes":
+        from . import bet
+        avg = bet.bet_mean(np.ascontiguousarray(data), device=devices[0] if devices else device)
+        mask = brain_mask_filter(avg, voxel_size, device=devices[0] if devices else device)
+        nifti.save(nifti.NiftiImage(avg, img.affine), path_to_save_data + "Data_avg.nii.gz")
+        nifti.save(nifti.NiftiImage(mask, img.affine), path_to_save_data + "mask.nii.gz")
     res = recon_met2_arrays(data, mask, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, device=device, denoise=denoise,
                             FA_smooth=FA_smooth, return_prepared=(denoise in ("TV", "MPPCA")), devices=devices, bootstrap=bootstrap,
                             **bias_kw)
+    if brain_mask == "yes":
+        res["mask"] = mask
     if bias_kw:
         nifti.save(nifti.NiftiImage(res["TWC_bias"], img.affine), path_to_save_data + "TWC_bias.nii.gz")
     if denoise in ("TV", "MPPCA"):                                  # motor:302-303
