@@ -423,13 +423,33 @@ int met2_nesma(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te,
  *      s2 = (lambda_p - lambda_0) / (4 sqrt(gamma)); if s2 < s1: sigma2 = s1, cut = p + 1.  k = r - cut signal components;
  *   4. out[v] = U_s (U_s^T x_v) with U_s the eigenvectors of the k largest eigenvalues, sigma[v] = sqrt(sigma2), rank[v] = k.
  * mask == 0: out = 0, sigma = 0, rank = 0.  N < 2: the voxel is copied through, sigma = 0, rank = 1.  A non-finite value anywhere in the
- * patch: copied through, sigma = 0, rank = -1.  The eigen-solver (a cyclic Jacobi, stopped when every |c_ij| <= 2^-52 sqrt(c_ii c_jj))
- * capped at its 30 sweeps: copied through, sigma = 0, rank = -2.  The output is not clipped: the projection can undershoot zero at late echoes.
+ * patch: copied through, sigma = 0, rank = -1; so is a voxel whose data are finite but whose C overflows (a non-finite trace; |x| above
+ * about 1e152).  The eigen-solver (a cyclic Jacobi, stopped when every |c_ij| <= 2^-52 sqrt(c_ii c_jj), the root taken so that it neither
+ * overflows nor vanishes while C is finite) capped at its 30 sweeps: copied through, sigma = 0, rank = -2.  Scaling the data by a power of two
+ * scales out and sigma by exactly that power while nothing over- or underflows.  Below |x| of about 1e-155 the entries of C are subnormal
+ * and the accuracy degrades (a residual of 1e-10 ||C|| at 1e-160 in an emulation; unmeasured on the device).
+ * The output is not clipped: the projection can undershoot zero at late echoes.
  * MET2_E_INVALID: window even or < 3, data or out NULL, out == data.  MET2_E_UNSUPPORTED: n_te < 2 or > 63; a window whose patch list
  * (4 w^3 bytes) does not fit in the 64 KB of LDS beside the two n_te x n_te matrices (w <= 7 fits at every n_te); more than 2^26 - 1 voxels.
  * An empty volume returns MET2_OK at once.  Deterministic; asynchronous on `stream`. */
 int met2_mppca(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, const uint8_t *mask, int32_t window,
                double *out, double *sigma, int32_t *rank, void *stream);
+
+/* met2_mppca with what each of its steps leaves, for tests and diagnostics (additive; ABI stays 6).  The same kernel code, instantiated a
+ * second time; out, sigma and rank are bit for bit those of met2_mppca when max_sweeps = 30.  max_sweeps, 1..30 (else MET2_E_INVALID), is the
+ * sweep cap of the eigen-solver; a voxel that has not converged by then gets rank -2.  DEVICE pointers, each may be NULL, nvox = nx ny nz:
+ *   n_patch [nvox] int32            N, the patch's voxel count;
+ *   patch   [nvox][w^3] int32       the patch list as the kernel holds it: the flat voxel offsets pv - v, in memory order; the first N are written;
+ *   gram    [nvox][n_te][n_te]      C as stored after step 2;
+ *   eigval  [nvox][n_te]            the diagonal of C after the solver, in index order (unsorted);
+ *   eigvec  [nvox][n_te][n_te]      V after the solver: column i belongs to eigval[i];
+ *   sweeps  [nvox] int32            the sweeps run, the last one that found nothing to rotate included.
+ * A voxel with mask == 0 writes n_patch = 0 and nothing else.  A voxel copied through for N < 2 or for a non-finite value writes n_patch and
+ * patch and nothing else.  A voxel whose C overflowed also writes gram, the diagonal and the identity it started from, and sweeps = 0.  A voxel
+ * that hit the sweep cap writes everything, as it stood then.  What a voxel does not write is left as the caller had it. */
+int met2_mppca_stages(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, const uint8_t *mask, int32_t window,
+                      double *out, double *sigma, int32_t *rank, int32_t max_sweeps, int32_t *n_patch, int32_t *patch, double *gram,
+                      double *eigval, double *eigvec, int32_t *sweeps, void *stream);
 
 /* Removal of Gibbs (truncation) ringing by local sub-voxel shifts (degibbs='yes'; Kellner, Dhital, Kiselev, Reisert, MRM 2016; step 2 of the
  * reference's example pipeline, example_script_run_MET2_preproc_and_recon.sh, which runs MRtrix's mrdegibbs there; stated here from the

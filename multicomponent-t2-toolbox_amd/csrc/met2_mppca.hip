@@ -8,11 +8,14 @@
 //     3. a parallel-ordered (round-robin) cyclic Jacobi on C with the eigenvectors V accumulated, both in the wave's LDS region: each of
 //        the n - 1 steps of a sweep rotates the floor(M / 2) disjoint pairs of a tournament round -- lane k forms pair k's rotation, then
 //        the rows, then the columns of C and V are rotated with the lanes over the columns / rows, floor(64 / M) pairs side by side.
-//        A pair with |c_pq| <= eps sqrt(c_pp c_qq) is left alone; a sweep that rotates nothing ends the solver, MET2_MPPCA_MAX_SWEEPS
-//        ends it otherwise (rank -2);
+//        A pair with |c_pq| <= eps sqrt(c_pp c_qq) is left alone (the root is taken of the product while that is finite and normal, of the
+//        factors otherwise, so that the test holds at every scale at which C is finite); a sweep that rotates nothing ends the solver,
+//        MET2_MPPCA_MAX_SWEEPS ends it otherwise (rank -2);
 //     4. the ascending order of the eigenvalues by counting (lane i counts the eigenvalues before its own), the threshold rule with the
 //        cumulative sum taken in the stated order, and the projection on the kept eigenvectors.
 // Every loop is bounded by a shape or a compile-time constant.  fp64 throughout; division and square root are IEEE.
+// mppca_kernel<true> (met2_mppca_stages) is the same code that also copies what each step leaves to global memory, and takes its sweep cap
+// from the caller; mppca_kernel<false> is what met2_mppca launches.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -38,6 +41,15 @@ struct MppcaArgs {
     int32_t *rank;
 };
 
+struct MppcaStageArgs : MppcaArgs {  // what mppca_kernel<true> writes beside; each may be NULL
+    int max_sweeps;
+    int32_t *n_patch, *patch, *sweeps;
+    double *gram, *eigval, *eigvec;
+};
+
+template <bool STAGES> struct mppca_args { typedef MppcaArgs type; };
+template <> struct mppca_args<true> { typedef MppcaStageArgs type; };
+
 // the lanes of one wave exchange values through LDS: a wave's LDS accesses complete in program order, the fences keep the compiler to it
 __device__ __forceinline__ void wave_lds_sync()
 {
@@ -56,6 +68,12 @@ __device__ __forceinline__ void rr_pair(int n, int t, int k, int &p, int &q)
     q = b;
 }
 
+template <bool STAGES> __device__ __forceinline__ int sweep_cap(const typename mppca_args<STAGES>::type &A)
+{
+    if constexpr (STAGES) return A.max_sweeps;
+    else return MET2_MPPCA_MAX_SWEEPS;
+}
+
 size_t aux_bytes(int win)
 {
     const size_t list = (size_t)win * win * win * sizeof(int32_t);
@@ -63,7 +81,8 @@ size_t aux_bytes(int win)
     return (need + 15) / 16 * 16;
 }
 
-__global__ __launch_bounds__(64) void mppca_kernel(MppcaArgs A)
+template <bool STAGES>
+__global__ __launch_bounds__(64) void mppca_kernel(typename mppca_args<STAGES>::type A)
 {
     extern __shared__ __attribute__((aligned(16))) double mppca_lds[];
     const int M = A.nt, LD = A.ld;
@@ -79,6 +98,7 @@ __global__ __launch_bounds__(64) void mppca_kernel(MppcaArgs A)
     if (A.mask && A.mask[v] == 0) {
         if (mine) ov[lane] = 0.0;
         if (lane == 0) { if (A.sigma) A.sigma[v] = 0.0; if (A.rank) A.rank[v] = 0; }
+        if constexpr (STAGES) { if (A.n_patch && lane == 0) A.n_patch[v] = 0; }
         return;
     }
     const int vz = (int)(v % A.nz), vy = (int)((v / A.nz) % A.ny), vx = (int)(v / ((int64_t)A.nz * A.ny));
@@ -103,6 +123,11 @@ __global__ __launch_bounds__(64) void mppca_kernel(MppcaArgs A)
         N += __popcll(b);
     }
     wave_lds_sync();
+    if constexpr (STAGES) {                                           // the list as it stands, before aux is taken for anything else
+        if (A.n_patch && lane == 0) A.n_patch[v] = N;
+        if (A.patch)
+            for (int i = lane; i < N; i += 64) A.patch[v * ((int64_t)A.win * A.win * A.win) + i] = list[i];
+    }
     const double xc = mine ? A.data[v * M + lane] : 0.0;
 
     // 2. the Gram matrix, column `lane` in registers
@@ -133,6 +158,10 @@ __global__ __launch_bounds__(64) void mppca_kernel(MppcaArgs A)
         for (int i = 0; i < MET2_MPPCA_MAX_TE; ++i)
             if (i < M && mine) { C[i * LD + lane] = acc[i]; V[i * LD + lane] = i == lane ? 1.0 : 0.0; }
         wave_lds_sync();
+        if constexpr (STAGES) {
+            if (A.gram && mine)
+                for (int i = 0; i < M; ++i) A.gram[(v * M + i) * M + lane] = C[i * LD + lane];
+        }
 
         // 3. Jacobi
         const int n = M + (M & 1), np = n / 2;
@@ -140,10 +169,18 @@ __global__ __launch_bounds__(64) void mppca_kernel(MppcaArgs A)
         const int g = lane / M, j = lane - g * M;
         const bool work = g < G;
         double *cc = aux, *ss = aux + 32;
-        double dsum = met2::wave_sum(mine ? C[lane * LD + lane] : 0.0);
+        const double dsum = met2::wave_sum(mine ? C[lane * LD + lane] : 0.0);
         const double floor_abs = dsum * 0x1p-80;                       // below this an entry is rounding dust of forming C
+        // The rotation test's threshold is eps sqrt(|c_pp c_qq|) while that product is finite and normal, eps sqrt|c_pp| sqrt|c_qq| otherwise: it
+        // neither overflows nor vanishes while C is finite.  Every |c_pp| is at most the trace (C is positive semidefinite), so below a trace of
+        // 2^500 no product overflows; and from a trace of 2^-480 on, a product below DBL_MIN has eps times its root (by either formula, at most
+        // 2^-563) below floor_abs (at least 2^-560), so that `off > floor_abs` decides alone.  Between the two the plain root is the whole test.
+        const bool extreme = __builtin_amdgcn_readfirstlane(!(dsum >= 0x1p-480 && dsum < 0x1p500) ? 1 : 0) != 0;
         bool converged = false;
-        for (int sweep = 0; sweep < MET2_MPPCA_MAX_SWEEPS && !converged; ++sweep) {
+        const int max_sweeps = sweep_cap<STAGES>(A);
+        int sweep = 0;
+        if (!(dsum <= DBL_MAX)) { rank = -1; converged = true; }      // C overflowed on finite data: wave-uniform, copied through
+        for (; sweep < max_sweeps && !converged; ++sweep) {
             int nrot = 0;
             for (int t = 0; t < n - 1; ++t) {
                 int p = 0, q = 0;
@@ -154,7 +191,10 @@ __global__ __launch_bounds__(64) void mppca_kernel(MppcaArgs A)
                     if (p < M && q < M) {
                         app = C[p * LD + p]; aqq = C[q * LD + q]; apq = C[p * LD + q];
                         const double off = fabs(apq);
-                        rot = !(off <= DBL_EPSILON * sqrt(fabs(app * aqq))) && off > floor_abs;
+                        const double pr = fabs(app * aqq);
+                        double gm = sqrt(pr);
+                        if (__builtin_expect(extreme, 0) && !(pr <= DBL_MAX && pr >= DBL_MIN)) gm = sqrt(fabs(app)) * sqrt(fabs(aqq));
+                        rot = !(off <= DBL_EPSILON * gm) && off > floor_abs;
                     }
                     double c = 1.0, s = 0.0;
                     if (rot) {
@@ -208,8 +248,14 @@ __global__ __launch_bounds__(64) void mppca_kernel(MppcaArgs A)
             }
             converged = nrot == 0;
         }
+        if constexpr (STAGES) {
+            if (A.sweeps && lane == 0) A.sweeps[v] = sweep;
+            if (A.eigval && mine) A.eigval[v * M + lane] = C[lane * LD + lane];
+            if (A.eigvec && mine)
+                for (int i = 0; i < M; ++i) A.eigvec[(v * M + i) * M + lane] = V[i * LD + lane];
+        }
         if (!converged) rank = -2;
-        else {
+        else if (rank == 0) {
             // 4. order, threshold, projection
             const int r = min(M, N), qn = max(M, N);
             const double d = mine ? C[lane * LD + lane] : 0.0;
@@ -259,8 +305,9 @@ __global__ __launch_bounds__(64) void mppca_kernel(MppcaArgs A)
 
 }  // namespace
 
-extern "C" int met2_mppca(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, const double *data, const uint8_t *mask,
-                          int32_t window, double *out, double *sigma, int32_t *rank, void *stream)
+template <bool STAGES>
+static int mppca_launch(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, const double *data, const uint8_t *mask, int32_t window,
+                        double *out, double *sigma, int32_t *rank, void *stream, typename mppca_args<STAGES>::type A)
 {
     if (nx < 0 || ny < 0 || nz < 0) return fail(MET2_E_INVALID, "bad shape");
     if (window < 3 || window % 2 == 0) return fail(MET2_E_INVALID, "the MP-PCA window must be odd and at least 3");
@@ -274,10 +321,27 @@ extern "C" int met2_mppca(int32_t device, int32_t nx, int32_t ny, int32_t nz, in
     if (data == out) return fail(MET2_E_INVALID, "MP-PCA cannot run in place");
     if (nvox > 0x3ffffffLL) return fail(MET2_E_UNSUPPORTED, "volume too large for one launch");
     USE_DEVICE(device);
-    MppcaArgs A;
     A.nx = nx; A.ny = ny; A.nz = nz; A.nt = nt; A.win = window; A.ld = ld;
     A.data = data; A.mask = mask; A.out = out; A.sigma = sigma; A.rank = rank;
-    hipLaunchKernelGGL(mppca_kernel, dim3((unsigned)nvox), dim3(64), lds, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(mppca_kernel<STAGES>, dim3((unsigned)nvox), dim3(64), lds, (hipStream_t)stream, A);
     HIPCHK(hipGetLastError());
     return MET2_OK;
+}
+
+extern "C" int met2_mppca(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, const double *data, const uint8_t *mask,
+                          int32_t window, double *out, double *sigma, int32_t *rank, void *stream)
+{
+    return mppca_launch<false>(device, nx, ny, nz, nt, data, mask, window, out, sigma, rank, stream, MppcaArgs());
+}
+
+extern "C" int met2_mppca_stages(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, const double *data, const uint8_t *mask,
+                                 int32_t window, double *out, double *sigma, int32_t *rank, int32_t max_sweeps, int32_t *n_patch,
+                                 int32_t *patch, double *gram, double *eigval, double *eigvec, int32_t *sweeps, void *stream)
+{
+    if (max_sweeps < 1 || max_sweeps > MET2_MPPCA_MAX_SWEEPS) return fail(MET2_E_INVALID, "max_sweeps must be 1 to 30");
+    MppcaStageArgs A;
+    A.max_sweeps = max_sweeps;
+    A.n_patch = n_patch; A.patch = patch; A.sweeps = sweeps;
+    A.gram = gram; A.eigval = eigval; A.eigvec = eigvec;
+    return mppca_launch<true>(device, nx, ny, nz, nt, data, mask, window, out, sigma, rank, stream, A);
 }

@@ -37,6 +37,11 @@ def motor():
     return importlib.import_module(PKG + ".motor")
 
 
+@pytest.fixture(scope="module")
+def stages(motor):
+    return importlib.import_module(PKG + ".mppca").mppca_stages
+
+
 @functools.lru_cache(maxsize=None)
 def reference(name):
     """(data, mask, window, restatement's result) of a committed case: computed once, shared, never written to"""
@@ -74,11 +79,73 @@ def test_parity_with_the_restatement(motor):
     assert torch.is_tensor(t) and t.is_cuda and np.array_equal(t.cpu().numpy(), out)
 
 
-@pytest.mark.parametrize("name", ["M2", "M7", "M16", "M33", "M63"])
+@pytest.mark.parametrize("name", ["M2", "M7", "M16", "M33", "M63", "M3", "M21", "M22", "M31", "M62"])
 def test_echo_count_edges(motor, name):
+    # G = floor(64 / M) pairs are rotated side by side: it changes at M = 3 (two pairs in G = 21), 21 -> 22 (G = 3 -> 2), 32 -> 33 (2 -> 1);
+    # 31 and 63 are odd (a dummy player), 62 is the even maximum
     data, mask, w, ref = reference(name)
     out, sigma, rank = motor.mppca_filter(data, mask, window=w, return_maps=True)
     check_against(ref, data, out, sigma, rank)
+
+
+def test_window_7_at_63_echoes(motor):
+    # the longest patch list that fits (4 * 343 bytes, past the 1024 bytes the rotations and the spectrum share with it) on data that is not zero
+    data, mask, w, ref = reference("W7M63")
+    assert w == 7 and data.shape[-1] == 63 and ref["n"].max() > 256
+    out, sigma, rank = motor.mppca_filter(data, mask, window=w, return_maps=True)
+    check_against(ref, data, out, sigma, rank)
+
+
+@pytest.mark.parametrize("name", ["parity", "M33"])
+@pytest.mark.parametrize("e", [40, -40])
+def test_scaling_by_a_power_of_two_is_exact(stages, name, e):
+    # every operation of the kernel commutes with a power of two short of over- and underflow (the sigma's square root too: the exponent is even)
+    data, mask, w, ref = reference(name)
+    a = stages(data, mask, window=w)
+    b = stages(np.ldexp(data, e), mask, window=w)
+    assert np.array_equal(b["out"], np.ldexp(a["out"], e)) and np.array_equal(b["sigma"], np.ldexp(a["sigma"], e))
+    assert np.array_equal(b["rank"], a["rank"]) and np.array_equal(b["sweeps"], a["sweeps"])
+    assert (a["rank"][mask != 0] > 0).any()
+
+
+def test_products_of_diagonal_entries_that_overflow(motor, stages):
+    # parity x 2^250: C is finite (about 2^550), c_pp c_qq is not; the rotation test must not take +inf for its threshold
+    data, mask, w, ref = reference("parity")
+    base = motor.mppca_filter(data, mask, window=w, return_maps=True)
+    big = stages(np.ldexp(data, 250), mask, window=w)
+    assert np.isfinite(big["gram"]).all() and np.ldexp(big["gram"], -500).max() > 1e6
+    assert np.array_equal(big["rank"], base[2])
+    scale = np.abs(data).max()
+    e_out = np.abs(np.ldexp(big["out"], -250) - base[0]).max() / scale
+    print("max |out / 2^250 - out| / max|data| = %.3e" % e_out)
+    assert e_out <= 1e-9
+    worst = {}
+    M = data.shape[-1]
+    gram, ev, V = (big[k].reshape((-1,) + big[k].shape[3:]) for k in ("gram", "eigval", "eigvec"))
+    ran = np.flatnonzero((big["n_patch"].reshape(-1) >= 2) & (big["rank"].reshape(-1) >= 0))
+    assert ran.size == int((big["n_patch"] >= 2).sum())
+    for v in ran:
+        Cm = np.ldexp(gram[v], -500)                               # exact: the figures are relative
+        bounds, _ = mp.eig_bounds(Cm)
+        got = mp.eig_figures(Cm, np.ldexp(ev[v], -500), V[v])
+        for k in got:
+            worst[k] = max(worst.get(k, 0.0), got[k] / bounds[k])
+            assert got[k] <= bounds[k], (v, k, got[k], bounds[k])
+    print("max figure / bound:", {k: "%.3f" % x for k, x in worst.items()})
+    assert (big["sweeps"][big["rank"] > 0] > 1).all()
+
+
+def test_gram_matrix_that_overflows(stages):
+    # parity x 2^520: the data are finite, C is not: every voxel is copied through with rank -1
+    data, mask, w, ref = reference("parity")
+    huge = np.ldexp(data, 520)
+    assert np.isfinite(huge).all()
+    res = stages(huge, mask, window=w)
+    on = (mask != 0) & (ref["n"] >= 2)
+    assert (res["rank"][on] == -1).all() and not res["sigma"].any()
+    assert np.array_equal(res["out"], huge)
+    out, sigma, rank = importlib.import_module(PKG + ".motor").mppca_filter(huge, mask, window=w, return_maps=True)
+    assert np.array_equal(out, huge) and np.array_equal(rank, res["rank"]) and not sigma.any()
 
 
 @pytest.mark.parametrize("name", ["wide", "tiny"])

@@ -1,7 +1,9 @@
 """CPU-only: the numpy restatement of MP-PCA denoising (tests/tools/mppca_numpy.py, the reference of tests/test_gpu_mppca.py) against
 known answers, the eigh route against an SVD of the patch matrix, and the seeds the GPU parity tests commit to: on those volumes the
 restatement itself must call no voxel a tie.  The ctypes declaration of met2_mppca against the header is covered by
-test_host_logic.py, which walks every entry of SYMBOLS."""
+test_host_logic.py, which walks every entry of SYMBOLS.  Also the helpers of the stage tests (tests/test_gpu_mppca_stages.py): the matrix-case
+builders, the four eigensystem figures with np.linalg.eigh's own values of them (the yardstick of the device's), and the threshold taken from
+an unsorted spectrum."""
 import importlib
 import os
 import sys
@@ -20,8 +22,9 @@ PKG = "multicomponent-t2-toolbox_amd"
 def test_library_exports_met2_mppca():
     importlib.import_module(PKG + "._build").build()
     lib = importlib.import_module(PKG + "._lib")
-    assert "met2_mppca" in lib.SYMBOLS
-    assert hasattr(lib.lib(), "met2_mppca")
+    assert "met2_mppca" in lib.SYMBOLS and "met2_mppca_stages" in lib.SYMBOLS
+    assert hasattr(lib.lib(), "met2_mppca") and hasattr(lib.lib(), "met2_mppca_stages")
+    assert len(lib.lib().met2_mppca_stages.argtypes) == 19
     assert lib.lib().met2_abi_version() == 6
 
 
@@ -96,3 +99,95 @@ def test_committed_seeds_hold_no_ties(name):
     data, mask, w = mp.case(name)
     res = mp.mppca(data, mask, w)
     assert not mp.ties(res).any(), (res["margin"].min(), res["gap"].min())
+
+
+# ---- the helpers of tests/test_gpu_mppca_stages.py
+
+def centre_patch(name):
+    data, mask, w = mp.matrix_case(name)
+    idx = mp.patch_indices(mask, w // 2, w // 2, w // 2, w)
+    M = data.shape[-1]
+    return data, mask, w, idx, np.ascontiguousarray(data.reshape(-1, M)[idx].T)
+
+
+def test_matrix_case_names_cover_the_issue_list():
+    names = mp.matrix_case_names()
+    assert len(names) == len(set(names)) == 3 * len(mp.TWO_POOL_M) + 2 + len(mp.SPECIAL) + len(mp.SPECTRA) + len(mp.EQUAL_DIAGONAL)
+    assert mp.TWO_POOL_M == (2, 3, 7, 21, 22, 31, 32, 33, 62, 63)
+    assert "tp_M63_N343" in names and "tp_M32_N343" in names
+
+
+@pytest.mark.parametrize("name", mp.matrix_case_names())
+def test_matrix_case_centre_patch_and_eigh_figures(name):
+    data, mask, w, idx, X = centre_patch(name)
+    M, N = X.shape
+    assert mask[w // 2, w // 2, w // 2] and mp.centre(w) in idx
+    if name.endswith("_N2"):
+        assert N == 2 and idx.tolist() == [mp.centre(w) - 1, mp.centre(w)]
+    else:
+        assert N == w ** 3 and np.array_equal(idx, np.arange(N))
+    assert np.isfinite(data).all()
+    # eigh's own figures on this matrix: what 50 times of bounds the device's (floored at M 2^-52)
+    Cm = X @ X.T
+    bounds, own = mp.eig_bounds(Cm)
+    print(name, {k: "%.2e" % v for k, v in own.items()})
+    for k in ("residual", "orth", "eigval", "trace"):
+        assert np.isfinite(own[k]) and 0.0 <= own[k] <= 1e-14, (k, own[k])
+        assert bounds[k] == max(50.0 * own[k], M * 2.0 ** -52)
+
+
+def test_eig_figures_see_a_wrong_eigensystem():
+    X = mp.two_pool_matrix(7, 27, 3)
+    Cm = X @ X.T
+    d, V = np.linalg.eigh(Cm)
+    bounds, own = mp.eig_bounds(Cm)
+    assert own == mp.eig_figures(Cm, d, V)
+    V2 = V.copy()
+    V2[:, 0] += 1e-10 * V[:, 1]                                    # not orthogonal any more
+    assert mp.eig_figures(Cm, d, V2)["orth"] > bounds["orth"]
+    d2 = d.copy()
+    d2[-1] *= 1 + 1e-12
+    f = mp.eig_figures(Cm, d2, V)
+    assert f["residual"] > bounds["residual"] and f["eigval"] > bounds["eigval"] and f["trace"] > bounds["trace"]
+    assert f["orth"] == own["orth"]
+    zero = mp.eig_figures(np.zeros((4, 4)), np.zeros(4), np.eye(4))    # ||C|| taken as 1
+    assert zero == {"residual": 0.0, "orth": 0.0, "eigval": 0.0, "trace": 0.0}
+
+
+def test_from_spectrum_and_equal_diagonal():
+    for name, (spec, N) in mp.SPECTRA.items():
+        X = mp.from_spectrum(spec, N, 1)
+        assert X.shape == (len(spec), N)
+        ev = np.linalg.eigvalsh(X @ X.T)
+        assert np.max(np.abs(ev - np.sort(spec))) <= 1e-13 * max(spec), name
+    for name, (M, N, a) in mp.EQUAL_DIAGONAL.items():
+        X = mp.equal_diagonal(M, N, a)
+        assert np.array_equal(X @ X.T, (N // M) * a * a * np.eye(M)), name
+    X = centre_patch("dup_echoes")[4]
+    assert np.array_equal(X[17], X[4])
+    X = centre_patch("zero_echoes")[4]
+    assert not X[5].any() and not X[20].any() and X[6].all()
+    X = centre_patch("identical")[4]
+    assert (X == X[:, :1]).all()
+
+
+@pytest.mark.parametrize("name", ["tp_M32_N125", "tp_M33_N27", "tp_M7_N2", "noise", "zero", "clustered", "eqdiag_M3"])
+def test_threshold_from_an_unsorted_spectrum(name):
+    data, mask, w, idx, X = centre_patch(name)
+    M, N = X.shape
+    r = min(M, N)
+    xv = data[w // 2, w // 2, w // 2]
+    out, sigma, k, _, _ = mp.mppca_voxel(X, xv)
+    d, V = np.linalg.eigh(X @ X.T)
+    perm = np.random.default_rng(5).permutation(M)                 # the solver leaves the spectrum in no order
+    k2, sigma2, order, lam = mp.threshold_from_eigval(d[perm], N)
+    assert k2 == k and sigma2 == sigma
+    assert np.array_equal(d[perm][order], d) and lam.shape == (r,)
+    Vs = V[:, perm][:, order[M - k:]]
+    assert np.max(np.abs(Vs @ (Vs.T @ xv) - out)) <= 1e-12 * max(np.abs(xv).max(), 1.0)
+    if name == "noise":
+        assert k == 0 and sigma > 0
+    if name == "zero":
+        assert k == r and sigma == 0.0
+    # ties go by index: equal values keep the order of their indices
+    assert mp.threshold_from_eigval(np.array([2.0, 1.0, 2.0, 1.0]), 9)[2].tolist() == [1, 3, 0, 2]

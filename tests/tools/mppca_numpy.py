@@ -149,6 +149,12 @@ CASES = {
     "M16": ((5, 4, 3), 16, 3, 8, False),
     "M33": ((5, 4, 3), 33, 3, 5, False),            # N <= 27 < M
     "M63": ((5, 4, 3), 63, 3, 4, False),
+    "M3": ((5, 4, 3), 3, 3, 24, False),             # G = 21 pairs' room, two pairs
+    "M21": ((5, 4, 3), 21, 3, 20, False),           # G = 3
+    "M22": ((5, 4, 3), 22, 3, 18, False),           # G = 2
+    "M31": ((5, 4, 3), 31, 3, 26, False),           # odd: a dummy player, G = 2
+    "M62": ((5, 4, 3), 62, 3, 14, False),           # the even maximum
+    "W7M63": ((7, 7, 7), 63, 7, 54, False),         # the longest patch list (343 entries) beside the largest matrices
     "wide": ((3, 9, 2), 12, 7, 9, False),           # the window wider than the volume
     "tiny": ((2, 2, 2), 12, 3, 10, False),
     "driver": ((8, 8, 4), 32, 5, 12, False),
@@ -160,3 +166,144 @@ def case(name):
     shape, M, w, seed, edge = CASES[name]
     data, mask = two_pool_volume(shape, M, seed, edge_line=edge)
     return data, mask, w
+
+
+# ---- matrix cases: a cube of side w whose centre voxel's patch (window w) is the whole cube, so that the centre's C = X X^T is a matrix the
+# test chose.  tests/test_gpu_mppca_stages.py looks at the centre voxel of each; tests/test_mppca_host.py at what eigh makes of them.
+
+def cube(X, n2=False):
+    """X [M, N] with N = w^3 (w = 3, 5, 7) -> (data [w, w, w, M], mask, w): voxel n of the cube, in memory order, holds column n.  n2: the mask
+    keeps the centre and the voxel before it only (N = 2)."""
+    M, N = X.shape
+    w = int(round(N ** (1.0 / 3.0)))
+    assert w ** 3 == N and w in (3, 5, 7)
+    data = np.ascontiguousarray(X.T).reshape(w, w, w, M)
+    mask = np.ones((w, w, w), dtype=np.uint8)
+    if n2:
+        mask[...] = 0
+        mask[w // 2, w // 2, w // 2 - 1:w // 2 + 1] = 1
+        data = data * mask[..., None]
+    return data, mask, w
+
+
+def from_spectrum(spec, N, seed):
+    """X [M, N] = Q sqrt(diag(spec)) W^T with Q [M, M] and W [N, M] orthonormal (N >= M): X X^T = Q diag(spec) Q^T up to rounding"""
+    spec = np.asarray(spec, dtype=np.float64)
+    M = spec.size
+    assert N >= M
+    rng = np.random.default_rng(seed)
+    Q, _ = np.linalg.qr(rng.standard_normal((M, M)))
+    W, _ = np.linalg.qr(rng.standard_normal((N, M)))
+    return (Q * np.sqrt(spec)) @ W.T
+
+
+def two_pool_matrix(M, N, seed):
+    """two-pool curves of N voxels as X [M, N]"""
+    w = int(round(N ** (1.0 / 3.0)))
+    data, _ = two_pool_volume((w, w, w), M, seed, holes=0)
+    return np.ascontiguousarray(data.reshape(N, M).T)
+
+
+def equal_diagonal(M, N, a):
+    """voxel n holds a e_(n mod M): with M | N every echo is hit N / M times and C = (N / M) a^2 I exactly"""
+    assert N % M == 0
+    X = np.zeros((M, N))
+    X[np.arange(N) % M, np.arange(N)] = a
+    return X
+
+
+TWO_POOL_M = (2, 3, 7, 21, 22, 31, 32, 33, 62, 63)          # the echo counts at which G = floor(64 / M) or the tournament's shape changes
+
+
+def _special(name):
+    rng = np.random.default_rng(100 + sorted(SPECIAL).index(name))
+    if name == "noise":                                      # zero-mean Gaussian noise: the rule keeps nothing
+        return rng.standard_normal((32, 125)) * 10.0
+    if name == "rank1":
+        return from_spectrum([0.0] * 31 + [5.0e6], 125, 21)
+    if name == "rank2":
+        return from_spectrum([0.0] * 30 + [3.0e4, 5.0e6], 125, 22)
+    if name == "identical":                                  # every voxel the same curve
+        return np.repeat(two_pool_matrix(32, 125, 23)[:, :1], 125, axis=1)
+    if name == "constant":
+        return np.full((32, 125), 37.0)
+    if name == "zero":
+        return np.zeros((32, 125))
+    X = two_pool_matrix(32, 125, 24)
+    if name == "zero_echoes":
+        X[[5, 20]] = 0.0
+    if name == "dup_echoes":
+        X[17] = X[4]
+    return X
+
+
+SPECIAL = {"noise", "rank1", "rank2", "identical", "constant", "zero", "zero_echoes", "dup_echoes"}
+SPECTRA = {
+    "clustered": ([1.0] * 10 + [4.0] * 10 + [9.0] * 12, 125),
+    "graded32": ([10.0 ** -p for p in range(32)], 125),
+    "graded63": ([10.0 ** (-p / 4.0) for p in range(63)], 343),
+}
+EQUAL_DIAGONAL = {"eqdiag_M3": (3, 27, 3.0), "eqdiag_M25": (25, 125, 0.75)}
+
+
+def matrix_case_names():
+    names = ["tp_M%d_N%d" % (M, N) for M in TWO_POOL_M for N in (2, 27, 125)] + ["tp_M63_N343", "tp_M32_N343"]
+    return names + sorted(SPECIAL) + sorted(SPECTRA) + sorted(EQUAL_DIAGONAL)
+
+
+def matrix_case(name):
+    """-> (data [w, w, w, M], mask, w): the centre voxel's patch is the whole cube (for ..._N2 the centre and one neighbour)"""
+    if name.startswith("tp_"):
+        M, N = (int(s[1:]) for s in name.split("_")[1:])
+        return cube(two_pool_matrix(M, max(N, 27), 40 + M), n2=(N == 2))
+    if name in SPECIAL:
+        return cube(_special(name))
+    if name in SPECTRA:
+        spec, N = SPECTRA[name]
+        return cube(from_spectrum(spec, N, 30 + len(spec)))
+    M, N, a = EQUAL_DIAGONAL[name]
+    return cube(equal_diagonal(M, N, a))
+
+
+def centre(w):
+    """the flat index of the cube's centre voxel"""
+    return (w ** 3) // 2
+
+
+def eig_figures(Cm, d, V):
+    """how good (d, V) is as an eigensystem of the symmetric Cm, each figure relative to ||Cm||_2 (1 where Cm is zero): the residual
+    ||Cm V - V diag(d)||_2, max |V^T V - I| (absolute: V has unit scale), max |sort(d) - eigvalsh(Cm)| and |tr Cm - sum d|.  The products are
+    taken in long double so that the figures are those of (d, V) and not of this function."""
+    Cm = np.asarray(Cm, dtype=np.float64)
+    L = np.longdouble
+    nrm = np.linalg.norm(Cm, 2)
+    nrm = float(nrm) if nrm > 0 else 1.0
+    R = Cm.astype(L) @ V.astype(L) - V.astype(L) * d.astype(L)[None, :]
+    O = V.astype(L).T @ V.astype(L) - np.eye(V.shape[0], dtype=L)
+    return {"residual": float(np.linalg.norm(R.astype(np.float64), 2)) / nrm,
+            "orth": float(np.abs(O).max()),
+            "eigval": float(np.abs(np.sort(d) - np.linalg.eigvalsh(Cm)).max()) / nrm,
+            "trace": float(abs(np.trace(Cm.astype(L)) - d.astype(L).sum())) / nrm}
+
+
+EIG_MARGIN = 50.0           # Jacobi applies some hundreds of rotations per column where LAPACK applies O(M) reflectors
+
+
+def eig_bounds(Cm):
+    """the bound of each figure for a solver under test: EIG_MARGIN times np.linalg.eigh's own figure on the same matrix, floored at M 2^-52"""
+    d, V = np.linalg.eigh(Cm)
+    own = eig_figures(Cm, d, V)
+    floor = Cm.shape[0] * 2.0 ** -52
+    return {k: max(EIG_MARGIN * v, floor) for k, v in own.items()}, own
+
+
+def threshold_from_eigval(d, N):
+    """the kernel's step 4 on the solver's unsorted diagonal d [M] with N patch voxels: the stable ascending order (ties by index), lambda =
+    max(d, 0) / q of the top r, the threshold loop -> (k, sigma, order, lam): order[M - k:] are the indices of the kept eigenvectors"""
+    d = np.asarray(d, dtype=np.float64)
+    M = d.size
+    r, q = min(M, N), max(M, N)
+    order = np.argsort(d, kind="stable")
+    lam = np.maximum(d[order][M - r:], 0.0) / float(q)
+    cut, sigma2, _ = threshold(lam, q)
+    return r - cut, np.sqrt(sigma2), order, lam
