@@ -543,6 +543,54 @@ int met2_gibbs_lines(int32_t device, int32_t n, int32_t nlines, const double *li
 int met2_bias_field(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double *v, const uint8_t *mask, const double voxel_mm[3],
                     int32_t n_class, int32_t n_outer, int32_t n_em, double fwhm_mm, double *out, double *field, double *classes, void *stream);
 
+/* The stages of met2_bias_field one by one, for tests and diagnostics.  Each launches the kernels of met2_bias_field through the host code
+ * that met2_bias_field itself runs, on input the caller supplies; each allocates and frees what it needs and BLOCKS (it enqueues on `stream`,
+ * waits for it and copies its small results to the host).  n = the voxels of the volume, N = n_domain, np = ceil(N / 1024), K = n_class.
+ * DEVICE pointers: v, y, b, out, field [n] fp64; mask [n] uint8 or NULL; idx [n] int32; in, out of the smoothing, smoothed, rw_out [n][2].
+ * HOST pointers: everything else.  idx[0..N) must hold voxel indices in [0, n): the kernels index y and b with them unchecked, as they do
+ * with the list met2_bias_field makes for itself.  Additive: MET2_ABI_VERSION stays 6.
+ *
+ * met2_bias_weights (host only, no device): step 1's radii and weights as met2_bias_field makes them: radius_out [3]; weights_out, room for
+ *   3 x 129 doubles, gets w_x[2 r_x + 1], w_y[2 r_y + 1], w_z[2 r_z + 1] one after the other, the layout met2_bias_smooth takes.
+ * met2_bias_domain (log, scan, compact): y = log v on Omega and 0 off it, all n written; idx[0..N) = Omega's voxel indices in ascending order,
+ *   idx[N..n) untouched; *n_domain = N.  A zero-sized volume: *n_domain = 0, MET2_OK, nothing written.
+ * met2_bias_init (stat1, stat1_final, stat2, init), step 2 on the caller's y, idx, N (N = 0 is allowed).  Each out may be NULL:
+ *   stats_out [4] = lo, hi, mean of y over idx[0..N), and 1.0 when N = 0 or hi == lo (degenerate), else 0.0;  hist_out [256] uint32, all 0 when
+ *   degenerate;  ss_part_out [np]: the partial sums of (y - mean)^2 over the chunks of 1024 consecutive list entries, in the order of step-1's
+ *   note below, untouched when degenerate (bias_init_kernel adds them up: var_k = (their sum) / N / K^2);  classes_out [3 K] = mu, var, pi, the
+ *   degenerate classes (mu = lo, var = 0, pi = 1 / K) when degenerate.
+ * met2_bias_em: classes_in [3 K] = mu, var, pi go into the device record, lc_k = -inf when pi_k == 0, otherwise log(pi_k) - 0.5 log(var_k) (the
+ *   M-step's own rule, evaluated on the device); then n_em >= 0 times E-step and M-step with u = y - b; then, when rw_out is not NULL, the
+ *   final E-step: rw_out[i] = (R, W) on idx[0..N) and (0, 0) elsewhere, all n pairs written.  Each may be NULL: part_out [3][K][np], the LAST
+ *   E-step's partial sums per chunk of the list: [0] of p_k, [1] of p_k u, [2] of p_k (u - m_k)^2 about the mean m_k that E-step ran with;
+ *   untouched when n_em = 0.  classes_out [3 K]: mu, var, pi after the last M-step (classes_in when n_em = 0).  The M-step adds the np
+ *   partials of a sum in this order: thread h of 256 adds partials h, 256 + h, 512 + h, .. in that order, a butterfly (xor 32, 16, .. 1)
+ *   adds the 64 lanes of a wave, the four waves add as (0 + 1) + (2 + 3) -- the order of every second-stage sum of the filter; within a chunk
+ *   thread h adds entries h, 256 + h, 512 + h, 768 + h, then the same butterfly and the same four waves.  N >= 1, finite mu, finite var > 0,
+ *   finite pi >= 0 (MET2_E_INVALID otherwise).
+ * met2_bias_smooth: the three passes x, y, z (axis = -1) or the pass of one axis (axis = 0, 1, 2) on the two channels of `in`, with the
+ *   caller's radii and weights: radius[3], each in 0..64; weights = w_x[2 r_x + 1], w_y[2 r_y + 1], w_z[2 r_z + 1] one after the other (all
+ *   three even when one axis is asked for).  out[i] = sum_t w[t + r] in[i + t] along the axis, zeros outside the volume, t ascending, each
+ *   tap a fused multiply-add.  out may be in.
+ * met2_bias_update (update, bmean, bmean_final, recentre): b += S_R / S_W where S_W > 0 (smoothed[i] = (S_R, S_W)); *bmean_out = the mean of
+ *   that b over idx[0..N) (NULL allowed; 0 when N = 0, and b is then not recentred); b -= that mean where S_W > 0.  b is updated in place and
+ *   untouched elsewhere.
+ * met2_bias_apply: field = exp(b) (NULL allowed), out = v / field where v is finite, a non-finite v copied through; out must not be v.
+ * The checks and codes are those of met2_bias_field where they apply; n < 1 (but for met2_bias_domain and met2_bias_apply, which return
+ * MET2_OK at once for n = 0), N outside 0..n and axis outside -1..2 are MET2_E_INVALID; all before any launch. */
+int met2_bias_weights(double fwhm_mm, const double voxel_mm[3], int32_t *radius_out, double *weights_out);
+int met2_bias_domain(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double *v, const uint8_t *mask, double *y, int32_t *idx,
+                     int64_t *n_domain, void *stream);
+int met2_bias_init(int32_t device, int64_t n, const double *y, const int32_t *idx, int64_t n_domain, int32_t n_class, double *stats_out,
+                   uint32_t *hist_out, double *ss_part_out, double *classes_out, void *stream);
+int met2_bias_em(int32_t device, int64_t n, const double *y, const double *b, const int32_t *idx, int64_t n_domain, int32_t n_class,
+                 const double *classes_in, int32_t n_em, double *part_out, double *classes_out, double *rw_out, void *stream);
+int met2_bias_smooth(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double *in, const int32_t radius[3], const double *weights,
+                     int32_t axis, double *out, void *stream);
+int met2_bias_update(int32_t device, int64_t n, double *b, const double *smoothed, const int32_t *idx, int64_t n_domain, double *bmean_out,
+                     void *stream);
+int met2_bias_apply(int32_t device, int64_t n, const double *v, const double *b, double *out, double *field, void *stream);
+
 /* Brain extraction (brain_mask='yes'; an extension: the reference's example pipeline makes the mask on the CPU, with FSL's
  * `fslmaths -Tmean` and `bet -m -f 0.4`, example_script_run_MET2_preproc_and_recon.sh step 3).  The surface model of Smith, Fast robust
  * automated brain extraction, HBM 17:143-155, 2002 -- the model bet runs -- WITHOUT bet's self-intersection retry pass, its skull and

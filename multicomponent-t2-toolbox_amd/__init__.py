@@ -14,6 +14,7 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
   gibbs.py                  gibbs_tables / gibbs_split / gibbs_lines: the stages of the Gibbs-ringing filter one by one (tests and diagnostics)
   bet.py                    bet_mean / bet_stats / bet_mesh / bet_evolve / bet_fill: the stages of the brain extraction one by one (tests and diagnostics)
+  bias.py                   bias_weights / bias_domain / bias_init / bias_em / bias_smooth / bias_update / bias_apply: the stages of the bias-field correction one by one (tests and diagnostics)
   mppca.py                  mppca_stages: the MP-PCA denoiser with what each of its steps leaves (tests and diagnostics)
   nifti.py                  NIfTI-1 reader / writer for the driver's on-disk contract
   dist.py                   one-process-per-GPU voxel sharding + the single gather of output maps

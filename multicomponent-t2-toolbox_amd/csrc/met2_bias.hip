@@ -22,6 +22,8 @@
 #include <stdint.h>
 
 #include <cmath>
+#include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/met2_hip.h"
@@ -452,6 +454,137 @@ __global__ __launch_bounds__(256) void bias_apply_kernel(const double *__restric
     }
 }
 
+
+// lc of classes the host wrote into the record, by bias_mstep_kernel's rule (met2_bias_em only; met2_bias_field never launches it)
+__global__ __launch_bounds__(64) void bias_lc_kernel(BiasStats *st, int K)
+{
+    const int k = threadIdx.x;
+    if (k < K) {
+        const double pi = st->pi[k], var = st->var[k];
+        st->lc[k] = pi == 0.0 ? -INFINITY : log(pi) - 0.5 * log(var);
+    }
+}
+
+// ---- the host code of the stages: each enqueues its launches on st and reads nothing back.  met2_bias_field and the stage entries below
+// ---- (met2_bias_domain .. met2_bias_apply) run these helpers and launch no kernel of the filter otherwise.
+struct BiasGrid {
+    int64_t n;                            // voxels
+    int nch;                              // chunks of the volume; of the compacted list at most as many
+    unsigned nel;                         // workgroups of the per-voxel kernels
+};
+
+BiasGrid bias_grid(int64_t n)
+{
+    BiasGrid g;
+    g.n = n;
+    g.nch = (int)((n + BIAS_CHUNK - 1) / BIAS_CHUNK);
+    g.nel = (unsigned)((n + 255) / 256);
+    return g;
+}
+
+// step 1's radii and weights on the host: hw[a][2 BIAS_MAX_R + 1], axis a's 2 rad[a] + 1 weights first in its row
+int bias_weights(double fwhm_mm, const double voxel_mm[3], int rad[3], double *hw)
+{
+    for (int a = 0; a < 3; ++a) {
+        const double sigma = fwhm_mm / (2.0 * std::sqrt(2.0 * std::log(2.0))) / voxel_mm[a];
+        if (4.0 * sigma + 0.5 >= (double)(BIAS_MAX_R + 1)) return fail(MET2_E_UNSUPPORTED, "the smoothing kernel reaches further than 64 voxels");
+        rad[a] = (int)(4.0 * sigma + 0.5);
+        double *w = hw + a * (2 * BIAS_MAX_R + 1), sum = 0.0;
+        for (int t = -rad[a]; t <= rad[a]; ++t) {
+            w[t + rad[a]] = rad[a] == 0 ? 1.0 : std::exp(-((double)t * (double)t) / (2.0 * sigma * sigma));
+            sum += w[t + rad[a]];
+        }
+        for (int t = 0; t <= 2 * rad[a]; ++t) w[t] /= sum;
+    }
+    return MET2_OK;
+}
+
+size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+
+// y, dom, the chunks' counts and offsets, idx[0..N), S->N
+void enq_domain(hipStream_t st, const BiasGrid &g, const double *v, const uint8_t *mask, double *y, uint8_t *dom, int32_t *cnt, int32_t *off,
+                int32_t *idx, BiasStats *S)
+{
+    const dim3 T(256), GC(g.nch), G1(1);
+    hipLaunchKernelGGL(bias_log_kernel, GC, T, 0, st, v, mask, g.n, y, dom, cnt);
+    hipLaunchKernelGGL(bias_scan_kernel, G1, T, 0, st, cnt, g.nch, off, S);
+    hipLaunchKernelGGL(bias_compact_kernel, GC, T, 0, st, dom, g.n, off, idx);
+}
+
+// lo, hi, mean, degenerate, the histogram and the initial classes; part[0..np) is left holding the partials of sum (y - mean)^2
+void enq_init(hipStream_t st, const BiasGrid &g, const double *y, const int32_t *idx, BiasStats *S, double *part, int K)
+{
+    const dim3 T(256), GC(g.nch), G1(1);
+    hipLaunchKernelGGL(bias_stat1_kernel, GC, T, 0, st, y, idx, S, g.nch, part);
+    hipLaunchKernelGGL(bias_stat1_final, G1, T, 0, st, part, g.nch, S);
+    hipLaunchKernelGGL(bias_stat2_kernel, GC, T, 0, st, y, idx, S, part);
+    hipLaunchKernelGGL(bias_init_kernel, G1, T, 0, st, part, S, K);
+}
+
+// one E-step and one M-step; part is left holding the partials of the 3 K sums
+void enq_em_step(hipStream_t st, const BiasGrid &g, const double *y, const double *b, const int32_t *idx, BiasStats *S, int K, double *part)
+{
+    const dim3 T(256), GC(g.nch), G1(1);
+    hipLaunchKernelGGL(bias_estep_kernel<false>, GC, T, 0, st, y, b, idx, S, K, g.nch, part, (double2 *)nullptr);
+    hipLaunchKernelGGL(bias_mstep_kernel, G1, T, 0, st, part, g.nch, S, K);
+}
+
+// RW = (R, W) on the domain and 0 off it; rw_bytes of it are cleared first
+hipError_t enq_rw(hipStream_t st, const BiasGrid &g, const double *y, const double *b, const int32_t *idx, const BiasStats *S, int K, double2 *RW,
+                  size_t rw_bytes)
+{
+    const hipError_t e = hipMemsetAsync(RW, 0, rw_bytes, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(bias_estep_kernel<true>, dim3(g.nch), dim3(256), 0, st, y, b, idx, S, K, g.nch, (double *)nullptr, RW);
+    return hipSuccess;
+}
+
+// x: nx samples at stride ny nz, the lines are the ny nz contiguous voxels; y: per x a slab of nz lines; z: contiguous, one line per (x, y)
+SmoothArgs smooth_args(int a, int nx, int ny, int nz, const double2 *src, double2 *dst, const double *w, int r)
+{
+    SmoothArgs P;
+    P.src = src; P.dst = dst; P.w = w; P.r = r;
+    if (a == 0) { P.A = nx; P.C = (int)((int64_t)ny * nz); P.O = 1; P.sa = (int64_t)ny * nz; P.sc = 1; P.so = 0; }
+    else if (a == 1) { P.A = ny; P.C = nz; P.O = nx; P.sa = nz; P.sc = 1; P.so = (int64_t)ny * nz; }
+    else { P.A = nz; P.C = (int)((int64_t)nx * ny); P.O = 1; P.sa = 1; P.sc = nz; P.so = 0; }
+    return P;
+}
+
+void enq_smooth(hipStream_t st, int a, const SmoothArgs &P)
+{
+    const int64_t tiles = (int64_t)((P.A + BIAS_TA - 1) / BIAS_TA) * ((P.C + BIAS_TC - 1) / BIAS_TC) * P.O;      // <= n
+    if (a == 2)
+        hipLaunchKernelGGL(bias_smooth_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, st, P);
+    else
+        hipLaunchKernelGGL(bias_smooth_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, st, P);
+}
+
+// b += S_R / S_W on D, S->bmean = mean_Omega(b), b -= bmean on D
+void enq_update(hipStream_t st, const BiasGrid &g, const double2 *SRW, const int32_t *idx, BiasStats *S, double *part, double *b)
+{
+    const dim3 T(256), GC(g.nch), GE(g.nel), G1(1);
+    hipLaunchKernelGGL(bias_update_kernel, GE, T, 0, st, SRW, g.n, b);
+    hipLaunchKernelGGL(bias_bmean_kernel, GC, T, 0, st, b, idx, S, part);
+    hipLaunchKernelGGL(bias_bmean_final, G1, T, 0, st, part, S);
+    hipLaunchKernelGGL(bias_recentre_kernel, GE, T, 0, st, SRW, g.n, S, b);
+}
+
+void enq_apply(hipStream_t st, const BiasGrid &g, const double *v, const double *b, const BiasStats *S, int K, double *out, double *field,
+               double *classes)
+{
+    hipLaunchKernelGGL(bias_apply_kernel, dim3(g.nel), dim3(256), 0, st, v, b, g.n, S, K, out, field, classes);
+}
+
+// what every stage entry does last: wait, give the work space back, report
+int bias_finish(const char *who, hipError_t err, hipStream_t st, void *work)
+{
+    if (err == hipSuccess) err = hipGetLastError();
+    const hipError_t e = hipStreamSynchronize(st);
+    if (err == hipSuccess) err = e;
+    (void)hipFree(work);
+    return err == hipSuccess ? MET2_OK : fail(MET2_E_HIP, std::string(who) + ": " + hipGetErrorString(err));
+}
+
 }  // namespace
 
 extern "C" int met2_bias_field(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double *v, const uint8_t *mask, const double voxel_mm[3],
@@ -473,25 +606,15 @@ extern "C" int met2_bias_field(int32_t device, int32_t nx, int32_t ny, int32_t n
     if (n > 0x7fffffffLL) return fail(MET2_E_UNSUPPORTED, "volume too large");
     int rad[3];
     std::vector<double> hw(3 * (2 * BIAS_MAX_R + 1), 0.0);
-    for (int a = 0; a < 3; ++a) {
-        const double sigma = fwhm_mm / (2.0 * std::sqrt(2.0 * std::log(2.0))) / voxel_mm[a];
-        if (4.0 * sigma + 0.5 >= (double)(BIAS_MAX_R + 1)) return fail(MET2_E_UNSUPPORTED, "the smoothing kernel reaches further than 64 voxels");
-        rad[a] = (int)(4.0 * sigma + 0.5);
-        double *w = hw.data() + a * (2 * BIAS_MAX_R + 1), sum = 0.0;
-        for (int t = -rad[a]; t <= rad[a]; ++t) {
-            w[t + rad[a]] = rad[a] == 0 ? 1.0 : std::exp(-((double)t * (double)t) / (2.0 * sigma * sigma));
-            sum += w[t + rad[a]];
-        }
-        for (int t = 0; t <= 2 * rad[a]; ++t) w[t] /= sum;
-    }
+    if (int rc = bias_weights(fwhm_mm, voxel_mm, rad, hw.data())) return rc;
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
 
-    const int nch = (int)((n + BIAS_CHUNK - 1) / BIAS_CHUNK);           // chunks of the volume; of the compacted list at most as many
-    const unsigned nel = (unsigned)((n + 255) / 256);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t b_d = up((size_t)n * 8), b_rw = up((size_t)n * 16), b_idx = up((size_t)n * 4), b_dom = up((size_t)n), b_cnt = up((size_t)nch * 4);
-    const size_t b_part = up((size_t)nch * 3 * BIAS_MAX_K * 8), b_st = up(sizeof(BiasStats)), b_w = up(hw.size() * 8);
+    const BiasGrid g = bias_grid(n);
+    const int nch = g.nch;
+    const size_t b_d = up256((size_t)n * 8), b_rw = up256((size_t)n * 16), b_idx = up256((size_t)n * 4), b_dom = up256((size_t)n),
+                 b_cnt = up256((size_t)nch * 4);
+    const size_t b_part = up256((size_t)nch * 3 * BIAS_MAX_K * 8), b_st = up256(sizeof(BiasStats)), b_w = up256(hw.size() * 8);
     char *work = nullptr;
     HIPCHK(hipMalloc(&work, 2 * b_d + 2 * b_rw + b_idx + b_dom + 2 * b_cnt + b_part + b_st + b_w));
     char *at = work;
@@ -508,55 +631,260 @@ extern "C" int met2_bias_field(int32_t device, int32_t nx, int32_t ny, int32_t n
     int rc = MET2_OK;
     hipError_t err = hipSuccess;
     auto ok = [&](hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; return err == hipSuccess; };
-    const dim3 T(256), GC(nch), GE(nel), G1(1);
     ok(hipMemsetAsync(S, 0, b_st, st));
     ok(hipMemsetAsync(b, 0, b_d, st));
     ok(hipMemcpyAsync(wd, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, st));      // hw lives until the wait below
     if (err == hipSuccess) {
-        hipLaunchKernelGGL(bias_log_kernel, GC, T, 0, st, v, mask, n, y, dom, cnt);
-        hipLaunchKernelGGL(bias_scan_kernel, G1, T, 0, st, cnt, nch, off, S);
-        hipLaunchKernelGGL(bias_compact_kernel, GC, T, 0, st, dom, n, off, idx);
-        hipLaunchKernelGGL(bias_stat1_kernel, GC, T, 0, st, y, idx, S, nch, part);
-        hipLaunchKernelGGL(bias_stat1_final, G1, T, 0, st, part, nch, S);
-        hipLaunchKernelGGL(bias_stat2_kernel, GC, T, 0, st, y, idx, S, part);
-        hipLaunchKernelGGL(bias_init_kernel, G1, T, 0, st, part, S, n_class);
+        enq_domain(st, g, v, mask, y, dom, cnt, off, idx, S);
+        enq_init(st, g, y, idx, S, part, n_class);
         ok(hipGetLastError());
     }
     SmoothArgs P[3];
-    for (int a = 0; a < 3; ++a) {
-        P[a].w = wd + a * (2 * BIAS_MAX_R + 1);
-        P[a].r = rad[a];
-    }
-    // x: nx samples at stride ny nz, the lines are the ny nz contiguous voxels; y: per x a slab of nz lines; z: contiguous, one line per (x, y)
-    P[0].src = RA; P[0].dst = RB; P[0].A = nx; P[0].C = (int)((int64_t)ny * nz); P[0].O = 1; P[0].sa = (int64_t)ny * nz; P[0].sc = 1; P[0].so = 0;
-    P[1].src = RB; P[1].dst = RA; P[1].A = ny; P[1].C = nz; P[1].O = nx; P[1].sa = nz; P[1].sc = 1; P[1].so = (int64_t)ny * nz;
-    P[2].src = RA; P[2].dst = RB; P[2].A = nz; P[2].C = (int)((int64_t)nx * ny); P[2].O = 1; P[2].sa = 1; P[2].sc = nz; P[2].so = 0;
+    P[0] = smooth_args(0, nx, ny, nz, RA, RB, wd, rad[0]);
+    P[1] = smooth_args(1, nx, ny, nz, RB, RA, wd + (2 * BIAS_MAX_R + 1), rad[1]);
+    P[2] = smooth_args(2, nx, ny, nz, RA, RB, wd + 2 * (2 * BIAS_MAX_R + 1), rad[2]);
     for (int it = 0; it < n_outer && err == hipSuccess; ++it) {
-        for (int em = 0; em < n_em; ++em) {
-            hipLaunchKernelGGL(bias_estep_kernel<false>, GC, T, 0, st, y, b, idx, S, n_class, nch, part, (double2 *)nullptr);
-            hipLaunchKernelGGL(bias_mstep_kernel, G1, T, 0, st, part, nch, S, n_class);
-        }
-        if (!ok(hipMemsetAsync(RA, 0, b_rw, st))) break;               // R = W = 0 off the domain; the y pass of the last round wrote here
-        hipLaunchKernelGGL(bias_estep_kernel<true>, GC, T, 0, st, y, b, idx, S, n_class, nch, (double *)nullptr, RA);
-        for (int a = 0; a < 3; ++a) {
-            const int64_t tiles = (int64_t)((P[a].A + BIAS_TA - 1) / BIAS_TA) * ((P[a].C + BIAS_TC - 1) / BIAS_TC) * P[a].O;      // <= n
-            if (a == 2)
-                hipLaunchKernelGGL(bias_smooth_kernel<true>, dim3((unsigned)tiles), T, 0, st, P[a]);
-            else
-                hipLaunchKernelGGL(bias_smooth_kernel<false>, dim3((unsigned)tiles), T, 0, st, P[a]);
-        }
-        hipLaunchKernelGGL(bias_update_kernel, GE, T, 0, st, RB, n, b);
-        hipLaunchKernelGGL(bias_bmean_kernel, GC, T, 0, st, b, idx, S, part);
-        hipLaunchKernelGGL(bias_bmean_final, G1, T, 0, st, part, S);
-        hipLaunchKernelGGL(bias_recentre_kernel, GE, T, 0, st, RB, n, S, b);
+        for (int em = 0; em < n_em; ++em) enq_em_step(st, g, y, b, idx, S, n_class, part);
+        if (!ok(enq_rw(st, g, y, b, idx, S, n_class, RA, b_rw))) break;  // R = W = 0 off the domain; the y pass of the last round wrote here
+        for (int a = 0; a < 3; ++a) enq_smooth(st, a, P[a]);
+        enq_update(st, g, RB, idx, S, part, b);
         ok(hipGetLastError());
     }
     if (err == hipSuccess) {
-        hipLaunchKernelGGL(bias_apply_kernel, GE, T, 0, st, v, b, n, S, n_class, out, field, classes);
+        enq_apply(st, g, v, b, S, n_class, out, field, classes);
         ok(hipGetLastError());
     }
     ok(hipStreamSynchronize(st));                                       // the work space goes back before the call returns
     if (err != hipSuccess) rc = fail(MET2_E_HIP, std::string("met2_bias_field: ") + hipGetErrorString(err));
     (void)hipFree(work);
     return rc;
+}
+
+// ---- the stages one by one, for tests and diagnostics (include/met2_hip.h) ----
+
+static int bias_check_list(int64_t n, const void *idx, int64_t N)
+{
+    if (n < 1) return fail(MET2_E_INVALID, "the bias stages need at least one voxel");
+    if (N < 0 || N > n) return fail(MET2_E_INVALID, "the domain's size must lie in 0..n");
+    if (!idx) return fail(MET2_E_INVALID, "NULL argument");
+    if (n > 0x7fffffffLL) return fail(MET2_E_UNSUPPORTED, "volume too large");
+    return MET2_OK;
+}
+
+extern "C" int met2_bias_weights(double fwhm_mm, const double voxel_mm[3], int32_t *radius_out, double *weights_out)
+{
+    if (!voxel_mm || !radius_out || !weights_out) return fail(MET2_E_INVALID, "NULL argument");
+    if (!(fwhm_mm > 0.0) || !std::isfinite(fwhm_mm)) return fail(MET2_E_INVALID, "the smoothing width must be positive and finite");
+    for (int a = 0; a < 3; ++a)
+        if (!(voxel_mm[a] > 0.0) || !std::isfinite(voxel_mm[a])) return fail(MET2_E_INVALID, "the voxel size must be positive and finite");
+    int rad[3];
+    std::vector<double> hw(3 * (2 * BIAS_MAX_R + 1), 0.0);
+    if (int rc = bias_weights(fwhm_mm, voxel_mm, rad, hw.data())) return rc;
+    for (int a = 0; a < 3; ++a) {
+        radius_out[a] = rad[a];
+        for (int t = 0; t <= 2 * rad[a]; ++t) *weights_out++ = hw[a * (2 * BIAS_MAX_R + 1) + t];
+    }
+    return MET2_OK;
+}
+
+extern "C" int met2_bias_domain(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double *v, const uint8_t *mask, double *y, int32_t *idx,
+                                int64_t *n_domain, void *stream)
+{
+    if (nx < 0 || ny < 0 || nz < 0) return fail(MET2_E_INVALID, "bad shape");
+    if (!n_domain) return fail(MET2_E_INVALID, "NULL argument");
+    const int64_t n = (int64_t)nx * ny * nz;
+    *n_domain = 0;
+    if (n == 0) return MET2_OK;
+    if (!v || !y || !idx) return fail(MET2_E_INVALID, "NULL argument");
+    if (n > 0x7fffffffLL) return fail(MET2_E_UNSUPPORTED, "volume too large");
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    const BiasGrid g = bias_grid(n);
+    const size_t b_dom = up256((size_t)n), b_cnt = up256((size_t)g.nch * 4), b_st = up256(sizeof(BiasStats));
+    char *work = nullptr;
+    HIPCHK(hipMalloc(&work, b_dom + 2 * b_cnt + b_st));
+    uint8_t *dom = (uint8_t *)work;
+    int32_t *cnt = (int32_t *)(work + b_dom), *off = (int32_t *)(work + b_dom + b_cnt);
+    BiasStats *S = (BiasStats *)(work + b_dom + 2 * b_cnt);
+    int32_t N = 0;
+    hipError_t err = hipMemsetAsync(S, 0, b_st, st);
+    if (err == hipSuccess) {
+        enq_domain(st, g, v, mask, y, dom, cnt, off, idx, S);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipMemcpyAsync(&N, &S->N, sizeof N, hipMemcpyDeviceToHost, st);
+    const int rc = bias_finish("met2_bias_domain", err, st, work);
+    if (rc == MET2_OK) *n_domain = N;
+    return rc;
+}
+
+extern "C" int met2_bias_init(int32_t device, int64_t n, const double *y, const int32_t *idx, int64_t n_domain, int32_t n_class, double *stats_out,
+                              uint32_t *hist_out, double *ss_part_out, double *classes_out, void *stream)
+{
+    if (n_class < 1) return fail(MET2_E_INVALID, "bias field needs at least one class");
+    if (int rc = bias_check_list(n, idx, n_domain)) return rc;
+    if (!y) return fail(MET2_E_INVALID, "NULL argument");
+    if (n_class > BIAS_MAX_K) return fail(MET2_E_UNSUPPORTED, "bias field supports at most 8 classes");
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    const BiasGrid g = bias_grid(n);
+    const int np = (int)((n_domain + BIAS_CHUNK - 1) / BIAS_CHUNK);
+    const size_t b_part = up256((size_t)g.nch * 3 * BIAS_MAX_K * 8), b_st = up256(sizeof(BiasStats));
+    char *work = nullptr;
+    HIPCHK(hipMalloc(&work, b_part + b_st));
+    double *part = (double *)work;
+    BiasStats *S = (BiasStats *)(work + b_part);
+    BiasStats h;
+    std::vector<double> hp((size_t)np);
+    const int32_t N = (int32_t)n_domain;
+    hipError_t err = hipMemsetAsync(S, 0, b_st, st);
+    if (err == hipSuccess) err = hipMemcpyAsync(&S->N, &N, sizeof N, hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) {
+        enq_init(st, g, y, idx, S, part, n_class);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipMemcpyAsync(&h, S, sizeof h, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess && np > 0) err = hipMemcpyAsync(hp.data(), part, (size_t)np * 8, hipMemcpyDeviceToHost, st);
+    const int rc = bias_finish("met2_bias_init", err, st, work);
+    if (rc != MET2_OK) return rc;
+    if (stats_out) { stats_out[0] = h.lo; stats_out[1] = h.hi; stats_out[2] = h.mean; stats_out[3] = (double)h.degenerate; }
+    if (hist_out) for (int j = 0; j < BIAS_NBINS; ++j) hist_out[j] = h.hist[j];
+    if (ss_part_out && !h.degenerate) for (int p = 0; p < np; ++p) ss_part_out[p] = hp[p];
+    if (classes_out)
+        for (int k = 0; k < n_class; ++k) { classes_out[k] = h.mu[k]; classes_out[n_class + k] = h.var[k]; classes_out[2 * n_class + k] = h.pi[k]; }
+    return MET2_OK;
+}
+
+extern "C" int met2_bias_em(int32_t device, int64_t n, const double *y, const double *b, const int32_t *idx, int64_t n_domain, int32_t n_class,
+                            const double *classes_in, int32_t n_em, double *part_out, double *classes_out, double *rw_out, void *stream)
+{
+    if (n_class < 1) return fail(MET2_E_INVALID, "bias field needs at least one class");
+    if (n_em < 0) return fail(MET2_E_INVALID, "n_em must not be negative");
+    if (int rc = bias_check_list(n, idx, n_domain)) return rc;
+    if (!y || !b || !classes_in) return fail(MET2_E_INVALID, "NULL argument");
+    if (n_domain < 1) return fail(MET2_E_INVALID, "the EM step needs a domain voxel");
+    if (n_class > BIAS_MAX_K) return fail(MET2_E_UNSUPPORTED, "bias field supports at most 8 classes");
+    BiasStats h;
+    std::memset(&h, 0, sizeof h);
+    h.N = (int32_t)n_domain;
+    for (int k = 0; k < n_class; ++k) {
+        h.mu[k] = classes_in[k]; h.var[k] = classes_in[n_class + k]; h.pi[k] = classes_in[2 * n_class + k];
+        if (!std::isfinite(h.mu[k]) || !std::isfinite(h.var[k]) || !(h.var[k] > 0.0) || !std::isfinite(h.pi[k]) || h.pi[k] < 0.0)
+            return fail(MET2_E_INVALID, "a class needs a finite mean, a positive finite variance and a finite weight >= 0");
+    }
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    const BiasGrid g = bias_grid(n);
+    const int np = (int)((n_domain + BIAS_CHUNK - 1) / BIAS_CHUNK);
+    const size_t b_part = up256((size_t)g.nch * 3 * BIAS_MAX_K * 8), b_st = up256(sizeof(BiasStats));
+    char *work = nullptr;
+    HIPCHK(hipMalloc(&work, b_part + b_st));
+    double *part = (double *)work;
+    BiasStats *S = (BiasStats *)(work + b_part);
+    std::vector<double> hp((size_t)3 * n_class * np);
+    hipError_t err = hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st);          // h lives until the wait
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(bias_lc_kernel, dim3(1), dim3(64), 0, st, S, n_class);
+        for (int em = 0; em < n_em; ++em) enq_em_step(st, g, y, b, idx, S, n_class, part);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess && rw_out) err = enq_rw(st, g, y, b, idx, S, n_class, (double2 *)rw_out, (size_t)n * 16);
+    if (err == hipSuccess && part_out && n_em > 0)
+        for (int q = 0; q < 3 && err == hipSuccess; ++q)
+            for (int k = 0; k < n_class && err == hipSuccess; ++k)
+                err = hipMemcpyAsync(hp.data() + ((size_t)q * n_class + k) * np, part + (int64_t)(q * BIAS_MAX_K + k) * g.nch, (size_t)np * 8,
+                                     hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipMemcpyAsync(&h, S, sizeof h, hipMemcpyDeviceToHost, st);
+    const int rc = bias_finish("met2_bias_em", err, st, work);
+    if (rc != MET2_OK) return rc;
+    if (part_out && n_em > 0) std::memcpy(part_out, hp.data(), hp.size() * 8);
+    if (classes_out)
+        for (int k = 0; k < n_class; ++k) { classes_out[k] = h.mu[k]; classes_out[n_class + k] = h.var[k]; classes_out[2 * n_class + k] = h.pi[k]; }
+    return MET2_OK;
+}
+
+extern "C" int met2_bias_smooth(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double *in, const int32_t radius[3], const double *weights,
+                                int32_t axis, double *out, void *stream)
+{
+    if (nx < 0 || ny < 0 || nz < 0) return fail(MET2_E_INVALID, "bad shape");
+    if (axis < -1 || axis > 2) return fail(MET2_E_INVALID, "axis must be 0, 1, 2 or -1 for all three");
+    if (!radius || !weights) return fail(MET2_E_INVALID, "NULL argument");
+    for (int a = 0; a < 3; ++a)
+        if (radius[a] < 0) return fail(MET2_E_INVALID, "a radius must not be negative");
+    const int64_t n = (int64_t)nx * ny * nz;
+    if (n == 0) return MET2_OK;
+    if (!in || !out) return fail(MET2_E_INVALID, "NULL argument");
+    for (int a = 0; a < 3; ++a)
+        if (radius[a] > BIAS_MAX_R) return fail(MET2_E_UNSUPPORTED, "the smoothing kernel reaches further than 64 voxels");
+    if (n > 0x7fffffffLL) return fail(MET2_E_UNSUPPORTED, "volume too large");
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<double> hw(3 * (2 * BIAS_MAX_R + 1), 0.0);                                // the filter's layout of the three weight vectors
+    const double *w = weights;
+    for (int a = 0; a < 3; ++a) {
+        for (int t = 0; t <= 2 * radius[a]; ++t) hw[a * (2 * BIAS_MAX_R + 1) + t] = w[t];
+        w += 2 * radius[a] + 1;
+    }
+    const size_t b_rw = up256((size_t)n * 16), b_w = up256(hw.size() * 8);
+    char *work = nullptr;
+    HIPCHK(hipMalloc(&work, 2 * b_rw + b_w));
+    double2 *RA = (double2 *)work, *RB = (double2 *)(work + b_rw);
+    double *wd = (double *)(work + 2 * b_rw);
+    hipError_t err = hipMemcpyAsync(wd, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, st);   // hw lives until the wait
+    if (err == hipSuccess) err = hipMemcpyAsync(RA, in, (size_t)n * 16, hipMemcpyDeviceToDevice, st);
+    double2 *res = RB;
+    if (err == hipSuccess) {
+        if (axis < 0) {                                               // RA -> RB -> RA -> RB, as the filter
+            enq_smooth(st, 0, smooth_args(0, nx, ny, nz, RA, RB, wd, radius[0]));
+            enq_smooth(st, 1, smooth_args(1, nx, ny, nz, RB, RA, wd + (2 * BIAS_MAX_R + 1), radius[1]));
+            enq_smooth(st, 2, smooth_args(2, nx, ny, nz, RA, RB, wd + 2 * (2 * BIAS_MAX_R + 1), radius[2]));
+        } else {
+            enq_smooth(st, axis, smooth_args(axis, nx, ny, nz, RA, RB, wd + axis * (2 * BIAS_MAX_R + 1), radius[axis]));
+        }
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipMemcpyAsync(out, res, (size_t)n * 16, hipMemcpyDeviceToDevice, st);
+    return bias_finish("met2_bias_smooth", err, st, work);
+}
+
+extern "C" int met2_bias_update(int32_t device, int64_t n, double *b, const double *smoothed, const int32_t *idx, int64_t n_domain, double *bmean_out,
+                                void *stream)
+{
+    if (int rc = bias_check_list(n, idx, n_domain)) return rc;
+    if (!b || !smoothed) return fail(MET2_E_INVALID, "NULL argument");
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    const BiasGrid g = bias_grid(n);
+    const size_t b_part = up256((size_t)g.nch * 8), b_st = up256(sizeof(BiasStats));
+    char *work = nullptr;
+    HIPCHK(hipMalloc(&work, b_part + b_st));
+    double *part = (double *)work;
+    BiasStats *S = (BiasStats *)(work + b_part);
+    BiasStats h;
+    std::memset(&h, 0, sizeof h);
+    h.N = (int32_t)n_domain;
+    h.degenerate = n_domain == 0 ? 1 : 0;                             // an empty domain is degenerate in the filter too: b is not recentred
+    hipError_t err = hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st);          // h lives until the wait
+    if (err == hipSuccess) {
+        enq_update(st, g, (const double2 *)smoothed, idx, S, part, b);
+        err = hipGetLastError();
+    }
+    double bmean = 0.0;
+    if (err == hipSuccess) err = hipMemcpyAsync(&bmean, &S->bmean, 8, hipMemcpyDeviceToHost, st);
+    const int rc = bias_finish("met2_bias_update", err, st, work);
+    if (rc == MET2_OK && bmean_out) *bmean_out = bmean;
+    return rc;
+}
+
+extern "C" int met2_bias_apply(int32_t device, int64_t n, const double *v, const double *b, double *out, double *field, void *stream)
+{
+    if (n < 0) return fail(MET2_E_INVALID, "bad shape");
+    if (n == 0) return MET2_OK;
+    if (!v || !b || !out) return fail(MET2_E_INVALID, "NULL argument");
+    if (v == out) return fail(MET2_E_INVALID, "the bias field cannot be removed in place");
+    if (n > 0x7fffffffLL) return fail(MET2_E_UNSUPPORTED, "volume too large");
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    enq_apply(st, bias_grid(n), v, b, (const BiasStats *)nullptr, 0, out, field, (double *)nullptr);    // no classes: the record is not read
+    return bias_finish("met2_bias_apply", hipSuccess, st, nullptr);
 }
