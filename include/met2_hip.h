@@ -503,6 +503,33 @@ int met2_gibbs_split(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t
 int met2_gibbs_lines(int32_t device, int32_t n, int32_t nlines, const double *lines, int32_t nshifts, int32_t min_w, int32_t max_w, double *out,
                      int8_t *shift, double *best, void *stream);
 
+/* Removal of Gibbs ringing along all three axes, for 3-D Fourier-encoded acquisitions whose partition axis is truncated in k-space like the
+ * other two (degibbs='3d'; Bautista, O'Muircheartaigh, Hajnal, Tournier, "Removal of Gibbs ringing artefacts for 3D acquisitions using
+ * subvoxel shifts", ISMRM 2021; stated here from the abstract, none of MRtrix's program text is used and parity with mrdegibbs is unpinned).
+ * DEVICE pointers: data [nx][ny][nz][n_te] fp64 in C order; out the same shape, must not alias data; out, each may be NULL: shift_x, shift_y,
+ * shift_z [nx][ny][nz][n_te] int8, the signed shift chosen per sample along each axis.  nshifts, min_w, max_w as for met2_degibbs.  Every echo
+ * volume V[nx][ny][nz] is processed on its own, in real fp64:
+ *   3-D split.  F = DFT3(V); for the frequency indices (p, q, r): cx = 1 + cos(2 pi p / nx), cy = 1 + cos(2 pi q / ny),
+ *     cz = 1 + cos(2 pi r / nz), each exactly 0 at the Nyquist index of an even axis; wx = cy cz, wy = cx cz, wz = cx cy,
+ *     den = wx + wy + wz; Ga = wa / den where den != 0.  den is 0 exactly where two or three of cx, cy, cz are 0 (three lines of k-space
+ *     when all axes are even): there, with m the number of axes whose c is 0, Ga = 1 / m on those axes and 0 on the remaining one (the
+ *     symmetric limit; NOT the rule of met2_degibbs, which drops its single corner term).  Gx + Gy + Gz = 1 everywhere.
+ *     Ia = Re IDFT3(F Ga), so Ix + Iy + Iz = V; the kernels form Iz as (V - Ix) - Iy.
+ *   out = (U(Ix along x) + U(Iy along y)) + U(Iz along z), U the operator of met2_degibbs, steps 1-5.
+ * An echo volume that holds a non-finite value is copied through unchanged (its shifts are 0); the other echoes are not affected.
+ * MET2_E_INVALID: a negative dimension, nshifts < 1, min_w < 1, min_w > max_w, data or out NULL, out == data.  MET2_E_UNSUPPORTED: nshifts > 32;
+ * nx, ny or nz outside 8..256; 2 (max_w + 1) > min(nx, ny, nz); 2^31 samples or more.  All of them before any launch.  A volume with a
+ * zero-sized dimension returns MET2_OK at once (after the checks of nshifts, min_w and max_w).
+ * Deterministic, echo by echo independent of the rest of the volume.  BLOCKING: the entry allocates its own work space (67 bytes per sample
+ * of a chunk of at most 2^22 samples, or of one echo volume; plus the three axes' tables), enqueues on `stream`, waits for it and frees the
+ * space.
+ * met2_gibbs_split3d: the 3-D split alone, through the host code and the chunk loop of met2_degibbs3d.  ix, iy, iz the shape of data, distinct
+ * from data and from each other.  An echo that holds a non-finite value gets what the arithmetic gives (not a copy).  BLOCKING. */
+int met2_degibbs3d(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, int32_t nshifts, int32_t min_w,
+                   int32_t max_w, double *out, int8_t *shift_x, int8_t *shift_y, int8_t *shift_z, void *stream);
+int met2_gibbs_split3d(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, double *ix, double *iy, double *iz,
+                       void *stream);
+
 /* Bias-field correction of a 3-D map (bias_correct='yes'; step 5 of the reference's example pipeline,
  * example_script_run_MET2_preproc_and_recon.sh, which runs FSL's `fast -t 3 -n 3 -H 0.1 -I 4 -l 20.0 -b` on the total water content map and
  * divides the estimated field out).  The EM bias-field estimation of Wells et al. (IEEE TMI 1996) and Guillemaud & Brady (IEEE TMI 1997): the

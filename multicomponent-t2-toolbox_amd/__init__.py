@@ -7,12 +7,12 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   epg.py                    create_Dic_3D, create_met2_design_matrix_epg
   flip_angle_algorithms.py  compute_optimal_FA, fitting_slice_FA_brute_force
   motor.py                  create_Laplacian_matrix, fitting_slice_T2, recon_met2_arrays (voxel loop), nesma_filter, mppca_filter (MP-PCA denoising: csrc/met2_mppca.hip),
-                            gibbs_filter (Gibbs-ringing removal, degibbs='yes': csrc/met2_gibbs.hip),
+                            gibbs_filter (Gibbs-ringing removal, degibbs='yes' and '3d': csrc/met2_gibbs.hip),
                             bias_field_filter (bias-field correction of the TWC map, bias_correct='yes': csrc/met2_bias.hip),
                             brain_mask_filter (brain extraction, brain_mask='yes': csrc/met2_bet.hip),
                             gaussian_smooth, ROI mode
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
-  gibbs.py                  gibbs_tables / gibbs_split / gibbs_lines: the stages of the Gibbs-ringing filter one by one (tests and diagnostics)
+  gibbs.py                  gibbs_tables / gibbs_split / gibbs_split3d / gibbs_lines: the stages of the Gibbs-ringing filter one by one (tests and diagnostics)
   bet.py                    bet_mean / bet_stats / bet_mesh / bet_evolve / bet_fill: the stages of the brain extraction one by one (tests and diagnostics)
   bias.py                   bias_weights / bias_domain / bias_init / bias_em / bias_smooth / bias_update / bias_apply: the stages of the bias-field correction one by one (tests and diagnostics)
   mppca.py                  mppca_stages: the MP-PCA denoiser with what each of its steps leaves (tests and diagnostics)

@@ -41,7 +41,7 @@ SYMBOLS = ["met2_default_options", "met2_abi_version", "met2_device_count", "met
            "met2_fit_bootstrap", "met2_fit_bootstrap_fa", "met2_bootstrap_replicates", "met2_bootstrap_series_stats", "met2_bootstrap_spectrum_stats",
            "met2_bootstrap_spec_launch_info", "met2_synth_two_lobe", "met2_eval_voxel_metrics", "met2_eval_reduce", "met2_refac_packed_calls", "met2_mppca", "met2_mppca_stages", "met2_degibbs", "met2_bias_field",
            "met2_bias_weights", "met2_bias_domain", "met2_bias_init", "met2_bias_em", "met2_bias_smooth", "met2_bias_update", "met2_bias_apply",
-           "met2_gibbs_table_cols", "met2_gibbs_tables", "met2_gibbs_split", "met2_gibbs_lines",
+           "met2_gibbs_table_cols", "met2_gibbs_tables", "met2_gibbs_split", "met2_gibbs_lines", "met2_degibbs3d", "met2_gibbs_split3d",
            "met2_brain_mask", "met2_bet_stats", "met2_bet_evolve", "met2_bet_fill", "met2_bet_mesh", "met2_bet_mean"]
 
 
@@ -85,6 +85,8 @@ def lib():
         L.met2_gibbs_tables.argtypes = [C.c_int32] * 3 + [vp, vp, vp]
         L.met2_gibbs_split.argtypes = [C.c_int32] * 5 + [vp, vp, vp, vp]
         L.met2_gibbs_lines.argtypes = [C.c_int32] * 3 + [vp] + [C.c_int32] * 3 + [vp, vp, vp, vp]
+        L.met2_degibbs3d.argtypes = [C.c_int32] * 5 + [vp] + [C.c_int32] * 3 + [vp, vp, vp, vp, vp]
+        L.met2_gibbs_split3d.argtypes = [C.c_int32] * 5 + [vp, vp, vp, vp, vp]
         L.met2_bias_field.argtypes = [C.c_int32] * 4 + [vp, vp, _dp] + [C.c_int32] * 3 + [C.c_double, vp, vp, vp, vp]
         L.met2_bias_weights.argtypes = [C.c_double, _dp, C.POINTER(C.c_int32), _dp]
         L.met2_bias_domain.argtypes = [C.c_int32] * 4 + [vp, vp, vp, vp, C.POINTER(C.c_int64), vp]

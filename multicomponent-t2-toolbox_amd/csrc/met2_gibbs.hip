@@ -13,6 +13,12 @@
 //                         neighbours through LDS for the windowed total variation; the running strict minimum with its three samples stays
 //                         in registers; the y-pass adds into the x-pass's result;
 //   gibbs_scatter_kernel  back to the caller's layout, non-finite slices copied through from the gathered input.
+// met2_degibbs3d (degibbs='3d'; Bautista, O'Muircheartaigh, Hajnal, Tournier, ISMRM 2021) works in chunks of whole echo volumes, echo-major
+// [echo][nx][ny][nz], with the same gather, tables, forward rows kernel (along z) and line kernel (along x, y and z by its strides), and
+//   gibbs_dft_axis_kernel  the complex DFT along y or x, forward or back, in place;
+//   gibbs_filter3d_kernel  F Gx and F Gy, the weight shared evenly where two or three axes sit at their Nyquist index;
+//   gibbs_idft_z_kernel    back along z, real part, scaled; the third part as Iz = (V - Ix) - Iy;
+//   gibbs_scatter3d_kernel gibbs_scatter_kernel with a third shift map.
 // Every loop is bounded by a shape or a compile-time constant; fp64 throughout.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -343,6 +349,157 @@ __global__ __launch_bounds__(256) void gibbs_unring_kernel(UnringArgs A)
     if (A.best) A.best[base] = best;                                    // uniform
 }
 
+// ---- met2_degibbs3d: the 3-D split.  The work layout is echo-major [echo][nx][ny][nz], z fastest: gibbs_gather_kernel makes it from the
+// caller's [nx ny nz][echoes] as it is (its "slice" is then an echo volume), the z lines are contiguous, gibbs_dft_rows_kernel is the forward
+// DFT along z and gibbs_unring_kernel runs along all three axes by its strides.
+
+// The DFT along an axis whose samples lie `stride` apart, in place and unscaled: T[o][a][i], o < nouter, a < n, i < stride; inverse != 0 takes
+// the conjugate matrix.  GIBBS_LB adjacent i per workgroup, through LDS both ways so that global memory is touched 128 B at a time;
+// blockDim.x >= n; grid nouter * ceil(stride / GIBBS_LB), the tile of i fastest
+__global__ __launch_bounds__(256) void gibbs_dft_axis_kernel(double2 *__restrict__ T, const double2 *__restrict__ Wa, int n, int stride, int inverse)
+{
+    __shared__ double2 tc[GIBBS_LB][GIBBS_MAX_N + 1];                    // the odd row keeps the tile's GIBBS_LB lines on different banks
+    const int tiles = (stride + GIBBS_LB - 1) / GIBBS_LB;
+    const int o = blockIdx.x / tiles;
+    const int i0 = (blockIdx.x - o * tiles) * GIBBS_LB;
+    double2 *To = T + (int64_t)o * n * stride + i0;
+    for (int i = threadIdx.x; i < GIBBS_LB * n; i += blockDim.x) {
+        const int a = i / GIBBS_LB, l = i - a * GIBBS_LB;
+        tc[l][a] = i0 + l < stride ? To[(int64_t)a * stride + l] : make_double2(0.0, 0.0);
+    }
+    __syncthreads();
+    const int p = threadIdx.x;
+    const bool mine = p < n;
+    double re[GIBBS_LB], im[GIBBS_LB];
+#pragma unroll
+    for (int l = 0; l < GIBBS_LB; ++l) { re[l] = 0.0; im[l] = 0.0; }
+    if (mine) {
+        for (int a = 0; a < n; ++a) {
+            const double2 w = Wa[a * n + p];
+            const double wy = inverse ? -w.y : w.y;
+#pragma unroll
+            for (int l = 0; l < GIBBS_LB; ++l) {
+                const double2 t = tc[l][a];
+                re[l] = fma(t.x, w.x, fma(-t.y, wy, re[l]));
+                im[l] = fma(t.x, wy, fma(t.y, w.x, im[l]));
+            }
+        }
+    }
+    __syncthreads();
+    if (mine) {
+#pragma unroll
+        for (int l = 0; l < GIBBS_LB; ++l) tc[l][p] = make_double2(re[l], im[l]);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < GIBBS_LB * n; i += blockDim.x) {
+        const int a = i / GIBBS_LB, l = i - a * GIBBS_LB;
+        if (i0 + l < stride) To[(int64_t)a * stride + l] = tc[l][a];
+    }
+}
+
+// A = F Gx, F <- F Gy over the chunk's [echo][p][q][r]; where two or three of cx, cy, cz are 0 the weight is shared evenly among those axes
+__global__ __launch_bounds__(256) void gibbs_filter3d_kernel(double2 *__restrict__ F, double2 *__restrict__ A, const double2 *__restrict__ Wx,
+                                                             const double2 *__restrict__ Wy, const double2 *__restrict__ Wz, int nx, int ny, int nz,
+                                                             int64_t total)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int r = (int)(i % nz);
+    const int64_t g = i / nz;
+    const int q = (int)(g % ny);
+    const int p = (int)((g / ny) % nx);
+    const double cx = 2 * p == nx ? 0.0 : 1.0 + Wx[nx + p].x;              // 1 + cos(2 pi p / nx)
+    const double cy = 2 * q == ny ? 0.0 : 1.0 + Wy[ny + q].x;
+    const double cz = 2 * r == nz ? 0.0 : 1.0 + Wz[nz + r].x;
+    const double wx = cy * cz, wy = cx * cz;
+    const double den = wx + wy + cx * cy;
+    double gx, gy;
+    if (den != 0.0) {
+        gx = wx / den;
+        gy = wy / den;
+    } else {
+        const double share = 1.0 / (double)((cx == 0.0) + (cy == 0.0) + (cz == 0.0));
+        gx = cx == 0.0 ? share : 0.0;
+        gy = cy == 0.0 ? share : 0.0;
+    }
+    const double2 f = F[i];
+    A[i] = make_double2(f.x * gx, f.y * gx);
+    F[i] = make_double2(f.x * gy, f.y * gy);
+}
+
+// I[g][b] = scale Re sum_r T[g][r] conj(Wz[r][b]) for the z lines g of the chunk; with Iz, also Iz = (V - Ix) - I; blockDim.x >= nz
+__global__ __launch_bounds__(256) void gibbs_idft_z_kernel(const double2 *__restrict__ T, const double2 *__restrict__ Wz, int nz, int nrows,
+                                                           double scale, double *__restrict__ I, const double *__restrict__ V,
+                                                           const double *__restrict__ Ix, double *__restrict__ Iz)
+{
+    __shared__ double2 vr[GIBBS_LB][GIBBS_MAX_N];
+    const int g0 = blockIdx.x * GIBBS_LB;
+    for (int i = threadIdx.x; i < GIBBS_LB * nz; i += blockDim.x) {
+        const int l = i / nz, r = i - l * nz;
+        vr[l][r] = g0 + l < nrows ? T[(int64_t)(g0 + l) * nz + r] : make_double2(0.0, 0.0);
+    }
+    __syncthreads();
+    const int b = threadIdx.x;
+    if (b >= nz) return;
+    double re[GIBBS_LB];
+#pragma unroll
+    for (int l = 0; l < GIBBS_LB; ++l) re[l] = 0.0;
+    for (int r = 0; r < nz; ++r) {
+        const double2 w = Wz[r * nz + b];
+#pragma unroll
+        for (int l = 0; l < GIBBS_LB; ++l) {
+            const double2 t = vr[l][r];
+            re[l] = fma(t.x, w.x, fma(t.y, w.y, re[l]));
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < GIBBS_LB; ++l) {
+        if (g0 + l < nrows) {
+            const int64_t at = (int64_t)(g0 + l) * nz + b;
+            const double v = re[l] * scale;
+            I[at] = v;
+            if (Iz) Iz[at] = (V[at] - Ix[at]) - v;                       // uniform
+        }
+    }
+}
+
+// gibbs_scatter_kernel with a third shift map: [echo][P] back to the caller's [P][echoes]; a flagged echo volume is copied through from W
+__global__ __launch_bounds__(256) void gibbs_scatter3d_kernel(const double *__restrict__ R, const double *__restrict__ W, const int8_t *__restrict__ sx,
+                                                              const int8_t *__restrict__ sy, const int8_t *__restrict__ sz,
+                                                              const int32_t *__restrict__ flag, int64_t P, int64_t ns, int64_t s0, int sc,
+                                                              double *__restrict__ out, int8_t *__restrict__ ox, int8_t *__restrict__ oy,
+                                                              int8_t *__restrict__ oz)
+{
+    __shared__ double tile[32][33];
+    __shared__ int8_t tx8[32][33], ty8[32][33], tz8[32][33];
+    const int64_t p0 = (int64_t)blockIdx.x * 32;
+    const int sb = blockIdx.y * 32;
+    for (int i = threadIdx.y; i < 32; i += 8) {
+        const int s = sb + i;
+        const int64_t p = p0 + threadIdx.x;
+        if (s < sc && p < P) {
+            const bool copy = flag[s] != 0;
+            const int64_t at = (int64_t)s * P + p;
+            tile[i][threadIdx.x] = copy ? W[at] : R[at];
+            if (ox) tx8[i][threadIdx.x] = copy ? (int8_t)0 : sx[at];
+            if (oy) ty8[i][threadIdx.x] = copy ? (int8_t)0 : sy[at];
+            if (oz) tz8[i][threadIdx.x] = copy ? (int8_t)0 : sz[at];
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.y; i < 32; i += 8) {
+        const int64_t p = p0 + i;
+        const int s = sb + threadIdx.x;
+        if (p < P && s < sc) {
+            const int64_t at = p * ns + s0 + s;
+            out[at] = tile[threadIdx.x][i];
+            if (ox) ox[at] = tx8[threadIdx.x][i];
+            if (oy) oy[at] = ty8[threadIdx.x][i];
+            if (oz) oz[at] = tz8[threadIdx.x][i];
+        }
+    }
+}
+
 inline int round64(int n) { return (n + 63) / 64 * 64; }
 
 inline int table_cols(int nshifts) { return (2 * nshifts + 1 + GIBBS_JB - 1) / GIBBS_JB * GIBBS_JB; }
@@ -460,7 +617,149 @@ int check_volume(int32_t nx, int32_t ny, int32_t nz, int32_t nt, int64_t min_axi
     return MET2_OK;
 }
 
+// The volume in chunks of whole echo volumes, [echo][nx][ny][nz].  split_x == NULL: the 3-D filter (out and the three shift maps as
+// met2_degibbs3d takes them).  Otherwise the 3-D split alone: Ix, Iy, Iz of every echo go to split_x, split_y, split_z, whatever the echo
+// holds.  The shapes and parameters have been checked.
+int run_volume3d(int32_t device, int32_t nx, int32_t ny, int32_t nz, int64_t nt, const double *data, int32_t nshifts, int32_t min_w, int32_t max_w,
+                 double *out, int8_t *shift_x, int8_t *shift_y, int8_t *shift_z, double *split_x, double *split_y, double *split_z, void *stream,
+                 const char *who)
+{
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+
+    const int64_t P = (int64_t)nx * ny * nz;
+    int64_t ecl = GIBBS_CHUNK_ELEMS / P;
+    if (ecl < 1) ecl = 1;
+    if (ecl > nt) ecl = nt;
+    const int ec_max = (int)ecl;                                       // at most 2^22 / 8^3 echoes
+    const int jp = table_cols(nshifts);
+    const size_t ce = (size_t)ec_max * (size_t)P;                      // samples of a chunk
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t b_W = up(ce * 8), b_T = up(ce * 16), b_I = up(ce * 8), b_sh = up(ce), b_flag = up((size_t)ec_max * 4);
+    const int32_t na[3] = {nx, ny, nz};
+    size_t b_Wa[3], b_ca[3], total = b_W + 2 * b_T + 3 * b_I + 3 * b_sh + b_flag;
+    for (int a = 0; a < 3; ++a) {
+        b_Wa[a] = up((size_t)na[a] * na[a] * 16);
+        b_ca[a] = up((size_t)na[a] * jp * 8);
+        total += b_Wa[a] + b_ca[a];
+    }
+    char *work = nullptr;
+    HIPCHK(hipMalloc(&work, total));
+    char *at = work;
+    auto take = [&at](size_t b) { char *p = at; at += b; return p; };
+    double *W = (double *)take(b_W);
+    double2 *T = (double2 *)take(b_T), *T2 = (double2 *)take(b_T);
+    double *Ix = (double *)take(b_I), *Iy = (double *)take(b_I), *Iz = (double *)take(b_I);
+    int8_t *sx = (int8_t *)take(b_sh), *sy = (int8_t *)take(b_sh), *sz = (int8_t *)take(b_sh);
+    int32_t *flag = (int32_t *)take(b_flag);
+    double2 *Wa[3];
+    double *ca[3];
+    for (int a = 0; a < 3; ++a) {
+        Wa[a] = (double2 *)take(b_Wa[a]);
+        ca[a] = (double *)take(b_ca[a]);
+    }
+
+    int rc = MET2_OK;
+    hipError_t err = hipSuccess;
+    auto ok = [&](hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; return err == hipSuccess; };
+    for (int a = 0; a < 3; ++a) launch_tables(st, na[a], nshifts, jp, Wa[a], ca[a]);
+    ok(hipGetLastError());
+    const int yz = ny * nz;                                            // <= 2^16
+    const int tiles_x = (yz + GIBBS_LB - 1) / GIBBS_LB, tiles_y = (nz + GIBBS_LB - 1) / GIBBS_LB;
+    const double scale = 1.0 / ((double)nx * (double)ny * (double)nz);
+    for (int64_t e0 = 0; e0 < nt && err == hipSuccess; e0 += ec_max) {
+        const int ec = (int)(nt - e0 < ec_max ? nt - e0 : ec_max);
+        const int64_t cs = (int64_t)ec * P;                            // < 2^31
+        const int nrows = (int)(cs / nz);                              // the chunk's z lines
+        if (!ok(hipMemsetAsync(flag, 0, b_flag, st))) break;
+        const dim3 tg((unsigned)((P + 31) / 32), (unsigned)((ec + 31) / 32));
+        const dim3 rows((unsigned)((nrows + GIBBS_LB - 1) / GIBBS_LB));
+        const dim3 gx((unsigned)((int64_t)ec * tiles_x)), gy((unsigned)((int64_t)ec * nx * tiles_y));    // <= 2^22 / 8 + ec and 2^22 / 64 + ec nx
+        hipLaunchKernelGGL(gibbs_gather_kernel, tg, dim3(32, 8), 0, st, data, P, nt, e0, ec, W, flag);
+        hipLaunchKernelGGL(gibbs_dft_rows_kernel, rows, dim3(round64(nz)), 0, st, W, Wa[2], nz, nrows, T);
+        hipLaunchKernelGGL(gibbs_dft_axis_kernel, gy, dim3(round64(ny)), 0, st, T, Wa[1], ny, nz, 0);
+        hipLaunchKernelGGL(gibbs_dft_axis_kernel, gx, dim3(round64(nx)), 0, st, T, Wa[0], nx, yz, 0);
+        hipLaunchKernelGGL(gibbs_filter3d_kernel, dim3((unsigned)((cs + 255) / 256)), dim3(256), 0, st, T, T2, Wa[0], Wa[1], Wa[2], nx, ny, nz, cs);
+        hipLaunchKernelGGL(gibbs_dft_axis_kernel, gx, dim3(round64(nx)), 0, st, T2, Wa[0], nx, yz, 1);
+        hipLaunchKernelGGL(gibbs_dft_axis_kernel, gy, dim3(round64(ny)), 0, st, T2, Wa[1], ny, nz, 1);
+        hipLaunchKernelGGL(gibbs_idft_z_kernel, rows, dim3(round64(nz)), 0, st, T2, Wa[2], nz, nrows, scale, Ix, (const double *)nullptr,
+                           (const double *)nullptr, (double *)nullptr);
+        hipLaunchKernelGGL(gibbs_dft_axis_kernel, gx, dim3(round64(nx)), 0, st, T, Wa[0], nx, yz, 1);
+        hipLaunchKernelGGL(gibbs_dft_axis_kernel, gy, dim3(round64(ny)), 0, st, T, Wa[1], ny, nz, 1);
+        hipLaunchKernelGGL(gibbs_idft_z_kernel, rows, dim3(round64(nz)), 0, st, T, Wa[2], nz, nrows, scale, Iy, W, Ix, Iz);
+        if (split_x) {                                                  // source and copy-through source the same: the flags change nothing
+            double *src[3] = {Ix, Iy, Iz}, *dst[3] = {split_x, split_y, split_z};
+            for (int a = 0; a < 3; ++a)
+                hipLaunchKernelGGL(gibbs_scatter_kernel, tg, dim3(32, 8), 0, st, src[a], src[a], sx, sy, flag, P, nt, e0, ec, dst[a],
+                                   (int8_t *)nullptr, (int8_t *)nullptr);
+            ok(hipGetLastError());
+            continue;
+        }
+        UnringArgs A;
+        A.nsh = nshifts; A.jp = jp; A.min_w = min_w; A.max_w = max_w; A.best = nullptr; A.dst = Ix;
+        // along x: per echo, the ny nz lines start side by side; the result overwrites Ix
+        A.src = Ix; A.ct = ca[0]; A.shift = shift_x ? sx : nullptr; A.n = nx; A.nlines = ec * yz; A.per_slice = yz; A.slice_stride = P;
+        A.line_stride = 1; A.stride = yz; A.accumulate = 0;
+        launch_unring(st, A);
+        // along y: per (echo, x), the nz lines start side by side; added to the x pass's result
+        A.src = Iy; A.ct = ca[1]; A.shift = shift_y ? sy : nullptr; A.n = ny; A.nlines = ec * nx * nz; A.per_slice = nz; A.slice_stride = yz;
+        A.line_stride = 1; A.stride = nz; A.accumulate = 1;
+        launch_unring(st, A);
+        // along z: the lines are contiguous, one after the other through the chunk
+        A.src = Iz; A.ct = ca[2]; A.shift = shift_z ? sz : nullptr; A.n = nz; A.nlines = nrows; A.per_slice = nrows; A.slice_stride = 0;
+        A.line_stride = nz; A.stride = 1; A.accumulate = 1;
+        launch_unring(st, A);
+        hipLaunchKernelGGL(gibbs_scatter3d_kernel, tg, dim3(32, 8), 0, st, Ix, W, sx, sy, sz, flag, P, nt, e0, ec, out, shift_x, shift_y, shift_z);
+        ok(hipGetLastError());
+    }
+    ok(hipStreamSynchronize(st));                                       // the work space goes back before the call returns
+    if (err != hipSuccess) rc = fail(MET2_E_HIP, std::string(who) + ": " + hipGetErrorString(err));
+    (void)hipFree(work);
+    return rc;
+}
+
+// the checks on the volume's shape that met2_degibbs3d and met2_gibbs_split3d share, after those of the parameters; *empty: nothing to do
+int check_volume3d(int32_t nx, int32_t ny, int32_t nz, int32_t nt, int64_t min_axis, bool *empty)
+{
+    *empty = nx == 0 || ny == 0 || nz == 0 || nt == 0;
+    if (*empty) return MET2_OK;
+    const int32_t lo = nx < ny ? (nx < nz ? nx : nz) : (ny < nz ? ny : nz), hi = nx > ny ? (nx > nz ? nx : nz) : (ny > nz ? ny : nz);
+    if (lo < GIBBS_MIN_N || hi > GIBBS_MAX_N) return fail(MET2_E_UNSUPPORTED, "degibbs in 3-D supports 8 to 256 samples along x, y and z");
+    if (min_axis > lo) return fail(MET2_E_UNSUPPORTED, "the total-variation window is too wide for the axis");
+    return MET2_OK;
+}
+
 }  // namespace
+
+extern "C" int met2_degibbs3d(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, const double *data, int32_t nshifts, int32_t min_w,
+                              int32_t max_w, double *out, int8_t *shift_x, int8_t *shift_y, int8_t *shift_z, void *stream)
+{
+    if (nx < 0 || ny < 0 || nz < 0 || nt < 0) return fail(MET2_E_INVALID, "bad shape");
+    if (nshifts < 1) return fail(MET2_E_INVALID, "degibbs needs at least one sub-voxel shift");
+    if (int rc = check_windows(min_w, max_w)) return rc;
+    if (int rc = check_shifts(nshifts)) return rc;
+    bool empty;
+    if (int rc = check_volume3d(nx, ny, nz, nt, 2 * ((int64_t)max_w + 1), &empty)) return rc;
+    if (empty) return MET2_OK;
+    if (!data || !out) return fail(MET2_E_INVALID, "NULL argument");
+    if (data == out) return fail(MET2_E_INVALID, "degibbs cannot run in place");
+    if (nt > 0x7fffffffLL / ((int64_t)nx * ny * nz)) return fail(MET2_E_UNSUPPORTED, "volume too large");
+    return run_volume3d(device, nx, ny, nz, nt, data, nshifts, min_w, max_w, out, shift_x, shift_y, shift_z, nullptr, nullptr, nullptr, stream,
+                        "met2_degibbs3d");
+}
+
+extern "C" int met2_gibbs_split3d(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, const double *data, double *ix, double *iy,
+                                  double *iz, void *stream)
+{
+    if (nx < 0 || ny < 0 || nz < 0 || nt < 0) return fail(MET2_E_INVALID, "bad shape");
+    bool empty;
+    if (int rc = check_volume3d(nx, ny, nz, nt, GIBBS_MIN_N, &empty)) return rc;
+    if (empty) return MET2_OK;
+    if (!data || !ix || !iy || !iz) return fail(MET2_E_INVALID, "NULL argument");
+    if (data == ix || data == iy || data == iz || ix == iy || ix == iz || iy == iz) return fail(MET2_E_INVALID, "the split cannot run in place");
+    if (nt > 0x7fffffffLL / ((int64_t)nx * ny * nz)) return fail(MET2_E_UNSUPPORTED, "volume too large");
+    return run_volume3d(device, nx, ny, nz, nt, data, 1, 1, 1, nullptr, nullptr, nullptr, nullptr, ix, iy, iz, stream, "met2_gibbs_split3d");
+}
 
 extern "C" int met2_degibbs(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, const double *data, int32_t nshifts, int32_t min_w,
                             int32_t max_w, double *out, int8_t *shift_x, int8_t *shift_y, void *stream)

@@ -1,5 +1,5 @@
-"""The stages of the Gibbs-ringing filter one by one (met2_gibbs_tables, met2_gibbs_split, met2_gibbs_lines in include/met2_hip.h), for
-tests and diagnostics: they launch the kernels of met2_degibbs through the host code met2_degibbs itself runs.  The filter itself is
+"""The stages of the Gibbs-ringing filter one by one (met2_gibbs_tables, met2_gibbs_split, met2_gibbs_split3d, met2_gibbs_lines in
+include/met2_hip.h), for tests and diagnostics: they launch the kernels of met2_degibbs and met2_degibbs3d through the host code those run.  The filter itself is
 motor.gibbs_filter.  numpy in -> numpy out, CUDA tensor in -> tensors out."""
 import numpy as np
 import torch
@@ -45,6 +45,21 @@ def gibbs_split(data, device=0):
     with torch.cuda.device(dev):
         check(lib().met2_gibbs_split(dev.index or 0, nx, ny, nz, nt, dd.data_ptr(), ix.data_ptr(), iy.data_ptr(), _stream(dev)))
     return (ix.cpu().numpy(), iy.cpu().numpy()) if as_numpy else (ix, iy)
+
+
+def gibbs_split3d(data, device=0):
+    """the 3-D split of every echo volume of `data` [nx,ny,nz,nt] -> (Ix, Iy, Iz), the same shape; Ix + Iy + Iz = data"""
+    as_numpy = not torch.is_tensor(data)
+    dev = torch.device("cuda", device) if as_numpy else data.device
+    dd = torch.as_tensor(data, dtype=torch.float64, device=dev).contiguous()
+    if dd.dim() != 4:
+        raise ValueError("data must be [nx,ny,nz,nt]")
+    parts = tuple(torch.empty_like(dd) for _ in range(3))
+    nx, ny, nz, nt = dd.shape
+    with torch.cuda.device(dev):
+        check(lib().met2_gibbs_split3d(dev.index or 0, nx, ny, nz, nt, dd.data_ptr(), parts[0].data_ptr(), parts[1].data_ptr(),
+                                       parts[2].data_ptr(), _stream(dev)))
+    return tuple(t.cpu().numpy() for t in parts) if as_numpy else parts
 
 
 def gibbs_lines(lines, nshifts=20, minW=1, maxW=3, device=0):

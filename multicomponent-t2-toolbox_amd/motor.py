@@ -108,13 +108,17 @@ def mppca_filter(data, mask, window=5, device=0, return_maps=False):
     return tuple(t.cpu().numpy() for t in (out, sigma, rank)) if as_numpy else (out, sigma, rank)
 
 
-def gibbs_filter(data, nshifts=20, minW=1, maxW=3, device=0, return_shifts=False):
+def gibbs_filter(data, nshifts=20, minW=1, maxW=3, device=0, return_shifts=False, mode="2d"):
     """Removal of Gibbs (truncation) ringing by local sub-voxel shifts (Kellner et al., MRM 2016; met2_degibbs in include/met2_hip.h states
     the algorithm) on the device: every (z, echo) slice of `data` [nx,ny,nz,nt] is unrung along x and y, 8 <= nx, ny <= 256.  The defaults
     are those of MRtrix's mrdegibbs, which the reference's example script runs at this place; parity with mrdegibbs itself is unpinned.  A
     slice that holds a non-finite value is copied through.  The output is not clipped: it can undershoot zero next to an edge.
-    return_shifts=True: (unrung, shift_x, shift_y), the int8 shifts (in units of 1 / (2 nshifts) voxel) chosen per sample along each axis.
-    numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    mode='3d' (met2_degibbs3d; Bautista et al., ISMRM 2021), for 3-D Fourier-encoded acquisitions: every echo volume is unrung along x, y
+    and z, 8 <= nx, ny, nz <= 256; an echo volume that holds a non-finite value is copied through.
+    return_shifts=True: (unrung, shift_x, shift_y), the int8 shifts (in units of 1 / (2 nshifts) voxel) chosen per sample along each axis;
+    with mode='3d' (unrung, shift_x, shift_y, shift_z).  numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    if mode not in ("2d", "3d"):
+        raise ValueError("mode must be '2d' or '3d'")
     as_numpy = not torch.is_tensor(data)
     dev = torch.device("cuda", device) if as_numpy else data.device
     dd = torch.as_tensor(data, dtype=torch.float64, device=dev).contiguous()
@@ -122,28 +126,28 @@ def gibbs_filter(data, nshifts=20, minW=1, maxW=3, device=0, return_shifts=False
         raise ValueError("data must be [nx,ny,nz,nt]")
     out = torch.empty_like(dd)
     nx, ny, nz, nt = dd.shape
-    sx = torch.empty(dd.shape, dtype=torch.int8, device=dev) if return_shifts else None
-    sy = torch.empty(dd.shape, dtype=torch.int8, device=dev) if return_shifts else None
+    shifts = tuple(torch.empty(dd.shape, dtype=torch.int8, device=dev) for _ in range(3 if mode == "3d" else 2)) if return_shifts else ()
+    entry = lib().met2_degibbs3d if mode == "3d" else lib().met2_degibbs
+    ptrs = [s.data_ptr() for s in shifts] if return_shifts else [None] * (3 if mode == "3d" else 2)
     with torch.cuda.device(dev):
-        check(lib().met2_degibbs(dev.index or 0, nx, ny, nz, nt, dd.data_ptr(), int(nshifts), int(minW), int(maxW), out.data_ptr(),
-                                 sx.data_ptr() if return_shifts else None, sy.data_ptr() if return_shifts else None,
-                                 torch.cuda.current_stream(dev).cuda_stream))
+        check(entry(dev.index or 0, nx, ny, nz, nt, dd.data_ptr(), int(nshifts), int(minW), int(maxW), out.data_ptr(), *ptrs,
+                    torch.cuda.current_stream(dev).cuda_stream))
     if not return_shifts:
         return out.cpu().numpy() if as_numpy else out
-    return tuple(t.cpu().numpy() for t in (out, sx, sy)) if as_numpy else (out, sx, sy)
+    return tuple(t.cpu().numpy() for t in (out,) + shifts) if as_numpy else (out,) + shifts
 
 
 def _degibbs_first(data, degibbs, prepared, device):
-    """degibbs='yes' of the drivers: the raw volume through gibbs_filter, before anything else -> the volume to go on with"""
-    if degibbs not in ("no", "yes"):
-        raise ValueError("degibbs must be 'no' or 'yes'")
+    """degibbs='yes' or '3d' of the drivers: the raw volume through gibbs_filter, before anything else -> the volume to go on with"""
+    if degibbs not in ("no", "yes", "3d"):
+        raise ValueError("degibbs must be 'no', 'yes' or '3d'")
     if degibbs == "no":
         return data
     if prepared:
-        raise ValueError("degibbs='yes' works on the raw volume and does not go with prepared=True")
+        raise ValueError("degibbs='%s' works on the raw volume and does not go with prepared=True" % degibbs)
     if np.ndim(data) != 4:
-        raise ValueError("degibbs='yes' needs data [nx,ny,nz,nt]")
-    return gibbs_filter(np.asarray(data, dtype=np.float64), device=device)
+        raise ValueError("degibbs='%s' needs data [nx,ny,nz,nt]" % degibbs)
+    return gibbs_filter(np.asarray(data, dtype=np.float64), device=device, mode="3d" if degibbs == "3d" else "2d")
 
 
 def brain_mask_filter(data, voxel_size, f=0.4, level=4, n_iter=1000, device=0, return_surface=False):
@@ -339,7 +343,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     first -- before the mask multiply, the clip and any denoise, so the clip also removes what the unringing leaves below zero; needs data
     [nx,ny,nz,nt]; ValueError with prepared=True; on the devices=[...] path it runs on devices[0], under distributed=True on every rank's own
     copy (it is deterministic).  MRtrix recommends MP-PCA denoising BEFORE unringing: a caller who wants that order calls mppca_filter and
-    gibbs_filter themselves and passes prepared=True.  degibbs='no' (default) changes nothing.
+    gibbs_filter themselves and passes prepared=True.  degibbs='3d': the same with gibbs_filter(mode='3d'), for 3-D Fourier-encoded acquisitions
+    (every echo volume unrung along x, y and z; needs 8 <= nz <= 256 too).  degibbs='no' (default) changes nothing.
     bias_correct='yes' (step 5 of the reference's example script, which runs FSL's fast on the TWC map there): after everything else the
     total water content map goes through bias_field_filter with the driver's mask and voxel_size=(dx, dy, dz) in mm; 'TWC' becomes the
     corrected map and 'TWC_bias' the estimated field; the other outputs, the bootstrap's included, are not touched.  Needs data [nx,ny,nz,nt]
@@ -673,7 +678,7 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     Est_Signal, reg_param .nii.gz at path_to_save_data, motor:475-503).  `num_cores` is accepted and ignored (one
     process drives the GPU; devices=[0, 1, ...]: that one process drives all the listed GPUs through met2_fit_host).  denoise: 'None',
     'NESMA' (motor:305-333), 'TV' (motor:293-304) or 'MPPCA' (an extension: mppca_filter; Data_denoised.nii.gz as for TV, and the noise
-    map MPPCA_sigma.nii.gz).  degibbs='yes' (see recon_met2_arrays): the raw volume is unrung first (gibbs_filter) and written as
+    map MPPCA_sigma.nii.gz).  degibbs='yes' or '3d' (see recon_met2_arrays): the raw volume is unrung first (gibbs_filter) and written as
     Data_degibbs.nii.gz.  bias_correct='yes' (see recon_met2_arrays): TWC.nii.gz is the bias-corrected map and TWC_bias.nii.gz the
     estimated field, as the example script leaves them; the voxel size is the data header's pixdim[1:4] (absolute values, 0 read as 1).
     brain_mask='yes' (see recon_met2_arrays): path_to_mask is None, the mask is made by brain_mask_filter from the echo mean (of the unrung
@@ -786,7 +791,7 @@ def motor_recon_met2_ROIs(TE_array, path_to_data, path_to_mask, path_to_ROIs, pa
     ROI_<label>/table_values.csv per ROI (:476-498; the PNG plots and the tabulate text table are not reproduced).
     Labels are taken from the ROI volume before the mask is applied, as the reference does (:175-178); a label that lies
     entirely outside the mask has no voxels and the reference's nnls_x2 raises ValueError on its nan kernel -- so does this.
-    degibbs='yes': the raw volume is unrung first (gibbs_filter; see recon_met2_arrays)."""
+    degibbs='yes' or '3d': the raw volume is unrung first (gibbs_filter; see recon_met2_arrays)."""
     import os
     from . import nifti
     img = nifti.load(path_to_data)
