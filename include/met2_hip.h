@@ -618,6 +618,82 @@ int met2_bias_update(int32_t device, int64_t n, double *b, const double *smoothe
                      void *stream);
 int met2_bias_apply(int32_t device, int64_t n, const double *v, const double *b, double *out, double *field, void *stream);
 
+/* Tissue segmentation of a 3-D map (segment='yes'; the second purpose of step 5 of the reference's example pipeline, whose
+ * `fast -t 3 -n 3 -H 0.1 -I 4 -l 20.0 -b` also writes a segmentation of the total water content map).  The hidden-Markov-random-field EM of
+ * Zhang, Brady & Smith (IEEE TMI 20:45-57, 2001): Gaussian classes in log intensity, a Potts prior over the six face neighbours, labels by
+ * iterated conditional modes (ICM).  Stated here from the paper; none of FSL's program text is used and parity with `fast` itself is
+ * unpinned.  There is no partial-volume model: the outputs are hard labels and class posteriors, fast's _seg and _prob_k, not its _pve_k.
+ * DEVICE pointers: v [nx][ny][nz] fp64 in C order (the driver passes the bias-corrected map); mask [nx][ny][nz] uint8 or NULL (every voxel);
+ * out, each may be NULL: seg [nx][ny][nz] uint8, prob [K][nx][ny][nz] fp64, classes [3 K] fp64.  HOST: voxel_mm[3] = (dx, dy, dz) in mm.
+ * K = n_class (the script: 3), beta (-H 0.1), n_outer (4), n_em (10), n_icm (8).
+ *   1. Domain, log, initial classes: steps 1 and 2 of met2_bias_field (Omega, N, y = log v, the histogram initialisation), then n_em EM steps
+ *      of its step 3 with b = 0.  The same kernels through the same host code.
+ *   2. Class constants, on the device: a_k = 1 / (2 var_k) (2 var_k is exact, so one rounding), h_k = 0.5 log var_k.  A class with pi_k = 0 is
+ *      dead: its energy is +inf, it is never chosen and its posterior is 0.
+ *   3. Initial labels: x_i = argmin_k D_ik over the live classes, D_ik = ((y_i - mu_k)^2 a_k) + h_k; ties go to the lowest k; off Omega the
+ *      label is 255.
+ *   4. Neighbourhood: the six face neighbours that lie inside the volume and in Omega.  Axis weight w_a = d_min / d_a, d_min = min(dx, dy, dz)
+ *      (thick slices couple less), made on the host.  P_ik = beta ((w_x c_x + w_y c_y) + w_z c_z), c_a in {0, 1, 2} the number of that axis'
+ *      Omega-neighbours whose label differs from k.
+ *   5. ICM, n_icm sweeps, always all of them (a converged sweep changes nothing; no counter is read back).  A sweep visits every voxel of
+ *      Omega with (ix + iy + iz) even, then every one with it odd; a visit sets x_i = argmin_k (D_ik + P_ik) over the live classes, ties to the
+ *      lowest k.  Voxels of one colour are not neighbours of each other: a colour pass is one launch and its result does not depend on the
+ *      order of the threads.  Every operation of D_ik + P_ik rounds once, in the order written (d = y - mu; (d d) a; + h; the products w_a c_a;
+ *      their sums left to right; beta times that; D + P), and none is fused into a multiply-add: given the device's mu_k, a_k, h_k, numpy
+ *      gives every energy to the bit.
+ *   6. Posterior given the labels: p_ik = exp(m_i - E_ik) / sum_k exp(m_i - E_ik) over the live classes, k ascending, E_ik = D_ik + P_ik,
+ *      m_i = min_k E_ik.
+ *   7. M-step with those p_ik: the formulas and the fixed summation tree of met2_bias_field's M-step (the same kernel) on the sums of p_k,
+ *      p_k y and (p_k (y - mu_k)) (y - mu_k), each term rounded operation by operation, in the E-step's layout of entries and partials;
+ *      pi_k = s_k / N.
+ *   8. n_outer times: steps 2, 5, 6, 7; the labels carry over.  After the last M-step steps 2, 5 and 6 once more for the outputs.
+ * Outputs: classes are numbered by ascending mu_k (rank_k = the number of j with mu_j < mu_k, or mu_j == mu_k and j < k; dead classes take
+ * part with the mean they kept): seg = rank + 1 on Omega and 0 off it, so in a water-content map 1 is the driest tissue and K the wettest;
+ * prob [rank] = the posteriors, 0 off Omega; classes = mu[K], var[K], pi[K], each in rank order.
+ * N = 0 or hi == lo: seg = 1 on Omega, prob[0] = 1 on Omega and the other rows 0, classes as met2_bias_field's (mu = lo, var = 0,
+ * pi = 1 / K); MET2_OK.
+ * MET2_E_INVALID: a negative dimension, K < 1, n_outer < 0, n_em < 1, n_icm < 0, voxel_mm NULL, a voxel size that is not positive and finite,
+ * beta negative or not finite, v NULL.  MET2_E_UNSUPPORTED: K > 8, 2^31 voxels or more.  All of them before any launch; the outputs are then
+ * untouched.  A volume with a zero-sized dimension returns MET2_OK at once (after the checks of the dimensions' signs, K, n_outer, n_em,
+ * n_icm, voxel_mm and beta).
+ * Deterministic: the sums are those of met2_bias_field (memory order, fixed tree), a colour pass does not depend on the order of its threads,
+ * and nothing else is shared between voxels; so the result is the same bits from run to run, does not depend on the launch geometry or the
+ * tiling, and does not change when the volume is embedded in a larger one whose added voxels are outside the mask.  The host reads nothing
+ * back during the call.  BLOCKING: the entry allocates its own work space (22 bytes per voxel, and 8 K more when prob is asked for),
+ * enqueues every launch on `stream` -- 7 + 2 n_em + 2 + n_outer (2 n_icm + 3) + 2 n_icm + 2 of them -- waits and frees the space. */
+int met2_tissue_segment(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double *v, const uint8_t *mask, const double voxel_mm[3],
+                        int32_t n_class, double beta, int32_t n_outer, int32_t n_em, int32_t n_icm, uint8_t *seg, double *prob, double *classes,
+                        void *stream);
+
+/* The stages of met2_tissue_segment one by one, for tests and diagnostics, after the pattern of met2_bias_*: each launches the production
+ * kernels through the host code met2_tissue_segment itself runs, on input the caller supplies, allocates and frees what it needs and BLOCKS.
+ * Steps 1 and 7 are met2_bias_domain, met2_bias_init and met2_bias_em (b = 0) and the M-step's sum (met2_bias_em's note).  n = the voxels,
+ * N = n_domain, np = ceil(N / 1024), K = n_class.  DEVICE pointers: y [n] fp64; idx [n] int32; labels [n] uint8 (a class 0..K-1 on Omega,
+ * 255 off it); prob_out, prob_raw, prob [K][n] fp64; seg [n] uint8.  HOST pointers: everything else; classes_in [3 K] = mu, var, pi with
+ * finite mu, finite var > 0 and finite pi >= 0.  idx[0..N) must hold voxel indices in [0, n), unchecked.  Additive: MET2_ABI_VERSION stays 6.
+ *
+ * met2_seg_consts: step 2; a_out [K], h_out [K], live_out [K] (1, or 0 for a dead class); each may be NULL.
+ * met2_seg_init: step 3; labels: all n written, 255 off idx[0..N).
+ * met2_seg_icm: step 5 in place on labels, with the caller's axis weights w[3] (finite, >= 0) and beta.  colour = -1: n_sweeps sweeps;
+ *   colour = 0 or 1: that colour pass of one sweep (none when n_sweeps = 0).  Omega is where labels != 255: the stencil needs no list.
+ * met2_seg_posterior: step 6 on idx[0..N), N >= 1; prob_out (NULL allowed) [k][i] = p_ik in the order of classes_in, all K n written, 0 off
+ *   the list; part_out (NULL allowed) [3][K][np]: per chunk of 1024 list entries the sums of p_k, p_k y and (p_k d) d, d = y - mu_k, every
+ *   operation rounded once, added in the order of met2_bias_em's note.
+ * met2_seg_finish: the rank by mu, seg, prob (NULL allowed; needs prob_raw, the posteriors in the order of classes_in) and classes_out
+ *   [3 K] in rank order (NULL allowed).  A label that is no class gives seg = 0 and prob = 0.
+ * The checks and codes are those of met2_tissue_segment where they apply; a volume without a voxel, N outside 0..n (1..n for the posterior),
+ * n_sweeps < 0, colour outside -1..1 and a bad weight are MET2_E_INVALID; all before any launch. */
+int met2_seg_consts(int32_t device, int32_t n_class, const double *classes_in, double *a_out, double *h_out, int32_t *live_out, void *stream);
+int met2_seg_init(int32_t device, int64_t n, const double *y, const int32_t *idx, int64_t n_domain, int32_t n_class, const double *classes_in,
+                  uint8_t *labels, void *stream);
+int met2_seg_icm(int32_t device, int32_t nx, int32_t ny, int32_t nz, uint8_t *labels, const double *y, int32_t n_class, const double *classes_in,
+                 const double w[3], double beta, int32_t n_sweeps, int32_t colour, void *stream);
+int met2_seg_posterior(int32_t device, int32_t nx, int32_t ny, int32_t nz, const uint8_t *labels, const double *y, const int32_t *idx,
+                       int64_t n_domain, int32_t n_class, const double *classes_in, const double w[3], double beta, double *prob_out,
+                       double *part_out, void *stream);
+int met2_seg_finish(int32_t device, int64_t n, const uint8_t *labels, const double *prob_raw, int32_t n_class, const double *classes_in,
+                    uint8_t *seg, double *prob, double *classes_out, void *stream);
+
 /* Brain extraction (brain_mask='yes'; an extension: the reference's example pipeline makes the mask on the CPU, with FSL's
  * `fslmaths -Tmean` and `bet -m -f 0.4`, example_script_run_MET2_preproc_and_recon.sh step 3).  The surface model of Smith, Fast robust
  * automated brain extraction, HBM 17:143-155, 2002 -- the model bet runs -- WITHOUT bet's self-intersection retry pass, its skull and

@@ -256,6 +256,61 @@ def _bias_last(res, mask, voxel_size, device):
     res["TWC_bias"] = field
 
 
+def tissue_segment_filter(vol, mask=None, voxel_size=(1, 1, 1), n_class=3, beta=0.1, n_outer=4, n_em=10, n_icm=8, device=0, return_prob=True):
+    """Tissue segmentation of a 3-D map (met2_tissue_segment in include/met2_hip.h states the algorithm: the hidden-Markov-random-field EM of
+    Zhang, Brady & Smith 2001, the model of FSL's fast: Gaussian classes in log intensity, a Potts prior of strength `beta` over the six face
+    neighbours weighted by the voxel size, labels by iterated conditional modes) on the device: `vol` [nx,ny,nz] (the drivers pass the
+    bias-corrected water-content map), `mask` [nx,ny,nz] or None (every voxel), `voxel_size` (dx, dy, dz) in mm.  The defaults are those of the
+    reference's example script (fast -n 3 -H 0.1); parity with fast itself is unpinned, and there is no partial-volume model: hard labels
+    and class posteriors (fast's _seg and _prob_k), no _pve_k maps.  Voxels outside the mask, non-finite or not positive are left out.
+    -> seg [nx,ny,nz] uint8: 0 where left out, otherwise 1..n_class by ascending class mean (1 the driest tissue of a water-content map);
+    return_prob=True: (seg, prob [n_class,nx,ny,nz]: the class posteriors in that order, 0 where left out, classes [3 n_class]: the class
+    means and variances of log(vol) and the class weights, in that order too).
+    numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    as_numpy = not torch.is_tensor(vol)
+    dev = torch.device("cuda", device) if as_numpy else vol.device
+    dd = torch.as_tensor(vol, dtype=torch.float64, device=dev).contiguous()
+    if dd.dim() != 3 or (mask is not None and tuple(np.shape(mask)) != tuple(dd.shape)):
+        raise ValueError("vol must be [nx,ny,nz] and mask the same shape")
+    vox = np.asarray(voxel_size, dtype=np.float64).reshape(-1)
+    if vox.shape != (3,):
+        raise ValueError("voxel_size must be (dx, dy, dz)")
+    mk = None if mask is None else (torch.as_tensor(mask, device=dev) != 0).to(torch.uint8).contiguous()
+    K = max(int(n_class), 0)
+    seg = torch.zeros(tuple(dd.shape), dtype=torch.uint8, device=dev)
+    prob = torch.zeros((K,) + tuple(dd.shape), dtype=torch.float64, device=dev) if return_prob else None
+    classes = torch.zeros(3 * K, dtype=torch.float64, device=dev) if return_prob else None
+    nx, ny, nz = dd.shape
+    with torch.cuda.device(dev):
+        check(lib().met2_tissue_segment(dev.index or 0, nx, ny, nz, dd.data_ptr(), None if mk is None else mk.data_ptr(), vox.ctypes.data_as(_dp),
+                                        int(n_class), float(beta), int(n_outer), int(n_em), int(n_icm), seg.data_ptr(),
+                                        prob.data_ptr() if return_prob else None, classes.data_ptr() if return_prob else None,
+                                        torch.cuda.current_stream(dev).cuda_stream))
+    if not return_prob:
+        return seg.cpu().numpy() if as_numpy else seg
+    return tuple(t.cpu().numpy() for t in (seg, prob, classes)) if as_numpy else (seg, prob, classes)
+
+
+def _segment_check(segment, bias_correct, distributed):
+    """segment of the drivers, checked before any device work -> True when the step is to run"""
+    if segment not in ("no", "yes"):
+        raise ValueError("segment must be 'no' or 'yes'")
+    if segment == "no":
+        return False
+    if bias_correct != "yes":
+        raise ValueError("segment='yes' needs bias_correct='yes': the bias-corrected map is what is segmented")
+    if distributed:
+        raise ValueError("segment='yes' does not go with distributed=True: the map is complete only after the gather")
+    return True
+
+
+def _segment_last(res, mask, voxel_size, device):
+    """segment='yes' of the drivers, after _bias_last: the corrected res['TWC'] through tissue_segment_filter -> 'TWC_seg', 'TWC_prob'"""
+    seg, prob, _ = tissue_segment_filter(np.ascontiguousarray(res["TWC"], dtype=np.float64), np.asarray(mask) != 0, voxel_size, device=device)
+    res["TWC_seg"] = seg
+    res["TWC_prob"] = prob
+
+
 def gaussian_smooth(data, sigma=2.0, truncate=4.0, device=0):
     """The Gaussian pre-smoothing of the FA step (motor:337-343): every echo volume of data [nx,ny,nz,nt] through the
     equivalent of scipy.ndimage.gaussian_filter(volume, sigma) (mode 'reflect', truncate 4), on the device, bit-identical
@@ -332,7 +387,7 @@ def _estimate_fa(plan, dd_fa, mm, FA_method, fa_index, T2s, T1s, tau, TR, alpha_
 def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2", FA_method="brute-force", myelin_T2=40.0,
                       fa_index=None, device=0, plan=None, denoise="None", prepared=False, FA_smooth="no", distributed=False,
                       return_prepared=False, devices=None, bootstrap=None, degibbs="no", bias_correct="no", voxel_size=None,
-                      brain_mask="no"):
+                      brain_mask="no", segment="no"):
     """Steps 1-4 of motor_recon_met2 (motor:293-373, 427-472) on arrays: data [nx,ny,nz,nt] (or
     [nvox, nt]), mask [nx,ny,nz].  Mirrors the driver's preparation: data *= mask (motor:180-182),
     negative values clipped to 0 (motor:279), optional NESMA / TV filter (motor:293-333, needs a 3-D volume) or denoise='MPPCA'
@@ -350,6 +405,12 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     corrected map and 'TWC_bias' the estimated field; the other outputs, the bootstrap's included, are not touched.  Needs data [nx,ny,nz,nt]
     and voxel_size; ValueError otherwise and with distributed=True; on the devices=[...] path it runs on devices[0], on the assembled map.
     Parity with fast itself is unpinned (no Markov random field term).  bias_correct='no' (default) changes nothing.
+    segment='yes' (the other product of that fast call; needs bias_correct='yes'): the corrected TWC map then goes through
+    tissue_segment_filter with the same mask and voxel_size (3 classes, beta 0.1: fast -n 3 -H 0.1) and the result gains 'TWC_seg' (uint8: 0
+    outside, 1..3 by ascending water content) and 'TWC_prob' [3,nx,ny,nz] (the class posteriors); nothing else changes.  ValueError before
+    any device work for a value other than 'no' / 'yes', without bias_correct='yes' and with distributed=True; on the devices=[...] path it
+    runs on devices[0].  Parity with fast itself is unpinned, and there are no partial-volume maps (no partial-volume model).  segment='no'
+    (default) changes no output and no launch.
     brain_mask='yes' (step 3 of the reference's example script, which runs FSL's fslmaths -Tmean and bet -m -f 0.4 there): `mask` is None
     and the mask is made by brain_mask_filter from the echo mean of the raw volume -- of the unrung one with degibbs='yes' -- with
     voxel_size=(dx, dy, dz) in mm, after degibbs and before the mask multiply; the result carries it as 'mask' (uint8).  Needs data
@@ -381,6 +442,7 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
         raise ValueError("FA_method must be 'spline' or 'brute-force'")
     if denoise not in ("None", None, "none", "NESMA", "TV", "MPPCA"):
         raise ValueError("denoise must be 'None', 'NESMA', 'TV' or 'MPPCA'")
+    seg = _segment_check(segment, bias_correct, distributed)
     bet = _brain_mask_check(brain_mask, mask, data, voxel_size, prepared, distributed)
     first_dev = devices[0] if devices else plan.device.index or 0 if plan is not None else device
     data = _degibbs_first(data, degibbs, prepared, first_dev)
@@ -389,7 +451,7 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     if bet:
         made = brain_mask_filter(np.ascontiguousarray(data), voxel_size, device=first_dev)
         res = recon_met2_arrays(data, made, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, fa_index, device, plan, denoise, False,
-                                FA_smooth, False, return_prepared, devices, bootstrap, "no", bias_correct, voxel_size)
+                                FA_smooth, False, return_prepared, devices, bootstrap, "no", bias_correct, voxel_size, "no", segment)
         res["mask"] = made
         return res
     bias = _bias_check(bias_correct, vol_shape, voxel_size, distributed)
@@ -419,6 +481,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
                 plan.close()
         if bias:
             _bias_last(res, mask, voxel_size, devices[0])
+        if seg:
+            _segment_last(res, mask, voxel_size, devices[0])
         return res
     dev = plan.device if plan is not None else torch.device("cuda", device)
     # a caller's own plan, a distributed run, or a bare voxel list: the volume on the device in one piece
@@ -463,6 +527,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
             _bootstrap_into(res, plan, reg_method, dd, fa_vol, mm, boot, (T2s, T1s, tau, TR))
         if bias:
             _bias_last(res, mask, voxel_size, dev.index or 0)
+        if seg:
+            _segment_last(res, mask, voxel_size, dev.index or 0)
         return res
     finally:
         if own:
@@ -672,7 +738,7 @@ def _recon_sharded(plan, dd, dd_fa, mm, reg_method, FA_method, fa_index, T2s, T1
 
 def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR, reg_method, reg_matrix, denoise, FA_method,
                      FA_smooth, myelin_T2, num_cores=-1, device=0, devices=None, bootstrap=None, degibbs="no", bias_correct="no",
-                     brain_mask="no"):
+                     brain_mask="no", segment="no"):
     """Drop-in for motor_recon_met2 (motor:165-506) with the reference's on-disk contract: NIfTI in
     (data [nx,ny,nz,nt], mask [nx,ny,nz]), ten NIfTI volumes out (MWF, IEWF, FWF, T2_M, T2_IE, TWC, FA, fsol_4D,
     Est_Signal, reg_param .nii.gz at path_to_save_data, motor:475-503).  `num_cores` is accepted and ignored (one
@@ -681,6 +747,9 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     map MPPCA_sigma.nii.gz).  degibbs='yes' or '3d' (see recon_met2_arrays): the raw volume is unrung first (gibbs_filter) and written as
     Data_degibbs.nii.gz.  bias_correct='yes' (see recon_met2_arrays): TWC.nii.gz is the bias-corrected map and TWC_bias.nii.gz the
     estimated field, as the example script leaves them; the voxel size is the data header's pixdim[1:4] (absolute values, 0 read as 1).
+    segment='yes' (see recon_met2_arrays; needs bias_correct='yes'): TWC_seg.nii.gz (0 outside, 1..3 by ascending water content) and
+    TWC_prob_0.nii.gz .. TWC_prob_2.nii.gz (the class posteriors), named after fast's _seg and _prob_k.  No TWC_pve_k is written: there is no
+    partial-volume model; parity with fast itself is unpinned.
     brain_mask='yes' (see recon_met2_arrays): path_to_mask is None, the mask is made by brain_mask_filter from the echo mean (of the unrung
     volume with degibbs='yes') with the header's voxel size, and Data_avg.nii.gz (the echo mean) and mask.nii.gz are written beside the
     outputs, as the example script's step 3 leaves Data_avg and Data_mask.
@@ -695,6 +764,7 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
         raise ValueError("brain_mask must be 'no' or 'yes'")
     if brain_mask == "yes" and path_to_mask is not None:
         raise ValueError("brain_mask='yes' makes the mask itself and does not go with path_to_mask")
+    _segment_check(segment, bias_correct, False)
     mask = None if brain_mask == "yes" else nifti.load(path_to_mask).get_fdata().astype(np.int64)
     if data.ndim != 4 or (mask is not None and mask.shape != data.shape[:3]):
         raise ValueError("data must be 4-D and mask must match its first three dimensions")
@@ -704,6 +774,8 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
         voxel_size = tuple(abs(float(p)) or 1.0 for p in pixdim[1:4])
     if bias_correct != "no":
         bias_kw = {"bias_correct": bias_correct, "voxel_size": voxel_size}
+    if segment != "no":
+        bias_kw["segment"] = segment
     if degibbs != "no":
         data = _degibbs_first(data, degibbs, False, devices[0] if devices else device)
         nifti.save(nifti.NiftiImage(data, img.affine), path_to_save_data + "Data_degibbs.nii.gz")
@@ -720,6 +792,10 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
         res["mask"] = mask
     if bias_kw:
         nifti.save(nifti.NiftiImage(res["TWC_bias"], img.affine), path_to_save_data + "TWC_bias.nii.gz")
+    if "TWC_seg" in res:
+        nifti.save(nifti.NiftiImage(res["TWC_seg"], img.affine), path_to_save_data + "TWC_seg.nii.gz")
+        for k in range(res["TWC_prob"].shape[0]):
+            nifti.save(nifti.NiftiImage(np.ascontiguousarray(res["TWC_prob"][k]), img.affine), path_to_save_data + "TWC_prob_%d.nii.gz" % k)
     if denoise in ("TV", "MPPCA"):                                  # motor:302-303
         nifti.save(nifti.NiftiImage(res.pop("data_prepared"), img.affine), path_to_save_data + "Data_denoised.nii.gz")
     if denoise == "MPPCA":
