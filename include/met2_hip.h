@@ -622,7 +622,7 @@ int met2_bias_apply(int32_t device, int64_t n, const double *v, const double *b,
  * `fast -t 3 -n 3 -H 0.1 -I 4 -l 20.0 -b` also writes a segmentation of the total water content map).  The hidden-Markov-random-field EM of
  * Zhang, Brady & Smith (IEEE TMI 20:45-57, 2001): Gaussian classes in log intensity, a Potts prior over the six face neighbours, labels by
  * iterated conditional modes (ICM).  Stated here from the paper; none of FSL's program text is used and parity with `fast` itself is
- * unpinned.  There is no partial-volume model: the outputs are hard labels and class posteriors, fast's _seg and _prob_k, not its _pve_k.
+ * unpinned.  The outputs are hard labels and class posteriors, fast's _seg and _prob_k; its _pve_k are met2_partial_volume's, below.
  * DEVICE pointers: v [nx][ny][nz] fp64 in C order (the driver passes the bias-corrected map); mask [nx][ny][nz] uint8 or NULL (every voxel);
  * out, each may be NULL: seg [nx][ny][nz] uint8, prob [K][nx][ny][nz] fp64, classes [3 K] fp64.  HOST: voxel_mm[3] = (dx, dy, dz) in mm.
  * K = n_class (the script: 3), beta (-H 0.1), n_outer (4), n_em (10), n_icm (8).
@@ -693,6 +693,90 @@ int met2_seg_posterior(int32_t device, int32_t nx, int32_t ny, int32_t nz, const
                        double *part_out, void *stream);
 int met2_seg_finish(int32_t device, int64_t n, const uint8_t *labels, const double *prob_raw, int32_t n_class, const double *classes_in,
                     uint8_t *seg, double *prob, double *classes_out, void *stream);
+
+/* Partial-volume tissue maps of a segmented 3-D map (segment='pve'; what the reference's `fast` call of step 5 writes by default: _pve_k,
+ * _pveseg and _mixeltype).  The mixel model of Santago & Gage (Quantification of MR brain images by mixture density and partial volume
+ * modeling, IEEE TMI 12:566-574, 1993) as Shattuck et al. (NeuroImage 13:856-876, 2001) and Tohka, Zijdenbos & Evans (NeuroImage 23:84-97,
+ * 2004) use it: a voxel is pure tissue or a mixture of two tissues, a mixture's likelihood is the Gaussian of the mixed intensity
+ * marginalised over a uniform fraction, a Potts-like prior over the six face neighbours couples the types, and the fraction of a mixed
+ * voxel is Tohka's closed form.  Stated here from the papers; none of FSL's program text is used and parity with `fast` itself is unpinned.
+ * It runs after met2_tissue_segment, on its outputs.
+ * DEVICE pointers: v [nx][ny][nz] fp64 in C order (the map that was segmented); seg [n] uint8 and prob [K][n] fp64 exactly as
+ * met2_tissue_segment writes them (rank order, 0 off Omega); out, each may be NULL: pve [K][n] fp64, pveseg [n] uint8, mixeltype [n] uint8,
+ * classes_lin [3 K] fp64.  HOST: voxel_mm[3] = (dx, dy, dz) in mm.  K = n_class (the script: 3), beta_pv (fast's -R, default 0.3, which the
+ * script leaves alone), n_icm (8).  n = nx ny nz; Omega = the voxels with seg != 0, N of them.
+ *   1. Class moments in LINEAR intensity (partial volume mixes intensities, not their logs): s_k = sum p_ik, mu_k = (sum p_ik v_i) / s_k;
+ *      then, in a second pass, var_k = (sum (p_ik d) d) / s_k with d = v_i - mu_k; pi_k = s_k / N.  The sums run over the compacted list of
+ *      Omega in memory order, in the fixed tree of met2_bias_em's note (chunks of 1024 list entries, then the partials); every term is
+ *      rounded operation by operation.  A class with s_k = 0 gets mu_k = var_k = pi_k = 0.  A class is DEAD when s_k = 0 or var_k is not
+ *      finite and positive.
+ *   2. Mixel types: t = 0..K-1 are pure; t = K + j (j = 0..K-2) is a mixture of the rank-adjacent classes j and j + 1; T = 2 K - 1 <= 15.
+ *      A mixture is dead when either member is dead or mu_{j+1} - mu_j is not positive.
+ *   3. Constants, on the device.  Pure: a_k = 1 / (2 var_k), h_k = 0.5 log var_k.  Every mixture has 64 midpoint nodes
+ *      alpha_m = (m + 0.5) / 64: m_jm = alpha_m mu_j + (1 - alpha_m) mu_{j+1}, s_jm = alpha_m^2 var_j + (1 - alpha_m)^2 var_{j+1},
+ *      a_jm = 1 / (2 s_jm), h_jm = 0.5 log s_jm: a table [K-1][64][3] = (m, a, h), the same for every voxel, which the energy kernel reads
+ *      from LDS.  The entries of a dead class or mixture are 0.
+ *   4. Energies, once, E [T][n].  Pure: E = ((d d) a_k) + h_k, d = v - mu_k.  Mixed: q_m = (((v - m_jm)^2) a_jm) + h_jm, q* = min_m q_m,
+ *      S = sum_m exp(q* - q_m) with m ascending, E = q* - log(S / 64): minus the log of the likelihood marginalised over the fraction by the
+ *      midpoint rule.  The common log(2 pi) / 2 is dropped.  No operation is fused into a multiply-add.  A dead type has E = +inf.
+ *      The midpoint rule needs (mu_{j+1} - mu_j) / 64 small against the classes' standard deviations, which holds for any map whose classes
+ *      can be told apart at all.
+ *   5. Initial types: t_i = argmin_t E_it over the live types, ties to the lowest t; off Omega the type is 255.  When no type is live,
+ *      t_i = seg_i - 1 and the sweeps change nothing.
+ *   6. Prior and ICM.  The six face neighbours inside the volume and Omega, axis weights w_a = d_min / d_a made on the host, as in
+ *      met2_tissue_segment.  The distance of two types, doubled so that it is an integer: delta2(t, u) = 0 for t = u, 1 when their member
+ *      sets ({k} for pure k, {j, j + 1} for mixture j) intersect, 2 otherwise.  c_a = the sum of delta2(t, type of the neighbour) over that
+ *      axis' Omega-neighbours, 0..4.  P_it = (beta_pv ((w_x c_x + w_y c_y) + w_z c_z)) 0.5, rounded in the order written.  n_icm checkerboard
+ *      sweeps in met2_tissue_segment's schedule (step 5 there: all of them, nothing read back, one launch per colour): a visit sets
+ *      t_i = argmin_t (E_it + P_it) over the live types, ties to the lowest t.  Given E, numpy gives every decision to the bit.
+ *   7. Outputs.  Pure type k: pve_k = 1, the others 0.  Mixture j: alpha = min(max((mu_{j+1} - v) / (mu_{j+1} - mu_j), 0), 1), pve_j = alpha,
+ *      pve_{j+1} = 1 - alpha (Tohka's estimator: the maximum-likelihood fraction for equal variances).  pve = 0 off Omega.
+ *      pveseg = 1 + argmax_k pve_k, ties to the lowest k, 0 off Omega.  mixeltype = t, 255 off Omega.  classes_lin = mu[K], var[K], pi[K].
+ * An empty Omega: pve = 0, pveseg = 0, mixeltype = 255, classes_lin = 0; MET2_OK.  A volume with a zero-sized dimension returns MET2_OK at
+ * once (after the checks of the dimensions' signs, K >= 1, n_icm, voxel_mm and beta_pv) and writes nothing.
+ * MET2_E_INVALID: a negative dimension, K < 1, n_icm < 0, voxel_mm NULL, a voxel size that is not positive and finite, beta_pv negative or
+ * not finite, v, seg or prob NULL.  MET2_E_UNSUPPORTED: K > 8, 2^31 voxels or more.  All of them before any launch; the outputs are then
+ * untouched.
+ * Deterministic: the sums are taken in memory order in a fixed tree, a colour pass does not depend on the order of its threads and nothing
+ * else is shared between voxels; so the result is the same bits from run to run, does not depend on the launch geometry or the tiling, and
+ * does not change when the volume is embedded in a larger one whose added voxels have seg = 0, at an offset (ox, oy, oz) with ox + oy + oz
+ * even (the colours of a sweep are those of the absolute coordinates: at an odd offset its two passes change places, which can settle a
+ * few voxels differently).  The host reads nothing back during the call.  BLOCKING: the entry allocates its own work space
+ * (8 (2 K - 1) + 5 bytes per voxel: E, the list and the types), enqueues every launch on `stream` -- 10 + 2 n_icm of them (3 for the list,
+ * 4 for the moments, the constants, the energies, the passes, the outputs) -- waits and frees the space. */
+int met2_partial_volume(int32_t device, int32_t nx, int32_t ny, int32_t nz, const double *v, const uint8_t *seg, const double *prob,
+                        const double voxel_mm[3], int32_t n_class, double beta_pv, int32_t n_icm, double *pve, uint8_t *pveseg,
+                        uint8_t *mixeltype, double *classes_lin, void *stream);
+
+/* The stages of met2_partial_volume one by one, for tests and diagnostics, after the pattern of met2_seg_*: each launches the production
+ * kernels through the host code met2_partial_volume itself runs, on input the caller supplies, allocates and frees what it needs and BLOCKS.
+ * n = the voxels, K = n_class, T = 2 K - 1, nch = ceil(n / 1024), N = the voxels with seg != 0, np = ceil(N / 1024).  DEVICE pointers: v [n]
+ * fp64; seg, types, pveseg, mixeltype [n] uint8; prob, pve [K][n] fp64; E, E_out [T][n] fp64.  HOST pointers: everything else; classes_in
+ * [3 K] = mu, var, pi in linear intensity, any values (step 1's rule says which classes are dead).  Additive: MET2_ABI_VERSION stays 6.
+ *
+ * met2_pve_moments: step 1 (the list of seg != 0, then the two passes).  Each may be NULL: *n_domain = N; part_out [3][K][nch], of which
+ *   the first np of every row are written: per chunk of 1024 list entries the sums of p_k, p_k v and (p_k d) d, added in the order of
+ *   met2_bias_em's note; classes_out [3 K] = mu, var, pi.
+ * met2_pve_consts: steps 2 and 3; a_out [K], h_out [K], live_out [T] (1, or 0 for a dead type), table_out [K-1][64][3]; each may be NULL.
+ * met2_pve_energy: steps 2 to 5 on the list of seg != 0; E_out: all T n written, 0 off the list; types_out (NULL allowed): all n written,
+ *   255 off the list.
+ * met2_pve_icm: step 6 in place on types, given E, the live flags live_in [T], the caller's axis weights w[3] (finite, >= 0) and beta_pv.
+ *   colour = -1: n_sweeps sweeps; colour = 0 or 1: that colour pass of one sweep (none when n_sweeps = 0).  Omega is where types != 255; E
+ *   is read there only.  A type must be 0..T-1 or 255.
+ * met2_pve_finish: step 7 from types and the means of classes_in; pve, pveseg, mixeltype: each may be NULL.  A type that is none of 0..T-1
+ *   counts as off Omega.
+ * The checks and codes are those of met2_partial_volume where they apply; a volume without a voxel, a NULL input, n_sweeps < 0, colour
+ * outside -1..1 and a bad weight are MET2_E_INVALID; all before any launch. */
+int met2_pve_moments(int32_t device, int64_t n, const double *v, const uint8_t *seg, const double *prob, int32_t n_class, int64_t *n_domain,
+                     double *part_out, double *classes_out, void *stream);
+int met2_pve_consts(int32_t device, int32_t n_class, const double *classes_in, double *a_out, double *h_out, int32_t *live_out,
+                    double *table_out, void *stream);
+int met2_pve_energy(int32_t device, int64_t n, const double *v, const uint8_t *seg, int32_t n_class, const double *classes_in, double *E_out,
+                    uint8_t *types_out, void *stream);
+int met2_pve_icm(int32_t device, int32_t nx, int32_t ny, int32_t nz, uint8_t *types, const double *E, int32_t n_class, const int32_t *live_in,
+                 const double w[3], double beta_pv, int32_t n_sweeps, int32_t colour, void *stream);
+int met2_pve_finish(int32_t device, int64_t n, const double *v, const uint8_t *types, int32_t n_class, const double *classes_in, double *pve,
+                    uint8_t *pveseg, uint8_t *mixeltype, void *stream);
 
 /* Brain extraction (brain_mask='yes'; an extension: the reference's example pipeline makes the mask on the CPU, with FSL's
  * `fslmaths -Tmean` and `bet -m -f 0.4`, example_script_run_MET2_preproc_and_recon.sh step 3).  The surface model of Smith, Fast robust

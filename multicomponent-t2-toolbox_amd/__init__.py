@@ -11,12 +11,14 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
                             bias_field_filter (bias-field correction of the TWC map, bias_correct='yes': csrc/met2_bias.hip),
                             brain_mask_filter (brain extraction, brain_mask='yes': csrc/met2_bet.hip),
                             tissue_segment_filter (tissue segmentation of the TWC map, segment='yes': csrc/met2_seg.hip),
+                            partial_volume_filter (partial-volume tissue maps of the TWC map, segment='pve': csrc/met2_pve.hip),
                             gaussian_smooth, ROI mode
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
   gibbs.py                  gibbs_tables / gibbs_split / gibbs_split3d / gibbs_lines: the stages of the Gibbs-ringing filter one by one (tests and diagnostics)
   bet.py                    bet_mean / bet_stats / bet_mesh / bet_evolve / bet_fill: the stages of the brain extraction one by one (tests and diagnostics)
   bias.py                   bias_weights / bias_domain / bias_init / bias_em / bias_smooth / bias_update / bias_apply: the stages of the bias-field correction one by one (tests and diagnostics)
   seg.py                    seg_consts / seg_init / seg_icm / seg_posterior / seg_finish: the stages of the tissue segmentation one by one (tests and diagnostics)
+  pve.py                    pve_moments / pve_consts / pve_energy / pve_icm / pve_finish: the stages of the partial-volume maps one by one (tests and diagnostics)
   mppca.py                  mppca_stages: the MP-PCA denoiser with what each of its steps leaves (tests and diagnostics)
   nifti.py                  NIfTI-1 reader / writer for the driver's on-disk contract
   dist.py                   one-process-per-GPU voxel sharding + the single gather of output maps
@@ -40,4 +42,7 @@ def __getattr__(name):
     if name == "tissue_segment_filter":        # motor.tissue_segment_filter, likewise
         from .motor import tissue_segment_filter
         return tissue_segment_filter
+    if name == "partial_volume_filter":        # motor.partial_volume_filter, likewise
+        from .motor import partial_volume_filter
+        return partial_volume_filter
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -261,8 +261,8 @@ def tissue_segment_filter(vol, mask=None, voxel_size=(1, 1, 1), n_class=3, beta=
     Zhang, Brady & Smith 2001, the model of FSL's fast: Gaussian classes in log intensity, a Potts prior of strength `beta` over the six face
     neighbours weighted by the voxel size, labels by iterated conditional modes) on the device: `vol` [nx,ny,nz] (the drivers pass the
     bias-corrected water-content map), `mask` [nx,ny,nz] or None (every voxel), `voxel_size` (dx, dy, dz) in mm.  The defaults are those of the
-    reference's example script (fast -n 3 -H 0.1); parity with fast itself is unpinned, and there is no partial-volume model: hard labels
-    and class posteriors (fast's _seg and _prob_k), no _pve_k maps.  Voxels outside the mask, non-finite or not positive are left out.
+    reference's example script (fast -n 3 -H 0.1); parity with fast itself is unpinned.  The outputs are hard labels and class posteriors
+    (fast's _seg and _prob_k); its _pve_k maps are partial_volume_filter's.  Voxels outside the mask, non-finite or not positive are left out.
     -> seg [nx,ny,nz] uint8: 0 where left out, otherwise 1..n_class by ascending class mean (1 the driest tissue of a water-content map);
     return_prob=True: (seg, prob [n_class,nx,ny,nz]: the class posteriors in that order, 0 where left out, classes [3 n_class]: the class
     means and variances of log(vol) and the class weights, in that order too).
@@ -291,24 +291,70 @@ def tissue_segment_filter(vol, mask=None, voxel_size=(1, 1, 1), n_class=3, beta=
     return tuple(t.cpu().numpy() for t in (seg, prob, classes)) if as_numpy else (seg, prob, classes)
 
 
+def partial_volume_filter(vol, mask=None, voxel_size=(1, 1, 1), n_class=3, beta=0.1, beta_pv=0.3, n_outer=4, n_em=10, n_icm=8, device=0,
+                          seg=None, prob=None):
+    """Partial-volume tissue maps of a 3-D map (met2_partial_volume in include/met2_hip.h states the algorithm: the mixel model of Santago &
+    Gage 1993 as Shattuck et al. 2001 and Tohka et al. 2004 use it -- every voxel pure tissue or a mixture of two rank-adjacent tissues, a
+    Potts-like prior of strength `beta_pv` over the six face neighbours, types by iterated conditional modes, the fraction of a mixed voxel
+    in Tohka's closed form) on the device, after the tissue segmentation: `seg` [nx,ny,nz] and `prob` [n_class,nx,ny,nz] as
+    tissue_segment_filter returns them, or None, and tissue_segment_filter runs first with `mask`, `beta`, `n_outer`, `n_em`, `n_icm`.  The
+    defaults are those of the reference's example script (fast -n 3 -H 0.1, and fast's own -R 0.3); parity with fast itself is unpinned.
+    -> (pve [n_class,nx,ny,nz]: the tissue fractions, summing to 1 on the segmented voxels and 0 elsewhere; pveseg [nx,ny,nz] uint8: 1 + the
+    class of the largest fraction, 0 elsewhere; mixeltype uint8: 0..n_class-1 pure, n_class + j a mixture of classes j and j + 1, 255
+    elsewhere; classes_lin [3 n_class]: the class means and variances of vol itself (not its log) and the class weights).
+    numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    if (seg is None) != (prob is None):
+        raise ValueError("seg and prob go together")
+    vox = np.asarray(voxel_size, dtype=np.float64).reshape(-1)
+    if vox.shape != (3,):
+        raise ValueError("voxel_size must be (dx, dy, dz)")
+    as_numpy = not torch.is_tensor(vol)
+    dev = torch.device("cuda", device) if as_numpy else vol.device
+    dd = torch.as_tensor(vol, dtype=torch.float64, device=dev).contiguous()
+    if dd.dim() != 3 or (mask is not None and tuple(np.shape(mask)) != tuple(dd.shape)):
+        raise ValueError("vol must be [nx,ny,nz] and mask the same shape")
+    K = max(int(n_class), 0)
+    if seg is None:
+        seg, prob, _ = tissue_segment_filter(dd, mask, vox, n_class, beta, n_outer, n_em, n_icm)
+    sg = torch.as_tensor(seg, device=dev).to(torch.uint8).contiguous()
+    pr = torch.as_tensor(prob, dtype=torch.float64, device=dev).contiguous()
+    if tuple(sg.shape) != tuple(dd.shape) or tuple(pr.shape) != (K,) + tuple(dd.shape):
+        raise ValueError("seg must have the shape of vol and prob must be [n_class] + that shape")
+    pve = torch.zeros((K,) + tuple(dd.shape), dtype=torch.float64, device=dev)
+    pveseg = torch.zeros(tuple(dd.shape), dtype=torch.uint8, device=dev)
+    mixel = torch.full(tuple(dd.shape), 255, dtype=torch.uint8, device=dev)
+    classes = torch.zeros(3 * K, dtype=torch.float64, device=dev)
+    nx, ny, nz = dd.shape
+    with torch.cuda.device(dev):
+        check(lib().met2_partial_volume(dev.index or 0, nx, ny, nz, dd.data_ptr(), sg.data_ptr(), pr.data_ptr(), vox.ctypes.data_as(_dp),
+                                        int(n_class), float(beta_pv), int(n_icm), pve.data_ptr(), pveseg.data_ptr(), mixel.data_ptr(),
+                                        classes.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    out = (pve, pveseg, mixel, classes)
+    return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
+
 def _segment_check(segment, bias_correct, distributed):
     """segment of the drivers, checked before any device work -> True when the step is to run"""
-    if segment not in ("no", "yes"):
-        raise ValueError("segment must be 'no' or 'yes'")
+    if segment not in ("no", "yes", "pve"):
+        raise ValueError("segment must be 'no', 'yes' or 'pve'")
     if segment == "no":
         return False
     if bias_correct != "yes":
-        raise ValueError("segment='yes' needs bias_correct='yes': the bias-corrected map is what is segmented")
+        raise ValueError("segment='%s' needs bias_correct='yes': the bias-corrected map is what is segmented" % segment)
     if distributed:
-        raise ValueError("segment='yes' does not go with distributed=True: the map is complete only after the gather")
+        raise ValueError("segment='%s' does not go with distributed=True: the map is complete only after the gather" % segment)
     return True
 
 
-def _segment_last(res, mask, voxel_size, device):
-    """segment='yes' of the drivers, after _bias_last: the corrected res['TWC'] through tissue_segment_filter -> 'TWC_seg', 'TWC_prob'"""
-    seg, prob, _ = tissue_segment_filter(np.ascontiguousarray(res["TWC"], dtype=np.float64), np.asarray(mask) != 0, voxel_size, device=device)
+def _segment_last(res, mask, voxel_size, device, segment="yes"):
+    """segment='yes' of the drivers, after _bias_last: the corrected res['TWC'] through tissue_segment_filter -> 'TWC_seg', 'TWC_prob';
+    segment='pve': those, then partial_volume_filter on them -> 'TWC_pve', 'TWC_pveseg', 'TWC_mixeltype'"""
+    twc = np.ascontiguousarray(res["TWC"], dtype=np.float64)
+    seg, prob, _ = tissue_segment_filter(twc, np.asarray(mask) != 0, voxel_size, device=device)
     res["TWC_seg"] = seg
     res["TWC_prob"] = prob
+    if segment == "pve":
+        res["TWC_pve"], res["TWC_pveseg"], res["TWC_mixeltype"], _ = partial_volume_filter(twc, None, voxel_size, device=device, seg=seg, prob=prob)
 
 
 def gaussian_smooth(data, sigma=2.0, truncate=4.0, device=0):
@@ -408,9 +454,11 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     segment='yes' (the other product of that fast call; needs bias_correct='yes'): the corrected TWC map then goes through
     tissue_segment_filter with the same mask and voxel_size (3 classes, beta 0.1: fast -n 3 -H 0.1) and the result gains 'TWC_seg' (uint8: 0
     outside, 1..3 by ascending water content) and 'TWC_prob' [3,nx,ny,nz] (the class posteriors); nothing else changes.  ValueError before
-    any device work for a value other than 'no' / 'yes', without bias_correct='yes' and with distributed=True; on the devices=[...] path it
-    runs on devices[0].  Parity with fast itself is unpinned, and there are no partial-volume maps (no partial-volume model).  segment='no'
-    (default) changes no output and no launch.
+    any device work for a value other than 'no' / 'yes' / 'pve', without bias_correct='yes' and with distributed=True; on the devices=[...]
+    path it runs on devices[0].  segment='pve': everything 'yes' gives, then partial_volume_filter on the map, the labels and the posteriors
+    (beta_pv 0.3: fast's -R default) adds 'TWC_pve' [3,nx,ny,nz] (the tissue fractions, what fast writes as _pve_k: a white-matter mask
+    for MWF statistics is TWC_pve[k] > 0.9, not a hard label), 'TWC_pveseg' and 'TWC_mixeltype' (uint8).  Parity with fast itself is
+    unpinned.  segment='no' (default) changes no output and no launch.
     brain_mask='yes' (step 3 of the reference's example script, which runs FSL's fslmaths -Tmean and bet -m -f 0.4 there): `mask` is None
     and the mask is made by brain_mask_filter from the echo mean of the raw volume -- of the unrung one with degibbs='yes' -- with
     voxel_size=(dx, dy, dz) in mm, after degibbs and before the mask multiply; the result carries it as 'mask' (uint8).  Needs data
@@ -482,7 +530,7 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
         if bias:
             _bias_last(res, mask, voxel_size, devices[0])
         if seg:
-            _segment_last(res, mask, voxel_size, devices[0])
+            _segment_last(res, mask, voxel_size, devices[0], segment)
         return res
     dev = plan.device if plan is not None else torch.device("cuda", device)
     # a caller's own plan, a distributed run, or a bare voxel list: the volume on the device in one piece
@@ -528,7 +576,7 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
         if bias:
             _bias_last(res, mask, voxel_size, dev.index or 0)
         if seg:
-            _segment_last(res, mask, voxel_size, dev.index or 0)
+            _segment_last(res, mask, voxel_size, dev.index or 0, segment)
         return res
     finally:
         if own:
@@ -748,8 +796,9 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     Data_degibbs.nii.gz.  bias_correct='yes' (see recon_met2_arrays): TWC.nii.gz is the bias-corrected map and TWC_bias.nii.gz the
     estimated field, as the example script leaves them; the voxel size is the data header's pixdim[1:4] (absolute values, 0 read as 1).
     segment='yes' (see recon_met2_arrays; needs bias_correct='yes'): TWC_seg.nii.gz (0 outside, 1..3 by ascending water content) and
-    TWC_prob_0.nii.gz .. TWC_prob_2.nii.gz (the class posteriors), named after fast's _seg and _prob_k.  No TWC_pve_k is written: there is no
-    partial-volume model; parity with fast itself is unpinned.
+    TWC_prob_0.nii.gz .. TWC_prob_2.nii.gz (the class posteriors), named after fast's _seg and _prob_k.  segment='pve' also writes
+    TWC_pve_0.nii.gz .. TWC_pve_2.nii.gz (the tissue fractions), TWC_pveseg.nii.gz and TWC_mixeltype.nii.gz, after fast's _pve_k, _pveseg
+    and _mixeltype.  Parity with fast itself is unpinned.
     brain_mask='yes' (see recon_met2_arrays): path_to_mask is None, the mask is made by brain_mask_filter from the echo mean (of the unrung
     volume with degibbs='yes') with the header's voxel size, and Data_avg.nii.gz (the echo mean) and mask.nii.gz are written beside the
     outputs, as the example script's step 3 leaves Data_avg and Data_mask.
@@ -796,6 +845,11 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
         nifti.save(nifti.NiftiImage(res["TWC_seg"], img.affine), path_to_save_data + "TWC_seg.nii.gz")
         for k in range(res["TWC_prob"].shape[0]):
             nifti.save(nifti.NiftiImage(np.ascontiguousarray(res["TWC_prob"][k]), img.affine), path_to_save_data + "TWC_prob_%d.nii.gz" % k)
+    if "TWC_pve" in res:
+        for k in range(res["TWC_pve"].shape[0]):
+            nifti.save(nifti.NiftiImage(np.ascontiguousarray(res["TWC_pve"][k]), img.affine), path_to_save_data + "TWC_pve_%d.nii.gz" % k)
+        nifti.save(nifti.NiftiImage(res["TWC_pveseg"], img.affine), path_to_save_data + "TWC_pveseg.nii.gz")
+        nifti.save(nifti.NiftiImage(res["TWC_mixeltype"], img.affine), path_to_save_data + "TWC_mixeltype.nii.gz")
     if denoise in ("TV", "MPPCA"):                                  # motor:302-303
         nifti.save(nifti.NiftiImage(res.pop("data_prepared"), img.affine), path_to_save_data + "Data_denoised.nii.gz")
     if denoise == "MPPCA":
