@@ -778,6 +778,54 @@ int met2_pve_icm(int32_t device, int32_t nx, int32_t ny, int32_t nz, uint8_t *ty
 int met2_pve_finish(int32_t device, int64_t n, const double *v, const uint8_t *types, int32_t n_class, const double *classes_in, double *pve,
                     uint8_t *pveseg, uint8_t *mixeltype, void *stream);
 
+/* Per-label statistics of maps and spectra (tissue_stats='yes'; additive, ABI stays 6): what turns the maps, a label volume (the tissue
+ * classes of met2_tissue_segment, a thresholded met2_partial_volume map, an atlas ROI image) and the spectra into "MWF in white matter:
+ * mean, SD, median, quartiles", and the per-tissue mean spectrum the reference leaves as a TO DO (motor/motor_recon_met2_real_data.py:
+ * 375-376).  No plan: `device` and `stream` only.  DEVICE pointers except q_host.
+ * Inputs.  label [nvox], int32: a value in [0, n_label) makes the voxel a member of that label, anything else a non-member.  Series s of
+ * voxel v is values[v voxel_stride + s series_stride], fp64, strides in doubles and > 0: maps are series-major ([S][nvox]: voxel_stride 1,
+ * series_stride nvox), spectra voxel-major ([nvox][n_t2]: voxel_stride n_t2, series_stride 1); both are read in place, along their
+ * contiguous axis.
+ * Per (label, series) the sample is the members' values that are not NaN (+-inf is outside the contract, as for
+ * met2_bootstrap_series_stats):
+ *   n            the sample size, as a double
+ *   mean         the sample mean
+ *   std          ddof = 1, two passes (the second around the mean); 0 for n = 1
+ *   quantile[j]  np.quantile(sample, q[j], method='linear') to the bit: h = (n - 1) q, the order statistics floor(h) and floor(h) + 1,
+ *                numpy's _lerp with its t >= 0.5 branch, no contraction (quantile.hpp, the implementation the bootstrap statistics use)
+ * -0.0 counts as +0.0.  n = 0 gives n = 0 and NaN for everything else (a zero in a table would read as a measurement).  Nothing depends on
+ * floating-point atomics: two runs give the same bits.  n and the quantiles do not depend on the order of the voxels either; the sums of
+ * mean and std run in the order of the member list -- chunks of MET2_STATS_CHUNK members, in a chunk 256 chains of 64 additions and a
+ * binary tree over them, the chunks of a label again by 256 chains (at most 512 long) and the tree -- so no chain is longer than 512
+ * terms: |mean error| <= 1e-13 max|v|, |std error| <= 1e-12 std + 1e-13 max|v|.
+ *   met2_label_index      the member list: order [nvox] holds the members' voxel indices grouped by ascending label, inside a label by
+ *                         ascending voxel index; offset [n_label + 1] the start of every label's group, offset[n_label] the member
+ *                         count.  A counting sort in integers (histogram, scan, stable scatter).
+ *   met2_label_moments    out [n_label][n_series][3] = n, mean, std
+ *   met2_label_quantiles  out [n_label][n_series][n_q]; q_host [n_q] on the HOST, 1 <= n_q.  The series are gathered tile by tile into
+ *                         a dense matrix of sortable 64-bit keys (at most 256 MiB a tile, one series at least); labels of at most
+ *                         MET2_STATS_SMALL_N members are sorted in LDS, the others selected by most-significant-digit radix, 8 levels of
+ *                         8 bits, all ranks of all (label, series) segments of a tile per pass, the bookkeeping on the device.
+ *   met2_label_stats      the three in one call: out [n_label][n_series][3 + n_q] = n, mean, std, quantiles; n_q = 0 is allowed.
+ * Each allocates and frees what it needs and BLOCKS.  Limits: nvox < 2^31, n_label <= MET2_STATS_MAX_LABEL, n_series <=
+ * MET2_STATS_MAX_SERIES, n_q <= MET2_STATS_MAX_Q (MET2_E_UNSUPPORTED beyond).  MET2_E_INVALID: n_label or n_series < 1, nvox < 0, a
+ * stride that is not positive, a probability outside [0, 1] or NaN, a NULL required pointer, offsets that decrease or do not start at 0.
+ * The parameter checks come before any read of device memory.  met2_label_stats_limits (host only) returns the five constants; any
+ * output may be NULL. */
+#define MET2_STATS_CHUNK 16384
+#define MET2_STATS_SMALL_N 1024
+#define MET2_STATS_MAX_LABEL 4096
+#define MET2_STATS_MAX_SERIES 32768
+#define MET2_STATS_MAX_Q 16
+int met2_label_stats_limits(int32_t *chunk, int32_t *small_n, int32_t *max_label, int32_t *max_series, int32_t *max_q);
+int met2_label_index(int32_t device, int64_t nvox, const int32_t *label, int32_t n_label, int32_t *offset, int32_t *order, void *stream);
+int met2_label_moments(int32_t device, int32_t n_label, const int32_t *offset, const int32_t *order, int32_t n_series, const double *values,
+                       int64_t voxel_stride, int64_t series_stride, double *out, void *stream);
+int met2_label_quantiles(int32_t device, int32_t n_label, const int32_t *offset, const int32_t *order, int32_t n_series, const double *values,
+                         int64_t voxel_stride, int64_t series_stride, int32_t n_q, const double *q_host, double *out, void *stream);
+int met2_label_stats(int32_t device, int64_t nvox, const int32_t *label, int32_t n_label, int32_t n_series, const double *values,
+                     int64_t voxel_stride, int64_t series_stride, int32_t n_q, const double *q_host, double *out, void *stream);
+
 /* Brain extraction (brain_mask='yes'; an extension: the reference's example pipeline makes the mask on the CPU, with FSL's
  * `fslmaths -Tmean` and `bet -m -f 0.4`, example_script_run_MET2_preproc_and_recon.sh step 3).  The surface model of Smith, Fast robust
  * automated brain extraction, HBM 17:143-155, 2002 -- the model bet runs -- WITHOUT bet's self-intersection retry pass, its skull and

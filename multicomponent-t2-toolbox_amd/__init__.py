@@ -12,6 +12,7 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
                             brain_mask_filter (brain extraction, brain_mask='yes': csrc/met2_bet.hip),
                             tissue_segment_filter (tissue segmentation of the TWC map, segment='yes': csrc/met2_seg.hip),
                             partial_volume_filter (partial-volume tissue maps of the TWC map, segment='pve': csrc/met2_pve.hip),
+                            label_stats_filter (per-tissue / per-ROI statistics of the maps and spectra, tissue_stats='yes': csrc/met2_stats.hip),
                             gaussian_smooth, ROI mode
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
   gibbs.py                  gibbs_tables / gibbs_split / gibbs_split3d / gibbs_lines: the stages of the Gibbs-ringing filter one by one (tests and diagnostics)
@@ -19,6 +20,7 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   bias.py                   bias_weights / bias_domain / bias_init / bias_em / bias_smooth / bias_update / bias_apply: the stages of the bias-field correction one by one (tests and diagnostics)
   seg.py                    seg_consts / seg_init / seg_icm / seg_posterior / seg_finish: the stages of the tissue segmentation one by one (tests and diagnostics)
   pve.py                    pve_moments / pve_consts / pve_energy / pve_icm / pve_finish: the stages of the partial-volume maps one by one (tests and diagnostics)
+  stats.py                  label_index / label_moments / label_quantiles / label_stats: per-label n, mean, std and np.quantile-exact quantiles of any series (csrc/met2_stats.hip)
   mppca.py                  mppca_stages: the MP-PCA denoiser with what each of its steps leaves (tests and diagnostics)
   nifti.py                  NIfTI-1 reader / writer for the driver's on-disk contract
   dist.py                   one-process-per-GPU voxel sharding + the single gather of output maps

@@ -44,7 +44,8 @@ SYMBOLS = ["met2_default_options", "met2_abi_version", "met2_device_count", "met
            "met2_gibbs_table_cols", "met2_gibbs_tables", "met2_gibbs_split", "met2_gibbs_lines", "met2_degibbs3d", "met2_gibbs_split3d",
            "met2_brain_mask", "met2_bet_stats", "met2_bet_evolve", "met2_bet_fill", "met2_bet_mesh", "met2_bet_mean",
            "met2_tissue_segment", "met2_seg_consts", "met2_seg_init", "met2_seg_icm", "met2_seg_posterior", "met2_seg_finish",
-           "met2_partial_volume", "met2_pve_moments", "met2_pve_consts", "met2_pve_energy", "met2_pve_icm", "met2_pve_finish"]
+           "met2_partial_volume", "met2_pve_moments", "met2_pve_consts", "met2_pve_energy", "met2_pve_icm", "met2_pve_finish",
+           "met2_label_stats_limits", "met2_label_index", "met2_label_moments", "met2_label_quantiles", "met2_label_stats"]
 
 
 def lib():
@@ -115,6 +116,11 @@ def lib():
         L.met2_pve_energy.argtypes = [C.c_int32, C.c_int64, vp, vp, C.c_int32, _dp, vp, vp, vp]
         L.met2_pve_icm.argtypes = [C.c_int32] * 4 + [vp, vp, C.c_int32, C.POINTER(C.c_int32), _dp, C.c_double, C.c_int32, C.c_int32, vp]
         L.met2_pve_finish.argtypes = [C.c_int32, C.c_int64, vp, vp, C.c_int32, _dp, vp, vp, vp, vp]
+        L.met2_label_stats_limits.argtypes = [C.POINTER(C.c_int32)] * 5
+        L.met2_label_index.argtypes = [C.c_int32, C.c_int64, vp, C.c_int32, vp, vp, vp]
+        L.met2_label_moments.argtypes = [C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, C.c_int64, C.c_int64, vp, vp]
+        L.met2_label_quantiles.argtypes = [C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, C.c_int64, C.c_int64, C.c_int32, _dp, vp, vp]
+        L.met2_label_stats.argtypes = [C.c_int32, C.c_int64, vp, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int64, C.c_int32, _dp, vp, vp]
         L.met2_tv_work_bytes.argtypes = [C.c_int32] * 5
         L.met2_tv_work_bytes.restype = C.c_int64
         L.met2_tv_chambolle.argtypes = [C.c_int32] * 5 + [vp, C.c_int32, _dp, C.c_double, C.c_double, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp]

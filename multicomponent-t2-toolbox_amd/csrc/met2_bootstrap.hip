@@ -29,6 +29,7 @@
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
 #include "philox.hpp"
+#include "quantile.hpp"
 #include "wave_ops.hpp"
 
 namespace met2 {
@@ -116,21 +117,8 @@ struct StatArgs {
 // numpy's ordering for np.sort: nan last
 __device__ __forceinline__ bool nan_last_gt(double a, double b) { return a > b || (a != a && b == b); }
 
-// np.quantile(values, p) with method 'linear' on the sorted values: h = (n - 1) p and numpy's _lerp, including its t >= 0.5 branch.
-// No contraction: a fused multiply-add would differ from numpy in the last bit.
-__device__ double quantile_sorted(const double *s, int n, double p)
-{
-#pragma clang fp contract(off)
-    if (s[n - 1] != s[n - 1]) return s[n - 1];                 // a nan among the values: numpy returns nan
-    const double h = (double)(n - 1) * p;
-    const double fl = floor(h);
-    int i0 = (int)fl, i1 = i0 + 1;
-    if (h >= (double)(n - 1)) i0 = i1 = n - 1;
-    const double g = h - fl;
-    const double a = s[i0], b = s[i1];
-    const double d = b - a;
-    return g >= 0.5 ? b - d * (1.0 - g) : a + d * g;
-}
+// np.quantile(values, p) with method 'linear' on the sorted values: quantile.hpp, shared with met2_stats.hip
+using met2::quantile_sorted;
 
 // The lanes of ONE wave exchange values through LDS: a wave's LDS accesses complete in program order, so what is needed is that the compiler
 // keeps them in it (the fences) and that the wave is converged (the barrier, which emits no instruction).  A workgroup barrier would tie the

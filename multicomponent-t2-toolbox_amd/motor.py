@@ -357,6 +357,112 @@ def _segment_last(res, mask, voxel_size, device, segment="yes"):
         res["TWC_pve"], res["TWC_pveseg"], res["TWC_mixeltype"], _ = partial_volume_filter(twc, None, voxel_size, device=device, seg=seg, prob=prob)
 
 
+STAT_QUANTITIES = ("MWF", "IEWF", "FWF", "T2_M", "T2_IE", "TWC", "FA", "reg_param")
+STAT_KEYS = ("n", "mean", "std", "quantiles", "spectrum_mean", "spectrum_quantiles")
+
+
+def label_stats_filter(res, labels, q=None, device=0):
+    """Per-label statistics of a result dict of recon_met2_arrays (met2_label_stats in include/met2_hip.h states the definitions; stats.py
+    holds the stages) on the device: `labels` is an integer volume shaped like the maps -- every distinct value > 0 is a label, mapped to
+    dense indices the way recon_met2_rois does, so a tissue segmentation and an atlas ROI image are served alike; `q` the probabilities
+    (stats.DEFAULT_Q).  Per label the sample of a quantity is its voxels that are not NaN.
+    -> dict(labels [L], quantities = STAT_QUANTITIES, q, n, mean, std [L, 8], quantiles [L, 8, n_q] (np.quantile's 'linear', to the bit),
+    spectrum_mean [L, n_t2]: the per-bin mean of fsol_4D over the label, normalised to sum 1 -- the reference's mean_T2_dist (motor:377) per
+    label, its TO DO (2) of motor:376 --, spectrum_quantiles [L, n_t2, n_q]: the per-bin quantiles scaled by the same factor, the spatial
+    band around it, T2s)."""
+    from . import stats
+    q = stats.DEFAULT_Q if q is None else tuple(float(x) for x in np.asarray(q, dtype=np.float64).reshape(-1))
+    lab_in = labels if torch.is_tensor(labels) else np.asarray(labels)
+    if (lab_in.dtype.is_floating_point if torch.is_tensor(lab_in) else lab_in.dtype.kind not in "iu"):
+        raise ValueError("labels must be an integer volume")
+    vol_shape = tuple(np.shape(res["MWF"]))
+    if tuple(lab_in.shape) != vol_shape:
+        raise ValueError("labels must have the shape of the maps")
+    dev = torch.device("cuda", device)
+    lab = torch.as_tensor(lab_in if torch.is_tensor(lab_in) else np.ascontiguousarray(lab_in).astype(np.int64), device=dev).to(torch.int64).reshape(-1)
+    ids = torch.unique(lab)
+    ids = ids[ids > 0]
+    L = int(ids.numel())
+    if L == 0:
+        raise ValueError("no label > 0")
+    pos = torch.searchsorted(ids, lab).clamp(max=L - 1)
+    dense = torch.where(ids[pos] == lab, pos, torch.full_like(pos, -1)).to(torch.int32)
+    maps = torch.stack([torch.as_tensor(np.ascontiguousarray(res[name], dtype=np.float64), device=dev).reshape(-1) for name in STAT_QUANTITIES])
+    fsol = torch.as_tensor(np.ascontiguousarray(res["fsol_4D"], dtype=np.float64), device=dev)
+    n_t2 = int(fsol.shape[-1])
+    st = stats.label_stats(maps, dense, L, q, "series")
+    sp = stats.label_stats(fsol.reshape(-1, n_t2), dense, L, q, "voxel")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        tot = sp[:, :, 1].sum(axis=1)
+        return {"labels": ids.cpu().numpy(), "quantities": STAT_QUANTITIES, "q": np.asarray(q), "n": st[:, :, 0], "mean": st[:, :, 1],
+                "std": st[:, :, 2], "quantiles": st[:, :, 3:], "spectrum_mean": sp[:, :, 1] / tot[:, None],
+                "spectrum_quantiles": sp[:, :, 3:] / tot[:, None, None], "T2s": np.asarray(res["T2s"])}
+
+
+def _tissue_stats_check(tissue_stats, segment, distributed, pve_threshold=0.9):
+    """tissue_stats of the drivers, checked before any device work -> True when the step is to run"""
+    if tissue_stats not in ("no", "yes"):
+        raise ValueError("tissue_stats must be 'no' or 'yes'")
+    if tissue_stats == "no":
+        return False
+    if segment not in ("yes", "pve"):
+        raise ValueError("tissue_stats='yes' needs segment='yes' or 'pve': the tissue classes are the labels")
+    if distributed:
+        raise ValueError("tissue_stats='yes' does not go with distributed=True: the maps are complete only after the gather")
+    if not 0.5 <= float(pve_threshold) < 1.0:
+        raise ValueError("pve_threshold must lie in [0.5, 1), so that no voxel carries two labels")
+    return True
+
+
+def tissue_labels(res, segment, pve_threshold=0.9):
+    """the label volume tissue_stats='yes' uses: segment='yes' -> TWC_seg (1..3); 'pve' -> k + 1 where TWC_pve[k] > pve_threshold, else 0"""
+    if segment != "pve":
+        return np.asarray(res["TWC_seg"]).astype(np.int32)
+    pve = np.asarray(res["TWC_pve"])
+    lab = np.zeros(pve.shape[1:], dtype=np.int32)
+    for k in range(pve.shape[0]):
+        lab[pve[k] > pve_threshold] = k + 1
+    return lab
+
+
+def _tissue_stats_last(res, dd, plan, segment, pve_threshold, myelin_T2):
+    """tissue_stats='yes' of the drivers, after _segment_last, on the plan's device: label_stats_filter on the tissue labels -> the dict
+    res['tissue_stats'], plus 'all' (the same statistics, one row, of the whole segmented domain TWC_seg > 0) and 'mean_signal_fsol'
+    [L + 1, n_t2] with 'mean_signal_<map>' [L + 1]: the X2 fit with penalty I and factor 1.01 of every label's mean signal on its mean
+    kernel (motor:379-403's dist_T2_mean2, per tissue; the last row the whole domain), by recon_met2_rois on the prepared data `dd` and
+    the run's flip-angle indices."""
+    device = plan.device.index or 0
+    lab = tissue_labels(res, segment, pve_threshold)
+    whole = (np.asarray(res["TWC_seg"]) > 0).astype(np.int32)
+    if not lab.any():
+        raise ValueError("tissue_stats='yes': no voxel carries a tissue label")
+    ts = label_stats_filter(res, lab, device=device)
+    al = label_stats_filter(res, whole, device=device)
+    ts["all"] = {k: al[k][0] for k in STAT_KEYS}
+    Id = create_Laplacian_matrix(plan.n_t2, 0)
+    data = torch.as_tensor(dd).to(plan.device)
+    fits = [recon_met2_rois(data, torch.as_tensor(r, device=plan.device), res["FA_index"], None, res["T2s"], Id, factor=1.01, myelin_T2=myelin_T2,
+                            plan=plan) for r in (lab, whole)]
+    ts["mean_signal_fsol"] = np.concatenate([f["fsol"] for f in fits])
+    for name in MAP_NAMES:
+        ts["mean_signal_" + name] = np.concatenate([f[name] for f in fits])
+    res["tissue_stats"] = ts
+
+
+def tissue_stats_tables(ts):
+    """the two tables motor_recon_met2 writes from res['tissue_stats'] -> (stats [(L + 1) * 8, 5 + n_q] of objects: label, quantity, n, mean,
+    std, q...; spectra [1 + 2 (L + 1), n_t2] of floats: T2s, then per label the normalised mean spectrum and the mean-signal spectrum);
+    the whole domain is the last label, 'all'"""
+    names = [str(int(x)) for x in ts["labels"]] + ["all"]
+    rows, spectra = [], [np.asarray(ts["T2s"], dtype=np.float64)]
+    for i, name in enumerate(names):
+        src = ts["all"] if name == "all" else {k: ts[k][i] for k in STAT_KEYS}
+        for j, quantity in enumerate(ts["quantities"]):
+            rows.append([name, quantity, src["n"][j], src["mean"][j], src["std"][j]] + list(src["quantiles"][j]))
+        spectra += [src["spectrum_mean"], ts["mean_signal_fsol"][i]]
+    return np.array(rows, dtype=object), np.array(spectra, dtype=np.float64)
+
+
 def gaussian_smooth(data, sigma=2.0, truncate=4.0, device=0):
     """The Gaussian pre-smoothing of the FA step (motor:337-343): every echo volume of data [nx,ny,nz,nt] through the
     equivalent of scipy.ndimage.gaussian_filter(volume, sigma) (mode 'reflect', truncate 4), on the device, bit-identical
@@ -433,7 +539,7 @@ def _estimate_fa(plan, dd_fa, mm, FA_method, fa_index, T2s, T1s, tau, TR, alpha_
 def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2", FA_method="brute-force", myelin_T2=40.0,
                       fa_index=None, device=0, plan=None, denoise="None", prepared=False, FA_smooth="no", distributed=False,
                       return_prepared=False, devices=None, bootstrap=None, degibbs="no", bias_correct="no", voxel_size=None,
-                      brain_mask="no", segment="no"):
+                      brain_mask="no", segment="no", tissue_stats="no", pve_threshold=0.9):
     """Steps 1-4 of motor_recon_met2 (motor:293-373, 427-472) on arrays: data [nx,ny,nz,nt] (or
     [nvox, nt]), mask [nx,ny,nz].  Mirrors the driver's preparation: data *= mask (motor:180-182),
     negative values clipped to 0 (motor:279), optional NESMA / TV filter (motor:293-333, needs a 3-D volume) or denoise='MPPCA'
@@ -459,6 +565,14 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     (beta_pv 0.3: fast's -R default) adds 'TWC_pve' [3,nx,ny,nz] (the tissue fractions, what fast writes as _pve_k: a white-matter mask
     for MWF statistics is TWC_pve[k] > 0.9, not a hard label), 'TWC_pveseg' and 'TWC_mixeltype' (uint8).  Parity with fast itself is
     unpinned.  segment='no' (default) changes no output and no launch.
+    tissue_stats='yes' (an extension: the reference's TO DO (2) of motor:376 and its mean-spectrum numbers of motor:377-403, per tissue;
+    needs segment='yes' or 'pve'): after the segmentation the result gains 'tissue_stats', the dict of label_stats_filter on the tissue labels
+    -- TWC_seg with segment='yes'; with 'pve' label k + 1 where TWC_pve[k] > pve_threshold (in [0.5, 1), so that no voxel has two labels)
+    -- plus 'all', the same statistics of the whole segmented domain (TWC_seg > 0), and 'mean_signal_fsol' [L + 1, n_t2] with
+    'mean_signal_<map>' [L + 1]: the X2 fit (penalty I, factor 1.01) of every label's mean signal on its mean kernel, the last row the
+    whole domain (recon_met2_rois on the prepared data and the run's FA_index).  ValueError before any device work for another value,
+    without the segmentation, for a threshold outside [0.5, 1) and with distributed=True; on the devices=[...] path it runs on devices[0].
+    tissue_stats='no' (default) changes no output and no launch.
     brain_mask='yes' (step 3 of the reference's example script, which runs FSL's fslmaths -Tmean and bet -m -f 0.4 there): `mask` is None
     and the mask is made by brain_mask_filter from the echo mean of the raw volume -- of the unrung one with degibbs='yes' -- with
     voxel_size=(dx, dy, dz) in mm, after degibbs and before the mask multiply; the result carries it as 'mask' (uint8).  Needs data
@@ -491,6 +605,7 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     if denoise not in ("None", None, "none", "NESMA", "TV", "MPPCA"):
         raise ValueError("denoise must be 'None', 'NESMA', 'TV' or 'MPPCA'")
     seg = _segment_check(segment, bias_correct, distributed)
+    tstats = _tissue_stats_check(tissue_stats, segment, distributed, pve_threshold)
     bet = _brain_mask_check(brain_mask, mask, data, voxel_size, prepared, distributed)
     first_dev = devices[0] if devices else plan.device.index or 0 if plan is not None else device
     data = _degibbs_first(data, degibbs, prepared, first_dev)
@@ -499,7 +614,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     if bet:
         made = brain_mask_filter(np.ascontiguousarray(data), voxel_size, device=first_dev)
         res = recon_met2_arrays(data, made, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, fa_index, device, plan, denoise, False,
-                                FA_smooth, False, return_prepared, devices, bootstrap, "no", bias_correct, voxel_size, "no", segment)
+                                FA_smooth, False, return_prepared, devices, bootstrap, "no", bias_correct, voxel_size, "no", segment, tissue_stats,
+                                pve_threshold)
         res["mask"] = made
         return res
     bias = _bias_check(bias_correct, vol_shape, voxel_size, distributed)
@@ -512,16 +628,23 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
         if plan is not None or distributed:
             raise ValueError("devices=[...] builds its own plans and does not go with distributed=True")
         res = _recon_multi_device(data, mask, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, fa_index, list(devices), prepared,
-                                  denoise, FA_smooth, return_prepared or boot is not None)
-        if boot is not None:
+                                  denoise, FA_smooth, return_prepared or boot is not None or tstats)
+        dd = None
+        if boot is not None or tstats:
             dd = res["data_prepared"] if return_prepared else res.pop("data_prepared")
             if not return_prepared:
                 res.pop("MPPCA_sigma", None)
             TE_array = np.asarray(TE_array, dtype=np.float64)
-            plan = Met2Plan(nt, res["T2s"].shape[0], 91 * 3 if FA_method == "spline" else 91, device=devices[0], myelin_T2=myelin_T2)
+
+        def device_plan():                                       # a plan with the run's dictionary on devices[0]: the host entry closed its own
+            p = Met2Plan(nt, res["T2s"].shape[0], 91 * 3 if FA_method == "spline" else 91, device=devices[0], myelin_T2=myelin_T2)
+            p.build_dictionary_epg(res["T2s"], 1000.0 * np.ones_like(res["T2s"]), float(TE_array[1] - TE_array[0]),
+                                   np.linspace(90.0, 180.0, p.n_fa), TR)
+            return p
+
+        if boot is not None:
+            plan = device_plan()
             try:
-                plan.build_dictionary_epg(res["T2s"], 1000.0 * np.ones_like(res["T2s"]), float(TE_array[1] - TE_array[0]),
-                                          np.linspace(90.0, 180.0, plan.n_fa), TR)
                 plan.set_penalty("InvT2" if reg_method == "T2SPARC" else reg_matrix, res["T2s"])
                 _bootstrap_into(res, plan, reg_method, torch.as_tensor(dd).to(plan.device), res["FA_index"], mask > 0, boot,
                                 (res["T2s"], 1000.0 * np.ones_like(res["T2s"]), float(TE_array[1] - TE_array[0]), TR))
@@ -531,6 +654,12 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
             _bias_last(res, mask, voxel_size, devices[0])
         if seg:
             _segment_last(res, mask, voxel_size, devices[0], segment)
+        if tstats:
+            plan = device_plan()
+            try:
+                _tissue_stats_last(res, dd, plan, segment, pve_threshold, myelin_T2)
+            finally:
+                plan.close()
         return res
     dev = plan.device if plan is not None else torch.device("cuda", device)
     # a caller's own plan, a distributed run, or a bare voxel list: the volume on the device in one piece
@@ -577,6 +706,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
             _bias_last(res, mask, voxel_size, dev.index or 0)
         if seg:
             _segment_last(res, mask, voxel_size, dev.index or 0, segment)
+        if tstats:
+            _tissue_stats_last(res, dd, plan, segment, pve_threshold, myelin_T2)
         return res
     finally:
         if own:
@@ -786,7 +917,7 @@ def _recon_sharded(plan, dd, dd_fa, mm, reg_method, FA_method, fa_index, T2s, T1
 
 def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR, reg_method, reg_matrix, denoise, FA_method,
                      FA_smooth, myelin_T2, num_cores=-1, device=0, devices=None, bootstrap=None, degibbs="no", bias_correct="no",
-                     brain_mask="no", segment="no"):
+                     brain_mask="no", segment="no", tissue_stats="no", pve_threshold=0.9):
     """Drop-in for motor_recon_met2 (motor:165-506) with the reference's on-disk contract: NIfTI in
     (data [nx,ny,nz,nt], mask [nx,ny,nz]), ten NIfTI volumes out (MWF, IEWF, FWF, T2_M, T2_IE, TWC, FA, fsol_4D,
     Est_Signal, reg_param .nii.gz at path_to_save_data, motor:475-503).  `num_cores` is accepted and ignored (one
@@ -802,7 +933,12 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     brain_mask='yes' (see recon_met2_arrays): path_to_mask is None, the mask is made by brain_mask_filter from the echo mean (of the unrung
     volume with degibbs='yes') with the header's voxel size, and Data_avg.nii.gz (the echo mean) and mask.nii.gz are written beside the
     outputs, as the example script's step 3 leaves Data_avg and Data_mask.
-    Not reproduced: the mean-spectrum PNG of motor:377-424.
+    tissue_stats='yes' (see recon_met2_arrays; needs segment='yes' or 'pve'): table_tissue_stats.csv, one row per (label, quantity) with the
+    columns label, quantity, n, mean, std and the quantiles 0.025, 0.25, 0.5, 0.75, 0.975 (the labels: the tissues 1..3, then 'all', the
+    whole segmented domain), and table_tissue_spectra.csv: the T2 grid, then per label the normalised mean spectrum of its voxels and
+    the spectrum fitted to its mean signal -- the numbers of the reference's mean-spectrum figure (motor:377-403), per tissue; written
+    with np.savetxt like the ROI driver's tables (tissue_stats_tables makes them).
+    Not reproduced: the mean-spectrum PNG of motor:404-424.
     bootstrap=dict(n_rep=..., seed=...) (an extension, see recon_met2_arrays) also writes <Q>_bootstrap.nii.gz [nx,ny,nz,5] for Q in
     BOOT_QUANTITIES (BOOT_STATS along the last axis) and sigma.nii.gz; with fa='brute-force' / 'spline' also FA_bootstrap.nii.gz [nx,ny,nz,5]
     (degrees), with spectrum=True also fsol_bootstrap_{mean,std,q025,q500,q975}.nii.gz [nx,ny,nz,n_t2] each."""
@@ -814,6 +950,7 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     if brain_mask == "yes" and path_to_mask is not None:
         raise ValueError("brain_mask='yes' makes the mask itself and does not go with path_to_mask")
     _segment_check(segment, bias_correct, False)
+    _tissue_stats_check(tissue_stats, segment, False, pve_threshold)
     mask = None if brain_mask == "yes" else nifti.load(path_to_mask).get_fdata().astype(np.int64)
     if data.ndim != 4 or (mask is not None and mask.shape != data.shape[:3]):
         raise ValueError("data must be 4-D and mask must match its first three dimensions")
@@ -825,6 +962,9 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
         bias_kw = {"bias_correct": bias_correct, "voxel_size": voxel_size}
     if segment != "no":
         bias_kw["segment"] = segment
+    if tissue_stats != "no":
+        bias_kw["tissue_stats"] = tissue_stats
+        bias_kw["pve_threshold"] = pve_threshold
     if degibbs != "no":
         data = _degibbs_first(data, degibbs, False, devices[0] if devices else device)
         nifti.save(nifti.NiftiImage(data, img.affine), path_to_save_data + "Data_degibbs.nii.gz")
@@ -850,6 +990,10 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
             nifti.save(nifti.NiftiImage(np.ascontiguousarray(res["TWC_pve"][k]), img.affine), path_to_save_data + "TWC_pve_%d.nii.gz" % k)
         nifti.save(nifti.NiftiImage(res["TWC_pveseg"], img.affine), path_to_save_data + "TWC_pveseg.nii.gz")
         nifti.save(nifti.NiftiImage(res["TWC_mixeltype"], img.affine), path_to_save_data + "TWC_mixeltype.nii.gz")
+    if "tissue_stats" in res:
+        table, spectra = tissue_stats_tables(res["tissue_stats"])
+        np.savetxt(path_to_save_data + "table_tissue_stats.csv", table, delimiter=",", fmt="%s")
+        np.savetxt(path_to_save_data + "table_tissue_spectra.csv", spectra, delimiter=",", fmt="%s")
     if denoise in ("TV", "MPPCA"):                                  # motor:302-303
         nifti.save(nifti.NiftiImage(res.pop("data_prepared"), img.affine), path_to_save_data + "Data_denoised.nii.gz")
     if denoise == "MPPCA":
