@@ -24,8 +24,20 @@ static inline int fail(int code, const std::string &msg) { return met2::abi_fail
 //                     (fit_kernel and its spill-over kernels only: the plan's seed kernel, the Bayes table and the flip-angle walk keep the lean loops)
 //   MET2_ROWWALK_REF  the fit kernels' model signal at one bin per lane runs on the whole wave with one lane read per passive position, not on two
 //                     half waves (test_gpu_row_walk.py; same reach as MET2_SUBST_REF)
+//   MET2_DUAL_REF     the fit kernels' dual at one bin per lane takes x by lane reads, never from its table in the wave's LDS region
+//                     (test_gpu_dual_lds.py; the X2 and NNLS fit kernels: no other kernel has the table)
+//   MET2_DUAL_TAB     launches of at most one wave per SIMD, which take the lane reads by default, keep the table (test_gpu_dual_lds.py: its
+//                     1 024-voxel cases); MET2_DUAL_REF wins over it
+//   MET2_KMAX=<k>     capacity of the fit kernels' passive set in LDS, 8 <= k < nT2 (test_value below; test_gpu_dual_lds.py: the capacity at
+//                     which the table's validity limit lies inside the sets the solves reach)
 //   MET2_DEBUG        synchronous launches with progress lines on stderr
 static inline bool test_switch(const char *name) { return getenv(name) != nullptr; }
+// a test variable that carries a number: its value if it lies in [lo, hi], else dflt
+static inline int test_value(const char *name, int lo, int hi, int dflt)
+{
+    if (const char *e = getenv(name)) { const int v = atoi(e); if (v >= lo && v <= hi) return v; }
+    return dflt;
+}
 
 // Development knobs (first-pass capacity, waves per CU, queue granularity, ...): read only by libraries built with -DMET2_TUNING, which take a
 // value in [lo, hi]; every other build uses dflt.

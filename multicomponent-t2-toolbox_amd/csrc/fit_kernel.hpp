@@ -83,6 +83,8 @@ struct FitArgs {
     static constexpr int TEST_REFAC_PAIR = 1;   // MET2_REFAC_PAIR: the warm re-factorisation never takes its packed leg (refactor_rowwise)
     static constexpr int TEST_SUBST_REF = 2;    // MET2_SUBST_REF: the substitutions' reference loops (back_subst, try_append)
     static constexpr int TEST_ROWWALK_REF = 4;  // MET2_ROWWALK_REF: model_signal on the whole wave, one lane read per position
+    static constexpr int TEST_DUAL_REF = 8;     // dual() takes x by lane reads, never from its table in LDS (nnls_wave.hpp: xtab_store): MET2_DUAL_REF, and
+                                                // every launch of at most one wave per SIMD (fit_impl)
     unsigned long long *refac_count = nullptr;   // test switch MET2_REFAC_COUNT: the calls that took it are counted here
 };
 
@@ -564,17 +566,21 @@ __device__ __forceinline__ void seed_load(NnlsState<NB> &st, const char *seed, i
 // The solver calls of the voxel routine.  BIG = false (the kernel's own voxel loop): the inlined solver, as in rounds 1-4.  BIG = true (the
 // spill-over voxel routine): one NOT-inlined instance of the solver with the spill-over legs compiled in (nnls_big.hpp: big_solve_fn), the
 // state handed over through the stack -- that routine then holds the lambda search and the objectives plus calls, not nine copies of the solver.
-template <int NB, int ONE, bool BIG>
+// The methods whose fit kernel at one bin per lane takes dual()'s x from its table in LDS (nnls_wave.hpp: xtab_store): X2 and plain NNLS.  With the
+// table leg the T2SPARC kernel needs 104 VGPRs where it had 102, the L-curve's spills 10 where it spilled 8 (36 -> 44 B of scratch per lane), the
+// X2 objective-grid kernel 83 VGPRs where it had 80 (5 waves per SIMD, not 6): those keep the lane reads (profiles/dualx_ab.txt, section 3).
+constexpr bool xtab_method(int method) { return method == MET2_X2 || method == MET2_NNLS; }
+template <int NB, int ONE, bool BIG, bool XTAB = false>
 __device__ __forceinline__ void solve_warm(const WaveShared &S, const Band<NB> &bd, NnlsState<NB> &st, double lam, bool aug, int lane)
 {
     if constexpr (BIG) { NnlsState<NB> sc = st; big_solve_fn<NB, ONE>(S, (big_lds_dp)S.R, bd, &sc, lam, (aug ? 1 : 0) | 2); st = sc; }
-    else nnls_solve_warm<NB, ONE>(S, bd, st, lam, aug, lane);
+    else nnls_solve_warm<NB, ONE, false, XTAB>(S, bd, st, lam, aug, lane);
 }
-template <int NB, int ONE, bool BIG>
+template <int NB, int ONE, bool BIG, bool XTAB = false>
 __device__ __forceinline__ void solve_cold(const WaveShared &S, const Band<NB> &bd, NnlsState<NB> &st, double lam, bool aug, int lane)
 {
     if constexpr (BIG) { NnlsState<NB> sc = st; big_solve_fn<NB, ONE>(S, (big_lds_dp)S.R, bd, &sc, lam, aug ? 1 : 0); st = sc; }
-    else nnls_solve<NB, ONE>(S, bd, st, lam, aug, lane);
+    else nnls_solve<NB, ONE, false, XTAB>(S, bd, st, lam, aug, lane);
 }
 template <int NB, bool BIG>
 __device__ __forceinline__ void refine(const WaveShared &S, NnlsState<NB> &st, double lam, double bvec, int lane)
@@ -591,6 +597,7 @@ __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S,
                                           int seed_k, bool have_seed, int lane, int wslot, int qslot)
 {
     constexpr int ONE = (NB == 2) ? (((METHOD >= 10 ? METHOD - 10 : METHOD) <= MET2_LCURVE) ? 1 : MET2_ONE_REFAC) : 0;
+    constexpr bool XT = xtab_method(METHOD);      // dual() with its x table (one bin per lane, BIG = false, translation units with MET2_DUAL_LDS)
     const int n = A.n, m = A.m;
     // ---- load, normalise by the first echo (motor:129-132), h = D^T b
     double b = (lane < m) ? A.data[v * A.vs + lane * A.es] : 0.0;
@@ -605,14 +612,14 @@ __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S,
     bool queued = false;                  // (the L-curve queues its voxel itself)
 
     if (METHOD == MET2_NNLS) {
-        solve_cold<NB, ONE, BIG>(S, bd, st, 0.0, false, lane);
+        solve_cold<NB, ONE, BIG, XT>(S, bd, st, 0.0, false, lane);
     } else if (METHOD == MET2_T2SPARC) {
-        if (have_seed) { seed_load<NB>(st, A.seed, seed_k, fa, lane); solve_warm<NB, ONE, BIG>(S, bd, st, A.t2sparc_lambda, true, lane); }
-        else solve_cold<NB, ONE, BIG>(S, bd, st, A.t2sparc_lambda, true, lane);
+        if (have_seed) { seed_load<NB>(st, A.seed, seed_k, fa, lane); solve_warm<NB, ONE, BIG, XT>(S, bd, st, A.t2sparc_lambda, true, lane); }
+        else solve_cold<NB, ONE, BIG, XT>(S, bd, st, A.t2sparc_lambda, true, lane);
         regv = lamv = A.t2sparc_lambda;
     } else if (METHOD == MET2_X2) {
         // algorithms.py:211-233
-        solve_cold<NB, ONE, BIG>(S, bd, st, 0.0, false, lane);
+        solve_cold<NB, ONE, BIG, XT>(S, bd, st, 0.0, false, lane);
         constexpr bool PIN = uni_brent(METHOD, NB);
         const double SSE = uni<PIN>(sse_of<NB>(S, st, b, lane));
         const double target = uni<PIN>(A.x2_factor * SSE);
@@ -630,7 +637,7 @@ __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S,
         int nref = 0;
         double lam = fminbound_tie_dev<uni_brent(METHOD, NB)>([&](double x, bool refined) {
             if (NB == 2 && (st.itmax_hit & 2)) return 0.0;
-            if (!(refined && x == last_x)) solve_warm<NB, ONE, BIG>(S, bd, st, x, true, lane);
+            if (!(refined && x == last_x)) solve_warm<NB, ONE, BIG, XT>(S, bd, st, x, true, lane);
             if (refined) refine<NB, BIG>(S, st, x, b, lane);
             const double SSEr = uni<PIN>(sse_of<NB>(S, st, b, lane));
             last_x = x; last_sse = SSEr;
@@ -655,7 +662,7 @@ __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S,
                                                             // next pass, the rest of its Brent path here costs nothing (two bins per lane,
                                                             // where 5-10 % of the voxels do; at one bin per lane ~1 % do and the test cost
                                                             // the X2 kernel two more spilled registers)
-            solve_warm<NB, ONE, BIG>(S, bd, st, x, true, lane);
+            solve_warm<NB, ONE, BIG, XT>(S, bd, st, x, true, lane);
             double SSEr = uni<PIN>(sse_of<NB>(S, st, b, lane));
 #ifdef MET2_CYCSTATS
             if (lane == 0) {
@@ -720,7 +727,7 @@ __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S,
         }
         for (int i = i0; i < A.nlam; ++i) {
             double lam = A.lam_grid[i];
-            solve_warm<NB, ONE, BIG>(S, bd, st, lam, true, lane);
+            solve_warm<NB, ONE, BIG, XT>(S, bd, st, lam, true, lane);
             if (!BIG && NB == 2 && (st.itmax_hit & 2)) { at = i; break; }      // capacity hit: the spill-over kernel goes on
             double sse = sse_of<NB>(S, st, b, lane);
             double sn = seminorm2<NB>(bd, st.x, n, lane);
@@ -755,7 +762,7 @@ __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S,
                     st.k = kk;
                 }
         }
-        solve_warm<NB, ONE, BIG>(S, bd, st, regv, true, lane);
+        solve_warm<NB, ONE, BIG, XT>(S, bd, st, regv, true, lane);
         if (!BIG && NB == 2 && (st.itmax_hit & 2)) at = A.nlam;
         }
         if (!BIG && NB == 2 && at >= 0 && A.lc_save) {
@@ -779,7 +786,7 @@ __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S,
         }
     } else if (METHOD == MET2_BAYESREG) {
         // bayesian_interpolation.py:84-105
-        solve_cold<NB, 0, BIG>(S, bd, st, 0.0, false, lane);
+        solve_cold<NB, 0, BIG, XT>(S, bd, st, 0.0, false, lane);
         int nnz = 0;
 #pragma unroll
         for (int bb = 0; bb < NB; ++bb) nnz += __popcll(ballot((lane + 64 * bb < n) && (st.x[bb] > 0.0)));
@@ -791,7 +798,7 @@ __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S,
         double *cholG = (NB == 2 && A.chol) ? A.chol + (size_t)wslot * (size_t)A.chol_stride : nullptr;
         double lam = fminbound_dev<uni_brent(METHOD, NB)>([&](double x) {
             if (NB == 2 && (st.itmax_hit & 2)) return 0.0;  // capacity hit: solved again in the next pass
-            solve_warm<NB, ONE, BIG>(S, bd, st, x, true, lane);
+            solve_warm<NB, ONE, BIG, XT>(S, bd, st, x, true, lane);
             BayesTable tab{nullptr, 0.0};
             if (A.btab && ev < A.nbtab) {                  // still on the abscissae every voxel shares?  (a rounding-level match: the table's
                 const double tl = A.blam[ev];              //  lambda_j is formed on the host, and B + lambda K does not care about an ulp)
@@ -807,7 +814,7 @@ __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S,
         }, []() {}, BIG ? A.lam_lo : 1e-8, BIG ? A.lam_hi : 2.0, A.xtol, A.maxfun, flag);
         if (flag == 1) stat |= MET2_ST_BRENT_MAXFUN;
         if (bc.failed) stat |= MET2_ST_CHOLFAIL;
-        if (!(NB == 2 && (st.itmax_hit & 2))) solve_warm<NB, ONE, BIG>(S, bd, st, lam, true, lane);
+        if (!(NB == 2 && (st.itmax_hit & 2))) solve_warm<NB, ONE, BIG, XT>(S, bd, st, lam, true, lane);
         regv = lamv = lam;
     } else if (METHOD == MET2_GCV || METHOD == MET2_GCV_LR) {
         // algorithms.py:276-283
@@ -816,12 +823,12 @@ __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S,
         if (have_seed) seed_load<NB>(st, A.seed, seed_k, fa, lane);
         double lam = fminbound_dev<uni_brent(METHOD, NB)>([&](double x) {
             if (NB == 2 && (st.itmax_hit & 2)) return 0.0;  // capacity hit: solved again in the next pass
-            solve_warm<NB, ONE, BIG>(S, bd, st, x, true, lane);
+            solve_warm<NB, ONE, BIG, XT>(S, bd, st, x, true, lane);
             return gcv_objective<NB, METHOD == MET2_GCV_LR>(S, bd, st, x, b, lane, overflow, gc);
         }, []() {}, BIG ? A.lam_lo : 1e-8, BIG ? A.lam_hi : 10.0, A.xtol, A.maxfun, flag);
         if (flag == 1) stat |= MET2_ST_BRENT_MAXFUN;
         if (overflow) stat |= MET2_ST_KOVERFLOW;
-        if (!(NB == 2 && (st.itmax_hit & 2))) solve_warm<NB, ONE, BIG>(S, bd, st, lam, true, lane);
+        if (!(NB == 2 && (st.itmax_hit & 2))) solve_warm<NB, ONE, BIG, XT>(S, bd, st, lam, true, lane);
         regv = lamv = lam;
     }
     if (METHOD >= 10) {
@@ -829,7 +836,7 @@ __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S,
         constexpr int BASE = METHOD - 10;
         double SSE = 1.0; BayesCtx bc; bc.failed = 0; bc.log_detL = A.log_detL; bc.beta = 1.0;
         if (BASE == MET2_X2 || BASE == MET2_BAYESREG) {
-            nnls_solve<NB>(S, bd, st, 0.0, false, lane);
+            nnls_solve<NB, 0, false, XT>(S, bd, st, 0.0, false, lane);
             SSE = sse_of<NB>(S, st, b, lane);
             int nnz = 0;
 #pragma unroll
@@ -842,7 +849,7 @@ __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S,
         GcvCache<NB> gc; gc.valid = 0; gc.next = 0;
         for (int i = 0; i < A.nlam; ++i) {
             const double x = A.lam_grid[i];
-            nnls_solve<NB>(S, bd, st, x, true, lane);
+            nnls_solve<NB, 0, false, XT>(S, bd, st, x, true, lane);
             double val;
             if (BASE == MET2_X2) val = fabs(sse_of<NB>(S, st, b, lane) - A.x2_factor * SSE) / SSE;
             else if (BASE == MET2_GCV || BASE == MET2_GCV_LR) val = gcv_objective<NB, BASE == MET2_GCV_LR>(S, bd, st, x, b, lane, overflow, gc);
@@ -880,11 +887,14 @@ __device__ __forceinline__ bool fit_voxel(const FitArgs &A, const WaveShared &S,
 }
 
 // the wave's view of the plan: everything of WaveShared that does not depend on the flip angle
-__device__ __forceinline__ void fit_shared(const FitArgs &A, WaveShared &S, double *sR, int wslot)
+// big: the view of a BIG = true instance (the spill-over voxel routine), which reads gbase; the others read the x table's limit from the same word
+__device__ __forceinline__ void fit_shared(const FitArgs &A, WaveShared &S, double *sR, int wslot, bool big)
 {
     S.R = sR; S.n = A.n; S.m = A.m; S.kmax = A.kmax; S.rcap = A.wave_doubles; S.K = A.Kd; S.kband = A.kband; S.Dt = nullptr; S.DtG = A.Dtfa; S.dtstride = A.m; S.buffer_rows = true; S.reorder = true; S.have_bdiag = false; S.bdiag[0] = S.bdiag[1] = 0.0;
     S.B = A.Bfa; S.D = A.Dfa; S.bstride = A.n; S.dstride = A.n;
-    S.Rg = A.big ? A.big + (size_t)wslot * (size_t)A.big_stride : nullptr; S.gbase = col_base(A.kmax);
+    S.Rg = A.big ? A.big + (size_t)wslot * (size_t)A.big_stride : nullptr;
+    if (big) S.gbase = col_base(A.kmax);
+    else S.xtab_k1 = (A.test_switches & FitArgs::TEST_DUAL_REF) ? 0 : 1 + xtab_limit(A.wave_doubles, A.kmax);
     S.refac_pair = (A.test_switches & FitArgs::TEST_REFAC_PAIR) != 0; S.subst_ref = (A.test_switches & FitArgs::TEST_SUBST_REF) != 0;
     S.rowwalk_ref = (A.test_switches & FitArgs::TEST_ROWWALK_REF) != 0; S.refac_count = A.refac_count;
 }
@@ -917,7 +927,7 @@ __device__ __attribute__((noinline)) void fit_voxel_spill(const FitArgs *Ap, big
     }
     v = (int64_t)big_rfl((u64)v); fa = big_rfl(fa); wslot = big_rfl(wslot); qslot = big_rfl(qslot); seed_cap = big_rfl(seed_cap);
     WaveShared S;
-    fit_shared(A, S, sR, wslot);
+    fit_shared(A, S, sR, wslot, true);
     fit_shared_fa<METHOD>(A, S, fa);
     Band<NB> bd;
     load_band<NB>(bd, A.kband, A.lband, lane);
@@ -948,7 +958,7 @@ __global__ __launch_bounds__(64 * method_max_waves(METHOD, NB)) void fit_kernel(
 
     const int wslot = (int)(blockIdx.x * (unsigned)A.waves + (unsigned)wave);      // this wave's slot in the per-wave scratch arrays
     WaveShared S;
-    fit_shared(A, S, sR, wslot);
+    fit_shared(A, S, sR, wslot, SECOND);
     Band<NB> bd;
     load_band<NB>(bd, A.kband, A.lband, lane);
     MetricLanes<NB> ml;

@@ -1137,7 +1137,7 @@ static int fit_geometry(const met2_plan *p, int method, LaunchGeom &g, int kmax_
 static int fast_kmax(const met2_plan *p, int method)
 {
     if (method >= 10 || (method == MET2_BAYESREG && p->n_t2 <= 64)) return 0;     // (BayesReg at one bin per lane factorises n x n in the wave's region)
-    { const int kk = tuning_env("MET2_KMAX", 8, p->n_t2 - 1, -1); if (kk > 0) return kk; }
+    { const int kk = test_value("MET2_KMAX", 8, p->n_t2 - 1, -1); if (kk > 0) return kk; }
     // the largest capacity that still lets 16 waves share the LDS, but not below 0.6 n.  The figures below were measured with the
     // capacity ladder of rounds 1-4, which solved the voxels that outgrew the capacity again in a clean-up launch at full capacity
     // (measured on X2/L2, nT2 = 60: kmax 48 -> 1.95 M voxels/s, 50 -> 2.10 M, 52 (14 waves) -> 2.03 M, 60 (11 waves) -> 1.84 M;
@@ -1934,7 +1934,11 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
     A.data = data; A.vs = voxel_stride; A.es = echo_stride; A.sb = sb; A.fsol = fsol; A.sig = sig; A.reg = reg; A.lam = lam; A.maps = maps; A.status = status; A.nvox = nvox;
 
     A.test_switches = (test_switch("MET2_REFAC_PAIR") ? FitArgs::TEST_REFAC_PAIR : 0) | (test_switch("MET2_SUBST_REF") ? FitArgs::TEST_SUBST_REF : 0) |
-                      (test_switch("MET2_ROWWALK_REF") ? FitArgs::TEST_ROWWALK_REF : 0);
+                      (test_switch("MET2_ROWWALK_REF") ? FitArgs::TEST_ROWWALK_REF : 0) | (test_switch("MET2_DUAL_REF") ? FitArgs::TEST_DUAL_REF : 0);
+    // dual()'s x table pays where other waves of the SIMD cover its LDS round trip.  A launch of at most one wave per SIMD (a short voxel list:
+    // fit_geometry) is as long as its slowest voxel's chain of latencies, and there the table is slower than the lane reads (configs[0], 1 024 voxels
+    // on 4 waves per CU: -0.7 %, profiles/dualx_ab.txt section 5c): such launches take the lane reads.  MET2_DUAL_TAB (tests) keeps the table.
+    if (g.waves <= 4 && !test_switch("MET2_DUAL_TAB")) A.test_switches |= FitArgs::TEST_DUAL_REF;
     A.refac_count = nullptr;
     if (test_switch("MET2_REFAC_COUNT")) HIPCHK(hipGetSymbolAddress((void **)&A.refac_count, HIP_SYMBOL(g_refac_packed_calls)));
     A.seed = nullptr;

@@ -35,6 +35,12 @@ namespace met2 {
 #define MET2_REORDER 2        // bins per lane from which warm starts re-order the passive set by descending x (reorder_by_x below); 1: always, 3: never
 #endif
 
+// The x table of dual() (xtab_* below) is compiled into the translation units that take the row-walk changes (wave_ops.hpp); -DMET2_DUAL_LDS=0
+// (development) builds them without it.
+#ifndef MET2_DUAL_LDS
+#define MET2_DUAL_LDS MET2_ROWWALK
+#endif
+
 #ifdef MET2_LOOPSTATS
 __device__ int g_loopstats[8];
 #define MET2_STAT(slot, v) atomicMax(&g_loopstats[slot], (int)(v))
@@ -80,7 +86,12 @@ struct WaveShared {
     bool buffer_rows;   // row loads of the global matrices as raw buffer loads (fit kernels); false: plain global loads (the FA walk, whose
                         // 19 MB of dictionaries at 48 x 120 missed L2 1.7x more often through the buffer path: 57 -> 66 ms per 131 k voxels)
     double *Rg = nullptr; // this wave's spill-over slot in global memory: columns c >= kmax of the factor, entry (r, c) at col_base(c) - gbase + r
-    int gbase = 0;        // col_base(kmax)   (nnls_big.hpp; used by the BIG = true instances of the routines below only)
+    union {               // (one word for both: a field more is an argument more of the not-inlined spill-over routines, 16 B of scratch per lane in each)
+        int gbase = 0;    // col_base(kmax)   (nnls_big.hpp; used by the BIG = true instances of the routines below only)
+        int xtab_k1;      // the BIG = false instances: 1 + the largest passive set whose factor leaves the x table of dual() alone (xtab_limit;
+                          // wave-uniform); 0: no table -- the kernels that do not set it, and the fit kernels when the launch asks for the lane reads.
+                          // fit_shared() (fit_kernel.hpp) writes the member that its instance reads, never the other one's value
+    };
     bool refac_pair = false;                     // the packed leg of refactor_rowwise is not taken (the test switch MET2_REFAC_PAIR)
     bool subst_ref = false;                      // the substitutions run their zero-filling reference loops, not the lean ones (the test switch MET2_SUBST_REF;
                                                  // set by the fit kernels only: the seed, Bayes-table and FA-walk kernels always run the lean loops)
@@ -572,8 +583,38 @@ __device__ __forceinline__ bool try_append(const WaveShared &S, const Band<NB> &
     return true;
 }
 
+// The x table (one bin per lane, the translation units built with MET2_DUAL_LDS).  dual() walks the passive set in fours and wants, per position,
+// the bin (for the row of B) and x.  Both used to come out of registers by lane reads: four for the bins, eight for the four 64-bit x -- 12 of the
+// 16 vector instructions of a group, for 4 FMAs.  The bins stay on lane reads (they make the row offsets scalar, and nothing may sit in front of the
+// row loads); x by position comes from a table in the slack of the wave's LDS region: the LAST 64 doubles of the region (16-byte aligned), which the
+// packed factor reaches only when the set grows beyond ktab = the largest k with col_base(k) <= rcap - 64 (48 at the shipped capacity of 50).
+// Entry p holds x at position p, and 0.0 from k on (the walk in fours runs past k).  It is read at wave-uniform addresses -- every lane the same
+// 16 bytes, a broadcast without bank conflicts -- two ds_read_b128 per group, issued behind the group's row loads, whose latency covers them.
+// WRITTEN where nnls_inner accepts z (z IS x by position there: one store per lane, no gather).  READ by dual() only, and every dual() of the
+// iteration (nnls_iterate_plain) runs either on an empty set (no read) or directly behind an nnls_inner that returned true, with nothing in
+// between: whatever changes x, ord or k -- try_append, remove_pos, seed_load, the restore of Brent's best point, refine_csne, the re-ordering
+// and the re-factorisation of a warm start, a column of a set beyond ktab written over the table -- is followed by an accepting nnls_inner
+// before the next dual(), which rewrites all 64 entries if k <= ktab then; and if k > ktab then, dual() runs the lane reads.  No stale entry is
+// ever read.  The FMAs are those of the lane reads, on the same doubles in the same order: the same bits.
+typedef __attribute__((address_space(3))) double *met2_lds_dp;
+typedef const __attribute__((address_space(3))) met2_d2 *met2_lds_cd2p;
+__host__ __device__ __forceinline__ constexpr int xtab_base(int rcap) { return (rcap - 64) & ~1; }
+__host__ __device__ __forceinline__ constexpr int xtab_limit(int rcap, int kmax)
+{
+    int k = -1;
+    if (rcap >= 64) for (k = 0; k < kmax && col_base(k + 1) <= xtab_base(rcap); ++k) ;
+    return k;
+}
+__device__ __forceinline__ void xtab_store(const WaveShared &S, int k, double z, int lane)
+{
+    if (k < S.xtab_k1) {
+        ((met2_lds_dp)S.R)[xtab_base(S.rcap) + lane] = lane_in(k >= 64 ? ~0ull : (1ull << k) - 1ull) ? z : 0.0;
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // dual vector w = h - (B + lam K) x, bin-indexed
-template <int NB>
+template <int NB, bool TAB = false>
 __device__ __forceinline__ void dual(const WaveShared &S, const Band<NB> &bd, const NnlsState<NB> &st, double lam, int lane, double (&w)[NB])
 {
     double kbl[NB][5];                                       // this lane's 5 diagonals of K, in flight during the B loop
@@ -593,6 +634,21 @@ __device__ __forceinline__ void dual(const WaveShared &S, const Band<NB> &bd, co
         jc[b] = (unsigned)min(lane + 64 * b, S.n - 1);
     }
     const int k = st.k;
+    bool tab = false;
+    if constexpr (TAB && NB == 1) tab = k < S.xtab_k1;
+    if (tab) {
+        // x from the table (see xtab_store): no gather, no select, and per group two LDS reads where eight lane reads were
+        const met2_lds_cd2p xt = (met2_lds_cd2p)(S.R + xtab_base(S.rcap));
+#pragma clang loop unroll(disable)
+        for (int p = 0; p < k; p += 4) {
+            double v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = ld_row_sel(S.buffer_rows, S.B, bcast_i(st.ord[0], p + q) * S.bstride, jc[0]);
+            const met2_d2 x01 = xt[p >> 1], x23 = xt[(p >> 1) + 1];
+            acc[0] = fma(v[0], x01.x, acc[0]); acc2[0] = fma(v[1], x01.y, acc2[0]);
+            acc[0] = fma(v[2], x23.x, acc[0]); acc2[0] = fma(v[3], x23.y, acc2[0]);
+        }
+    } else {
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         const double t = gatherN<NB>(st.x, st.ord[b]);                   // x by position; zero past the set, where ord still
@@ -615,6 +671,7 @@ __device__ __forceinline__ void dual(const WaveShared &S, const Band<NB> &bd, co
             acc[b] = fma(v[2][b], xs[2], acc[b]); acc2[b] = fma(v[3][b], xs[3], acc2[b]);
         }
     }
+    }
 #pragma unroll
     for (int b = 0; b < NB; ++b) acc[b] += acc2[b];
     double kx[NB];
@@ -632,7 +689,8 @@ namespace met2 {
 // Lawson-Hanson's secondary loop: from a feasible x and a factor consistent with (P, lambda), move to
 // the solution of the passive sub-problem, dropping variables that hit zero on the way.
 // Returns false when the iteration cap is reached.
-template <int NB, int NP = NB, bool BS1 = false>
+// TAB: the accepted z goes to the x table of dual() (xtab_store).
+template <int NB, int NP = NB, bool BS1 = false, bool TAB = false>
 __device__ __forceinline__ bool nnls_inner(const WaveShared &S, NnlsState<NB> &st, int &iter, int itmax, int lane)
 {
     for (;;) {
@@ -661,6 +719,7 @@ __device__ __forceinline__ bool nnls_inner(const WaveShared &S, NnlsState<NB> &s
         if (!any) {
 #pragma unroll
             for (int b = 0; b < NB; ++b) st.x[b] = zb[b];
+            if constexpr (TAB && NB == 1) xtab_store(S, st.k, z[0], lane);
             return true;
         }
         double rmin = 2.0;
@@ -674,6 +733,7 @@ __device__ __forceinline__ bool nnls_inner(const WaveShared &S, NnlsState<NB> &s
         if (!(alpha < 2.0)) {                                // "alpha still 2": accept z
 #pragma unroll
             for (int b = 0; b < NB; ++b) st.x[b] = zb[b];
+            if constexpr (TAB && NB == 1) xtab_store(S, st.k, z[0], lane);
             return true;
         }
         u64 hit[NB];
@@ -704,22 +764,25 @@ __device__ __forceinline__ bool nnls_inner(const WaveShared &S, NnlsState<NB> &s
 // The passive-set iteration on NB position slots (the general form).
 // BIG (here and below): the instance compiled into the spill-over voxel routine (nnls_big.hpp) -- a set that wants to outgrow the LDS capacity
 // S.kmax goes on with its columns beyond it in the wave's global slot; BIG = false flags the voxel instead (st.itmax_hit bit 1).
-template <int NB, bool BS1 = false, bool BIG = false>
+// XTAB = true: an instance with the x table of dual() -- asked for by the fit kernels' voxel routine only, for the methods that have the registers for it
+// (fit_kernel.hpp: xtab_method); every other caller (the seed, table, flip-angle-walk, bootstrap and evaluation kernels) compiles the lane reads alone.
+template <int NB, bool BS1 = false, bool BIG = false, bool XTAB = false>
 __device__ __forceinline__ void nnls_iterate_plain(const WaveShared &S, const Band<NB> &bd, NnlsState<NB> &st, double lam, int mrows, int lane,
                                                    bool warm)
 {
     const int n = S.n, itmax = 3 * n;
+    constexpr bool TAB = MET2_DUAL_LDS && XTAB && NB == 1 && !BIG;   // the x table of dual(): this loop is its only writer (through nnls_inner) and reader
     int iter = 0;
     if constexpr (BIG) if (st.k > S.kmax) { int outer0 = 0; iterate_big<NB>(S, bd, st, lam, mrows, lane, warm, iter, outer0); return; }      // (a warm start beyond the LDS capacity)
     MET2_CYC_BEGIN(c_in0);
-    if (warm && st.k > 0 && !nnls_inner<NB, NB, BS1>(S, st, iter, itmax, lane)) { st.itmax_hit |= 1; return; }
+    if (warm && st.k > 0 && !nnls_inner<NB, NB, BS1, TAB>(S, st, iter, itmax, lane)) { st.itmax_hit |= 1; return; }
     MET2_CYC_END(2, c_in0);
     for (int outer = 0; outer <= itmax + 1; ++outer) {     // every pass runs >= 1 counted inner pass
         if (st.k >= n || st.k >= mrows) break;
         double w[NB];
         MET2_CYC_BEGIN(c_du);
-        if (MET2_DOUBLE == 2) { dual<NB>(S, bd, st, lam, lane, w); asm volatile("" :: "v"(w[0])); }
-        dual<NB>(S, bd, st, lam, lane, w);
+        if (MET2_DOUBLE == 2) { dual<NB, TAB>(S, bd, st, lam, lane, w); asm volatile("" :: "v"(w[0])); }
+        dual<NB, TAB>(S, bd, st, lam, lane, w);
         MET2_CYC_END(3, c_du);
         MET2_CYC_ADD(13, 1);
         if (st.k >= S.kmax) {
@@ -763,7 +826,7 @@ __device__ __forceinline__ void nnls_iterate_plain(const WaveShared &S, const Ba
         MET2_CYC_ADD(14, 1);
         if (!accepted) break;
         MET2_CYC_BEGIN(c_in);
-        const bool inner_ok = nnls_inner<NB, NB, BS1>(S, st, iter, itmax, lane);
+        const bool inner_ok = nnls_inner<NB, NB, BS1, TAB>(S, st, iter, itmax, lane);
         MET2_CYC_END(2, c_in);
         MET2_CYC_ADD(15, 1);
         if (!inner_ok) { st.itmax_hit |= 1; break; }
@@ -854,7 +917,7 @@ __device__ __forceinline__ bool iterate_leg(const WaveShared &S, const Band<NB> 
 // Passive-set iterations until the KKT conditions hold.  mrows = rows of the (augmented) system.
 // warm: x is a feasible point whose support is the current passive set and R/y were just rebuilt for
 // (P, lam) -- start with the secondary loop instead of from the empty set.
-template <int NB, int ONE = 0, bool BIG = false>
+template <int NB, int ONE = 0, bool BIG = false, bool XTAB = false>
 __device__ __forceinline__ void nnls_iterate(const WaveShared &S, const Band<NB> &bd, NnlsState<NB> &st, double lam, int mrows, int lane,
                                              bool warm = false)
 {
@@ -867,7 +930,7 @@ __device__ __forceinline__ void nnls_iterate(const WaveShared &S, const Band<NB>
         } else
             (void)iterate_leg<NB, NB>(S, bd, st, lam, mrows, lane, warm, iter, outer);
     } else
-        nnls_iterate_plain<NB, (NB == 2 && ONE == 3), BIG>(S, bd, st, lam, mrows, lane, warm);
+        nnls_iterate_plain<NB, (NB == 2 && ONE == 3), BIG, XTAB>(S, bd, st, lam, mrows, lane, warm);
 }
 
 template <int NB>
@@ -1401,11 +1464,11 @@ __device__ __forceinline__ bool refactor(const WaveShared &S, const Band<NB> &bd
 }
 
 // cold-start solve; on return st.x is the solution
-template <int NB, int ONE = 0, bool BIG = false>
+template <int NB, int ONE = 0, bool BIG = false, bool XTAB = false>
 __device__ __forceinline__ void nnls_solve(const WaveShared &S, const Band<NB> &bd, NnlsState<NB> &st, double lam, bool aug, int lane)
 {
     nnls_reset<NB>(st);
-    nnls_iterate<NB, ONE, BIG>(S, bd, st, lam, aug ? S.m + S.n : S.m, lane);
+    nnls_iterate<NB, ONE, BIG, XTAB>(S, bd, st, lam, aug ? S.m + S.n : S.m, lane);
 }
 
 // Pivot order for a warm start: the passive bins by DESCENDING x.  The re-factorisation builds the factor in whatever order it is
@@ -1469,11 +1532,11 @@ __device__ __forceinline__ void reorder_by_x(const WaveShared &S, NnlsState<NB> 
 // rebuild the factor for the new lambda in the same pivot order, then iterate.  The minimiser of the
 // strictly convex problem does not depend on the starting point, so this returns the same x as the
 // cold start up to rounding; it only skips the passes that would rebuild the same passive set.
-template <int NB, int ONE = 0, bool BIG = false>
+template <int NB, int ONE = 0, bool BIG = false, bool XTAB = false>
 __device__ __forceinline__ void nnls_solve_warm(const WaveShared &S, const Band<NB> &bd, NnlsState<NB> &st, double lam, bool aug, int lane)
 {
     const int kold = st.k;
-    if (kold == 0) { nnls_solve<NB, ONE, BIG>(S, bd, st, lam, aug, lane); return; }
+    if (kold == 0) { nnls_solve<NB, ONE, BIG, XTAB>(S, bd, st, lam, aug, lane); return; }
     MET2_CYC_BEGIN(c_ref);
     if (NB >= MET2_REORDER && S.reorder && kold >= 4 && S.rcap >= kold + 4 + 32 * NB + 2) reorder_by_x<NB>(S, st, lane);
     if (!refactor<NB, ONE, BIG>(S, bd, st, lam, lane)) {
@@ -1495,7 +1558,7 @@ __device__ __forceinline__ void nnls_solve_warm(const WaveShared &S, const Band<
     }
     MET2_CYC_END(1, c_ref);
     MET2_CYC_ADD(12, 1);
-    nnls_iterate<NB, ONE, BIG>(S, bd, st, lam, aug ? S.m + S.n : S.m, lane, true);
+    nnls_iterate<NB, ONE, BIG, XTAB>(S, bd, st, lam, aug ? S.m + S.n : S.m, lane, true);
 }
 
 // D x  (lane e < m holds (D x)_e), using the passive set of st
