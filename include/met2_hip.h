@@ -317,6 +317,52 @@ int met2_bootstrap_spectrum_stats(int32_t device, int64_t nvox, int32_t n_rep, i
  * doubles between two series of a tile, dynamic LDS in bytes (at most 65 536).  Any output may be NULL. */
 int met2_bootstrap_spec_launch_info(int32_t n_rep, int32_t *tile_bins, int32_t *tile_stride, int64_t *lds_bytes);
 
+/* ---- Rician noise floor (an extension: the reference has no counterpart; additive, ABI stays 6) ----------
+ * The echoes are magnitudes, so their noise is Rician: with t = A^2 / (2 sigma^2) the mean of a magnitude with true amplitude A >= 0 and
+ * noise sigma > 0 is
+ *   m(A, sigma) = sigma sqrt(pi / 2) [(1 + t) i0e(t / 2) + t i1e(t / 2)],   i0e(x) = exp(-x) I0(x), i1e(x) = exp(-x) I1(x)
+ * (the exponentially scaled modified Bessel functions: the unscaled ones overflow at A / sigma ~ 53).  The bias b(A, sigma) = m(A, sigma) - A
+ * is >= 0, b(0, sigma) = sigma sqrt(pi / 2), b ~ sigma^2 / (2 A) for A >> sigma; b(A, 0) = 0 by definition and A < 0 is read as 0.  The
+ * inverse A = m^-1(M, sigma) is the root of m(A, sigma) = M for M > sigma sqrt(pi / 2) and 0 otherwise (m is increasing in A).  A fit treats
+ * the floor sigma sqrt(pi / 2) of the late echoes as signal -- a spurious long-T2 pool.  What is here:
+ *   met2_rician_bias     b[i] = b(A[i], sigma[i]), i < n.  The device function every other kernel calls (float64 Chebyshev series of i0e and
+ *                        i1e; from A / sigma = 1024 on the asymptotic series of b).  |b - exact| <= 1e-13 max(A, sigma) for A / sigma from 0 to 1e12
+ *   met2_rician_step     out[v][e] = data[v][e] - b(model[v][e], sigma[v]); not clipped: the fit's gate reads the echo sum and the first echo
+ *                        only, normalises by the first echo, and its NNLS does not need y >= 0.  A voxel that would fall out of that gate
+ *                        afterwards (out[v][0] <= 0 or sum_e out[v][e] <= 0) is left uncorrected, out = data for all its echoes, and flag[v] = 1;
+ *                        voxels with mask = 0 or sigma = 0 are copied, flag 0.  Several voxels per wave (one at n_te > 32); the sum is taken in a fixed order
+ *   met2_rician_invert   out[v][e] = m^-1(data[v][e], sigma[v]) (mask = 0 or sigma = 0: copied).
+ *                        |m(out, sigma) - max(data, sigma sqrt(pi / 2))| <= 1e-13 max(data, sigma): the condition is on the forward residual
+ *                        because the inverse is ill-conditioned at A -> 0, where dm / dA = 0
+ *   met2_noise_sigma     the estimate met2_fit_bootstrap makes when no sigma is given (bit for bit its sigma_out): a plain-NNLS pass at the
+ *                        voxel's flip angle, then sqrt(sum_e residual_e^2 / max(n_te - #{x > 0}, 1)); sig0 [nvox][n_te] or NULL: that pass's
+ *                        model signal.  Blocking (reports an FA index outside the dictionary); scratch stays with the plan
+ *   met2_fit_rician      sigma_v = sigma[v], or met2_noise_sigma's on the raw data when sigma is NULL (returned in sigma_out either way).
+ *                        y^0 = data; for k = 0 .. n_iter: fit y^k as met2_fit_strided does, giving the model signal s^k; if k < n_iter,
+ *                        y^(k+1) = step(data, s^k, sigma): the correction is always applied to the RAW data, never accumulated.  The outputs
+ *                        are the last fit's (sig is then the noise-free signal estimate); flag [nvox] is the last step's.  n_iter = 0 is
+ *                        met2_fit_strided bit for bit; 0 <= n_iter <= 16.  A voxel whose status lacks MET2_ST_FITTED after pass 0 is never
+ *                        corrected; the flip angle is fixed through the passes.  Passes 1 .. n_iter run in chunks of whole voxels (262 144;
+ *                        4 096 for L-curve at n_t2 > 64) through met2_fit_enqueue_strided on scratch kept with the plan until
+ *                        met2_plan_destroy.  Blocking (one wait after pass 0, which reports an FA index outside the dictionary, one at the end)
+ * All pointers are DEVICE pointers.  data: echo e of voxel v at data[v * voxel_stride + e * echo_stride] (strides in doubles, > 0), as for
+ * met2_fit_strided; model, out, sig0: [nvox][n_te] rows; sigma, sigma_out [nvox] (>= 0); mask [nvox] uint8 or NULL = all ones; flag [nvox]
+ * int32, may be NULL; out must not overlap data.  fsol, sig, reg, lam, maps, status as for met2_fit_strided (sig, lam, maps, status, sigma_out,
+ * flag may be NULL).  The three kernel entries take `device` and are asynchronous on `stream`.
+ * What this is not: sigma is not re-estimated after a correction, and the residual estimate is biased low where many echoes sit in the
+ * floor; met2_rician_invert treats its input as the Rician MEAN, which a denoised magnitude only approximates; nothing here makes the fit a
+ * maximum-likelihood Rician fit. */
+int met2_rician_bias(int32_t device, int64_t n, const double *A, const double *sigma, double *b, void *stream);
+int met2_rician_step(int32_t device, int64_t nvox, int32_t n_te, const double *data, int64_t voxel_stride, int64_t echo_stride,
+                     const double *model, const double *sigma, const uint8_t *mask, double *out, int32_t *flag, void *stream);
+int met2_rician_invert(int32_t device, int64_t nvox, int32_t n_te, const double *data, int64_t voxel_stride, int64_t echo_stride,
+                       const double *sigma, const uint8_t *mask, double *out, void *stream);
+int met2_noise_sigma(met2_plan *plan, int64_t nvox, const double *data, int64_t voxel_stride, int64_t echo_stride, const double *fa_index,
+                     const uint8_t *mask, double *sigma_out, double *sig0, void *stream);
+int met2_fit_rician(met2_plan *plan, int32_t method, int64_t nvox, const double *data, int64_t voxel_stride, int64_t echo_stride,
+                    const double *fa_index, const uint8_t *mask, const double *sigma, int32_t n_iter, double *fsol, double *sig, double *reg,
+                    double *lam, double *maps, int32_t *status, double *sigma_out, int32_t *flag, void *stream);
+
 /* ---- Monte-Carlo accuracy study (scripts_synthetic_data_evaluation/Paper_Comparison/evaluate_all_methods_two_lobes_SNR*.py) -------
  * met2_synth_two_lobe draws n two-lobe voxels by the reference's recipe (:156-190, :376-428).  Per voxel, from counter-based Philox4x32-10
  * (philox.hpp) with key (lo32(seed), hi32(seed)) and counter (c0, stream, lo32(id), hi32(id)), id = voxel_offset + v:

@@ -21,6 +21,8 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   seg.py                    seg_consts / seg_init / seg_icm / seg_posterior / seg_finish: the stages of the tissue segmentation one by one (tests and diagnostics)
   pve.py                    pve_moments / pve_consts / pve_energy / pve_icm / pve_finish: the stages of the partial-volume maps one by one (tests and diagnostics)
   stats.py                  label_index / label_moments / label_quantiles / label_stats: per-label n, mean, std and np.quantile-exact quantiles of any series (csrc/met2_stats.hip)
+  rician.py                 bias / step / invert: the kernels of the Rician noise-floor correction one by one (csrc/met2_rician.hip; Met2Plan.fit_rician and
+                            noise_sigma, rician='iterative' | 'direct' of the drivers)
   mppca.py                  mppca_stages: the MP-PCA denoiser with what each of its steps leaves (tests and diagnostics)
   nifti.py                  NIfTI-1 reader / writer for the driver's on-disk contract
   dist.py                   one-process-per-GPU voxel sharding + the single gather of output maps

@@ -7,6 +7,7 @@
 // replicate fits go through met2_fit_enqueue_strided on per-plan scratch, chunk after chunk on the caller's stream, and the statistics of every
 // chunk's voxels are taken behind its fit.  met2_fit_bootstrap_fa re-estimates the flip angle of every replicate row before its fit (the
 // plan's brute-force walk, or the coarse walk and the spline selection) and can return the statistics of the replicates' spectra per T2 bin.
+// met2_noise_sigma is that noise estimate on its own (noise_sigma_enqueue: the one copy the bootstrap and met2_fit_rician, met2_rician.hip, take it from).
 // Four kernels of this file:
 //   bootstrap_sigma_kernel        sigma_v from the plain-NNLS pass (one thread per voxel)
 //   bootstrap_gen_kernel          the replicate rows of a chunk (one thread per echo; counter-based Philox4x32-10, HBM-write-bound)
@@ -286,6 +287,8 @@ struct BootWork {
     char *rows = nullptr;           // data | fsol | maps | reg | fa | status | mask
     int64_t cap_aux = 0;            // bytes
     char *aux = nullptr;            // spline mode: the coarse walk's residuals [rows][n_lr]
+    int64_t cap_ric = 0;            // bytes
+    char *ric = nullptr;            // met2_fit_rician's scratch (met2_rician.hip lays it out)
 };
 std::mutex g_boot_mutex;
 std::map<met2_plan *, BootWork> g_boot;
@@ -297,6 +300,7 @@ void free_boot(BootWork &w)
     if (w.vox) (void)hipFree(w.vox);
     if (w.rows) (void)hipFree(w.rows);
     if (w.aux) (void)hipFree(w.aux);
+    if (w.ric) (void)hipFree(w.ric);
     w = BootWork();
 }
 
@@ -341,7 +345,62 @@ __attribute__((visibility("hidden"))) void bootstrap_release(met2_plan *plan)
     }
     free_boot(w);
 }
+
+// met2_fit_rician's scratch: `bytes` kept with the plan like the bootstrap's own
+__attribute__((visibility("hidden"))) int rician_scratch(met2_plan *plan, int device, size_t bytes, char **out)
+{
+    BootWork *w;
+    {
+        std::lock_guard<std::mutex> lock(g_boot_mutex);
+        w = &g_boot[plan];
+    }
+    w->device = device;
+    const int rc = grow(w->ric, w->cap_ric, (int64_t)bytes, 1);
+    *out = w->ric;
+    return rc;
+}
+
+// The noise estimate of bayesian_interpolation.py:88-93 on the raw echoes, enqueued on `stream`: a plain-NNLS pass at the voxel's flip angle into
+// fsol0 [nvox][nt2], sig0 [nvox][nte] and reg0 [nvox] (scratch of the caller's), then bootstrap_sigma_kernel.  The one copy that met2_fit_bootstrap,
+// met2_noise_sigma and met2_fit_rician take sigma_v from.
+__attribute__((visibility("hidden"))) int noise_sigma_enqueue(met2_plan *plan, int nte, int nt2, int64_t nvox, const double *data, int64_t vs, int64_t es,
+                                                              const double *fa_index, const uint8_t *mask, double *fsol0, double *sig0, double *reg0,
+                                                              double *sigma_out, void *stream)
+{
+    int rc = met2_fit_enqueue_strided(plan, MET2_NNLS, nvox, data, vs, es, fa_index, mask, fsol0, sig0, reg0, nullptr, nullptr, nullptr, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(bootstrap_sigma_kernel, dim3(gen_grid(nvox)), dim3(256), 0, (hipStream_t)stream, nvox, nte, nt2, data, vs, es, fsol0, sig0, sigma_out);
+    HIPCHK(hipGetLastError());
+    return MET2_OK;
+}
 }  // namespace met2
+
+extern "C" int met2_noise_sigma(met2_plan *plan, int64_t nvox, const double *data, int64_t voxel_stride, int64_t echo_stride, const double *fa_index,
+                                const uint8_t *mask, double *sigma_out, double *sig0, void *stream)
+{
+    if (nvox < 0 || nvox > 0x7fffffff) return fail(MET2_E_INVALID, "nvox out of range");
+    if (voxel_stride <= 0 || echo_stride <= 0) return fail(MET2_E_INVALID, "strides must be positive");
+    if (!plan) return fail(MET2_E_INVALID, "NULL plan");
+    if (nvox == 0) return MET2_OK;
+    if (!data || !sigma_out) return fail(MET2_E_INVALID, "NULL argument");
+    int nte, nt2, dev;
+    int rc = plan_shape(plan, nte, nt2, dev);
+    if (rc) return rc;
+    USE_DEVICE(dev);
+    BootWork *w;
+    {
+        std::lock_guard<std::mutex> lock(g_boot_mutex);
+        w = &g_boot[plan];
+    }
+    w->device = dev;
+    rc = grow(w->vox, w->cap_vox, nvox, align256(sizeof(double) * (2 * nte + nt2 + 2) + sizeof(int32_t)));      // boot_impl's bytes per voxel
+    if (rc) return rc;
+    double *v_sig0 = (double *)w->vox, *v_fsol0 = v_sig0 + nvox * nte, *v_reg0 = v_fsol0 + nvox * nt2;
+    rc = met2::noise_sigma_enqueue(plan, nte, nt2, nvox, data, voxel_stride, echo_stride, fa_index, mask, v_fsol0, sig0 ? sig0 : v_sig0, v_reg0, sigma_out,
+                                   stream);
+    if (rc) return rc;
+    return met2_plan_finish(plan, stream);       // reports an FA index outside the dictionary
+}
 
 extern "C" int met2_bootstrap_replicates(met2_plan *plan, int64_t nvox, const double *center, const double *sigma, const int64_t *voxel_id,
                                          int32_t n_rep, int64_t seed, double *out, void *stream)
@@ -438,12 +497,9 @@ int boot_impl(met2_plan *plan, int32_t method, int32_t fa_mode, int nquant, int6
     if (sigma) {
         if (sigma_out && sigma_out != sigma) HIPCHK(hipMemcpyAsync(sigma_out, sigma, sizeof(double) * (size_t)nvox, hipMemcpyDeviceToDevice, s));
     } else {
-        rc = met2_fit_enqueue_strided(plan, MET2_NNLS, nvox, data, voxel_stride, echo_stride, fa_index, mask, v_fsol0, v_sig0, v_reg0, nullptr, nullptr,
-                                      nullptr, stream);
-        if (rc) return rc;
         double *so = sigma_out ? sigma_out : v_sigma;
-        hipLaunchKernelGGL(bootstrap_sigma_kernel, dim3(gen_grid(nvox)), dim3(256), 0, s, nvox, nte, nt2, data, voxel_stride, echo_stride, v_fsol0, v_sig0, so);
-        HIPCHK(hipGetLastError());
+        rc = met2::noise_sigma_enqueue(plan, nte, nt2, nvox, data, voxel_stride, echo_stride, fa_index, mask, v_fsol0, v_sig0, v_reg0, so, stream);
+        if (rc) return rc;
         sg = so;
     }
     // one wait: an FA index outside the dictionary is reported before any replicate is fitted

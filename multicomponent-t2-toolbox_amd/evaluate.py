@@ -196,13 +196,19 @@ class EvalResult:
 
 
 def evaluate_methods(n_voxels=10000, snr=(50.0, 150.0), seed=0, nte=32, te=10.0, npc=60, TR=3000.0, methods=PAPER_METHODS, lambda_grid=None,
-                     chunk=65536, per_voxel=False, device=0, x2_factor=1.02, gmare_fie="nnls"):
+                     chunk=65536, per_voxel=False, device=0, x2_factor=1.02, gmare_fie="nnls", rician=None, rician_iters=3):
     """The reference's study (evaluate_all_methods_two_lobes_SNR*.py) for one SNR band: snr=(lo, hi), or None for the noise-free band.
     Per chunk of voxels on one plan (nte x npc x 91 flip angles): generate; brute-force flip angle over the 91-angle dictionary on the
     noisy, unnormalised signal (:398); fit every method (lambda from the fit's `lam`, :469); per-voxel metrics.  Then one reduction per
     method over all voxels.  gmare_fie='nnls' is the reference's GMARE: its fIE term reads the NNLS fit for every method (:107); 'own'
-    reads each method's.  Results do not depend on `chunk`."""
+    reads each method's.  Results do not depend on `chunk`.  rician='iterative' (an extension): every method's fit goes through
+    Met2Plan.fit_rician with rician_iters passes, the noise level estimated per voxel (Met2Plan.noise_sigma), not taken from the truth; the
+    tables keep their layout."""
     methods = tuple(methods)
+    if rician not in (None, "iterative"):
+        raise ValueError("rician must be None or 'iterative'")
+    if not 0 <= int(rician_iters) <= 16:
+        raise ValueError("rician_iters must lie in [0, 16]")
     for m in methods:
         if m not in METHOD_SPEC:
             raise ValueError("unknown method %r (have %s)" % (m, PAPER_METHODS))
@@ -239,8 +245,12 @@ def evaluate_methods(n_voxels=10000, snr=(50.0, 150.0), seed=0, nte=32, te=10.0,
                 step = _LCURVE_SLICE if method == "L_curve" and npc > 64 else e - s
                 for a in range(0, e - s, step):
                     b = min(e - s, a + step)
-                    out = plan.fit(method, g["data"][a:b], fa_index=fa[a:b], want_sig=False, want_maps=False, want_status=False,
-                                   want_lambda=method != "NNLS")
+                    if rician:
+                        out = plan.fit_rician(method, g["data"][a:b], n_iter=int(rician_iters), fa_index=fa[a:b], want_sig=False, want_maps=False,
+                                              want_status=False, want_lambda=method != "NNLS")
+                    else:
+                        out = plan.fit(method, g["data"][a:b], fa_index=fa[a:b], want_sig=False, want_maps=False, want_status=False,
+                                       want_lambda=method != "NNLS")
                     pv[m][:, s + a:s + b] = voxel_metrics(plan, out["fsol"], g["dist2"][a:b])
                     if method != "NNLS":
                         lam[m][s + a:s + b] = out["lam"]
@@ -252,7 +262,7 @@ def evaluate_methods(n_voxels=10000, snr=(50.0, 150.0), seed=0, nte=32, te=10.0,
             pvd = {m: dict({f: pv[m][i].cpu().numpy() for i, f in enumerate(FIELDS)}, lam=lam[m].cpu().numpy()) for m in fitted}
             pvd["truth"] = {f: truth[i].cpu().numpy() for i, f in enumerate(TRUTH)}
             pvd["fa_index"] = fa_all.cpu().numpy()
-        params = dict(n_voxels=n_voxels, snr=snr, seed=seed, nte=nte, te=te, npc=npc, TR=TR, chunk=chunk, gmare_fie=gmare_fie)
+        params = dict(n_voxels=n_voxels, snr=snr, seed=seed, nte=nte, te=te, npc=npc, TR=TR, chunk=chunk, gmare_fie=gmare_fie, rician=rician, rician_iters=int(rician_iters))
         return EvalResult(methods, agg[:, :13], agg[:, 13:], pvd, params)
     finally:
         plan.close()

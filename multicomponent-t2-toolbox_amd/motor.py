@@ -539,7 +539,7 @@ def _estimate_fa(plan, dd_fa, mm, FA_method, fa_index, T2s, T1s, tau, TR, alpha_
 def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2", FA_method="brute-force", myelin_T2=40.0,
                       fa_index=None, device=0, plan=None, denoise="None", prepared=False, FA_smooth="no", distributed=False,
                       return_prepared=False, devices=None, bootstrap=None, degibbs="no", bias_correct="no", voxel_size=None,
-                      brain_mask="no", segment="no", tissue_stats="no", pve_threshold=0.9):
+                      brain_mask="no", segment="no", tissue_stats="no", pve_threshold=0.9, rician="no", rician_sigma=None, rician_iters=3):
     """Steps 1-4 of motor_recon_met2 (motor:293-373, 427-472) on arrays: data [nx,ny,nz,nt] (or
     [nvox, nt]), mask [nx,ny,nz].  Mirrors the driver's preparation: data *= mask (motor:180-182),
     negative values clipped to 0 (motor:279), optional NESMA / TV filter (motor:293-333, needs a 3-D volume) or denoise='MPPCA'
@@ -595,8 +595,19 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     fa and want_spectrum): fa='fixed' (default) | 'brute-force' | 'spline' -- other than 'fixed' it must be the run's FA_method, every
     replicate then gets its own flip angle and 'FA_bootstrap' [vol..., 5] (degrees) is added; it does not go with FA_smooth='yes' (see
     _bootstrap_check).  spectrum=True adds 'fsol_bootstrap' [vol..., n_t2, 5], the per-bin band of the T2 spectrum.
+    rician='iterative' | 'direct' (an extension: the Rician noise floor of the echo magnitudes, which the fit otherwise reads as a long-T2 pool;
+    one device, through a plan).  'iterative': after the FA step the fit is Met2Plan.fit_rician with rician_iters passes (default 3) at the
+    noise level rician_sigma (a number or a volume) or, without one, at the residual estimate of Met2Plan.noise_sigma; adds 'sigma', 'SNR'
+    (first echo of the model signal over sigma, 0 where sigma = 0) and 'rician_flag'; 'Est_Signal' is then the noise-free signal estimate.
+    'direct': the prepared volume goes through rician.invert before the FA step and the fit, which run once -- the one-shot correction of
+    denoised magnitudes; it needs a sigma map, rician_sigma or the one denoise='MPPCA' leaves, and adds 'sigma' and 'data_rician' (the
+    corrected volume).  It treats a denoised magnitude as the Rician mean, which it only approximates.  sigma is never re-estimated after a
+    correction, and the residual estimate is biased low where many echoes sit in the floor; neither mode makes the fit a maximum-likelihood
+    Rician fit.  ValueError before any device work for another value, for 'direct' without a sigma source, and with devices=[...],
+    distributed=True or bootstrap=...  rician='no' (default) changes no output and no launch.
     Returns a dict with the driver's ten outputs."""
     boot = _bootstrap_args(bootstrap)
+    ric = _rician_check(rician, rician_sigma, rician_iters, denoise, prepared, devices, distributed, bootstrap)
     if boot is not None and distributed:
         raise ValueError("bootstrap runs on one device and does not go with distributed=True")
     _bootstrap_check(boot, FA_method, FA_smooth)
@@ -615,13 +626,13 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
         made = brain_mask_filter(np.ascontiguousarray(data), voxel_size, device=first_dev)
         res = recon_met2_arrays(data, made, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, fa_index, device, plan, denoise, False,
                                 FA_smooth, False, return_prepared, devices, bootstrap, "no", bias_correct, voxel_size, "no", segment, tissue_stats,
-                                pve_threshold)
+                                pve_threshold, rician=rician, rician_sigma=rician_sigma, rician_iters=rician_iters)
         res["mask"] = made
         return res
     bias = _bias_check(bias_correct, vol_shape, voxel_size, distributed)
     nt = data.shape[-1]
     mask = np.asarray(mask).reshape(vol_shape)
-    if devices is None and plan is None and not distributed and data.ndim >= 2:
+    if devices is None and plan is None and not distributed and data.ndim >= 2 and not ric:
         devices = [device]                                       # the default: one device, through the C ABI's host entry (met2_fit_host: the block
                                                                  # pipeline inside the library; the torch pipeline of rounds 3-4 is retired to tests/tools)
     if devices is not None:
@@ -665,12 +676,17 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     # a caller's own plan, a distributed run, or a bare voxel list: the volume on the device in one piece
     extra = {}
     dd, mk = _prepare_volume(data, mask, dev, prepared, denoise, extra)
+    mm = (mk > 0)
+    sigma_vol = _rician_sigma(ric, rician_sigma, extra, vol_shape, dev)
+    dd_prepared = dd
+    if ric == "direct":
+        from . import rician as _rician
+        dd = _rician.invert(dd, sigma_vol, mm)
     dd_fa = dd
     if FA_smooth == "yes" and fa_index is None:
         if len(vol_shape) != 3:
             raise ValueError("FA_smooth='yes' needs data [nx,ny,nz,nt]")
         dd_fa = gaussian_smooth(dd, 2.0)
-    mm = (mk > 0)
     TE_array = np.asarray(TE_array, dtype=np.float64)
     tau = float(TE_array[1] - TE_array[0])
     Npc = 96 if reg_method == "T2SPARC" else 60
@@ -686,10 +702,21 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
         if distributed:
             return _recon_sharded(plan, dd, dd_fa, mm, reg_method, FA_method, fa_index, T2s, T1s, tau, TR, alpha_values, device, vol_shape)
         fa_vol = _estimate_fa(plan, dd_fa, mm, FA_method, fa_index, T2s, T1s, tau, TR, alpha_values, device)
-        out = plan.fit(reg_method, dd, fa_index=fa_vol, mask=mm)
+        if ric == "iterative":
+            out = plan.fit_rician(reg_method, dd, n_iter=int(rician_iters), sigma=sigma_vol, fa_index=fa_vol, mask=mm)
+        else:
+            out = plan.fit(reg_method, dd, fa_index=fa_vol, mask=mm)
         tot_fa = dd_fa.sum(dim=-1)
         res = {"fsol_4D": out["fsol"].cpu().numpy(), "Est_Signal": out["sig"].cpu().numpy(), "reg_param": out["reg"].cpu().numpy(),
                "FA_index": fa_vol.cpu().numpy()}
+        if ric == "iterative":
+            sg = out["sigma"]
+            res["sigma"] = sg.cpu().numpy()
+            res["SNR"] = torch.where(sg > 0, out["sig"][..., 0] / torch.where(sg > 0, sg, torch.ones_like(sg)), torch.zeros_like(sg)).cpu().numpy()
+            res["rician_flag"] = out["rician_flag"].cpu().numpy()
+        elif ric == "direct":
+            res["sigma"] = sigma_vol.cpu().numpy()
+            res["data_rician"] = dd.cpu().numpy()
         fitted_fa = (mm & (tot_fa > 0)).cpu().numpy()      # gate of the FA step (fa_estimation.py:45)
         res["FA"] = np.where(fitted_fa, alpha_values[res["FA_index"].astype(int)], 0.0)
         maps = out["maps"].cpu().numpy()
@@ -697,7 +724,7 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
             res[name] = maps[i]
         res["T2s"] = T2s
         if return_prepared:
-            res["data_prepared"] = dd.cpu().numpy()
+            res["data_prepared"] = dd_prepared.cpu().numpy()
             for name, t in extra.items():
                 res[name] = t.cpu().numpy()
         if boot is not None:
@@ -712,6 +739,39 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     finally:
         if own:
             plan.close()
+
+
+def _rician_check(rician, rician_sigma, rician_iters, denoise, prepared, devices, distributed, bootstrap):
+    """rician of recon_met2_arrays -> None, 'iterative' or 'direct'; what it cannot be combined with is raised before any device work."""
+    if rician not in ("no", "iterative", "direct"):
+        raise ValueError("rician must be 'no', 'iterative' or 'direct'")
+    if rician == "no":
+        return None
+    if devices is not None:
+        raise ValueError("rician='%s' runs through one plan and does not go with devices=[...]" % rician)
+    if distributed:
+        raise ValueError("rician='%s' does not go with distributed=True" % rician)
+    if bootstrap is not None:
+        raise ValueError("rician='%s' does not go with bootstrap=...: the replicates would be drawn around a corrected fit" % rician)
+    if not 0 <= int(rician_iters) <= 16:
+        raise ValueError("rician_iters must lie in [0, 16]")
+    if rician_sigma is not None and np.any(np.asarray(rician_sigma, dtype=np.float64) < 0):
+        raise ValueError("rician_sigma must be >= 0")
+    if rician == "direct" and rician_sigma is None and (denoise != "MPPCA" or prepared):
+        raise ValueError("rician='direct' needs a sigma map: rician_sigma, or denoise='MPPCA' (not prepared=True), whose map it takes")
+    return rician
+
+
+def _rician_sigma(ric, rician_sigma, extra, vol_shape, dev):
+    """The noise level of the run as a device volume shaped like the voxels: rician_sigma (a number or a volume), MP-PCA's map for 'direct'
+    without one, None for 'iterative' without one (the fit then estimates it)."""
+    if not ric:
+        return None
+    if rician_sigma is None:
+        return extra["MPPCA_sigma"].reshape(vol_shape) if ric == "direct" else None
+    sg = np.asarray(rician_sigma, dtype=np.float64)
+    sg = np.full(vol_shape, float(sg)) if sg.ndim == 0 else sg.reshape(vol_shape)
+    return torch.as_tensor(sg, dtype=torch.float64, device=dev)
 
 
 def _bootstrap_args(bootstrap):
@@ -917,7 +977,7 @@ def _recon_sharded(plan, dd, dd_fa, mm, reg_method, FA_method, fa_index, T2s, T1
 
 def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR, reg_method, reg_matrix, denoise, FA_method,
                      FA_smooth, myelin_T2, num_cores=-1, device=0, devices=None, bootstrap=None, degibbs="no", bias_correct="no",
-                     brain_mask="no", segment="no", tissue_stats="no", pve_threshold=0.9):
+                     brain_mask="no", segment="no", tissue_stats="no", pve_threshold=0.9, rician="no", rician_sigma=None, rician_iters=3):
     """Drop-in for motor_recon_met2 (motor:165-506) with the reference's on-disk contract: NIfTI in
     (data [nx,ny,nz,nt], mask [nx,ny,nz]), ten NIfTI volumes out (MWF, IEWF, FWF, T2_M, T2_IE, TWC, FA, fsol_4D,
     Est_Signal, reg_param .nii.gz at path_to_save_data, motor:475-503).  `num_cores` is accepted and ignored (one
@@ -941,7 +1001,9 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     Not reproduced: the mean-spectrum PNG of motor:404-424.
     bootstrap=dict(n_rep=..., seed=...) (an extension, see recon_met2_arrays) also writes <Q>_bootstrap.nii.gz [nx,ny,nz,5] for Q in
     BOOT_QUANTITIES (BOOT_STATS along the last axis) and sigma.nii.gz; with fa='brute-force' / 'spline' also FA_bootstrap.nii.gz [nx,ny,nz,5]
-    (degrees), with spectrum=True also fsol_bootstrap_{mean,std,q025,q500,q975}.nii.gz [nx,ny,nz,n_t2] each."""
+    (degrees), with spectrum=True also fsol_bootstrap_{mean,std,q025,q500,q975}.nii.gz [nx,ny,nz,n_t2] each.
+    rician='iterative' | 'direct' with rician_sigma and rician_iters (an extension, see recon_met2_arrays; not with devices=[...] or bootstrap):
+    also writes sigma.nii.gz; 'iterative' SNR.nii.gz and rician_flag.nii.gz, 'direct' Data_rician.nii.gz (the corrected volume)."""
     from . import nifti
     img = nifti.load(path_to_data)
     data = img.get_fdata().astype(np.float64, copy=False)           # Fortran-ordered, like nibabel's: read in place by the solver
@@ -951,6 +1013,10 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
         raise ValueError("brain_mask='yes' makes the mask itself and does not go with path_to_mask")
     _segment_check(segment, bias_correct, False)
     _tissue_stats_check(tissue_stats, segment, False, pve_threshold)
+    if _rician_check(rician, rician_sigma, rician_iters, denoise, False, devices, False, bootstrap):
+        rician_kw = {"rician": rician, "rician_sigma": rician_sigma, "rician_iters": rician_iters}
+    else:
+        rician_kw = {}
     mask = None if brain_mask == "yes" else nifti.load(path_to_mask).get_fdata().astype(np.int64)
     if data.ndim != 4 or (mask is not None and mask.shape != data.shape[:3]):
         raise ValueError("data must be 4-D and mask must match its first three dimensions")
@@ -976,9 +1042,16 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
         nifti.save(nifti.NiftiImage(mask, img.affine), path_to_save_data + "mask.nii.gz")
     res = recon_met2_arrays(data, mask, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, device=device, denoise=denoise,
                             FA_smooth=FA_smooth, return_prepared=(denoise in ("TV", "MPPCA")), devices=devices, bootstrap=bootstrap,
-                            **bias_kw)
+                            **bias_kw, **rician_kw)
     if brain_mask == "yes":
         res["mask"] = mask
+    if rician_kw:
+        nifti.save(nifti.NiftiImage(res["sigma"], img.affine), path_to_save_data + "sigma.nii.gz")
+        if rician == "iterative":
+            nifti.save(nifti.NiftiImage(res["SNR"], img.affine), path_to_save_data + "SNR.nii.gz")
+            nifti.save(nifti.NiftiImage(res["rician_flag"], img.affine), path_to_save_data + "rician_flag.nii.gz")
+        else:
+            nifti.save(nifti.NiftiImage(res.pop("data_rician"), img.affine), path_to_save_data + "Data_rician.nii.gz")
     if bias_kw:
         nifti.save(nifti.NiftiImage(res["TWC_bias"], img.affine), path_to_save_data + "TWC_bias.nii.gz")
     if "TWC_seg" in res:

@@ -346,6 +346,71 @@ class Met2Plan:
             res["fa_stats_deg"] = self.fa_stats_degrees(res["fa_stats"])
         return res
 
+    def _sigma_arg(self, sigma, nvox, order):
+        """sigma of fit_rician: None, one number for every voxel, or one entry per voxel (flat in the data's voxel order or shaped like the volume)"""
+        if sigma is None:
+            return None
+        if not torch.is_tensor(sigma) and np.ndim(sigma) == 0:
+            sigma = torch.full((nvox,), float(sigma), dtype=torch.float64, device=self.device)
+        sg = sigma if torch.is_tensor(sigma) else torch.as_tensor(np.asarray(sigma, dtype=np.float64))
+        if sg.numel() != nvox:
+            raise ValueError("sigma has %d entries for %d voxels" % (sg.numel(), nvox))
+        if bool((sg < 0).any()) or bool(torch.isnan(sg).any()):
+            raise ValueError("sigma must be >= 0")
+        return self._per_voxel(sg, nvox, torch.float64, "sigma", order)
+
+    def noise_sigma(self, data, fa_index=None, mask=None, want_sig0=False):
+        """The per-voxel noise estimate fit_bootstrap and fit_rician make when no sigma is given (met2_noise_sigma; bayesian_interpolation.py:88-93):
+        a plain-NNLS pass at the voxel's flip angle, then sqrt(sum of squared residuals / max(n_te - #{x > 0}, 1)).  data, fa_index, mask as for
+        fit().  Returns sigma [vol...], or (sigma, sig0 [vol..., n_te]) with want_sig0 (that pass's model signal)."""
+        self._check_data(data)
+        data, nvox, vs, es, vol, order = voxel_layout(data, self.n_te)
+        fa_index = self._per_voxel(fa_index, nvox, torch.float64, "fa_index", order)
+        mask = self._per_voxel(mask, nvox, torch.uint8, "mask", order)
+        sigma = torch.empty((nvox,), dtype=torch.float64, device=self.device)
+        sig0 = torch.empty((nvox, self.n_te), dtype=torch.float64, device=self.device) if want_sig0 else None
+        with torch.cuda.device(self.device):
+            check(lib().met2_noise_sigma(self._h, nvox, _ptr(data), vs, es, _ptr(fa_index), _ptr(mask), _ptr(sigma), _ptr(sig0), self._stream()))
+        if len(vol) > 1:
+            sigma = unflatten(sigma, vol, order)
+            sig0 = None if sig0 is None else unflatten(sig0, vol, order)
+        return (sigma, sig0) if want_sig0 else sigma
+
+    def fit_rician(self, method, data, n_iter=3, sigma=None, fa_index=None, mask=None, want_sig=True, want_maps=True, want_status=True,
+                   want_lambda=False):
+        """fit() with the Rician noise floor of the echo magnitudes taken out (met2_fit_rician; an extension with no counterpart in the
+        reference): the raw echoes minus the Rician bias b(s_hat, sigma) at the previous fit's model signal s_hat are refitted, n_iter times
+        over (0 <= n_iter <= 16; 0 is fit() bit for bit).  sigma: one number, one entry per voxel, or None = noise_sigma() on the raw data; it
+        is not re-estimated between the passes.  data, fa_index, mask as for fit().  Returns fit()'s dict -- of the last pass: sig is the
+        noise-free signal estimate -- plus sigma [vol...] and rician_flag [vol...] (int32: 1 where the last correction would have pushed the
+        voxel out of the fit's gate and it was fitted on its raw echoes).  This is a bias correction around a least-squares fit, not a
+        maximum-likelihood Rician fit."""
+        if method not in METHODS:
+            raise ValueError("unknown reg_method %r" % (method,))
+        n_iter = int(n_iter)
+        if not 0 <= n_iter <= 16:
+            raise ValueError("n_iter must lie in [0, 16], got %d" % n_iter)
+        self._check_data(data)
+        data, nvox, vs, es, vol, order = voxel_layout(data, self.n_te)
+        dev = self.device
+        sigma = self._sigma_arg(sigma, nvox, order)
+        fa_index = self._per_voxel(fa_index, nvox, torch.float64, "fa_index", order)
+        mask = self._per_voxel(mask, nvox, torch.uint8, "mask", order)
+        e = lambda shape, dt=torch.float64: torch.empty(shape, dtype=dt, device=dev)
+        fsol, reg = e((nvox, self.n_t2)), e((nvox,))
+        sig = e((nvox, self.n_te)) if want_sig else None
+        lam = e((nvox,)) if want_lambda else None
+        maps = e((6, nvox)) if want_maps else None
+        status = e((nvox,), torch.int32) if want_status else None
+        sigma_out, flag = e((nvox,)), e((nvox,), torch.int32)
+        with torch.cuda.device(dev):
+            check(lib().met2_fit_rician(self._h, METHODS[method], nvox, _ptr(data), vs, es, _ptr(fa_index), _ptr(mask), _ptr(sigma), n_iter, _ptr(fsol),
+                                        _ptr(sig), _ptr(reg), _ptr(lam), _ptr(maps), _ptr(status), _ptr(sigma_out), _ptr(flag), self._stream()))
+        res = {"fsol": fsol, "sig": sig, "reg": reg, "lam": lam, "maps": maps, "status": status, "sigma": sigma_out, "rician_flag": flag}
+        if len(vol) > 1:
+            res = {k: (None if t is None else unflatten(t, vol, order, lead=1 if k == "maps" else 0)) for k, t in res.items()}
+        return res
+
     def bootstrap_replicates(self, center, sigma, n_rep, seed=0, voxel_id=None):
         """The replicates fit_bootstrap fits (met2_bootstrap_replicates): center [nvox, n_te] and sigma [nvox] float64 CUDA tensors,
         voxel_id [nvox] int64 (default 0..nvox-1) -> [nvox, n_rep, n_te].  No gating: every voxel gets replicates."""

@@ -2,7 +2,8 @@
 writes it: table_errors.{txt,csv} and table_regularization.{txt,csv}.
 
     python scripts/evaluate_methods.py --snr 50 150 --n 10000 --out DIR
-    python scripts/evaluate_methods.py --snr inf --n 10000 --nte 48 --npc 120 --out DIR"""
+    python scripts/evaluate_methods.py --snr inf --n 10000 --nte 48 --npc 120 --out DIR
+    python scripts/evaluate_methods.py --snr 50 150 --n 10000 --rician iterative --out DIR    (every fit with the Rician noise floor taken out)"""
 import argparse
 import importlib
 import os
@@ -25,6 +26,8 @@ def main(argv=None):
     ap.add_argument("--methods", nargs="+", default=None, help="row labels (default: the ten of the paper), e.g. '1. NNLS' '4. X2-L2'")
     ap.add_argument("--chunk", type=int, default=65536)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--rician", choices=["iterative"], default=None, help="fit through Met2Plan.fit_rician (sigma estimated per voxel)")
+    ap.add_argument("--rician-iters", type=int, default=3)
     ap.add_argument("--out", required=True, help="directory for the four table files")
     a = ap.parse_args(argv)
     if len(a.snr) == 1 and a.snr[0].lower() == "inf":
@@ -36,7 +39,7 @@ def main(argv=None):
     importlib.import_module(PKG + "._build").build()
     t = time.perf_counter()
     res = ev.evaluate_methods(n_voxels=a.n, snr=snr, seed=a.seed, nte=a.nte, npc=a.npc, methods=tuple(a.methods or ev.PAPER_METHODS),
-                              chunk=a.chunk, device=a.device)
+                              chunk=a.chunk, device=a.device, rician=a.rician, rician_iters=a.rician_iters)
     wall = time.perf_counter() - t
     res.write_tables(a.out)
     print(res.error_table())
