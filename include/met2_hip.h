@@ -115,6 +115,23 @@ int met2_plan_get_shape(met2_plan *plan, int32_t *n_te, int32_t *n_t2, int32_t *
 int met2_plan_build_dictionary_epg(met2_plan *plan, const double *T2s, const double *T1s, double tau,
                                    const double *alpha_deg, double TR, void *stream);
 
+/* The same dictionary for slice-selective pulses (2-D multi-slice multi-echo spin echo; an extension with no counterpart in the
+ * reference): the excitation and refocusing angles vary across the slice and the decay is the integral of the echo trains over the slice
+ * profile (Lebel & Wilman, Magn Reson Med 64:1005-1014, 2010).  The profile is three host arrays of length n_z, 1 <= n_z <= 64: r_exc[z] and
+ * r_ref[z], the excitation and refocusing angles at position z relative to the nominal ones (1.0 at the centre of ideal pulses), and the
+ * quadrature weights w[z], used as given (not normalised).  For a = alpha_deg[fa] and bin j, with H_z[e] echo e of the train of the plain
+ * entry at alpha = (a * r_ref[z]) * pi/180 and alpha_exc = ((a / 2.0) * r_exc[z]) * pi/180 (operations in this order):
+ *     acc = 0;  for z = 0 .. n_z-1 ascending:  acc = acc + (w[z] * H_z[e])       (product and sum rounded separately, no fma)
+ *     D[fa][e][j] = acc * (1 - exp(-TR / T1s[j]))
+ * The summation order is part of the definition: the result does not depend on the device or the launch.  With n_z = 1 and
+ * r_exc = r_ref = w = {1.0} it is the plain entry's dictionary bit for bit, with one exception: an echo that is -0 in the plain
+ * dictionary (a negative value that underflowed) comes back as +0, since 0 + (-0) = +0.  The TR factor stays the reference's: a steady state that
+ * depends on the local excitation angle is out of scope, as are complex (phase) profiles.  Everything after the dictionary is the plain
+ * entry's (Gram matrices, low-rank basis, seeds, T2 grid).  MET2_E_INVALID before any launch, the plan's dictionary untouched, for a NULL
+ * pointer, n_z outside 1..64, a profile value that is not finite or negative, and weights that are all zero. */
+int met2_plan_build_dictionary_epg_profile(met2_plan *plan, const double *T2s, const double *T1s, double tau, const double *alpha_deg, double TR,
+                                           int32_t n_z, const double *r_exc, const double *r_ref, const double *w, void *stream);
+
 /* Dictionary handed in by the caller, reference layout Dic_3D[n_te][n_t2][n_fa] (host).
  * Replaces the `Dic_3D` argument of fitting_slice_T2 (motor:113). */
 int met2_plan_set_dictionary(met2_plan *plan, const double *dic3d_host);

@@ -4,7 +4,8 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   csrc/                     HIP kernels + the C ABI of include/met2_hip.h
   plan.py                   Met2Plan (ctypes face of the C ABI; torch for device memory only)
   intravoxel_algorithms.py  nnls, nnls_tik, nnls_x2, nnls_lcurve_wrapper, nnls_gcv, BayesReg_nnls
-  epg.py                    create_Dic_3D, create_met2_design_matrix_epg
+  epg.py                    create_Dic_3D, create_met2_design_matrix_epg; slice_profile / hann_sinc / pulse_profile / pulse_pair_profile: slice-profile-aware
+                            dictionaries for 2-D multi-slice data (slice_profile=... of Met2Plan.build_dictionary_epg and the drivers)
   flip_angle_algorithms.py  compute_optimal_FA, fitting_slice_FA_brute_force
   motor.py                  create_Laplacian_matrix, fitting_slice_T2, recon_met2_arrays (voxel loop), nesma_filter, mppca_filter (MP-PCA denoising: csrc/met2_mppca.hip),
                             gibbs_filter (Gibbs-ringing removal, degibbs='yes' and '3d': csrc/met2_gibbs.hip),

@@ -33,7 +33,7 @@ class TvGeometry(C.Structure):
 
 # every symbol include/met2_hip.h declares
 SYMBOLS = ["met2_default_options", "met2_abi_version", "met2_device_count", "met2_last_error", "met2_plan_create",
-           "met2_plan_destroy", "met2_plan_set_options", "met2_plan_get_options", "met2_plan_build_dictionary_epg", "met2_plan_set_dictionary", "met2_plan_get_dictionary",
+           "met2_plan_destroy", "met2_plan_set_options", "met2_plan_get_options", "met2_plan_build_dictionary_epg", "met2_plan_build_dictionary_epg_profile", "met2_plan_set_dictionary", "met2_plan_get_dictionary",
            "met2_plan_set_penalty", "met2_plan_set_penalty_dense", "met2_plan_get_penalty", "met2_plan_set_lambda_grid",
            "met2_plan_set_t2_grid", "met2_fit", "met2_fit_strided", "met2_fit_enqueue_strided", "met2_plan_finish", "met2_fa_bruteforce", "met2_fa_bruteforce_strided", "met2_fa_spline_select",
            "met2_fa_spline_select_strided", "met2_roi_reduce", "met2_nesma", "met2_tv_work_bytes", "met2_tv_chambolle", "met2_tv_last_timing", "met2_tv_launch_info", "met2_tv_detail", "met2_tv_sigma", "met2_smooth_separable", "met2_metrics", "met2_plan_last_kernel_ms", "met2_plan_last_second_pass_ms", "met2_plan_last_spill_count",
@@ -63,6 +63,7 @@ def lib():
         L.met2_plan_set_options.argtypes = [vp, C.POINTER(Options)]
         L.met2_plan_get_options.argtypes = [vp, C.POINTER(Options)]
         L.met2_plan_build_dictionary_epg.argtypes = [vp, _dp, _dp, C.c_double, _dp, C.c_double, vp]
+        L.met2_plan_build_dictionary_epg_profile.argtypes = [vp, _dp, _dp, C.c_double, _dp, C.c_double, C.c_int32, _dp, _dp, _dp, vp]
         L.met2_plan_set_dictionary.argtypes = [vp, _dp]
         L.met2_plan_get_dictionary.argtypes = [vp, _dp]
         L.met2_plan_set_penalty.argtypes = [vp, C.c_int32, _dp]

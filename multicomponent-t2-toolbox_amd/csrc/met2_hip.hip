@@ -4,7 +4,9 @@
 //   epg_dictionary_kernel   epg/epg.py:47-162      one wavefront per (T2, flip angle); the EPG
 //                                                  coherence orders live on the lanes, the
 //                                                  shift operator is a lane shuffle
-//   gram_kernel             B_fa = D_fa^T D_fa, D_fa^T   (once per plan)
+//   epg_profile_dictionary_kernel                  the same trains summed over a slice profile: one workgroup per
+//                                                  (T2, flip angle), its waves share the profile's points
+//   gram_kernel            B_fa = D_fa^T D_fa, D_fa^T   (once per plan)
 //   classify/scan/scatter   gates of motor:124,131 + counting sort of voxels by FA index, so that
 //                           neighbouring entries of the work list read the same D / B rows from L2
 //   fit_kernel<METHOD>      motor:113-162 + motor:443-472: one voxel per wavefront; every wave of the
@@ -86,6 +88,48 @@ int met2::abi_fail(int code, const std::string &msg) { g_err = msg; return code;
 // EPG dictionary  (epg/epg.py:64-153).  Lane k holds order k: Fp = F_k (lane 0: F_0),
 // Fm = F_-k, Z = Z_k.  One inter-echo period = P T P, P = shift then relax over tau/2.
 // ------------------------------------------------------------------------------------------
+// One echo train on one wave: the state after the excitation (the reference's: sin(aexc) in F_0, cos(aexc) in F_-1) and the
+// constants of the refocusing pulse alpha (radians) and of the relaxation over tau/2.  Both dictionary kernels run this recursion.
+struct EpgTrain { double E2, E1, c2, s2, sa, ca, Fp, Fm, Z; };
+
+__device__ __forceinline__ EpgTrain epg_train_begin(int lane, double alpha, double aexc, double tau, double T2, double T1)
+{
+    EpgTrain t;
+    const double th = tau / 2.0;
+    const double R2 = 1.0 / T2, R1 = 1.0 / T1;
+    t.E2 = exp(-th * R2); t.E1 = exp(-th * R1);
+    const double ca2 = cos(alpha / 2.0), sa2 = sin(alpha / 2.0);
+    t.c2 = ca2 * ca2; t.s2 = sa2 * sa2; t.sa = sin(alpha); t.ca = cos(alpha);
+    t.Fp = (lane == 0) ? sin(aexc) : 0.0;
+    t.Fm = (lane == 1) ? cos(aexc) : 0.0;
+    t.Z = 0.0;
+    return t;
+}
+
+// one inter-echo period of an n-echo train; afterwards lane 0's Fp is the echo amplitude
+__device__ __forceinline__ void epg_train_period(EpgTrain &t, int lane, int n)
+{
+    for (int half = 0; half < 2; ++half) {
+        double up = gather(t.Fp, (lane + 63) & 63);   // F_{k-1}
+        double dn = gather(t.Fm, (lane + 1) & 63);    // F_-(k+1)
+        dn = (lane < n) ? dn : 0.0;                   // F_-n <- 0
+        t.Fp = (lane == 0) ? dn : up;                 // F_0 <- F_-1 ; F_k <- F_{k-1}
+        t.Fm = (lane == 0) ? 0.0 : dn;
+        t.Fp *= t.E2; t.Fm *= t.E2; t.Z *= t.E1;
+        if (lane > n) { t.Fp = 0.0; t.Fm = 0.0; t.Z = 0.0; }
+        if (half == 0 && lane >= 1) {
+            // c2 a + s2 b + sa z,  s2 a + c2 b - sa z,  -sa/2 a + sa/2 b + ca z: the fused multiply-adds are written out, in the grouping the
+            // dictionary kernel has always been compiled to, so that both kernels round alike and no compiler's choice of what to contract
+            // changes a dictionary
+            #pragma clang fp contract(off)
+            const double a = t.Fp, b = t.Fm, z = t.Z, hs = 0.5 * t.sa;
+            t.Fp = fma(t.sa, z, fma(t.c2, a, t.s2 * b));
+            t.Fm = fma(-t.sa, z, fma(t.s2, a, t.c2 * b));
+            t.Z = fma(t.ca, z, fma(hs, b, -(hs * a)));
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void epg_dictionary_kernel(int nte, int nt2, int nfa, const double *__restrict__ T2s,
                                                              const double *__restrict__ T1s, double tau,
                                                              const double *__restrict__ alpha_deg, double TR,
@@ -97,33 +141,51 @@ __global__ __launch_bounds__(256) void epg_dictionary_kernel(int nte, int nt2, i
     const int fa = gw / nt2, j = gw - fa * nt2;
     const double rad = M_PI / 180.0;
     const double alpha = alpha_deg[fa] * rad, aexc = alpha_deg[fa] / 2.0 * rad;
-    const double th = tau / 2.0;
-    const double R2 = 1.0 / T2s[j], R1 = 1.0 / T1s[j];
-    const double E2 = exp(-th * R2), E1 = exp(-th * R1);
-    const double ca2 = cos(alpha / 2.0), sa2 = sin(alpha / 2.0);
-    const double c2 = ca2 * ca2, s2 = sa2 * sa2, sa = sin(alpha), ca = cos(alpha);
+    EpgTrain t = epg_train_begin(lane, alpha, aexc, tau, T2s[j], T1s[j]);
     const double scale = 1.0 - exp(-TR / T1s[j]);
-    const int n = nte;
-    double Fp = (lane == 0) ? sin(aexc) : 0.0;
-    double Fm = (lane == 1) ? cos(aexc) : 0.0;
-    double Z = 0.0;
     for (int e = 0; e < nte; ++e) {
-        for (int half = 0; half < 2; ++half) {
-            double up = gather(Fp, (lane + 63) & 63);     // F_{k-1}
-            double dn = gather(Fm, (lane + 1) & 63);      // F_-(k+1)
-            dn = (lane < n) ? dn : 0.0;                   // F_-n <- 0
-            Fp = (lane == 0) ? dn : up;                   // F_0 <- F_-1 ; F_k <- F_{k-1}
-            Fm = (lane == 0) ? 0.0 : dn;
-            Fp *= E2; Fm *= E2; Z *= E1;
-            if (lane > n) { Fp = 0.0; Fm = 0.0; Z = 0.0; }
-            if (half == 0 && lane >= 1) {
-                double a = Fp, b = Fm, z = Z;
-                Fp = c2 * a + s2 * b + sa * z;
-                Fm = s2 * a + c2 * b - sa * z;
-                Z = -0.5 * sa * a + 0.5 * sa * b + ca * z;
-            }
+        epg_train_period(t, lane, nte);
+        if (lane == 0) D[((size_t)fa * nte + e) * nt2 + j] = t.Fp * scale;
+    }
+}
+
+// The dictionary of a slice profile (met2_plan_build_dictionary_epg_profile): D[fa][e][j] = scale_j * sum_z w[z] H_z[e], H_z the train above
+// at the refocusing angle (a * r_ref[z]) and the excitation angle ((a / 2) * r_exc[z]).  One workgroup of four waves per (fa, t2) column:
+// wave v runs the points z = v, v + 4, ...; lane e keeps echo e (in lane 0 after each period), so a finished point is one row of the LDS tile
+// [n_z][64].  Then lanes e < nte of wave 0 sum their column over z in ascending order, product and sum rounded separately: the order is
+// part of the entry's definition and no launch geometry enters it.
+__global__ __launch_bounds__(256) void epg_profile_dictionary_kernel(int nte, int nt2, int nz, const double *__restrict__ T2s,
+                                                                     const double *__restrict__ T1s, double tau,
+                                                                     const double *__restrict__ alpha_deg, double TR,
+                                                                     const double *__restrict__ r_exc, const double *__restrict__ r_ref,
+                                                                     const double *__restrict__ w, double *__restrict__ D /* [nfa][nte][nt2] */)
+{
+    extern __shared__ double epg_tile[];                  // [nz][64]
+    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
+    const int fa = (int)blockIdx.x / nt2, j = (int)blockIdx.x - fa * nt2;
+    const double rad = M_PI / 180.0;
+    const double a = alpha_deg[fa], T2 = T2s[j], T1 = T1s[j];
+    for (int z = wave; z < nz; z += 4) {
+        const double alpha = (a * r_ref[z]) * rad, aexc = ((a / 2.0) * r_exc[z]) * rad;
+        EpgTrain t = epg_train_begin(lane, alpha, aexc, tau, T2, T1);
+        double keep = 0.0;
+        for (int e = 0; e < nte; ++e) {
+            epg_train_period(t, lane, nte);
+            const double h = bcast(t.Fp, 0);
+            keep = (lane == e) ? h : keep;
         }
-        if (lane == 0) D[((size_t)fa * nte + e) * nt2 + j] = Fp * scale;
+        epg_tile[z * 64 + lane] = keep;
+    }
+    __syncthreads();
+    if (wave == 0 && lane < nte) {
+        #pragma clang fp contract(off)
+        double acc = 0.0;
+        for (int z = 0; z < nz; ++z) {
+            const double term = w[z] * epg_tile[z * 64 + lane];
+            acc = acc + term;
+        }
+        const double scale = 1.0 - exp(-TR / T1);
+        D[((size_t)fa * nte + lane) * nt2 + j] = acc * scale;
     }
 }
 
@@ -1649,6 +1711,43 @@ int met2_plan_build_dictionary_epg(met2_plan *p, const double *T2s, const double
     int rc = build_gram(p, s);
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipFree(tmp));
+    if (rc) return rc;
+    rc = ensure_seeds(p, s);
+    if (rc) return rc;
+    return met2_plan_set_t2_grid(p, T2s);
+}
+
+int met2_plan_build_dictionary_epg_profile(met2_plan *p, const double *T2s, const double *T1s, double tau, const double *alpha_deg,
+                                           double TR, int32_t n_z, const double *r_exc, const double *r_ref, const double *w, void *stream)
+{
+    if (!p || !T2s || !T1s || !alpha_deg || !r_exc || !r_ref || !w) return fail(MET2_E_INVALID, "NULL argument");
+    if (n_z < 1 || n_z > 64) return fail(MET2_E_INVALID, "slice profile: n_z must lie in 1..64");
+    double wsum = 0.0;
+    for (int z = 0; z < n_z; ++z) {
+        if (!std::isfinite(r_exc[z]) || !std::isfinite(r_ref[z]) || !std::isfinite(w[z]) || r_exc[z] < 0.0 || r_ref[z] < 0.0 || w[z] < 0.0)
+            return fail(MET2_E_INVALID, "slice profile: r_exc, r_ref and w must be finite and >= 0");
+        wsum += w[z];
+    }
+    if (!(wsum > 0.0)) return fail(MET2_E_INVALID, "slice profile: the weights are all zero");
+    USE_DEVICE(p->opt.device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n0 = (size_t)(2 * p->n_t2 + p->n_fa);
+    std::vector<double> h(n0 + 3 * (size_t)n_z);
+    memcpy(h.data(), T2s, sizeof(double) * p->n_t2);
+    memcpy(h.data() + p->n_t2, T1s, sizeof(double) * p->n_t2);
+    memcpy(h.data() + 2 * p->n_t2, alpha_deg, sizeof(double) * p->n_fa);
+    memcpy(h.data() + n0, r_exc, sizeof(double) * n_z);
+    memcpy(h.data() + n0 + n_z, r_ref, sizeof(double) * n_z);
+    memcpy(h.data() + n0 + 2 * n_z, w, sizeof(double) * n_z);
+    struct Scratch { double *p = nullptr; ~Scratch() { if (p) (void)hipFree(p); } } scratch;      // freed on every return, the failing ones included
+    HIPCHK(hipMalloc(&scratch.p, sizeof(double) * h.size()));
+    double *tmp = scratch.p;
+    HIPCHK(hipMemcpy(tmp, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(epg_profile_dictionary_kernel, dim3(p->n_fa * p->n_t2), dim3(256), sizeof(double) * 64 * (size_t)n_z, s, p->n_te, p->n_t2,
+                       n_z, tmp, tmp + p->n_t2, tau, tmp + 2 * p->n_t2, TR, tmp + n0, tmp + n0 + n_z, tmp + n0 + 2 * n_z, p->dD);
+    HIPCHK(hipGetLastError());
+    int rc = build_gram(p, s);
+    HIPCHK(hipStreamSynchronize(s));
     if (rc) return rc;
     rc = ensure_seeds(p, s);
     if (rc) return rc;

@@ -527,7 +527,7 @@ def _estimate_fa(plan, dd_fa, mm, FA_method, fa_index, T2s, T1s, tau, TR, alpha_
         alpha_values_spline = np.linspace(90.0, 180.0, 15)                                      # motor:237
         plan_lr = Met2Plan(plan.n_te, plan.n_t2, 15, device=device)
         try:
-            plan_lr.build_dictionary_epg(T2s, T1s, tau, alpha_values_spline, TR)
+            plan_lr.build_dictionary_epg(T2s, T1s, tau, alpha_values_spline, TR, slice_profile=plan.slice_profile)
             fa, _, _ = plan.fa_spline(plan_lr, alpha_values_spline, alpha_values, dd_fa, mm, want_km=False)
         finally:
             plan_lr.close()
@@ -539,7 +539,8 @@ def _estimate_fa(plan, dd_fa, mm, FA_method, fa_index, T2s, T1s, tau, TR, alpha_
 def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2", FA_method="brute-force", myelin_T2=40.0,
                       fa_index=None, device=0, plan=None, denoise="None", prepared=False, FA_smooth="no", distributed=False,
                       return_prepared=False, devices=None, bootstrap=None, degibbs="no", bias_correct="no", voxel_size=None,
-                      brain_mask="no", segment="no", tissue_stats="no", pve_threshold=0.9, rician="no", rician_sigma=None, rician_iters=3):
+                      brain_mask="no", segment="no", tissue_stats="no", pve_threshold=0.9, rician="no", rician_sigma=None, rician_iters=3,
+                      slice_profile=None):
     """Steps 1-4 of motor_recon_met2 (motor:293-373, 427-472) on arrays: data [nx,ny,nz,nt] (or
     [nvox, nt]), mask [nx,ny,nz].  Mirrors the driver's preparation: data *= mask (motor:180-182),
     negative values clipped to 0 (motor:279), optional NESMA / TV filter (motor:293-333, needs a 3-D volume) or denoise='MPPCA'
@@ -605,9 +606,17 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     correction, and the residual estimate is biased low where many echoes sit in the floor; neither mode makes the fit a maximum-likelihood
     Rician fit.  ValueError before any device work for another value, for 'direct' without a sigma source, and with devices=[...],
     distributed=True or bootstrap=...  rician='no' (default) changes no output and no launch.
+    slice_profile=<the dict of epg.slice_profile> (an extension, for 2-D multi-slice multi-echo spin echo: the flip angles vary across the
+    slice and the decay is the integral of the echo trains over the profile, Lebel & Wilman 2010): every dictionary of the run -- the run's
+    own plan, the coarse plan of FA_method='spline', and with them what tissue_stats and bootstrap=dict(fa='fixed') reuse -- is built by
+    Met2Plan.build_dictionary_epg(slice_profile=...); one device, through a plan.  'FA' is then the nominal refocusing angle at the slice
+    centre, on the unchanged 90..180 degree grid.  A caller's own plan= keeps the dictionary it has: ValueError if slice_profile is given
+    too and differs from plan.slice_profile.  ValueError before any device work with devices=[...], distributed=True and a bootstrap whose
+    fa is not 'fixed'.  slice_profile=None (default) changes no output and no launch.
     Returns a dict with the driver's ten outputs."""
     boot = _bootstrap_args(bootstrap)
     ric = _rician_check(rician, rician_sigma, rician_iters, denoise, prepared, devices, distributed, bootstrap)
+    slice_profile = _slice_profile_check(slice_profile, plan, devices, distributed, boot)
     if boot is not None and distributed:
         raise ValueError("bootstrap runs on one device and does not go with distributed=True")
     _bootstrap_check(boot, FA_method, FA_smooth)
@@ -626,13 +635,13 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
         made = brain_mask_filter(np.ascontiguousarray(data), voxel_size, device=first_dev)
         res = recon_met2_arrays(data, made, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, fa_index, device, plan, denoise, False,
                                 FA_smooth, False, return_prepared, devices, bootstrap, "no", bias_correct, voxel_size, "no", segment, tissue_stats,
-                                pve_threshold, rician=rician, rician_sigma=rician_sigma, rician_iters=rician_iters)
+                                pve_threshold, rician=rician, rician_sigma=rician_sigma, rician_iters=rician_iters, slice_profile=slice_profile)
         res["mask"] = made
         return res
     bias = _bias_check(bias_correct, vol_shape, voxel_size, distributed)
     nt = data.shape[-1]
     mask = np.asarray(mask).reshape(vol_shape)
-    if devices is None and plan is None and not distributed and data.ndim >= 2 and not ric:
+    if devices is None and plan is None and not distributed and data.ndim >= 2 and not ric and slice_profile is None:
         devices = [device]                                       # the default: one device, through the C ABI's host entry (met2_fit_host: the block
                                                                  # pipeline inside the library; the torch pipeline of rounds 3-4 is retired to tests/tools)
     if devices is not None:
@@ -696,7 +705,7 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     own = plan is None
     if own:
         plan = Met2Plan(nt, Npc, alpha_values.shape[0], device=device, myelin_T2=myelin_T2)
-        plan.build_dictionary_epg(T2s, T1s, tau, alpha_values, TR)
+        plan.build_dictionary_epg(T2s, T1s, tau, alpha_values, TR, slice_profile=slice_profile)
         plan.set_penalty("InvT2" if reg_method == "T2SPARC" else reg_matrix, T2s)   # run_real_data_script.py:91-93
     try:
         if distributed:
@@ -762,6 +771,23 @@ def _rician_check(rician, rician_sigma, rician_iters, denoise, prepared, devices
     return rician
 
 
+def _slice_profile_check(slice_profile, plan, devices, distributed, boot):
+    """slice_profile of recon_met2_arrays -> None or the validated profile dict; what it cannot be combined with is raised before any device work."""
+    if slice_profile is None:
+        return None
+    from . import epg as _epg
+    prof = _epg.check_profile(slice_profile["r_exc"], slice_profile["r_ref"], slice_profile["w"])        # the weights as given
+    if devices is not None:
+        raise ValueError("slice_profile runs through one plan and does not go with devices=[...]")
+    if distributed:
+        raise ValueError("slice_profile does not go with distributed=True")
+    if boot is not None and boot["fa"] != "fixed":
+        raise ValueError("slice_profile goes with bootstrap fa='fixed' only, not fa=%r" % (boot["fa"],))
+    if plan is not None and not _epg.same_profile(prof, plan.slice_profile):
+        raise ValueError("slice_profile differs from the one the caller's plan was built with (plan.slice_profile)")
+    return prof
+
+
 def _rician_sigma(ric, rician_sigma, extra, vol_shape, dev):
     """The noise level of the run as a device volume shaped like the voxels: rician_sigma (a number or a volume), MP-PCA's map for 'direct'
     without one, None for 'iterative' without one (the fit then estimates it)."""
@@ -812,7 +838,7 @@ def _bootstrap_into(res, plan, reg_method, dd, fa_vol, mask, boot, epg=None):
         if boot["fa"] == "spline":
             alpha_lr = np.linspace(90.0, 180.0, 15)                          # motor:237
             plan_lr = Met2Plan(plan.n_te, plan.n_t2, 15, device=plan.device.index or 0)
-            plan_lr.build_dictionary_epg(epg[0], epg[1], epg[2], alpha_lr, epg[3])
+            plan_lr.build_dictionary_epg(epg[0], epg[1], epg[2], alpha_lr, epg[3], slice_profile=plan.slice_profile)
             plan.attach_fa_spline(plan_lr, alpha_lr)
         out = plan.fit_bootstrap(reg_method, dd, n_rep=boot["n_rep"], seed=boot["seed"], fa_index=fa_vol, mask=mask, voxel_id=vid,
                                  want_sig=True, want_status=False, fa=boot["fa"], want_spectrum=boot["spectrum"])
@@ -977,7 +1003,8 @@ def _recon_sharded(plan, dd, dd_fa, mm, reg_method, FA_method, fa_index, T2s, T1
 
 def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR, reg_method, reg_matrix, denoise, FA_method,
                      FA_smooth, myelin_T2, num_cores=-1, device=0, devices=None, bootstrap=None, degibbs="no", bias_correct="no",
-                     brain_mask="no", segment="no", tissue_stats="no", pve_threshold=0.9, rician="no", rician_sigma=None, rician_iters=3):
+                     brain_mask="no", segment="no", tissue_stats="no", pve_threshold=0.9, rician="no", rician_sigma=None, rician_iters=3,
+                     slice_profile=None):
     """Drop-in for motor_recon_met2 (motor:165-506) with the reference's on-disk contract: NIfTI in
     (data [nx,ny,nz,nt], mask [nx,ny,nz]), ten NIfTI volumes out (MWF, IEWF, FWF, T2_M, T2_IE, TWC, FA, fsol_4D,
     Est_Signal, reg_param .nii.gz at path_to_save_data, motor:475-503).  `num_cores` is accepted and ignored (one
@@ -1003,7 +1030,9 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     BOOT_QUANTITIES (BOOT_STATS along the last axis) and sigma.nii.gz; with fa='brute-force' / 'spline' also FA_bootstrap.nii.gz [nx,ny,nz,5]
     (degrees), with spectrum=True also fsol_bootstrap_{mean,std,q025,q500,q975}.nii.gz [nx,ny,nz,n_t2] each.
     rician='iterative' | 'direct' with rician_sigma and rician_iters (an extension, see recon_met2_arrays; not with devices=[...] or bootstrap):
-    also writes sigma.nii.gz; 'iterative' SNR.nii.gz and rician_flag.nii.gz, 'direct' Data_rician.nii.gz (the corrected volume)."""
+    also writes sigma.nii.gz; 'iterative' SNR.nii.gz and rician_flag.nii.gz, 'direct' Data_rician.nii.gz (the corrected volume).
+    slice_profile=<the dict of epg.slice_profile> (an extension, see recon_met2_arrays; not with devices=[...] or a bootstrap whose fa is not
+    'fixed'): the dictionaries are built over the slice profile; FA.nii.gz is then the nominal refocusing angle at the slice centre."""
     from . import nifti
     img = nifti.load(path_to_data)
     data = img.get_fdata().astype(np.float64, copy=False)           # Fortran-ordered, like nibabel's: read in place by the solver
@@ -1017,6 +1046,9 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
         rician_kw = {"rician": rician, "rician_sigma": rician_sigma, "rician_iters": rician_iters}
     else:
         rician_kw = {}
+    profile_kw = {}
+    if _slice_profile_check(slice_profile, None, devices, False, _bootstrap_args(bootstrap)) is not None:
+        profile_kw = {"slice_profile": slice_profile}
     mask = None if brain_mask == "yes" else nifti.load(path_to_mask).get_fdata().astype(np.int64)
     if data.ndim != 4 or (mask is not None and mask.shape != data.shape[:3]):
         raise ValueError("data must be 4-D and mask must match its first three dimensions")
@@ -1042,7 +1074,7 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
         nifti.save(nifti.NiftiImage(mask, img.affine), path_to_save_data + "mask.nii.gz")
     res = recon_met2_arrays(data, mask, TE_array, TR, reg_method, reg_matrix, FA_method, myelin_T2, device=device, denoise=denoise,
                             FA_smooth=FA_smooth, return_prepared=(denoise in ("TV", "MPPCA")), devices=devices, bootstrap=bootstrap,
-                            **bias_kw, **rician_kw)
+                            **bias_kw, **rician_kw, **profile_kw)
     if brain_mask == "yes":
         res["mask"] = mask
     if rician_kw:

@@ -91,6 +91,7 @@ class Met2Plan:
         lam[1:] = np.logspace(np.log10(1e-8), np.log10(10.0), num=49, endpoint=True, base=10.0)
         self._lam_grid = None
         self.alpha_values = None                  # the flip angles in degrees, once build_dictionary_epg has set them
+        self.slice_profile = None                 # the slice profile build_dictionary_epg was given, if any
         self.set_lambda_grid(lam)
 
     def close(self):
@@ -123,10 +124,23 @@ class Met2Plan:
         return {k: getattr(opt, k) for k in (names or ("x2_factor", "t2sparc_lambda", "brent_xtol", "brent_maxfun", "t2_myelin_cut", "t2_ie_cut",
                                                            "x2_lo", "x2_hi", "gcv_lo", "gcv_hi", "bayes_lo", "bayes_hi"))}
 
-    def build_dictionary_epg(self, T2s, T1s, tau, alpha_values, TR):
+    def build_dictionary_epg(self, T2s, T1s, tau, alpha_values, TR, slice_profile=None):
+        """slice_profile: None (one flip angle per voxel, the reference's dictionary) or the dict of epg.slice_profile -- the dictionary is
+        then the weighted sum of the echo trains over the slice (met2_plan_build_dictionary_epg_profile) and alpha_values are the nominal
+        refocusing angles at the slice centre; the plan keeps the profile as plan.slice_profile."""
         (_, p2), (_, p1), (_, pa) = _h(T2s), _h(T1s), _h(alpha_values)
         keep = (_h(T2s), _h(T1s), _h(alpha_values))
-        check(lib().met2_plan_build_dictionary_epg(self._h, keep[0][1], keep[1][1], float(tau), keep[2][1], float(TR), self._stream()))
+        if slice_profile is None:
+            check(lib().met2_plan_build_dictionary_epg(self._h, keep[0][1], keep[1][1], float(tau), keep[2][1], float(TR), self._stream()))
+        else:
+            prof = tuple(_h(np.atleast_1d(np.asarray(slice_profile[k], dtype=np.float64))) for k in ("r_exc", "r_ref", "w"))
+            n_z = prof[0][0].shape[0]
+            if any(a.ndim != 1 or a.shape[0] != n_z for a, _ in prof):
+                raise ValueError("slice_profile: r_exc, r_ref and w must be 1-D arrays of one length")
+            check(lib().met2_plan_build_dictionary_epg_profile(self._h, keep[0][1], keep[1][1], float(tau), keep[2][1], float(TR), n_z,
+                                                               prof[0][1], prof[1][1], prof[2][1], self._stream()))
+            slice_profile = {k: a.copy() for k, (a, _) in zip(("r_exc", "r_ref", "w"), prof)}
+        self.slice_profile = slice_profile
         self.alpha_values = keep[2][0].copy()
         return self
 
@@ -136,6 +150,7 @@ class Met2Plan:
             raise ValueError("Dic_3D must be [n_te, n_t2, n_fa] = %s, got %s" % ((self.n_te, self.n_t2, self.n_fa), a.shape))
         check(lib().met2_plan_set_dictionary(self._h, p))
         self.alpha_values = None
+        self.slice_profile = None
         return self
 
     def get_dictionary(self):
