@@ -7,14 +7,16 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   epg.py                    create_Dic_3D, create_met2_design_matrix_epg; slice_profile / hann_sinc / pulse_profile / pulse_pair_profile: slice-profile-aware
                             dictionaries for 2-D multi-slice data (slice_profile=... of Met2Plan.build_dictionary_epg and the drivers)
   flip_angle_algorithms.py  compute_optimal_FA, fitting_slice_FA_brute_force
-  motor.py                  create_Laplacian_matrix, fitting_slice_T2, recon_met2_arrays (voxel loop), nesma_filter, mppca_filter (MP-PCA denoising: csrc/met2_mppca.hip),
+  motor.py                  create_Laplacian_matrix, fitting_slice_T2, the drivers: recon_met2_arrays (steps 1-4 on arrays; _resolve_run states what the options
+                            refuse and where they run), motor_recon_met2 (the on-disk contract), the ROI mode; re-exports the filters
+  filters.py                the whole-volume filters, one C ABI call each: nesma_filter, mppca_filter (MP-PCA denoising: csrc/met2_mppca.hip),
                             gibbs_filter (Gibbs-ringing removal, degibbs='yes' and '3d': csrc/met2_gibbs.hip),
                             bias_field_filter (bias-field correction of the TWC map, bias_correct='yes': csrc/met2_bias.hip),
                             brain_mask_filter (brain extraction, brain_mask='yes': csrc/met2_bet.hip),
                             tissue_segment_filter (tissue segmentation of the TWC map, segment='yes': csrc/met2_seg.hip),
                             partial_volume_filter (partial-volume tissue maps of the TWC map, segment='pve': csrc/met2_pve.hip),
                             label_stats_filter (per-tissue / per-ROI statistics of the maps and spectra, tissue_stats='yes': csrc/met2_stats.hip),
-                            gaussian_smooth, ROI mode
+                            gaussian_smooth
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
   gibbs.py                  gibbs_tables / gibbs_split / gibbs_split3d / gibbs_lines: the stages of the Gibbs-ringing filter one by one (tests and diagnostics)
   bet.py                    bet_mean / bet_stats / bet_mesh / bet_evolve / bet_fill: the stages of the brain extraction one by one (tests and diagnostics)
@@ -34,20 +36,11 @@ from ._lib import Met2Error  # noqa: F401
 from .plan import BOOT_QUANTITIES, BOOT_QUANTITIES_FA, BOOT_STATS, MAP_NAMES, METHODS, PENALTIES, Met2Plan  # noqa: F401
 
 
+_LAZY = ("gibbs_filter", "bias_field_filter", "brain_mask_filter", "tissue_segment_filter", "partial_volume_filter")   # motor's, imported on first use
+
+
 def __getattr__(name):
-    if name == "gibbs_filter":                 # motor.gibbs_filter, imported on first use
-        from .motor import gibbs_filter
-        return gibbs_filter
-    if name == "bias_field_filter":            # motor.bias_field_filter, likewise
-        from .motor import bias_field_filter
-        return bias_field_filter
-    if name == "brain_mask_filter":            # motor.brain_mask_filter, likewise
-        from .motor import brain_mask_filter
-        return brain_mask_filter
-    if name == "tissue_segment_filter":        # motor.tissue_segment_filter, likewise
-        from .motor import tissue_segment_filter
-        return tissue_segment_filter
-    if name == "partial_volume_filter":        # motor.partial_volume_filter, likewise
-        from .motor import partial_volume_filter
-        return partial_volume_filter
+    if name in _LAZY:
+        from . import motor
+        return getattr(motor, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

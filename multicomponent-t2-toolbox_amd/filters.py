@@ -1,0 +1,262 @@
+"""The whole-volume filters of the drivers, each one call into the C ABI (one translation unit under csrc/ per filter): nesma_filter,
+mppca_filter, gibbs_filter, brain_mask_filter, bias_field_filter, tissue_segment_filter, partial_volume_filter, label_stats_filter and
+gaussian_smooth.  All take numpy arrays (and return numpy) or CUDA tensors (and return tensors on the same device); motor.py's drivers
+call them and re-export the names."""
+import numpy as np
+import torch
+
+from ._lib import _dp, check, lib
+
+
+def _enter(x, device):
+    """-> (x as a float64 contiguous tensor on the device, that device, whether the caller gave numpy)"""
+    as_numpy = not torch.is_tensor(x)
+    dev = torch.device("cuda", device) if as_numpy else x.device
+    return torch.as_tensor(x, dtype=torch.float64, device=dev).contiguous(), dev, as_numpy
+
+
+def _voxel_size(voxel_size):
+    vox = np.ascontiguousarray(np.asarray(voxel_size, dtype=np.float64).reshape(-1))
+    if vox.shape != (3,):
+        raise ValueError("voxel_size must be (dx, dy, dz)")
+    return vox
+
+
+def _mask_u8(mask, dev, chosen):
+    """mask -> uint8 on the device, 1 where chosen(mask) holds; None stays None (every voxel)"""
+    return None if mask is None else chosen(torch.as_tensor(mask, device=dev)).to(torch.uint8).contiguous()
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _call(dev, entry, *args):
+    """one entry of the library on dev's current stream"""
+    with torch.cuda.device(dev):
+        check(getattr(lib(), entry)(dev.index or 0, *args, torch.cuda.current_stream(dev).cuda_stream))
+
+
+def _leave(out, as_numpy):
+    """a tensor or a tuple of tensors, as numpy when numpy came in"""
+    if not as_numpy:
+        return out
+    return out.cpu().numpy() if torch.is_tensor(out) else tuple(t.cpu().numpy() for t in out)
+
+
+def _nonzero(m):
+    return m != 0
+
+
+def nesma_filter(data, mask, device=0):
+    """The NESMA filter of the driver (motor:305-333) on the device: `data` [nx,ny,nz,nt] as the driver holds it at
+    that point (multiplied by the mask, negatives clipped), `mask` [nx,ny,nz]; voxels with mask == 1 become the
+    mean of the similar voxels (relative L1 distance < 2.5 %) of their 12^3 window, all others zero.  Accepts numpy
+    arrays (returns numpy) or CUDA tensors (returns a tensor on the same device)."""
+    dd, dev, as_numpy = _enter(data, device)
+    if dd.dim() != 4 or tuple(np.shape(mask)) != tuple(dd.shape[:3]):
+        raise ValueError("data must be [nx,ny,nz,nt] and mask [nx,ny,nz]")
+    mk = _mask_u8(mask, dev, lambda m: m == 1)
+    out = torch.empty_like(dd)
+    _call(dev, "met2_nesma", *dd.shape, dd.data_ptr(), mk.data_ptr(), out.data_ptr())
+    return _leave(out, as_numpy)
+
+
+def mppca_filter(data, mask, window=5, device=0, return_maps=False):
+    """Marchenko-Pastur PCA denoising (Veraart et al., NeuroImage 2016; met2_mppca in include/met2_hip.h states the algorithm) on the
+    device: `data` [nx,ny,nz,nt], 2 <= nt <= 63, `mask` [nx,ny,nz]; every voxel with mask != 0 is projected on the signal subspace of
+    the decay curves of its window^3 patch (masked voxels only), all others become zero.  The output is not clipped.
+    return_maps=True: (denoised, sigma [nx,ny,nz] the noise level, rank [nx,ny,nz] int32 the components kept; -1 where the patch holds
+    a non-finite value and -2 where the eigen-solver gave up, both copied through).  numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    dd, dev, as_numpy = _enter(data, device)
+    if dd.dim() != 4 or tuple(np.shape(mask)) != tuple(dd.shape[:3]):
+        raise ValueError("data must be [nx,ny,nz,nt] and mask [nx,ny,nz]")
+    mk = _mask_u8(mask, dev, _nonzero)
+    out = torch.empty_like(dd)
+    sigma = torch.empty(dd.shape[:3], dtype=torch.float64, device=dev) if return_maps else None
+    rank = torch.empty(dd.shape[:3], dtype=torch.int32, device=dev) if return_maps else None
+    _call(dev, "met2_mppca", *dd.shape, dd.data_ptr(), mk.data_ptr(), int(window), out.data_ptr(), _ptr(sigma), _ptr(rank))
+    return _leave((out, sigma, rank) if return_maps else out, as_numpy)
+
+
+def gibbs_filter(data, nshifts=20, minW=1, maxW=3, device=0, return_shifts=False, mode="2d"):
+    """Removal of Gibbs (truncation) ringing by local sub-voxel shifts (Kellner et al., MRM 2016; met2_degibbs in include/met2_hip.h states
+    the algorithm) on the device: every (z, echo) slice of `data` [nx,ny,nz,nt] is unrung along x and y, 8 <= nx, ny <= 256.  The defaults
+    are those of MRtrix's mrdegibbs, which the reference's example script runs at this place; parity with mrdegibbs itself is unpinned.  A
+    slice that holds a non-finite value is copied through.  The output is not clipped: it can undershoot zero next to an edge.
+    mode='3d' (met2_degibbs3d; Bautista et al., ISMRM 2021), for 3-D Fourier-encoded acquisitions: every echo volume is unrung along x, y
+    and z, 8 <= nx, ny, nz <= 256; an echo volume that holds a non-finite value is copied through.
+    return_shifts=True: (unrung, shift_x, shift_y), the int8 shifts (in units of 1 / (2 nshifts) voxel) chosen per sample along each axis;
+    with mode='3d' (unrung, shift_x, shift_y, shift_z).  numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    if mode not in ("2d", "3d"):
+        raise ValueError("mode must be '2d' or '3d'")
+    dd, dev, as_numpy = _enter(data, device)
+    if dd.dim() != 4:
+        raise ValueError("data must be [nx,ny,nz,nt]")
+    out = torch.empty_like(dd)
+    shifts = tuple(torch.empty(dd.shape, dtype=torch.int8, device=dev) if return_shifts else None for _ in range(3 if mode == "3d" else 2))
+    _call(dev, "met2_degibbs3d" if mode == "3d" else "met2_degibbs", *dd.shape, dd.data_ptr(), int(nshifts), int(minW), int(maxW),
+          out.data_ptr(), *map(_ptr, shifts))
+    return _leave((out,) + shifts if return_shifts else out, as_numpy)
+
+def brain_mask_filter(data, voxel_size, f=0.4, level=4, n_iter=1000, device=0, return_surface=False):
+    """Brain extraction (met2_brain_mask in include/met2_hip.h states the algorithm: the surface model of Smith, HBM 2002, which FSL's bet
+    runs, without bet's self-intersection retry pass and its -R / -S / -B variants) on the device: `data` [nx,ny,nz], or [nx,ny,nz,nt], which
+    is averaged over the echoes first; `voxel_size` (dx, dy, dz) in mm.  The defaults are those of the reference's example script
+    (bet -m -f 0.4; level 4 is bet's mesh of 2562 vertices); parity with bet itself is unpinned.  -> uint8 mask [nx,ny,nz], 1 inside the
+    surface.  return_surface=True: (mask, vertices [nv, 3] in mm, triangles [nt, 3] int32, statistics: a dict of t2, t, t98, tm, cx, cy, cz,
+    r).  numpy in -> numpy out, CUDA tensor in -> tensors out (the triangles and the statistics are host objects either way)."""
+    from . import bet
+    as_numpy = not torch.is_tensor(data)
+    if (np.ndim(data) if as_numpy else data.dim()) not in (3, 4):
+        raise ValueError("data must be [nx,ny,nz] or [nx,ny,nz,nt]")
+    vox = _voxel_size(voxel_size)
+    dd, dev, _ = _enter(data, device)
+    if dd.dim() == 4:
+        dd = bet.bet_mean(dd)
+    mask = torch.empty(dd.shape, dtype=torch.uint8, device=dev)
+    n = 4 ** min(max(int(level), 0), 4)
+    verts = torch.empty((10 * n + 2, 3), dtype=torch.float64, device=dev) if return_surface else None
+    st = np.zeros(8, dtype=np.float64)
+    _call(dev, "met2_brain_mask", *dd.shape, dd.data_ptr(), vox.ctypes.data_as(_dp), float(f), int(level), int(n_iter), mask.data_ptr(),
+          _ptr(verts), st.ctypes.data_as(_dp))
+    if not return_surface:
+        return _leave(mask, as_numpy)
+    stats = {k: float(x) for k, x in zip(bet.STAT_KEYS, st)}
+    return _leave((mask, verts), as_numpy) + (bet.bet_mesh(level)[1], stats)
+
+def bias_field_filter(vol, mask=None, voxel_size=(1, 1, 1), n_class=3, n_outer=4, n_em=10, fwhm=20.0, device=0, return_field=False):
+    """Bias-field correction of a 3-D map (met2_bias_field in include/met2_hip.h states the algorithm: the EM estimator of Wells et al. 1996
+    and Guillemaud & Brady 1997, which FSL's fast iterates, without fast's Markov random field term) on the device: `vol` [nx,ny,nz], `mask`
+    [nx,ny,nz] or None (every voxel), `voxel_size` (dx, dy, dz) in mm.  The defaults are those of the reference's example script
+    (fast -n 3 -I 4 -l 20.0); parity with fast itself is unpinned.  The field is estimated on the masked voxels that are finite and positive
+    and divided out wherever it is defined; non-finite voxels are copied through.
+    return_field=True: (corrected, field, classes [3 n_class] = the final class means and variances of log(vol) and the class weights).
+    numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    dd, dev, as_numpy = _enter(vol, device)
+    if dd.dim() != 3 or (mask is not None and tuple(np.shape(mask)) != tuple(dd.shape)):
+        raise ValueError("vol must be [nx,ny,nz] and mask the same shape")
+    vox = _voxel_size(voxel_size)
+    mk = _mask_u8(mask, dev, _nonzero)
+    out = torch.empty_like(dd)
+    field = torch.empty_like(dd) if return_field else None
+    classes = torch.empty(3 * max(int(n_class), 0), dtype=torch.float64, device=dev) if return_field else None
+    _call(dev, "met2_bias_field", *dd.shape, dd.data_ptr(), _ptr(mk), vox.ctypes.data_as(_dp), int(n_class), int(n_outer), int(n_em),
+          float(fwhm), out.data_ptr(), _ptr(field), _ptr(classes))
+    return _leave((out, field, classes) if return_field else out, as_numpy)
+
+def tissue_segment_filter(vol, mask=None, voxel_size=(1, 1, 1), n_class=3, beta=0.1, n_outer=4, n_em=10, n_icm=8, device=0, return_prob=True):
+    """Tissue segmentation of a 3-D map (met2_tissue_segment in include/met2_hip.h states the algorithm: the hidden-Markov-random-field EM of
+    Zhang, Brady & Smith 2001, the model of FSL's fast: Gaussian classes in log intensity, a Potts prior of strength `beta` over the six face
+    neighbours weighted by the voxel size, labels by iterated conditional modes) on the device: `vol` [nx,ny,nz] (the drivers pass the
+    bias-corrected water-content map), `mask` [nx,ny,nz] or None (every voxel), `voxel_size` (dx, dy, dz) in mm.  The defaults are those of the
+    reference's example script (fast -n 3 -H 0.1); parity with fast itself is unpinned.  The outputs are hard labels and class posteriors
+    (fast's _seg and _prob_k); its _pve_k maps are partial_volume_filter's.  Voxels outside the mask, non-finite or not positive are left out.
+    -> seg [nx,ny,nz] uint8: 0 where left out, otherwise 1..n_class by ascending class mean (1 the driest tissue of a water-content map);
+    return_prob=True: (seg, prob [n_class,nx,ny,nz]: the class posteriors in that order, 0 where left out, classes [3 n_class]: the class
+    means and variances of log(vol) and the class weights, in that order too).
+    numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    dd, dev, as_numpy = _enter(vol, device)
+    if dd.dim() != 3 or (mask is not None and tuple(np.shape(mask)) != tuple(dd.shape)):
+        raise ValueError("vol must be [nx,ny,nz] and mask the same shape")
+    vox = _voxel_size(voxel_size)
+    mk = _mask_u8(mask, dev, _nonzero)
+    K = max(int(n_class), 0)
+    seg = torch.zeros(tuple(dd.shape), dtype=torch.uint8, device=dev)
+    prob = torch.zeros((K,) + tuple(dd.shape), dtype=torch.float64, device=dev) if return_prob else None
+    classes = torch.zeros(3 * K, dtype=torch.float64, device=dev) if return_prob else None
+    _call(dev, "met2_tissue_segment", *dd.shape, dd.data_ptr(), _ptr(mk), vox.ctypes.data_as(_dp), int(n_class), float(beta), int(n_outer),
+          int(n_em), int(n_icm), seg.data_ptr(), _ptr(prob), _ptr(classes))
+    return _leave((seg, prob, classes) if return_prob else seg, as_numpy)
+
+
+def partial_volume_filter(vol, mask=None, voxel_size=(1, 1, 1), n_class=3, beta=0.1, beta_pv=0.3, n_outer=4, n_em=10, n_icm=8, device=0,
+                          seg=None, prob=None):
+    """Partial-volume tissue maps of a 3-D map (met2_partial_volume in include/met2_hip.h states the algorithm: the mixel model of Santago &
+    Gage 1993 as Shattuck et al. 2001 and Tohka et al. 2004 use it -- every voxel pure tissue or a mixture of two rank-adjacent tissues, a
+    Potts-like prior of strength `beta_pv` over the six face neighbours, types by iterated conditional modes, the fraction of a mixed voxel
+    in Tohka's closed form) on the device, after the tissue segmentation: `seg` [nx,ny,nz] and `prob` [n_class,nx,ny,nz] as
+    tissue_segment_filter returns them, or None, and tissue_segment_filter runs first with `mask`, `beta`, `n_outer`, `n_em`, `n_icm`.  The
+    defaults are those of the reference's example script (fast -n 3 -H 0.1, and fast's own -R 0.3); parity with fast itself is unpinned.
+    -> (pve [n_class,nx,ny,nz]: the tissue fractions, summing to 1 on the segmented voxels and 0 elsewhere; pveseg [nx,ny,nz] uint8: 1 + the
+    class of the largest fraction, 0 elsewhere; mixeltype uint8: 0..n_class-1 pure, n_class + j a mixture of classes j and j + 1, 255
+    elsewhere; classes_lin [3 n_class]: the class means and variances of vol itself (not its log) and the class weights).
+    numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    if (seg is None) != (prob is None):
+        raise ValueError("seg and prob go together")
+    vox = _voxel_size(voxel_size)
+    dd, dev, as_numpy = _enter(vol, device)
+    if dd.dim() != 3 or (mask is not None and tuple(np.shape(mask)) != tuple(dd.shape)):
+        raise ValueError("vol must be [nx,ny,nz] and mask the same shape")
+    K = max(int(n_class), 0)
+    if seg is None:
+        seg, prob, _ = tissue_segment_filter(dd, mask, vox, n_class, beta, n_outer, n_em, n_icm)
+    sg = torch.as_tensor(seg, device=dev).to(torch.uint8).contiguous()
+    pr = torch.as_tensor(prob, dtype=torch.float64, device=dev).contiguous()
+    if tuple(sg.shape) != tuple(dd.shape) or tuple(pr.shape) != (K,) + tuple(dd.shape):
+        raise ValueError("seg must have the shape of vol and prob must be [n_class] + that shape")
+    pve = torch.zeros((K,) + tuple(dd.shape), dtype=torch.float64, device=dev)
+    pveseg = torch.zeros(tuple(dd.shape), dtype=torch.uint8, device=dev)
+    mixel = torch.full(tuple(dd.shape), 255, dtype=torch.uint8, device=dev)
+    classes = torch.zeros(3 * K, dtype=torch.float64, device=dev)
+    _call(dev, "met2_partial_volume", *dd.shape, dd.data_ptr(), sg.data_ptr(), pr.data_ptr(), vox.ctypes.data_as(_dp), int(n_class),
+          float(beta_pv), int(n_icm), pve.data_ptr(), pveseg.data_ptr(), mixel.data_ptr(), classes.data_ptr())
+    return _leave((pve, pveseg, mixel, classes), as_numpy)
+
+STAT_QUANTITIES = ("MWF", "IEWF", "FWF", "T2_M", "T2_IE", "TWC", "FA", "reg_param")
+STAT_KEYS = ("n", "mean", "std", "quantiles", "spectrum_mean", "spectrum_quantiles")
+
+
+def label_stats_filter(res, labels, q=None, device=0):
+    """Per-label statistics of a result dict of recon_met2_arrays (met2_label_stats in include/met2_hip.h states the definitions; stats.py
+    holds the stages) on the device: `labels` is an integer volume shaped like the maps -- every distinct value > 0 is a label, mapped to
+    dense indices the way recon_met2_rois does, so a tissue segmentation and an atlas ROI image are served alike; `q` the probabilities
+    (stats.DEFAULT_Q).  Per label the sample of a quantity is its voxels that are not NaN.
+    -> dict(labels [L], quantities = STAT_QUANTITIES, q, n, mean, std [L, 8], quantiles [L, 8, n_q] (np.quantile's 'linear', to the bit),
+    spectrum_mean [L, n_t2]: the per-bin mean of fsol_4D over the label, normalised to sum 1 -- the reference's mean_T2_dist (motor:377) per
+    label, its TO DO (2) of motor:376 --, spectrum_quantiles [L, n_t2, n_q]: the per-bin quantiles scaled by the same factor, the spatial
+    band around it, T2s)."""
+    from . import stats
+    q = stats.DEFAULT_Q if q is None else tuple(float(x) for x in np.asarray(q, dtype=np.float64).reshape(-1))
+    lab_in = labels if torch.is_tensor(labels) else np.asarray(labels)
+    if (lab_in.dtype.is_floating_point if torch.is_tensor(lab_in) else lab_in.dtype.kind not in "iu"):
+        raise ValueError("labels must be an integer volume")
+    vol_shape = tuple(np.shape(res["MWF"]))
+    if tuple(lab_in.shape) != vol_shape:
+        raise ValueError("labels must have the shape of the maps")
+    dev = torch.device("cuda", device)
+    lab = torch.as_tensor(lab_in if torch.is_tensor(lab_in) else np.ascontiguousarray(lab_in).astype(np.int64), device=dev).to(torch.int64).reshape(-1)
+    ids = torch.unique(lab)
+    ids = ids[ids > 0]
+    L = int(ids.numel())
+    if L == 0:
+        raise ValueError("no label > 0")
+    pos = torch.searchsorted(ids, lab).clamp(max=L - 1)
+    dense = torch.where(ids[pos] == lab, pos, torch.full_like(pos, -1)).to(torch.int32)
+    maps = torch.stack([torch.as_tensor(np.ascontiguousarray(res[name], dtype=np.float64), device=dev).reshape(-1) for name in STAT_QUANTITIES])
+    fsol = torch.as_tensor(np.ascontiguousarray(res["fsol_4D"], dtype=np.float64), device=dev)
+    n_t2 = int(fsol.shape[-1])
+    st = stats.label_stats(maps, dense, L, q, "series")
+    sp = stats.label_stats(fsol.reshape(-1, n_t2), dense, L, q, "voxel")
+    with np.errstate(invalid="ignore", divide="ignore"):
+        tot = sp[:, :, 1].sum(axis=1)
+        return {"labels": ids.cpu().numpy(), "quantities": STAT_QUANTITIES, "q": np.asarray(q), "n": st[:, :, 0], "mean": st[:, :, 1],
+                "std": st[:, :, 2], "quantiles": st[:, :, 3:], "spectrum_mean": sp[:, :, 1] / tot[:, None],
+                "spectrum_quantiles": sp[:, :, 3:] / tot[:, None, None], "T2s": np.asarray(res["T2s"])}
+
+def gaussian_smooth(data, sigma=2.0, truncate=4.0, device=0):
+    """The Gaussian pre-smoothing of the FA step (motor:337-343): every echo volume of data [nx,ny,nz,nt] through the
+    equivalent of scipy.ndimage.gaussian_filter(volume, sigma) (mode 'reflect', truncate 4), on the device, bit-identical
+    to scipy.  numpy in -> numpy out, CUDA tensor in -> tensor out."""
+    dd, dev, as_numpy = _enter(data, device)
+    if dd.dim() != 4:
+        raise ValueError("data must be [nx,ny,nz,nt]")
+    radius = int(truncate * float(sigma) + 0.5)                      # scipy.ndimage.gaussian_filter1d
+    x = np.arange(-radius, radius + 1)
+    w = np.exp(-0.5 / (float(sigma) * float(sigma)) * x ** 2)
+    w = np.ascontiguousarray(w / w.sum(), dtype=np.float64)
+    out = torch.empty_like(dd)
+    work = torch.empty_like(dd)
+    _call(dev, "met2_smooth_separable", *dd.shape, radius, w.ctypes.data_as(_dp), dd.data_ptr(), out.data_ptr(), work.data_ptr())
+    torch.cuda.current_stream(dev).synchronize()                     # `work` and the host weights stay alive until here
+    return _leave(out, as_numpy)

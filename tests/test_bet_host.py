@@ -204,6 +204,7 @@ def test_driver_argument_checks_raise_before_the_library_is_touched(monkeypatch)
 
     monkeypatch.setattr(motor, "lib", no_lib)
     monkeypatch.setattr(importlib.import_module(PKG + ".bet"), "lib", no_lib)
+    monkeypatch.setattr(importlib.import_module(PKG + ".filters"), "lib", no_lib)     # brain_mask_filter's
     data = np.ones((8, 8, 4, 32))
     mask = np.ones((8, 8, 4))
     TE = 10.0 * np.arange(1, 33)

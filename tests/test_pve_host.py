@@ -206,3 +206,96 @@ def test_segment_pve_adds_exactly_three_keys(monkeypatch):
     for k in yes:
         assert np.array_equal(got[k], yes[k])
     assert got["TWC_pve"].shape == (3, 4, 4, 2) and got["TWC_pveseg"].dtype == np.uint8 and got["TWC_mixeltype"].dtype == np.uint8
+
+
+def test_bad_degibbs_and_bias_options_are_refused_before_any_device_work(monkeypatch):
+    """the degibbs and bias_correct checks sit in the drivers' one resolver, before gibbs_filter and brain_mask_filter run"""
+    motor = importlib.import_module(PKG + ".motor")
+    filters = importlib.import_module(PKG + ".filters")
+
+    def touched(*a, **k):
+        raise AssertionError("the device was touched")
+
+    monkeypatch.setattr(motor, "lib", touched)
+    monkeypatch.setattr(filters, "lib", touched)
+    monkeypatch.setattr(motor, "gibbs_filter", touched)
+    monkeypatch.setattr(motor, "brain_mask_filter", touched)
+    data, mask, TE = np.ones((8, 8, 8, 8)), np.ones((8, 8, 8)), 10.0 * np.arange(1, 9)
+    with pytest.raises(ValueError, match="bias_correct must be 'no' or 'yes'"):
+        motor.recon_met2_arrays(data, mask, TE, 3000.0, degibbs="yes", bias_correct="maybe")
+    with pytest.raises(ValueError, match=r"bias_correct='yes' needs voxel_size=\(dx, dy, dz\) in mm"):
+        motor.recon_met2_arrays(data, mask, TE, 3000.0, degibbs="yes", bias_correct="yes")
+    with pytest.raises(ValueError, match="degibbs must be 'no', 'yes' or '3d'"):
+        motor.recon_met2_arrays(data, None, TE, 3000.0, degibbs="sometimes", brain_mask="yes", voxel_size=(1, 1, 1))
+
+
+def test_both_drivers_take_the_same_options():
+    motor = importlib.import_module(PKG + ".motor")
+    arrays = [("data", None), ("mask", None), ("TE_array", None), ("TR", None), ("reg_method", "X2"), ("reg_matrix", "L2"),
+              ("FA_method", "brute-force"), ("myelin_T2", 40.0), ("fa_index", None), ("device", 0), ("plan", None), ("denoise", "None"),
+              ("prepared", False), ("FA_smooth", "no"), ("distributed", False), ("return_prepared", False), ("devices", None), ("bootstrap", None),
+              ("degibbs", "no"), ("bias_correct", "no"), ("voxel_size", None), ("brain_mask", "no"), ("segment", "no"), ("tissue_stats", "no"),
+              ("pve_threshold", 0.9), ("rician", "no"), ("rician_sigma", None), ("rician_iters", 3), ("slice_profile", None)]
+    on_disk = [("TE_array", None), ("path_to_data", None), ("path_to_mask", None), ("path_to_save_data", None), ("TR", None), ("reg_method", None),
+               ("reg_matrix", None), ("denoise", None), ("FA_method", None), ("FA_smooth", None), ("myelin_T2", None), ("num_cores", -1),
+               ("device", 0), ("devices", None), ("bootstrap", None), ("degibbs", "no"), ("bias_correct", "no"), ("brain_mask", "no"),
+               ("segment", "no"), ("tissue_stats", "no"), ("pve_threshold", 0.9), ("rician", "no"), ("rician_sigma", None), ("rician_iters", 3),
+               ("slice_profile", None)]
+    signature = lambda f: [(k, None if p.default is inspect.Parameter.empty else p.default) for k, p in inspect.signature(f).parameters.items()]
+    assert signature(motor.recon_met2_arrays) == arrays
+    assert signature(motor.motor_recon_met2) == on_disk
+    for name, default in on_disk[[k for k, _ in on_disk].index("devices"):]:
+        assert (name, default) in arrays, name
+
+
+def test_the_device_list_leg_builds_one_plan_for_its_tail(monkeypatch):
+    """devices=[...] with a bootstrap and tissue statistics: the post-fit steps run once each, in order, on ONE plan made on devices[0],
+    which is closed whatever a step does.  The fit, the plan and the steps are recorders that touch no device."""
+    motor = importlib.import_module(PKG + ".motor")
+    data, mask, TE = np.ones((4, 4, 2, 8)), np.ones((4, 4, 2)), 10.0 * np.arange(1, 9)
+    steps, plans = [], []
+
+    class Plan:
+        def __init__(self, n_te, n_t2, n_fa, device=0, **k):
+            self.shape, self.device, self.closed = (n_te, n_t2, n_fa), device, 0
+            plans.append(self)
+
+        def build_dictionary_epg(self, *a, **k):
+            return self
+
+        def set_penalty(self, *a, **k):
+            return self
+
+        def close(self):
+            self.closed += 1
+
+    def fit(*a, **k):
+        return {"TWC": np.full((4, 4, 2), 2.0), "MWF": np.zeros((4, 4, 2)), "FA_index": np.zeros((4, 4, 2)), "data_prepared": data.copy()}
+
+    def step(name, fail=False):
+        def record(res, *a, **k):
+            steps.append((name, [x for x in a if isinstance(x, Plan)]))
+            if fail:
+                raise RuntimeError(name + " failed")
+        return record
+
+    monkeypatch.setattr(motor, "_recon_multi_device", fit)
+    monkeypatch.setattr(motor, "Met2Plan", Plan)
+    monkeypatch.setattr(motor, "_bootstrap_into", step("bootstrap"))
+    monkeypatch.setattr(motor, "_bias_last", step("bias"))
+    monkeypatch.setattr(motor, "_segment_last", step("segment"))
+    monkeypatch.setattr(motor, "_tissue_stats_last", step("tissue statistics"))
+    kw = dict(bootstrap=dict(n_rep=2), bias_correct="yes", voxel_size=(1.0, 1.0, 2.0), segment="yes", tissue_stats="yes")
+    res = motor.recon_met2_arrays(data, mask, TE, 3000.0, devices=[3, 5], **kw)
+    assert [name for name, _ in steps] == ["bootstrap", "bias", "segment", "tissue statistics"]
+    assert len(plans) == 1 and plans[0].closed == 1 and plans[0].device == 3 and plans[0].shape == (8, 60, 91)
+    assert steps[0][1] == [plans[0]] and steps[3][1] == [plans[0]]       # the bootstrap and the statistics share it
+    assert "data_prepared" not in res                                    # asked for by the tail only, not by the caller
+    del steps[:], plans[:]
+    monkeypatch.setattr(motor, "_segment_last", step("segment", fail=True))
+    with pytest.raises(RuntimeError, match="segment failed"):
+        motor.recon_met2_arrays(data, mask, TE, 3000.0, devices=[3, 5], **kw)
+    assert [name for name, _ in steps] == ["bootstrap", "bias", "segment"] and len(plans) == 1 and plans[0].closed == 1
+    del steps[:], plans[:]
+    motor.recon_met2_arrays(data, mask, TE, 3000.0, devices=[3], bias_correct="yes", voxel_size=(1.0, 1.0, 2.0))
+    assert [name for name, _ in steps] == ["bias"] and not plans          # no plan where nothing needs one
