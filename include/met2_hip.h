@@ -514,6 +514,52 @@ int met2_mppca_stages(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_
                       double *out, double *sigma, int32_t *rank, int32_t max_sweeps, int32_t *n_patch, int32_t *patch, double *gram,
                       double *eigval, double *eigvec, int32_t *sweeps, void *stream);
 
+/* met2_mppca with a box window and, optionally, the average over the overlapping patches (mppca_filter's window= and average=; additive, ABI stays
+ * 6; the averaging after Manjon et al., PLoS ONE 2013; pinned against its numpy restatement only, tests/tools/mppca_box_numpy.py -- parity
+ * with MRtrix's dwidenoise or DIPY is unpinned).  DEVICE pointers as for met2_mppca, and out, each may be NULL: n_patch [nx][ny][nz] int32,
+ * wsum [nx][ny][nz].  window (HOST) = (wx, wy, wz), each odd and >= 1, wx wy wz >= 3.
+ *   Patch.  The patch of a voxel c with mask != 0 is the box of half-widths (wx / 2, wy / 2, wz / 2) around it, clipped at the volume's faces,
+ *     restricted to voxels with mask != 0 and listed in memory order.  Steps 1-3 of met2_mppca run unchanged on it and give k_c, sigma_c and
+ *     U_c, the eigenvectors of the k_c largest eigenvalues.  The copy-through classes are those of met2_mppca: N < 2 (rank 1), a non-finite
+ *     value or an overflowing C (rank -1), the eigen-solver's give-up (rank -2).
+ *   average = 0.  Step 4 of met2_mppca: out[v] = U_v (U_v^T x_v), sigma[v] = sigma_v, rank[v] = k_v, n_patch[v] = N_v, wsum[v] = 0.  With
+ *     wx = wy = wz = w this is met2_mppca(window = w) bit for bit (the same kernel code).  One launch, no work space, asynchronous on `stream`.
+ *   average = 1.  For a voxel v with mask != 0 let C(v) be the masked voxels of the same clipped box around v, in ascending memory order (the
+ *     box is symmetric: these are the centres whose patch holds v).  A centre votes unless it is in a copy-through class; its weight is
+ *     w_c = 1 / (1 + k_c).  out[v] = (sum_c w_c U_c (U_c^T x_v)) / (sum_c w_c), sigma[v] = (sum_c w_c sigma_c) / (sum_c w_c), both sums over
+ *     the voting centres of C(v) in that order; rank[v] = v's own k_v (the negative codes included), n_patch[v] = N_v, wsum[v] = sum_c w_c.  No
+ *     voting centre: out[v] = x_v, sigma[v] = 0, wsum[v] = 0.  A centre of rank 0 votes with weight 1 and a zero curve.
+ *     The order of the arithmetic: per centre p = sum_j u_j (u_j . x_v) over the kept eigenvectors by ascending eigenvalue, one fused
+ *     multiply-add per term; each dot product is a 64-lane tree (neighbouring lanes first: pairs, fours, eights, sixteens, then
+ *     (row 0 + row 1) + (row 2 + row 3)) over the echoes; then acc = fma(w_c, p, acc), wsum += w_c, ssum = fma(w_c, sigma_c, ssum).
+ *   mask == 0: out = 0, sigma = 0, rank = 0, n_patch = 0, wsum = 0.  Scaling the data by a power of two scales out and sigma by exactly that
+ *   power while nothing over- or underflows; rank, n_patch and wsum do not change.
+ *   Work space (average = 1).  Per centre a 24-byte head and its k_c kept eigenvectors, k_c n_te doubles taken from a pool by one atomic add
+ *     (where a centre's vectors lie in the pool depends on the order of arrival, what they hold does not); 16 bytes hold the pool's count.
+ *     With P = min(wx, nx) min(wy, ny) min(wz, nz), the largest patch of the volume and the most centres that hold one voxel, and
+ *     K = min(n_te, P), the most vectors a centre keeps: c centres need at most 16 + c (24 + 8 n_te K) bytes, and are reckoned at
+ *     16 + 24 c + 8 max(c n_te min(K, 8), P n_te K) bytes -- 8 vectors per centre (measured means at 32 echoes: 1.1 to 1.3), and never less
+ *     than one voxel's centres need at most.  The volume is cut into boxes of output voxels whose centres -- the box widened by the
+ *     half-widths, clipped -- fit as reckoned: whole (y, z) planes while one plane's centres fit, else whole z lines of one plane, else runs
+ *     of one line; centres in the overlap of two boxes are decomposed again.  A box whose centres keep more vectors than the pool holds
+ *     writes nothing past it, is halved along its longest side and run again; a box of one voxel always fits.  (The overfilled attempt's
+ *     decomposition is thrown away: where most centres keep more than 8 vectors, every halving decomposes the box once more.  Unmeasured.)
+ *     The entry allocates one
+ *     device block of at most max_work_bytes (0: the default, which is the whole volume's largest need capped at 2^30 bytes = 1 GiB,
+ *     whatever the volume), enqueues on `stream`, waits for it -- after every box that could have overfilled the pool, and at the end -- and
+ *     frees the block: BLOCKING.  The result does not depend on the cut and repeats to the bit.  met2_mppca_box_work_bytes gives min_bytes
+ *     (one voxel's centres at any rank: at most 343 of them, 10.9 MB at 63 echoes) and default_bytes for a shape without touching a device;
+ *     both are 0 for average = 0 and for an empty volume.
+ * MET2_E_INVALID: a negative dimension, window NULL, an entry even or < 1, wx wy wz < 3, average outside {0, 1}, max_work_bytes < 0, or
+ * (average = 1) > 0 and below min_bytes -- the message names the minimum --, data or out NULL, out == data.  MET2_E_UNSUPPORTED: n_te < 2 or
+ * > 63; wx wy wz > 343 (the patch list, 4 wx wy wz bytes, must fit in LDS beside the two n_te x n_te matrices at every n_te); more than
+ * 2^26 - 1 voxels.  The checks of window, average and n_te come first; an empty volume then returns MET2_OK at once.  Deterministic. */
+int met2_mppca_box(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, const uint8_t *mask,
+                   const int32_t window[3], int32_t average, int64_t max_work_bytes, double *out, double *sigma, int32_t *rank,
+                   int32_t *n_patch, double *wsum, void *stream);
+int met2_mppca_box_work_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const int32_t window[3], int32_t average,
+                              int64_t *min_bytes, int64_t *default_bytes);
+
 /* Removal of Gibbs (truncation) ringing by local sub-voxel shifts (degibbs='yes'; Kellner, Dhital, Kiselev, Reisert, MRM 2016; step 2 of the
  * reference's example pipeline, example_script_run_MET2_preproc_and_recon.sh, which runs MRtrix's mrdegibbs there; stated here from the
  * paper, none of MRtrix's program text is used and parity with mrdegibbs itself is unpinned).

@@ -9,7 +9,7 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   flip_angle_algorithms.py  compute_optimal_FA, fitting_slice_FA_brute_force
   motor.py                  create_Laplacian_matrix, fitting_slice_T2, the drivers: recon_met2_arrays (steps 1-4 on arrays; _resolve_run states what the options
                             refuse and where they run), motor_recon_met2 (the on-disk contract), the ROI mode; re-exports the filters
-  filters.py                the whole-volume filters, one C ABI call each: nesma_filter, mppca_filter (MP-PCA denoising: csrc/met2_mppca.hip),
+  filters.py                the whole-volume filters, one C ABI call each: nesma_filter, mppca_filter (MP-PCA denoising, cubic or box window, optional overlapping-patch averaging: csrc/met2_mppca.hip),
                             gibbs_filter (Gibbs-ringing removal, degibbs='yes' and '3d': csrc/met2_gibbs.hip),
                             bias_field_filter (bias-field correction of the TWC map, bias_correct='yes': csrc/met2_bias.hip),
                             brain_mask_filter (brain extraction, brain_mask='yes': csrc/met2_bet.hip),

@@ -39,7 +39,7 @@ SYMBOLS = ["met2_default_options", "met2_abi_version", "met2_device_count", "met
            "met2_fa_spline_select_strided", "met2_roi_reduce", "met2_nesma", "met2_tv_work_bytes", "met2_tv_chambolle", "met2_tv_last_timing", "met2_tv_launch_info", "met2_tv_detail", "met2_tv_sigma", "met2_smooth_separable", "met2_metrics", "met2_plan_last_kernel_ms", "met2_plan_last_second_pass_ms", "met2_plan_last_spill_count",
            "met2_plan_launch_info", "met2_plan_gcv_form", "met2_plan_get_shape", "met2_fit_host", "met2_plan_attach_fa_spline", "met2_host_trim",
            "met2_fit_bootstrap", "met2_fit_bootstrap_fa", "met2_bootstrap_replicates", "met2_bootstrap_series_stats", "met2_bootstrap_spectrum_stats",
-           "met2_bootstrap_spec_launch_info", "met2_synth_two_lobe", "met2_eval_voxel_metrics", "met2_eval_reduce", "met2_refac_packed_calls", "met2_mppca", "met2_mppca_stages", "met2_degibbs", "met2_bias_field",
+           "met2_bootstrap_spec_launch_info", "met2_synth_two_lobe", "met2_eval_voxel_metrics", "met2_eval_reduce", "met2_refac_packed_calls", "met2_mppca", "met2_mppca_stages", "met2_mppca_box", "met2_mppca_box_work_bytes", "met2_degibbs", "met2_bias_field",
            "met2_bias_weights", "met2_bias_domain", "met2_bias_init", "met2_bias_em", "met2_bias_smooth", "met2_bias_update", "met2_bias_apply",
            "met2_gibbs_table_cols", "met2_gibbs_tables", "met2_gibbs_split", "met2_gibbs_lines", "met2_degibbs3d", "met2_gibbs_split3d",
            "met2_brain_mask", "met2_bet_stats", "met2_bet_evolve", "met2_bet_fill", "met2_bet_mesh", "met2_bet_mean",
@@ -84,6 +84,8 @@ def lib():
         L.met2_nesma.argtypes = [C.c_int32] * 5 + [vp] * 4
         L.met2_mppca.argtypes = [C.c_int32] * 5 + [vp, vp, C.c_int32, vp, vp, vp, vp]
         L.met2_mppca_stages.argtypes = [C.c_int32] * 5 + [vp, vp, C.c_int32, vp, vp, vp, C.c_int32] + [vp] * 7
+        L.met2_mppca_box.argtypes = [C.c_int32] * 5 + [vp, vp, C.POINTER(C.c_int32), C.c_int32, C.c_int64] + [vp] * 6
+        L.met2_mppca_box_work_bytes.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.met2_degibbs.argtypes = [C.c_int32] * 5 + [vp] + [C.c_int32] * 3 + [vp, vp, vp, vp]
         L.met2_gibbs_table_cols.argtypes = [C.c_int32]
         L.met2_gibbs_table_cols.restype = C.c_int32

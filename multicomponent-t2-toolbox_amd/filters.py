@@ -1,5 +1,5 @@
 """The whole-volume filters of the drivers, each one call into the C ABI (one translation unit under csrc/ per filter): nesma_filter,
-mppca_filter, gibbs_filter, brain_mask_filter, bias_field_filter, tissue_segment_filter, partial_volume_filter, label_stats_filter and
+mppca_filter (with mppca_window and mppca_work_bytes), gibbs_filter, brain_mask_filter, bias_field_filter, tissue_segment_filter, partial_volume_filter, label_stats_filter and
 gaussian_smooth.  All take numpy arrays (and return numpy) or CUDA tensors (and return tensors on the same device); motor.py's drivers
 call them and re-export the names."""
 import numpy as np
@@ -62,12 +62,44 @@ def nesma_filter(data, mask, device=0):
     return _leave(out, as_numpy)
 
 
-def mppca_filter(data, mask, window=5, device=0, return_maps=False):
+def mppca_window(window, average=False):
+    """an odd int w >= 3 (the cube) or three odd ints >= 1 holding at least 3 voxels -> (wx, wy, wz); ValueError otherwise, and for more
+    than 343 voxels wherever met2_mppca_box would run (three ints, or average)"""
+    a = np.atleast_1d(np.asarray(window))
+    if a.dtype.kind not in "iu" or a.shape not in ((1,), (3,)):
+        raise ValueError("the MP-PCA window must be an odd int >= 3 or three odd ints (wx, wy, wz)")
+    w = tuple(int(x) for x in a) * (3 if a.size == 1 else 1)
+    if any(x < 1 or x % 2 == 0 for x in w) or w[0] * w[1] * w[2] < 3:
+        raise ValueError("the MP-PCA window must be an odd int >= 3 or (wx, wy, wz), each odd and >= 1, holding at least 3 voxels")
+    if (a.size == 3 or average) and w[0] * w[1] * w[2] > 343:
+        raise ValueError("an MP-PCA window (wx, wy, wz), and any window with averaging, must hold at most 343 voxels")
+    return w
+
+
+def mppca_work_bytes(shape, window, average=True):
+    """(min_bytes, default_bytes) of mppca_filter's work space for data of `shape` [nx,ny,nz,nt] (met2_mppca_box_work_bytes; no device
+    needed): max_work_bytes may lie anywhere from min_bytes up; both are 0 without averaging."""
+    import ctypes as C
+    nx, ny, nz, nt = (int(x) for x in shape)
+    lo, dflt = C.c_int64(0), C.c_int64(0)
+    check(lib().met2_mppca_box_work_bytes(nx, ny, nz, nt, (C.c_int32 * 3)(*mppca_window(window, True)), int(bool(average)), C.byref(lo), C.byref(dflt)))
+    return lo.value, dflt.value
+
+
+def mppca_filter(data, mask, window=5, average=False, device=0, return_maps=False, max_work_bytes=0):
     """Marchenko-Pastur PCA denoising (Veraart et al., NeuroImage 2016; met2_mppca in include/met2_hip.h states the algorithm) on the
     device: `data` [nx,ny,nz,nt], 2 <= nt <= 63, `mask` [nx,ny,nz]; every voxel with mask != 0 is projected on the signal subspace of
     the decay curves of its window^3 patch (masked voxels only), all others become zero.  The output is not clipped.
-    return_maps=True: (denoised, sigma [nx,ny,nz] the noise level, rank [nx,ny,nz] int32 the components kept; -1 where the patch holds
-    a non-finite value and -2 where the eigen-solver gave up, both copied through).  numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    window=(wx, wy, wz) (met2_mppca_box): a box patch, each side odd, for anisotropic voxels -- (5, 5, 1) keeps to the slice of a 2-D
+    multi-slice acquisition.  average=True (met2_mppca_box, average = 1): every voxel becomes the weighted mean of the estimates of all the
+    patches that hold it, weights 1 / (1 + rank) (Manjon et al., PLoS ONE 2013); sigma is the same mean of the patches' noise levels.  The
+    patches' bases are held in a work space of at most max_work_bytes (0: the library's default, at most 1 GiB; mppca_work_bytes gives the
+    minimum), the volume going through in as many pieces as that takes; the result does not depend on it.  The call then waits for the device.
+    An int window without average is the call of met2_mppca it always was.  Pinned against its numpy restatement only (tests/tools).
+    return_maps=True: (denoised, sigma [nx,ny,nz] the noise level, rank [nx,ny,nz] int32 the components kept by the voxel's own patch; -1
+    where the patch holds a non-finite value and -2 where the eigen-solver gave up, both copied through -- with average=True only where no
+    patch that holds the voxel has a say).  numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    import ctypes as C
     dd, dev, as_numpy = _enter(data, device)
     if dd.dim() != 4 or tuple(np.shape(mask)) != tuple(dd.shape[:3]):
         raise ValueError("data must be [nx,ny,nz,nt] and mask [nx,ny,nz]")
@@ -75,7 +107,11 @@ def mppca_filter(data, mask, window=5, device=0, return_maps=False):
     out = torch.empty_like(dd)
     sigma = torch.empty(dd.shape[:3], dtype=torch.float64, device=dev) if return_maps else None
     rank = torch.empty(dd.shape[:3], dtype=torch.int32, device=dev) if return_maps else None
-    _call(dev, "met2_mppca", *dd.shape, dd.data_ptr(), mk.data_ptr(), int(window), out.data_ptr(), _ptr(sigma), _ptr(rank))
+    if np.ndim(window) == 0 and not average:                       # the call of before, refusals included: a bad int window is the library's Met2Error
+        _call(dev, "met2_mppca", *dd.shape, dd.data_ptr(), mk.data_ptr(), int(window), out.data_ptr(), _ptr(sigma), _ptr(rank))
+    else:
+        _call(dev, "met2_mppca_box", *dd.shape, dd.data_ptr(), mk.data_ptr(), (C.c_int32 * 3)(*mppca_window(window, True)), int(bool(average)),
+              int(max_work_bytes), out.data_ptr(), _ptr(sigma), _ptr(rank), None, None)
     return _leave((out, sigma, rank) if return_maps else out, as_numpy)
 
 

@@ -213,10 +213,10 @@ def tissue_stats_tables(ts):
     return np.array(rows, dtype=object), np.array(spectra, dtype=np.float64)
 
 
-def _prepare_volume(data, mask, dev, prepared, denoise, maps=None):
+def _prepare_volume(data, mask, dev, prepared, denoise, maps=None, mppca=(5, False)):
     """The driver's preparation (motor:180-182, :279, :293-333) on the device.  The volume keeps the memory order it
     arrives in (nibabel arrays are Fortran-ordered; the solver reads either order in place).  denoise='MPPCA' (an extension) leaves its
-    noise map in maps['MPPCA_sigma'] when the caller hands a dict in."""
+    noise map in maps['MPPCA_sigma'] when the caller hands a dict in; mppca = (window, average) as mppca_filter takes them."""
     dd = torch.as_tensor(data, dtype=torch.float64, device=dev)
     mk = torch.as_tensor(mask, device=dev)
     if not prepared:
@@ -234,7 +234,7 @@ def _prepare_volume(data, mask, dev, prepared, denoise, maps=None):
         elif denoise == "MPPCA":
             if dd.dim() != 4:
                 raise ValueError("MPPCA needs data [nx,ny,nz,nt]")
-            dd, sigma, _ = mppca_filter(dd, mk, return_maps=True)
+            dd, sigma, _ = mppca_filter(dd, mk, window=mppca[0], average=mppca[1], return_maps=True)
             dd = torch.where(dd < 0.0, torch.zeros((), dtype=torch.float64, device=dev), dd)   # the projection can undershoot at late echoes
             if maps is not None:
                 maps["MPPCA_sigma"] = sigma
@@ -257,16 +257,16 @@ def _estimate_fa(plan, dd_fa, mm, FA_method, fa_index, T2s, T1s, tau, TR, alpha_
     return unflatten(fa, vol, order)
 
 
-_Run = collections.namedtuple("_Run", "degibbs brain_mask denoise rician boot slice_profile bias segment tissue_stats pve_threshold first_dev")
+_Run = collections.namedtuple("_Run", "degibbs brain_mask denoise rician boot slice_profile bias segment tissue_stats pve_threshold first_dev mppca")
 
 
 def _resolve_run(data_shape, mask, *, FA_method, FA_smooth, denoise, device, devices, bootstrap, degibbs, bias_correct, voxel_size, brain_mask,
                  segment, tissue_stats, pve_threshold, rician, rician_sigma, rician_iters, slice_profile, prepared=False, distributed=False,
                  plan=None, mask_name="a mask"):
     """The options of recon_met2_arrays and motor_recon_met2 as given -> the _Run record of the steps that run: degibbs ('no' | 'yes' |
-    '3d'), brain_mask (bool), denoise, rician (None | 'iterative' | 'direct'), boot (None or the dict with n_rep, seed, fa, spectrum),
-    slice_profile (None or the validated dict), bias (bool), segment ('no' | 'yes' | 'pve'), tissue_stats (bool), pve_threshold, and
-    first_dev: devices[0], else the caller's plan's device, else `device`.  Both drivers call it first, so every refusal is a ValueError
+    '3d'), brain_mask (bool), denoise (the method's name), rician (None | 'iterative' | 'direct'), boot (None or the dict with n_rep, seed, fa, spectrum),
+    slice_profile (None or the validated dict), bias (bool), segment ('no' | 'yes' | 'pve'), tissue_stats (bool), pve_threshold,
+    first_dev: devices[0], else the caller's plan's device, else `device`, and mppca: (window, average) as mppca_filter takes them.  Both drivers call it first, so every refusal is a ValueError
     before any device work.  The rules, in the order they are checked (the first bad option wins):
       bootstrap       takes the keys n_rep, seed, fa ('fixed' | 'brute-force' | 'spline') and spectrum only.
       rician          'no' | 'iterative' | 'direct'.  Runs through one plan: not with devices=[...], distributed=True or bootstrap=...;
@@ -275,7 +275,12 @@ def _resolve_run(data_shape, mask, *, FA_method, FA_smooth, denoise, device, dev
                       whose fa is 'fixed', and it must equal the profile a caller's plan= was built with.
       bootstrap       runs on one device: not with distributed=True.  An fa other than 'fixed' must be the run's FA_method and does not go
                       with FA_smooth='yes'.
-      FA_method       'brute-force' | 'spline'.      denoise   'None' | 'NESMA' | 'TV' | 'MPPCA'.
+      FA_method       'brute-force' | 'spline'.
+      denoise         'None' | 'NESMA' | 'TV' | 'MPPCA', or a dict with the key method (one of those) and, optionally, mppca_window and
+                      mppca_average and no other key.  mppca_window: an odd int >= 3 or (wx, wy, wz), each odd and >= 1, 3 to 343 voxels
+                      (filters.mppca_window; default 5); mppca_average: 'no' | 'yes' (default 'no'; with 'yes' an int window holds at most
+                      343 voxels too); either away from its default needs method 'MPPCA'.  (The two ride in `denoise` because the
+                      drivers' argument lists are fixed.)
       segment         'no' | 'yes' | 'pve'; needs bias_correct='yes'; not with distributed=True.
       tissue_stats    'no' | 'yes'; needs segment='yes' or 'pve'; not with distributed=True; pve_threshold in [0.5, 1).
       brain_mask      'no' | 'yes'; makes the mask itself: `mask` is None; works on the raw volume: not with prepared=True; not with
@@ -287,6 +292,9 @@ def _resolve_run(data_shape, mask, *, FA_method, FA_smooth, denoise, device, dev
     tissue_stats all run on devices[0]; only the FA step and the fit are dealt over the list.  Under distributed=True degibbs runs on every
     rank's own copy (it is deterministic)."""
     boot = _bootstrap_args(bootstrap)
+    denoise_given, mppca_window, mppca_average = denoise, 5, "no"
+    if isinstance(denoise, dict):                                # what is wrong with the dict is said where denoise is checked, below
+        denoise, mppca_window, mppca_average = denoise.get("method"), denoise.get("mppca_window", 5), denoise.get("mppca_average", "no")
     if rician not in ("no", "iterative", "direct"):
         raise ValueError("rician must be 'no', 'iterative' or 'direct'")
     if rician != "no":
@@ -318,8 +326,17 @@ def _resolve_run(data_shape, mask, *, FA_method, FA_smooth, denoise, device, dev
     _bootstrap_check(boot, FA_method, FA_smooth)
     if FA_method not in ("brute-force", "spline"):
         raise ValueError("FA_method must be 'spline' or 'brute-force'")
-    if denoise not in ("None", None, "none", "NESMA", "TV", "MPPCA"):
+    if isinstance(denoise_given, dict) and ("method" not in denoise_given or set(denoise_given) - {"method", "mppca_window", "mppca_average"}):
+        raise ValueError("denoise as a dict takes method, mppca_window and mppca_average, and needs method; got %s" % sorted(denoise_given))
+    if not isinstance(denoise, (str, type(None))) or denoise not in ("None", None, "none", "NESMA", "TV", "MPPCA"):
         raise ValueError("denoise must be 'None', 'NESMA', 'TV' or 'MPPCA'")
+    if mppca_average not in ("no", "yes"):
+        raise ValueError("mppca_average must be 'no' or 'yes'")
+    from . import filters as _filters
+    _filters.mppca_window(mppca_window, mppca_average == "yes")
+    if denoise != "MPPCA" and (mppca_average != "no" or np.ndim(mppca_window) != 0 or mppca_window != 5):
+        raise ValueError("mppca_window and mppca_average need the denoise method 'MPPCA'")
+    mppca = (mppca_window if np.ndim(mppca_window) == 0 else tuple(int(w) for w in mppca_window), mppca_average == "yes")
     _segment_check(segment, bias_correct, distributed)
     tstats = _tissue_stats_check(tissue_stats, segment, distributed, pve_threshold)
     volume = len(data_shape) == 4
@@ -357,7 +374,7 @@ def _resolve_run(data_shape, mask, *, FA_method, FA_smooth, denoise, device, dev
         raise ValueError("devices=[...] builds its own plans and does not go with distributed=True")
     first_dev = devices[0] if devices else plan.device.index or 0 if plan is not None else device
     return _Run(degibbs, brain_mask == "yes", denoise, None if rician == "no" else rician, boot, slice_profile, bias_correct == "yes", segment,
-                tstats, pve_threshold, first_dev)
+                tstats, pve_threshold, first_dev, mppca)
 
 
 def _finish(run, res, dd, mask, plan, proto, reg_method, voxel_size, myelin_T2):
@@ -382,7 +399,10 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     """Steps 1-4 of motor_recon_met2 (motor:293-373, 427-472) on arrays: data [nx,ny,nz,nt] (or
     [nvox, nt]), mask [nx,ny,nz].  Mirrors the driver's preparation: data *= mask (motor:180-182),
     negative values clipped to 0 (motor:279), optional NESMA / TV filter (motor:293-333, needs a 3-D volume) or denoise='MPPCA'
-    (mppca_filter with window 5, an extension; what it leaves below zero is set to zero; return_prepared=True then adds 'MPPCA_sigma'),
+    (mppca_filter with window 5, an extension; what it leaves below zero is set to zero; return_prepared=True then adds 'MPPCA_sigma';
+    denoise={'method': 'MPPCA', 'mppca_window': (wx, wy, wz), 'mppca_average': 'yes'} hands mppca_filter a box patch for anisotropic
+    voxels, e.g. (5, 5, 1) for 2-D multi-slice data, and has it average the estimates of all patches that hold a voxel -- its window and
+    average; either key may be left out; rician='direct' takes the noise map of whichever mode ran),
     and the constants of _protocol.  `prepared=True` says the caller already did that preparation (mask multiply, clip, denoise).
     Every option below defaults to a value that changes no output and no launch; what each refuses, always before any device work, and
     where it runs on the devices=[...] leg is stated once, in _resolve_run.
@@ -456,8 +476,8 @@ def recon_met2_arrays(data, mask, TE_array, TR, reg_method="X2", reg_matrix="L2"
     own = None
     try:
         if devices is not None:
-            res = _recon_multi_device(data, mask, proto, reg_method, FA_method, myelin_T2, fa_index, list(devices), prepared, denoise, FA_smooth,
-                                      return_prepared=return_prepared or needs_plan)
+            res = _recon_multi_device(data, mask, proto, reg_method, FA_method, myelin_T2, fa_index, list(devices), prepared, run.denoise, FA_smooth,
+                                      return_prepared=return_prepared or needs_plan, mppca=run.mppca)
             dd = None
             if needs_plan:                                       # a plan with the run's dictionary on devices[0]: the host entry closed its own
                 dd = res["data_prepared"] if return_prepared else res.pop("data_prepared")
@@ -485,7 +505,7 @@ def _recon_one_plan(run, plan, proto, data, mask, reg_method, FA_method, fa_inde
     volume the fit read); under distributed=True (what _recon_sharded returns, None)."""
     dev, vol_shape = plan.device, data.shape[:-1]
     extra = {}
-    dd, mk = _prepare_volume(data, mask, dev, prepared, run.denoise, extra)
+    dd, mk = _prepare_volume(data, mask, dev, prepared, run.denoise, extra, run.mppca)
     mm = (mk > 0)
     sigma_vol = _rician_sigma(run.rician, rician_sigma, extra, vol_shape, dev)
     dd_prepared = dd
@@ -600,7 +620,8 @@ def _match_layout(t, order):
     return t if t.permute(*rev).is_contiguous() else t.permute(*rev).contiguous().permute(*rev)
 
 
-def _recon_multi_device(data, mask, proto, reg_method, FA_method, myelin_T2, fa_index, devices, prepared, denoise, FA_smooth, return_prepared=False):
+def _recon_multi_device(data, mask, proto, reg_method, FA_method, myelin_T2, fa_index, devices, prepared, denoise, FA_smooth, return_prepared=False,
+                        mppca=(5, False)):
     """recon_met2_arrays(devices=[...]): one process, one plan per listed device, driven by met2_fit_host (host.fit_host).  The driver's
     preparation runs on the host for plain runs and, with a whole-volume filter (motor:293-343), on devices[0]; steps 2-4 then go through
     the host entry, which deals blocks of the voxel list to the devices."""
@@ -621,7 +642,7 @@ def _recon_multi_device(data, mask, proto, reg_method, FA_method, myelin_T2, fa_
     extra = {}                                                   # what a filter leaves beside the volume (MPPCA: its noise map)
     if filtered:
         dev0 = torch.device("cuda", devices[0])
-        dd, _ = _prepare_volume(data, mask, dev0, prepared, denoise, extra)
+        dd, _ = _prepare_volume(data, mask, dev0, prepared, denoise, extra, mppca)
         one_device = len(set(devices)) == 1                      # the filtered volume stays where it is: met2_fit_host copies its blocks device to device
         place = (lambda t: t) if one_device else to_pinned
         if FA_smooth == "yes" and fa_index is None:
@@ -731,7 +752,7 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
     Est_Signal, reg_param .nii.gz at path_to_save_data, motor:475-503).  `num_cores` is accepted and ignored (one
     process drives the GPU; devices=[0, 1, ...]: that one process drives all the listed GPUs through met2_fit_host).  denoise: 'None',
     'NESMA' (motor:305-333), 'TV' (motor:293-304) or 'MPPCA' (an extension: mppca_filter; Data_denoised.nii.gz as for TV, and the noise
-    map MPPCA_sigma.nii.gz).  degibbs='yes' or '3d' (see recon_met2_arrays): the raw volume is unrung first (gibbs_filter) and written as
+    map MPPCA_sigma.nii.gz; the dict form with mppca_window and mppca_average as for recon_met2_arrays).  degibbs='yes' or '3d' (see recon_met2_arrays): the raw volume is unrung first (gibbs_filter) and written as
     Data_degibbs.nii.gz.  bias_correct='yes' (see recon_met2_arrays): TWC.nii.gz is the bias-corrected map and TWC_bias.nii.gz the
     estimated field, as the example script leaves them; the voxel size is the data header's pixdim[1:4] (absolute values, 0 read as 1).
     segment='yes' (see recon_met2_arrays; needs bias_correct='yes'): TWC_seg.nii.gz (0 outside, 1..3 by ascending water content) and
@@ -779,7 +800,7 @@ def motor_recon_met2(TE_array, path_to_data, path_to_mask, path_to_save_data, TR
         save(avg, "Data_avg")
         save(mask, "mask")
     res = recon_met2_arrays(data, mask, TE_array, TR, reg_method=reg_method, reg_matrix=reg_matrix, FA_method=FA_method, myelin_T2=myelin_T2,
-                            device=device, denoise=denoise, FA_smooth=FA_smooth, return_prepared=(denoise in ("TV", "MPPCA")), devices=devices,
+                            device=device, denoise=denoise, FA_smooth=FA_smooth, return_prepared=(run.denoise in ("TV", "MPPCA")), devices=devices,
                             bootstrap=bootstrap, bias_correct=bias_correct, voxel_size=voxel_size, segment=segment, tissue_stats=tissue_stats,
                             pve_threshold=pve_threshold, rician=rician, rician_sigma=rician_sigma, rician_iters=rician_iters,
                             slice_profile=slice_profile)
