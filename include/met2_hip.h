@@ -935,6 +935,57 @@ int met2_label_quantiles(int32_t device, int32_t n_label, const int32_t *offset,
 int met2_label_stats(int32_t device, int64_t nvox, const int32_t *label, int32_t n_label, int32_t n_series, const double *values,
                      int64_t voxel_stride, int64_t series_stride, int32_t n_q, const double *q_host, double *out, void *stream);
 
+/* Affine resampling of volumes and label images (an extension; additive, ABI stays 6): what brings an atlas ROI image onto the grid of the
+ * maps, or the maps into a template space, through a GIVEN transform; estimating the transform is not part of the library.  It is
+ * scipy.ndimage.affine_transform(src, A[:, :3], offset=A[:, 3], output_shape=dst, mode='constant', cval=cval), restated; no plan: `device`
+ * and `stream` only.  All arithmetic is fp64 and no product is fused into a sum: every operation below rounds once, in the order written.
+ * Shapes.  The source grid is [nx][ny][nz] (src_dims), the destination grid [mx][my][mz] (dst_dims), both in C order, z fastest; series s
+ * of source voxel v = (x ny + y) nz + z is src[v src_voxel_stride + s src_series_stride], of destination voxel w
+ * dst[w dst_voxel_stride + s dst_series_stride], strides in elements and > 0: series-major maps [S][x][y][z] have voxel stride 1 and series
+ * stride nvox, voxel-major echo data [x][y][z][S] voxel stride S and series stride 1; both are read and written in place.
+ * Transform.  A [12] on the HOST, row-major 3 x 4, finite: destination voxel (i, j, k) lies at the continuous source coordinates
+ *     c_a = ((A[a][3] + A[a][0] i) + A[a][1] j) + A[a][2] k,   a = x, y, z   (four roundings after the three products; i, j, k as doubles)
+ *   Inside.  The voxel is inside when 0 <= c_a <= n_a - 1 on all three axes (a NaN coordinate is outside).  An outside voxel gets cval in
+ *     every series (the fill label for labels) and inside = 0; nothing is extrapolated.  inside [mx][my][mz] uint8 may be NULL.
+ *   Order 0.  The sample at floor(c_a + 0.5) per axis.
+ *   Order 1.  f = floor(c), t = c - f (exact), weights w = (1 - t, t) for the taps f, f + 1 per axis;
+ *     out = sum_p sum_q sum_r ((wx_p wy_q) wz_r) v[p][q][r], p outermost, each ascending, starting from the first term.
+ *   Order 3.  The cubic B-spline on the coefficients of the prefilter below: taps f - 1 .. f + 2, weights, with u = 1 - t,
+ *     (u u u / 6, ((3 t - 6) t t + 4) / 6, ((3 u - 6) u u + 4) / 6, t t t / 6); the 64 terms are added in the nesting of order 1.
+ *   Taps off the line.  A tap m outside 0 .. n - 1 is mirrored about the end samples (whole-sample symmetric): m mod 2 (n - 1), and
+ *     2 (n - 1) minus that where it exceeds n - 1; for n = 1 every tap is sample 0.  (Only orders 1 and 3 have such taps, and only next to a face.)
+ *   Prefilter (order 3), per axis in the order x, y, z, every line of n > 1 samples on its own, a line of one sample left as it is:
+ *     z1 = sqrt(3) - 2, lambda = (1 - z1)(1 - 1 / z1), zn = z1^(n - 1) (pow on the host); x_i = lambda s_i;
+ *     c_0 = x_0 + zn x_(n-1); for i = 1 .. n - 2, p = z1^i by repeated multiplication: c_0 += p (x_i + zn x_(n-1-i)); c_0 /= 1 - zn zn
+ *       (the sum over the mirrored, periodic line, exact: nothing is truncated);
+ *     c_i = x_i + z1 c_(i-1), i = 1 .. n - 1;   c_(n-1) = (z1 c_(n-2) + c_(n-1)) z1 / (z1 z1 - 1);   c_i = z1 (c_(i+1) - c_i), i = n - 2 .. 0.
+ *     This is Unser's recursive filter (IEEE TSP 41:821-848, 1993) as scipy.ndimage.spline_filter(mode='mirror') runs it.
+ * Entries.  DEVICE pointers except A.
+ *   met2_resample            order 0, 1 or 3.  For order 3 the coefficient volumes of a chunk of series live in a device block of at most
+ *                            max_work_bytes (0: the default) that the entry allocates and frees; the series go through a chunk at a time,
+ *                            and every (voxel, series) gets the same bits whatever the chunking.  BLOCKING for order 3; orders 0 and 1
+ *                            allocate nothing and are asynchronous on `stream`.
+ *   met2_resample_work_bytes (host only) min_bytes = one series' coefficients, 8 nx ny nz; default_bytes = all series', capped at 2^30 bytes
+ *                            but never below min_bytes; both 0 for orders 0 and 1.
+ *   met2_resample_labels     int32 labels, order 0, fill where outside.  Asynchronous on `stream`.
+ *   met2_resample_prefilter  the stage entry: coef [n_series][nx][ny][nz] = the prefilter of every series, nothing else.  Asynchronous.
+ * Limits.  Source axes 1 .. MET2_RESAMPLE_MAX_AXIS, destination axes >= 1 with at most 2^31 - 1 voxels in all, 1 <= n_series <=
+ * MET2_RESAMPLE_MAX_SERIES (MET2_E_UNSUPPORTED beyond the upper ends).  MET2_E_INVALID: an axis or n_series < 1, an order other than 0, 1, 3,
+ * a stride < 1, destination strides under which two (voxel, series) pairs share an element (neither dst_series_stride >= nvox
+ * dst_voxel_stride nor dst_voxel_stride >= n_series dst_series_stride), a NULL required pointer, dst == src, an entry of A that is not
+ * finite, max_work_bytes < 0 or (order 3) > 0 and below min_bytes.  Every check comes before any device work: the outputs are then untouched.
+ * Deterministic: no atomics, one thread per output element. */
+#define MET2_RESAMPLE_MAX_AXIS 512
+#define MET2_RESAMPLE_MAX_SERIES 32768
+int met2_resample(int32_t device, int32_t order, const int32_t src_dims[3], int32_t n_series, const double *src, int64_t src_voxel_stride,
+                  int64_t src_series_stride, const int32_t dst_dims[3], const double A[12], double cval, double *dst, int64_t dst_voxel_stride,
+                  int64_t dst_series_stride, uint8_t *inside, int64_t max_work_bytes, void *stream);
+int met2_resample_work_bytes(int32_t order, const int32_t src_dims[3], int32_t n_series, int64_t *min_bytes, int64_t *default_bytes);
+int met2_resample_labels(int32_t device, const int32_t src_dims[3], const int32_t *labels, const int32_t dst_dims[3], const double A[12],
+                         int32_t fill, int32_t *out, uint8_t *inside, void *stream);
+int met2_resample_prefilter(int32_t device, const int32_t src_dims[3], int32_t n_series, const double *src, int64_t src_voxel_stride,
+                            int64_t src_series_stride, double *coef, void *stream);
+
 /* Brain extraction (brain_mask='yes'; an extension: the reference's example pipeline makes the mask on the CPU, with FSL's
  * `fslmaths -Tmean` and `bet -m -f 0.4`, example_script_run_MET2_preproc_and_recon.sh step 3).  The surface model of Smith, Fast robust
  * automated brain extraction, HBM 17:143-155, 2002 -- the model bet runs -- WITHOUT bet's self-intersection retry pass, its skull and

@@ -8,7 +8,7 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
                             dictionaries for 2-D multi-slice data (slice_profile=... of Met2Plan.build_dictionary_epg and the drivers)
   flip_angle_algorithms.py  compute_optimal_FA, fitting_slice_FA_brute_force
   motor.py                  create_Laplacian_matrix, fitting_slice_T2, the drivers: recon_met2_arrays (steps 1-4 on arrays; _resolve_run states what the options
-                            refuse and where they run), motor_recon_met2 (the on-disk contract), the ROI mode; re-exports the filters
+                            refuse and where they run), motor_recon_met2 (the on-disk contract), the ROI mode, motor_atlas_stats; re-exports the filters
   filters.py                the whole-volume filters, one C ABI call each: nesma_filter, mppca_filter (MP-PCA denoising, cubic or box window, optional overlapping-patch averaging: csrc/met2_mppca.hip),
                             gibbs_filter (Gibbs-ringing removal, degibbs='yes' and '3d': csrc/met2_gibbs.hip),
                             bias_field_filter (bias-field correction of the TWC map, bias_correct='yes': csrc/met2_bias.hip),
@@ -16,6 +16,8 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
                             tissue_segment_filter (tissue segmentation of the TWC map, segment='yes': csrc/met2_seg.hip),
                             partial_volume_filter (partial-volume tissue maps of the TWC map, segment='pve': csrc/met2_pve.hip),
                             label_stats_filter (per-tissue / per-ROI statistics of the maps and spectra, tissue_stats='yes': csrc/met2_stats.hip),
+                            resample_filter / resample_labels_filter (affine resampling onto another grid) and atlas_stats_filter (label_stats_filter for an
+                            atlas on a grid of its own): csrc/met2_resample.hip,
                             gaussian_smooth
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
   gibbs.py                  gibbs_tables / gibbs_split / gibbs_split3d / gibbs_lines: the stages of the Gibbs-ringing filter one by one (tests and diagnostics)
@@ -24,6 +26,8 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   seg.py                    seg_consts / seg_init / seg_icm / seg_posterior / seg_finish: the stages of the tissue segmentation one by one (tests and diagnostics)
   pve.py                    pve_moments / pve_consts / pve_energy / pve_icm / pve_finish: the stages of the partial-volume maps one by one (tests and diagnostics)
   stats.py                  label_index / label_moments / label_quantiles / label_stats: per-label n, mean, std and np.quantile-exact quantiles of any series (csrc/met2_stats.hip)
+  resample.py               resample / resample_labels / prefilter / work_bytes: the affine resampling's entries (csrc/met2_resample.hip), and the transform
+                            algebra in numpy: voxel_matrix, invert, from_flirt / to_flirt
   rician.py                 bias / step / invert: the kernels of the Rician noise-floor correction one by one (csrc/met2_rician.hip; Met2Plan.fit_rician and
                             noise_sigma, rician='iterative' | 'direct' of the drivers)
   mppca.py                  mppca_stages: the MP-PCA denoiser with what each of its steps leaves (tests and diagnostics)

@@ -1,6 +1,6 @@
 """The whole-volume filters of the drivers, each one call into the C ABI (one translation unit under csrc/ per filter): nesma_filter,
-mppca_filter (with mppca_window and mppca_work_bytes), gibbs_filter, brain_mask_filter, bias_field_filter, tissue_segment_filter, partial_volume_filter, label_stats_filter and
-gaussian_smooth.  All take numpy arrays (and return numpy) or CUDA tensors (and return tensors on the same device); motor.py's drivers
+mppca_filter (with mppca_window and mppca_work_bytes), gibbs_filter, brain_mask_filter, bias_field_filter, tissue_segment_filter, partial_volume_filter, label_stats_filter,
+resample_filter, resample_labels_filter, atlas_stats_filter and gaussian_smooth.  All take numpy arrays (and return numpy) or CUDA tensors (and return tensors on the same device); motor.py's drivers
 call them and re-export the names."""
 import numpy as np
 import torch
@@ -279,6 +279,46 @@ def label_stats_filter(res, labels, q=None, device=0):
         return {"labels": ids.cpu().numpy(), "quantities": STAT_QUANTITIES, "q": np.asarray(q), "n": st[:, :, 0], "mean": st[:, :, 1],
                 "std": st[:, :, 2], "quantiles": st[:, :, 3:], "spectrum_mean": sp[:, :, 1] / tot[:, None],
                 "spectrum_quantiles": sp[:, :, 3:] / tot[:, None, None], "T2s": np.asarray(res["T2s"])}
+
+def resample_filter(vol, A, shape, order=1, cval=0.0, device=0, return_inside=False, max_work_bytes=0, series_axis=-1):
+    """Affine resampling of a volume onto another grid (met2_resample in include/met2_hip.h states the algorithm:
+    scipy.ndimage.affine_transform(vol, A[:, :3], offset=A[:, 3], output_shape=shape, order=order, mode='constant', cval=cval), restated) on the
+    device: `vol` [nx,ny,nz], or 4-D -- [nx,ny,nz,S] as the drivers hold echo data and spectra (series_axis=-1), or [S,nx,ny,nz] as they hold
+    stacked maps (series_axis=0) --, every series through the same transform and read in place; `A` [3, 4] takes a voxel index of the grid
+    `shape` = (mx, my, mz) to continuous voxel coordinates of `vol` (resample.voxel_matrix makes it from two NIfTI affines).  order 0 is
+    nearest neighbour, 1 trilinear, 3 the cubic B-spline; voxels that fall outside `vol` get `cval`.  Nothing is smoothed: a map that goes onto
+    a coarser grid should pass gaussian_smooth first.  max_work_bytes bounds the work space of order 3 (resample.work_bytes gives the minimum;
+    0: the library's default); the result does not depend on it.
+    -> the resampled array in the layout of `vol`; return_inside=True: (array, inside [mx,my,mz] uint8, 1 where the voxel was interpolated).
+    numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    from . import resample
+    if series_axis not in (-1, 0, 3):
+        raise ValueError("series_axis must be -1 ([nx,ny,nz,S]) or 0 ([S,nx,ny,nz])")
+    return resample.resample(vol, A, shape, order=order, cval=cval, layout="series" if series_axis == 0 else "voxel", device=device,
+                             return_inside=return_inside, max_work_bytes=max_work_bytes)
+
+
+def resample_labels_filter(labels, A, shape, fill=0, device=0):
+    """An integer label volume (an atlas ROI image, a parcellation) onto the grid `shape` through `A` (see resample_filter), nearest neighbour
+    (met2_resample_labels); `fill` where a voxel falls outside the label image.  -> int32 [mx,my,mz].  numpy in -> numpy out, CUDA tensor in
+    -> tensor out."""
+    from . import resample
+    return resample.resample_labels(labels, A, shape, fill=fill, device=device)
+
+
+def atlas_stats_filter(res, labels, labels_affine, affine, world=None, q=None, device=0):
+    """label_stats_filter for a label image that does not lie on the grid of the maps: `labels` [lx,ly,lz] integers with the voxel-to-world
+    affine `labels_affine`, `affine` the maps' own (both as nifti.load gives them), `world` [4, 4] taking the maps' world mm to the label
+    image's (None: both share scanner space; resample.from_flirt reads a FLIRT matrix).  The labels are resampled onto the maps' grid
+    (resample_labels_filter, nearest neighbour, 0 outside) and the statistics taken there.
+    -> the dict of label_stats_filter plus labels_resampled [nx,ny,nz] int32."""
+    from . import resample
+    A = resample.voxel_matrix(affine, labels_affine, world)
+    lab = resample_labels_filter(labels, A, tuple(np.shape(res["MWF"])), fill=0, device=device)
+    out = label_stats_filter(res, lab, q=q, device=device)
+    out["labels_resampled"] = lab.cpu().numpy() if torch.is_tensor(lab) else lab
+    return out
+
 
 def gaussian_smooth(data, sigma=2.0, truncate=4.0, device=0):
     """The Gaussian pre-smoothing of the FA step (motor:337-343): every echo volume of data [nx,ny,nz,nt] through the

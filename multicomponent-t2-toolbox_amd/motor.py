@@ -1,5 +1,6 @@
 """Drop-ins for motor/motor_recon_met2_real_data.py: create_Laplacian_matrix, fitting_slice_T2, recon_met2_arrays (the driver's steps 1-4
-on in-memory arrays), motor_recon_met2 (the same with the on-disk contract) and the ROI mode (recon_met2_rois, motor_recon_met2_ROIs).
+on in-memory arrays), motor_recon_met2 (the same with the on-disk contract), the ROI mode (recon_met2_rois, motor_recon_met2_ROIs) and the
+atlas statistics of written maps (motor_atlas_stats).
 The whole-volume filters the drivers call (nesma_filter ... gaussian_smooth) are filters.py's, re-exported here; the drivers reach them
 through this module's names.  Plots and the mean-spectrum PNG are not reproduced."""
 import collections
@@ -11,8 +12,9 @@ import torch
 from ._cache import plan_for
 from ._lib import check, lib
 from .evaluate import study_t2_grid
-from .filters import (STAT_KEYS, STAT_QUANTITIES, bias_field_filter, brain_mask_filter, gaussian_smooth, gibbs_filter,  # noqa: F401
-                      label_stats_filter, mppca_filter, nesma_filter, partial_volume_filter, tissue_segment_filter)
+from .filters import (STAT_KEYS, STAT_QUANTITIES, atlas_stats_filter, bias_field_filter, brain_mask_filter, gaussian_smooth,  # noqa: F401
+                      gibbs_filter, label_stats_filter, mppca_filter, nesma_filter, partial_volume_filter, resample_filter,
+                      resample_labels_filter, tissue_segment_filter)
 from .plan import BOOT_QUANTITIES, BOOT_STATS, MAP_NAMES, Met2Plan
 
 
@@ -836,6 +838,65 @@ _OUTPUT_FILES = (
     + tuple(_file(k) for k in ("MWF", "IEWF", "FWF", "T2_M", "T2_IE", "TWC", "FA", "fsol_4D", "Est_Signal", "reg_param"))
     + tuple(_file(q + "_bootstrap") for q in BOOT_QUANTITIES)
     + (_file("FA_bootstrap"), _file("fsol_bootstrap", "fsol_bootstrap_%s", axis=-1, names=BOOT_STATS)))
+
+
+def roi_stats_tables(st, names=None):
+    """the two tables motor_atlas_stats writes from the dict of atlas_stats_filter, in the layout of tissue_stats_tables -> (stats
+    [(L + 1) * 8, 5 + n_q] of objects: label, quantity, n, mean, std, q...; spectra [1 + (L + 1), n_t2] of floats: T2s, then per label the
+    normalised mean spectrum); the last label, 'all', is every voxel that carries a label, where st['all'] is given.  `names` maps a label
+    value to the name that stands in the label column (a dict, or a sequence indexed by label value); other labels keep their number.
+    There is no mean-signal spectrum row: the echo data are not read."""
+    def name_of(x):
+        x = int(x)
+        if isinstance(names, dict):
+            return str(names.get(x, x))
+        return str(names[x]) if names is not None and 0 <= x < len(names) else str(x)
+
+    labels = [name_of(x) for x in st["labels"]] + (["all"] if "all" in st else [])
+    rows, spectra = [], [np.asarray(st["T2s"], dtype=np.float64)]
+    for i, name in enumerate(labels):
+        src = st["all"] if i == len(st["labels"]) else {k: st[k][i] for k in STAT_KEYS}
+        for j, quantity in enumerate(st["quantities"]):
+            rows.append([name, quantity, src["n"][j], src["mean"][j], src["std"][j]] + list(src["quantiles"][j]))
+        spectra.append(src["spectrum_mean"])
+    return np.array(rows, dtype=object), np.array(spectra, dtype=np.float64)
+
+
+def motor_atlas_stats(path_to_save_data, path_to_labels, path_to_world=None, names=None):
+    """Per-ROI statistics of the maps motor_recon_met2 wrote at path_to_save_data (MWF ... reg_param and fsol_4D .nii.gz, found through
+    _OUTPUT_FILES' naming), for an atlas or parcellation image that lies on a grid of its own: path_to_labels is its NIfTI, whose affine places it
+    in world space; path_to_world an optional plain-text 4 x 4 matrix (np.loadtxt) taking the maps' world mm to the label image's (None: both
+    share scanner space; resample.from_flirt turns a FLIRT matrix into one).  The labels go onto the maps' grid by nearest neighbour
+    (atlas_stats_filter) and are written as ROIs_resampled.nii.gz with the maps' affine; table_roi_stats.csv holds one row per (label,
+    quantity) -- label, quantity, n, mean, std and the quantiles 0.025 .. 0.975; the last label, 'all', is every labelled voxel --, and
+    table_roi_spectra.csv the T2 grid and per label the normalised mean spectrum (roi_stats_tables; `names` as there).  Runs on device 0.
+    -> the dict of atlas_stats_filter with 'all' added."""
+    from . import nifti
+    stems = {key: stem for key, stem, _, _, _ in _OUTPUT_FILES}
+    res, affine = {}, None
+    for key in STAT_QUANTITIES + ("fsol_4D",):
+        img = nifti.load(path_to_save_data + stems[key] + ".nii.gz")
+        res[key] = img.get_fdata()
+        affine = img.affine if affine is None else affine
+    if res["fsol_4D"].ndim != 4 or any(res[k].shape != res["fsol_4D"].shape[:3] for k in STAT_QUANTITIES):
+        raise ValueError("the maps at path_to_save_data do not share one grid")
+    res["T2s"] = study_t2_grid(res["fsol_4D"].shape[-1])
+    lab_img = nifti.load(path_to_labels)
+    labels = lab_img.get_fdata()
+    if labels.ndim != 3 or not np.array_equal(labels, np.round(labels)):
+        raise ValueError("the label image must be a 3-D volume of integers")
+    world = None if path_to_world is None else np.loadtxt(path_to_world, dtype=np.float64)
+    if world is not None and world.shape != (4, 4):
+        raise ValueError("path_to_world must hold a 4 x 4 matrix")
+    st = atlas_stats_filter(res, labels.astype(np.int64), lab_img.affine, affine, world=world)
+    lab = st["labels_resampled"]
+    al = label_stats_filter(res, (lab > 0).astype(np.int32), q=st["q"])
+    st["all"] = {k: al[k][0] for k in STAT_KEYS}
+    nifti.save(nifti.NiftiImage(lab, affine), path_to_save_data + "ROIs_resampled.nii.gz")
+    table, spectra = roi_stats_tables(st, names)
+    np.savetxt(path_to_save_data + "table_roi_stats.csv", table, delimiter=",", fmt="%s")
+    np.savetxt(path_to_save_data + "table_roi_spectra.csv", spectra, delimiter=",", fmt="%s")
+    return st
 
 
 def recon_met2_rois(data, rois, fa_index, Dic_3D, T2s, Laplac, factor=1.01, myelin_T2=40.0, device=0, plan=None):
