@@ -155,3 +155,50 @@ def transforms(dims, shape):
         "outside": np.column_stack([np.eye(3), np.array([-1000.0, 0.0, 0.0])]),
     }
     return out
+
+
+# ---------------------------------------------------------------- the cases of tests/test_gpu_resample_edges.py (and of its host checks)
+
+EDGE_N_SERIES = (4, 5, 31, 32, 33, 48, 60, 64, 65, 120)          # echo data holds 32 or 48 series, spectra 60 or 120
+EDGE_DIMS = ((9, 8, 7), (3, 4, 65))                               # 504 voxels: 7 voxel tiles of 64 and one of 56; a z line of the wave width plus one
+EDGE_TRANSFORMS = ("rotated", "half")
+GATHER_DIMS = ((2, 3, 4), (4, 4, 4), (5, 13, 1), (9, 8, 7))       # 24 voxels (one partial voxel tile), 64 (one full), 65 with nz = 1 (no z pass), 504
+CHUNK_SERIES = (33, 40)                                           # order-3 chunks of 120 series: 33 + 33 + 33 + 21 and 40 + 40 + 40
+STRIDE_N_SERIES = (5, 33)
+LONG_AXES = (("nz512", (2, 2, 512), (1, 4)), ("nx512", (512, 2, 2), (1, 4)), ("ny512", (2, 512, 2), (1, 4)),
+             ("nz125", (5, 13, 125), (1,)), ("nz126", (5, 13, 126), (1,)))
+LONG_TRANSFORMS = ("half", "scale")
+MIN_INSIDE = 200                                                  # inside voxels every resampling case must have (and one outside at least)
+
+GATHER_TILE_V, GATHER_TILE_S, Z_LDS_DOUBLES = 64, 32, 8064        # RS_TILE_V, RS_TILE_S, RS_Z_LDS_DOUBLES of met2_resample.hip
+
+
+def group_width(n_series):
+    """lanes per voxel of rs_group_kernel: min(64, the next power of two >= max(n_series, 4))"""
+    g = 4
+    while g < 64 and g < n_series:
+        g *= 2
+    return g
+
+
+def group_turns(n_series):
+    """turns of rs_group_kernel's loop over the series"""
+    return -(-n_series // group_width(n_series))
+
+
+def series_tiles(n_series):
+    """(series tiles of rs_gather_kernel<true>, series in the last one)"""
+    n = -(-n_series // GATHER_TILE_S)
+    return n, n_series - (n - 1) * GATHER_TILE_S
+
+
+def z_tiles(nz, lines):
+    """(lines of a tile of rs_prefilter_z_kernel, tiles, lines in the last one)"""
+    t = min(64, Z_LDS_DOUBLES // (nz | 1))
+    n = -(-lines // t)
+    return t, n, lines - (n - 1) * t
+
+
+def edge_volume(dims, n_series):
+    """the source of an edge case: the same values wherever the case is computed"""
+    return volume(np.random.default_rng(list(dims) + [n_series, 61]), dims, n_series)
