@@ -936,7 +936,7 @@ int met2_label_stats(int32_t device, int64_t nvox, const int32_t *label, int32_t
                      int64_t voxel_stride, int64_t series_stride, int32_t n_q, const double *q_host, double *out, void *stream);
 
 /* Affine resampling of volumes and label images (an extension; additive, ABI stays 6): what brings an atlas ROI image onto the grid of the
- * maps, or the maps into a template space, through a GIVEN transform; estimating the transform is not part of the library.  It is
+ * maps, or the maps into a template space, through a GIVEN transform (estimating one: met2_register_cost below scores candidates, register.py searches).  It is
  * scipy.ndimage.affine_transform(src, A[:, :3], offset=A[:, 3], output_shape=dst, mode='constant', cval=cval), restated; no plan: `device`
  * and `stream` only.  All arithmetic is fp64 and no product is fused into a sum: every operation below rounds once, in the order written.
  * Shapes.  The source grid is [nx][ny][nz] (src_dims), the destination grid [mx][my][mz] (dst_dims), both in C order, z fastest; series s
@@ -985,6 +985,64 @@ int met2_resample_labels(int32_t device, const int32_t src_dims[3], const int32_
                          int32_t fill, int32_t *out, uint8_t *inside, void *stream);
 int met2_resample_prefilter(int32_t device, const int32_t src_dims[3], int32_t n_series, const double *src, int64_t src_voxel_stride,
                             int64_t src_series_stride, double *coef, void *stream);
+
+/* The cost function of rigid / affine registration (an extension; additive, ABI stays 6): how well a MOVING volume, resampled through each of
+ * K candidate transforms, matches a FIXED volume -- all K in one launch.  The search that proposes the candidates is register.py's; the
+ * library only scores them.  No plan: `device` and `stream` only.  DEVICE pointers except the dims, the ranges and A.
+ * Sampling.  Candidate k is A[k][12] on the HOST, in the convention of met2_resample with the fixed grid [mx][my][mz] as the destination and
+ *   the moving grid [nx][ny][nz] as the source: fixed voxel (i, j, k) lies at c_a = ((A[a][3] + A[a][0] i) + A[a][1] j) + A[a][2] k, is
+ *   inside when 0 <= c_a <= n_a - 1 on all three axes, and its moving value y is met2_resample's order 1 there, mirrored taps and n = 1 axes
+ *   included, to the bit (the two share their device code).  fp64 throughout, no product fused into a sum.
+ * Bins.  fixed_bin [mx my mz] int32: 0 .. n_bins - 1, anything else (use -1) excludes the voxel -- this is how a mask enters.  Only the fixed
+ *   image is binned, once per image, by met2_register_index: the included voxels grouped by ascending bin, inside a bin by ascending voxel
+ *   index (met2_label_index), and cut into RUNS of MET2_REGISTER_RUN consecutive members of one bin, the last run of a bin shorter.
+ *   n_included is their number.  normcorr and leastsq take the same index; they read x = fixed[v] besides.
+ * Sums.  Per candidate, over the included voxels that are inside (n_inside of them), of d = y - cy and e = x - cx, where the shifts
+ *   cy = lo + (hi - lo) / 2 of moving_range = (lo, hi) and cx of fixed_range are fixed per call (the ranges are the caller's: the minimum and
+ *   maximum of the volumes, or any finite lo <= hi; a shift only moves where cancellation sets in, in exact arithmetic the cost is the same):
+ *   per run, slot t of the run's 256 (absent and outside members are zeros): within each group of 64 slots, for s = 32, 16, .., 1 slot t
+ *   takes slot t + s, then the four groups as (g0 + g1) + (g2 + g3); per bin, the runs r = l, l + 64, l + 128, ... of the bin are added in
+ *   ascending order for l = 0 .. 63, and the 64 chains go through the same group tree; over the bins, slot b of 256 (bins beyond n_bins are
+ *   zeros) through the tree of a run.  No floating-point atomics; the counts are integers.  A candidate's n_inside and cost therefore have the
+ *   same bits from call to call, whatever K is and wherever the candidate stands in A.
+ *   C(q, s, n) = max(q - s s / n, 0) is n times a variance from the shifted sums.
+ *   MET2_REGISTER_CORRATIO  per bin n_b, S_b = sum d, Q_b = sum d d; cost = min((sum_b C(Q_b, S_b, n_b)) / C(Q, S, n_inside), 1), the sum over
+ *                           the bins with n_b > 0 by the tree: sum_b n_b Var_b(y) / (n_inside Var(y)), the correlation ratio (Roche et al.,
+ *                           MICCAI 1998), flirt's default.  `fixed` and fixed_range may be NULL.
+ *   MET2_REGISTER_NORMCORR  1 - r r, r r = min(c c / (vx vy), 1) with c = Sde - Se Sd / n, vx = C(See, Se, n), vy = C(Sdd, Sd, n); not below 0.
+ *   MET2_REGISTER_LEASTSQ   (sum (x - y)(x - y)) / n_inside.  No shifts are taken; `fixed` is read, fixed_range may be NULL.  (moving_range is required for every
+ *                           kind: the zero-variance rule and the shift come from it.)
+ * Worst value.  A candidate with n_inside = 0 or n_inside < min_overlap n_included (as doubles, one product), or whose variance is zero where a
+ *   ratio needs one -- C(..) <= n_inside 1e-24 m m with m = max(|lo|, |hi|) of that volume's range: a constant volume interpolates to itself up
+ *   to rounding --, gets 1 (corratio, normcorr) or MET2_REGISTER_LEASTSQ_WORST (leastsq).  A cost is never NaN for finite volumes.
+ * Entries.
+ *   met2_register_limits      (host only) the five constants; any output may be NULL
+ *   met2_register_work_bytes  (host only) index_bytes = 4 (2 (n_bins + 1) + mx my mz); cost_bytes = 96 K + 44 K (ceil(mx my mz / 256) + n_bins):
+ *                             the transforms, and per (candidate, run) five sums and a count
+ *   met2_register_index       fills `index` (index_bytes at least; 4-byte aligned) from fixed_bin.  BLOCKS (met2_label_index does).
+ *   met2_register_cost        n_inside [K] int64 and cost [K] of the K candidates; `work` (cost_bytes at least, 8-byte aligned) is scratch that
+ *                             must not be shared by calls on different streams.  Asynchronous on `stream`: the transforms go to the head of `work` by a copy enqueued on `stream`, so A
+ *                             must stay valid and unchanged until the work this call enqueued has completed (wait for `stream`, or for
+ *                             an event recorded after the call), like every host array of an asynchronous entry.
+ * Limits.  Fixed and moving axes 1 .. MET2_REGISTER_MAX_AXIS, 1 <= n_bins <= MET2_REGISTER_MAX_BINS, 1 <= K <= MET2_REGISTER_MAX_K
+ * (MET2_E_UNSUPPORTED beyond the upper ends).  MET2_E_INVALID: an axis, n_bins or K < 1, an unknown kind, a NULL required pointer, a range
+ * that is not finite or has lo > hi, an entry of A that is not finite, min_overlap outside [0, 1] or NaN, a work space or index that is too
+ * small or misaligned.  Every check comes before any device work: the outputs are then untouched. */
+#define MET2_REGISTER_CORRATIO 0
+#define MET2_REGISTER_NORMCORR 1
+#define MET2_REGISTER_LEASTSQ 2
+#define MET2_REGISTER_RUN 256
+#define MET2_REGISTER_MAX_AXIS 512
+#define MET2_REGISTER_MAX_BINS 256
+#define MET2_REGISTER_MAX_K 256
+#define MET2_REGISTER_LEASTSQ_WORST 1.0e300
+int met2_register_limits(int32_t *run, int32_t *max_axis, int32_t *max_bins, int32_t *max_k, double *leastsq_worst);
+int met2_register_work_bytes(const int32_t fixed_dims[3], int32_t n_bins, int32_t K, int64_t *index_bytes, int64_t *cost_bytes);
+int met2_register_index(int32_t device, const int32_t fixed_dims[3], const int32_t *fixed_bin, int32_t n_bins, void *index, int64_t index_bytes,
+                        void *stream);
+int met2_register_cost(int32_t device, int32_t kind, const int32_t fixed_dims[3], int32_t n_bins, const void *index, const double *fixed,
+                       const double fixed_range[2], const int32_t moving_dims[3], const double *moving, const double moving_range[2], int32_t K,
+                       const double *A, double min_overlap, void *work, int64_t work_bytes, int64_t *n_inside, double *cost, void *stream);
 
 /* Brain extraction (brain_mask='yes'; an extension: the reference's example pipeline makes the mask on the CPU, with FSL's
  * `fslmaths -Tmean` and `bet -m -f 0.4`, example_script_run_MET2_preproc_and_recon.sh step 3).  The surface model of Smith, Fast robust

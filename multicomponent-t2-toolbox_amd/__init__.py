@@ -17,7 +17,8 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
                             partial_volume_filter (partial-volume tissue maps of the TWC map, segment='pve': csrc/met2_pve.hip),
                             label_stats_filter (per-tissue / per-ROI statistics of the maps and spectra, tissue_stats='yes': csrc/met2_stats.hip),
                             resample_filter / resample_labels_filter (affine resampling onto another grid) and atlas_stats_filter (label_stats_filter for an
-                            atlas on a grid of its own): csrc/met2_resample.hip,
+                            atlas on a grid of its own, with template=... after registering the atlas' template to the maps): csrc/met2_resample.hip,
+                            register_filter (rigid / affine registration of two volumes: register.py, csrc/met2_register.hip),
                             gaussian_smooth
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
   gibbs.py                  gibbs_tables / gibbs_split / gibbs_split3d / gibbs_lines: the stages of the Gibbs-ringing filter one by one (tests and diagnostics)
@@ -28,6 +29,9 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   stats.py                  label_index / label_moments / label_quantiles / label_stats: per-label n, mean, std and np.quantile-exact quantiles of any series (csrc/met2_stats.hip)
   resample.py               resample / resample_labels / prefilter / work_bytes: the affine resampling's entries (csrc/met2_resample.hip), and the transform
                             algebra in numpy: voxel_matrix, invert, from_flirt / to_flirt
+  register.py               register: the coarse-to-fine direction-set search for the world matrix that brings a moving volume onto a fixed one, dof 6 / 7 / 9 / 12,
+                            cost 'corratio' | 'normcorr' | 'leastsq'; prepare / cost: a batch of candidate transforms scored in one launch (csrc/met2_register.hip);
+                            params_to_world / world_to_params, pyramid, the intensity rule
   rician.py                 bias / step / invert: the kernels of the Rician noise-floor correction one by one (csrc/met2_rician.hip; Met2Plan.fit_rician and
                             noise_sigma, rician='iterative' | 'direct' of the drivers)
   mppca.py                  mppca_stages: the MP-PCA denoiser with what each of its steps leaves (tests and diagnostics)

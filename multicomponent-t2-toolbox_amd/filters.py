@@ -1,6 +1,6 @@
 """The whole-volume filters of the drivers, each one call into the C ABI (one translation unit under csrc/ per filter): nesma_filter,
 mppca_filter (with mppca_window and mppca_work_bytes), gibbs_filter, brain_mask_filter, bias_field_filter, tissue_segment_filter, partial_volume_filter, label_stats_filter,
-resample_filter, resample_labels_filter, atlas_stats_filter and gaussian_smooth.  All take numpy arrays (and return numpy) or CUDA tensors (and return tensors on the same device); motor.py's drivers
+resample_filter, resample_labels_filter, register_filter, atlas_stats_filter and gaussian_smooth.  All take numpy arrays (and return numpy) or CUDA tensors (and return tensors on the same device); motor.py's drivers
 call them and re-export the names."""
 import numpy as np
 import torch
@@ -306,17 +306,42 @@ def resample_labels_filter(labels, A, shape, fill=0, device=0):
     return resample.resample_labels(labels, A, shape, fill=fill, device=device)
 
 
-def atlas_stats_filter(res, labels, labels_affine, affine, world=None, q=None, device=0):
+def register_filter(fixed, fixed_affine, moving, moving_affine, **options):
+    """Rigid or affine registration of `moving` onto `fixed` (register.register states the search, met2_register_cost in include/met2_hip.h
+    the similarity measures, which run on the device): numpy volumes [nx,ny,nz] with their voxel-to-world affines, `options` those of
+    register.register (dof=6, cost='corratio', n_bins, scales_mm, init, search_deg, mask, min_overlap, xtol, ftol, max_sweeps, batch, device).
+    -> world [4, 4], fixed-world mm -> moving-world mm: what resample.voxel_matrix(fixed_affine, moving_affine, world) takes to bring
+    `moving`, or a label image that lies in its space, onto the grid of `fixed`."""
+    from . import register
+    return register.register(fixed, fixed_affine, moving, moving_affine, **options)["world"]
+
+
+def atlas_stats_filter(res, labels, labels_affine, affine, world=None, q=None, device=0, template=None, template_affine=None, register=None,
+                       reference=None):
     """label_stats_filter for a label image that does not lie on the grid of the maps: `labels` [lx,ly,lz] integers with the voxel-to-world
     affine `labels_affine`, `affine` the maps' own (both as nifti.load gives them), `world` [4, 4] taking the maps' world mm to the label
     image's (None: both share scanner space; resample.from_flirt reads a FLIRT matrix).  The labels are resampled onto the maps' grid
     (resample_labels_filter, nearest neighbour, 0 outside) and the statistics taken there.
-    -> the dict of label_stats_filter plus labels_resampled [nx,ny,nz] int32."""
+    template [tx,ty,tz]: an intensity image in the label image's world space (template_affine; None: labels_affine), the atlas' anatomical
+    image.  `world` is then estimated: the template is registered (register_filter, options `register`: a dict) to `reference`, a volume on the
+    maps' grid (None: res['TWC']).  A template together with a world matrix is refused.
+    -> the dict of label_stats_filter plus labels_resampled [nx,ny,nz] int32, and, with a template, world [4, 4]."""
     from . import resample
+    if template is None and (template_affine is not None or register is not None or reference is not None):
+        raise ValueError("template_affine, register and reference go with a template")
+    if template is not None:
+        if world is not None:
+            raise ValueError("give a template or a world matrix, not both")
+        ref = res["TWC"] if reference is None else reference
+        ref = ref.cpu().numpy() if torch.is_tensor(ref) else np.asarray(ref)
+        tpl = template.cpu().numpy() if torch.is_tensor(template) else np.asarray(template)
+        world = register_filter(ref, affine, tpl, labels_affine if template_affine is None else template_affine, **dict(register or {}, device=device))
     A = resample.voxel_matrix(affine, labels_affine, world)
     lab = resample_labels_filter(labels, A, tuple(np.shape(res["MWF"])), fill=0, device=device)
     out = label_stats_filter(res, lab, q=q, device=device)
     out["labels_resampled"] = lab.cpu().numpy() if torch.is_tensor(lab) else lab
+    if template is not None:
+        out["world"] = world
     return out
 
 

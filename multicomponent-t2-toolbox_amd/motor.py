@@ -13,8 +13,8 @@ from ._cache import plan_for
 from ._lib import check, lib
 from .evaluate import study_t2_grid
 from .filters import (STAT_KEYS, STAT_QUANTITIES, atlas_stats_filter, bias_field_filter, brain_mask_filter, gaussian_smooth,  # noqa: F401
-                      gibbs_filter, label_stats_filter, mppca_filter, nesma_filter, partial_volume_filter, resample_filter,
-                      resample_labels_filter, tissue_segment_filter)
+                      gibbs_filter, label_stats_filter, mppca_filter, nesma_filter, partial_volume_filter, register_filter,
+                      resample_filter, resample_labels_filter, tissue_segment_filter)
 from .plan import BOOT_QUANTITIES, BOOT_STATS, MAP_NAMES, Met2Plan
 
 
@@ -862,7 +862,7 @@ def roi_stats_tables(st, names=None):
     return np.array(rows, dtype=object), np.array(spectra, dtype=np.float64)
 
 
-def motor_atlas_stats(path_to_save_data, path_to_labels, path_to_world=None, names=None):
+def motor_atlas_stats(path_to_save_data, path_to_labels, path_to_world=None, names=None, path_to_template=None, register=None):
     """Per-ROI statistics of the maps motor_recon_met2 wrote at path_to_save_data (MWF ... reg_param and fsol_4D .nii.gz, found through
     _OUTPUT_FILES' naming), for an atlas or parcellation image that lies on a grid of its own: path_to_labels is its NIfTI, whose affine places it
     in world space; path_to_world an optional plain-text 4 x 4 matrix (np.loadtxt) taking the maps' world mm to the label image's (None: both
@@ -870,8 +870,18 @@ def motor_atlas_stats(path_to_save_data, path_to_labels, path_to_world=None, nam
     (atlas_stats_filter) and are written as ROIs_resampled.nii.gz with the maps' affine; table_roi_stats.csv holds one row per (label,
     quantity) -- label, quantity, n, mean, std and the quantiles 0.025 .. 0.975; the last label, 'all', is every labelled voxel --, and
     table_roi_spectra.csv the T2 grid and per label the normalised mean spectrum (roi_stats_tables; `names` as there).  Runs on device 0.
-    -> the dict of atlas_stats_filter with 'all' added."""
-    from . import nifti
+    path_to_template: the atlas' intensity image, a NIfTI in the label image's world space, instead of path_to_world (both: refused).  The world
+    matrix is then estimated: the template is registered (register_filter; `register`: a dict of its options) to the maps' reference volume,
+    Data_avg.nii.gz at path_to_save_data or, where that is absent, TWC.nii.gz.  template_to_maps_world.txt holds the matrix (np.savetxt; what
+    path_to_world reads), template_to_maps_flirt.mat its FLIRT form (resample.to_flirt: `flirt -in <template> -ref <reference> -applyxfm
+    -init` takes it), template_resampled.nii.gz the template on the maps' grid, trilinear, for a look.
+    -> the dict of atlas_stats_filter with 'all' added (and 'world' with a template)."""
+    import os
+    from . import nifti, resample
+    if path_to_template is not None and path_to_world is not None:
+        raise ValueError("give path_to_template or path_to_world, not both")
+    if path_to_template is None and register is not None:
+        raise ValueError("register goes with path_to_template")
     stems = {key: stem for key, stem, _, _, _ in _OUTPUT_FILES}
     res, affine = {}, None
     for key in STAT_QUANTITIES + ("fsol_4D",):
@@ -888,7 +898,23 @@ def motor_atlas_stats(path_to_save_data, path_to_labels, path_to_world=None, nam
     world = None if path_to_world is None else np.loadtxt(path_to_world, dtype=np.float64)
     if world is not None and world.shape != (4, 4):
         raise ValueError("path_to_world must hold a 4 x 4 matrix")
+    if path_to_template is not None:
+        tpl = nifti.load(path_to_template)
+        template = tpl.get_fdata()
+        if template.ndim != 3:
+            raise ValueError("the template must be a 3-D volume")
+        ref_path = path_to_save_data + "Data_avg.nii.gz"
+        ref = nifti.load(ref_path if os.path.exists(ref_path) else path_to_save_data + stems["TWC"] + ".nii.gz").get_fdata()
+        if ref.shape != res["MWF"].shape:
+            raise ValueError("the reference volume does not lie on the grid of the maps")
+        world = register_filter(ref, affine, template, tpl.affine, **dict(register or {}))
+        np.savetxt(path_to_save_data + "template_to_maps_world.txt", world)
+        np.savetxt(path_to_save_data + "template_to_maps_flirt.mat", resample.to_flirt(world, tpl.affine, template.shape, affine, ref.shape))
+        on_maps = resample_filter(template, resample.voxel_matrix(affine, tpl.affine, world), ref.shape, order=1)
+        nifti.save(nifti.NiftiImage(on_maps, affine), path_to_save_data + "template_resampled.nii.gz")
     st = atlas_stats_filter(res, labels.astype(np.int64), lab_img.affine, affine, world=world)
+    if path_to_template is not None:
+        st["world"] = world
     lab = st["labels_resampled"]
     al = label_stats_filter(res, (lab > 0).astype(np.int32), q=st["q"])
     st["all"] = {k: al[k][0] for k in STAT_KEYS}

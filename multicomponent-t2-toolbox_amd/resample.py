@@ -5,7 +5,7 @@ and motor.atlas_stats_filter.
 
 A transform is `A` [3, 4]: destination voxel (i, j, k) lies at the continuous SOURCE voxel coordinates A[:, :3] @ (i, j, k) + A[:, 3].
 voxel_matrix makes it from the two images' voxel-to-world affines (nifti.py reads them) and an optional world-to-world matrix; from_flirt and
-to_flirt translate such a world matrix from and to FSL's FLIRT convention.  Estimating a transform is not part of the package.
+to_flirt translate such a world matrix from and to FSL's FLIRT convention.  register.py estimates one.
 
 The stage wrappers take `values` series-major [S, nx, ny, nz] (layout='series': maps) or voxel-major [nx, ny, nz, S] (layout='voxel': echo
 data, spectra), read in place, and return the same layout on the destination grid; a 3-D volume is one series.  numpy arrays in, numpy out;
