@@ -1,4 +1,5 @@
-// abi_common.hpp -- error plumbing and the environment switches shared by the translation units of libmet2_hip.so.
+// abi_common.hpp -- error plumbing and the environment switches shared by the translation units of libmet2_hip.so.  (The plan and the
+// hidden functions that cross units: plan.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // fit_kernel.hpp -- the per-voxel fit kernel (motor:113-162 + motor:443-472) and what it is made of: the lambda searches (scipy's bounded Brent
 // restated, with the tie guard), the L-curve corner, the metrics epilogue, the plan-level seed and factor-table kernels, and the launcher
-// template.  Shared by the translation units of libmet2_hip.so: met2_hip.hip holds the C ABI and every other kernel; with -DMET2_SPLIT_TU
+// template.  Shared by met2_hip.hip (the plan, the sort, fit_impl and the FA walk) and met2_fit_*.hip: with -DMET2_SPLIT_TU
 // (the shipped build) the fit kernels are instantiated in met2_fit_*.hip, one family of methods per file, so that they compile side by side
 // (one translation unit took 100 s); without it (development builds: -DMET2_ONLY, -DMET2_CYCSTATS ...) met2_hip.hip instantiates them all.
 #pragma once
@@ -10,6 +10,9 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "plan.hpp"
+#include "brent.hpp"
+#include "metrics.hpp"
 #include "nnls_wave.hpp"
 #include "objectives.hpp"
 
@@ -31,9 +34,6 @@ struct SortBufs {
 // ------------------------------------------------------------------------------------------
 // fit kernel
 // ------------------------------------------------------------------------------------------
-#ifndef MET2_BAYES_TABLE
-#define MET2_BAYES_TABLE 10               // shared Brent abscissae with plan-level factors (0 disables the tables)
-#endif
 // Internal kernel variant of MET2_GCV (not part of the ABI): the trace from the 17 x 17 form in the plan's low-rank basis (objectives.hpp,
 // gcv_basis_kernel); chosen by fit_impl when every flip angle's dictionary is of numerical rank <= 16.
 #define MET2_GCV_LR 6
@@ -88,9 +88,6 @@ struct FitArgs {
     unsigned long long *refac_count = nullptr;   // test switch MET2_REFAC_COUNT: the calls that took it are counted here
 };
 
-// The searches below run redundantly on all lanes, on wave-uniform doubles that the VALU computes into vector registers: eleven of them live across
-// every objective evaluation (a whole NNLS solve), 22 VGPRs of the solver's budget.  uni() moves such a value into a scalar register pair
-// (v_readfirstlane x 2); what the scalar file cannot hold the compiler keeps in the lanes of one VGPR (v_writelane), 64 scalars per register.
 // Per kernel (bit of MET2_UNI_MASK: X2 1 | 2, GCV 4 | 8, BayesReg 16 | 32 at one | two bins per lane): measured, the scalar copies cost the
 // two-bins-per-lane X2 and GCV kernels more in lane reads and writes than their (L2-resident) spills did.
 #ifndef MET2_UNI_MASK
@@ -102,96 +99,7 @@ constexpr bool uni_brent(int method, int nb)
     const int bit = base == MET2_X2 ? 0 : ((base == MET2_GCV || base == MET2_GCV_LR) ? 2 : (base == MET2_BAYESREG ? 4 : -1));
     return bit >= 0 && ((MET2_UNI_MASK >> (bit + (nb == 2 ? 1 : 0))) & 1);
 }
-template <bool PIN>
-__device__ __forceinline__ double uni(double v)
-{
-    if constexpr (PIN) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-    } else return v;
-}
-#define MET2_UNI_PIN() do { a = uni<PIN>(a); b = uni<PIN>(b); fulc = uni<PIN>(fulc); nfc = uni<PIN>(nfc); xf = uni<PIN>(xf); rat = uni<PIN>(rat); e = uni<PIN>(e); \
-                            x = uni<PIN>(x); fx = uni<PIN>(fx); ffulc = uni<PIN>(ffulc); fnfc = uni<PIN>(fnfc); } while (0)
-
-// SciPy's bounded Brent (scipy.optimize.fminbound, called at algorithms.py:219,280 and
-// bayesian_interpolation.py:101), restated; executed redundantly by all lanes on uniform values.
-// on_best() is called whenever the abscissa just evaluated becomes Brent's best point xf (the value fminbound returns): callers
-// keep the solver state of that evaluation and skip the solve scipy's callers repeat at the returned lambda.
-template <bool PIN, class F, class G>
-__device__ __forceinline__ double fminbound_dev(F &&fn, G &&on_best, double x1, double x2, double xatol, int maxfun, int &flag)
-{
-    const double sqrt_eps = sqrt(2.2e-16);
-    const double golden_mean = 0.5 * (3.0 - sqrt(5.0));
-    double a = x1, b = x2;
-    double fulc = a + golden_mean * (b - a);
-    double nfc = fulc, xf = fulc;
-    double rat = 0.0, e = 0.0;
-    double x = xf;
-    double fx = fn(x);
-    on_best();
-    int num = 1;
-    flag = 0;
-    double fu = INFINITY;
-    double ffulc = fx, fnfc = fx;
-    double xm = 0.5 * (a + b);
-    double tol1 = sqrt_eps * fabs(xf) + xatol / 3.0;
-    double tol2 = 2.0 * tol1;
-    while (fabs(xf - xm) > (tol2 - 0.5 * (b - a))) {
-        bool golden = true;
-        if (fabs(e) > tol1) {
-            golden = false;
-            double r = (xf - nfc) * (fx - ffulc);
-            double q = (xf - fulc) * (fx - fnfc);
-            double p = (xf - fulc) * q - (xf - nfc) * r;
-            q = 2.0 * (q - r);
-            if (q > 0.0) p = -p;
-            q = fabs(q);
-            r = e;
-            e = rat;
-            if ((fabs(p) < fabs(0.5 * q * r)) && (p > q * (a - xf)) && (p < q * (b - xf))) {
-                rat = (p + 0.0) / q;
-                x = xf + rat;
-                if (((x - a) < tol2) || ((b - x) < tol2)) {
-                    double d = xm - xf;
-                    double si = (double)((d > 0.0) - (d < 0.0) + (d == 0.0));
-                    rat = tol1 * si;
-                }
-            } else golden = true;
-        }
-        if (golden) {
-            e = (xf >= xm) ? a - xf : b - xf;
-            rat = golden_mean * e;
-        }
-        double si = (double)((rat > 0.0) - (rat < 0.0) + (rat == 0.0));
-        double ar = fabs(rat);
-        x = xf + si * (ar > tol1 ? ar : tol1);
-        MET2_UNI_PIN();
-        fu = fn(x);
-        num++;
-        if (fu <= fx) {
-            if (x >= xf) a = xf; else b = xf;
-            fulc = nfc; ffulc = fnfc;
-            nfc = xf; fnfc = fx;
-            xf = x; fx = fu;
-            on_best();
-        } else {
-            if (x < xf) a = x; else b = x;
-            if ((fu <= fnfc) || (nfc == xf)) {
-                fulc = nfc; ffulc = fnfc;
-                nfc = x; fnfc = fu;
-            } else if ((fu <= ffulc) || (fulc == xf) || (fulc == nfc)) {
-                fulc = x; ffulc = fu;
-            }
-        }
-        xm = 0.5 * (a + b);
-        tol1 = sqrt_eps * fabs(xf) + xatol / 3.0;
-        tol2 = 2.0 * tol1;
-        if (num >= maxfun) { flag = 1; break; }
-    }
-    if (isnan(xf) || isnan(fx) || isnan(fu)) flag = 2;
-    return xf;
-}
+// uni<PIN>() and the search itself, fminbound_dev<PIN>: brent.hpp
 
 // X2: Brent's near-ties are decided on refined objective values (fminbound_tie_dev).  Measured on one MI355X (profiles/r04_tie_guard.txt):
 // the 13 voxels of tests/golden/golden_x2_failset.npz (HIP and the CPU checker disagree) -- HIP equals the REFERENCE in 9 instead of 4, as the
@@ -351,59 +259,6 @@ __device__ __forceinline__ int select_corner_dev(double le, double ln, int nl, i
     return first_lane(ballot(tie && (double)bestk == kmin));
 }
 
-// Per-lane constants of the metrics windows (motor:221-224, 444)
-template <int NB>
-struct MetricLanes {
-    double logt2[NB];
-    bool isM[NB], isIE[NB], isCSF[NB];
-};
-
-template <int NB>
-__device__ __forceinline__ void metric_lanes(MetricLanes<NB> &ml, const double *t2s, int n, double cut_m, double cut_ie, int lane)
-{
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int j = lane + 64 * b;
-        const double t2 = (j < n) ? t2s[j] : 1.0;
-        ml.logt2[b] = (j < n) ? log(t2) : 0.0;
-        ml.isM[b] = (j < n) && (t2 <= cut_m);
-        ml.isIE[b] = (j < n) && (t2 > cut_m) && (t2 <= cut_ie);
-        ml.isCSF[b] = (j < n) && (t2 >= cut_ie);
-    }
-}
-
-// motor:448-468 for one voxel held bin-indexed in xs (already un-normalised); lane 0 writes the six maps
-template <int NB>
-__device__ __forceinline__ void write_metrics(const MetricLanes<NB> &ml, const double (&xs)[NB], bool mk, double *maps, int64_t nvox,
-                                              int64_t v, int lane)
-{
-    const double epsilon = 1.0e-16;
-    double tot = 0.0;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) tot += xs[b];
-    const double vt = wave_sum(tot) + epsilon;
-    double fm = 0.0, fie = 0.0, fcsf = 0.0, lm = 0.0, lie = 0.0;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const double xn = xs[b] / vt;
-        fm += ml.isM[b] ? xn : 0.0;
-        fie += ml.isIE[b] ? xn : 0.0;
-        fcsf += ml.isCSF[b] ? xn : 0.0;
-        lm += ml.isM[b] ? xn * ml.logt2[b] : 0.0;
-        lie += ml.isIE[b] ? xn * ml.logt2[b] : 0.0;
-    }
-    fcsf = wave_sum(fcsf);
-    wave_sum2(fm, fie);
-    wave_sum2(lm, lie);
-    if (lane == 0) {
-        maps[0 * nvox + v] = mk ? fm : 0.0;
-        maps[1 * nvox + v] = mk ? fie : 0.0;
-        maps[2 * nvox + v] = mk ? fcsf : 0.0;
-        maps[3 * nvox + v] = mk ? exp(lm / (fm + epsilon)) : 0.0;
-        maps[4 * nvox + v] = mk ? exp(lie / (fie + epsilon)) : 0.0;
-        maps[5 * nvox + v] = mk ? vt : 0.0;
-    }
-}
 
 template <int NB>
 __device__ __forceinline__ void load_band(Band<NB> &bd, const double *kband, const double *lband, int lane)

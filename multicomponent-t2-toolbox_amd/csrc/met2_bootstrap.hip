@@ -30,14 +30,9 @@
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
 #include "philox.hpp"
+#include "plan.hpp"
 #include "quantile.hpp"
 #include "wave_ops.hpp"
-
-namespace met2 {
-__attribute__((visibility("hidden"))) int plan_reserve(met2_plan *plan, int64_t nvox);      // the plan's per-voxel scratch (met2_hip.hip)
-__attribute__((visibility("hidden"))) bool fa_spline_attachment(met2_plan *plan, met2_plan **plan_lr, std::vector<double> *alpha_lr,
-                                                                std::vector<double> *alpha_hr);   // met2_host.hip
-}
 
 namespace {
 

@@ -18,11 +18,8 @@
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
 #include "philox.hpp"
+#include "plan.hpp"
 #include "wave_ops.hpp"
-
-namespace met2 {
-__attribute__((visibility("hidden"))) const double *plan_t2_grid(met2_plan *p);      // met2_hip.hip
-}
 
 namespace {
 
@@ -354,7 +351,7 @@ int plan_info(met2_plan *plan, int &nte, int &nt2, met2_options &o, const double
     if (rc) return rc;
     rc = met2_plan_get_options(plan, &o);
     if (rc) return rc;
-    t2s = met2::plan_t2_grid(plan);
+    t2s = plan->have_t2 ? plan->dT2 : nullptr;
     if (!t2s) return fail(MET2_E_STATE, "no T2 grid set");
     nte = a; nt2 = b;
     return MET2_OK;

@@ -1,23 +1,23 @@
-// met2_hip.hip -- gfx950 kernels and the C ABI of include/met2_hip.h.
+// met2_hip.hip -- the core of libmet2_hip.so: the plan, the sort, the fit and the brute-force flip-angle walk.
 //
+// Host code
+//   error plumbing (met2_last_error), options, the plan's lifecycle (struct met2_plan itself: plan.hpp), the lambda grid
+//   fit_geometry, fast_kmax, kernel_method, launch_*: the geometry and the instance of a fit launch
+//   ensure_seeds            the plan-level seeds and BayesReg factor tables (seed_kernel, bayes_table_kernel: fit_kernel.hpp)
+//   fit_impl                met2_fit / met2_fit_strided / met2_fit_enqueue_strided, met2_plan_finish
+//   met2_fa_bruteforce[_strided], the timing and launch-info getters
 // Kernels
-//   epg_dictionary_kernel   epg/epg.py:47-162      one wavefront per (T2, flip angle); the EPG
-//                                                  coherence orders live on the lanes, the
-//                                                  shift operator is a lane shuffle
-//   epg_profile_dictionary_kernel                  the same trains summed over a slice profile: one workgroup per
-//                                                  (T2, flip angle), its waves share the profile's points
-//   gram_kernel            B_fa = D_fa^T D_fa, D_fa^T   (once per plan)
-//   classify/scan/scatter   gates of motor:124,131 + counting sort of voxels by FA index, so that
+//   reset_sort / classify / scan / scatter   gates of motor:124,131 + counting sort of voxels by FA index, so that
 //                           neighbouring entries of the work list read the same D / B rows from L2
-//   fit_kernel<METHOD>      motor:113-162 + motor:443-472: one voxel per wavefront; every wave of the
+//   fit_kernel<METHOD>      (fit_kernel.hpp) motor:113-162 + motor:443-472: one voxel per wavefront; every wave of the
 //                           persistent workgroups pulls its own voxels from per-XCD queue cursors over
 //                           the FA-sorted list; D, D^T, B and K rows are read through L1/L2
-//   fa_kernel               fa_estimation.py:74-111: brute force over the plan's flip angles
-//   fa_spline_kernel        fa_estimation.py:54-59
-//   roi_reduce / roi_kernel motor_recon_met2_real_data_ROI.py:405-420: per-ROI mean signal and mean kernel
-//   nesma_kernel, smooth_axis_kernel   motor:305-343
 //   finalize_unfitted       zeros / all-zero-spectrum metrics for gated-out voxels
-//   metrics_kernel          motor:443-472 standalone
+//   fa_project_kernel, fa_kernel   fa_estimation.py:74-111: brute force over the plan's flip angles
+// The walk lives here because it shares fit_geometry and the sort buffers with the fit, needs the solver headers, and in
+// -DMET2_CYCSTATS builds reads the counters the fit writes (one copy per translation unit).
+// The dictionary and the penalty: met2_dictionary.hip.  NESMA, the smoother, the FA spline selection: met2_prefilter.hip.
+// The ROI reduction and the stand-alone metrics: met2_roi_metrics.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>
@@ -30,6 +30,7 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "plan.hpp"
 #include "nnls_wave.hpp"
 #include "objectives.hpp"
 #include "fit_kernel.hpp"
@@ -79,200 +80,8 @@ extern template int launch_fit_nb<6, 2, true>(const FitArgs &, const LaunchGeom 
 // ------------------------------------------------------------------------------------------
 // error plumbing
 // ------------------------------------------------------------------------------------------
-namespace met2 { __attribute__((visibility("hidden"))) void host_release(met2_plan *plan); }
-namespace met2 { __attribute__((visibility("hidden"))) void bootstrap_release(met2_plan *plan); }
 static thread_local std::string g_err;
 int met2::abi_fail(int code, const std::string &msg) { g_err = msg; return code; }
-
-// ------------------------------------------------------------------------------------------
-// EPG dictionary  (epg/epg.py:64-153).  Lane k holds order k: Fp = F_k (lane 0: F_0),
-// Fm = F_-k, Z = Z_k.  One inter-echo period = P T P, P = shift then relax over tau/2.
-// ------------------------------------------------------------------------------------------
-// One echo train on one wave: the state after the excitation (the reference's: sin(aexc) in F_0, cos(aexc) in F_-1) and the
-// constants of the refocusing pulse alpha (radians) and of the relaxation over tau/2.  Both dictionary kernels run this recursion.
-struct EpgTrain { double E2, E1, c2, s2, sa, ca, Fp, Fm, Z; };
-
-__device__ __forceinline__ EpgTrain epg_train_begin(int lane, double alpha, double aexc, double tau, double T2, double T1)
-{
-    EpgTrain t;
-    const double th = tau / 2.0;
-    const double R2 = 1.0 / T2, R1 = 1.0 / T1;
-    t.E2 = exp(-th * R2); t.E1 = exp(-th * R1);
-    const double ca2 = cos(alpha / 2.0), sa2 = sin(alpha / 2.0);
-    t.c2 = ca2 * ca2; t.s2 = sa2 * sa2; t.sa = sin(alpha); t.ca = cos(alpha);
-    t.Fp = (lane == 0) ? sin(aexc) : 0.0;
-    t.Fm = (lane == 1) ? cos(aexc) : 0.0;
-    t.Z = 0.0;
-    return t;
-}
-
-// one inter-echo period of an n-echo train; afterwards lane 0's Fp is the echo amplitude
-__device__ __forceinline__ void epg_train_period(EpgTrain &t, int lane, int n)
-{
-    for (int half = 0; half < 2; ++half) {
-        double up = gather(t.Fp, (lane + 63) & 63);   // F_{k-1}
-        double dn = gather(t.Fm, (lane + 1) & 63);    // F_-(k+1)
-        dn = (lane < n) ? dn : 0.0;                   // F_-n <- 0
-        t.Fp = (lane == 0) ? dn : up;                 // F_0 <- F_-1 ; F_k <- F_{k-1}
-        t.Fm = (lane == 0) ? 0.0 : dn;
-        t.Fp *= t.E2; t.Fm *= t.E2; t.Z *= t.E1;
-        if (lane > n) { t.Fp = 0.0; t.Fm = 0.0; t.Z = 0.0; }
-        if (half == 0 && lane >= 1) {
-            // c2 a + s2 b + sa z,  s2 a + c2 b - sa z,  -sa/2 a + sa/2 b + ca z: the fused multiply-adds are written out, in the grouping the
-            // dictionary kernel has always been compiled to, so that both kernels round alike and no compiler's choice of what to contract
-            // changes a dictionary
-            #pragma clang fp contract(off)
-            const double a = t.Fp, b = t.Fm, z = t.Z, hs = 0.5 * t.sa;
-            t.Fp = fma(t.sa, z, fma(t.c2, a, t.s2 * b));
-            t.Fm = fma(-t.sa, z, fma(t.s2, a, t.c2 * b));
-            t.Z = fma(t.ca, z, fma(hs, b, -(hs * a)));
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void epg_dictionary_kernel(int nte, int nt2, int nfa, const double *__restrict__ T2s,
-                                                             const double *__restrict__ T1s, double tau,
-                                                             const double *__restrict__ alpha_deg, double TR,
-                                                             double *__restrict__ D /* [nfa][nte][nt2] */)
-{
-    const int lane = lane_id();
-    const int gw = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    if (gw >= nfa * nt2) return;
-    const int fa = gw / nt2, j = gw - fa * nt2;
-    const double rad = M_PI / 180.0;
-    const double alpha = alpha_deg[fa] * rad, aexc = alpha_deg[fa] / 2.0 * rad;
-    EpgTrain t = epg_train_begin(lane, alpha, aexc, tau, T2s[j], T1s[j]);
-    const double scale = 1.0 - exp(-TR / T1s[j]);
-    for (int e = 0; e < nte; ++e) {
-        epg_train_period(t, lane, nte);
-        if (lane == 0) D[((size_t)fa * nte + e) * nt2 + j] = t.Fp * scale;
-    }
-}
-
-// The dictionary of a slice profile (met2_plan_build_dictionary_epg_profile): D[fa][e][j] = scale_j * sum_z w[z] H_z[e], H_z the train above
-// at the refocusing angle (a * r_ref[z]) and the excitation angle ((a / 2) * r_exc[z]).  One workgroup of four waves per (fa, t2) column:
-// wave v runs the points z = v, v + 4, ...; lane e keeps echo e (in lane 0 after each period), so a finished point is one row of the LDS tile
-// [n_z][64].  Then lanes e < nte of wave 0 sum their column over z in ascending order, product and sum rounded separately: the order is
-// part of the entry's definition and no launch geometry enters it.
-__global__ __launch_bounds__(256) void epg_profile_dictionary_kernel(int nte, int nt2, int nz, const double *__restrict__ T2s,
-                                                                     const double *__restrict__ T1s, double tau,
-                                                                     const double *__restrict__ alpha_deg, double TR,
-                                                                     const double *__restrict__ r_exc, const double *__restrict__ r_ref,
-                                                                     const double *__restrict__ w, double *__restrict__ D /* [nfa][nte][nt2] */)
-{
-    extern __shared__ double epg_tile[];                  // [nz][64]
-    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
-    const int fa = (int)blockIdx.x / nt2, j = (int)blockIdx.x - fa * nt2;
-    const double rad = M_PI / 180.0;
-    const double a = alpha_deg[fa], T2 = T2s[j], T1 = T1s[j];
-    for (int z = wave; z < nz; z += 4) {
-        const double alpha = (a * r_ref[z]) * rad, aexc = ((a / 2.0) * r_exc[z]) * rad;
-        EpgTrain t = epg_train_begin(lane, alpha, aexc, tau, T2, T1);
-        double keep = 0.0;
-        for (int e = 0; e < nte; ++e) {
-            epg_train_period(t, lane, nte);
-            const double h = bcast(t.Fp, 0);
-            keep = (lane == e) ? h : keep;
-        }
-        epg_tile[z * 64 + lane] = keep;
-    }
-    __syncthreads();
-    if (wave == 0 && lane < nte) {
-        #pragma clang fp contract(off)
-        double acc = 0.0;
-        for (int z = 0; z < nz; ++z) {
-            const double term = w[z] * epg_tile[z * 64 + lane];
-            acc = acc + term;
-        }
-        const double scale = 1.0 - exp(-TR / T1);
-        D[((size_t)fa * nte + lane) * nt2 + j] = acc * scale;
-    }
-}
-
-__global__ __launch_bounds__(256) void gram_kernel(int nte, int nt2, const double *__restrict__ D, double *__restrict__ B,
-                                                   double *__restrict__ Dt)
-{
-    const double *Df = D + (size_t)blockIdx.x * nte * nt2;
-    double *Bf = B + (size_t)blockIdx.x * nt2 * nt2;
-    double *Dtf = Dt + (size_t)blockIdx.x * nte * nt2;          // [t2][te]: the model signal D x reads columns of D
-    for (int idx = threadIdx.x; idx < nt2 * nte; idx += blockDim.x) {
-        int a = idx / nte, e = idx - a * nte;
-        Dtf[idx] = Df[e * nt2 + a];
-    }
-    for (int idx = threadIdx.x; idx < nt2 * nt2; idx += blockDim.x) {
-        int a = idx / nt2, b = idx - a * nt2;
-        double t = 0.0;
-        for (int e = 0; e < nte; ++e) t = fma(Df[e * nt2 + a], Df[e * nt2 + b], t);
-        Bf[idx] = t;
-    }
-}
-
-// reference layout [te][t2][fa]  <->  device layout [fa][te][t2]
-__global__ void relayout_kernel(int nte, int nt2, int nfa, const double *__restrict__ src, double *__restrict__ dst, int to_device)
-{
-    size_t total = (size_t)nte * nt2 * nfa;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        size_t f = i / ((size_t)nte * nt2), r = i - f * nte * nt2;     // i indexes [fa][te][t2]
-        size_t ref = r * nfa + f;
-        if (to_device) dst[i] = src[ref]; else dst[ref] = src[i];
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// GCV's low-rank basis (objectives.hpp, "Round 4"): per flip angle an orthonormal Q (m x 16) of the dominant column space of D by
-// pivoted Gram-Schmidt (the column of largest remaining norm, orthogonalised twice against the vectors found so far), then
-// A = Q^T D from the ORIGINAL dictionary, stored transposed ([bin][16]: a support bin's 16 coefficients are one 128-byte line).
-// res[fa] = largest remaining column norm / largest column norm: what the basis leaves of D.  One wave per flip angle; the
-// remainder R (m x n) lives in LDS, lane <-> column for the sweeps over columns, lane <-> echo for the basis vectors.
-// ------------------------------------------------------------------------------------------
-#define MET2_GCV_LR_TOL 1e-9
-__global__ __launch_bounds__(64) void gcv_basis_kernel(int m, int n, const double *__restrict__ D, double *__restrict__ Aq, double *__restrict__ Qt,
-                                                       double *__restrict__ res)
-{
-    extern __shared__ double basis_lds[];
-    double *R = basis_lds, *Q = basis_lds + (size_t)m * n;             // R[m][n], Q[16][64]
-    const int fa = blockIdx.x, lane = threadIdx.x;
-    const double *Df = D + (size_t)fa * m * n;
-    for (int i = lane; i < m * n; i += 64) R[i] = Df[i];
-    for (int i = lane; i < MET2_GCV_LR_RANK * 64; i += 64) Q[i] = 0.0;
-    __syncthreads();
-    auto colnorm2 = [&](int j) { double sum = 0.0; for (int e = 0; e < m; ++e) { const double v = R[e * n + j]; sum = fma(v, v, sum); } return sum; };
-    double nrm0 = 0.0;
-    for (int s = 0; s < MET2_GCV_LR_RANK; ++s) {
-        const double c0 = lane < n ? colnorm2(lane) : -1.0, c1 = lane + 64 < n ? colnorm2(lane + 64) : -1.0;
-        const double mx = wave_max(fmax(c0, c1));
-        if (s == 0) nrm0 = mx;
-        if (!(mx > nrm0 * 1e-30)) break;                                // nothing left above rounding: the dictionary has rank s
-        const u64 b0 = ballot(c0 == mx), b1 = ballot(c1 == mx);
-        const int piv = b0 ? first_lane(b0) : 64 + first_lane(b1);
-        double q = lane < m ? R[lane * n + piv] : 0.0;
-        for (int pass = 0; pass < 2; ++pass)
-            for (int t = 0; t < s; ++t) { const double qt = Q[t * 64 + lane]; const double d = wave_sum(q * qt); q = fma(-d, qt, q); }
-        q = q / sqrt(wave_sum(q * q));
-        Q[s * 64 + lane] = q;
-        __syncthreads();
-        for (int j = lane; j < n; j += 64) {                            // R -= q (q^T R)
-            double a = 0.0;
-            for (int e = 0; e < m; ++e) a = fma(Q[s * 64 + e], R[e * n + j], a);
-            for (int e = 0; e < m; ++e) R[e * n + j] = fma(-a, Q[s * 64 + e], R[e * n + j]);
-        }
-        __syncthreads();
-    }
-    {
-        const double c0 = lane < n ? colnorm2(lane) : -1.0, c1 = lane + 64 < n ? colnorm2(lane + 64) : -1.0;
-        const double mx = wave_max(fmax(c0, c1));
-        if (lane == 0) res[fa] = nrm0 > 0.0 ? sqrt(fmax(mx, 0.0) / nrm0) : 0.0;
-    }
-    for (int j = lane; j < n; j += 64)
-        for (int s = 0; s < MET2_GCV_LR_RANK; ++s) {
-            double a = 0.0;
-            for (int e = 0; e < m; ++e) a = fma(Q[s * 64 + e], Df[e * n + j], a);
-            Aq[((size_t)fa * n + j) * MET2_GCV_LR_RANK + s] = a;
-        }
-    // the basis itself, one vector per row ([fa][16][m]): the FA walk's lower bounds project the voxel's signal on it (fa_kernel)
-    for (int s = 0; s < MET2_GCV_LR_RANK; ++s)
-        if (lane < m) Qt[((size_t)fa * MET2_GCV_LR_RANK + s) * m + lane] = Q[s * 64 + lane];
-}
 
 // ------------------------------------------------------------------------------------------
 // voxel classification and counting sort by FA index
@@ -642,275 +451,6 @@ __global__ __launch_bounds__(64 * WAVES) void fa_kernel(FaArgs A)
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// spline flip-angle selection (flip_angle_algorithms/fa_estimation.py:54-59): cubic (not-a-knot)
-// interpolation of the coarse-grid NNLS residuals, bounded Brent over [90, 180] (scipy
-// minimize_scalar(method='Bounded'): xatol 1e-5, maxiter 500), snap to the fine FA grid.
-// One thread per voxel; the residuals come from fa_kernel on the coarse dictionary.
-// ------------------------------------------------------------------------------------------
-// NESMA filter (motor:305-333): every voxel with mask == 1 becomes the mean of the voxels of its
-// [x-6, x+6) x [y-6, y+6) x [z-6, z+6) window (clipped to the volume) whose relative L1 distance
-// 100 * sum|s_nb - s_c| / sum(s_c) is below 2.5 %.  One wave per output voxel, lane <-> echo; the
-// window is walked in batches of 8 neighbours: |s_nb - s_c| goes through the wave's LDS strip so
-// that lane group q (8 lanes) can sum neighbour q in the order of numpy's pairwise sum (8 running
-// sums, tree combine, tail in order), which keeps the 2.5 % test and the running mean bit-identical
-// to the reference's np.sum / np.mean.  The four waves of a workgroup take consecutive z, so their
-// windows overlap by 11/12 and the re-reads hit L1/L2.
-// ------------------------------------------------------------------------------------------
-#define MET2_NESMA_HW 6
-#define MET2_NESMA_MAX_NT 128
-struct NesmaArgs {
-    int nx, ny, nz, nt;
-    const double *data;       // [nx][ny][nz][nt]
-    const uint8_t *mask;      // [nx][ny][nz], filtered where == 1 (NULL = everywhere)
-    double *out;              // [nx][ny][nz][nt]
-    int64_t nvox;
-    int srow;                 // LDS row stride in doubles: >= nt, = 8 mod 32
-};
-
-// numpy pairwise sum of S[q][0..nt) for the lane's group q = lane / 8 (nt <= 128): valid on every lane of the group
-__device__ __forceinline__ double np_rowsum_group(const double *Sq, int nt, int j)
-{
-    double r;
-    if (nt < 8) {
-        r = 0.0;
-        for (int i = 0; i < nt; ++i) r += Sq[i];
-        return r;
-    }
-    const int n8 = nt - (nt & 7);
-    r = Sq[j];
-    for (int i = 8; i < n8; i += 8) r += Sq[i + j];
-    r = r + dpp_mov<0xB1>(r);       // r0+r1 | r2+r3 | ...
-    r = r + dpp_mov<0x4E>(r);       // (r0+r1)+(r2+r3) | (r4+r5)+(r6+r7)
-    r = r + dpp_mov<0x141>(r);      // both halves of the group
-    for (int i = n8; i < nt; ++i) r += Sq[i];
-    return r;
-}
-
-// RE < 2.5 with RE = fl(fl(100 S) / sumc), decided without the division whenever 100 S is clear of 2.5 sumc by
-// more than the rounding of both sides (the exact quotient is only formed for the voxels inside that band)
-struct NesmaTest {
-    double sumc, lo, hi;
-    bool fast;
-    __device__ __forceinline__ void init(double sc)
-    {
-        sumc = sc; fast = sc > 0.0 && sc < 1e300;
-        lo = 2.5 * sc * (1.0 - 1e-15); hi = 2.5 * sc * (1.0 + 1e-15);
-    }
-    __device__ __forceinline__ u64 similar(double S) const
-    {
-        const double t = 100.0 * S;
-        const bool yes = t < lo, no = !(t <= hi);
-        if (fast && ballot(!yes && !no) == 0ull) return ballot(yes);
-        return ballot(t / sumc < 2.5);
-    }
-};
-
-// the value the lane 32 above holds (v_permlane32_swap: upper half of one operand <-> lower half of the other)
-__device__ __forceinline__ double from_upper_half(double v)
-{
-    const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-    auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return __hiloint2double((int)b[1], (int)a[1]);
-}
-
-// One batch = the z-run of one (x, y) of the window: up to 12 neighbours that are contiguous in memory, so the
-// window walk is two nested loops with a pointer bump and the batch geometry (run length L) is fixed per voxel.
-// PACK = 1: lane <-> echo (NE echoes per lane), one neighbour per load.  PACK = 2 (nt <= 32): the two halves of the
-// wave load two consecutive neighbours at once; the running sum lives in the lower half and takes the odd neighbours
-// through v_permlane32_swap so that the additions keep the reference's order.  LDS rows are padded to a stride of
-// 8 mod 32 doubles, which spreads the 8 lane groups of a row-sum read over all banks.
-// NT > 0 fixes the echo count at compile time (row sums fully unrolled); NT = 0 reads it from the arguments.
-template <int NE, int PACK, int NT>
-__global__ __launch_bounds__(256) void nesma_kernel(NesmaArgs A)
-{
-    extern __shared__ double nesma_lds[];
-    constexpr int STEPS = 2 * MET2_NESMA_HW / PACK;
-    const int lane = lane_id(), w = (int)(threadIdx.x >> 6);
-    const int nt = NT > 0 ? NT : A.nt, SR = NT > 0 ? ((NT + 23) / 32) * 32 + 8 : A.srow;
-    double *S = nesma_lds + (size_t)w * 2 * MET2_NESMA_HW * SR;
-    // workgroups are dealt round-robin to the 8 XCDs: give XCD i the i-th contiguous eighth of the volume so that
-    // the windows its CUs walk at the same time overlap in its own L2
-    const unsigned nb = gridDim.x, per = (nb + 7u) / 8u;
-    const unsigned bid = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-    const int64_t v = (int64_t)bid * 4 + w;
-    if (bid >= nb || v >= A.nvox) return;                      // wave-uniform
-    const int h = PACK == 2 ? lane >> 5 : 0;
-    const int e0 = PACK == 2 ? (lane & 31) : lane, e1 = lane + 64;
-    const bool has0 = e0 < nt, has1 = NE > 1 && e1 < nt;
-    const bool writer = h == 0;
-    double *orow = A.out + v * nt;
-    if (A.mask && A.mask[v] != 1) {
-        if (has0 && writer) orow[e0] = 0.0;
-        if (has1) orow[e1] = 0.0;
-        return;
-    }
-    const int z = (int)(v % A.nz), y = (int)((v / A.nz) % A.ny), x = (int)(v / ((int64_t)A.nz * A.ny));
-    const int x0 = max(x - MET2_NESMA_HW, 0), x1 = min(x + MET2_NESMA_HW, A.nx);
-    const int y0 = max(y - MET2_NESMA_HW, 0), y1 = min(y + MET2_NESMA_HW, A.ny);
-    const int z0 = max(z - MET2_NESMA_HW, 0), z1 = min(z + MET2_NESMA_HW, A.nz);
-    const int L = z1 - z0;                                     // 1..12 neighbours per batch
-    const int q = lane >> 3, j = lane & 7;
-    const double *crow = A.data + v * nt;
-    const double c0 = has0 ? crow[e0] : 0.0, c1 = has1 ? crow[e1] : 0.0;
-    if (has0 && writer) S[e0] = c0;
-    if (has1) S[e1] = c1;
-    __builtin_amdgcn_wave_barrier();
-    NesmaTest T;
-    T.init(bcast(np_rowsum_group(S, nt, j), 0));
-    __builtin_amdgcn_wave_barrier();
-    const double *S0 = S + min(q, L - 1) * SR, *S1 = S + min(8 + (q & 3), L - 1) * SR;
-    const int64_t ystride = (int64_t)A.nz * nt, xstride = ystride * A.ny;
-    unsigned off0[STEPS], off1[STEPS];                         // the lane's element of each row of a run
-#pragma unroll
-    for (int t = 0; t < STEPS; ++t) {
-        const int r = min(PACK * t + h, L - 1);
-        off0[t] = (unsigned)(r * nt + min(e0, nt - 1));
-        off1[t] = (unsigned)(r * nt + min(e1, nt - 1));
-    }
-    u64 live0 = 0, live1 = 0;                                  // bit 8 r set for the rows a run has
-    for (int r = 0; r < L; ++r) { if (r < 8) live0 |= 1ull << (8 * r); else live1 |= 1ull << (8 * (r - 8)); }
-    double acc0 = 0.0, acc1 = 0.0;
-    int cnt = 0;
-    for (int i = x0; i < x1; ++i) {
-        const double *strip = A.data + i * xstride + y0 * ystride + (int64_t)z0 * nt;
-        for (int jj = y0; jj < y1; ++jj, strip += ystride) {
-            // all loads of the run first (rows past the run re-read its last row; they are never summed), then the
-            // |difference| rows into LDS
-            double nb0[STEPS], nb1[STEPS];
-#pragma unroll
-            for (int t = 0; t < STEPS; ++t) {
-                nb0[t] = strip[off0[t]];
-                nb1[t] = NE > 1 ? strip[off1[t]] : 0.0;
-            }
-#pragma unroll
-            for (int t = 0; t < STEPS; ++t) {
-                const int r = PACK * t + h;
-                if (has0) S[r * SR + e0] = fabs(nb0[t] - c0);
-                if (NE > 1 && has1) S[r * SR + e1] = fabs(nb1[t] - c1);
-            }
-            __builtin_amdgcn_wave_barrier();
-            const u64 ok0 = T.similar(np_rowsum_group(S0, nt, j));           // 8 identical bits per lane group
-            const u64 ok1 = L > 8 ? T.similar(np_rowsum_group(S1, nt, j)) : 0ull;
-            __builtin_amdgcn_wave_barrier();
-            const u64 v0 = ok0 & live0, v1 = ok1 & live1;                    // bit 8 r: neighbour r (8 + r) of the run is similar
-            cnt += __builtin_popcountll(v0) + __builtin_popcountll(v1);
-#pragma unroll
-            for (int t = 0; t < STEPS; ++t) {
-                if (PACK == 1) {
-                    if (((t < 8 ? v0 : v1) >> (8 * (t & 7))) & 1ull) { acc0 += nb0[t]; if (NE > 1) acc1 += nb1[t]; }
-                } else {
-                    const int ra = 2 * t, rb = 2 * t + 1;
-                    if (((ra < 8 ? v0 : v1) >> (8 * (ra & 7))) & 1ull) acc0 += nb0[t];
-                    if (((rb < 8 ? v0 : v1) >> (8 * (rb & 7))) & 1ull) acc0 += from_upper_half(nb0[t]);
-                }
-            }
-        }
-    }
-    const double dc = (double)cnt;                             // empty set -> 0/0 = nan, as np.mean of nothing
-    if (has0 && writer) orow[e0] = acc0 / dc;
-    if (has1) orow[e1] = acc1 / dc;
-}
-
-// ------------------------------------------------------------------------------------------
-// Gaussian pre-smoothing of the FA step (motor:337-343: scipy.ndimage.gaussian_filter(vol, 2.0) on every echo volume):
-// one separable pass per axis over the whole [nx][ny][nz][nt] array (nt innermost: all echoes at once, coalesced for
-// every axis), 'reflect' boundary, accumulation in the order of scipy's correlate1d for symmetric kernels (centre, then
-// the pairs from the outermost inwards) with separate multiply and add roundings, so the result is bit-identical.
-// ------------------------------------------------------------------------------------------
-#define MET2_SMOOTH_MAX_RADIUS 32
-struct SmoothArgs {
-    int n, radius;
-    int64_t stride, total;
-    const double *src;
-    double *dst;
-    double w[2 * MET2_SMOOTH_MAX_RADIUS + 1];
-};
-
-__device__ __forceinline__ int reflect_index_dev(int i, int n)
-{
-    if (n == 1) return 0;
-    const int period = 2 * n;
-    i %= period; if (i < 0) i += period;
-    return i < n ? i : period - 1 - i;
-}
-
-__global__ __launch_bounds__(256) void smooth_axis_kernel(SmoothArgs A)
-{
-#pragma clang fp contract(off)                                      // scipy's C loop rounds the product and the sum separately
-    const int r = A.radius, n = A.n;
-    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < A.total; idx += (int64_t)gridDim.x * blockDim.x) {
-        const int i = (int)((idx / A.stride) % n);
-        const double *base = A.src + (idx - (int64_t)i * A.stride);
-        double t = A.src[idx] * A.w[r];
-        if (i >= r && i + r < n) {                                  // interior: no reflection
-            for (int j = -r; j < 0; ++j) {
-                const double pr = (base[(int64_t)(i + j) * A.stride] + base[(int64_t)(i - j) * A.stride]) * A.w[j + r];
-                t = t + pr;
-            }
-        } else {
-            for (int j = -r; j < 0; ++j) {
-                const double pr = (base[(int64_t)reflect_index_dev(i + j, n) * A.stride] + base[(int64_t)reflect_index_dev(i - j, n) * A.stride]) * A.w[j + r];
-                t = t + pr;
-            }
-        }
-        A.dst[idx] = t;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-#define MET2_MAX_LR 32
-struct SplineArgs {
-    int nlr, nhr, nte;
-    const double *alpha_lr;   // [nlr] device
-    const double *W;          // [nlr][nlr] device: knot slopes = W y
-    const double *alpha_hr;   // [nhr] device
-    const double *resid;      // [nvox][nlr]
-    const double *data;       // echo e of voxel v at data[v * vs + e * es]
-    int64_t vs, es;
-    const uint8_t *mask;
-    double *fa_index, *xmin;
-    int64_t nvox;
-};
-
-__device__ __forceinline__ double spline_eval_dev(int n, const double *x, const double *y, const double *s, double xx)
-{
-    int i = 0;
-    while (i < n - 2 && xx >= x[i + 1]) ++i;
-    const double h = x[i + 1] - x[i], t = (xx - x[i]) / h;
-    const double h00 = (1.0 + 2.0 * t) * (1.0 - t) * (1.0 - t), h10 = t * (1.0 - t) * (1.0 - t);
-    const double h01 = t * t * (3.0 - 2.0 * t), h11 = t * t * (t - 1.0);
-    return h00 * y[i] + h10 * h * s[i] + h01 * y[i + 1] + h11 * h * s[i + 1];
-}
-
-__global__ __launch_bounds__(128) void fa_spline_kernel(SplineArgs A)
-{
-    __shared__ double sx[MET2_MAX_LR];
-    for (int i = threadIdx.x; i < A.nlr; i += blockDim.x) sx[i] = A.alpha_lr[i];
-    __syncthreads();
-    const int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (v >= A.nvox) return;
-    double sum = 0.0;
-    for (int e = 0; e < A.nte; ++e) sum += A.data[v * A.vs + e * A.es];
-    const bool mk = A.mask ? (A.mask[v] != 0) : true;
-    if (!(mk && sum > 0.0)) { A.fa_index[v] = 0.0; if (A.xmin) A.xmin[v] = 0.0; return; }
-    double y[MET2_MAX_LR], s[MET2_MAX_LR];
-    const int n = A.nlr;
-    for (int i = 0; i < n; ++i) y[i] = A.resid[(size_t)v * n + i];
-    for (int i = 0; i < n; ++i) {
-        double t = 0.0;
-        for (int j = 0; j < n; ++j) t = fma(A.W[i * n + j], y[j], t);
-        s[i] = t;
-    }
-    int flag;
-    const double xs = fminbound_dev<false>([&](double x) { return spline_eval_dev(n, sx, y, s, x); }, []() {}, 90.0, 180.0, 1e-5, 500, flag);
-    int best = 0; double dbest = fabs(A.alpha_hr[0] - xs);            // np.argmin(|alpha - x|): first minimum
-    for (int a = 1; a < A.nhr; ++a) { double d = fabs(A.alpha_hr[a] - xs); if (d < dbest) { dbest = d; best = a; } }
-    A.fa_index[v] = (double)best;
-    if (A.xmin) A.xmin[v] = xs;
-}
-
 // zeros for gated-out voxels (motor:115-117) and the metrics an all-zero spectrum gets at
 // motor:448-468 when mask > 0 (T2_M = T2_IE = exp(0) = 1, TWC = 1e-16)
 __global__ __launch_bounds__(256) void finalize_unfitted_kernel(int64_t nvox, int n, int m, const int *__restrict__ key,
@@ -935,174 +475,11 @@ __global__ __launch_bounds__(256) void finalize_unfitted_kernel(int64_t nvox, in
     }
 }
 
-// motor:443-472 standalone: one wavefront per voxel
-template <int NB>
-__global__ __launch_bounds__(256) void metrics_kernel(int64_t nvox, int n, const double *__restrict__ t2s, double cut_m, double cut_ie,
-                                                      const double *__restrict__ fsol, const uint8_t *__restrict__ mask,
-                                                      double *__restrict__ maps)
-{
-    const int lane = lane_id();
-    MetricLanes<NB> ml;
-    metric_lanes<NB>(ml, t2s, n, cut_m, cut_ie, lane);
-    const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t v = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; v < nvox; v += nw) {
-        const bool mk = mask ? (mask[v] != 0) : true;
-        double xs[NB];
-#pragma unroll
-        for (int b = 0; b < NB; ++b) xs[b] = (lane + 64 * b < n && mk) ? fsol[(size_t)v * n + lane + 64 * b] : 0.0;
-        write_metrics<NB>(ml, xs, mk, maps, nvox, v, lane);
-    }
-}
-
-
-// ------------------------------------------------------------------------------------------
-// ROI mode (motor/motor_recon_met2_real_data_ROI.py:405-420): per ROI the mean signal over its voxels and the mean
-// EPG kernel (every voxel contributes the dictionary slice of its own flip angle).  Deterministic two-level
-// reduction: a wave per (slice of the voxel list, ROI) accumulates the echoes of its matching voxels in voxel order
-// (lane <-> echo) and a flip-angle histogram; one workgroup per ROI then adds the slices in order and forms
-// mean kernel = sum_fa count[fa] D[fa] / nv.
-// ------------------------------------------------------------------------------------------
-struct RoiArgs {
-    int nte, nt2, nfa, nroi, nslice;
-    int64_t nvox, vs, es;
-    const double *data;
-    const int32_t *roi;        // [nvox] ROI ordinal 0..nroi-1, negative = none
-    const double *fa_index;    // [nvox] or NULL
-    double *part_sig;          // [nroi][nslice][64]
-    int *part_cnt;             // [nroi][nslice][nfa]
-    const double *Dsrc;        // [nfa][nte][nt2]
-    double *Ddst;              // [nroi][nte][nt2]
-    double *mean_sig;          // [nroi][nte]
-    double *count;             // [nroi] voxels per ROI
-    int *err;
-};
-
-__global__ __launch_bounds__(64) void roi_partial_kernel(RoiArgs A)
-{
-    extern __shared__ int roi_hist[];
-    const int lane = lane_id();
-    const int sl = (int)blockIdx.x, r = (int)blockIdx.y;
-    for (int f = lane; f < A.nfa; f += 64) roi_hist[f] = 0;
-    __builtin_amdgcn_wave_barrier();
-    const int64_t per = (A.nvox + A.nslice - 1) / A.nslice;
-    const int64_t lo = sl * per, hi = min(A.nvox, lo + per);
-    double acc = 0.0;
-    for (int64_t base = lo; base < hi; base += 64) {
-        const int64_t v = base + lane;
-        u64 hit = ballot(v < hi && A.roi[v] == r);
-        while (hit) {
-            const int bit = first_lane(hit);
-            hit &= hit - 1ull;
-            const int64_t vv = base + bit;
-            if (lane < A.nte) acc += A.data[vv * A.vs + lane * A.es];
-            const int fa = A.fa_index ? (int)A.fa_index[vv] : 0;
-            if (fa < 0 || fa >= A.nfa) { if (lane == 0) atomicOr(A.err, 1); }
-            else if (lane == 0) roi_hist[fa] += 1;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    A.part_sig[((size_t)r * A.nslice + sl) * 64 + lane] = acc;
-    for (int f = lane; f < A.nfa; f += 64) A.part_cnt[((size_t)r * A.nslice + sl) * A.nfa + f] = roi_hist[f];
-}
-
-__global__ __launch_bounds__(256) void roi_finish_kernel(RoiArgs A)
-{
-    extern __shared__ int roi_tot[];           // [nfa]
-    __shared__ double s_nv;
-    const int r = (int)blockIdx.x;
-    for (int f = threadIdx.x; f < A.nfa; f += blockDim.x) {
-        int c = 0;
-        for (int sl = 0; sl < A.nslice; ++sl) c += A.part_cnt[((size_t)r * A.nslice + sl) * A.nfa + f];
-        roi_tot[f] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long nv = 0;
-        for (int f = 0; f < A.nfa; ++f) nv += roi_tot[f];
-        s_nv = (double)nv;
-        A.count[r] = (double)nv;
-    }
-    __syncthreads();
-    const double nv = s_nv;
-    if ((int)threadIdx.x < A.nte) {
-        double t = 0.0;
-        for (int sl = 0; sl < A.nslice; ++sl) t += A.part_sig[((size_t)r * A.nslice + sl) * 64 + threadIdx.x];
-        A.mean_sig[(size_t)r * A.nte + threadIdx.x] = t / nv;
-    }
-    const int sz = A.nte * A.nt2;
-    for (int i = threadIdx.x; i < sz; i += blockDim.x) {
-        double t = 0.0;
-        for (int f = 0; f < A.nfa; ++f) { const int c = roi_tot[f]; if (c) t = fma((double)c, A.Dsrc[(size_t)f * sz + i], t); }
-        A.Ddst[(size_t)r * sz + i] = t / nv;
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // plan
 // ------------------------------------------------------------------------------------------
 // re-factorisations that took the packed leg of refactor_rowwise, counted by fits under the test switch MET2_REFAC_COUNT (met2_refac_packed_calls)
 __device__ unsigned long long g_refac_packed_calls;
-
-struct met2_plan {
-    int n_te, n_t2, n_fa;
-    met2_options opt;
-    int cus;
-    double *dD = nullptr;       // [nfa][nte][nt2]
-    double *dB = nullptr;       // [nfa][nt2][nt2]
-    double *dKband = nullptr;   // [5][64]
-    double *dLband = nullptr;   // [5][64]
-    double *dDt = nullptr;      // [n_fa][n_t2][n_te] transposed dictionary
-    double *dKd = nullptr;      // [n_t2][n_t2] dense L^T L (row loads of the warm-start refactorisation)
-    double *dLam = nullptr;     // [nlam]
-    double *dT2 = nullptr;      // [nt2]
-    int nlam = 0;
-    bool have_dict = false, have_pen = false, have_t2 = false;
-    std::vector<double> Lhost;  // dense penalty as given
-    double log_detL = 0.0;      // log(det(L)) as bayesian_interpolation.py:100,123 uses it (-inf for L2)
-    // sort buffers (grown on demand)
-    int64_t cap_vox = 0;
-    int *dKey = nullptr, *dPerm = nullptr, *dSmall = nullptr, *dOvf = nullptr;      // dSmall: hist|cursor|bucket_start|chunk_start|queue|err
-    char *dSeed = nullptr;                                // seed_kernel's output: [4][nfa] SeedRec
-    bool seeds_valid = false; double seeds_key[7] = {0};  // (t2sparc_lambda and the six interval ends the seeds and tables were built for)
-    bool seeds_ok = false;                                // B + lambda K is positive definite at the seed lambdas (checked on the host for
-                                                          // flip angle 0): only then is the seeded start the cold start's solution
-    double *dH = nullptr; int64_t cap_h = 0;              // FA walk: h of every flip angle for one pass of voxels (fa_project_kernel), grown on demand
-    double *dBtab = nullptr; int btab_stride = 0;         // BayesReg factor tables [nfa][MET2_BAYES_TABLE][btab_stride] (built with the seeds)
-    double *dQt = nullptr;                                // [nfa][16][n_te]: the basis vectors themselves (lower bounds of the brute-force FA search)
-    double *dAq = nullptr, *dAqRes = nullptr;             // GCV: [nfa][n_t2][16] = (Q^T D)^T in the flip angle's low-rank basis, [nfa] what the basis leaves of D
-    double gcv_res = 0.0;                                 // the largest of dAqRes
-    bool gcv_lr = false;                                  // every flip angle's dictionary is of numerical rank <= 16: the GCV trace takes the 17 x 17 form
-    double *dChol = nullptr; int64_t cap_chol = 0;        // BayesReg at two bins per lane: one packed factor per resident wave (chol_lean), grown on demand
-    double *dLcSave = nullptr; int64_t cap_lc = 0;        // L-curve at two bins per lane: the sweep states of queued voxels (fit_kernel.hpp: FitArgs::lc_save) and, behind them, lc_at
-    double *dBig = nullptr; int64_t cap_big = 0;          // the waves' spill-over slots: factor columns beyond the LDS capacity (nnls_big.hpp), grown on demand
-    int last_spill = 0;                                   // voxels of the last finished fit(s) that used them
-    double blam[MET2_BAYES_TABLE > 0 ? MET2_BAYES_TABLE : 1];
-    int *hErr = nullptr;                                  // pinned [4]: the FA-range error word of an enqueued fit lands here, and its spill-over queue's tail (= count) and head
-    bool err_pending = false;
-    hipStream_t err_stream = nullptr;                     // the stream the fits since the last finish were enqueued on (one plan serves one stream at a time)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-    bool timed = false, timed2 = false;
-};
-
-// determinant by LU with partial pivoting (scipy.linalg.det at bayesian_interpolation.py:100)
-static double det_lu(int n, const double *Ain)
-{
-    std::vector<double> A(Ain, Ain + (size_t)n * n);
-    double det = 1.0;
-    for (int c = 0; c < n; ++c) {
-        int piv = c; double mx = fabs(A[(size_t)c * n + c]);
-        for (int r = c + 1; r < n; ++r) if (fabs(A[(size_t)r * n + c]) > mx) { mx = fabs(A[(size_t)r * n + c]); piv = r; }
-        if (mx == 0.0) return 0.0;
-        if (piv != c) { for (int j = 0; j < n; ++j) std::swap(A[(size_t)c * n + j], A[(size_t)piv * n + j]); det = -det; }
-        double d = A[(size_t)c * n + c];
-        det *= d;
-        for (int r = c + 1; r < n; ++r) {
-            double l = A[(size_t)r * n + c] / d;
-            if (l != 0.0) for (int j = c + 1; j < n; ++j) A[(size_t)r * n + j] -= l * A[(size_t)c * n + j];
-        }
-    }
-    return det;
-}
 
 static void default_lambda_grid(std::vector<double> &g)
 {
@@ -1126,15 +503,12 @@ static int ensure_sort_bufs(met2_plan *p, int64_t nvox)
 }
 
 // met2_fit_host reserves a plan's per-voxel scratch for its largest block before the block loop (met2_host.hip)
-namespace met2 { __attribute__((visibility("hidden"))) int plan_reserve(met2_plan *p, int64_t nvox)
+int met2::plan_reserve(met2_plan *p, int64_t nvox)
 {
     if (!p) return fail(MET2_E_INVALID, "NULL plan");
     USE_DEVICE(p->opt.device);
     return ensure_sort_bufs(p, nvox);
-} }
-
-// the plan's T2 grid (a device array of n_t2) for met2_eval.hip; NULL before one is set
-namespace met2 { __attribute__((visibility("hidden"))) const double *plan_t2_grid(met2_plan *p) { return p && p->have_t2 ? p->dT2 : nullptr; } }
+}
 
 static SortBufs sort_bufs(met2_plan *p)
 {
@@ -1271,172 +645,6 @@ static int launch_method(int method, const FitArgs &A, const LaunchGeom &g, hipS
     }
 }
 
-
-// slope weights of the not-a-knot cubic spline: knot slopes = W y (the system depends on the knots only)
-static void spline_weights_host(int n, const double *x, std::vector<double> &W)
-{
-    std::vector<double> A((size_t)n * n, 0.0), Rm((size_t)n * n, 0.0);   // A s = Rm y
-    auto h = [&](int i) { return x[i + 1] - x[i]; };
-    {   // not-a-knot at x[1]
-        const double h0 = h(0), h1 = h(1);
-        A[0] = h1; A[1] = h0 + h1;
-        // rhs = ((3h0+2h1) h1 d0 + h0^2 d1)/(h0+h1), d0 = (y1-y0)/h0, d1 = (y2-y1)/h1
-        const double c0 = (3.0 * h0 + 2.0 * h1) * h1 / (h0 + h1) / h0, c1 = h0 * h0 / (h0 + h1) / h1;
-        Rm[0] += -c0; Rm[1] += c0 - c1; Rm[2] += c1;
-    }
-    for (int i = 1; i < n - 1; ++i) {
-        const double hm = h(i - 1), hp = h(i);
-        A[(size_t)i * n + i - 1] = hp; A[(size_t)i * n + i] = 2.0 * (hm + hp); A[(size_t)i * n + i + 1] = hm;
-        const double cm = 3.0 * hp / hm, cp = 3.0 * hm / hp;               // rhs = 3 (hp dm + hm dp)
-        Rm[(size_t)i * n + i - 1] += -cm; Rm[(size_t)i * n + i] += cm - cp; Rm[(size_t)i * n + i + 1] += cp;
-    }
-    {   // not-a-knot at x[n-2]
-        const double ha = h(n - 3), hb = h(n - 2);
-        A[(size_t)(n - 1) * n + n - 2] = ha + hb; A[(size_t)(n - 1) * n + n - 1] = ha;
-        const double ca = hb * hb / (ha + hb) / ha, cb = (2.0 * ha + 3.0 * hb) * ha / (ha + hb) / hb;
-        Rm[(size_t)(n - 1) * n + n - 3] += -ca; Rm[(size_t)(n - 1) * n + n - 2] += ca - cb; Rm[(size_t)(n - 1) * n + n - 1] += cb;
-    }
-    // W = A^-1 Rm by Gaussian elimination with partial pivoting on [A | Rm]
-    for (int c = 0; c < n; ++c) {
-        int p = c; double mx = fabs(A[(size_t)c * n + c]);
-        for (int r = c + 1; r < n; ++r) if (fabs(A[(size_t)r * n + c]) > mx) { mx = fabs(A[(size_t)r * n + c]); p = r; }
-        if (p != c) for (int j = 0; j < n; ++j) { std::swap(A[(size_t)c * n + j], A[(size_t)p * n + j]); std::swap(Rm[(size_t)c * n + j], Rm[(size_t)p * n + j]); }
-        for (int r = c + 1; r < n; ++r) {
-            const double l = A[(size_t)r * n + c] / A[(size_t)c * n + c];
-            if (l == 0.0) continue;
-            for (int j = c; j < n; ++j) A[(size_t)r * n + j] -= l * A[(size_t)c * n + j];
-            for (int j = 0; j < n; ++j) Rm[(size_t)r * n + j] -= l * Rm[(size_t)c * n + j];
-        }
-    }
-    W.assign((size_t)n * n, 0.0);
-    for (int c = n - 1; c >= 0; --c)
-        for (int j = 0; j < n; ++j) {
-            double t = Rm[(size_t)c * n + j];
-            for (int q = c + 1; q < n; ++q) t -= A[(size_t)c * n + q] * W[(size_t)q * n + j];
-            W[(size_t)c * n + j] = t / A[(size_t)c * n + c];
-        }
-}
-
-extern "C" int met2_smooth_separable(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, int32_t radius, const double *weights,
-                                     const double *data, double *out, double *work, void *stream)
-{
-    if (nx < 0 || ny < 0 || nz < 0 || nt < 1) return fail(MET2_E_INVALID, "bad shape");
-    if (radius < 0 || radius > MET2_SMOOTH_MAX_RADIUS) return fail(MET2_E_UNSUPPORTED, "kernel radius must be 0..32");
-    const int64_t total = (int64_t)nx * ny * nz * nt;
-    if (total == 0) return MET2_OK;
-    if (!weights || !data || !out) return fail(MET2_E_INVALID, "NULL argument");
-    if (data == out || work == out || work == data) return fail(MET2_E_INVALID, "data, out and work must be distinct");
-    USE_DEVICE(device);
-    hipStream_t s = (hipStream_t)stream;
-    double *tmp = work;
-    if (!tmp) HIPCHK(hipMalloc(&tmp, sizeof(double) * (size_t)total));
-    SmoothArgs A;
-    A.radius = radius; A.total = total;
-    for (int i = 0; i < 2 * radius + 1; ++i) A.w[i] = weights[i];
-    const int dims[3] = {nx, ny, nz};
-    const int64_t strides[3] = {(int64_t)ny * nz * nt, (int64_t)nz * nt, (int64_t)nt};
-    const double *src = data;
-    double *dst = out;                                              // x: data -> out, y: out -> work, z: work -> out
-    const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 64);
-    for (int ax = 0; ax < 3; ++ax) {
-        A.n = dims[ax]; A.stride = strides[ax]; A.src = src; A.dst = dst;
-        hipLaunchKernelGGL(smooth_axis_kernel, dim3(grid), dim3(256), 0, s, A);
-        src = dst;
-        dst = (dst == out) ? tmp : out;
-    }
-    HIPCHK(hipGetLastError());
-    if (!work) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(tmp)); }
-    return MET2_OK;
-}
-
-extern "C" int met2_nesma(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, const double *data,
-                          const uint8_t *mask, double *out, void *stream)
-{
-    if (nx < 0 || ny < 0 || nz < 0 || nt < 1) return fail(MET2_E_INVALID, "bad shape");
-    if (nt > MET2_NESMA_MAX_NT) return fail(MET2_E_UNSUPPORTED, "NESMA supports at most 128 echoes");
-    const int64_t nvox = (int64_t)nx * ny * nz;
-    if (nvox == 0) return MET2_OK;
-    if (!data || !out) return fail(MET2_E_INVALID, "NULL argument");
-    if (data == out) return fail(MET2_E_INVALID, "NESMA cannot run in place");
-    if ((nvox + 3) / 4 > 0x7fffffffLL) return fail(MET2_E_UNSUPPORTED, "volume too large for one launch");
-    USE_DEVICE(device);
-    hipStream_t s = (hipStream_t)stream;
-    NesmaArgs A;
-    A.nx = nx; A.ny = ny; A.nz = nz; A.nt = nt; A.data = data; A.mask = mask; A.out = out; A.nvox = nvox;
-    const dim3 grid((unsigned)((((nvox + 3) / 4 + 7) / 8) * 8)), block(256);      // a multiple of 8 for the XCD remap
-    A.srow = ((nt + 23) / 32) * 32 + 8;
-    const size_t lds = sizeof(double) * 4 * 2 * MET2_NESMA_HW * (size_t)A.srow;
-    if (nt == 32)      hipLaunchKernelGGL((nesma_kernel<1, 2, 32>), grid, block, lds, s, A);
-    else if (nt < 32)  hipLaunchKernelGGL((nesma_kernel<1, 2, 0>), grid, block, lds, s, A);
-    else if (nt == 48) hipLaunchKernelGGL((nesma_kernel<1, 1, 48>), grid, block, lds, s, A);
-    else if (nt <= 64) hipLaunchKernelGGL((nesma_kernel<1, 1, 0>), grid, block, lds, s, A);
-    else               hipLaunchKernelGGL((nesma_kernel<2, 1, 0>), grid, block, lds, s, A);
-    HIPCHK(hipGetLastError());
-    return MET2_OK;
-}
-
-struct SplineTables { int device = -1; double *d = nullptr; size_t cap = 0; std::vector<double> last; };
-static thread_local SplineTables g_spline_tables;
-// for host threads that end (met2_fit_host's per-plan threads): frees the calling thread's tables
-namespace met2 { __attribute__((visibility("hidden"))) void spline_tables_release()
-{
-    SplineTables &T = g_spline_tables;
-    if (T.d) { DevGuard g(T.device); (void)hipDeviceSynchronize(); (void)hipFree(T.d); }
-    T.d = nullptr; T.cap = 0; T.device = -1; T.last.clear();
-} }
-
-extern "C" int met2_fa_spline_select_strided(int32_t device, int64_t nvox, int32_t n_lr, const double *alpha_lr, const double *resid,
-                                             int32_t n_hr, const double *alpha_hr, int32_t n_te, const double *data, int64_t voxel_stride,
-                                             int64_t echo_stride, const uint8_t *mask, double *fa_index, double *xmin, void *stream)
-{
-    if (nvox == 0) return MET2_OK;
-    if (!alpha_lr || !resid || !alpha_hr || !data || !fa_index) return fail(MET2_E_INVALID, "NULL argument");
-    if (n_lr < 4 || n_lr > MET2_MAX_LR) return fail(MET2_E_UNSUPPORTED, "coarse FA grid must have 4..32 points");
-    if (n_hr < 1 || n_te < 1) return fail(MET2_E_INVALID, "bad shape");
-    for (int i = 1; i < n_lr; ++i) if (!(alpha_lr[i] > alpha_lr[i - 1])) return fail(MET2_E_INVALID, "coarse FA grid must increase");
-    if (nvox <= 0) return MET2_OK;
-    USE_DEVICE(device);
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<double> W;
-    spline_weights_host(n_lr, alpha_lr, W);
-    const size_t nd = (size_t)n_lr + (size_t)n_lr * n_lr + (size_t)n_hr;
-    std::vector<double> hb(nd);
-    memcpy(hb.data(), alpha_lr, sizeof(double) * n_lr);
-    memcpy(hb.data() + n_lr, W.data(), sizeof(double) * n_lr * n_lr);
-    memcpy(hb.data() + n_lr + (size_t)n_lr * n_lr, alpha_hr, sizeof(double) * n_hr);
-    // The tables (two grids and the spline's weight matrix, a few KB) live in a per-thread device buffer that is written only when they
-    // CHANGE: a driver calls this once per chunk with the same grids, and an allocation + blocking wait + hipFree per call stood in the
-    // way of its pipeline (hipFree waits for the whole device).  Changing them waits for the device first (a kernel of an earlier call may
-    // still read the old ones).
-    SplineTables &T = g_spline_tables;
-    if (T.device != device || T.cap < nd) {
-        if (T.d) { DevGuard old(T.device); HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(T.d)); T.d = nullptr; T.cap = 0; T.last.clear(); }
-        HIPCHK(hipMalloc((void **)&T.d, sizeof(double) * std::max<size_t>(nd, 2048)));
-        T.cap = std::max<size_t>(nd, 2048); T.device = device;
-    }
-    if (T.last != hb) {
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(T.d, hb.data(), sizeof(double) * nd, hipMemcpyHostToDevice));
-        T.last = hb;
-    }
-    double *dbuf = T.d;
-    SplineArgs A;
-    A.nlr = n_lr; A.nhr = n_hr; A.nte = n_te;
-    A.alpha_lr = dbuf; A.W = dbuf + n_lr; A.alpha_hr = dbuf + n_lr + (size_t)n_lr * n_lr;
-    A.resid = resid; A.data = data; A.vs = voxel_stride; A.es = echo_stride; A.mask = mask; A.fa_index = fa_index; A.xmin = xmin; A.nvox = nvox;
-    hipLaunchKernelGGL(fa_spline_kernel, dim3((unsigned)((nvox + 127) / 128)), dim3(128), 0, s, A);
-    HIPCHK(hipGetLastError());
-    return MET2_OK;
-}
-
-extern "C" int met2_fa_spline_select(int32_t device, int64_t nvox, int32_t n_lr, const double *alpha_lr, const double *resid,
-                                     int32_t n_hr, const double *alpha_hr, int32_t n_te, const double *data, const uint8_t *mask,
-                                     double *fa_index, double *xmin, void *stream)
-{
-    return met2_fa_spline_select_strided(device, nvox, n_lr, alpha_lr, resid, n_hr, alpha_hr, n_te, data, n_te, 1, mask, fa_index, xmin, stream);
-}
-
-
 // Plan-level seeds (seed_kernel) are built where the dictionary, the penalty or T2SPARC's lambda are SET -- entries that
 // synchronise -- never inside a fit: a fit on another stream or thread only ever reads finished records.
 // Seeded starts equal the cold-start solution only when B + lambda K is positive definite (one minimiser).  That holds for the
@@ -1462,7 +670,7 @@ static bool host_posdef(int n, std::vector<double> G)
     return true;
 }
 
-static int ensure_seeds(met2_plan *p, hipStream_t s)
+int met2::ensure_seeds(met2_plan *p, hipStream_t s)
 {
     if (!p->have_dict || !p->have_pen) return MET2_OK;
     const double key[7] = {p->opt.t2sparc_lambda, p->opt.x2_lo, p->opt.x2_hi, p->opt.gcv_lo, p->opt.gcv_hi, p->opt.bayes_lo, p->opt.bayes_hi};
@@ -1586,6 +794,7 @@ int met2_plan_create(met2_plan **out, int32_t n_te, int32_t n_t2, int32_t n_fa, 
     if (p->opt.device < 0 || p->opt.device >= ndev) { delete p; return fail(MET2_E_INVALID, "device ordinal out of range"); }
     DevGuard dev_guard_(p->opt.device);
     if (dev_guard_.err != hipSuccess) { delete p; return fail(MET2_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dev_guard_.err)); }
+    struct Guard { met2_plan *p; ~Guard() { if (p) (void)met2_plan_destroy(p); } } guard{p};      // a failing return below releases the plan and what it holds by then
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, p->opt.device));
     p->cus = prop.multiProcessorCount;
@@ -1609,8 +818,11 @@ int met2_plan_create(met2_plan **out, int32_t n_te, int32_t n_t2, int32_t n_fa, 
     HIPCHK(hipEventCreate(&p->ev2));
     std::vector<double> g;
     default_lambda_grid(g);
+    const int rc = met2_plan_set_lambda_grid(p, g.data(), (int)g.size());
+    if (rc) return rc;
+    guard.p = nullptr;
     *out = p;
-    return met2_plan_set_lambda_grid(p, g.data(), (int)g.size());
+    return MET2_OK;
 }
 
 int met2_plan_set_options(met2_plan *p, const met2_options *opt)
@@ -1657,202 +869,6 @@ int met2_plan_destroy(met2_plan *p)
     if (p->ev1) (void)hipEventDestroy(p->ev1);
     if (p->ev2) (void)hipEventDestroy(p->ev2);
     delete p;
-    return MET2_OK;
-}
-
-// Everything that is derived from the dictionary alone: Gram matrices, the transposed copy, GCV's low-rank basis.  Blocks (its callers do).
-static int build_gram(met2_plan *p, hipStream_t s)
-{
-    hipLaunchKernelGGL(gram_kernel, dim3(p->n_fa), dim3(256), 0, s, p->n_te, p->n_t2, p->dD, p->dB, p->dDt);
-    HIPCHK(hipGetLastError());
-    const int lds = (int)sizeof(double) * (p->n_te * p->n_t2 + MET2_GCV_LR_RANK * 64);
-    HIPCHK(hipFuncSetAttribute((const void *)gcv_basis_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL(gcv_basis_kernel, dim3(p->n_fa), dim3(64), lds, s, p->n_te, p->n_t2, p->dD, p->dAq, p->dQt, p->dAqRes);
-    HIPCHK(hipGetLastError());
-    std::vector<double> res(p->n_fa);
-    HIPCHK(hipMemcpyAsync(res.data(), p->dAqRes, sizeof(double) * p->n_fa, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    bool ok = true;
-    p->gcv_res = 0.0;
-    for (double r : res) { ok = ok && (r <= MET2_GCV_LR_TOL); p->gcv_res = (r > p->gcv_res || r != r) ? r : p->gcv_res; }      // (nan: not low rank)
-    p->gcv_lr = ok;
-    p->have_dict = true; p->seeds_valid = false;
-    return MET2_OK;
-}
-
-int met2_plan_set_t2_grid(met2_plan *p, const double *T2s)
-{
-    if (!p || !T2s) return fail(MET2_E_INVALID, "NULL argument");
-    USE_DEVICE(p->opt.device);
-    HIPCHK(hipMemcpy(p->dT2, T2s, sizeof(double) * p->n_t2, hipMemcpyHostToDevice));
-    p->have_t2 = true;
-    return MET2_OK;
-}
-
-int met2_plan_build_dictionary_epg(met2_plan *p, const double *T2s, const double *T1s, double tau, const double *alpha_deg,
-                                   double TR, void *stream)
-{
-    if (!p || !T2s || !T1s || !alpha_deg) return fail(MET2_E_INVALID, "NULL argument");
-    USE_DEVICE(p->opt.device);
-    hipStream_t s = (hipStream_t)stream;
-    double *tmp = nullptr;
-    size_t nb = sizeof(double) * (size_t)(2 * p->n_t2 + p->n_fa);
-    HIPCHK(hipMalloc(&tmp, nb));
-    std::vector<double> h(2 * p->n_t2 + p->n_fa);
-    memcpy(h.data(), T2s, sizeof(double) * p->n_t2);
-    memcpy(h.data() + p->n_t2, T1s, sizeof(double) * p->n_t2);
-    memcpy(h.data() + 2 * p->n_t2, alpha_deg, sizeof(double) * p->n_fa);
-    HIPCHK(hipMemcpy(tmp, h.data(), nb, hipMemcpyHostToDevice));
-    int waves = p->n_fa * p->n_t2;
-    int blocks = (waves + 3) / 4;
-    hipLaunchKernelGGL(epg_dictionary_kernel, dim3(blocks), dim3(256), 0, s, p->n_te, p->n_t2, p->n_fa, tmp, tmp + p->n_t2, tau,
-                       tmp + 2 * p->n_t2, TR, p->dD);
-    HIPCHK(hipGetLastError());
-    int rc = build_gram(p, s);
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipFree(tmp));
-    if (rc) return rc;
-    rc = ensure_seeds(p, s);
-    if (rc) return rc;
-    return met2_plan_set_t2_grid(p, T2s);
-}
-
-int met2_plan_build_dictionary_epg_profile(met2_plan *p, const double *T2s, const double *T1s, double tau, const double *alpha_deg,
-                                           double TR, int32_t n_z, const double *r_exc, const double *r_ref, const double *w, void *stream)
-{
-    if (!p || !T2s || !T1s || !alpha_deg || !r_exc || !r_ref || !w) return fail(MET2_E_INVALID, "NULL argument");
-    if (n_z < 1 || n_z > 64) return fail(MET2_E_INVALID, "slice profile: n_z must lie in 1..64");
-    double wsum = 0.0;
-    for (int z = 0; z < n_z; ++z) {
-        if (!std::isfinite(r_exc[z]) || !std::isfinite(r_ref[z]) || !std::isfinite(w[z]) || r_exc[z] < 0.0 || r_ref[z] < 0.0 || w[z] < 0.0)
-            return fail(MET2_E_INVALID, "slice profile: r_exc, r_ref and w must be finite and >= 0");
-        wsum += w[z];
-    }
-    if (!(wsum > 0.0)) return fail(MET2_E_INVALID, "slice profile: the weights are all zero");
-    USE_DEVICE(p->opt.device);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n0 = (size_t)(2 * p->n_t2 + p->n_fa);
-    std::vector<double> h(n0 + 3 * (size_t)n_z);
-    memcpy(h.data(), T2s, sizeof(double) * p->n_t2);
-    memcpy(h.data() + p->n_t2, T1s, sizeof(double) * p->n_t2);
-    memcpy(h.data() + 2 * p->n_t2, alpha_deg, sizeof(double) * p->n_fa);
-    memcpy(h.data() + n0, r_exc, sizeof(double) * n_z);
-    memcpy(h.data() + n0 + n_z, r_ref, sizeof(double) * n_z);
-    memcpy(h.data() + n0 + 2 * n_z, w, sizeof(double) * n_z);
-    struct Scratch { double *p = nullptr; ~Scratch() { if (p) (void)hipFree(p); } } scratch;      // freed on every return, the failing ones included
-    HIPCHK(hipMalloc(&scratch.p, sizeof(double) * h.size()));
-    double *tmp = scratch.p;
-    HIPCHK(hipMemcpy(tmp, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(epg_profile_dictionary_kernel, dim3(p->n_fa * p->n_t2), dim3(256), sizeof(double) * 64 * (size_t)n_z, s, p->n_te, p->n_t2,
-                       n_z, tmp, tmp + p->n_t2, tau, tmp + 2 * p->n_t2, TR, tmp + n0, tmp + n0 + n_z, tmp + n0 + 2 * n_z, p->dD);
-    HIPCHK(hipGetLastError());
-    int rc = build_gram(p, s);
-    HIPCHK(hipStreamSynchronize(s));
-    if (rc) return rc;
-    rc = ensure_seeds(p, s);
-    if (rc) return rc;
-    return met2_plan_set_t2_grid(p, T2s);
-}
-
-int met2_plan_set_dictionary(met2_plan *p, const double *dic)
-{
-    if (!p || !dic) return fail(MET2_E_INVALID, "NULL argument");
-    USE_DEVICE(p->opt.device);
-    size_t nb = sizeof(double) * (size_t)p->n_fa * p->n_te * p->n_t2;
-    double *tmp = nullptr;
-    HIPCHK(hipMalloc(&tmp, nb));
-    HIPCHK(hipMemcpy(tmp, dic, nb, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(relayout_kernel, dim3(256), dim3(256), 0, 0, p->n_te, p->n_t2, p->n_fa, tmp, p->dD, 1);
-    HIPCHK(hipGetLastError());
-    int rc = build_gram(p, 0);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipFree(tmp));
-    if (rc) return rc;
-    return ensure_seeds(p, 0);
-}
-
-int met2_plan_get_dictionary(met2_plan *p, double *dic)
-{
-    if (!p || !dic) return fail(MET2_E_INVALID, "NULL argument");
-    if (!p->have_dict) return fail(MET2_E_STATE, "no dictionary in the plan");
-    USE_DEVICE(p->opt.device);
-    size_t nb = sizeof(double) * (size_t)p->n_fa * p->n_te * p->n_t2;
-    double *tmp = nullptr;
-    HIPCHK(hipMalloc(&tmp, nb));
-    hipLaunchKernelGGL(relayout_kernel, dim3(256), dim3(256), 0, 0, p->n_te, p->n_t2, p->n_fa, p->dD, tmp, 0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(dic, tmp, nb, hipMemcpyDeviceToHost));
-    HIPCHK(hipFree(tmp));
-    return MET2_OK;
-}
-
-int met2_plan_set_penalty_dense(met2_plan *p, const double *L)
-{
-    if (!p || !L) return fail(MET2_E_INVALID, "NULL argument");
-    const int n = p->n_t2;
-    for (int i = 0; i < n * n; ++i) if (!std::isfinite(L[i])) return fail(MET2_E_INVALID, "non-finite penalty matrix");
-    std::vector<double> K((size_t)n * n, 0.0);
-    for (int a = 0; a < n; ++a) for (int b = 0; b < n; ++b) {
-        double t = 0.0;
-        for (int i = 0; i < n; ++i) t += L[(size_t)i * n + a] * L[(size_t)i * n + b];
-        K[(size_t)a * n + b] = t;
-    }
-    for (int a = 0; a < n; ++a) for (int b = 0; b < n; ++b) if (abs(a - b) > 2) {
-        if (K[(size_t)a * n + b] != 0.0) return fail(MET2_E_UNSUPPORTED, "L^T L has bandwidth > 2");
-        if (L[(size_t)a * n + b] != 0.0) return fail(MET2_E_UNSUPPORTED, "penalty matrix has bandwidth > 2");
-    }
-    std::vector<double> kb(5 * 128, 0.0), lb(5 * 128, 0.0);
-    for (int j = 0; j < n; ++j) for (int d = 0; d < 5; ++d) {
-        int c = j + d - 2;
-        if (c < 0 || c >= n) continue;
-        kb[d * 128 + j] = K[(size_t)j * n + c];
-        lb[d * 128 + j] = L[(size_t)j * n + c];
-    }
-    USE_DEVICE(p->opt.device);
-    HIPCHK(hipMemcpy(p->dKband, kb.data(), sizeof(double) * 5 * 128, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p->dLband, lb.data(), sizeof(double) * 5 * 128, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p->dKd, K.data(), sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
-    p->Lhost.assign(L, L + (size_t)n * n);
-    p->log_detL = log(det_lu(n, L));
-    p->have_pen = true; p->seeds_valid = false;
-    return ensure_seeds(p, 0);
-}
-
-int met2_plan_set_penalty(met2_plan *p, int32_t which, const double *T2s)
-{
-    if (!p) return fail(MET2_E_INVALID, "NULL plan");
-    const int n = p->n_t2;
-    std::vector<double> L((size_t)n * n, 0.0);
-    switch (which) {   // motor:86-111, 263-269
-    case MET2_PEN_I: for (int i = 0; i < n; ++i) L[(size_t)i * n + i] = 1.0; break;
-    case MET2_PEN_L1: for (int i = 0; i < n; ++i) { L[(size_t)i * n + i] = 1.0; if (i > 0) L[(size_t)i * n + i - 1] = -1.0; } break;
-    case MET2_PEN_L2:
-        for (int i = 0; i < n; ++i) {
-            L[(size_t)i * n + i] = 2.0;
-            if (i > 0) L[(size_t)i * n + i - 1] = -1.0;
-            if (i < n - 1) L[(size_t)i * n + i + 1] = -1.0;
-        }
-        L[0] = 1.0; L[(size_t)(n - 1) * n + n - 1] = 1.0;
-        break;
-    case MET2_PEN_INVT2:
-        if (!T2s) return fail(MET2_E_INVALID, "InvT2 needs the T2 grid");
-        for (int i = 0; i < n; ++i) {
-            double prev = (i == 0) ? T2s[0] - 1.0 : T2s[i - 1];
-            double d = T2s[i] - prev;
-            if (i == 0) d = T2s[1] - T2s[0];
-            L[(size_t)i * n + i] = 1.0 / d;
-        }
-        break;
-    default: return fail(MET2_E_INVALID, "unknown penalty");
-    }
-    return met2_plan_set_penalty_dense(p, L.data());
-}
-
-int met2_plan_get_penalty(met2_plan *p, double *L)
-{
-    if (!p || !L) return fail(MET2_E_INVALID, "NULL argument");
-    if (!p->have_pen) return fail(MET2_E_STATE, "no penalty set");
-    memcpy(L, p->Lhost.data(), sizeof(double) * p->Lhost.size());
     return MET2_OK;
 }
 
@@ -1950,6 +966,16 @@ static int debug_counters(int method, hipStream_t s)
     fprintf(stderr, "[met2] loop maxima: tries=%d sweeps=%d outer=%d iter=%d taken=%d round=%d jacobi_sweeps=%d last_sweep_rotations=%d\n", ls[0], ls[1], ls[2], ls[3], ls[4], ls[5], ls[6], ls[7]);
 #endif
     fflush(stderr);
+    return MET2_OK;
+}
+
+// a scratch buffer of the plan's that a fit grows on demand: waits for the stream's work on the old one before it goes
+static int grow_device(double *&buf, int64_t &cap, int64_t need, hipStream_t s)
+{
+    if (cap >= need) return MET2_OK;
+    if (buf) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(buf)); buf = nullptr; cap = 0; }
+    HIPCHK(hipMalloc(&buf, sizeof(double) * (size_t)need));
+    cap = need;
     return MET2_OK;
 }
 
@@ -2052,11 +1078,8 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
         // chol_lean's scratch: one packed factor per wave of the launch (the spill-over kernel runs with the same geometry)
         const int stride = (col_base(p->n_t2) + 15) & ~15;
         const int64_t need = (int64_t)g.grid * g.waves * stride;
-        if (p->cap_chol < need) {
-            if (p->dChol) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(p->dChol)); p->dChol = nullptr; p->cap_chol = 0; }
-            HIPCHK(hipMalloc(&p->dChol, sizeof(double) * (size_t)need));
-            p->cap_chol = need;
-        }
+        rc = grow_device(p->dChol, p->cap_chol, need, s);
+        if (rc) return rc;
         A.chol = p->dChol; A.chol_stride = stride;
     }
     // spill-over slots (nnls_big.hpp): a set that outgrows the LDS capacity of the launch goes on in the spill-over kernel, its columns beyond
@@ -2068,11 +1091,8 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
         rc = fit_geometry(p, kmeth, gw, kfast, 0, -1);                      // the slots are allocated once, not per block of a host pipeline
         if (rc) return rc;
         const int64_t need = (int64_t)gw.grid * gw.waves * stride;
-        if (p->cap_big < need) {
-            if (p->dBig) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(p->dBig)); p->dBig = nullptr; p->cap_big = 0; }
-            HIPCHK(hipMalloc(&p->dBig, sizeof(double) * (size_t)need));
-            p->cap_big = need;
-        }
+        rc = grow_device(p->dBig, p->cap_big, need, s);
+        if (rc) return rc;
         A.big = p->dBig; A.big_stride = stride;
     }
     A.lc_save = nullptr; A.lc_at = nullptr; A.lc_cap = 0;
@@ -2080,11 +1100,8 @@ static int fit_impl(met2_plan *p, int32_t method, int64_t nvox, const double *da
         // records for a sixteenth of the voxels (5 % of them overflow on measured spectra), between 4 096 and 262 144 (2.4 GB): entries beyond start over
         const int64_t cap = std::min<int64_t>(nvox, std::min<int64_t>(262144, std::max<int64_t>(4096, nvox / 16)));
         const int64_t need = cap * (LC_SAVE_DOUBLES * 64) + (cap + 1) / 2;
-        if (p->cap_lc < need) {
-            if (p->dLcSave) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(p->dLcSave)); p->dLcSave = nullptr; p->cap_lc = 0; }
-            HIPCHK(hipMalloc(&p->dLcSave, sizeof(double) * (size_t)need));
-            p->cap_lc = need;
-        }
+        rc = grow_device(p->dLcSave, p->cap_lc, need, s);
+        if (rc) return rc;
         A.lc_save = p->dLcSave; A.lc_at = (int *)(p->dLcSave + cap * (LC_SAVE_DOUBLES * 64)); A.lc_cap = (int)cap;
     }
     for (int j = 0; j < (MET2_BAYES_TABLE > 0 ? MET2_BAYES_TABLE : 1); ++j) A.blam[j] = p->blam[j];
@@ -2238,60 +1255,6 @@ int met2_fa_bruteforce_strided(met2_plan *p, int64_t nvox, const double *data, i
     }
 #endif
     p->timed = true;
-    return MET2_OK;
-}
-
-int met2_roi_reduce(met2_plan *src, met2_plan *dst, int64_t nvox, const double *data, int64_t voxel_stride, int64_t echo_stride,
-                    const int32_t *roi_index, const double *fa_index, double *mean_signal, double *count, void *stream)
-{
-    if (!src || !dst || !data || !roi_index || !mean_signal || !count) return fail(MET2_E_INVALID, "NULL argument");
-    if (!src->have_dict) return fail(MET2_E_STATE, "no dictionary in the source plan");
-    if (src->n_te != dst->n_te || src->n_t2 != dst->n_t2) return fail(MET2_E_INVALID, "source and destination plans differ in shape");
-    if (src->opt.device != dst->opt.device) return fail(MET2_E_INVALID, "source and destination plans live on different devices");
-    if (voxel_stride == 0 || echo_stride == 0) return fail(MET2_E_INVALID, "zero stride");
-    if (nvox <= 0) return fail(MET2_E_INVALID, "empty voxel list");
-    USE_DEVICE(src->opt.device);
-    hipStream_t s = (hipStream_t)stream;
-    RoiArgs A;
-    A.nte = src->n_te; A.nt2 = src->n_t2; A.nfa = src->n_fa; A.nroi = dst->n_fa;
-    A.nslice = (int)std::min<int64_t>(256, (nvox + 4095) / 4096);
-    A.nvox = nvox; A.vs = voxel_stride; A.es = echo_stride; A.data = data; A.roi = roi_index; A.fa_index = fa_index;
-    A.Dsrc = src->dD; A.Ddst = dst->dD; A.mean_sig = mean_signal; A.count = count;
-    void *scratch = nullptr;
-    const size_t nsig = sizeof(double) * (size_t)A.nroi * A.nslice * 64, ncnt = sizeof(int) * (size_t)A.nroi * A.nslice * A.nfa;
-    HIPCHK(hipMalloc(&scratch, nsig + ncnt + 16));
-    A.part_sig = (double *)scratch; A.part_cnt = (int *)((char *)scratch + nsig); A.err = (int *)((char *)scratch + nsig + ncnt);
-    HIPCHK(hipMemsetAsync(A.err, 0, sizeof(int), s));
-    hipLaunchKernelGGL(roi_partial_kernel, dim3(A.nslice, A.nroi), dim3(64), sizeof(int) * A.nfa, s, A);
-    hipLaunchKernelGGL(roi_finish_kernel, dim3(A.nroi), dim3(256), sizeof(int) * A.nfa, s, A);
-    HIPCHK(hipGetLastError());
-    int rc = build_gram(dst, s);
-    int herr = 0;
-    HIPCHK(hipMemcpyAsync(&herr, A.err, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipFree(scratch));
-    if (rc) return rc;
-    rc = ensure_seeds(dst, s);
-    if (rc) return rc;
-    if (herr & 1) return fail(MET2_E_INVALID, "FA index outside the dictionary's flip-angle axis");
-    return MET2_OK;
-}
-
-int met2_metrics(met2_plan *p, int64_t nvox, const double *fsol, const uint8_t *mask, double *maps, void *stream)
-{
-    if (!p || !fsol || !maps) return fail(MET2_E_INVALID, "NULL argument");
-    if (!p->have_t2) return fail(MET2_E_STATE, "no T2 grid set");
-    if (nvox <= 0) return MET2_OK;
-    USE_DEVICE(p->opt.device);
-    int blocks = (int)((nvox + 3) / 4);
-    if (blocks > p->cus * 16) blocks = p->cus * 16;
-    if (p->n_t2 <= 64)
-        hipLaunchKernelGGL(metrics_kernel<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, nvox, p->n_t2, p->dT2, p->opt.t2_myelin_cut,
-                           p->opt.t2_ie_cut, fsol, mask, maps);
-    else
-        hipLaunchKernelGGL(metrics_kernel<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, nvox, p->n_t2, p->dT2, p->opt.t2_myelin_cut,
-                           p->opt.t2_ie_cut, fsol, mask, maps);
-    HIPCHK(hipGetLastError());
     return MET2_OK;
 }
 

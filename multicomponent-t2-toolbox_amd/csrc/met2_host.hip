@@ -26,11 +26,7 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
-
-namespace met2 {
-__attribute__((visibility("hidden"))) void spline_tables_release();
-__attribute__((visibility("hidden"))) int plan_reserve(met2_plan *plan, int64_t nvox);      // the plan's per-voxel scratch for blocks of nvox voxels (met2_hip.hip)
-}
+#include "plan.hpp"
 
 namespace {
 

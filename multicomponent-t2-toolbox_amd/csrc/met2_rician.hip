@@ -18,17 +18,9 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "plan.hpp"
 #include "rician_math.hpp"
 #include "wave_ops.hpp"
-
-namespace met2 {
-__attribute__((visibility("hidden"))) int plan_reserve(met2_plan *plan, int64_t nvox);      // the plan's per-voxel scratch (met2_hip.hip)
-// met2_bootstrap.hip: `bytes` of scratch kept with the plan until met2_plan_destroy; the sigma estimate of met2_noise_sigma on scratch of the caller's
-__attribute__((visibility("hidden"))) int rician_scratch(met2_plan *plan, int device, size_t bytes, char **out);
-__attribute__((visibility("hidden"))) int noise_sigma_enqueue(met2_plan *plan, int nte, int nt2, int64_t nvox, const double *data, int64_t vs, int64_t es,
-                                                              const double *fa_index, const uint8_t *mask, double *fsol0, double *sig0, double *reg0,
-                                                              double *sigma_out, void *stream);
-}
 
 namespace {
 

@@ -6,6 +6,7 @@
 // next warm start).
 #pragma once
 #include "nnls_wave.hpp"
+#include "plan.hpp"      // MET2_GCV_LR_RANK
 
 namespace met2 {
 
@@ -534,7 +535,6 @@ __device__ __forceinline__ double bayes_objective(const WaveShared &S, const Ban
 // distance to the reference's formula is the same for both (median 5.8e-5, p90 6.9e-4).  Everything downstream -- tridiagonalisation,
 // multisection, weights -- is the code below with m = 16: 15 Householder steps on 16 rows instead of 47 on 48, Sturm chains of 17 rows
 // instead of 49, 2.7 KB of LDS instead of 20.4.  A plan whose dictionary is NOT of numerical rank <= 16 keeps the full form.
-#define MET2_GCV_LR_RANK 16
 __host__ __device__ inline int gcv_cols(int m) { return (m + 3) & ~3; }
 __host__ __device__ inline int gcv_row_stride(int m) { int np = gcv_cols(m); while ((np & 3) != 2) ++np; return np; }
 __host__ __device__ inline int gcv_vec_len(int m) { return gcv_cols(m); }

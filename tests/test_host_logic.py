@@ -30,6 +30,17 @@ def test_library_builds_and_exports_header_symbols():
     assert L.met2_abi_version() == 6
 
 
+def test_build_lists_name_every_source_and_header():
+    # _build.stale() and the per-object checks look at SOURCES and HEADERS only: a file of csrc/ that is missing from them is never rebuilt
+    b = importlib.import_module(PKG + "._build")
+    on_disk = os.listdir(b.CSRC)
+    assert len(set(b.SOURCES)) == len(b.SOURCES) and len(set(b.HEADERS)) == len(b.HEADERS)
+    assert {f for f in on_disk if f.endswith(".hip")} == set(b.SOURCES)
+    public = os.path.join("..", "..", "include", "met2_hip.h")
+    assert public in b.HEADERS and os.path.exists(os.path.join(b.CSRC, public))
+    assert {f for f in on_disk if f.endswith(".hpp")} == set(b.HEADERS) - {public}
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     if torch.cuda.is_available():
