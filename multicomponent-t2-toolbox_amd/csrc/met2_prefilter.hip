@@ -3,6 +3,7 @@
 //
 // Kernels
 //   nesma_kernel            motor:305-333
+//   nesma_one_echo_kernel   motor:305-333 at one echo
 //   smooth_axis_kernel      motor:337-343
 //   fa_spline_kernel        fa_estimation.py:54-59
 #include <hip/hip_runtime.h>
@@ -187,6 +188,78 @@ __global__ __launch_bounds__(256) void nesma_kernel(NesmaArgs A)
     const double dc = (double)cnt;                             // empty set -> 0/0 = nan, as np.mean of nothing
     if (has0 && writer) orow[e0] = acc0 / dc;
     if (has1) orow[e1] = acc1 / dc;
+}
+
+// One echo (nt == 1): np.mean(rows[similar], axis=0) of an [n, 1] array is a contiguous reduction, which numpy sums pairwise (8 running
+// sums on blocks of at most 128 values, longer vectors halved recursively) and not in window order as it does the rows of nt >= 2.
+// numpy's pairwise sum of a[0..n), n <= 128
+__device__ __forceinline__ double np_pairwise_block(const double *a, int n)
+{
+    if (n < 8) {
+        double r = 0.0;
+        for (int i = 0; i < n; ++i) r += a[i];
+        return r;
+    }
+    double r[8];
+    for (int j = 0; j < 8; ++j) r[j] = a[j];
+    const int n8 = n - (n & 7);
+    for (int i = 8; i < n8; i += 8)
+        for (int j = 0; j < 8; ++j) r[j] += a[i + j];
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (int i = n8; i < n; ++i) res += a[i];
+    return res;
+}
+
+// numpy's pairwise sum of a[0..n), n <= 12^3, on one lane: the recursion pw(a, n) = pw(a, n2) + pw(a + n2, n - n2), n2 = n / 2 rounded
+// down to a multiple of 8, walked with an explicit stack (at most 5 levels: 1728 -> 871 -> 442 -> 228 -> 121)
+__device__ double np_pairwise_serial(const double *a, int n)
+{
+    int off[8], len[8], stage[8], sp = 0;
+    double left[8], ret = 0.0;
+    off[0] = 0; len[0] = n; stage[0] = 0;
+    while (sp >= 0) {
+        if (len[sp] <= 128) { ret = np_pairwise_block(a + off[sp], len[sp]); --sp; continue; }
+        int n2 = len[sp] / 2; n2 -= n2 % 8;
+        if (stage[sp] == 0)      { stage[sp] = 1; off[sp + 1] = off[sp]; len[sp + 1] = n2; stage[sp + 1] = 0; ++sp; }
+        else if (stage[sp] == 1) { stage[sp] = 2; left[sp] = ret; off[sp + 1] = off[sp] + n2; len[sp + 1] = len[sp] - n2; stage[sp + 1] = 0; ++sp; }
+        else                     { ret = left[sp] + ret; --sp; }
+    }
+    return ret;
+}
+
+// One wave per voxel: the similar neighbours go into LDS in window order, lane 0 sums them as numpy does.  (A one-echo series has no
+// decay to fit; the path is here so that the entry is the reference's filter at every echo count it accepts.)
+__global__ __launch_bounds__(64) void nesma_one_echo_kernel(NesmaArgs A)
+{
+    __shared__ double sel[8 * MET2_NESMA_HW * MET2_NESMA_HW * MET2_NESMA_HW];
+    const int lane = lane_id();
+    const int64_t v = blockIdx.x;
+    if (A.mask && A.mask[v] != 1) {                            // workgroup-uniform
+        if (lane == 0) A.out[v] = 0.0;
+        return;
+    }
+    const int z = (int)(v % A.nz), y = (int)((v / A.nz) % A.ny), x = (int)(v / ((int64_t)A.nz * A.ny));
+    const int x0 = max(x - MET2_NESMA_HW, 0), x1 = min(x + MET2_NESMA_HW, A.nx);
+    const int y0 = max(y - MET2_NESMA_HW, 0), y1 = min(y + MET2_NESMA_HW, A.ny);
+    const int z0 = max(z - MET2_NESMA_HW, 0), z1 = min(z + MET2_NESMA_HW, A.nz);
+    const int L = z1 - z0, wy = y1 - y0, n = (x1 - x0) * wy * L;          // n <= 12^3
+    const double c = A.data[v], sumc = 0.0 + c;
+    int cnt = 0;
+    for (int b = 0; b < n; b += 64) {
+        const int k = b + lane;
+        bool ok = false;
+        double nb = 0.0;
+        if (k < n) {
+            const int i = x0 + k / (wy * L), jj = y0 + (k / L) % wy, kk = z0 + k % L;
+            nb = A.data[((int64_t)i * A.ny + jj) * A.nz + kk];
+            ok = 100.0 * (0.0 + fabs(nb - c)) / sumc < 2.5;
+        }
+        const u64 m = ballot(ok);
+        if (ok) sel[cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = nb;
+        cnt += __builtin_popcountll(m);
+    }
+    __syncthreads();
+    if (lane == 0) A.out[v] = np_pairwise_serial(sel, cnt) / (double)cnt;    // empty set -> 0/0 = nan
 }
 
 // ------------------------------------------------------------------------------------------
@@ -386,7 +459,11 @@ extern "C" int met2_nesma(int32_t device, int32_t nx, int32_t ny, int32_t nz, in
     const dim3 grid((unsigned)((((nvox + 3) / 4 + 7) / 8) * 8)), block(256);      // a multiple of 8 for the XCD remap
     A.srow = ((nt + 23) / 32) * 32 + 8;
     const size_t lds = sizeof(double) * 4 * 2 * MET2_NESMA_HW * (size_t)A.srow;
-    if (nt == 32)      hipLaunchKernelGGL((nesma_kernel<1, 2, 32>), grid, block, lds, s, A);
+    if (nt == 1) {
+        if (nvox > 0x7fffffffLL) return fail(MET2_E_UNSUPPORTED, "volume too large for one launch");
+        hipLaunchKernelGGL(nesma_one_echo_kernel, dim3((unsigned)nvox), dim3(64), 0, s, A);
+    }
+    else if (nt == 32) hipLaunchKernelGGL((nesma_kernel<1, 2, 32>), grid, block, lds, s, A);
     else if (nt < 32)  hipLaunchKernelGGL((nesma_kernel<1, 2, 0>), grid, block, lds, s, A);
     else if (nt == 48) hipLaunchKernelGGL((nesma_kernel<1, 1, 48>), grid, block, lds, s, A);
     else if (nt <= 64) hipLaunchKernelGGL((nesma_kernel<1, 1, 0>), grid, block, lds, s, A);

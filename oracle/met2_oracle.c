@@ -1064,6 +1064,7 @@ MET2O_API void met2o_nesma(int nx, int ny, int nz, int nt, const double *data, c
 #pragma omp parallel
     {
         double *diff = (double *)malloc(sizeof(double) * nt), *acc = (double *)malloc(sizeof(double) * nt);
+        double *sel = (double *)malloc(sizeof(double) * 8 * hw * hw * hw);
 #pragma omp for schedule(dynamic, 8) collapse(2)
         for (int x = 0; x < nx; ++x)
             for (int y = 0; y < ny; ++y)
@@ -1081,11 +1082,14 @@ MET2O_API void met2o_nesma(int nx, int ny, int nz, int nt, const double *data, c
                         const double *nb = data + (((size_t)i * ny + j) * nz + k) * nt;
                         for (int e = 0; e < nt; ++e) diff[e] = fabs(nb[e] - c[e]);
                         const double RE = 100.0 * np_pairwise_sum(diff, nt) / sumc;
-                        if (RE < 2.5) { for (int e = 0; e < nt; ++e) acc[e] += nb[e]; cnt++; }
+                        if (RE < 2.5) { if (nt == 1) sel[cnt] = nb[0]; for (int e = 0; e < nt; ++e) acc[e] += nb[e]; cnt++; }
                     }
+                    /* np.mean(rows[similar], axis=0) adds the rows in order, except that an [n, 1] array is one contiguous vector,
+                     * which numpy sums pairwise */
+                    if (nt == 1) acc[0] = np_pairwise_sum(sel, cnt);
                     for (int e = 0; e < nt; ++e) out[v * nt + e] = acc[e] / (double)cnt;      /* mean of an empty set: nan */
                 }
-        free(diff); free(acc);
+        free(diff); free(acc); free(sel);
     }
 }
 
