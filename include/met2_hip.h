@@ -1027,10 +1027,41 @@ int met2_resample_prefilter(int32_t device, const int32_t src_dims[3], int32_t n
  * Limits.  Fixed and moving axes 1 .. MET2_REGISTER_MAX_AXIS, 1 <= n_bins <= MET2_REGISTER_MAX_BINS, 1 <= K <= MET2_REGISTER_MAX_K
  * (MET2_E_UNSUPPORTED beyond the upper ends).  MET2_E_INVALID: an axis, n_bins or K < 1, an unknown kind, a NULL required pointer, a range
  * that is not finite or has lo > hi, an entry of A that is not finite, min_overlap outside [0, 1] or NaN, a work space or index that is too
- * small or misaligned.  Every check comes before any device work: the outputs are then untouched. */
+ * small or misaligned.  Every check comes before any device work: the outputs are then untouched.
+ *
+ * Mutual information (met2_register_joint_cost; additive, ABI stays 6): MET2_REGISTER_MI and MET2_REGISTER_NMI assume only a statistical
+ * dependence between the two images' intensities.  They have an entry of their own; met2_register_cost keeps refusing them.  The index,
+ * the sampling, the copy of A to the head of `work`, min_overlap and the checks are those above.
+ * Moving bin.  With moving_range = (lo, hi) and scale = (double)moving_bins / (hi - lo), formed once on the host in fp64, a sample y falls in
+ *   j = min(max(floor((y - lo) scale), 0), moving_bins - 1): the subtraction and the product are two roundings, not fused.  hi = lo (or a
+ *   width so small that the quotient is not finite) gives scale = 0: every sample in bin 0.  The fixed bin b is the index's.
+ * Counts.  Per candidate the joint histogram n[b][j] over the included voxels that are inside, its row sums n_b, its column sums m_j and
+ *   N = n_inside: integers, formed with integer atomic adds only (per run into moving_bins counters on chip, then the non-zero counters
+ *   into row b of the candidate's table in `work`, which every call zeroes on `stream` first).  Integer adds commute, so the histogram is the
+ *   same whatever the order of arrival, whatever K is and wherever the candidate stands in A.  No floating-point atomics.
+ * Cost.  T(c) = c log(c) for c > 0 and 0 for c = 0, in fp64, one product.  Sxy = sum of T(n[b][j]): the cells of the table, flat index
+ *   b moving_bins + j, in 256 chains -- chain t adds the cells t, t + 256, t + 512, ... in ascending order -- and the chains through the tree
+ *   of a run (above: groups of 64 with s = 32 .. 1, then (g0 + g1) + (g2 + g3)); Sx = sum of T(n_b) with slot b of 256 through the same
+ *   tree (slots beyond n_bins are zeros), Sy = sum of T(m_j) likewise.  Hxy = log N - Sxy / N, Hx = log N - Sx / N, Hy = log N - Sy / N.
+ *   MET2_REGISTER_MI   min(-((Hx + Hy) - Hxy), 0): minus the mutual information
+ *   MET2_REGISTER_NMI  min(-((Hx + Hy) / Hxy), -1): minus Studholme's normalised mutual information (Pattern Recognition 32:71-86, 1999),
+ *                      negated as flirt's normmi is, so that smaller is better
+ *   A cost has the same bits from call to call.
+ * Worst value.  MET2_REGISTER_MI_WORST = 0 and MET2_REGISTER_NMI_WORST = -1 (independent images): for n_inside = 0, for n_inside < min_overlap
+ *   n_included, and where every inside voxel falls in one fixed bin or in one moving bin -- some n_b = N or some m_j = N, tested on the
+ *   integers.  Never NaN for finite volumes.
+ * Entries.
+ *   met2_register_joint_work_bytes  (host only) work_bytes = 96 K + 4 K n_bins moving_bins: the transforms and the candidates' tables
+ *   met2_register_joint_cost        n_inside [K] int64 and cost [K]; `joint`, where not NULL, receives the tables, int32 [K][n_bins][moving_bins]
+ *                                   (4-byte aligned), by a copy on `stream` after the costs are formed.  `work` (work_bytes at least, 8-byte
+ *                                   aligned) and A as for met2_register_cost.  Asynchronous on `stream`.
+ * Limits and errors as above, with 1 <= moving_bins <= MET2_REGISTER_MAX_BINS (below: MET2_E_INVALID; beyond: MET2_E_UNSUPPORTED), a kind other
+ * than the two (MET2_E_INVALID) and a misaligned `joint` (MET2_E_INVALID). */
 #define MET2_REGISTER_CORRATIO 0
 #define MET2_REGISTER_NORMCORR 1
 #define MET2_REGISTER_LEASTSQ 2
+#define MET2_REGISTER_MI 3
+#define MET2_REGISTER_NMI 4
 #define MET2_REGISTER_RUN 256
 #define MET2_REGISTER_MAX_AXIS 512
 #define MET2_REGISTER_MAX_BINS 256
@@ -1043,6 +1074,13 @@ int met2_register_index(int32_t device, const int32_t fixed_dims[3], const int32
 int met2_register_cost(int32_t device, int32_t kind, const int32_t fixed_dims[3], int32_t n_bins, const void *index, const double *fixed,
                        const double fixed_range[2], const int32_t moving_dims[3], const double *moving, const double moving_range[2], int32_t K,
                        const double *A, double min_overlap, void *work, int64_t work_bytes, int64_t *n_inside, double *cost, void *stream);
+#define MET2_REGISTER_MI_WORST 0.0
+#define MET2_REGISTER_NMI_WORST -1.0
+int met2_register_joint_work_bytes(const int32_t fixed_dims[3], int32_t n_bins, int32_t moving_bins, int32_t K, int64_t *work_bytes);
+int met2_register_joint_cost(int32_t device, int32_t kind, const int32_t fixed_dims[3], int32_t n_bins, const void *index,
+                             const int32_t moving_dims[3], const double *moving, const double moving_range[2], int32_t moving_bins, int32_t K,
+                             const double *A, double min_overlap, void *work, int64_t work_bytes, int64_t *n_inside, double *cost,
+                             int32_t *joint, void *stream);
 
 /* Brain extraction (brain_mask='yes'; an extension: the reference's example pipeline makes the mask on the CPU, with FSL's
  * `fslmaths -Tmean` and `bet -m -f 0.4`, example_script_run_MET2_preproc_and_recon.sh step 3).  The surface model of Smith, Fast robust

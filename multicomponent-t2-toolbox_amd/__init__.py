@@ -30,7 +30,7 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   resample.py               resample / resample_labels / prefilter / work_bytes: the affine resampling's entries (csrc/met2_resample.hip), and the transform
                             algebra in numpy: voxel_matrix, invert, from_flirt / to_flirt
   register.py               register: the coarse-to-fine direction-set search for the world matrix that brings a moving volume onto a fixed one, dof 6 / 7 / 9 / 12,
-                            cost 'corratio' | 'normcorr' | 'leastsq'; prepare / cost: a batch of candidate transforms scored in one launch (csrc/met2_register.hip);
+                            cost 'corratio' | 'normcorr' | 'leastsq' | 'mi' | 'nmi' (the last two from a joint histogram sized per level: level_bins); prepare / cost: a batch of candidate transforms scored in one launch (csrc/met2_register.hip);
                             params_to_world / world_to_params, pyramid, the intensity rule
   rician.py                 bias / step / invert: the kernels of the Rician noise-floor correction one by one (csrc/met2_rician.hip; Met2Plan.fit_rician and
                             noise_sigma, rician='iterative' | 'direct' of the drivers)

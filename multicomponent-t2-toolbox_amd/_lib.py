@@ -48,7 +48,8 @@ SYMBOLS = ["met2_default_options", "met2_abi_version", "met2_device_count", "met
            "met2_label_stats_limits", "met2_label_index", "met2_label_moments", "met2_label_quantiles", "met2_label_stats",
            "met2_rician_bias", "met2_rician_step", "met2_rician_invert", "met2_noise_sigma", "met2_fit_rician",
            "met2_resample", "met2_resample_work_bytes", "met2_resample_labels", "met2_resample_prefilter",
-           "met2_register_limits", "met2_register_work_bytes", "met2_register_index", "met2_register_cost"]
+           "met2_register_limits", "met2_register_work_bytes", "met2_register_index", "met2_register_cost",
+           "met2_register_joint_work_bytes", "met2_register_joint_cost"]
 
 
 def lib():
@@ -166,6 +167,8 @@ def lib():
         L.met2_register_work_bytes.argtypes = [i3, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.met2_register_index.argtypes = [C.c_int32, i3, vp, C.c_int32, vp, C.c_int64, vp]
         L.met2_register_cost.argtypes = [C.c_int32, C.c_int32, i3, C.c_int32, vp, vp, _dp, i3, vp, _dp, C.c_int32, _dp, C.c_double, vp, C.c_int64, vp, vp, vp]
+        L.met2_register_joint_work_bytes.argtypes = [i3, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+        L.met2_register_joint_cost.argtypes = [C.c_int32, C.c_int32, i3, C.c_int32, vp, i3, vp, _dp, C.c_int32, C.c_int32, _dp, C.c_double, vp, C.c_int64, vp, vp, vp, vp]
         L.met2_synth_two_lobe.argtypes = [vp, C.POINTER(SynthParams), C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp]
         L.met2_eval_voxel_metrics.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
         L.met2_eval_reduce.argtypes = [C.c_int64, vp, vp, vp, vp, vp, vp]

@@ -10,6 +10,14 @@
 //   rg_final_kernel<KIND> one block per candidate: wave w takes the bins w, w + 4, ...; lane l adds the runs l, l + 64, ... of the bin in
 //                        ascending order, the lanes go through the same wave tree; then the bins (slot b of 256, empty slots zero) through the
 //                        block tree, and thread 0 forms the cost
+//   rg_joint_kernel      met2_register_joint_cost (mutual information): the grid and the sampling of rg_cost_kernel; the run's samples are
+//                        counted per moving bin in LDS (integer LDS atomics), and the counters that are not zero are added to row b of the
+//                        candidate's table [n_bins][moving_bins] in `work` (integer global atomics: at most min(256, moving_bins) a block).
+//                        Per-run histograms summed in a fixed order, as the other costs keep their sums, would take 4 moving_bins bytes per
+//                        (run, candidate) -- 272 MB at 128 x 128 x 64, 64 bins and 256 candidates --; integer adds commute, so the table
+//                        has the same value without that
+//   rg_joint_final_kernel one block per candidate: the row and column sums of the table (integers, in LDS), the three sums of c log c in
+//                        a fixed order (the header states it) and the cost
 // No floating-point atomics and no dependence of a candidate's sums on K or on its place in the batch: candidate k reads A[k] and writes
 // part[k] and nothing else.  The candidates of a run share its member list and the moving volume through the caches: at a pyramid level the
 // moving volume is a few MiB at most, so the eight gathers per voxel are served by L2 and not by HBM.
@@ -223,6 +231,100 @@ __global__ void __launch_bounds__(RG_RUN) rg_final_kernel(RgArgs P)
     P.cost[k] = cost;
 }
 
+// ---------------------------------------------------------------- the joint histogram and the mutual-information costs
+struct RgJointArgs {
+    int nx, ny, nz;                        // moving
+    int mx, my, mz;                        // fixed
+    int n_bins, moving_bins, kind;
+    const double *A;                       // [K][12]
+    const int32_t *offset, *run_first, *order;
+    const double *moving;
+    double lo, scale;                      // moving bin = floor((y - lo) scale), clamped
+    double min_overlap, worst;
+    int32_t *table;                        // [K][n_bins][moving_bins], zero before rg_joint_kernel
+    int64_t *n_inside;                     // [K]
+    double *cost;                          // [K]
+};
+
+// one block per (run, candidate), the grid of rg_cost_kernel: the run's samples go into moving_bins counters in LDS, the counters that are
+// not zero into row b of the candidate's table.  Integer adds commute: the table does not depend on the order of arrival.
+__global__ void __launch_bounds__(RG_RUN) rg_joint_kernel(RgJointArgs P)
+{
+    __shared__ int hist[MET2_REGISTER_MAX_BINS];
+    const int r = blockIdx.x, k = blockIdx.y, n_bins = P.n_bins, mb = P.moving_bins;
+    if (r >= P.run_first[n_bins]) return;                          // the whole block leaves: no barrier is missed
+    int lo = 0, hi = n_bins;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (P.run_first[mid] <= r) lo = mid; else hi = mid;
+    }
+    const int start = P.offset[lo] + (r - P.run_first[lo]) * RG_RUN;
+    const int count = min(RG_RUN, P.offset[lo + 1] - start);
+    const int t = threadIdx.x;
+    hist[t] = 0;
+    __syncthreads();
+    if (t < count) {
+        RsGeom G;
+        G.nx = P.nx; G.ny = P.ny; G.nz = P.nz;
+        G.mx = P.mx; G.my = P.my; G.mz = P.mz;
+#pragma unroll
+        for (int e = 0; e < 12; ++e) G.A[e] = P.A[(size_t)k * 12 + e];
+        const int v = P.order[start + t];
+        const int kz = v % G.mz, rest = v / G.mz;
+        RsTaps<1> T;
+        if (rs_taps<1>(G, rest / G.my, rest % G.my, kz, T)) {
+            const double y = rs_value<1, double>(T, P.moving, 1);
+            const double s = floor(rn_mul(rn_sub(y, P.lo), P.scale));
+            const int j = (int)fmin(fmax(s, 0.0), (double)(mb - 1));       // clamped as a double: j lies in 0 .. mb - 1 whatever the range given
+            atomicAdd(&hist[j], 1);
+        }
+    }
+    __syncthreads();
+    if (t < mb && hist[t] > 0) atomicAdd(P.table + ((size_t)k * n_bins + lo) * mb + t, hist[t]);
+}
+
+__device__ __forceinline__ double rg_clogc(int c) { return c > 0 ? rn_mul((double)c, log((double)c)) : 0.0; }
+
+// one block per candidate: thread t takes the cells t, t + 256, ... of the table [n_bins moving_bins] in ascending order -- T(n_bj) added as
+// it goes, the counts into the row and the column sums in LDS (integers) --, then the three sums of T through the block tree: the cells'
+// chains, the rows as slot b of 256, the columns as slot j of 256
+__global__ void __launch_bounds__(RG_RUN) rg_joint_final_kernel(RgJointArgs P)
+{
+    __shared__ int row[MET2_REGISTER_MAX_BINS], col[MET2_REGISTER_MAX_BINS];
+    __shared__ double lds[4];
+    __shared__ int lds_n[4];
+    const int k = blockIdx.x, t = threadIdx.x, n_bins = P.n_bins, mb = P.moving_bins, cells = n_bins * mb;
+    const int32_t *table = P.table + (size_t)k * cells;
+    row[t] = 0;
+    col[t] = 0;
+    __syncthreads();
+    double t_cell = 0.0;
+    for (int c = t; c < cells; c += RG_RUN) {
+        const int n = table[c];
+        if (n > 0) {
+            t_cell = rn_add(t_cell, rg_clogc(n));
+            atomicAdd(&row[c / mb], n);
+            atomicAdd(&col[c % mb], n);
+        }
+    }
+    __syncthreads();
+    const int nb = row[t], mj = col[t];
+    const int n_in = rg_block_sum(nb, lds_n);
+    const int single = rg_block_sum((int)(n_in > 0 && (nb == n_in || mj == n_in)), lds_n);    // every voxel in one fixed bin, or in one moving bin
+    const double txy = rg_block_sum(t_cell, lds), tx = rg_block_sum(rg_clogc(nb), lds), ty = rg_block_sum(rg_clogc(mj), lds);
+    if (t != 0) return;
+    const double N = (double)n_in;
+    double cost = P.worst;
+    if (n_in > 0 && !(N < rn_mul(P.min_overlap, (double)P.offset[n_bins])) && single == 0) {
+        const double logn = log(N);
+        const double hx = rn_sub(logn, tx / N), hy = rn_sub(logn, ty / N), hxy = rn_sub(logn, txy / N);
+        if (P.kind == MET2_REGISTER_MI) cost = fmin(-rn_sub(rn_add(hx, hy), hxy), 0.0);
+        else cost = fmin(-(rn_add(hx, hy) / hxy), -1.0);
+    }
+    P.n_inside[k] = n_in;
+    P.cost[k] = cost;
+}
+
 int rg_check_dims(const int32_t *d, const char *what)
 {
     if (!d) return fail(MET2_E_INVALID, std::string("NULL ") + what + " dims");
@@ -348,5 +450,78 @@ extern "C" int met2_register_cost(int32_t device, int32_t kind, const int32_t fi
     if (kind == MET2_REGISTER_CORRATIO) HIPCHK(rg_launch<MET2_REGISTER_CORRATIO>(P, K, st));
     if (kind == MET2_REGISTER_NORMCORR) HIPCHK(rg_launch<MET2_REGISTER_NORMCORR>(P, K, st));
     if (kind == MET2_REGISTER_LEASTSQ) HIPCHK(rg_launch<MET2_REGISTER_LEASTSQ>(P, K, st));
+    return MET2_OK;
+}
+
+namespace {
+
+int rg_check_joint_counts(int32_t n_bins, int32_t moving_bins, int32_t K)
+{
+    int rc;
+    if ((rc = rg_check_counts(n_bins, K))) return rc;
+    if (moving_bins < 1) return fail(MET2_E_INVALID, "moving_bins must be positive");
+    if (moving_bins > MET2_REGISTER_MAX_BINS) return fail(MET2_E_UNSUPPORTED, "more than 256 moving bins");
+    return MET2_OK;
+}
+
+int64_t rg_joint_bytes(int n_bins, int moving_bins, int K) { return rg_part_offset(K) + (int64_t)K * n_bins * moving_bins * 4; }
+
+}  // namespace
+
+extern "C" int met2_register_joint_work_bytes(const int32_t fixed_dims[3], int32_t n_bins, int32_t moving_bins, int32_t K, int64_t *work_bytes)
+{
+    int rc;
+    if ((rc = rg_check_dims(fixed_dims, "fixed")) || (rc = rg_check_joint_counts(n_bins, moving_bins, K))) return rc;
+    if (work_bytes) *work_bytes = rg_joint_bytes(n_bins, moving_bins, K);
+    return MET2_OK;
+}
+
+extern "C" int met2_register_joint_cost(int32_t device, int32_t kind, const int32_t fixed_dims[3], int32_t n_bins, const void *index,
+                                        const int32_t moving_dims[3], const double *moving, const double moving_range[2], int32_t moving_bins,
+                                        int32_t K, const double *A, double min_overlap, void *work, int64_t work_bytes, int64_t *n_inside,
+                                        double *cost, int32_t *joint, void *stream)
+{
+    int rc;
+    if (kind != MET2_REGISTER_MI && kind != MET2_REGISTER_NMI) return fail(MET2_E_INVALID, "kind must be MET2_REGISTER_MI or MET2_REGISTER_NMI");
+    if ((rc = rg_check_dims(fixed_dims, "fixed")) || (rc = rg_check_dims(moving_dims, "moving")) || (rc = rg_check_joint_counts(n_bins, moving_bins, K)))
+        return rc;
+    if (!index || !moving || !A || !work || !n_inside || !cost) return fail(MET2_E_INVALID, "NULL argument");
+    if ((rc = rg_check_range(moving_range, "moving"))) return rc;
+    for (int64_t e = 0; e < (int64_t)K * 12; ++e)
+        if (!std::isfinite(A[e])) return fail(MET2_E_INVALID, "every entry of every transform must be finite");
+    if (!(min_overlap >= 0.0 && min_overlap <= 1.0)) return fail(MET2_E_INVALID, "min_overlap must lie in [0, 1]");
+    if (work_bytes < rg_joint_bytes(n_bins, moving_bins, K))
+        return fail(MET2_E_INVALID, "the work space needs " + std::to_string(rg_joint_bytes(n_bins, moving_bins, K)) + " bytes");
+    if (((uintptr_t)work & 7) || ((uintptr_t)index & 3) || ((uintptr_t)joint & 3))
+        return fail(MET2_E_INVALID, "work must be aligned to 8 bytes, index and joint to 4");
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    RgJointArgs P;
+    P.nx = moving_dims[0]; P.ny = moving_dims[1]; P.nz = moving_dims[2];
+    P.mx = fixed_dims[0]; P.my = fixed_dims[1]; P.mz = fixed_dims[2];
+    P.n_bins = n_bins;
+    P.moving_bins = moving_bins;
+    P.kind = kind;
+    P.A = (const double *)work;
+    P.offset = (const int32_t *)index;
+    P.run_first = P.offset + n_bins + 1;
+    P.order = P.run_first + n_bins + 1;
+    P.moving = moving;
+    P.lo = moving_range[0];
+    P.scale = moving_range[1] > moving_range[0] ? (double)moving_bins / (moving_range[1] - moving_range[0]) : 0.0;
+    if (!std::isfinite(P.scale)) P.scale = 0.0;                    // a range so narrow that the quotient overflows counts as hi = lo
+    P.min_overlap = min_overlap;
+    P.worst = kind == MET2_REGISTER_MI ? MET2_REGISTER_MI_WORST : MET2_REGISTER_NMI_WORST;
+    P.table = (int32_t *)((char *)work + rg_part_offset(K));
+    P.n_inside = n_inside;
+    P.cost = cost;
+    const size_t table_bytes = (size_t)K * n_bins * moving_bins * 4;
+    HIPCHK(hipMemcpyAsync(work, A, (size_t)K * 12 * sizeof(double), hipMemcpyHostToDevice, st));       // A lives until the stream has run it: the header says so
+    HIPCHK(hipMemsetAsync(P.table, 0, table_bytes, st));           // in every call: the table of the call before is gone
+    hipLaunchKernelGGL(rg_joint_kernel, dim3((unsigned)rg_max_runs(fixed_dims, n_bins), (unsigned)K), dim3(RG_RUN), 0, st, P);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(rg_joint_final_kernel, dim3((unsigned)K), dim3(RG_RUN), 0, st, P);
+    HIPCHK(hipGetLastError());
+    if (joint) HIPCHK(hipMemcpyAsync(joint, P.table, table_bytes, hipMemcpyDeviceToDevice, st));
     return MET2_OK;
 }

@@ -309,7 +309,9 @@ def resample_labels_filter(labels, A, shape, fill=0, device=0):
 def register_filter(fixed, fixed_affine, moving, moving_affine, **options):
     """Rigid or affine registration of `moving` onto `fixed` (register.register states the search, met2_register_cost in include/met2_hip.h
     the similarity measures, which run on the device): numpy volumes [nx,ny,nz] with their voxel-to-world affines, `options` those of
-    register.register (dof=6, cost='corratio', n_bins, scales_mm, init, search_deg, mask, min_overlap, xtol, ftol, max_sweeps, batch, device).
+    register.register (dof=6, cost='corratio' | 'normcorr' | 'leastsq' | 'mi' | 'nmi', n_bins, scales_mm, init, search_deg, mask, min_overlap, xtol,
+    ftol, max_sweeps, batch, device).  'mi' and 'nmi' (mutual information and its normalised form, met2_register_joint_cost) assume only a
+    statistical dependence between the two contrasts: the measures to fall back to where 'corratio' locks onto the wrong structure.
     -> world [4, 4], fixed-world mm -> moving-world mm: what resample.voxel_matrix(fixed_affine, moving_affine, world) takes to bring
     `moving`, or a label image that lies in its space, onto the grid of `fixed`."""
     from . import register
@@ -323,7 +325,7 @@ def atlas_stats_filter(res, labels, labels_affine, affine, world=None, q=None, d
     image's (None: both share scanner space; resample.from_flirt reads a FLIRT matrix).  The labels are resampled onto the maps' grid
     (resample_labels_filter, nearest neighbour, 0 outside) and the statistics taken there.
     template [tx,ty,tz]: an intensity image in the label image's world space (template_affine; None: labels_affine), the atlas' anatomical
-    image.  `world` is then estimated: the template is registered (register_filter, options `register`: a dict) to `reference`, a volume on the
+    image.  `world` is then estimated: the template is registered (register_filter, options `register`: a dict, e.g. {"cost": "nmi"}) to `reference`, a volume on the
     maps' grid (None: res['TWC']).  A template together with a world matrix is refused.
     -> the dict of label_stats_filter plus labels_resampled [nx,ny,nz] int32, and, with a template, world [4, 4]."""
     from . import resample

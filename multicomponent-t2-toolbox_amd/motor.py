@@ -871,7 +871,7 @@ def motor_atlas_stats(path_to_save_data, path_to_labels, path_to_world=None, nam
     quantity) -- label, quantity, n, mean, std and the quantiles 0.025 .. 0.975; the last label, 'all', is every labelled voxel --, and
     table_roi_spectra.csv the T2 grid and per label the normalised mean spectrum (roi_stats_tables; `names` as there).  Runs on device 0.
     path_to_template: the atlas' intensity image, a NIfTI in the label image's world space, instead of path_to_world (both: refused).  The world
-    matrix is then estimated: the template is registered (register_filter; `register`: a dict of its options) to the maps' reference volume,
+    matrix is then estimated: the template is registered (register_filter; `register`: a dict of its options, e.g. {"cost": "nmi"} for normalised mutual information) to the maps' reference volume,
     Data_avg.nii.gz at path_to_save_data or, where that is absent, TWC.nii.gz.  template_to_maps_world.txt holds the matrix (np.savetxt; what
     path_to_world reads), template_to_maps_flirt.mat its FLIRT form (resample.to_flirt: `flirt -in <template> -ref <reference> -applyxfm
     -init` takes it), template_resampled.nii.gz the template on the maps' grid, trilinear, for a look.

@@ -1,7 +1,8 @@
 """Rigid and affine registration of two volumes: the estimate of the `world` matrix of resample.voxel_matrix (destination-world mm ->
 source-world mm) that brings a MOVING volume (the source) onto a FIXED volume (the destination).  The similarity of the two under a batch
 of candidate transforms is one launch on the device (met2_register_cost in include/met2_hip.h, which states the three measures and their
-sums; csrc/met2_register.hip); the search that proposes the candidates is here, in numpy, and is deterministic: no random restarts.
+sums; csrc/met2_register.hip); the search that proposes the candidates is here, in numpy, and is deterministic: no random restarts.  Mutual
+information and its normalised form ('mi', 'nmi') come from a joint histogram of both images (met2_register_joint_cost).
 
   params_to_world / world_to_params   the parametrisation, FLIRT's ordering: three rotations in degrees about `centre`, three translations in
                                       mm, then 1 (dof 7) or 3 scales, then 3 skews
@@ -14,7 +15,13 @@ Intensity rule.  Per pyramid level and per image, lo and hi are the 0.02 and 0.9
 fixed image: inside the mask); the image becomes clip((v - lo) / (hi - lo), 0, 1), all zeros where hi = lo, non-finite voxels 0.  The fixed
 image's bin is min(floor(n_bins s), n_bins - 1) of its scaled value s; a voxel outside the mask, or not finite, gets -1 and takes no part.
 
-Out of scope: mutual information, a mask or a weighting of the moving image, non-linear warps, motion correction from echo to echo.  Parity
+Histogram rule ('mi', 'nmi').  The joint histogram is square, B x B, and B is set per pyramid level: B = min(n_bins, max(4, c)) with c the
+integer cube root of n_included, the number of that level's fixed voxels that have a bin (level_bins).  A level of a few hundred voxels then
+has a handful of samples per cell; with 64 x 64 cells there it has far more cells than samples, every placement scores alike, and the search
+runs off (tests/test_register_mi_host.py keeps that case).  The moving image's bin is the library's: floor((y - lo) B / (hi - lo)) of the
+interpolated value, clamped to 0 .. B - 1, with (lo, hi) the range of the scaled moving image.
+
+Out of scope: Parzen-window or partial-volume histograms, a histogram that is not square in register, a mask or a weighting of the moving image, non-linear warps, motion correction from echo to echo.  Parity
 with FSL's flirt is unpinned: FSL was not available; the measures are the published ones (Roche et al., MICCAI 1998; Jenkinson & Smith,
 Med. Image Anal. 5:143-156, 2001; Jenkinson et al., NeuroImage 17:825-841, 2002)."""
 import ctypes as C
@@ -24,7 +31,8 @@ import numpy as np
 from . import resample
 from ._lib import _dp, check, lib
 
-KINDS = {"corratio": 0, "normcorr": 1, "leastsq": 2}          # MET2_REGISTER_CORRATIO, _NORMCORR, _LEASTSQ
+KINDS = {"corratio": 0, "normcorr": 1, "leastsq": 2, "mi": 3, "nmi": 4}      # MET2_REGISTER_CORRATIO, _NORMCORR, _LEASTSQ, _MI, _NMI
+JOINT_KINDS = ("mi", "nmi")                                   # scored from a joint histogram, by met2_register_joint_cost
 DOFS = (6, 7, 9, 12)
 MAX_AXIS, MAX_BINS, MAX_K = 512, 256, 256                     # MET2_REGISTER_MAX_AXIS, _MAX_BINS, _MAX_K
 LEASTSQ_WORST = 1.0e300                                       # MET2_REGISTER_LEASTSQ_WORST
@@ -32,8 +40,8 @@ ROBUST_Q = (0.02, 0.98)
 
 
 def worst(kind):
-    """the value a candidate without enough overlap, or without variance, gets"""
-    return LEASTSQ_WORST if _kind(kind) == 2 else 1.0
+    """the value a candidate without enough overlap, or without variance (mi, nmi: with one occupied row or column), gets"""
+    return {2: LEASTSQ_WORST, 3: 0.0, 4: -1.0}.get(_kind(kind), 1.0)
 
 
 # ---------------------------------------------------------------- the parametrisation (numpy, no device)
@@ -46,7 +54,7 @@ def _dof(dof):
 
 def _kind(kind):
     if kind not in KINDS:
-        raise ValueError("cost must be 'corratio', 'normcorr' or 'leastsq'")
+        raise ValueError("cost must be 'corratio', 'normcorr', 'leastsq', 'mi' or 'nmi'")
     return KINDS[kind]
 
 
@@ -156,10 +164,22 @@ def bin_intensity(scaled, n_bins, vol=None, mask=None):
     return b
 
 
-def _n_bins(n_bins):
+def _n_bins(n_bins, what="n_bins"):
     if isinstance(n_bins, bool) or int(n_bins) != n_bins or not 1 <= int(n_bins) <= MAX_BINS:
-        raise ValueError("n_bins must lie in 1 .. %d" % MAX_BINS)
+        raise ValueError("%s must lie in 1 .. %d" % (what, MAX_BINS))
     return int(n_bins)
+
+
+def level_bins(n_bins, n_included):
+    """the side B of the square joint histogram of 'mi' and 'nmi' on a level with n_included binned fixed voxels: min(n_bins, max(4, c)), c the
+    integer cube root of n_included (the largest c with c^3 <= n_included), so that the mean cell occupancy grows with the level"""
+    n = int(n_included)
+    c = int(round(max(n, 0) ** (1.0 / 3.0)))
+    while c ** 3 > n:
+        c -= 1
+    while (c + 1) ** 3 <= n:
+        c += 1
+    return min(_n_bins(n_bins), max(4, c))
 
 
 def _min_overlap(x):
@@ -202,16 +222,27 @@ def work_bytes(fixed_shape, n_bins, K):
     return a.value, b.value
 
 
+def joint_work_bytes(fixed_shape, n_bins, moving_bins, K):
+    """the bytes of met2_register_joint_cost's work space (met2_register_joint_work_bytes; no device needed)"""
+    a = C.c_int64(-1)
+    check(lib().met2_register_joint_work_bytes(resample._i3(_volume_dims(fixed_shape, "fixed")), int(n_bins), int(moving_bins), int(K), C.byref(a)))
+    return a.value
+
+
 # ---------------------------------------------------------------- the stage wrappers of the device cost
 
-def prepare(fixed, fixed_bin, moving, kind="corratio", n_bins=64, min_overlap=0.25, device=0):
+def prepare(fixed, fixed_bin, moving, kind="corratio", n_bins=64, min_overlap=0.25, device=0, moving_bins=None):
     """Everything of a cost that does not depend on the candidates, once per pair of volumes: the volumes on the device, the fixed voxels
     indexed by bin (met2_register_index), the ranges.  `fixed` and `moving` are used as they are (no scaling), `fixed_bin` int32 with -1 for
     voxels that take no part.  -> f(A_batch [K, 3, 4]) -> (n_inside [K] int64, cost [K]); numpy in, numpy out; device tensors in, tensors out.
-    This is also the signature a `cost_fn` of register has."""
+    This is also the signature a `cost_fn` of register has.  'mi' and 'nmi' go to met2_register_joint_cost: the moving samples fall into
+    `moving_bins` bins (default n_bins) over the moving volume's range, and f(A_batch, want_joint=True) -> (n_inside, cost, joint
+    [K, n_bins, moving_bins] int32), the joint histograms the costs were formed from."""
     import torch
     k = _kind(kind)
     n_bins, min_overlap = _n_bins(n_bins), _min_overlap(min_overlap)
+    joint_kind = kind in JOINT_KINDS
+    moving_bins = n_bins if moving_bins is None else _n_bins(moving_bins, "moving_bins")
     as_numpy = not torch.is_tensor(fixed)
     fdims = _volume_dims(fixed.shape, "fixed")
     mdims = _volume_dims(moving.shape, "moving")
@@ -232,30 +263,41 @@ def prepare(fixed, fixed_bin, moving, kind="corratio", n_bins=64, min_overlap=0.
         check(lib().met2_register_index(dev.index or 0, resample._i3(fdims), b.data_ptr(), n_bins, index.data_ptr(), index_bytes, stream))
     work, pending = {}, []                                         # pending: (event, transforms) of calls that may still read their host array
 
-    def evaluate(A_batch):
+    def evaluate(A_batch, want_joint=False):
         a = _batch(A_batch.cpu().numpy() if torch.is_tensor(A_batch) else A_batch)
         K = a.shape[0]
+        if want_joint and not joint_kind:
+            raise ValueError("only 'mi' and 'nmi' form a joint histogram")
         if K not in work:
-            work[K] = torch.empty((work_bytes(fdims, n_bins, K)[1] + 7) // 8, dtype=torch.float64, device=dev)
+            need = joint_work_bytes(fdims, n_bins, moving_bins, K) if joint_kind else work_bytes(fdims, n_bins, K)[1]
+            work[K] = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
         n_inside = torch.empty(K, dtype=torch.int64, device=dev)
         cost = torch.empty(K, dtype=torch.float64, device=dev)
+        joint = torch.empty((K, n_bins, moving_bins), dtype=torch.int32, device=dev) if want_joint else None
         with torch.cuda.device(dev):
-            check(lib().met2_register_cost(dev.index or 0, k, resample._i3(fdims), n_bins, index.data_ptr(), f.data_ptr(), frange, resample._i3(mdims),
-                                           m.data_ptr(), mrange, K, a.ctypes.data_as(_dp), min_overlap, work[K].data_ptr(), work[K].numel() * 8,
-                                           n_inside.data_ptr(), cost.data_ptr(), resample._stream(dev)))
+            if joint_kind:
+                check(lib().met2_register_joint_cost(dev.index or 0, k, resample._i3(fdims), n_bins, index.data_ptr(), resample._i3(mdims), m.data_ptr(), mrange,
+                                                     moving_bins, K, a.ctypes.data_as(_dp), min_overlap, work[K].data_ptr(), work[K].numel() * 8,
+                                                     n_inside.data_ptr(), cost.data_ptr(), joint.data_ptr() if want_joint else None, resample._stream(dev)))
+            else:
+                check(lib().met2_register_cost(dev.index or 0, k, resample._i3(fdims), n_bins, index.data_ptr(), f.data_ptr(), frange, resample._i3(mdims),
+                                               m.data_ptr(), mrange, K, a.ctypes.data_as(_dp), min_overlap, work[K].data_ptr(), work[K].numel() * 8,
+                                               n_inside.data_ptr(), cost.data_ptr(), resample._stream(dev)))
+        out = (n_inside, cost, joint) if want_joint else (n_inside, cost)
         if as_numpy:                                               # the copies wait for the stream: `a` has been read by then
-            return n_inside.cpu().numpy(), cost.cpu().numpy()
+            return tuple(x.cpu().numpy() for x in out)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(dev))
         pending[:] = [(e, x) for e, x in pending if not e.query()] + [(done, a)]    # met2_register_cost: A stays valid until its call has run
-        return n_inside, cost
+        return out
 
     return evaluate
 
 
 def cost(fixed, moving, A_batch, kind="corratio", n_bins=64, mask=None, min_overlap=0.25, device=0):
     """The cost of every candidate of A_batch [K, 3, 4] (fixed voxel indices -> continuous moving voxel coordinates) with the intensity rule of
-    this module applied to both volumes (n_bins counts for 'corratio'; the other two use one bin).  -> (n_inside [K] int64, cost [K]).  numpy in, numpy out; device tensors in, tensors out."""
+    this module applied to both volumes (n_bins counts for 'corratio', and for 'mi' and 'nmi', which bin both volumes with it; 'normcorr' and
+    'leastsq' use one bin).  -> (n_inside [K] int64, cost [K]).  numpy in, numpy out; device tensors in, tensors out."""
     import torch
     tens = torch.is_tensor(fixed)
     fx = fixed.cpu().numpy() if tens else np.asarray(fixed)
@@ -264,7 +306,7 @@ def cost(fixed, moving, A_batch, kind="corratio", n_bins=64, mask=None, min_over
     if mk is not None and mk.shape != fx.shape:
         raise ValueError("mask must have the shape of fixed")
     fs = scale_intensity(fx, mk)
-    nb = _n_bins(n_bins) if kind == "corratio" else 1
+    nb = _n_bins(n_bins) if kind == "corratio" or kind in JOINT_KINDS else 1
     n, c = prepare(fs, bin_intensity(fs, nb, fx, mk), scale_intensity(mv), kind, nb, min_overlap,
                    fixed.device.index if tens and fixed.is_cuda else device)(A_batch)
     if not tens:
@@ -360,7 +402,9 @@ def register(fixed, fixed_affine, moving, moving_affine, dof=6, cost="corratio",
     """Estimate `world` (fixed-world mm -> moving-world mm; resample.voxel_matrix(fixed_affine, moving_affine, world) then resamples `moving`
     onto the grid of `fixed`).  numpy volumes [nx,ny,nz] with their voxel-to-world affines.
     dof 6 (rigid), 7 (+ one scale), 9 (+ three scales) or 12 (+ skews); cost 'corratio' (images of different contrast; flirt's default),
-    'normcorr' or 'leastsq' (the same contrast); n_bins of the fixed image for corratio (the other two put every voxel that counts in one bin:
+    'normcorr' or 'leastsq' (the same contrast), 'mi' or 'nmi' (mutual information and Studholme's normalised mutual information, negated so
+    that smaller is better: only a statistical dependence of the two contrasts is assumed; their joint histogram is square and sized per level,
+    B = min(n_bins, max(4, integer cube root of the level's binned fixed voxels)) -- the histogram rule of this module); n_bins of the fixed image for corratio (normcorr and leastsq put every voxel that counts in one bin:
     the member list then runs in voxel order, and the reads of the fixed image are contiguous).  `mask` [nx,ny,nz] selects the fixed voxels that count.
     Levels: scales_mm, coarse to fine (default 4, 2 and 1 times the fixed image's smallest voxel size); both images go on isotropic grids of that
     voxel size (pyramid), are scaled and binned by the intensity rule of this module per level; the mask goes through the same interpolation and
@@ -377,7 +421,7 @@ def register(fixed, fixed_affine, moving, moving_affine, dof=6, cost="corratio",
     min(1 / 2, 3 / (batch - 1)) until it is below xtol voxels of the level.  A sweep searches every direction, then the sweep's displacement,
     which replaces the direction of the largest decrease; a stage ends after max_sweeps sweeps or when a sweep gains less than ftol.
     cost_fn(fixed, fixed_bin, moving, kind, n_bins, min_overlap) -> f(A_batch) -> (n_inside, cost) replaces the device cost (prepare has this
-    signature), `filters` the device filters of pyramid: the search then needs no device.
+    signature; for 'mi' and 'nmi' n_bins is the level's B and fixed_bin has B bins), `filters` the device filters of pyramid: the search then needs no device.
     -> dict(world [4, 4], params [dof] (about `centre`), centre [3] = the fixed image's centre of mass, cost, n_inside, dof, levels: one entry
     per (level, stage) in the order they ran, dict(scale_mm, shape, dof: the stage's, cost: at the stage's end, n_eval and n_calls: the
     candidates scored and the cost calls made by that stage alone -- a level's first stage includes the level's first score and the
@@ -437,7 +481,9 @@ def register(fixed, fixed_affine, moving, moving_affine, dof=6, cost="corratio",
             own_grid = fv.shape == fx.shape and np.array_equal(faff, fa)
             lmask = mk if own_grid else filt[1](mk.astype(np.float64), (resample.invert(fa) @ faff)[:3], fv.shape) >= 0.5
         fs = scale_intensity(fv, lmask)
-        nb = n_bins if kind == "corratio" else 1                    # the other two have no use for bins: one bin keeps the voxels in their order
+        nb = n_bins if kind == "corratio" else 1                    # normcorr and leastsq have no use for bins: one bin keeps the voxels in their order
+        if kind in JOINT_KINDS:                                     # the histogram rule: the voxels that get a bin do not depend on the number of bins
+            nb = level_bins(n_bins, int((bin_intensity(fs, 1, fv, lmask) >= 0).sum()))
         evaluate = make(fs, bin_intensity(fs, nb, fv, lmask), scale_intensity(mvol), kind, nb, min_overlap, **kw)
         count = {"n_eval": 0, "n_calls": 0}
 

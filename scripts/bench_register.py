@@ -10,7 +10,13 @@
    40 x 36 x 32 and 44 x 40 x 36 voxels), wall clock with the device costs and with the numpy restatement in fp64 (tests/tools/register_numpy.py)
    as cost_fn, its candidates dealt to `threads` threads, the pyramid on the CPU (scipy): after a warm-up the median of `reg-reps` device runs
    and of `numpy-reps` restatement runs, the two alternating, every single time kept beside it (a run is a fraction of a second).  Both runs take the same path unless a comparison ties
-   in the last bits; the mean displacement from the true transform is given for both."""
+   in the last bits; the mean displacement from the true transform is given for both.
+With --kinds mi nmi (any of the two) the mutual-information costs are measured instead, into profiles/register_mi_bench.json; the default output
+is untouched:
+1. One launch of met2_register_joint_cost (the H2D copy of the transforms, the table's memset, the histogram kernel and the final kernel) at
+   64 x 64 bins for K = 1, 16 and 64, next to one launch of 'corratio' at 64 bins on the same inputs and candidates, the two alternating; the
+   ratio of the medians is what the histogram costs on top of corratio's sampling.
+2. One whole 6-dof registration per kind of the 1 mm phantom, device against the fp64 restatement (tests/tools/register_mi_numpy.py), as above."""
 import argparse
 import importlib
 import json
@@ -76,8 +82,10 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reg-reps", type=int, default=7)
     ap.add_argument("--numpy-reps", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "register_bench.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--kinds", nargs="+", choices=("mi", "nmi"), default=None, help="measure these mutual-information costs instead (-> profiles/register_mi_bench.json)")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "register_mi_bench.json" if a.kinds else "register_bench.json")
     assert torch.cuda.is_available(), "the benchmark needs the device"
     import register_numpy as gn
     reg = importlib.import_module(PKG + ".register")
@@ -92,6 +100,8 @@ def main():
     dev = torch.device("cuda", 0)
     tf, tm, tb = torch.as_tensor(fixed, device=dev), torch.as_tensor(moving, device=dev), torch.as_tensor(bins, device=dev)
     rows = {"shape": list(shape), "reps": a.reps, "device": torch.cuda.get_device_name(0), "cost_launch": [], "registration": []}
+    if a.kinds:
+        return main_mi(a, gn, reg, shape, tf, tm, tb, rows)
     for kind in gn.KINDS:
         nb = 64 if kind == "corratio" else 1                       # as register.register calls it
         f = reg.prepare(tf, tb if nb == 64 else torch.zeros_like(tb), tm, kind, nb, 0.25)
@@ -129,6 +139,64 @@ def main():
                 host_s.append(time.perf_counter() - t0)
         t_dev, t_host = float(np.median(dev_s)), float(np.median(host_s))
         rows["registration"].append({"case": name, "dof": dof, "cost": kind, "fixed_shape": list(fx.shape), "moving_shape": list(mv.shape), "voxel_mm": a.voxel,
+                                     "levels_mm": [l["scale_mm"] for l in out["levels"]], "n_eval": sum(l["n_eval"] for l in out["levels"]),
+                                     "n_launches": sum(l["n_calls"] for l in out["levels"]), "device_s": t_dev, "device_s_all": dev_s, "numpy_threads": a.threads,
+                                     "numpy_s": t_host, "numpy_s_all": host_s, "numpy_n_eval": sum(l["n_eval"] for l in ref["levels"]), "numpy_over_device": t_host / t_dev,
+                                     "mean_displacement_mm": gn.mean_displacement(out["world"], true_world, mask, fa),
+                                     "numpy_mean_displacement_mm": gn.mean_displacement(ref["world"], true_world, mask, fa)})
+        print(json.dumps(rows["registration"][-1]))
+    with open(a.out, "w") as f:
+        json.dump(rows, f, indent=1)
+        f.write("\n")
+
+
+def main_mi(a, gn, reg, shape, tf, tm, tb, rows):
+    import register_mi_numpy as mn
+    corratio = reg.prepare(tf, tb, tm, "corratio", 64, 0.25)
+    for kind in a.kinds:
+        f = reg.prepare(tf, tb, tm, kind, 64, 0.25)                # 64 x 64 cells
+        for K in (1, 16, 64):
+            A = transforms(shape, K, np.random.default_rng(K))
+            (ms, cr_ms), (lo, cr_lo), (hi, cr_hi) = device_ms([lambda: f(A), lambda: corratio(A)], a.reps)
+            rows["cost_launch"].append({"cost": kind, "n_bins": 64, "moving_bins": 64, "K": K, "launch_ms": ms, "launch_ms_min": lo, "launch_ms_max": hi,
+                                        "ms_per_candidate": ms / K, "corratio_ms": cr_ms, "corratio_ms_min": cr_lo, "corratio_ms_max": cr_hi,
+                                        "over_corratio": ms / cr_ms})
+            print(json.dumps(rows["cost_launch"][-1]))
+    pool = ThreadPoolExecutor(a.threads)
+
+    def threaded(fixed_, bin_, moving_, kind_, n_bins_, min_overlap_):
+        bin_, moving_ = np.asarray(bin_), np.asarray(moving_, dtype=np.float64)
+        mrange = mn.range_of(moving_)
+
+        def one(m):
+            y, ins = gn.sample(moving_, m, bin_.shape, np.float64)
+            n, n_incl, joint = mn.joint_of_sample(bin_, mrange, y, ins, n_bins_, n_bins_)
+            return n, mn.cost_of_joint(joint, kind_, n_incl, min_overlap_, np.float64)
+
+        def evaluate(A):
+            out = list(pool.map(one, A))
+            return np.array([o[0] for o in out], dtype=np.int64), np.array([o[1] for o in out])
+        return evaluate
+
+    p, dof, _, _ = gn.E2E_CASES["rigid6"]
+    true_world = reg.params_to_world(p, dof, centre=gn.TRUE_CENTRE)
+    fx, fa, mv, ma, mask = phantom_pair(gn, true_world, a.voxel)
+    for kind in a.kinds:
+        reg.register(fx, fa, mv, ma, dof=6, cost=kind, scales_mm=[8.0], max_sweeps=1)          # warm-up: code objects, allocator
+        torch.cuda.synchronize()
+        dev_s, host_s = [], []
+        for rep in range(max(a.reg_reps, a.numpy_reps)):              # the two legs alternate
+            if rep < a.reg_reps:
+                t0 = time.perf_counter()
+                out = reg.register(fx, fa, mv, ma, dof=dof, cost=kind)
+                torch.cuda.synchronize()
+                dev_s.append(time.perf_counter() - t0)
+            if rep < a.numpy_reps:
+                t0 = time.perf_counter()
+                ref = reg.register(fx, fa, mv, ma, dof=dof, cost=kind, cost_fn=threaded, filters=gn.FILTERS)
+                host_s.append(time.perf_counter() - t0)
+        t_dev, t_host = float(np.median(dev_s)), float(np.median(host_s))
+        rows["registration"].append({"case": "rigid6_" + kind, "dof": dof, "cost": kind, "fixed_shape": list(fx.shape), "moving_shape": list(mv.shape), "voxel_mm": a.voxel,
                                      "levels_mm": [l["scale_mm"] for l in out["levels"]], "n_eval": sum(l["n_eval"] for l in out["levels"]),
                                      "n_launches": sum(l["n_calls"] for l in out["levels"]), "device_s": t_dev, "device_s_all": dev_s, "numpy_threads": a.threads,
                                      "numpy_s": t_host, "numpy_s_all": host_s, "numpy_n_eval": sum(l["n_eval"] for l in ref["levels"]), "numpy_over_device": t_host / t_dev,
