@@ -1,6 +1,7 @@
-// bias_common.hpp -- what met2_bias.hip (bias-field correction) and met2_seg.hip (tissue segmentation) share: the device record, the fixed-order
-// sums, the kernels of the domain (log, scan, compact), of the initial classes (stat1, stat2, init) and of the EM step (E-step, M-step), and the
-// host code that enqueues them.  Everything sits in an unnamed namespace: each translation unit compiles its own copy from this one text.
+// bias_common.hpp -- what met2_bias.hip (bias-field correction), met2_seg.hip (tissue segmentation) and met2_pve.hip (partial volume) share: the
+// device record, the block scan, the kernels of the domain (log, scan, compact), of the initial classes (stat1, stat2, init) and of the EM step
+// (E-step, M-step), and the host code that enqueues them.  The fixed-order sums come from device_helpers.hpp, the work space and the entries'
+// common ending from device_work.hpp.  Everything sits in an unnamed namespace: each translation unit compiles its own copy from this one text.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,6 +11,8 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "device_helpers.hpp"
+#include "device_work.hpp"
 
 namespace {
 
@@ -27,22 +30,6 @@ struct BiasStats {
     double mu[BIAS_MAX_K], var[BIAS_MAX_K], pi[BIAS_MAX_K], lc[BIAS_MAX_K];     // lc = log pi - log(var) / 2
     uint32_t hist[BIAS_NBINS];
 };
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);          // every lane adds the same two numbers: the same bits in all lanes
-    return v;
-}
-
-// the sum over a workgroup of 256 threads in a fixed order, returned to every thread; red: 4 doubles of LDS
-__device__ __forceinline__ double block_sum(double v, double *red)
-{
-    v = wave_sum(v);
-    __syncthreads();                                                  // the previous call's readers are done
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // inclusive scan over the 256 threads; sc: 256 ints of LDS
 __device__ __forceinline__ int block_scan(int x, int *sc)
@@ -357,8 +344,6 @@ BiasGrid bias_grid(int64_t n)
     return g;
 }
 
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-
 // y, dom, the chunks' counts and offsets, idx[0..N), S->N
 void enq_domain(hipStream_t st, const BiasGrid &g, const double *v, const uint8_t *mask, double *y, uint8_t *dom, int32_t *cnt, int32_t *off,
                 int32_t *idx, BiasStats *S)
@@ -385,16 +370,6 @@ void enq_em_step(hipStream_t st, const BiasGrid &g, const double *y, const doubl
     const dim3 T(256), GC(g.nch), G1(1);
     hipLaunchKernelGGL(bias_estep_kernel<false>, GC, T, 0, st, y, b, idx, S, K, g.nch, part, (double2 *)nullptr);
     hipLaunchKernelGGL(bias_mstep_kernel, G1, T, 0, st, part, g.nch, S, K);
-}
-
-// what every stage entry does last: wait, give the work space back, report
-int bias_finish(const char *who, hipError_t err, hipStream_t st, void *work)
-{
-    if (err == hipSuccess) err = hipGetLastError();
-    const hipError_t e = hipStreamSynchronize(st);
-    if (err == hipSuccess) err = e;
-    (void)hipFree(work);
-    return err == hipSuccess ? MET2_OK : fail(MET2_E_HIP, std::string(who) + ": " + hipGetErrorString(err));
 }
 
 }  // namespace

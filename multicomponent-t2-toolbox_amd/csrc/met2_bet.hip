@@ -29,6 +29,8 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "device_helpers.hpp"
+#include "device_work.hpp"
 
 #pragma clang fp contract(off)
 
@@ -44,22 +46,6 @@ namespace {
 #define BET_L_EVERY 50
 #define BET_RMIN 3.33
 #define BET_RMAX 10.0
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);          // every lane adds the same two numbers: the same bits in all lanes
-    return v;
-}
-
-// the sum over a workgroup of 256 threads in a fixed order, returned to every thread; red: 4 doubles of LDS
-__device__ __forceinline__ double block_sum(double v, double *red)
-{
-    v = wave_sum(v);
-    __syncthreads();                                                  // the previous call's readers are done
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 __global__ __launch_bounds__(256) void bet_mean_kernel(const double *__restrict__ data, int64_t n, int nt, double *__restrict__ out)
 {
@@ -171,6 +157,7 @@ __global__ __launch_bounds__(256) void bet_cog_kernel(const double *__restrict__
 }
 
 // keys in the order of the values they stand for
+// (not to_key of met2_stats.hip or tv_key of met2_tv.hip: the median set holds finite values only, and -0.0 keeps its own key below +0.0's)
 __device__ __forceinline__ uint64_t sort_key(double x)
 {
     const uint64_t b = (uint64_t)__double_as_longlong(x);
@@ -301,7 +288,7 @@ __global__ __launch_bounds__(BET_T) void bet_evolve_kernel(EvolveArgs A)
                 }
                 s += sv;
             }
-            s = wave_sum(s);
+            s = wave_sum_xor(s);
             if ((tid & 63) == 0) red[tid >> 6] = s;                    // the last readers of red are a barrier behind
             __syncthreads();
             double tot = 0.0;
@@ -528,29 +515,22 @@ int stats_host(const double *v, const Grid &g, double st[8], int64_t *count, hip
     const int64_t n = (int64_t)g.nx * g.ny * g.nz;
     if (n == 0) return fail(MET2_E_INVALID, "brain extraction: the set v > t is empty (no voxel)");
     const int nch = (int)((n + BET_CHUNK - 1) / BET_CHUNK);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t b_part = up((size_t)nch * 8), b_cnt = up((size_t)nch * 4), b_hist = up(BET_NBINS * 4), b_res = 256;
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, 4 * b_part + b_cnt + b_hist + b_res));
-    double *part = (double *)work;
-    int32_t *pcnt = (int32_t *)(work + 4 * b_part);
-    uint32_t *hist = (uint32_t *)(work + 4 * b_part + b_cnt);
-    unsigned long long *res = (unsigned long long *)(work + 4 * b_part + b_cnt + b_hist);
+    DeviceWork W(s);
+    const auto part = W.take<double>((size_t)4 * nch);                 // four rows of partials, which the kernels address at stride nch: one piece serves
+    const auto pcnt = W.take<int32_t>(nch);
+    const auto hist = W.take<uint32_t>(BET_NBINS);
+    const auto res = W.take<unsigned long long>(2);
+    if (!W.alloc()) return W.finish("met2_bet_stats");
     std::vector<double> hp((size_t)4 * nch);
     std::vector<int32_t> hc(nch);
     std::vector<uint32_t> hh(BET_NBINS);
-    int rc = MET2_OK;
-    hipError_t err = hipSuccess;
-    auto ok = [&](hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; return err == hipSuccess; };
-    auto done = [&](int code, const char *msg) { (void)hipFree(work); return code == MET2_OK ? MET2_OK : fail(code, msg); };
     const dim3 T(256), GC(nch);
 
     hipLaunchKernelGGL(bet_range_kernel, GC, T, 0, s, v, n, part, part + nch, pcnt);
-    ok(hipGetLastError());
-    ok(hipMemcpyAsync(hp.data(), part, (size_t)2 * nch * 8, hipMemcpyDeviceToHost, s));
-    ok(hipMemcpyAsync(hc.data(), pcnt, (size_t)nch * 4, hipMemcpyDeviceToHost, s));
-    ok(hipStreamSynchronize(s));
-    if (err != hipSuccess) { rc = fail(MET2_E_HIP, std::string("met2_bet_stats: ") + hipGetErrorString(err)); (void)hipFree(work); return rc; }
+    W.ok(hipGetLastError());
+    W.ok(hipMemcpyAsync(hp.data(), part, (size_t)2 * nch * 8, hipMemcpyDeviceToHost, s));
+    W.ok(hipMemcpyAsync(hc.data(), pcnt, (size_t)nch * 4, hipMemcpyDeviceToHost, s));
+    if (!W.ok(hipStreamSynchronize(s))) return W.finish("met2_bet_stats");
     double lo = INFINITY, hi = -INFINITY;
     int64_t N = 0;
     for (int c = 0; c < nch; ++c) {
@@ -558,14 +538,13 @@ int stats_host(const double *v, const Grid &g, double st[8], int64_t *count, hip
         hi = std::fmax(hi, hp[nch + c]);
         N += hc[c];
     }
-    if (N == 0 || !(hi > lo)) return done(MET2_E_INVALID, "brain extraction: the set v > t is empty (no finite voxel, or a constant volume)");
+    if (N == 0 || !(hi > lo)) return fail(MET2_E_INVALID, "brain extraction: the set v > t is empty (no finite voxel, or a constant volume)");
 
-    ok(hipMemsetAsync(hist, 0, b_hist, s));
+    W.ok(hipMemsetAsync(hist, 0, hist.bytes, s));
     hipLaunchKernelGGL(bet_hist_kernel, GC, T, 0, s, v, n, lo, hi, hist);
-    ok(hipGetLastError());
-    ok(hipMemcpyAsync(hh.data(), hist, BET_NBINS * 4, hipMemcpyDeviceToHost, s));
-    ok(hipStreamSynchronize(s));
-    if (err != hipSuccess) { rc = fail(MET2_E_HIP, std::string("met2_bet_stats: ") + hipGetErrorString(err)); (void)hipFree(work); return rc; }
+    W.ok(hipGetLastError());
+    W.ok(hipMemcpyAsync(hh.data(), hist, BET_NBINS * 4, hipMemcpyDeviceToHost, s));
+    if (!W.ok(hipStreamSynchronize(s))) return W.finish("met2_bet_stats");
     int j2 = -1, j98 = -1;
     int64_t C = 0;
     for (int j = 0; j < BET_NBINS; ++j) {
@@ -578,18 +557,17 @@ int stats_host(const double *v, const Grid &g, double st[8], int64_t *count, hip
     const double t = t2 + 0.1 * (t98 - t2);
 
     hipLaunchKernelGGL(bet_cog_kernel, GC, T, 0, s, v, n, g, t, t2, t98, nch, part, pcnt);
-    ok(hipGetLastError());
-    ok(hipMemcpyAsync(hp.data(), part, (size_t)4 * nch * 8, hipMemcpyDeviceToHost, s));
-    ok(hipMemcpyAsync(hc.data(), pcnt, (size_t)nch * 4, hipMemcpyDeviceToHost, s));
-    ok(hipStreamSynchronize(s));
-    if (err != hipSuccess) { rc = fail(MET2_E_HIP, std::string("met2_bet_stats: ") + hipGetErrorString(err)); (void)hipFree(work); return rc; }
+    W.ok(hipGetLastError());
+    W.ok(hipMemcpyAsync(hp.data(), part, (size_t)4 * nch * 8, hipMemcpyDeviceToHost, s));
+    W.ok(hipMemcpyAsync(hc.data(), pcnt, (size_t)nch * 4, hipMemcpyDeviceToHost, s));
+    if (!W.ok(hipStreamSynchronize(s))) return W.finish("met2_bet_stats");
     double sum[4] = {0.0, 0.0, 0.0, 0.0};
     int64_t cnt = 0;
     for (int c = 0; c < nch; ++c) {
         for (int q = 0; q < 4; ++q) sum[q] += hp[(size_t)q * nch + c];
         cnt += hc[c];
     }
-    if (cnt == 0 || !(sum[0] > 0.0)) return done(MET2_E_INVALID, "brain extraction: the set v > t is empty");
+    if (cnt == 0 || !(sum[0] > 0.0)) return fail(MET2_E_INVALID, "brain extraction: the set v > t is empty");
     Sphere sp;
     sp.cx = sum[1] / sum[0];
     sp.cy = sum[2] / sum[0];
@@ -604,12 +582,12 @@ int stats_host(const double *v, const Grid &g, double st[8], int64_t *count, hip
     uint64_t decided = 0, prefix = 0;
     int64_t n_tm = 0, rank = 0;
     uint32_t h256[256];
-    for (int shift = 56; shift >= 0 && err == hipSuccess; shift -= 8) {
-        ok(hipMemsetAsync(hist, 0, 256 * 4, s));
+    for (int shift = 56; shift >= 0 && W.ok(); shift -= 8) {
+        W.ok(hipMemsetAsync(hist, 0, 256 * 4, s));
         hipLaunchKernelGGL(bet_select_kernel, GC, T, 0, s, v, n, g, sp, decided, prefix, shift, hist);
-        ok(hipGetLastError());
-        ok(hipMemcpyAsync(h256, hist, 256 * 4, hipMemcpyDeviceToHost, s));
-        if (!ok(hipStreamSynchronize(s))) break;
+        W.ok(hipGetLastError());
+        W.ok(hipMemcpyAsync(h256, hist, 256 * 4, hipMemcpyDeviceToHost, s));
+        if (!W.ok(hipStreamSynchronize(s))) break;
         if (shift == 56) {
             for (int b = 0; b < 256; ++b) n_tm += h256[b];
             if (n_tm == 0) break;
@@ -621,7 +599,7 @@ int stats_host(const double *v, const Grid &g, double st[8], int64_t *count, hip
         decided |= 0xffULL << shift;
     }
     double tm = t;                                                     // nothing to take the median of
-    if (err == hipSuccess && n_tm > 0) {
+    if (W.ok() && n_tm > 0) {
         auto value = [](uint64_t key) {
             const uint64_t bits = (key >> 63) ? key & 0x7fffffffffffffffULL : ~key;
             double x;
@@ -632,18 +610,17 @@ int stats_host(const double *v, const Grid &g, double st[8], int64_t *count, hip
         tm = a;
         if (n_tm % 2 == 0) {
             unsigned long long init[2] = {0ULL, ~0ULL}, got[2] = {0ULL, ~0ULL};
-            ok(hipMemcpyAsync(res, init, 16, hipMemcpyHostToDevice, s));
+            W.ok(hipMemcpyAsync(res, init, 16, hipMemcpyHostToDevice, s));
             hipLaunchKernelGGL(bet_upper_kernel, GC, T, 0, s, v, n, g, sp, prefix, res);
-            ok(hipGetLastError());
-            ok(hipMemcpyAsync(got, res, 16, hipMemcpyDeviceToHost, s));
-            ok(hipStreamSynchronize(s));
+            W.ok(hipGetLastError());
+            W.ok(hipMemcpyAsync(got, res, 16, hipMemcpyDeviceToHost, s));
+            W.ok(hipStreamSynchronize(s));
             const int64_t k1 = (n_tm - 1) / 2 + 1;                     // the upper middle's rank
             const double b = (int64_t)got[0] > k1 ? a : value(got[1]);
             tm = (a + b) / 2.0;
         }
     }
-    (void)hipFree(work);
-    if (err != hipSuccess) return fail(MET2_E_HIP, std::string("met2_bet_stats: ") + hipGetErrorString(err));
+    if (int rc = W.finish("met2_bet_stats")) return rc;
     st[0] = t2; st[1] = t; st[2] = t98; st[3] = tm; st[4] = sp.cx; st[5] = sp.cy; st[6] = sp.cz; st[7] = r;
     if (count) *count = cnt;
     return MET2_OK;
@@ -660,9 +637,9 @@ int evolve_host(const double *v, const Grid &g, const double st[8], double f, co
         degsum += M.deg[i];
         for (int k = 0; k < 6; ++k) ring[(size_t)i * 6 + k] = (int16_t)M.ring[(size_t)i * 6 + k];
     }
-    const size_t b_ring = ((size_t)nv * 12 + 255) / 256 * 256;
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_ring));
+    DeviceWork W(s);
+    const auto dring = W.take<int16_t>((size_t)nv * 6);
+    if (!W.alloc()) return W.finish("met2_bet_evolve");
     EvolveArgs A;
     A.v = v;
     A.g = g;
@@ -673,20 +650,12 @@ int evolve_host(const double *v, const Grid &g, const double st[8], double f, co
     A.bt = std::pow(f, 0.275);
     A.nv = nv; A.n_iter = n_iter; A.degsum = degsum;
     A.xin = xin; A.xout = xout;
-    A.ring = (const int16_t *)work;
+    A.ring = dring;
     const int lds = 2 * 3 * nv * 8 + nv * 12;                          // positions and rings: 153 720 bytes at level 4, of the CU's 160 KiB
-    hipError_t err = hipSuccess;
-    auto ok = [&](hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; return err == hipSuccess; };
-    ok(hipMemcpyAsync(work, ring.data(), (size_t)nv * 12, hipMemcpyHostToDevice, s));
-    ok(hipFuncSetAttribute((const void *)bet_evolve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL(bet_evolve_kernel, dim3(1), dim3(BET_T), lds, s, A);
-        ok(hipGetLastError());
-    }
-    ok(hipStreamSynchronize(s));                                       // the host tables live until here
-    (void)hipFree(work);
-    if (err != hipSuccess) return fail(MET2_E_HIP, std::string("met2_bet_evolve: ") + hipGetErrorString(err));
-    return MET2_OK;
+    W.ok(hipMemcpyAsync(dring, ring.data(), (size_t)nv * 12, hipMemcpyHostToDevice, s));
+    W.ok(hipFuncSetAttribute((const void *)bet_evolve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if (W.ok()) hipLaunchKernelGGL(bet_evolve_kernel, dim3(1), dim3(BET_T), lds, s, A);
+    return W.finish("met2_bet_evolve");                                // waits: the host tables live until here
 }
 
 int fill_host(const Grid &g, int nv, const double *X, int ntri, const int32_t *tri, uint8_t *mask, hipStream_t s)
@@ -781,23 +750,18 @@ extern "C" int met2_brain_mask(int32_t device, int32_t nx, int32_t ny, int32_t n
     const double half = 0.5 * st[7];
     for (int i = 0; i < nv; ++i)
         for (int a = 0; a < 3; ++a) x0[(size_t)3 * i + a] = st[4 + a] + M.unit[(size_t)3 * i + a] * half;
-    const size_t b_x = ((size_t)nv * 24 + 255) / 256 * 256;
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_x + (size_t)nt * 12));
-    double *X = (double *)work;
-    int32_t *tri = (int32_t *)(work + b_x);
-    hipError_t err = hipSuccess;
-    auto ok = [&](hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; return err == hipSuccess; };
-    ok(hipMemcpyAsync(X, x0.data(), (size_t)nv * 24, hipMemcpyHostToDevice, s));
-    ok(hipMemcpyAsync(tri, M.tri.data(), (size_t)nt * 12, hipMemcpyHostToDevice, s));
+    DeviceWork W(s);
+    const auto X = W.take<double>((size_t)nv * 3);
+    const auto tri = W.take<int32_t>((size_t)nt * 3);
+    if (!W.alloc()) return W.finish("met2_brain_mask");
+    W.ok(hipMemcpyAsync(X, x0.data(), (size_t)nv * 24, hipMemcpyHostToDevice, s));
+    W.ok(hipMemcpyAsync(tri, M.tri.data(), (size_t)nt * 12, hipMemcpyHostToDevice, s));
     int rc = MET2_OK;
-    if (err == hipSuccess) rc = evolve_host(v, g, st, f, M, n_iter, X, X, s);          // waits: x0 lives until here
-    if (err == hipSuccess && rc == MET2_OK) rc = fill_host(g, nv, X, nt, tri, mask_out, s);
-    if (err == hipSuccess && rc == MET2_OK && vertices_out) ok(hipMemcpyAsync(vertices_out, X, (size_t)nv * 24, hipMemcpyDeviceToDevice, s));
-    ok(hipStreamSynchronize(s));                                       // the work space goes back before the call returns
-    (void)hipFree(work);
-    if (rc != MET2_OK) return rc;
-    if (err != hipSuccess) return fail(MET2_E_HIP, std::string("met2_brain_mask: ") + hipGetErrorString(err));
+    if (W.ok()) rc = evolve_host(v, g, st, f, M, n_iter, X, X, s);                   // waits: x0 lives until here
+    if (W.ok() && rc == MET2_OK) rc = fill_host(g, nv, X, nt, tri, mask_out, s);
+    if (rc != MET2_OK) return rc;                                      // (the work space goes back behind a wait on this return too)
+    if (W.ok() && vertices_out) W.ok(hipMemcpyAsync(vertices_out, X, (size_t)nv * 24, hipMemcpyDeviceToDevice, s));
+    if (int e = W.finish("met2_brain_mask")) return e;
     if (stats_out) std::copy(st, st + 8, stats_out);
     return MET2_OK;
 }

@@ -231,52 +231,38 @@ extern "C" int met2_bias_field(int32_t device, int32_t nx, int32_t ny, int32_t n
 
     const BiasGrid g = bias_grid(n);
     const int nch = g.nch;
-    const size_t b_d = up256((size_t)n * 8), b_rw = up256((size_t)n * 16), b_idx = up256((size_t)n * 4), b_dom = up256((size_t)n),
-                 b_cnt = up256((size_t)nch * 4);
-    const size_t b_part = up256((size_t)nch * 3 * BIAS_MAX_K * 8), b_st = up256(sizeof(BiasStats)), b_w = up256(hw.size() * 8);
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, 2 * b_d + 2 * b_rw + b_idx + b_dom + 2 * b_cnt + b_part + b_st + b_w));
-    char *at = work;
-    auto take = [&at](size_t b) { char *p = at; at += b; return p; };
-    double *y = (double *)take(b_d), *b = (double *)take(b_d);
-    double2 *RA = (double2 *)take(b_rw), *RB = (double2 *)take(b_rw);
-    int32_t *idx = (int32_t *)take(b_idx);
-    uint8_t *dom = (uint8_t *)take(b_dom);
-    int32_t *cnt = (int32_t *)take(b_cnt), *off = (int32_t *)take(b_cnt);
-    double *part = (double *)take(b_part);
-    BiasStats *S = (BiasStats *)take(b_st);
-    double *wd = (double *)take(b_w);
+    DeviceWork W(st);
+    const auto y = W.take<double>(n), b = W.take<double>(n);
+    const auto RA = W.take<double2>(n), RB = W.take<double2>(n);
+    const auto idx = W.take<int32_t>(n);
+    const auto dom = W.take<uint8_t>(n);
+    const auto cnt = W.take<int32_t>(nch), off = W.take<int32_t>(nch);
+    const auto part = W.take<double>((size_t)nch * 3 * BIAS_MAX_K);
+    const auto S = W.take<BiasStats>(1);
+    const auto wd = W.take<double>(hw.size());
+    if (!W.alloc()) return W.finish("met2_bias_field");
 
-    int rc = MET2_OK;
-    hipError_t err = hipSuccess;
-    auto ok = [&](hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; return err == hipSuccess; };
-    ok(hipMemsetAsync(S, 0, b_st, st));
-    ok(hipMemsetAsync(b, 0, b_d, st));
-    ok(hipMemcpyAsync(wd, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, st));      // hw lives until the wait below
-    if (err == hipSuccess) {
+    W.ok(hipMemsetAsync(S, 0, S.bytes, st));
+    W.ok(hipMemsetAsync(b, 0, b.bytes, st));
+    W.ok(hipMemcpyAsync(wd, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, st));    // hw lives until the wait below
+    if (W.ok()) {
         enq_domain(st, g, v, mask, y, dom, cnt, off, idx, S);
         enq_init(st, g, y, idx, S, part, n_class);
-        ok(hipGetLastError());
+        W.ok(hipGetLastError());
     }
     SmoothArgs P[3];
     P[0] = smooth_args(0, nx, ny, nz, RA, RB, wd, rad[0]);
     P[1] = smooth_args(1, nx, ny, nz, RB, RA, wd + (2 * BIAS_MAX_R + 1), rad[1]);
     P[2] = smooth_args(2, nx, ny, nz, RA, RB, wd + 2 * (2 * BIAS_MAX_R + 1), rad[2]);
-    for (int it = 0; it < n_outer && err == hipSuccess; ++it) {
+    for (int it = 0; it < n_outer && W.ok(); ++it) {
         for (int em = 0; em < n_em; ++em) enq_em_step(st, g, y, b, idx, S, n_class, part);
-        if (!ok(enq_rw(st, g, y, b, idx, S, n_class, RA, b_rw))) break;  // R = W = 0 off the domain; the y pass of the last round wrote here
+        if (!W.ok(enq_rw(st, g, y, b, idx, S, n_class, RA, RA.bytes))) break;  // R = W = 0 off the domain; the y pass of the last round wrote here
         for (int a = 0; a < 3; ++a) enq_smooth(st, a, P[a]);
         enq_update(st, g, RB, idx, S, part, b);
-        ok(hipGetLastError());
+        W.ok(hipGetLastError());
     }
-    if (err == hipSuccess) {
-        enq_apply(st, g, v, b, S, n_class, out, field, classes);
-        ok(hipGetLastError());
-    }
-    ok(hipStreamSynchronize(st));                                       // the work space goes back before the call returns
-    if (err != hipSuccess) rc = fail(MET2_E_HIP, std::string("met2_bias_field: ") + hipGetErrorString(err));
-    (void)hipFree(work);
-    return rc;
+    if (W.ok()) enq_apply(st, g, v, b, S, n_class, out, field, classes);
+    return W.finish("met2_bias_field");
 }
 
 // ---- the stages one by one, for tests and diagnostics (include/met2_hip.h) ----
@@ -319,20 +305,18 @@ extern "C" int met2_bias_domain(int32_t device, int32_t nx, int32_t ny, int32_t 
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     const BiasGrid g = bias_grid(n);
-    const size_t b_dom = up256((size_t)n), b_cnt = up256((size_t)g.nch * 4), b_st = up256(sizeof(BiasStats));
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_dom + 2 * b_cnt + b_st));
-    uint8_t *dom = (uint8_t *)work;
-    int32_t *cnt = (int32_t *)(work + b_dom), *off = (int32_t *)(work + b_dom + b_cnt);
-    BiasStats *S = (BiasStats *)(work + b_dom + 2 * b_cnt);
+    DeviceWork W(st);
+    const auto dom = W.take<uint8_t>(n);
+    const auto cnt = W.take<int32_t>(g.nch), off = W.take<int32_t>(g.nch);
+    const auto S = W.take<BiasStats>(1);
+    if (!W.alloc()) return W.finish("met2_bias_domain");
     int32_t N = 0;
-    hipError_t err = hipMemsetAsync(S, 0, b_st, st);
-    if (err == hipSuccess) {
+    if (W.ok(hipMemsetAsync(S, 0, S.bytes, st))) {
         enq_domain(st, g, v, mask, y, dom, cnt, off, idx, S);
-        err = hipGetLastError();
+        W.ok(hipGetLastError());
     }
-    if (err == hipSuccess) err = hipMemcpyAsync(&N, &S->N, sizeof N, hipMemcpyDeviceToHost, st);
-    const int rc = bias_finish("met2_bias_domain", err, st, work);
+    if (W.ok()) W.ok(hipMemcpyAsync(&N, &S->N, sizeof N, hipMemcpyDeviceToHost, st));
+    const int rc = W.finish("met2_bias_domain");
     if (rc == MET2_OK) *n_domain = N;
     return rc;
 }
@@ -348,23 +332,20 @@ extern "C" int met2_bias_init(int32_t device, int64_t n, const double *y, const 
     hipStream_t st = (hipStream_t)stream;
     const BiasGrid g = bias_grid(n);
     const int np = (int)((n_domain + BIAS_CHUNK - 1) / BIAS_CHUNK);
-    const size_t b_part = up256((size_t)g.nch * 3 * BIAS_MAX_K * 8), b_st = up256(sizeof(BiasStats));
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_part + b_st));
-    double *part = (double *)work;
-    BiasStats *S = (BiasStats *)(work + b_part);
+    DeviceWork W(st);
+    const auto part = W.take<double>((size_t)g.nch * 3 * BIAS_MAX_K);
+    const auto S = W.take<BiasStats>(1);
+    if (!W.alloc()) return W.finish("met2_bias_init");
     BiasStats h;
     std::vector<double> hp((size_t)np);
     const int32_t N = (int32_t)n_domain;
-    hipError_t err = hipMemsetAsync(S, 0, b_st, st);
-    if (err == hipSuccess) err = hipMemcpyAsync(&S->N, &N, sizeof N, hipMemcpyHostToDevice, st);
-    if (err == hipSuccess) {
+    if (W.ok(hipMemsetAsync(S, 0, S.bytes, st)) && W.ok(hipMemcpyAsync(&S->N, &N, sizeof N, hipMemcpyHostToDevice, st))) {
         enq_init(st, g, y, idx, S, part, n_class);
-        err = hipGetLastError();
+        W.ok(hipGetLastError());
     }
-    if (err == hipSuccess) err = hipMemcpyAsync(&h, S, sizeof h, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess && np > 0) err = hipMemcpyAsync(hp.data(), part, (size_t)np * 8, hipMemcpyDeviceToHost, st);
-    const int rc = bias_finish("met2_bias_init", err, st, work);
+    if (W.ok()) W.ok(hipMemcpyAsync(&h, S, sizeof h, hipMemcpyDeviceToHost, st));
+    if (W.ok() && np > 0) W.ok(hipMemcpyAsync(hp.data(), part, (size_t)np * 8, hipMemcpyDeviceToHost, st));
+    const int rc = W.finish("met2_bias_init");
     if (rc != MET2_OK) return rc;
     if (stats_out) { stats_out[0] = h.lo; stats_out[1] = h.hi; stats_out[2] = h.mean; stats_out[3] = (double)h.degenerate; }
     if (hist_out) for (int j = 0; j < BIAS_NBINS; ++j) hist_out[j] = h.hist[j];
@@ -395,26 +376,24 @@ extern "C" int met2_bias_em(int32_t device, int64_t n, const double *y, const do
     hipStream_t st = (hipStream_t)stream;
     const BiasGrid g = bias_grid(n);
     const int np = (int)((n_domain + BIAS_CHUNK - 1) / BIAS_CHUNK);
-    const size_t b_part = up256((size_t)g.nch * 3 * BIAS_MAX_K * 8), b_st = up256(sizeof(BiasStats));
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_part + b_st));
-    double *part = (double *)work;
-    BiasStats *S = (BiasStats *)(work + b_part);
+    DeviceWork W(st);
+    const auto part = W.take<double>((size_t)g.nch * 3 * BIAS_MAX_K);
+    const auto S = W.take<BiasStats>(1);
+    if (!W.alloc()) return W.finish("met2_bias_em");
     std::vector<double> hp((size_t)3 * n_class * np);
-    hipError_t err = hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st);          // h lives until the wait
-    if (err == hipSuccess) {
+    if (W.ok(hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st))) {               // h lives until the wait
         hipLaunchKernelGGL(bias_lc_kernel, dim3(1), dim3(64), 0, st, S, n_class);
         for (int em = 0; em < n_em; ++em) enq_em_step(st, g, y, b, idx, S, n_class, part);
-        err = hipGetLastError();
+        W.ok(hipGetLastError());
     }
-    if (err == hipSuccess && rw_out) err = enq_rw(st, g, y, b, idx, S, n_class, (double2 *)rw_out, (size_t)n * 16);
-    if (err == hipSuccess && part_out && n_em > 0)
-        for (int q = 0; q < 3 && err == hipSuccess; ++q)
-            for (int k = 0; k < n_class && err == hipSuccess; ++k)
-                err = hipMemcpyAsync(hp.data() + ((size_t)q * n_class + k) * np, part + (int64_t)(q * BIAS_MAX_K + k) * g.nch, (size_t)np * 8,
-                                     hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipMemcpyAsync(&h, S, sizeof h, hipMemcpyDeviceToHost, st);
-    const int rc = bias_finish("met2_bias_em", err, st, work);
+    if (W.ok() && rw_out) W.ok(enq_rw(st, g, y, b, idx, S, n_class, (double2 *)rw_out, (size_t)n * 16));
+    if (part_out && n_em > 0)
+        for (int q = 0; q < 3; ++q)
+            for (int k = 0; k < n_class && W.ok(); ++k)
+                W.ok(hipMemcpyAsync(hp.data() + ((size_t)q * n_class + k) * np, part + (int64_t)(q * BIAS_MAX_K + k) * g.nch, (size_t)np * 8,
+                                    hipMemcpyDeviceToHost, st));
+    if (W.ok()) W.ok(hipMemcpyAsync(&h, S, sizeof h, hipMemcpyDeviceToHost, st));
+    const int rc = W.finish("met2_bias_em");
     if (rc != MET2_OK) return rc;
     if (part_out && n_em > 0) std::memcpy(part_out, hp.data(), hp.size() * 8);
     if (classes_out)
@@ -444,15 +423,14 @@ extern "C" int met2_bias_smooth(int32_t device, int32_t nx, int32_t ny, int32_t 
         for (int t = 0; t <= 2 * radius[a]; ++t) hw[a * (2 * BIAS_MAX_R + 1) + t] = w[t];
         w += 2 * radius[a] + 1;
     }
-    const size_t b_rw = up256((size_t)n * 16), b_w = up256(hw.size() * 8);
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, 2 * b_rw + b_w));
-    double2 *RA = (double2 *)work, *RB = (double2 *)(work + b_rw);
-    double *wd = (double *)(work + 2 * b_rw);
-    hipError_t err = hipMemcpyAsync(wd, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, st);   // hw lives until the wait
-    if (err == hipSuccess) err = hipMemcpyAsync(RA, in, (size_t)n * 16, hipMemcpyDeviceToDevice, st);
+    DeviceWork W(st);
+    const auto RA = W.take<double2>(n), RB = W.take<double2>(n);
+    const auto wd = W.take<double>(hw.size());
+    if (!W.alloc()) return W.finish("met2_bias_smooth");
+    W.ok(hipMemcpyAsync(wd, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, st));              // hw lives until the wait
+    if (W.ok()) W.ok(hipMemcpyAsync(RA, in, (size_t)n * 16, hipMemcpyDeviceToDevice, st));
     double2 *res = RB;
-    if (err == hipSuccess) {
+    if (W.ok()) {
         if (axis < 0) {                                               // RA -> RB -> RA -> RB, as the filter
             enq_smooth(st, 0, smooth_args(0, nx, ny, nz, RA, RB, wd, radius[0]));
             enq_smooth(st, 1, smooth_args(1, nx, ny, nz, RB, RA, wd + (2 * BIAS_MAX_R + 1), radius[1]));
@@ -460,10 +438,10 @@ extern "C" int met2_bias_smooth(int32_t device, int32_t nx, int32_t ny, int32_t 
         } else {
             enq_smooth(st, axis, smooth_args(axis, nx, ny, nz, RA, RB, wd + axis * (2 * BIAS_MAX_R + 1), radius[axis]));
         }
-        err = hipGetLastError();
+        W.ok(hipGetLastError());
     }
-    if (err == hipSuccess) err = hipMemcpyAsync(out, res, (size_t)n * 16, hipMemcpyDeviceToDevice, st);
-    return bias_finish("met2_bias_smooth", err, st, work);
+    if (W.ok()) W.ok(hipMemcpyAsync(out, res, (size_t)n * 16, hipMemcpyDeviceToDevice, st));
+    return W.finish("met2_bias_smooth");
 }
 
 extern "C" int met2_bias_update(int32_t device, int64_t n, double *b, const double *smoothed, const int32_t *idx, int64_t n_domain, double *bmean_out,
@@ -474,23 +452,21 @@ extern "C" int met2_bias_update(int32_t device, int64_t n, double *b, const doub
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     const BiasGrid g = bias_grid(n);
-    const size_t b_part = up256((size_t)g.nch * 8), b_st = up256(sizeof(BiasStats));
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_part + b_st));
-    double *part = (double *)work;
-    BiasStats *S = (BiasStats *)(work + b_part);
+    DeviceWork W(st);
+    const auto part = W.take<double>(g.nch);
+    const auto S = W.take<BiasStats>(1);
+    if (!W.alloc()) return W.finish("met2_bias_update");
     BiasStats h;
     std::memset(&h, 0, sizeof h);
     h.N = (int32_t)n_domain;
     h.degenerate = n_domain == 0 ? 1 : 0;                             // an empty domain is degenerate in the filter too: b is not recentred
-    hipError_t err = hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st);          // h lives until the wait
-    if (err == hipSuccess) {
+    if (W.ok(hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st))) {               // h lives until the wait
         enq_update(st, g, (const double2 *)smoothed, idx, S, part, b);
-        err = hipGetLastError();
+        W.ok(hipGetLastError());
     }
     double bmean = 0.0;
-    if (err == hipSuccess) err = hipMemcpyAsync(&bmean, &S->bmean, 8, hipMemcpyDeviceToHost, st);
-    const int rc = bias_finish("met2_bias_update", err, st, work);
+    if (W.ok()) W.ok(hipMemcpyAsync(&bmean, &S->bmean, 8, hipMemcpyDeviceToHost, st));
+    const int rc = W.finish("met2_bias_update");
     if (rc == MET2_OK && bmean_out) *bmean_out = bmean;
     return rc;
 }
@@ -505,5 +481,5 @@ extern "C" int met2_bias_apply(int32_t device, int64_t n, const double *v, const
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     enq_apply(st, bias_grid(n), v, b, (const BiasStats *)nullptr, 0, out, field, (double *)nullptr);    // no classes: the record is not read
-    return bias_finish("met2_bias_apply", hipSuccess, st, nullptr);
+    return DeviceWork(st).finish("met2_bias_apply");
 }

@@ -29,6 +29,7 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "device_helpers.hpp"
 #include "philox.hpp"
 #include "plan.hpp"
 #include "quantile.hpp"
@@ -110,21 +111,8 @@ struct StatArgs {
     int32_t *rep_status;            // [nvox] or NULL
 };
 
-// numpy's ordering for np.sort: nan last
-__device__ __forceinline__ bool nan_last_gt(double a, double b) { return a > b || (a != a && b == b); }
-
 // np.quantile(values, p) with method 'linear' on the sorted values: quantile.hpp, shared with met2_stats.hip
 using met2::quantile_sorted;
-
-// The lanes of ONE wave exchange values through LDS: a wave's LDS accesses complete in program order, so what is needed is that the compiler
-// keeps them in it (the fences) and that the wave is converged (the barrier, which emits no instruction).  A workgroup barrier would tie the
-// waves of bootstrap_spec_stats_kernel, which sort series of their own, to each other.
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // The statistics of one series, by one wave: buf[0..B) holds the values and buf[B..P) nan (P = the next power of two), written by anyone
 // and made visible to this wave before the call.  Mean and std in two passes in a fixed order (lane-strided partial sums, then wave_sum);
@@ -218,7 +206,6 @@ inline int spec_tile_pad(int w) { return w >= 16 ? 1 : 16 / w; }
 // The launch geometry of bootstrap_spec_stats_kernel for series of n_rep values, the one copy every launch site and
 // met2_bootstrap_spec_launch_info take it from: sort slots, tile shape and the dynamic LDS ([w][S] tile and [5][w] results) in bytes.
 struct SpecGeom { int P, w, lw, S; size_t lds; };
-inline int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 inline SpecGeom spec_geometry(int n_rep)
 {
     SpecGeom g;

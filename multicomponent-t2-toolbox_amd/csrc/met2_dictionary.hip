@@ -23,6 +23,7 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "device_work.hpp"
 #include "plan.hpp"
 #include "wave_ops.hpp"
 
@@ -275,22 +276,23 @@ int met2_plan_build_dictionary_epg(met2_plan *p, const double *T2s, const double
     if (!p || !T2s || !T1s || !alpha_deg) return fail(MET2_E_INVALID, "NULL argument");
     USE_DEVICE(p->opt.device);
     hipStream_t s = (hipStream_t)stream;
-    double *tmp = nullptr;
     size_t nb = sizeof(double) * (size_t)(2 * p->n_t2 + p->n_fa);
-    HIPCHK(hipMalloc(&tmp, nb));
+    DeviceWork W(s);
+    const auto tmp = W.take<double>(nb / sizeof(double));
+    if (!W.alloc()) return W.finish("met2_plan_build_dictionary_epg");
     std::vector<double> h(2 * p->n_t2 + p->n_fa);
     memcpy(h.data(), T2s, sizeof(double) * p->n_t2);
     memcpy(h.data() + p->n_t2, T1s, sizeof(double) * p->n_t2);
     memcpy(h.data() + 2 * p->n_t2, alpha_deg, sizeof(double) * p->n_fa);
-    HIPCHK(hipMemcpy(tmp, h.data(), nb, hipMemcpyHostToDevice));
     int waves = p->n_fa * p->n_t2;
     int blocks = (waves + 3) / 4;
-    hipLaunchKernelGGL(epg_dictionary_kernel, dim3(blocks), dim3(256), 0, s, p->n_te, p->n_t2, p->n_fa, tmp, tmp + p->n_t2, tau,
-                       tmp + 2 * p->n_t2, TR, p->dD);
-    HIPCHK(hipGetLastError());
-    int rc = build_gram(p, s);
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipFree(tmp));
+    int rc = MET2_OK;
+    if (W.ok(hipMemcpy(tmp, h.data(), nb, hipMemcpyHostToDevice))) {
+        hipLaunchKernelGGL(epg_dictionary_kernel, dim3(blocks), dim3(256), 0, s, p->n_te, p->n_t2, p->n_fa, tmp, tmp + p->n_t2, tau,
+                           tmp + 2 * p->n_t2, TR, p->dD);
+        if (W.ok(hipGetLastError())) rc = build_gram(p, s);
+    }
+    if (int e = W.finish("met2_plan_build_dictionary_epg")) return e;
     if (rc) return rc;
     rc = ensure_seeds(p, s);
     if (rc) return rc;
@@ -319,15 +321,16 @@ int met2_plan_build_dictionary_epg_profile(met2_plan *p, const double *T2s, cons
     memcpy(h.data() + n0, r_exc, sizeof(double) * n_z);
     memcpy(h.data() + n0 + n_z, r_ref, sizeof(double) * n_z);
     memcpy(h.data() + n0 + 2 * n_z, w, sizeof(double) * n_z);
-    struct Scratch { double *p = nullptr; ~Scratch() { if (p) (void)hipFree(p); } } scratch;      // freed on every return, the failing ones included
-    HIPCHK(hipMalloc(&scratch.p, sizeof(double) * h.size()));
-    double *tmp = scratch.p;
-    HIPCHK(hipMemcpy(tmp, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(epg_profile_dictionary_kernel, dim3(p->n_fa * p->n_t2), dim3(256), sizeof(double) * 64 * (size_t)n_z, s, p->n_te, p->n_t2,
-                       n_z, tmp, tmp + p->n_t2, tau, tmp + 2 * p->n_t2, TR, tmp + n0, tmp + n0 + n_z, tmp + n0 + 2 * n_z, p->dD);
-    HIPCHK(hipGetLastError());
-    int rc = build_gram(p, s);
-    HIPCHK(hipStreamSynchronize(s));
+    DeviceWork W(s);
+    const auto tmp = W.take<double>(h.size());
+    if (!W.alloc()) return W.finish("met2_plan_build_dictionary_epg_profile");
+    int rc = MET2_OK;
+    if (W.ok(hipMemcpy(tmp, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice))) {
+        hipLaunchKernelGGL(epg_profile_dictionary_kernel, dim3(p->n_fa * p->n_t2), dim3(256), sizeof(double) * 64 * (size_t)n_z, s, p->n_te, p->n_t2,
+                           n_z, tmp, tmp + p->n_t2, tau, tmp + 2 * p->n_t2, TR, tmp + n0, tmp + n0 + n_z, tmp + n0 + 2 * n_z, p->dD);
+        if (W.ok(hipGetLastError())) rc = build_gram(p, s);
+    }
+    if (int e = W.finish("met2_plan_build_dictionary_epg_profile")) return e;
     if (rc) return rc;
     rc = ensure_seeds(p, s);
     if (rc) return rc;
@@ -339,14 +342,16 @@ int met2_plan_set_dictionary(met2_plan *p, const double *dic)
     if (!p || !dic) return fail(MET2_E_INVALID, "NULL argument");
     USE_DEVICE(p->opt.device);
     size_t nb = sizeof(double) * (size_t)p->n_fa * p->n_te * p->n_t2;
-    double *tmp = nullptr;
-    HIPCHK(hipMalloc(&tmp, nb));
-    HIPCHK(hipMemcpy(tmp, dic, nb, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(relayout_kernel, dim3(256), dim3(256), 0, 0, p->n_te, p->n_t2, p->n_fa, tmp, p->dD, 1);
-    HIPCHK(hipGetLastError());
-    int rc = build_gram(p, 0);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipFree(tmp));
+    DeviceWork W(0);
+    const auto tmp = W.take<double>(nb / sizeof(double));
+    if (!W.alloc()) return W.finish("met2_plan_set_dictionary");
+    int rc = MET2_OK;
+    if (W.ok(hipMemcpy(tmp, dic, nb, hipMemcpyHostToDevice))) {
+        hipLaunchKernelGGL(relayout_kernel, dim3(256), dim3(256), 0, 0, p->n_te, p->n_t2, p->n_fa, tmp, p->dD, 1);
+        if (W.ok(hipGetLastError())) rc = build_gram(p, 0);
+        W.ok(hipDeviceSynchronize());
+    }
+    if (int e = W.finish("met2_plan_set_dictionary")) return e;
     if (rc) return rc;
     return ensure_seeds(p, 0);
 }
@@ -357,13 +362,12 @@ int met2_plan_get_dictionary(met2_plan *p, double *dic)
     if (!p->have_dict) return fail(MET2_E_STATE, "no dictionary in the plan");
     USE_DEVICE(p->opt.device);
     size_t nb = sizeof(double) * (size_t)p->n_fa * p->n_te * p->n_t2;
-    double *tmp = nullptr;
-    HIPCHK(hipMalloc(&tmp, nb));
+    DeviceWork W(0);
+    const auto tmp = W.take<double>(nb / sizeof(double));
+    if (!W.alloc()) return W.finish("met2_plan_get_dictionary");
     hipLaunchKernelGGL(relayout_kernel, dim3(256), dim3(256), 0, 0, p->n_te, p->n_t2, p->n_fa, p->dD, tmp, 0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(dic, tmp, nb, hipMemcpyDeviceToHost));
-    HIPCHK(hipFree(tmp));
-    return MET2_OK;
+    if (W.ok(hipGetLastError())) W.ok(hipMemcpy(dic, tmp, nb, hipMemcpyDeviceToHost));
+    return W.finish("met2_plan_get_dictionary");
 }
 
 int met2_plan_set_penalty_dense(met2_plan *p, const double *L)

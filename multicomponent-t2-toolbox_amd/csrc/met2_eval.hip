@@ -17,6 +17,7 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "device_helpers.hpp"
 #include "philox.hpp"
 #include "plan.hpp"
 #include "wave_ops.hpp"
@@ -166,9 +167,6 @@ __global__ __launch_bounds__(64) void synth_two_lobe_kernel(SynthArgs A)
         A.truth[lane * A.n + lv] = r;
     }
 }
-
-// numpy's ordering for np.sort: nan last
-__device__ __forceinline__ bool nan_last_gt(double a, double b) { return a > b || (a != a && b == b); }
 
 __device__ void bitonic_sort(double *buf, int P, int lane)
 {

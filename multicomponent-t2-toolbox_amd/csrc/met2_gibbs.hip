@@ -27,6 +27,7 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "device_work.hpp"
 
 namespace {
 
@@ -545,33 +546,24 @@ int run_volume(int32_t device, int32_t nx, int32_t ny, int64_t ns, const double 
     const int sc_max = (int)scl;
     const int jp = table_cols(nshifts);
     const size_t ce = (size_t)sc_max * (size_t)P;                      // samples of a chunk
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t b_W = up(ce * 8), b_T = up(ce * 16), b_I = up(ce * 8), b_sh = up(ce), b_small = up((size_t)sc_max * 8);
-    const size_t b_Wx = up((size_t)nx * nx * 16), b_Wy = up((size_t)ny * ny * 16), b_cx = up((size_t)nx * jp * 8), b_cy = up((size_t)ny * jp * 8);
-    const size_t total = b_W + b_T + 2 * b_I + 2 * b_sh + 2 * b_small + b_Wx + b_Wy + b_cx + b_cy;
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, total));
-    char *at = work;
-    auto take = [&at](size_t b) { char *p = at; at += b; return p; };
-    double *W = (double *)take(b_W);
-    double2 *T = (double2 *)take(b_T);
-    double *Ix = (double *)take(b_I), *Iy = (double *)take(b_I);
-    int8_t *sx = (int8_t *)take(b_sh), *sy = (int8_t *)take(b_sh);
-    double *corner = (double *)take(b_small);
-    int32_t *flag = (int32_t *)take(b_small);
-    double2 *Wx = (double2 *)take(b_Wx), *Wy = (double2 *)take(b_Wy);
-    double *cx = (double *)take(b_cx), *cy = (double *)take(b_cy);
+    DeviceWork work(st);
+    const auto W = work.take<double>(ce);
+    const auto T = work.take<double2>(ce);
+    const auto Ix = work.take<double>(ce), Iy = work.take<double>(ce);
+    const auto sx = work.take<int8_t>(ce), sy = work.take<int8_t>(ce);
+    const auto corner = work.take<double>(sc_max);
+    const auto flag = work.take<int32_t>((size_t)sc_max * 2);           // sc_max flags in a piece as large as the corner terms': one memset clears both
+    const auto Wx = work.take<double2>((size_t)nx * nx), Wy = work.take<double2>((size_t)ny * ny);
+    const auto cx = work.take<double>((size_t)nx * jp), cy = work.take<double>((size_t)ny * jp);
+    if (!work.alloc()) return work.finish(who);
 
-    int rc = MET2_OK;
-    hipError_t err = hipSuccess;
-    auto ok = [&](hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; return err == hipSuccess; };
     launch_tables(st, nx, nshifts, jp, Wx, cx);
     launch_tables(st, ny, nshifts, jp, Wy, cy);
-    ok(hipGetLastError());
-    for (int64_t s0 = 0; s0 < ns && err == hipSuccess; s0 += sc_max) {
+    work.ok(hipGetLastError());
+    for (int64_t s0 = 0; s0 < ns && work.ok(); s0 += sc_max) {
         const int sc = (int)(ns - s0 < sc_max ? ns - s0 : sc_max);
         const int nrows = sc * nx;
-        if (!ok(hipMemsetAsync(corner, 0, 2 * b_small, st))) break;     // the corner terms and the flags lie side by side
+        if (!work.ok(hipMemsetAsync(corner, 0, 2 * corner.bytes, st))) break;    // the corner terms and the flags lie side by side
         const dim3 tg((unsigned)((P + 31) / 32), (unsigned)((sc + 31) / 32));
         hipLaunchKernelGGL(gibbs_gather_kernel, tg, dim3(32, 8), 0, st, data, P, ns, s0, sc, W, flag);
         hipLaunchKernelGGL(gibbs_dft_rows_kernel, dim3((nrows + GIBBS_LB - 1) / GIBBS_LB), dim3(round64(ny)), 0, st, W, Wy, ny, nrows, T);
@@ -583,26 +575,23 @@ int run_volume(int32_t device, int32_t nx, int32_t ny, int64_t ns, const double 
                                (int8_t *)nullptr);
             hipLaunchKernelGGL(gibbs_scatter_kernel, tg, dim3(32, 8), 0, st, Iy, Iy, sx, sy, flag, P, ns, s0, sc, split_y, (int8_t *)nullptr,
                                (int8_t *)nullptr);
-            ok(hipGetLastError());
+            work.ok(hipGetLastError());
             continue;
         }
         UnringArgs A;
         A.nsh = nshifts; A.jp = jp; A.min_w = min_w; A.max_w = max_w; A.slice_stride = P; A.best = nullptr;
         // along x: the lines are a slice's columns; the result overwrites Ix
-        A.src = Ix; A.dst = Ix; A.ct = cx; A.shift = shift_x ? sx : nullptr; A.n = nx; A.nlines = sc * ny; A.per_slice = ny; A.line_stride = 1;
+        A.src = Ix; A.dst = Ix; A.ct = cx; A.shift = shift_x ? (int8_t *)sx : nullptr; A.n = nx; A.nlines = sc * ny; A.per_slice = ny; A.line_stride = 1;
         A.stride = ny; A.accumulate = 0;
         launch_unring(st, A);
         // along y: the rows; added to the x-pass's result
-        A.src = Iy; A.dst = Ix; A.ct = cy; A.shift = shift_y ? sy : nullptr; A.n = ny; A.nlines = nrows; A.per_slice = nx; A.line_stride = ny;
+        A.src = Iy; A.dst = Ix; A.ct = cy; A.shift = shift_y ? (int8_t *)sy : nullptr; A.n = ny; A.nlines = nrows; A.per_slice = nx; A.line_stride = ny;
         A.stride = 1; A.accumulate = 1;
         launch_unring(st, A);
         hipLaunchKernelGGL(gibbs_scatter_kernel, tg, dim3(32, 8), 0, st, Ix, W, sx, sy, flag, P, ns, s0, sc, out, shift_x, shift_y);
-        ok(hipGetLastError());
+        work.ok(hipGetLastError());
     }
-    ok(hipStreamSynchronize(st));                                       // the work space goes back before the call returns
-    if (err != hipSuccess) rc = fail(MET2_E_HIP, std::string(who) + ": " + hipGetErrorString(err));
-    (void)hipFree(work);
-    return rc;
+    return work.finish(who);
 }
 
 // the checks on the volume's shape that met2_degibbs and met2_gibbs_split share, after those of the parameters; *empty: nothing to do
@@ -634,44 +623,31 @@ int run_volume3d(int32_t device, int32_t nx, int32_t ny, int32_t nz, int64_t nt,
     const int ec_max = (int)ecl;                                       // at most 2^22 / 8^3 echoes
     const int jp = table_cols(nshifts);
     const size_t ce = (size_t)ec_max * (size_t)P;                      // samples of a chunk
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t b_W = up(ce * 8), b_T = up(ce * 16), b_I = up(ce * 8), b_sh = up(ce), b_flag = up((size_t)ec_max * 4);
     const int32_t na[3] = {nx, ny, nz};
-    size_t b_Wa[3], b_ca[3], total = b_W + 2 * b_T + 3 * b_I + 3 * b_sh + b_flag;
+    DeviceWork work(st);
+    const auto W = work.take<double>(ce);
+    const auto T = work.take<double2>(ce), T2 = work.take<double2>(ce);
+    const auto Ix = work.take<double>(ce), Iy = work.take<double>(ce), Iz = work.take<double>(ce);
+    const auto sx = work.take<int8_t>(ce), sy = work.take<int8_t>(ce), sz = work.take<int8_t>(ce);
+    const auto flag = work.take<int32_t>(ec_max);
+    DeviceWork::Piece<double2> Wa[3];
+    DeviceWork::Piece<double> ca[3];
     for (int a = 0; a < 3; ++a) {
-        b_Wa[a] = up((size_t)na[a] * na[a] * 16);
-        b_ca[a] = up((size_t)na[a] * jp * 8);
-        total += b_Wa[a] + b_ca[a];
+        Wa[a] = work.take<double2>((size_t)na[a] * na[a]);
+        ca[a] = work.take<double>((size_t)na[a] * jp);
     }
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, total));
-    char *at = work;
-    auto take = [&at](size_t b) { char *p = at; at += b; return p; };
-    double *W = (double *)take(b_W);
-    double2 *T = (double2 *)take(b_T), *T2 = (double2 *)take(b_T);
-    double *Ix = (double *)take(b_I), *Iy = (double *)take(b_I), *Iz = (double *)take(b_I);
-    int8_t *sx = (int8_t *)take(b_sh), *sy = (int8_t *)take(b_sh), *sz = (int8_t *)take(b_sh);
-    int32_t *flag = (int32_t *)take(b_flag);
-    double2 *Wa[3];
-    double *ca[3];
-    for (int a = 0; a < 3; ++a) {
-        Wa[a] = (double2 *)take(b_Wa[a]);
-        ca[a] = (double *)take(b_ca[a]);
-    }
+    if (!work.alloc()) return work.finish(who);
 
-    int rc = MET2_OK;
-    hipError_t err = hipSuccess;
-    auto ok = [&](hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; return err == hipSuccess; };
     for (int a = 0; a < 3; ++a) launch_tables(st, na[a], nshifts, jp, Wa[a], ca[a]);
-    ok(hipGetLastError());
+    work.ok(hipGetLastError());
     const int yz = ny * nz;                                            // <= 2^16
     const int tiles_x = (yz + GIBBS_LB - 1) / GIBBS_LB, tiles_y = (nz + GIBBS_LB - 1) / GIBBS_LB;
     const double scale = 1.0 / ((double)nx * (double)ny * (double)nz);
-    for (int64_t e0 = 0; e0 < nt && err == hipSuccess; e0 += ec_max) {
+    for (int64_t e0 = 0; e0 < nt && work.ok(); e0 += ec_max) {
         const int ec = (int)(nt - e0 < ec_max ? nt - e0 : ec_max);
         const int64_t cs = (int64_t)ec * P;                            // < 2^31
         const int nrows = (int)(cs / nz);                              // the chunk's z lines
-        if (!ok(hipMemsetAsync(flag, 0, b_flag, st))) break;
+        if (!work.ok(hipMemsetAsync(flag, 0, flag.bytes, st))) break;
         const dim3 tg((unsigned)((P + 31) / 32), (unsigned)((ec + 31) / 32));
         const dim3 rows((unsigned)((nrows + GIBBS_LB - 1) / GIBBS_LB));
         const dim3 gx((unsigned)((int64_t)ec * tiles_x)), gy((unsigned)((int64_t)ec * nx * tiles_y));    // <= 2^22 / 8 + ec and 2^22 / 64 + ec nx
@@ -692,30 +668,27 @@ int run_volume3d(int32_t device, int32_t nx, int32_t ny, int32_t nz, int64_t nt,
             for (int a = 0; a < 3; ++a)
                 hipLaunchKernelGGL(gibbs_scatter_kernel, tg, dim3(32, 8), 0, st, src[a], src[a], sx, sy, flag, P, nt, e0, ec, dst[a],
                                    (int8_t *)nullptr, (int8_t *)nullptr);
-            ok(hipGetLastError());
+            work.ok(hipGetLastError());
             continue;
         }
         UnringArgs A;
         A.nsh = nshifts; A.jp = jp; A.min_w = min_w; A.max_w = max_w; A.best = nullptr; A.dst = Ix;
         // along x: per echo, the ny nz lines start side by side; the result overwrites Ix
-        A.src = Ix; A.ct = ca[0]; A.shift = shift_x ? sx : nullptr; A.n = nx; A.nlines = ec * yz; A.per_slice = yz; A.slice_stride = P;
+        A.src = Ix; A.ct = ca[0]; A.shift = shift_x ? (int8_t *)sx : nullptr; A.n = nx; A.nlines = ec * yz; A.per_slice = yz; A.slice_stride = P;
         A.line_stride = 1; A.stride = yz; A.accumulate = 0;
         launch_unring(st, A);
         // along y: per (echo, x), the nz lines start side by side; added to the x pass's result
-        A.src = Iy; A.ct = ca[1]; A.shift = shift_y ? sy : nullptr; A.n = ny; A.nlines = ec * nx * nz; A.per_slice = nz; A.slice_stride = yz;
+        A.src = Iy; A.ct = ca[1]; A.shift = shift_y ? (int8_t *)sy : nullptr; A.n = ny; A.nlines = ec * nx * nz; A.per_slice = nz; A.slice_stride = yz;
         A.line_stride = 1; A.stride = nz; A.accumulate = 1;
         launch_unring(st, A);
         // along z: the lines are contiguous, one after the other through the chunk
-        A.src = Iz; A.ct = ca[2]; A.shift = shift_z ? sz : nullptr; A.n = nz; A.nlines = nrows; A.per_slice = nrows; A.slice_stride = 0;
+        A.src = Iz; A.ct = ca[2]; A.shift = shift_z ? (int8_t *)sz : nullptr; A.n = nz; A.nlines = nrows; A.per_slice = nrows; A.slice_stride = 0;
         A.line_stride = nz; A.stride = 1; A.accumulate = 1;
         launch_unring(st, A);
         hipLaunchKernelGGL(gibbs_scatter3d_kernel, tg, dim3(32, 8), 0, st, Ix, W, sx, sy, sz, flag, P, nt, e0, ec, out, shift_x, shift_y, shift_z);
-        ok(hipGetLastError());
+        work.ok(hipGetLastError());
     }
-    ok(hipStreamSynchronize(st));                                       // the work space goes back before the call returns
-    if (err != hipSuccess) rc = fail(MET2_E_HIP, std::string(who) + ": " + hipGetErrorString(err));
-    (void)hipFree(work);
-    return rc;
+    return work.finish(who);
 }
 
 // the checks on the volume's shape that met2_degibbs3d and met2_gibbs_split3d share, after those of the parameters; *empty: nothing to do
@@ -825,21 +798,15 @@ extern "C" int met2_gibbs_lines(int32_t device, int32_t n, int32_t nlines, const
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     const int jp = table_cols(nshifts);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t b_W = up((size_t)n * n * 16), b_c = up((size_t)n * jp * 8);
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_W + b_c));
-    double *ct = (double *)(work + b_W);
-    launch_tables(st, n, nshifts, jp, (double2 *)work, ct);
+    DeviceWork work(st);
+    const auto W = work.take<double2>((size_t)n * n);
+    const auto ct = work.take<double>((size_t)n * jp);
+    if (!work.alloc()) return work.finish("met2_gibbs_lines");
+    launch_tables(st, n, nshifts, jp, W, ct);
     UnringArgs A;
     A.nsh = nshifts; A.jp = jp; A.min_w = min_w; A.max_w = max_w; A.slice_stride = 0; A.best = best;
     A.src = lines; A.dst = out; A.ct = ct; A.shift = shift; A.n = n; A.nlines = nlines; A.per_slice = nlines; A.line_stride = n;
     A.stride = 1; A.accumulate = 0;
     launch_unring(st, A);
-    hipError_t err = hipGetLastError();
-    const hipError_t e2 = hipStreamSynchronize(st);                     // the work space goes back before the call returns
-    if (err == hipSuccess) err = e2;
-    (void)hipFree(work);
-    if (err != hipSuccess) return fail(MET2_E_HIP, std::string("met2_gibbs_lines: ") + hipGetErrorString(err));
-    return MET2_OK;
+    return work.finish("met2_gibbs_lines");
 }

@@ -39,6 +39,8 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "device_helpers.hpp"
+#include "device_work.hpp"
 #include "wave_ops.hpp"
 
 namespace {
@@ -82,14 +84,6 @@ template <bool STAGES, int BOX = 0> struct mppca_args { typedef MppcaArgs type; 
 template <> struct mppca_args<true, 0> { typedef MppcaStageArgs type; };
 template <> struct mppca_args<false, 1> { typedef MppcaBoxArgs type; };
 template <> struct mppca_args<false, 2> { typedef MppcaBoxArgs type; };
-
-// the lanes of one wave exchange values through LDS: a wave's LDS accesses complete in program order, the fences keep the compiler to it
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // pair k of round t of the round-robin tournament over n players (n even): player n - 1 stays, the others turn
 __device__ __forceinline__ void rr_pair(int n, int t, int k, int &p, int &q)
@@ -611,8 +605,10 @@ extern "C" int met2_mppca_box(int32_t device, int32_t nx, int32_t ny, int32_t nz
     S.tile(budget, bx, by, bz);
     const int64_t cmax = S.centres(bx, by, bz);
     const int64_t bytes = S.all_bytes(cmax) < budget ? S.all_bytes(cmax) : budget;      // more than every centre at any rank is never needed
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, (size_t)bytes));
+    DeviceWork W(st);
+    const auto piece = W.take<char>((size_t)bytes);                     // one piece: BoxShape's byte counts, which the budget is held against, lay it out
+    if (!W.alloc()) return W.finish("met2_mppca_box");
+    char *work = piece;
     A.used = (unsigned long long *)work;
     A.head = (MppcaHead *)(work + BoxShape::fixed);
     A.basis = (double *)(work + BoxShape::fixed + cmax * (int64_t)sizeof(MppcaHead));
@@ -621,8 +617,6 @@ extern "C" int met2_mppca_box(int32_t device, int32_t nx, int32_t ny, int32_t nz
     G.nx = nx; G.ny = ny; G.nz = nz; G.nt = nt; G.hx = S.hx; G.hy = S.hy; G.hz = S.hz;
     G.data = data; G.mask = mask; G.head = A.head; G.basis = A.basis;
     G.out = out; G.sigma = sigma; G.wsum = wsum; G.rank = rank; G.n_patch = n_patch;
-    hipError_t err = hipSuccess;
-    auto ok = [&](hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; return err == hipSuccess; };
     auto lo = [](int o, int h) { return o - h > 0 ? o - h : 0; };
     auto hi = [](int o, int b, int h, int n) { return o + b + h < n ? o + b + h : n; };
     std::vector<OutBox> todo;                                           // a stack: the boxes of the cut in reverse, so that they run in memory order
@@ -630,26 +624,26 @@ extern "C" int met2_mppca_box(int32_t device, int32_t nx, int32_t ny, int32_t nz
         for (int oy = (ny - 1) / by * by; oy >= 0; oy -= by)
             for (int oz = (nz - 1) / bz * bz; oz >= 0; oz -= bz)
                 todo.push_back(OutBox{ox, oy, oz, ox + bx < nx ? bx : nx - ox, oy + by < ny ? by : ny - oy, oz + bz < nz ? bz : nz - oz});
-    while (!todo.empty() && err == hipSuccess) {
+    while (!todo.empty() && W.ok()) {
         const OutBox b = todo.back();
         todo.pop_back();
         A.cx0 = lo(b.x, S.hx); A.cy0 = lo(b.y, S.hy); A.cz0 = lo(b.z, S.hz);
         const int cnx = hi(b.x, b.nx, S.hx, nx) - A.cx0;
         A.cny = hi(b.y, b.ny, S.hy, ny) - A.cy0; A.cnz = hi(b.z, b.nz, S.hz, nz) - A.cz0;
         const int64_t nc = (int64_t)cnx * A.cny * A.cnz;                // <= cmax: the box is at most bx x by x bz
-        if (nc > cmax) { err = hipErrorInvalidValue; break; }
-        if (!ok(hipMemsetAsync(A.used, 0, sizeof(unsigned long long), st))) break;
+        if (nc > cmax) { W.ok(hipErrorInvalidValue); break; }
+        if (!W.ok(hipMemsetAsync(A.used, 0, sizeof(unsigned long long), st))) break;
         hipLaunchKernelGGL((mppca_kernel<false, 2>), dim3((unsigned)nc), dim3(64), lds, st, A);
-        if (!ok(hipGetLastError())) break;
+        if (!W.ok(hipGetLastError())) break;
         if (nc * S.worst > A.pool) {                                    // the centres may have kept more than the pool holds: look
             unsigned long long used = 0;
-            if (!ok(hipMemcpyAsync(&used, A.used, sizeof(used), hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st))) break;
+            if (!W.ok(hipMemcpyAsync(&used, A.used, sizeof(used), hipMemcpyDeviceToHost, st)) || !W.ok(hipStreamSynchronize(st))) break;
             if (used > (unsigned long long)A.pool) {                    // halve the box along its longest side and run the halves (one voxel never gets here)
                 OutBox p = b, q = b;
                 if (b.nx >= b.ny && b.nx >= b.nz) { p.nx = b.nx / 2; q.x = b.x + p.nx; q.nx = b.nx - p.nx; }
                 else if (b.ny >= b.nz) { p.ny = b.ny / 2; q.y = b.y + p.ny; q.ny = b.ny - p.ny; }
                 else { p.nz = b.nz / 2; q.z = b.z + p.nz; q.nz = b.nz - p.nz; }
-                if ((int64_t)b.nx * b.ny * b.nz < 2) { err = hipErrorInvalidValue; break; }
+                if ((int64_t)b.nx * b.ny * b.nz < 2) { W.ok(hipErrorInvalidValue); break; }
                 todo.push_back(q);
                 todo.push_back(p);
                 continue;
@@ -658,10 +652,7 @@ extern "C" int met2_mppca_box(int32_t device, int32_t nx, int32_t ny, int32_t nz
         G.ox0 = b.x; G.oy0 = b.y; G.oz0 = b.z; G.ony = b.ny; G.onz = b.nz;
         G.cx0 = A.cx0; G.cy0 = A.cy0; G.cz0 = A.cz0; G.cny = A.cny; G.cnz = A.cnz;
         hipLaunchKernelGGL(mppca_average_kernel, dim3((unsigned)((int64_t)b.nx * b.ny * b.nz)), dim3(64), 0, st, G);
-        ok(hipGetLastError());
+        W.ok(hipGetLastError());
     }
-    ok(hipStreamSynchronize(st));                                       // the work space goes back before the call returns
-    (void)hipFree(work);
-    if (err != hipSuccess) return fail(MET2_E_HIP, std::string("met2_mppca_box: ") + hipGetErrorString(err));
-    return MET2_OK;
+    return W.finish("met2_mppca_box");
 }

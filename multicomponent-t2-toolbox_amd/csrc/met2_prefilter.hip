@@ -19,6 +19,7 @@
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
 #include "brent.hpp"
+#include "device_work.hpp"
 #include "plan.hpp"
 #include "wave_ops.hpp"
 
@@ -421,8 +422,10 @@ extern "C" int met2_smooth_separable(int32_t device, int32_t nx, int32_t ny, int
     if (data == out || work == out || work == data) return fail(MET2_E_INVALID, "data, out and work must be distinct");
     USE_DEVICE(device);
     hipStream_t s = (hipStream_t)stream;
-    double *tmp = work;
-    if (!tmp) HIPCHK(hipMalloc(&tmp, sizeof(double) * (size_t)total));
+    DeviceWork W(s);                                                // the caller's work is neither waited for nor freed
+    const auto piece = W.take<double>((size_t)total);
+    if (!W.alloc(work)) return W.finish("met2_smooth_separable");
+    double *tmp = piece;
     SmoothArgs A;
     A.radius = radius; A.total = total;
     for (int i = 0; i < 2 * radius + 1; ++i) A.w[i] = weights[i];
@@ -437,9 +440,7 @@ extern "C" int met2_smooth_separable(int32_t device, int32_t nx, int32_t ny, int
         src = dst;
         dst = (dst == out) ? tmp : out;
     }
-    HIPCHK(hipGetLastError());
-    if (!work) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipFree(tmp)); }
-    return MET2_OK;
+    return W.finish("met2_smooth_separable");
 }
 
 extern "C" int met2_nesma(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t nt, const double *data,

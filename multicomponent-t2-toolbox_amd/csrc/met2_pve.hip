@@ -50,25 +50,6 @@ struct PveGeom {
     double beta, wx, wy, wz;
 };
 
-// One rounding each: under this pragma the compiler may not contract them into a fused multiply-add once they are inlined (met2_seg.hip).
-__device__ __forceinline__ double rn_mul(double x, double y)
-{
-#pragma clang fp contract(off)
-    return x * y;
-}
-
-__device__ __forceinline__ double rn_add(double x, double y)
-{
-#pragma clang fp contract(off)
-    return x + y;
-}
-
-__device__ __forceinline__ double rn_sub(double x, double y)
-{
-#pragma clang fp contract(off)
-    return x - y;
-}
-
 // ((v - m)^2 a) + h
 __device__ __forceinline__ double pve_term(double v, double m, double a, double h)
 {
@@ -475,31 +456,24 @@ extern "C" int met2_partial_volume(int32_t device, int32_t nx, int32_t ny, int32
     hipStream_t st = (hipStream_t)stream;
 
     const BiasGrid g = bias_grid(n);
-    const size_t b_E = up256((size_t)n * 8 * T), b_idx = up256((size_t)n * 4), b_u8 = up256((size_t)n), b_cnt = up256((size_t)g.nch * 4);
-    const size_t b_part = up256((size_t)g.nch * 3 * BIAS_MAX_K * 8), b_st = up256(sizeof(BiasStats)), b_rec = up256(sizeof(PveRec));
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_E + b_idx + b_u8 + 2 * b_cnt + b_part + b_st + b_rec));
-    char *at = work;
-    auto take = [&at](size_t b) { char *p = at; at += b; return p; };
-    double *E = (double *)take(b_E);
-    int32_t *idx = (int32_t *)take(b_idx);
-    uint8_t *typ = (uint8_t *)take(b_u8);
-    int32_t *cnt = (int32_t *)take(b_cnt), *off = (int32_t *)take(b_cnt);
-    double *part = (double *)take(b_part);
-    BiasStats *S = (BiasStats *)take(b_st);
-    PveRec *R = (PveRec *)take(b_rec);
+    DeviceWork W(st);
+    const auto E = W.take<double>((size_t)n * T);
+    const auto idx = W.take<int32_t>(n);
+    const auto typ = W.take<uint8_t>(n);
+    const auto cnt = W.take<int32_t>(g.nch), off = W.take<int32_t>(g.nch);
+    const auto part = W.take<double>((size_t)g.nch * 3 * BIAS_MAX_K);
+    const auto S = W.take<BiasStats>(1);
+    const auto R = W.take<PveRec>(1);
+    if (!W.alloc()) return W.finish("met2_partial_volume");
 
     enq_pve_domain(st, g, seg, cnt, off, idx, S);
     enq_pve_moments(st, g, v, prob, idx, S, R, K, part);
     enq_pve_consts(st, R, K);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = enq_pve_energy(st, g, v, seg, idx, S, R, K, E, typ);
-    if (err == hipSuccess) {
+    if (W.ok(hipGetLastError()) && W.ok(enq_pve_energy(st, g, v, seg, idx, S, R, K, E, typ))) {
         enq_pve_icm(st, n_icm, typ, E, R, K, G);
         if (pve || pveseg || mixeltype || classes_lin) enq_pve_finish(st, g, v, typ, R, K, pve, pveseg, mixeltype, classes_lin);
-        err = hipGetLastError();
     }
-    return bias_finish("met2_partial_volume", err, st, work);
+    return W.finish("met2_partial_volume");
 }
 
 // ---- the stages one by one, for tests and diagnostics (include/met2_hip.h) ----
@@ -512,26 +486,22 @@ extern "C" int met2_pve_moments(int32_t device, int64_t n, const double *v, cons
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     const BiasGrid g = bias_grid(n);
-    const size_t b_idx = up256((size_t)n * 4), b_cnt = up256((size_t)g.nch * 4), b_part = up256((size_t)g.nch * 3 * BIAS_MAX_K * 8);
-    const size_t b_st = up256(sizeof(BiasStats)), b_rec = up256(sizeof(PveRec));
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_idx + 2 * b_cnt + b_part + b_st + b_rec));
-    char *at = work;
-    auto take = [&at](size_t b) { char *p = at; at += b; return p; };
-    int32_t *idx = (int32_t *)take(b_idx), *cnt = (int32_t *)take(b_cnt), *off = (int32_t *)take(b_cnt);
-    double *part = (double *)take(b_part);
-    BiasStats *S = (BiasStats *)take(b_st);
-    PveRec *R = (PveRec *)take(b_rec);
+    DeviceWork W(st);
+    const auto idx = W.take<int32_t>(n), cnt = W.take<int32_t>(g.nch), off = W.take<int32_t>(g.nch);
+    const auto part = W.take<double>((size_t)g.nch * 3 * BIAS_MAX_K);
+    const auto S = W.take<BiasStats>(1);
+    const auto R = W.take<PveRec>(1);
+    if (!W.alloc()) return W.finish("met2_pve_moments");
     BiasStats hs;
     PveRec hr;
     std::vector<double> hp((size_t)3 * BIAS_MAX_K * g.nch);
     enq_pve_domain(st, g, seg, cnt, off, idx, S);
     enq_pve_moments(st, g, v, prob, idx, S, R, K, part);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipMemcpyAsync(&hs, S, sizeof hs, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipMemcpyAsync(&hr, R, sizeof hr, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipMemcpyAsync(hp.data(), part, hp.size() * 8, hipMemcpyDeviceToHost, st);
-    const int rc = bias_finish("met2_pve_moments", err, st, work);
+    W.ok(hipGetLastError());
+    if (W.ok()) W.ok(hipMemcpyAsync(&hs, S, sizeof hs, hipMemcpyDeviceToHost, st));
+    if (W.ok()) W.ok(hipMemcpyAsync(&hr, R, sizeof hr, hipMemcpyDeviceToHost, st));
+    if (W.ok()) W.ok(hipMemcpyAsync(hp.data(), part, hp.size() * 8, hipMemcpyDeviceToHost, st));
+    const int rc = W.finish("met2_pve_moments");
     if (rc != MET2_OK) return rc;
     const int64_t N = hs.N, np = (N + BIAS_CHUNK - 1) / BIAS_CHUNK;   // a chunk past np was never written
     if (n_domain) *n_domain = N;
@@ -551,18 +521,17 @@ extern "C" int met2_pve_consts(int32_t device, int32_t n_class, const double *cl
     const int K = n_class;
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, up256(sizeof(PveRec))));
-    PveRec *R = (PveRec *)work;
+    DeviceWork W(st);
+    const auto R = W.take<PveRec>(1);
+    if (!W.alloc()) return W.finish("met2_pve_consts");
     std::vector<PveRec> h(2);                                          // [0] in, [1] out; alive until the wait
     pve_record(K, classes_in, &h[0]);
-    hipError_t err = hipMemcpyAsync(R, &h[0], sizeof(PveRec), hipMemcpyHostToDevice, st);
-    if (err == hipSuccess) {
+    if (W.ok(hipMemcpyAsync(R, &h[0], sizeof(PveRec), hipMemcpyHostToDevice, st))) {
         enq_pve_consts(st, R, K);
-        err = hipGetLastError();
+        W.ok(hipGetLastError());
     }
-    if (err == hipSuccess) err = hipMemcpyAsync(&h[1], R, sizeof(PveRec), hipMemcpyDeviceToHost, st);
-    const int rc = bias_finish("met2_pve_consts", err, st, work);
+    if (W.ok()) W.ok(hipMemcpyAsync(&h[1], R, sizeof(PveRec), hipMemcpyDeviceToHost, st));
+    const int rc = W.finish("met2_pve_consts");
     if (rc != MET2_OK) return rc;
     for (int k = 0; k < K; ++k) {
         if (a_out) a_out[k] = h[1].a[k];
@@ -582,25 +551,21 @@ extern "C" int met2_pve_energy(int32_t device, int64_t n, const double *v, const
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
     const BiasGrid g = bias_grid(n);
-    const size_t b_idx = up256((size_t)n * 4), b_cnt = up256((size_t)g.nch * 4), b_st = up256(sizeof(BiasStats)), b_rec = up256(sizeof(PveRec));
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_idx + 2 * b_cnt + b_st + b_rec));
-    char *at = work;
-    auto take = [&at](size_t b) { char *p = at; at += b; return p; };
-    int32_t *idx = (int32_t *)take(b_idx), *cnt = (int32_t *)take(b_cnt), *off = (int32_t *)take(b_cnt);
-    BiasStats *S = (BiasStats *)take(b_st);
-    PveRec *R = (PveRec *)take(b_rec);
+    DeviceWork W(st);
+    const auto idx = W.take<int32_t>(n), cnt = W.take<int32_t>(g.nch), off = W.take<int32_t>(g.nch);
+    const auto S = W.take<BiasStats>(1);
+    const auto R = W.take<PveRec>(1);
+    if (!W.alloc()) return W.finish("met2_pve_energy");
     std::vector<PveRec> h(1);                                          // alive until the wait
     pve_record(K, classes_in, &h[0]);
-    hipError_t err = hipMemcpyAsync(R, &h[0], sizeof(PveRec), hipMemcpyHostToDevice, st);
-    if (err == hipSuccess) err = hipMemsetAsync(E_out, 0, (size_t)n * 8 * (2 * K - 1), st);
-    if (err == hipSuccess) {
+    W.ok(hipMemcpyAsync(R, &h[0], sizeof(PveRec), hipMemcpyHostToDevice, st));
+    if (W.ok() && W.ok(hipMemsetAsync(E_out, 0, (size_t)n * 8 * (2 * K - 1), st))) {
         enq_pve_domain(st, g, seg, cnt, off, idx, S);
         enq_pve_consts(st, R, K);
-        err = hipGetLastError();
+        W.ok(hipGetLastError());
     }
-    if (err == hipSuccess) err = enq_pve_energy(st, g, v, seg, idx, S, R, K, E_out, types_out);
-    return bias_finish("met2_pve_energy", err, st, work);
+    if (W.ok()) W.ok(enq_pve_energy(st, g, v, seg, idx, S, R, K, E_out, types_out));
+    return W.finish("met2_pve_energy");
 }
 
 extern "C" int met2_pve_icm(int32_t device, int32_t nx, int32_t ny, int32_t nz, uint8_t *types, const double *E, int32_t n_class,
@@ -618,24 +583,22 @@ extern "C" int met2_pve_icm(int32_t device, int32_t nx, int32_t ny, int32_t nz, 
     G.nx = nx; G.ny = ny; G.nz = nz; G.beta = beta_pv; G.wx = w[0]; G.wy = w[1]; G.wz = w[2];
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, up256(sizeof(PveRec))));
-    PveRec *R = (PveRec *)work;
+    DeviceWork W(st);
+    const auto R = W.take<PveRec>(1);
+    if (!W.alloc()) return W.finish("met2_pve_icm");
     std::vector<PveRec> h(1);                                          // alive until the wait
     std::memset(&h[0], 0, sizeof(PveRec));
     for (int t = 0; t < 2 * K - 1; ++t) {
         h[0].live[t] = live_in[t] != 0 ? 1 : 0;
         h[0].live[PVE_MAX_T] += h[0].live[t];
     }
-    hipError_t err = hipMemcpyAsync(R, &h[0], sizeof(PveRec), hipMemcpyHostToDevice, st);
-    if (err == hipSuccess) {
+    if (W.ok(hipMemcpyAsync(R, &h[0], sizeof(PveRec), hipMemcpyHostToDevice, st))) {
         if (colour < 0)
             enq_pve_icm(st, n_sweeps, types, E, R, K, G);
         else if (n_sweeps > 0)
             enq_pve_pass(st, colour, types, E, R, K, G);
-        err = hipGetLastError();
     }
-    return bias_finish("met2_pve_icm", err, st, work);
+    return W.finish("met2_pve_icm");
 }
 
 extern "C" int met2_pve_finish(int32_t device, int64_t n, const double *v, const uint8_t *types, int32_t n_class, const double *classes_in,
@@ -645,15 +608,12 @@ extern "C" int met2_pve_finish(int32_t device, int64_t n, const double *v, const
     const int K = n_class;
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, up256(sizeof(PveRec))));
-    PveRec *R = (PveRec *)work;
+    DeviceWork W(st);
+    const auto R = W.take<PveRec>(1);
+    if (!W.alloc()) return W.finish("met2_pve_finish");
     std::vector<PveRec> h(1);                                          // alive until the wait
     pve_record(K, classes_in, &h[0]);
-    hipError_t err = hipMemcpyAsync(R, &h[0], sizeof(PveRec), hipMemcpyHostToDevice, st);
-    if (err == hipSuccess) {
+    if (W.ok(hipMemcpyAsync(R, &h[0], sizeof(PveRec), hipMemcpyHostToDevice, st)))
         enq_pve_finish(st, bias_grid(n), v, types, R, K, pve, pveseg, mixeltype, (double *)nullptr);
-        err = hipGetLastError();
-    }
-    return bias_finish("met2_pve_finish", err, st, work);
+    return W.finish("met2_pve_finish");
 }

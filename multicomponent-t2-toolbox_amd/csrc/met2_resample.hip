@@ -25,6 +25,7 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "device_work.hpp"
 
 #pragma clang fp contract(off)
 
@@ -341,20 +342,15 @@ extern "C" int met2_resample(int32_t device, int32_t order, const int32_t src_di
     const int64_t budget = max_work_bytes > 0 ? max_work_bytes : dflt;
     const int chunk = (int)std::min<int64_t>(n_series, budget / lo);
     const int64_t nvox = lo / 8;
-    double *work = nullptr;
-    HIPCHK(hipMalloc(&work, (size_t)chunk * lo));
-    hipError_t err = hipSuccess;
-    for (int s0 = 0; s0 < n_series && err == hipSuccess; s0 += chunk) {
+    DeviceWork W(st);
+    const auto work = W.take<double>((size_t)chunk * nvox);
+    if (!W.alloc()) return W.finish("met2_resample");
+    for (int s0 = 0; s0 < n_series && W.ok(); s0 += chunk) {
         const int ns = std::min(chunk, n_series - s0);
-        err = rs_prefilter_launch(src_dims, ns, src + s0 * src_series_stride, src_voxel_stride, src_series_stride, work, st);
-        if (err == hipSuccess)
-            err = rs_interp_launch<3>(G, ns, work, 1, nvox, cval, dst + s0 * dst_series_stride, dst_voxel_stride, dst_series_stride, s0 == 0 ? inside : nullptr, st);
+        if (W.ok(rs_prefilter_launch(src_dims, ns, src + s0 * src_series_stride, src_voxel_stride, src_series_stride, work, st)))
+            W.ok(rs_interp_launch<3>(G, ns, work, 1, nvox, cval, dst + s0 * dst_series_stride, dst_voxel_stride, dst_series_stride, s0 == 0 ? inside : nullptr, st));
     }
-    const hipError_t sync = hipStreamSynchronize(st);
-    (void)hipFree(work);
-    if (err == hipSuccess) err = sync;
-    if (err != hipSuccess) return fail(MET2_E_HIP, std::string("met2_resample: ") + hipGetErrorString(err));
-    return MET2_OK;
+    return W.finish("met2_resample");
 }
 
 extern "C" int met2_resample_labels(int32_t device, const int32_t src_dims[3], const int32_t *labels, const int32_t dst_dims[3], const double A[12],

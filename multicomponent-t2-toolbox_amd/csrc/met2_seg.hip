@@ -43,26 +43,6 @@ struct SegGeom {
     double beta, wx, wy, wz;
 };
 
-// One rounding each.  The toolchain's __dmul_rn, __dadd_rn and __dsub_rn are the plain operators, which the compiler may contract into a fused
-// multiply-add once they are inlined; under this pragma it may not, so these are what those names promise.
-__device__ __forceinline__ double rn_mul(double x, double y)
-{
-#pragma clang fp contract(off)
-    return x * y;
-}
-
-__device__ __forceinline__ double rn_add(double x, double y)
-{
-#pragma clang fp contract(off)
-    return x + y;
-}
-
-__device__ __forceinline__ double rn_sub(double x, double y)
-{
-#pragma clang fp contract(off)
-    return x - y;
-}
-
 // D_k = (y - mu_k)^2 a_k + h_k
 __device__ __forceinline__ double seg_data_term(double yv, double mu, double a, double h)
 {
@@ -390,48 +370,41 @@ extern "C" int met2_tissue_segment(int32_t device, int32_t nx, int32_t ny, int32
     hipStream_t st = (hipStream_t)stream;
 
     const BiasGrid g = bias_grid(n);
-    const size_t b_d = up256((size_t)n * 8), b_idx = up256((size_t)n * 4), b_u8 = up256((size_t)n), b_cnt = up256((size_t)g.nch * 4);
-    const size_t b_part = up256((size_t)g.nch * 3 * BIAS_MAX_K * 8), b_st = up256(sizeof(BiasStats)), b_sc = up256(sizeof(SegConsts));
-    const size_t b_prob = prob ? up256((size_t)n * 8 * K) : 0;
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, 2 * b_d + b_idx + 2 * b_u8 + 2 * b_cnt + b_part + b_st + b_sc + b_prob));
-    char *at = work;
-    auto take = [&at](size_t b) { char *p = at; at += b; return p; };
-    double *y = (double *)take(b_d), *b = (double *)take(b_d);
-    int32_t *idx = (int32_t *)take(b_idx);
-    uint8_t *dom = (uint8_t *)take(b_u8), *lab = (uint8_t *)take(b_u8);
-    int32_t *cnt = (int32_t *)take(b_cnt), *off = (int32_t *)take(b_cnt);
-    double *part = (double *)take(b_part);
-    BiasStats *S = (BiasStats *)take(b_st);
-    SegConsts *SC = (SegConsts *)take(b_sc);
-    double *prob_raw = prob ? (double *)take(b_prob) : nullptr;
+    DeviceWork W(st);
+    const auto y = W.take<double>(n), b = W.take<double>(n);
+    const auto idx = W.take<int32_t>(n);
+    const auto dom = W.take<uint8_t>(n), lab = W.take<uint8_t>(n);
+    const auto cnt = W.take<int32_t>(g.nch), off = W.take<int32_t>(g.nch);
+    const auto part = W.take<double>((size_t)g.nch * 3 * BIAS_MAX_K);
+    const auto S = W.take<BiasStats>(1);
+    const auto SC = W.take<SegConsts>(1);
+    const auto praw = W.take<double>(prob ? (size_t)n * K : 0);
+    if (!W.alloc()) return W.finish("met2_tissue_segment");
+    double *prob_raw = prob ? (double *)praw : nullptr;
 
-    hipError_t err = hipSuccess;
-    auto ok = [&](hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; return err == hipSuccess; };
-    ok(hipMemsetAsync(S, 0, b_st, st));
-    ok(hipMemsetAsync(b, 0, b_d, st));                                  // step 1's EM runs with b = 0
-    if (err == hipSuccess) {
+    W.ok(hipMemsetAsync(S, 0, S.bytes, st));
+    W.ok(hipMemsetAsync(b, 0, b.bytes, st));                              // step 1's EM runs with b = 0
+    if (W.ok()) {
         enq_domain(st, g, v, mask, y, dom, cnt, off, idx, S);
         enq_init(st, g, y, idx, S, part, K);
         for (int em = 0; em < n_em; ++em) enq_em_step(st, g, y, b, idx, S, K, part);
         enq_seg_consts(st, S, SC, K);
-        ok(hipGetLastError());
+        W.ok(hipGetLastError());
     }
-    if (err == hipSuccess) ok(enq_seg_init(st, g, y, idx, S, SC, K, lab));
-    for (int it = 0; it < n_outer && err == hipSuccess; ++it) {
+    if (W.ok()) W.ok(enq_seg_init(st, g, y, idx, S, SC, K, lab));
+    for (int it = 0; it < n_outer && W.ok(); ++it) {
         enq_seg_icm(st, n_icm, lab, y, S, SC, K, G);
         enq_seg_posterior(st, g, y, idx, lab, S, SC, K, G, part, nullptr);
         hipLaunchKernelGGL(bias_mstep_kernel, dim3(1), dim3(256), 0, st, part, g.nch, S, K);
         enq_seg_consts(st, S, SC, K);
-        ok(hipGetLastError());
+        W.ok(hipGetLastError());
     }
-    if (err == hipSuccess) {
+    if (W.ok()) {
         enq_seg_icm(st, n_icm, lab, y, S, SC, K, G);
         if (prob) enq_seg_posterior(st, g, y, idx, lab, S, SC, K, G, part, prob_raw);
         if (seg || prob || classes) enq_seg_finish(st, g, lab, dom, prob_raw, S, K, seg, prob, classes);
-        ok(hipGetLastError());
     }
-    return bias_finish("met2_tissue_segment", err, st, work);
+    return W.finish("met2_tissue_segment");
 }
 
 // ---- the stages one by one, for tests and diagnostics (include/met2_hip.h) ----
@@ -443,19 +416,17 @@ extern "C" int met2_seg_consts(int32_t device, int32_t n_class, const double *cl
     if (int rc = seg_record(1, n_class, classes_in, &h)) return rc;
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
-    const size_t b_st = up256(sizeof(BiasStats)), b_sc = up256(sizeof(SegConsts));
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_st + b_sc));
-    BiasStats *S = (BiasStats *)work;
-    SegConsts *SC = (SegConsts *)(work + b_st);
+    DeviceWork W(st);
+    const auto S = W.take<BiasStats>(1);
+    const auto SC = W.take<SegConsts>(1);
+    if (!W.alloc()) return W.finish("met2_seg_consts");
     SegConsts c;
-    hipError_t err = hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st);          // h lives until the wait
-    if (err == hipSuccess) {
+    if (W.ok(hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st))) {               // h lives until the wait
         enq_seg_consts(st, S, SC, n_class);
-        err = hipGetLastError();
+        W.ok(hipGetLastError());
     }
-    if (err == hipSuccess) err = hipMemcpyAsync(&c, SC, sizeof c, hipMemcpyDeviceToHost, st);
-    const int rc = bias_finish("met2_seg_consts", err, st, work);
+    if (W.ok()) W.ok(hipMemcpyAsync(&c, SC, sizeof c, hipMemcpyDeviceToHost, st));
+    const int rc = W.finish("met2_seg_consts");
     if (rc != MET2_OK) return rc;
     for (int k = 0; k < n_class; ++k) {
         if (a_out) a_out[k] = c.a[k];
@@ -476,19 +447,16 @@ extern "C" int met2_seg_init(int32_t device, int64_t n, const double *y, const i
     if (n > 0x7fffffffLL) return fail(MET2_E_UNSUPPORTED, "volume too large");
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
-    const size_t b_st = up256(sizeof(BiasStats)), b_sc = up256(sizeof(SegConsts));
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_st + b_sc));
-    BiasStats *S = (BiasStats *)work;
-    SegConsts *SC = (SegConsts *)(work + b_st);
-    hipError_t err = hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st);          // h lives until the wait
-    if (err == hipSuccess) {
+    DeviceWork W(st);
+    const auto S = W.take<BiasStats>(1);
+    const auto SC = W.take<SegConsts>(1);
+    if (!W.alloc()) return W.finish("met2_seg_init");
+    if (W.ok(hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st))) {               // h lives until the wait
         enq_seg_consts(st, S, SC, n_class);
-        err = hipGetLastError();
+        W.ok(hipGetLastError());
     }
-    if (err == hipSuccess) err = enq_seg_init(st, bias_grid(n), y, idx, S, SC, n_class, labels);
-    if (err == hipSuccess) err = hipGetLastError();
-    return bias_finish("met2_seg_init", err, st, work);
+    if (W.ok()) W.ok(enq_seg_init(st, bias_grid(n), y, idx, S, SC, n_class, labels));
+    return W.finish("met2_seg_init");
 }
 
 extern "C" int met2_seg_icm(int32_t device, int32_t nx, int32_t ny, int32_t nz, uint8_t *labels, const double *y, int32_t n_class,
@@ -508,21 +476,18 @@ extern "C" int met2_seg_icm(int32_t device, int32_t nx, int32_t ny, int32_t nz, 
     G.nx = nx; G.ny = ny; G.nz = nz; G.beta = beta; G.wx = w[0]; G.wy = w[1]; G.wz = w[2];
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
-    const size_t b_st = up256(sizeof(BiasStats)), b_sc = up256(sizeof(SegConsts));
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_st + b_sc));
-    BiasStats *S = (BiasStats *)work;
-    SegConsts *SC = (SegConsts *)(work + b_st);
-    hipError_t err = hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st);          // h lives until the wait
-    if (err == hipSuccess) {
+    DeviceWork W(st);
+    const auto S = W.take<BiasStats>(1);
+    const auto SC = W.take<SegConsts>(1);
+    if (!W.alloc()) return W.finish("met2_seg_icm");
+    if (W.ok(hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st))) {               // h lives until the wait
         enq_seg_consts(st, S, SC, n_class);
         if (colour < 0)
             enq_seg_icm(st, n_sweeps, labels, y, S, SC, n_class, G);
         else if (n_sweeps > 0)
             enq_seg_pass(st, colour, labels, y, S, SC, n_class, G);
-        err = hipGetLastError();
     }
-    return bias_finish("met2_seg_icm", err, st, work);
+    return W.finish("met2_seg_icm");
 }
 
 extern "C" int met2_seg_posterior(int32_t device, int32_t nx, int32_t ny, int32_t nz, const uint8_t *labels, const double *y, const int32_t *idx,
@@ -544,26 +509,25 @@ extern "C" int met2_seg_posterior(int32_t device, int32_t nx, int32_t ny, int32_
     hipStream_t st = (hipStream_t)stream;
     const BiasGrid g = bias_grid(n);
     const int np = (int)((n_domain + BIAS_CHUNK - 1) / BIAS_CHUNK);
-    const size_t b_part = up256((size_t)g.nch * 3 * BIAS_MAX_K * 8), b_st = up256(sizeof(BiasStats)), b_sc = up256(sizeof(SegConsts));
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_part + b_st + b_sc));
-    double *part = (double *)work;
-    BiasStats *S = (BiasStats *)(work + b_part);
-    SegConsts *SC = (SegConsts *)(work + b_part + b_st);
+    DeviceWork W(st);
+    const auto part = W.take<double>((size_t)g.nch * 3 * BIAS_MAX_K);
+    const auto S = W.take<BiasStats>(1);
+    const auto SC = W.take<SegConsts>(1);
+    if (!W.alloc()) return W.finish("met2_seg_posterior");
     std::vector<double> hp((size_t)3 * n_class * np);
-    hipError_t err = hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st);          // h lives until the wait
-    if (err == hipSuccess && prob_out) err = hipMemsetAsync(prob_out, 0, (size_t)n * 8 * n_class, st);
-    if (err == hipSuccess) {
+    W.ok(hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st));                     // h lives until the wait
+    if (W.ok() && prob_out) W.ok(hipMemsetAsync(prob_out, 0, (size_t)n * 8 * n_class, st));
+    if (W.ok()) {
         enq_seg_consts(st, S, SC, n_class);
         enq_seg_posterior(st, g, y, idx, labels, S, SC, n_class, G, part, prob_out);
-        err = hipGetLastError();
+        W.ok(hipGetLastError());
     }
-    if (err == hipSuccess && part_out)
-        for (int q = 0; q < 3 && err == hipSuccess; ++q)
-            for (int k = 0; k < n_class && err == hipSuccess; ++k)
-                err = hipMemcpyAsync(hp.data() + ((size_t)q * n_class + k) * np, part + (int64_t)(q * BIAS_MAX_K + k) * g.nch, (size_t)np * 8,
-                                     hipMemcpyDeviceToHost, st);
-    const int rc = bias_finish("met2_seg_posterior", err, st, work);
+    if (part_out)
+        for (int q = 0; q < 3; ++q)
+            for (int k = 0; k < n_class && W.ok(); ++k)
+                W.ok(hipMemcpyAsync(hp.data() + ((size_t)q * n_class + k) * np, part + (int64_t)(q * BIAS_MAX_K + k) * g.nch, (size_t)np * 8,
+                                    hipMemcpyDeviceToHost, st));
+    const int rc = W.finish("met2_seg_posterior");
     if (rc != MET2_OK) return rc;
     if (part_out) std::memcpy(part_out, hp.data(), hp.size() * 8);
     return MET2_OK;
@@ -580,19 +544,17 @@ extern "C" int met2_seg_finish(int32_t device, int64_t n, const uint8_t *labels,
     if (n > 0x7fffffffLL) return fail(MET2_E_UNSUPPORTED, "volume too large");
     USE_DEVICE(device);
     hipStream_t st = (hipStream_t)stream;
-    const size_t b_st = up256(sizeof(BiasStats)), b_c = up256((size_t)3 * BIAS_MAX_K * 8);
-    char *work = nullptr;
-    HIPCHK(hipMalloc(&work, b_st + b_c));
-    BiasStats *S = (BiasStats *)work;
-    double *cd = (double *)(work + b_st);
+    DeviceWork W(st);
+    const auto S = W.take<BiasStats>(1);
+    const auto cd = W.take<double>(3 * BIAS_MAX_K);
+    if (!W.alloc()) return W.finish("met2_seg_finish");
     double hc[3 * BIAS_MAX_K];
-    hipError_t err = hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st);          // h lives until the wait
-    if (err == hipSuccess) {
+    if (W.ok(hipMemcpyAsync(S, &h, sizeof h, hipMemcpyHostToDevice, st))) {               // h lives until the wait
         enq_seg_finish(st, bias_grid(n), labels, (const uint8_t *)nullptr, prob_raw, S, n_class, seg, prob, cd);
-        err = hipGetLastError();
+        W.ok(hipGetLastError());
     }
-    if (err == hipSuccess) err = hipMemcpyAsync(hc, cd, (size_t)3 * n_class * 8, hipMemcpyDeviceToHost, st);
-    const int rc = bias_finish("met2_seg_finish", err, st, work);
+    if (W.ok()) W.ok(hipMemcpyAsync(hc, cd, (size_t)3 * n_class * 8, hipMemcpyDeviceToHost, st));
+    const int rc = W.finish("met2_seg_finish");
     if (rc != MET2_OK) return rc;
     if (classes_out) std::memcpy(classes_out, hc, (size_t)3 * n_class * 8);
     return MET2_OK;

@@ -27,6 +27,8 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "device_helpers.hpp"
+#include "device_work.hpp"
 #include "quantile.hpp"
 
 namespace {
@@ -39,14 +41,6 @@ namespace {
 #define STATS_IDX_BLOCKS 1024                   // blocks of voxels of the counting sort, at most
 #define STATS_KEY_BYTES ((size_t)256 << 20)     // the key matrix of a tile of series stays under this (one series at least)
 #define STATS_HIST_BYTES ((size_t)64 << 20)     // and its global histograms under this
-
-// the lanes of ONE wave exchange values through LDS (see met2_bootstrap.hip)
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // ---------------------------------------------------------------------------------------------------------------- member list
 
@@ -129,8 +123,9 @@ __global__ __launch_bounds__(256) void label_scan_labels_kernel(int n_label, con
 
 // ---------------------------------------------------------------------------------------------------------------- shared pieces
 
-// sum over the 256 threads of a workgroup in a fixed order: xor tree inside a wave, then the four waves in turn.  Every thread gets the sum.
-__device__ __forceinline__ double block_sum(double x, double *red4, int tid)
+// sum over the 256 threads of a workgroup in a fixed order: xor tree inside a wave, then the four waves in turn (not device_helpers.hpp's
+// block_sum, which adds the waves in pairs: other bits).  Every thread gets the sum.
+__device__ __forceinline__ double block_sum_chain(double x, double *red4, int tid)
 {
     for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
     __syncthreads();                                           // red4 may still be read from the call before
@@ -212,7 +207,7 @@ __global__ __launch_bounds__(256) void label_moment_kernel(MomArgs A)
     }
 #pragma unroll
     for (int s = 0; s < STATS_TS; ++s) {
-        const double t = block_sum(acc[s], red4, tid);
+        const double t = block_sum_chain(acc[s], red4, tid);
         long long n = 0;
         if (PASS == 0) n = block_sum_int(cnt[s], red4i, tid);
         if (tid == 0 && s < ns) {
@@ -246,7 +241,7 @@ __global__ __launch_bounds__(256) void label_moment_combine_kernel(CombArgs A)
         acc += A.part[(int64_t)(c0 + c) * A.n_series + s];
         if (PASS == 0) n += A.part_n[(int64_t)(c0 + c) * A.n_series + s];
     }
-    acc = block_sum(acc, red4, tid);
+    acc = block_sum_chain(acc, red4, tid);
     double *o = A.out + ((int64_t)l * A.n_series + s) * A.out_stride;
     if (PASS == 0) {
         n = block_sum_int(n, red4i, tid);
@@ -263,6 +258,7 @@ __global__ __launch_bounds__(256) void label_moment_combine_kernel(CombArgs A)
 // ---------------------------------------------------------------------------------------------------------------- quantiles
 
 // sortable key of a double: ascending keys = ascending values, -0.0 is +0.0, every NaN the largest key
+// (not sort_key of met2_bet.hip, which keeps -0.0 apart and gives NaN no place, or tv_key of met2_tv.hip, which orders magnitudes)
 __device__ __forceinline__ uint64_t to_key(double x)
 {
     if (x != x) return ~0ull;
@@ -314,7 +310,6 @@ struct QArgs {
     uint32_t *krank;                // [nseg][R] the rank among the keys that share the prefix
 };
 
-__device__ __forceinline__ int next_pow2_dev(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 
 // labels of at most SMALL_N members: workgroup = (label, series), bitonic sort of the keys in LDS, then quantile_sorted
 __global__ __launch_bounds__(256) void label_small_kernel(QArgs A)
@@ -327,7 +322,7 @@ __global__ __launch_bounds__(256) void label_small_kernel(QArgs A)
     double *o = A.out + ((int64_t)l * A.n_series + A.s0 + s) * A.out_stride + A.out_col;
     if (tid == 0) nan_s = 0;
     __syncthreads();
-    const int P = next_pow2_dev(len);
+    const int P = next_pow2(len);
     const uint64_t *k = A.keys + (int64_t)s * A.M + begin;
     int nan = 0;
     for (int i = tid; i < P; i += 256) {
@@ -483,24 +478,11 @@ __global__ __launch_bounds__(256) void label_select_finish_kernel(QArgs A)
 
 // ---------------------------------------------------------------------------------------------------------------- host side
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes)
-    {
-        HIPCHK(hipMalloc(&p, bytes ? bytes : 1));
-        return MET2_OK;
-    }
-    template <class T> T *as() const { return (T *)p; }
-};
-
-template <class T> int upload(DevBuf &b, const std::vector<T> &h, hipStream_t s)
+// h into its piece d of the work space W
+template <class T> bool upload(DeviceWork &W, void *d, const std::vector<T> &h, hipStream_t s)
 {
-    int rc = b.alloc(sizeof(T) * h.size());
-    if (rc) return rc;
-    if (!h.empty()) HIPCHK(hipMemcpyAsync(b.p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));                           // h may go away behind the call
-    return MET2_OK;
+    if (!h.empty()) W.ok(hipMemcpyAsync(d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, s));
+    return W.ok(hipStreamSynchronize(s));                      // h may go away behind the call
 }
 
 int common_checks(int32_t n_label, int32_t n_series, const double *values, int64_t voxel_stride, int64_t series_stride)
@@ -561,23 +543,20 @@ int index_impl(int64_t nvox, const int32_t *label, int n_label, int32_t *offset,
     const int64_t nb = std::max<int64_t>(1, std::min<int64_t>(STATS_IDX_BLOCKS, (nvox + 1023) / 1024));
     const int64_t per = ((std::max<int64_t>(nvox, 1) + nb - 1) / nb + 63) / 64 * 64;
     const int nblocks = (int)std::max<int64_t>(1, (nvox + per - 1) / per);
-    DevBuf cnt, total;
-    int rc = cnt.alloc(sizeof(int32_t) * (size_t)nblocks * n_label);
-    if (rc) return rc;
-    rc = total.alloc(sizeof(int32_t) * (size_t)n_label);
-    if (rc) return rc;
+    const char *who = "met2_label_index";
+    DeviceWork W(s);
+    const auto cnt = W.take<int32_t>((size_t)nblocks * n_label), total = W.take<int32_t>(n_label);
+    if (!W.alloc()) return W.finish(who);
     const size_t lds = sizeof(int32_t) * (size_t)n_label;
-    hipLaunchKernelGGL(label_index_kernel<false>, dim3(nblocks), dim3(64), lds, s, nvox, per, label, n_label, cnt.as<int32_t>(), (const int32_t *)nullptr,
+    hipLaunchKernelGGL(label_index_kernel<false>, dim3(nblocks), dim3(64), lds, s, nvox, per, label, n_label, cnt, (const int32_t *)nullptr,
                        (int32_t *)nullptr);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(label_scan_blocks_kernel, dim3((n_label + 255) / 256), dim3(256), 0, s, nblocks, n_label, cnt.as<int32_t>(), total.as<int32_t>());
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(label_scan_labels_kernel, dim3(1), dim3(256), 0, s, n_label, (const int32_t *)total.as<int32_t>(), offset);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(label_index_kernel<true>, dim3(nblocks), dim3(64), lds, s, nvox, per, label, n_label, cnt.as<int32_t>(), (const int32_t *)offset, order);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    return MET2_OK;
+    if (!W.ok(hipGetLastError())) return W.finish(who);
+    hipLaunchKernelGGL(label_scan_blocks_kernel, dim3((n_label + 255) / 256), dim3(256), 0, s, nblocks, n_label, cnt, total);
+    if (!W.ok(hipGetLastError())) return W.finish(who);
+    hipLaunchKernelGGL(label_scan_labels_kernel, dim3(1), dim3(256), 0, s, n_label, (const int32_t *)total, offset);
+    if (!W.ok(hipGetLastError())) return W.finish(who);
+    hipLaunchKernelGGL(label_index_kernel<true>, dim3(nblocks), dim3(64), lds, s, nvox, per, label, n_label, cnt, (const int32_t *)offset, order);
+    return W.finish(who);
 }
 
 TileSrc tile_src(const int32_t *order, const double *values, int64_t vs, int64_t ss)
@@ -593,34 +572,36 @@ int moments_impl(const std::vector<int32_t> &off, int n_label, const int32_t *or
     Chunks ch;
     ch.build(off, n_label, 0);
     const size_t nch = ch.label.size();
-    DevBuf d_label, d_begin, d_len, d_c0, d_nc, part, part_n;
-    int rc;
-    if ((rc = upload(d_label, ch.label, s)) || (rc = upload(d_begin, ch.begin, s)) || (rc = upload(d_len, ch.len, s)) ||
-        (rc = upload(d_c0, ch.chunk0, s)) || (rc = upload(d_nc, ch.nchunks, s)))
-        return rc;
-    if ((rc = part.alloc(sizeof(double) * nch * n_series)) || (rc = part_n.alloc(sizeof(int32_t) * nch * n_series))) return rc;
+    const char *who = "met2_label_moments";
+    DeviceWork W(s);
+    const auto d_label = W.take<int32_t>(nch), d_begin = W.take<int32_t>(nch), d_len = W.take<int32_t>(nch);
+    const auto d_c0 = W.take<int32_t>(n_label), d_nc = W.take<int32_t>(n_label);
+    const auto part = W.take<double>(nch * n_series);
+    const auto part_n = W.take<int32_t>(nch * n_series);
+    if (!W.alloc()) return W.finish(who);
+    if (!upload(W, d_label, ch.label, s) || !upload(W, d_begin, ch.begin, s) || !upload(W, d_len, ch.len, s) || !upload(W, d_c0, ch.chunk0, s) ||
+        !upload(W, d_nc, ch.nchunks, s))
+        return W.finish(who);
     MomArgs M;
     M.src = tile_src(order, values, vs, ss);
-    M.chunk_label = d_label.as<int32_t>(); M.chunk_begin = d_begin.as<int32_t>(); M.chunk_len = d_len.as<int32_t>();
-    M.n_series = n_series; M.part = part.as<double>(); M.part_n = part_n.as<int32_t>(); M.out = out; M.out_stride = out_stride;
+    M.chunk_label = d_label; M.chunk_begin = d_begin; M.chunk_len = d_len;
+    M.n_series = n_series; M.part = part; M.part_n = part_n; M.out = out; M.out_stride = out_stride;
     CombArgs Cb;
-    Cb.label_chunk0 = d_c0.as<int32_t>(); Cb.label_nchunks = d_nc.as<int32_t>(); Cb.n_series = n_series; Cb.part = part.as<double>();
-    Cb.part_n = part_n.as<int32_t>(); Cb.out = out; Cb.out_stride = out_stride;
+    Cb.label_chunk0 = d_c0; Cb.label_nchunks = d_nc; Cb.n_series = n_series; Cb.part = part;
+    Cb.part_n = part_n; Cb.out = out; Cb.out_stride = out_stride;
     const dim3 gm((unsigned)nch, (unsigned)((n_series + STATS_TS - 1) / STATS_TS)), gc((unsigned)n_label, (unsigned)n_series);
     if (nch) {
         hipLaunchKernelGGL(label_moment_kernel<0>, gm, dim3(256), 0, s, M);
-        HIPCHK(hipGetLastError());
+        if (!W.ok(hipGetLastError())) return W.finish(who);
     }
     hipLaunchKernelGGL(label_moment_combine_kernel<0>, gc, dim3(256), 0, s, Cb);
-    HIPCHK(hipGetLastError());
+    if (!W.ok(hipGetLastError())) return W.finish(who);
     if (nch) {
         hipLaunchKernelGGL(label_moment_kernel<1>, gm, dim3(256), 0, s, M);
-        HIPCHK(hipGetLastError());
+        if (!W.ok(hipGetLastError())) return W.finish(who);
     }
     hipLaunchKernelGGL(label_moment_combine_kernel<1>, gc, dim3(256), 0, s, Cb);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    return MET2_OK;
+    return W.finish(who);
 }
 
 int quantiles_impl(const std::vector<int32_t> &off, int n_label, const int32_t *offset, const int32_t *order, int n_series, const double *values,
@@ -639,55 +620,56 @@ int quantiles_impl(const std::vector<int32_t> &off, int n_label, const int32_t *
     ts = std::min<int64_t>(ts, std::max<int64_t>(1, (int64_t)(STATS_HIST_BYTES / ((size_t)n_label * R * 256 * sizeof(uint32_t)))));
     ts = std::min<int64_t>(ts, 32768);
     const int64_t nseg = ts * n_label;
-    DevBuf keys, ghist, nanc, pre_a, pre_b, krank, d_q, d_label, d_begin, d_len;
-    int rc;
+    const char *who = "met2_label_quantiles";
+    DeviceWork W(s);
+    const size_t sel = nch ? (size_t)nseg : 0;                 // the selection's pieces are empty without a large label: its kernels are not launched
+    const auto d_q = W.take<double>(n_q);
+    const auto d_label = W.take<int32_t>(nch), d_begin = W.take<int32_t>(nch), d_len = W.take<int32_t>(nch);
+    const auto keys = W.take<uint64_t>((size_t)ts * (size_t)M);
+    const auto ghist = W.take<uint32_t>(sel * R * 256);
+    const auto nanc = W.take<int32_t>(sel);
+    const auto pre_a = W.take<uint64_t>(sel * R), pre_b = W.take<uint64_t>(sel * R);
+    const auto krank = W.take<uint32_t>(sel * R);
+    if (!W.alloc()) return W.finish(who);
     std::vector<double> qv(q_host, q_host + n_q);
-    if ((rc = upload(d_q, qv, s)) || (rc = upload(d_label, ch.label, s)) || (rc = upload(d_begin, ch.begin, s)) || (rc = upload(d_len, ch.len, s)))
-        return rc;
-    if ((rc = keys.alloc(sizeof(uint64_t) * (size_t)ts * (size_t)M))) return rc;
-    const size_t hist_bytes = sizeof(uint32_t) * (size_t)nseg * R * 256;
-    if (nch) {
-        if ((rc = ghist.alloc(hist_bytes)) || (rc = nanc.alloc(sizeof(int32_t) * (size_t)nseg)) || (rc = pre_a.alloc(sizeof(uint64_t) * (size_t)nseg * R)) ||
-            (rc = pre_b.alloc(sizeof(uint64_t) * (size_t)nseg * R)) || (rc = krank.alloc(sizeof(uint32_t) * (size_t)nseg * R)))
-            return rc;
-    }
+    if (!upload(W, d_q, qv, s) || !upload(W, d_label, ch.label, s) || !upload(W, d_begin, ch.begin, s) || !upload(W, d_len, ch.len, s))
+        return W.finish(who);
     QArgs Q;
-    Q.keys = keys.as<uint64_t>(); Q.M = M; Q.offset = offset; Q.n_label = n_label; Q.n_series = n_series; Q.n_q = n_q; Q.R = R; Q.q = d_q.as<double>();
+    Q.keys = keys; Q.M = M; Q.offset = offset; Q.n_label = n_label; Q.n_series = n_series; Q.n_q = n_q; Q.R = R; Q.q = d_q;
     Q.out = out; Q.out_stride = out_stride; Q.out_col = out_col;
-    Q.chunk_label = d_label.as<int32_t>(); Q.chunk_begin = d_begin.as<int32_t>(); Q.chunk_len = d_len.as<int32_t>();
-    Q.ghist = ghist.as<uint32_t>(); Q.nan_count = nanc.as<int32_t>(); Q.krank = krank.as<uint32_t>();
+    Q.chunk_label = d_label; Q.chunk_begin = d_begin; Q.chunk_len = d_len;
+    Q.ghist = ghist; Q.nan_count = nanc; Q.krank = krank;
     const TileSrc src = tile_src(order, values, vs, ss);
     for (int64_t s0 = 0; s0 < n_series; s0 += ts) {
         const int ns = (int)std::min<int64_t>(ts, n_series - s0);
         Q.s0 = (int)s0; Q.ns = ns;
         if (M > 0) {
             hipLaunchKernelGGL(label_key_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)((ns + STATS_TS - 1) / STATS_TS)), dim3(256), 0, s, src, M,
-                               (int)s0, ns, keys.as<uint64_t>());
-            HIPCHK(hipGetLastError());
+                               (int)s0, ns, keys);
+            if (!W.ok(hipGetLastError())) return W.finish(who);
         }
         if (any_small) {
             hipLaunchKernelGGL(label_small_kernel, dim3((unsigned)n_label, (unsigned)ns), dim3(256), 0, s, Q);
-            HIPCHK(hipGetLastError());
+            if (!W.ok(hipGetLastError())) return W.finish(who);
         }
         if (!nch) continue;
-        HIPCHK(hipMemsetAsync(nanc.p, 0, sizeof(int32_t) * (size_t)nseg, s));
+        if (!W.ok(hipMemsetAsync(nanc, 0, sizeof(int32_t) * (size_t)nseg, s))) return W.finish(who);
         const unsigned step_grid = (unsigned)(((int64_t)ns * n_label * R + 255) / 256);
         for (int level = 0; level < 8; ++level) {
             Q.level = level;
-            Q.prefix_in = (level & 1) ? pre_a.as<uint64_t>() : pre_b.as<uint64_t>();
-            Q.prefix_out = (level & 1) ? pre_b.as<uint64_t>() : pre_a.as<uint64_t>();
-            HIPCHK(hipMemsetAsync(ghist.p, 0, sizeof(uint32_t) * (size_t)ns * n_label * R * 256, s));
+            Q.prefix_in = (level & 1) ? pre_a : pre_b;
+            Q.prefix_out = (level & 1) ? pre_b : pre_a;
+            if (!W.ok(hipMemsetAsync(ghist, 0, sizeof(uint32_t) * (size_t)ns * n_label * R * 256, s))) return W.finish(who);
             hipLaunchKernelGGL(label_select_hist_kernel, dim3((unsigned)nch, (unsigned)ns), dim3(256), 0, s, Q);
-            HIPCHK(hipGetLastError());
+            if (!W.ok(hipGetLastError())) return W.finish(who);
             hipLaunchKernelGGL(label_select_step_kernel, dim3(step_grid), dim3(256), 0, s, Q);
-            HIPCHK(hipGetLastError());
+            if (!W.ok(hipGetLastError())) return W.finish(who);
         }
-        Q.prefix_in = pre_b.as<uint64_t>();                    // level 7 wrote pre_b
+        Q.prefix_in = pre_b;                                   // level 7 wrote pre_b
         hipLaunchKernelGGL(label_select_finish_kernel, dim3((unsigned)(((int64_t)ns * n_label * n_q + 255) / 256)), dim3(256), 0, s, Q);
-        HIPCHK(hipGetLastError());
+        if (!W.ok(hipGetLastError())) return W.finish(who);
     }
-    HIPCHK(hipStreamSynchronize(s));
-    return MET2_OK;
+    return W.finish(who);
 }
 
 }  // namespace
@@ -749,14 +731,14 @@ extern "C" int met2_label_stats(int32_t device, int64_t nvox, const int32_t *lab
     if (nvox > 0x7fffffff) return fail(MET2_E_UNSUPPORTED, "2^31 voxels or more");
     USE_DEVICE(device);
     hipStream_t s = (hipStream_t)stream;
-    DevBuf offset, order;
-    if ((rc = offset.alloc(sizeof(int32_t) * ((size_t)n_label + 1))) || (rc = order.alloc(sizeof(int32_t) * (size_t)nvox))) return rc;
-    if ((rc = index_impl(nvox, label, n_label, offset.as<int32_t>(), order.as<int32_t>(), s))) return rc;
+    DeviceWork W(s);                                           // every stage below waits for the stream before it returns
+    const auto offset = W.take<int32_t>((size_t)n_label + 1), order = W.take<int32_t>(nvox);
+    if (!W.alloc()) return W.finish("met2_label_stats");
+    if ((rc = index_impl(nvox, label, n_label, offset, order, s))) return rc;
     std::vector<int32_t> off;
-    if ((rc = fetch_offsets(offset.as<int32_t>(), n_label, off, s))) return rc;
+    if ((rc = fetch_offsets(offset, n_label, off, s))) return rc;
     const int64_t stride = 3 + n_q;
-    if ((rc = moments_impl(off, n_label, order.as<int32_t>(), n_series, values, voxel_stride, series_stride, out, stride, s))) return rc;
+    if ((rc = moments_impl(off, n_label, order, n_series, values, voxel_stride, series_stride, out, stride, s))) return rc;
     if (n_q == 0) return MET2_OK;
-    return quantiles_impl(off, n_label, offset.as<int32_t>(), order.as<int32_t>(), n_series, values, voxel_stride, series_stride, n_q, q_host, out,
-                          stride, 3, s);
+    return quantiles_impl(off, n_label, offset, order, n_series, values, voxel_stride, series_stride, n_q, q_host, out, stride, 3, s);
 }

@@ -33,6 +33,8 @@
 
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
+#include "device_helpers.hpp"
+#include "device_work.hpp"
 
 namespace {
 
@@ -133,17 +135,6 @@ __global__ __launch_bounds__(256) void tv_detail_kernel(TvDetailArgs A)
     A.coef[(int64_t)t * A.nc + o] = s3;
 }
 
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v)               // butterfly: the same order on every run
-{
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 struct TvSigmaArgs {
     int64_t nc;
     const double *coef;
@@ -157,6 +148,7 @@ struct TvSigmaArgs {
 // candidates are gathered into LDS and the remaining bits are decided there, one per pass; (3) for an even count one more pass over the
 // array finds the upper middle value (the smallest key above the lower one, unless the lower one is repeated).
 #define TV_SIGMA_CAP 6144
+// (not sort_key of met2_bet.hip or to_key of met2_stats.hip: the key orders |v|, and a zero of either sign sorts last, out of the median's set)
 __device__ __forceinline__ unsigned long long tv_key(double v)
 {
     return (v == 0.0) ? ~0ull : (unsigned long long)__double_as_longlong(fabs(v));
@@ -171,7 +163,7 @@ __global__ __launch_bounds__(1024) void tv_sigma_kernel(TvSigmaArgs A)
     const double *c = A.coef + (int64_t)t * A.nc;
     // block-wide sums of up to four per-thread counters
     auto block_sum4 = [&](long long v0, long long v1, long long v2, long long v3, long long *out) {
-        int a0 = wave_sum_i((int)v0), a1 = wave_sum_i((int)v1), a2 = wave_sum_i((int)v2), a3 = wave_sum_i((int)v3);
+        int a0 = wave_sum_xor((int)v0), a1 = wave_sum_xor((int)v1), a2 = wave_sum_xor((int)v2), a3 = wave_sum_xor((int)v3);
         __syncthreads();                                             // the previous use of red[] has been read
         if (lane == 0) { red[0][w] = a0; red[1][w] = a1; red[2][w] = a2; red[3][w] = a3; }
         __syncthreads();
@@ -436,7 +428,7 @@ __global__ __launch_bounds__(64 * OY, MET2_TV_WPE) void tv_iter_kernel(TvIterArg
         if (EDGE) { hp0 = bcast_lane(hnxt, 0); hnxt = hnn; oh_c = oh_n; }
         __syncthreads();
     }
-    acc_d = wave_sum_d(acc_d); acc_n = wave_sum_d(acc_n);
+    acc_d = wave_sum_xor(acc_d); acc_n = wave_sum_xor(acc_n);
     if (lane == 0) { red[0][wy] = acc_d; red[1][wy] = acc_n; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -654,14 +646,13 @@ extern "C" int met2_tv_detail(int32_t device, int32_t nx, int32_t ny, int32_t nz
     if (!rev && tv_gather_lds(n_te) > 64 * 1024) return fail(MET2_E_UNSUPPORTED, "more than 127 echoes: pass the volume echo-major");
     USE_DEVICE(device);
     hipStream_t s = (hipStream_t)stream;
-    double *F = nullptr;
-    if (!rev) HIPCHK(hipMalloc((void **)&F, sizeof(double) * (size_t)L.elems));
-    struct Free { double *p; ~Free() { if (p) (void)hipFree(p); } } guard{F};
-    if (!rev) launch_gather(L, n_te, data, F, s);
+    DeviceWork W(s);
+    const auto piece = W.take<double>(rev ? 0 : (size_t)L.elems);
+    if (!W.alloc()) return W.finish("met2_tv_detail");
+    const double *F = piece;
+    if (!rev) launch_gather(L, n_te, data, piece, s);
     launch_detail(rev, n0, n1, n2, L, n_te, rev ? data : F, coef, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    return MET2_OK;
+    return W.finish("met2_tv_detail");
 }
 
 extern "C" int met2_tv_sigma(int32_t device, int32_t n_te, int64_t nc, const double *coef, const double *weight, double weight_factor,
@@ -672,21 +663,15 @@ extern "C" int met2_tv_sigma(int32_t device, int32_t n_te, int64_t nc, const dou
     if (!coef) return fail(MET2_E_INVALID, "NULL argument");
     USE_DEVICE(device);
     hipStream_t s = (hipStream_t)stream;
-    const size_t state_bytes = (sizeof(TvState) * (size_t)n_te + 255) & ~(size_t)255;
-    char *W = nullptr;
-    HIPCHK(hipMalloc((void **)&W, state_bytes + sizeof(double) * (size_t)n_te));
-    struct Free { char *p; ~Free() { if (p) (void)hipFree(p); } } guard{W};
-    TvState *state = (TvState *)W;
-    double *dweight = nullptr;
-    if (weight) {
-        dweight = (double *)(W + state_bytes);
-        HIPCHK(hipMemcpyAsync(dweight, weight, sizeof(double) * n_te, hipMemcpyHostToDevice, s));
-    }
+    DeviceWork W(s);
+    const auto state = W.take<TvState>(n_te);
+    const auto dw = W.take<double>(n_te);
+    if (!W.alloc()) return W.finish("met2_tv_sigma");
+    double *dweight = weight ? (double *)dw : nullptr;
+    if (weight && !W.ok(hipMemcpyAsync(dweight, weight, sizeof(double) * n_te, hipMemcpyHostToDevice, s))) return W.finish("met2_tv_sigma");
     launch_sigma(n_te, nc, coef, state, weight_factor, dweight, s);
     hipLaunchKernelGGL(tv_sigma_report_kernel, dim3((unsigned)((n_te + 63) / 64)), dim3(64), 0, s, (int)n_te, (const TvState *)state, sigma, weight_out, copy);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    return MET2_OK;
+    return W.finish("met2_tv_sigma");
 }
 
 extern "C" int met2_tv_chambolle(int32_t device, int32_t nx, int32_t ny, int32_t nz, int32_t n_te, const double *data, int32_t echo_major,
@@ -708,12 +693,13 @@ extern "C" int met2_tv_chambolle(int32_t device, int32_t nx, int32_t ny, int32_t
     if (work && work_bytes < (int64_t)L.bytes) return fail(MET2_E_INVALID, "work buffer smaller than met2_tv_work_bytes()");
     USE_DEVICE(device);
     hipStream_t s = (hipStream_t)stream;
-    char *W = (char *)work;
-    if (!W) HIPCHK(hipMalloc((void **)&W, L.bytes));
-    struct Free { char *p; bool own; ~Free() { if (own && p) (void)hipFree(p); } } guard{W, work == nullptr};
-    double *F = (double *)(W + L.off_F), *P0 = (double *)(W + L.off_P0), *P1 = (double *)(W + L.off_P1);
-    double *coef = (double *)(W + L.off_coef), *partial = (double *)(W + L.off_partial);
-    TvState *state = (TvState *)(W + L.off_state);
+    DeviceWork W(s);                                                 // the caller's work space is neither waited for nor freed
+    const auto block = W.take<char>(L.bytes);                        // one piece: tv_layout, which met2_tv_work_bytes reports from, lays it out
+    if (!W.alloc(work)) return W.finish("met2_tv_chambolle");
+    char *B = block;
+    double *F = (double *)(B + L.off_F), *P0 = (double *)(B + L.off_P0), *P1 = (double *)(B + L.off_P1);
+    double *coef = (double *)(B + L.off_coef), *partial = (double *)(B + L.off_partial);
+    TvState *state = (TvState *)(B + L.off_state);
     const size_t lds_t = tv_gather_lds(n_te);
     if (!rev && lds_t > 64 * 1024) return fail(MET2_E_UNSUPPORTED, "more than 127 echoes: pass the volume echo-major");
 
@@ -724,7 +710,7 @@ extern "C" int met2_tv_chambolle(int32_t device, int32_t nx, int32_t ny, int32_t
     // 2. noise level and weight per echo
     double *dweight = nullptr;
     if (weight) {
-        dweight = (double *)(W + L.off_weight);
+        dweight = (double *)(B + L.off_weight);
         HIPCHK(hipMemcpyAsync(dweight, weight, sizeof(double) * n_te, hipMemcpyHostToDevice, s));
     }
     if (!weight || sigma) {
@@ -798,9 +784,7 @@ extern "C" int met2_tv_chambolle(int32_t device, int32_t nx, int32_t ny, int32_t
         hipLaunchKernelGGL(tv_scatter_kernel, dim3((unsigned)((L.vol + 63) / 64)), dim3(256), lds_t, s, C);
     }
     if (sigma || iters) hipLaunchKernelGGL(tv_report_kernel, dim3((unsigned)((n_te + 63) / 64)), dim3(64), 0, s, (int)n_te, (const TvState *)state, sigma, iters);
-    HIPCHK(hipGetLastError());
-    if (!work) HIPCHK(hipStreamSynchronize(s));
-    return MET2_OK;
+    return W.finish("met2_tv_chambolle");
 }
 
 extern "C" int met2_tv_last_timing(double *iter_ms, int32_t *launches)

@@ -6,26 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_helpers.hpp"     // rn_mul, rn_add, rn_sub: the file-scope pragma already forbids contraction; they name the intent where the order is the contract
+
 namespace {
-
-// One rounding each: see met2_seg.hip.  (The file-scope pragma already forbids contraction; these name the intent where the order is the contract.)
-__device__ __forceinline__ double rn_mul(double x, double y)
-{
-#pragma clang fp contract(off)
-    return x * y;
-}
-
-__device__ __forceinline__ double rn_add(double x, double y)
-{
-#pragma clang fp contract(off)
-    return x + y;
-}
-
-__device__ __forceinline__ double rn_sub(double x, double y)
-{
-#pragma clang fp contract(off)
-    return x - y;
-}
 
 struct RsGeom {
     int nx, ny, nz;                        // source

@@ -41,6 +41,28 @@ def test_build_lists_name_every_source_and_header():
     assert {f for f in on_disk if f.endswith(".hpp")} == set(b.HEADERS) - {public}
 
 
+def test_imaging_units_share_one_work_space_owner_and_one_copy_of_the_helpers():
+    # a source check: a call's device work space is device_work.hpp's business, and a helper that several units need is defined once
+    b = importlib.import_module(PKG + "._build")
+    read = lambda f: open(os.path.join(b.CSRC, f)).read()
+    units = ["met2_bias.hip", "met2_seg.hip", "met2_pve.hip", "met2_bet.hip", "met2_gibbs.hip", "met2_mppca.hip", "met2_resample.hip", "met2_tv.hip",
+             "met2_stats.hip", "met2_prefilter.hip", "met2_dictionary.hip", "bias_common.hpp", "resample_taps.hpp"]
+    for f in units:
+        text = read(f)
+        if f == "met2_prefilter.hip":                       # the one exception: the FA-spline tables' cross-call cache, T.d
+            lines = [l for l in text.splitlines() if "hipMalloc(" in l or "hipFree(" in l]
+            assert lines and all("T.d" in l for l in lines), lines
+        else:
+            assert "hipMalloc(" not in text and "hipFree(" not in text, f
+        for gone in ("bias_finish", "DevBuf", "struct Free", "struct Scratch"):
+            assert gone not in text, (f, gone)
+    owner = read("device_work.hpp")
+    assert "hipMalloc(" in owner and "hipFree(" in owner
+    for name in ("rn_mul", "wave_lds_sync", "nan_last_gt"):
+        defined = [f for f in sorted(os.listdir(b.CSRC)) if f.endswith((".hip", ".hpp")) and re.search(r"^[\w \t]*\b(?:double|void|bool)\s+%s\s*\(" % name, read(f), re.M)]
+        assert defined == ["device_helpers.hpp"], (name, defined)
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     if torch.cuda.is_available():
