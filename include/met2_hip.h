@@ -1259,6 +1259,67 @@ int met2_plan_launch_info(met2_plan *plan, int32_t method, int32_t *grid, int32_
  * basis (true for EPG dictionaries: ~1e-10 at 48 x 120, ~1e-12 at 32 x 60); 0: from the (n_te + 1) x (n_te + 1) matrix. */
 int met2_plan_gcv_form(met2_plan *plan, int32_t *low_rank, double *residual);
 
+/* Resampling through a displacement field, and the device stages of a greedy deformable (non-linear) registration with the squared local
+ * normalised cross-correlation, LNCC (an extension; additive, ABI stays 6).  The loop around the stages is warp.py's: warp, force, fluid
+ * smoothing of the force (met2_smooth_separable), its largest norm, composition, elastic smoothing of the field.  The metric is that of ANTs'
+ * CC and of `greedy -m NCC` (Avants et al., Med. Image Anal. 12:26-41, 2008), and the force is their CENTRE-VOXEL approximation of its
+ * gradient, not the sum over all windows that hold a voxel.  Parity with ANTs, greedy or fnirt is unpinned: none was available.  No plan:
+ * `device` and `stream` only.  All arithmetic is fp64, no product is fused into a sum, every operation rounds once in the order written;
+ * there are no floating-point atomics.  DEVICE pointers except the dims, A and gain.
+ * Field.  disp [mx][my][mz][3] lives on the destination (fixed) grid, in voxels of that grid: the layout of echo data, so
+ *   met2_smooth_separable smooths a field with n_te = 3.
+ * met2_warp.  met2_resample with a field, orders 0 and 1: destination voxel x = (i, j, k) samples the source at c = A (x + u(x)):
+ *     p_a = x_a + u_a (one rounding per axis);  c_a = ((A[a][3] + A[a][0] p_x) + A[a][1] p_y) + A[a][2] p_z;
+ *   then the inside test, the taps, the weights and the tap sum of met2_resample.  A zero field reproduces met2_resample to the bit.  Strides,
+ *   series, cval and inside as there.  Asynchronous.  disp == NULL is refused (met2_resample is that call).
+ * met2_warp_labels.  int32 labels, order 0, `fill` where outside.  Asynchronous.
+ * met2_warp_compose.  The one kernel for composition and for a change of grid.  u_src [nx][ny][nz][3] on its own grid, the destination grid
+ *   [mx][my][mz], A[12] (destination voxel -> u_src's voxel), gain[3], v [mx][my][mz][3] or NULL, step, vmax2 (one double on the device) or NULL:
+ *     s = step / sqrt(*vmax2), 0 where *vmax2 is not > 0, `step` itself where vmax2 is NULL;   w_a = s v_a(x) (0 where v is NULL);
+ *     p_a = x_a + w_a;  c_a as above, then clamped into 0 .. n_a - 1 (a coordinate that is not a number: 0) -- there is never an outside;
+ *     out_a(x) = w_a + gain_a t_a,  t_a = the order-1 tap sum of channel a of u_src at c.
+ *   Composition phi <- phi o (id + w) is A = identity, gain = 1 on one grid; carrying a field to another pyramid level is v = NULL with A
+ *   the level-to-level voxel matrix and gain the ratio of the voxel sizes.  The scale is read on the device: an iteration needs no host
+ *   synchronisation.  out must not alias u_src or v.  Asynchronous.
+ * met2_warp_max_norm2.  *vmax2 = max over the n_voxels voxels of (v_x v_x + v_y v_y) + v_z v_z (0 for a zero field; a norm that is not a
+ *   number is passed over): per block, then one integer atomic max on the bit pattern, which orders as the non-negative values do.  Asynchronous.
+ * met2_warp_lncc.  The metric force from fixed F, warped W and inside m (uint8), all [nx][ny][nz], a radius r in 1 .. MET2_WARP_MAX_RADIUS
+ *   and eps >= 0:
+ *     channels  c0 = m (1 or 0), c1 = F where m else 0, c2 = W where m else 0, c3 = c1 c1, c4 = c2 c2, c5 = c1 c2;
+ *     box sums  over the (2 r + 1)^3 window clipped to the volume, separable, along x, then y, then z; every output is the direct sum of its
+ *               <= 2 r + 1 terms in ascending order (no running sum): n, sF, sW, sFF, sWW, sFW;
+ *     A = sFW - (sF sW) / n,  B = sFF - (sF sF) / n,  C = sWW - (sW sW) / n;
+ *     a voxel is VALID when m and n >= 2 and B > eps and C > eps;   cc = (A A) / (B C);
+ *     f = ((2 A) / (B C)) ((F - sF / n) - (A / C) (W - sW / n));
+ *     g_a = (W(x+) - W(x-)) / 2, x+ and x- the face neighbours along a where they are in the grid AND inside, the centre voxel otherwise
+ *       (a moving image with a background that is not zero would otherwise show a false edge at the rim of its field of view);
+ *     force_a = f g_a at a valid voxel, 0 elsewhere;   metric[0] = the sum of cc over the valid voxels, metric[1] = their number.
+ *   force [nx][ny][nz][3]; metric [2] at a device address of the caller's choice (a level's trace is read back once).  The sums of metric are
+ *   taken per thread in ascending voxel order, per block by a tree, over the blocks in a fixed order: the same bits from call to call.
+ *   Stage entries: met2_warp_lncc_sums (sums [6][nx][ny][nz], in the order above), met2_warp_lncc_force (from given sums).
+ *   Work space: `work` of at least work_bytes = met2_warp_work_bytes (host only; enough for every one of the three entries) on the device,
+ *   and the call is asynchronous; or NULL, and the entry allocates its own block and waits for the stream.
+ * Limits.  Every axis 1 .. MET2_RESAMPLE_MAX_AXIS, series as met2_resample (MET2_E_UNSUPPORTED beyond).  MET2_E_INVALID: an axis < 1, an
+ * order other than 0 or 1, bad strides (met2_resample's rule), a NULL required pointer, aliased outputs, an entry of A, gain or step that is
+ * not finite, a radius outside 1 .. 4, eps < 0 or not finite, a work block that is too small.  Every check comes before any device work:
+ * the outputs are then untouched. */
+#define MET2_WARP_MAX_RADIUS 4
+int met2_warp(int32_t device, int32_t order, const int32_t src_dims[3], int32_t n_series, const double *src, int64_t src_voxel_stride,
+              int64_t src_series_stride, const int32_t dst_dims[3], const double A[12], const double *disp, double cval, double *dst,
+              int64_t dst_voxel_stride, int64_t dst_series_stride, uint8_t *inside, void *stream);
+int met2_warp_labels(int32_t device, const int32_t src_dims[3], const int32_t *labels, const int32_t dst_dims[3], const double A[12],
+                     const double *disp, int32_t fill, int32_t *out, uint8_t *inside, void *stream);
+int met2_warp_compose(int32_t device, const int32_t src_dims[3], const double *u_src, const int32_t dst_dims[3], const double A[12],
+                      const double gain[3], const double *v, double step, const double *vmax2, double *out, void *stream);
+int met2_warp_max_norm2(int32_t device, int64_t n_voxels, const double *v, double *vmax2, void *stream);
+int met2_warp_work_bytes(const int32_t dims[3], int64_t *bytes);
+int met2_warp_lncc_sums(int32_t device, const int32_t dims[3], const double *fixed, const double *warped, const uint8_t *inside, int32_t radius,
+                        double *sums, void *work, int64_t work_bytes, void *stream);
+int met2_warp_lncc_force(int32_t device, const int32_t dims[3], const double *fixed, const double *warped, const uint8_t *inside,
+                         const double *sums, double eps, double *force, double *metric, void *work, int64_t work_bytes, void *stream);
+int met2_warp_lncc(int32_t device, const int32_t dims[3], const double *fixed, const double *warped, const uint8_t *inside, int32_t radius,
+                   double eps, double *force, double *metric, void *work, int64_t work_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,8 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
                             resample_filter / resample_labels_filter (affine resampling onto another grid) and atlas_stats_filter (label_stats_filter for an
                             atlas on a grid of its own, with template=... after registering the atlas' template to the maps): csrc/met2_resample.hip,
                             register_filter (rigid / affine registration of two volumes: register.py, csrc/met2_register.hip),
+                            warp_register_filter / warp_filter / warp_labels_filter (non-linear registration and resampling through a displacement
+                            field; atlas_stats_filter(nonlinear=...)): warp.py, csrc/met2_warp.hip,
                             gaussian_smooth
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
   gibbs.py                  gibbs_tables / gibbs_split / gibbs_split3d / gibbs_lines: the stages of the Gibbs-ringing filter one by one (tests and diagnostics)
@@ -32,6 +34,8 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   register.py               register: the coarse-to-fine direction-set search for the world matrix that brings a moving volume onto a fixed one, dof 6 / 7 / 9 / 12,
                             cost 'corratio' | 'normcorr' | 'leastsq' | 'mi' | 'nmi' (the last two from a joint histogram sized per level: level_bins); prepare / cost: a batch of candidate transforms scored in one launch (csrc/met2_register.hip);
                             params_to_world / world_to_params, pyramid, the intensity rule
+  warp.py                   register: greedy deformable registration with the squared local normalised cross-correlation, coarse to fine, after the world
+                            matrix of register.py; warp / warp_labels / compose / max_norm2 / lncc / lncc_sums / lncc_force: its stages one by one (csrc/met2_warp.hip)
   rician.py                 bias / step / invert: the kernels of the Rician noise-floor correction one by one (csrc/met2_rician.hip; Met2Plan.fit_rician and
                             noise_sigma, rician='iterative' | 'direct' of the drivers)
   mppca.py                  mppca_stages: the MP-PCA denoiser with what each of its steps leaves (tests and diagnostics)

@@ -49,7 +49,9 @@ SYMBOLS = ["met2_default_options", "met2_abi_version", "met2_device_count", "met
            "met2_rician_bias", "met2_rician_step", "met2_rician_invert", "met2_noise_sigma", "met2_fit_rician",
            "met2_resample", "met2_resample_work_bytes", "met2_resample_labels", "met2_resample_prefilter",
            "met2_register_limits", "met2_register_work_bytes", "met2_register_index", "met2_register_cost",
-           "met2_register_joint_work_bytes", "met2_register_joint_cost"]
+           "met2_register_joint_work_bytes", "met2_register_joint_cost",
+           "met2_warp", "met2_warp_labels", "met2_warp_compose", "met2_warp_max_norm2", "met2_warp_work_bytes", "met2_warp_lncc_sums",
+           "met2_warp_lncc_force", "met2_warp_lncc"]
 
 
 def lib():
@@ -169,6 +171,14 @@ def lib():
         L.met2_register_cost.argtypes = [C.c_int32, C.c_int32, i3, C.c_int32, vp, vp, _dp, i3, vp, _dp, C.c_int32, _dp, C.c_double, vp, C.c_int64, vp, vp, vp]
         L.met2_register_joint_work_bytes.argtypes = [i3, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
         L.met2_register_joint_cost.argtypes = [C.c_int32, C.c_int32, i3, C.c_int32, vp, i3, vp, _dp, C.c_int32, C.c_int32, _dp, C.c_double, vp, C.c_int64, vp, vp, vp, vp]
+        L.met2_warp.argtypes = [C.c_int32, C.c_int32, i3, C.c_int32, vp, C.c_int64, C.c_int64, i3, _dp, vp, C.c_double, vp, C.c_int64, C.c_int64, vp, vp]
+        L.met2_warp_labels.argtypes = [C.c_int32, i3, vp, i3, _dp, vp, C.c_int32, vp, vp, vp]
+        L.met2_warp_compose.argtypes = [C.c_int32, i3, vp, i3, _dp, _dp, vp, C.c_double, vp, vp, vp]
+        L.met2_warp_max_norm2.argtypes = [C.c_int32, C.c_int64, vp, vp, vp]
+        L.met2_warp_work_bytes.argtypes = [i3, C.POINTER(C.c_int64)]
+        L.met2_warp_lncc_sums.argtypes = [C.c_int32, i3, vp, vp, vp, C.c_int32, vp, vp, C.c_int64, vp]
+        L.met2_warp_lncc_force.argtypes = [C.c_int32, i3, vp, vp, vp, vp, C.c_double, vp, vp, vp, C.c_int64, vp]
+        L.met2_warp_lncc.argtypes = [C.c_int32, i3, vp, vp, vp, C.c_int32, C.c_double, vp, vp, vp, C.c_int64, vp]
         L.met2_synth_two_lobe.argtypes = [vp, C.POINTER(SynthParams), C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp]
         L.met2_eval_voxel_metrics.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
         L.met2_eval_reduce.argtypes = [C.c_int64, vp, vp, vp, vp, vp, vp]

@@ -68,17 +68,25 @@ __device__ __forceinline__ void rs_axis(double c, int n, int stride, int *o, dou
     }
 }
 
+// -> whether the source coordinates (cx, cy, cz) are inside; then T holds their taps (met2_warp.hip comes in here, with the coordinates of a
+// displaced voxel)
+template <int ORDER>
+__device__ __forceinline__ bool rs_taps_at(const RsGeom &G, double cx, double cy, double cz, RsTaps<ORDER> &T)
+{
+    if (!(rs_inside(cx, G.nx) && rs_inside(cy, G.ny) && rs_inside(cz, G.nz))) return false;
+    rs_axis<ORDER>(cx, G.nx, G.ny * G.nz, T.ox, T.wx);
+    rs_axis<ORDER>(cy, G.ny, G.nz, T.oy, T.wy);
+    rs_axis<ORDER>(cz, G.nz, 1, T.oz, T.wz);
+    return true;
+}
+
 // -> whether destination voxel (i, j, k) is inside; then T holds its taps
 template <int ORDER>
 __device__ __forceinline__ bool rs_taps(const RsGeom &G, int i, int j, int k, RsTaps<ORDER> &T)
 {
     const double di = (double)i, dj = (double)j, dk = (double)k;
     const double cx = rs_coord(G.A, di, dj, dk), cy = rs_coord(G.A + 4, di, dj, dk), cz = rs_coord(G.A + 8, di, dj, dk);
-    if (!(rs_inside(cx, G.nx) && rs_inside(cy, G.ny) && rs_inside(cz, G.nz))) return false;
-    rs_axis<ORDER>(cx, G.nx, G.ny * G.nz, T.ox, T.wx);
-    rs_axis<ORDER>(cy, G.ny, G.nz, T.oy, T.wy);
-    rs_axis<ORDER>(cz, G.nz, 1, T.oz, T.wz);
-    return true;
+    return rs_taps_at<ORDER>(G, cx, cy, cz, T);
 }
 
 // the value of one series at the taps: sum_p sum_q sum_r ((wx_p wy_q) wz_r) v, p outermost, from the first term on

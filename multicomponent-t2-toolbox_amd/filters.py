@@ -1,6 +1,6 @@
 """The whole-volume filters of the drivers, each one call into the C ABI (one translation unit under csrc/ per filter): nesma_filter,
 mppca_filter (with mppca_window and mppca_work_bytes), gibbs_filter, brain_mask_filter, bias_field_filter, tissue_segment_filter, partial_volume_filter, label_stats_filter,
-resample_filter, resample_labels_filter, register_filter, atlas_stats_filter and gaussian_smooth.  All take numpy arrays (and return numpy) or CUDA tensors (and return tensors on the same device); motor.py's drivers
+resample_filter, resample_labels_filter, register_filter, warp_register_filter, warp_filter, warp_labels_filter, atlas_stats_filter and gaussian_smooth.  All take numpy arrays (and return numpy) or CUDA tensors (and return tensors on the same device); motor.py's drivers
 call them and re-export the names."""
 import numpy as np
 import torch
@@ -318,8 +318,37 @@ def register_filter(fixed, fixed_affine, moving, moving_affine, **options):
     return register.register(fixed, fixed_affine, moving, moving_affine, **options)["world"]
 
 
+def warp_register_filter(fixed, fixed_affine, moving, moving_affine, world=None, **options):
+    """Non-linear (deformable) registration of `moving` onto `fixed` after the rigid or affine `world` of register_filter (None: the
+    identity): greedy registration with the squared local normalised cross-correlation, coarse to fine, its stages on the device (warp.register
+    states the loop and the options: radius, step, sigma_fluid, sigma_elastic, iters, scales_mm, device; met2_warp_lncc in include/met2_hip.h
+    the metric and its force).  The metric is that of ANTs' CC and of `greedy -m NCC`, the force their centre-voxel approximation of its
+    gradient; parity with ANTs, greedy or fnirt is unpinned: none was available.
+    -> dict(disp [nx, ny, nz, 3]: the displacement field on the grid of `fixed`, in its voxels -- what warp_filter and warp_labels_filter take
+    together with resample.voxel_matrix(fixed_affine, moving_affine, world) --, world, levels: per level its shape, iterations and metric trace)."""
+    from . import warp
+    return warp.register(fixed, fixed_affine, moving, moving_affine, world, **options)
+
+
+def warp_filter(vol, A, disp, order=1, cval=0.0, series_axis=-1, return_inside=False, device=0):
+    """resample_filter through a displacement field (met2_warp): the grid is that of `disp` [mx, my, mz, 3], whose voxel x samples `vol` at
+    A (x + disp(x)); order 0 or 1; `vol` 3-D or 4-D as in resample_filter.  -> the warped array in the layout of `vol`; return_inside=True:
+    (array, inside [mx, my, mz] uint8).  numpy in -> numpy out, CUDA tensor in -> tensors out."""
+    from . import warp
+    if series_axis not in (-1, 0, 3):
+        raise ValueError("series_axis must be -1 ([nx,ny,nz,S]) or 0 ([S,nx,ny,nz])")
+    return warp.warp(vol, A, disp, order=order, cval=cval, layout="series" if series_axis == 0 else "voxel", device=device, return_inside=return_inside)
+
+
+def warp_labels_filter(labels, A, disp, fill=0, device=0):
+    """resample_labels_filter through a displacement field (met2_warp_labels): nearest neighbour, `fill` where a voxel falls outside the
+    label image.  -> int32 on the grid of `disp`.  numpy in -> numpy out, CUDA tensor in -> tensor out."""
+    from . import warp
+    return warp.warp_labels(labels, A, disp, fill=fill, device=device)
+
+
 def atlas_stats_filter(res, labels, labels_affine, affine, world=None, q=None, device=0, template=None, template_affine=None, register=None,
-                       reference=None):
+                       reference=None, nonlinear=None, disp=None):
     """label_stats_filter for a label image that does not lie on the grid of the maps: `labels` [lx,ly,lz] integers with the voxel-to-world
     affine `labels_affine`, `affine` the maps' own (both as nifti.load gives them), `world` [4, 4] taking the maps' world mm to the label
     image's (None: both share scanner space; resample.from_flirt reads a FLIRT matrix).  The labels are resampled onto the maps' grid
@@ -327,24 +356,54 @@ def atlas_stats_filter(res, labels, labels_affine, affine, world=None, q=None, d
     template [tx,ty,tz]: an intensity image in the label image's world space (template_affine; None: labels_affine), the atlas' anatomical
     image.  `world` is then estimated: the template is registered (register_filter, options `register`: a dict, e.g. {"cost": "nmi"}) to `reference`, a volume on the
     maps' grid (None: res['TWC']).  A template together with a world matrix is refused.
-    -> the dict of label_stats_filter plus labels_resampled [nx,ny,nz] int32, and, with a template, world [4, 4]."""
+    nonlinear (with a template): True, or a dict of warp_register_filter's options -- after the affine registration the template is registered
+    non-linearly to the reference from that `world`, and the labels go through the displacement field (warp_labels_filter).  disp
+    [nx,ny,nz,3]: a field estimated before, on the maps' grid, applied after `world` (not together with nonlinear).
+    -> the dict of label_stats_filter plus labels_resampled [nx,ny,nz] int32, with a template world [4, 4], and with nonlinear disp and
+    warp_levels (the levels of warp_register_filter)."""
     from . import resample
     if template is None and (template_affine is not None or register is not None or reference is not None):
         raise ValueError("template_affine, register and reference go with a template")
+    if nonlinear is not None and not (nonlinear is True or isinstance(nonlinear, dict)):
+        raise ValueError("nonlinear must be None, True or a dict of warp_register_filter's options")
+    if nonlinear is not None and template is None:
+        raise ValueError("nonlinear goes with a template: the field is estimated from the template")
+    if nonlinear is not None and disp is not None:
+        raise ValueError("give nonlinear or a field estimated before, not both")
     if template is not None:
         if world is not None:
             raise ValueError("give a template or a world matrix, not both")
         ref = res["TWC"] if reference is None else reference
         ref = ref.cpu().numpy() if torch.is_tensor(ref) else np.asarray(ref)
         tpl = template.cpu().numpy() if torch.is_tensor(template) else np.asarray(template)
-        world = register_filter(ref, affine, tpl, labels_affine if template_affine is None else template_affine, **dict(register or {}, device=device))
+        tpl_affine = labels_affine if template_affine is None else template_affine
+        world = register_filter(ref, affine, tpl, tpl_affine, **dict(register or {}, device=device))
+        if nonlinear is not None:
+            nl = warp_register_filter(ref, affine, tpl, tpl_affine, world, **dict({"device": device}, **(nonlinear if isinstance(nonlinear, dict) else {})))
+            disp = nl["disp"]
     A = resample.voxel_matrix(affine, labels_affine, world)
-    lab = resample_labels_filter(labels, A, tuple(np.shape(res["MWF"])), fill=0, device=device)
+    shape = tuple(np.shape(res["MWF"]))
+    if disp is None:
+        lab = resample_labels_filter(labels, A, shape, fill=0, device=device)
+    else:
+        if tuple(np.shape(disp)) != shape + (3,):
+            raise ValueError("disp must be [nx,ny,nz,3] on the grid of the maps")
+        lab = warp_labels_filter(labels, A, disp, fill=0, device=device)
     out = label_stats_filter(res, lab, q=q, device=device)
     out["labels_resampled"] = lab.cpu().numpy() if torch.is_tensor(lab) else lab
     if template is not None:
         out["world"] = world
+    if nonlinear is not None:
+        out["disp"], out["warp_levels"] = disp, nl["levels"]
     return out
+
+
+def gaussian_weights(sigma, truncate=4.0):
+    """(radius, weights [2 radius + 1]) of scipy.ndimage.gaussian_filter1d: what met2_smooth_separable takes"""
+    radius = int(truncate * float(sigma) + 0.5)
+    x = np.arange(-radius, radius + 1)
+    w = np.exp(-0.5 / (float(sigma) * float(sigma)) * x ** 2)
+    return radius, np.ascontiguousarray(w / w.sum(), dtype=np.float64)
 
 
 def gaussian_smooth(data, sigma=2.0, truncate=4.0, device=0):
@@ -354,10 +413,7 @@ def gaussian_smooth(data, sigma=2.0, truncate=4.0, device=0):
     dd, dev, as_numpy = _enter(data, device)
     if dd.dim() != 4:
         raise ValueError("data must be [nx,ny,nz,nt]")
-    radius = int(truncate * float(sigma) + 0.5)                      # scipy.ndimage.gaussian_filter1d
-    x = np.arange(-radius, radius + 1)
-    w = np.exp(-0.5 / (float(sigma) * float(sigma)) * x ** 2)
-    w = np.ascontiguousarray(w / w.sum(), dtype=np.float64)
+    radius, w = gaussian_weights(sigma, truncate)
     out = torch.empty_like(dd)
     work = torch.empty_like(dd)
     _call(dev, "met2_smooth_separable", *dd.shape, radius, w.ctypes.data_as(_dp), dd.data_ptr(), out.data_ptr(), work.data_ptr())

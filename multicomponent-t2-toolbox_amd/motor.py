@@ -14,7 +14,8 @@ from ._lib import check, lib
 from .evaluate import study_t2_grid
 from .filters import (STAT_KEYS, STAT_QUANTITIES, atlas_stats_filter, bias_field_filter, brain_mask_filter, gaussian_smooth,  # noqa: F401
                       gibbs_filter, label_stats_filter, mppca_filter, nesma_filter, partial_volume_filter, register_filter,
-                      resample_filter, resample_labels_filter, tissue_segment_filter)
+                      resample_filter, resample_labels_filter, tissue_segment_filter, warp_filter, warp_labels_filter,
+                      warp_register_filter)
 from .plan import BOOT_QUANTITIES, BOOT_STATS, MAP_NAMES, Met2Plan
 
 
@@ -862,7 +863,7 @@ def roi_stats_tables(st, names=None):
     return np.array(rows, dtype=object), np.array(spectra, dtype=np.float64)
 
 
-def motor_atlas_stats(path_to_save_data, path_to_labels, path_to_world=None, names=None, path_to_template=None, register=None):
+def motor_atlas_stats(path_to_save_data, path_to_labels, path_to_world=None, names=None, path_to_template=None, register=None, nonlinear=None):
     """Per-ROI statistics of the maps motor_recon_met2 wrote at path_to_save_data (MWF ... reg_param and fsol_4D .nii.gz, found through
     _OUTPUT_FILES' naming), for an atlas or parcellation image that lies on a grid of its own: path_to_labels is its NIfTI, whose affine places it
     in world space; path_to_world an optional plain-text 4 x 4 matrix (np.loadtxt) taking the maps' world mm to the label image's (None: both
@@ -875,13 +876,21 @@ def motor_atlas_stats(path_to_save_data, path_to_labels, path_to_world=None, nam
     Data_avg.nii.gz at path_to_save_data or, where that is absent, TWC.nii.gz.  template_to_maps_world.txt holds the matrix (np.savetxt; what
     path_to_world reads), template_to_maps_flirt.mat its FLIRT form (resample.to_flirt: `flirt -in <template> -ref <reference> -applyxfm
     -init` takes it), template_resampled.nii.gz the template on the maps' grid, trilinear, for a look.
-    -> the dict of atlas_stats_filter with 'all' added (and 'world' with a template)."""
+    nonlinear (with path_to_template; None: nothing below happens and every file is what it was): True, or a dict of warp_register_filter's
+    options.  After the affine registration the template is registered non-linearly to the reference from that matrix, and the labels go
+    through the displacement field (warp_labels_filter).  template_to_maps_warp.nii.gz holds the field (4-D [x, y, z, 3], in voxels of the
+    maps' grid, applied after the world matrix), template_warped.nii.gz the template through matrix and field, trilinear.
+    -> the dict of atlas_stats_filter with 'all' added (and 'world' with a template; 'disp' and 'warp_levels' with nonlinear)."""
     import os
     from . import nifti, resample
     if path_to_template is not None and path_to_world is not None:
         raise ValueError("give path_to_template or path_to_world, not both")
     if path_to_template is None and register is not None:
         raise ValueError("register goes with path_to_template")
+    if nonlinear is not None and not (nonlinear is True or isinstance(nonlinear, dict)):
+        raise ValueError("nonlinear must be None, True or a dict of warp_register_filter's options")
+    if nonlinear is not None and path_to_template is None:
+        raise ValueError("nonlinear goes with path_to_template: the field is estimated from the template")
     stems = {key: stem for key, stem, _, _, _ in _OUTPUT_FILES}
     res, affine = {}, None
     for key in STAT_QUANTITIES + ("fsol_4D",):
@@ -912,9 +921,17 @@ def motor_atlas_stats(path_to_save_data, path_to_labels, path_to_world=None, nam
         np.savetxt(path_to_save_data + "template_to_maps_flirt.mat", resample.to_flirt(world, tpl.affine, template.shape, affine, ref.shape))
         on_maps = resample_filter(template, resample.voxel_matrix(affine, tpl.affine, world), ref.shape, order=1)
         nifti.save(nifti.NiftiImage(on_maps, affine), path_to_save_data + "template_resampled.nii.gz")
-    st = atlas_stats_filter(res, labels.astype(np.int64), lab_img.affine, affine, world=world)
+    nl = None
+    if nonlinear is not None:
+        nl = warp_register_filter(ref, affine, template, tpl.affine, world, **(nonlinear if isinstance(nonlinear, dict) else {}))
+        nifti.save(nifti.NiftiImage(nl["disp"], affine), path_to_save_data + "template_to_maps_warp.nii.gz")
+        warped = warp_filter(template, resample.voxel_matrix(affine, tpl.affine, world), nl["disp"], order=1)
+        nifti.save(nifti.NiftiImage(warped, affine), path_to_save_data + "template_warped.nii.gz")
+    st = atlas_stats_filter(res, labels.astype(np.int64), lab_img.affine, affine, world=world, **({} if nl is None else {"disp": nl["disp"]}))
     if path_to_template is not None:
         st["world"] = world
+    if nl is not None:
+        st["disp"], st["warp_levels"] = nl["disp"], nl["levels"]
     lab = st["labels_resampled"]
     al = label_stats_filter(res, (lab > 0).astype(np.int32), q=st["q"])
     st["all"] = {k: al[k][0] for k in STAT_KEYS}

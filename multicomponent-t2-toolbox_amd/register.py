@@ -21,7 +21,7 @@ has a handful of samples per cell; with 64 x 64 cells there it has far more cell
 runs off (tests/test_register_mi_host.py keeps that case).  The moving image's bin is the library's: floor((y - lo) B / (hi - lo)) of the
 interpolated value, clamped to 0 .. B - 1, with (lo, hi) the range of the scaled moving image.
 
-Out of scope: Parzen-window or partial-volume histograms, a histogram that is not square in register, a mask or a weighting of the moving image, non-linear warps, motion correction from echo to echo.  Parity
+Out of scope: Parzen-window or partial-volume histograms, a histogram that is not square in register, a mask or a weighting of the moving image, motion correction from echo to echo (non-linear warps: warp.py, which starts from this module's matrix).  Parity
 with FSL's flirt is unpinned: FSL was not available; the measures are the published ones (Roche et al., MICCAI 1998; Jenkinson & Smith,
 Med. Image Anal. 5:143-156, 2001; Jenkinson et al., NeuroImage 17:825-841, 2002)."""
 import ctypes as C
