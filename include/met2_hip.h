@@ -1320,6 +1320,45 @@ int met2_warp_lncc_force(int32_t device, const int32_t dims[3], const double *fi
 int met2_warp_lncc(int32_t device, const int32_t dims[3], const double *fixed, const double *warped, const uint8_t *inside, int32_t radius,
                    double eps, double *force, double *metric, void *work, int64_t work_bytes, void *stream);
 
+/* The inverse of a displacement field by fixed-point iteration, and the Jacobian determinant of a field (an extension; additive, ABI stays
+ * 6).  With T(x) = A (x + u(x)) of met2_warp (u on the fixed grid, A: fixed voxel -> moving voxel, L its 3 x 3 part) the inverse is wanted
+ * in the same form, so that met2_warp and met2_warp_labels apply it unchanged: v on the MOVING grid in its voxels, B = A^-1, moving voxel y
+ * samples the fixed grid at B (y + v(y)).  That gives v(y) = -L u(B (y + v(y))), a fixed-point equation (Chen et al., Med. Phys. 35:81-88,
+ * 2008) iterated as v_0 = 0, v_{k+1}(y) = -L u_tri(clamp(B (y + v_k(y)))).  It contracts where the Lipschitz constant of L u B is below 1
+ * and nowhere else: the step returns the largest change, and met2_warp_jacobian counts the voxels at which u folds, for the user to judge.
+ * The loop is warp.py's (a fixed number of steps, no host synchronisation inside).  Parity with ANTs, greedy or invwarp is unpinned: none
+ * was available.  No plan, no work space: `device` and `stream` only.  All arithmetic is fp64, no product is fused into a sum, every
+ * operation rounds once in the order written; there are no floating-point atomics.  DEVICE pointers except the dims, B, N and scale.
+ * met2_warp_invert_step.  One step, general enough to be held against met2_warp_compose: u_src [nx][ny][nz][3] on its own grid, the
+ *   destination grid [mx][my][mz], B[12] (destination voxel -> u_src's voxel), N[9] (row-major 3 x 3), v_in [mx][my][mz][3] or NULL,
+ *   v_out [mx][my][mz][3], inside [mx][my][mz] uint8 or NULL, res2 (one double on the device) or NULL.  Per destination voxel y:
+ *     p_a = y_a + v_in_a(y) (one rounding per axis; y_a where v_in is NULL, the bits v_in = 0 gives);
+ *     c_a = ((B[a][3] + B[a][0] p_x) + B[a][1] p_y) + B[a][2] p_z                                   -- met2_warp's coordinates;
+ *     inside(y) = met2_resample's inside test on c: 0 <= c_a <= n_a - 1 on every axis;
+ *     c_a is then clamped into 0 .. n_a - 1 as met2_warp_compose clamps it (a coordinate that is not a number: 0);
+ *     t_a = the order-1 tap sum of channel a of u_src at c (met2_resample's taps, weights and order of summation);
+ *     v_out_a(y) = (N[a][0] t_x + N[a][1] t_y) + N[a][2] t_z;
+ *     d_a = v_out_a - v_in_a (v_out_a - 0 where v_in is NULL);   *res2 = max over y of (d_x d_x + d_y d_y) + d_z d_z
+ *   (0 where every voxel's is 0; a value that is not a number is passed over): per thread, per block by a tree, then one integer atomic max
+ *   per block on the bit pattern, which orders as the non-negative values do (a block whose maximum does not exceed what *res2 holds by
+ *   then leaves it out: the value only grows during the call).  The entry zeroes *res2 on the stream first.
+ *   An inverse step is N = -L, B = A^-1, both formed by the caller on the host.  v_out must not alias u_src or v_in.  Asynchronous.
+ * met2_warp_jacobian.  u [nx][ny][nz][3], scale, det [nx][ny][nz], n_nonpositive (one int64 on the device) or NULL:
+ *     J_ab = delta_ab + D_b u_a;   D_b f = (f(x + e_b) - f(x - e_b)) / 2 where both neighbours are in the grid, f(x + e_b) - f(x) at the lower
+ *     rim, f(x) - f(x - e_b) at the upper rim (an axis of length 2 has rims only), 0 on an axis of length 1;   J_aa = 1 + D_a u_a;
+ *     m_0 = J_11 J_22 - J_12 J_21,  m_1 = J_10 J_22 - J_12 J_20,  m_2 = J_10 J_21 - J_11 J_20    (two products, then their difference);
+ *     det(x) = scale ((J_00 m_0 - J_01 m_1) + J_02 m_2)                                          -- the expansion along the first row;
+ *     *n_nonpositive = the number of voxels whose det is not > 0 (one that is not a number counts): per thread, per block by a tree of
+ *     integers, then one integer atomic add per block.  The entry zeroes it on the stream first.
+ *   With scale = 1 this is the local volume change of x -> x + u(x) in voxels; scale = det L makes it that of T.  det must not alias u.
+ *   Asynchronous.
+ * Limits.  Every axis 1 .. MET2_RESAMPLE_MAX_AXIS (MET2_E_UNSUPPORTED beyond).  MET2_E_INVALID: an axis < 1, a NULL required pointer,
+ * aliased outputs, an entry of B or N, or a scale, that is not finite.  Every check comes before any device work: the outputs are then
+ * untouched. */
+int met2_warp_invert_step(int32_t device, const int32_t src_dims[3], const double *u_src, const int32_t dst_dims[3], const double B[12],
+                          const double N[9], const double *v_in, double *v_out, uint8_t *inside, double *res2, void *stream);
+int met2_warp_jacobian(int32_t device, const int32_t dims[3], const double *u, double scale, double *det, int64_t *n_nonpositive, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

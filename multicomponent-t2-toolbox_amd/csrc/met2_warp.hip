@@ -1,6 +1,7 @@
 // met2_warp.hip -- met2_warp, met2_warp_labels, met2_warp_compose, met2_warp_max_norm2, met2_warp_lncc (and its stage entries
-// met2_warp_lncc_sums, met2_warp_lncc_force, met2_warp_work_bytes): resampling through a displacement field and the device stages of a greedy
-// deformable registration with the squared local normalised cross-correlation (include/met2_hip.h states the contract; warp.py holds the loop).
+// met2_warp_lncc_sums, met2_warp_lncc_force, met2_warp_work_bytes), met2_warp_invert_step, met2_warp_jacobian: resampling through a
+// displacement field, the device stages of a greedy deformable registration with the squared local normalised cross-correlation, and the
+// step of a field's fixed-point inverse with its Jacobian determinant (include/met2_hip.h states the contract; warp.py holds the loops).
 // Written from that statement and from Avants et al. (Med. Image Anal. 12:26-41, 2008), whose centre-voxel force this is.
 //   wp_voxel_kernel<ORDER, V>  met2_resample's rs_voxel_kernel with a field: one destination voxel per thread, threads along the destination's
 //                              z; p = x + u(x) (one rounding per axis), then rs_coord, the inside test and the taps of resample_taps.hpp
@@ -9,6 +10,14 @@
 //                              channels of the source field through one set of order-1 taps
 //   wp_max_norm2_kernel        max |v|^2: per thread, per block (a tree in LDS), then ONE integer atomic max per block on the bit pattern of the
 //                              non-negative double -- a max does not depend on the order, and no floating-point atomic is used
+//   wp_invert_step_kernel      wp_compose_kernel's shape for one step of the fixed-point inverse: p = y + v_in(y), the coordinates before the clamp
+//                              give `inside`, the three channels of the source field through one set of order-1 taps, a 3 x 3 product, and the
+//                              largest squared change fused in (wp_max_norm2_kernel's tree and integer atomic max): a pass of its own would
+//                              read both fields again.  Chen et al., Med. Phys. 35:81-88, 2008 is the iteration; warp.py holds the loop
+//   wp_jacobian_kernel         one voxel per thread, threads along z: the six face neighbours' three channels straight from memory (the z
+//                              neighbours are the wave's own lines, the x and y neighbours whole coalesced lines that L2 keeps between the
+//                              blocks that share them; no LDS tile), the determinant along the first row, and the count of voxels whose
+//                              determinant is not > 0 by a tree of integers and ONE integer atomic add per block
 //   wp_box_line_kernel<R, FIRST>  the box sums along x or y, the volume seen as [outer][n][inner], lanes along `inner` (which ends in z, the
 //                              contiguous axis): a thread owns WP_SEG consecutive outputs of one line and slides a window of 2 R + 1 values
 //                              through registers, so it reads every input of its segment once (and 2 R of its neighbours'), coalesced over
@@ -43,6 +52,7 @@ namespace {
 #define WP_SEG 16                          // wp_box_line_kernel: outputs of a line per thread
 #define WP_Z_TILE 256                      // wp_box_z_kernel: elements of a tile (= the block)
 #define WP_FORCE_GRID 1024                 // wp_force_kernel: blocks at the most; their shares are added by wp_metric_kernel
+#define WP_INVERSE_GRID 2048               // wp_invert_step_kernel, wp_jacobian_kernel: blocks at the most, one atomic each
 
 template <int ORDER, typename V>
 __global__ void __launch_bounds__(RS_BLOCK) wp_voxel_kernel(RsGeom G, int n_series, const V *__restrict__ src, int64_t svs, int64_t sss,
@@ -121,6 +131,108 @@ __global__ void __launch_bounds__(RS_BLOCK) wp_max_norm2_kernel(int64_t n, const
         __syncthreads();
     }
     if (threadIdx.x == 0) atomicMax(out, (unsigned long long)__double_as_longlong(sh[0]));   // >= 0: the bit patterns order as the values do
+}
+
+struct WpMat3 { double n[9]; };
+
+// (N[a][0] x + N[a][1] y) + N[a][2] z
+__device__ __forceinline__ double wp_row3(const double *row, double x, double y, double z)
+{
+    return rn_add(rn_add(rn_mul(row[0], x), rn_mul(row[1], y)), rn_mul(row[2], z));
+}
+
+__global__ void __launch_bounds__(RS_BLOCK) wp_invert_step_kernel(RsGeom G, WpMat3 N, const double *__restrict__ u_src, const double *__restrict__ v_in,
+                                                                  double *__restrict__ v_out, uint8_t *__restrict__ inside, unsigned long long *__restrict__ res2)
+{
+    __shared__ double sh[RS_BLOCK];
+    const int64_t n_dst = (int64_t)G.mx * G.my * G.mz;
+    double mx = 0.0;
+    for (int64_t w = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x; w < n_dst; w += (int64_t)gridDim.x * RS_BLOCK) {
+        int i, j, k;
+        rs_split(w, G, i, j, k);
+        double ax = 0.0, ay = 0.0, az = 0.0;
+        if (v_in) {
+            ax = v_in[3 * w];
+            ay = v_in[3 * w + 1];
+            az = v_in[3 * w + 2];
+        }
+        const double px = rn_add((double)i, ax), py = rn_add((double)j, ay), pz = rn_add((double)k, az);
+        const double rx = rs_coord(G.A, px, py, pz), ry = rs_coord(G.A + 4, px, py, pz), rz = rs_coord(G.A + 8, px, py, pz);
+        if (inside) inside[w] = rs_inside(rx, G.nx) && rs_inside(ry, G.ny) && rs_inside(rz, G.nz) ? 1 : 0;
+        RsTaps<1> T;
+        (void)rs_taps_at<1>(G, wp_clamp(rx, G.nx), wp_clamp(ry, G.ny), wp_clamp(rz, G.nz), T);     // always inside after the clamp
+        const double tx = rs_value<1, double>(T, u_src, 3), ty = rs_value<1, double>(T, u_src + 1, 3), tz = rs_value<1, double>(T, u_src + 2, 3);
+        const double ox = wp_row3(N.n, tx, ty, tz), oy = wp_row3(N.n + 3, tx, ty, tz), oz = wp_row3(N.n + 6, tx, ty, tz);
+        v_out[3 * w] = ox;
+        v_out[3 * w + 1] = oy;
+        v_out[3 * w + 2] = oz;
+        const double dx = rn_sub(ox, ax), dy = rn_sub(oy, ay), dz = rn_sub(oz, az);
+        const double q = rn_add(rn_add(rn_mul(dx, dx), rn_mul(dy, dy)), rn_mul(dz, dz));
+        if (q > mx) mx = q;                                        // a change that is not a number is passed over
+    }
+    if (!res2) return;                                             // the same for every thread of the launch
+    sh[threadIdx.x] = mx;
+    __syncthreads();
+    for (int s = RS_BLOCK / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s && sh[threadIdx.x + s] > sh[threadIdx.x]) sh[threadIdx.x] = sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        // *res2 only grows during the launch, so a block whose maximum does not exceed what it reads there (0 is what the entry wrote) has
+        // nothing to add: the atomics on the one address, which the memory side takes one after the other, fall from one per block to a few
+        const unsigned long long m = (unsigned long long)__double_as_longlong(sh[0]);                      // >= 0: the bit patterns order as the values do
+        if (m > __hip_atomic_load(res2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(res2, m);
+    }
+}
+
+// D_b of the three channels at voxel e, which has the index `at` of `n` along an axis of `stride` voxels: the neighbours are taken at
+// lo = max(at - 1, 0) and hi = min(at + 1, n - 1), so the difference is the central one where hi - lo = 2 and the one-sided one at a rim
+__device__ __forceinline__ void wp_diff3(const double *__restrict__ u, int64_t e, int at, int n, int64_t stride, double *d)
+{
+    const int lo = at > 0 ? -1 : 0, hi = at < n - 1 ? 1 : 0;
+    if (hi == lo) {                                                // an axis of length 1
+        d[0] = d[1] = d[2] = 0.0;
+        return;
+    }
+    const double *a = u + 3 * (e + hi * stride), *b = u + 3 * (e + lo * stride);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double df = rn_sub(a[c], b[c]);
+        d[c] = hi - lo == 2 ? df / 2.0 : df;
+    }
+}
+
+__global__ void __launch_bounds__(RS_BLOCK) wp_jacobian_kernel(int nx, int ny, int nz, const double *__restrict__ u, double scale, double *__restrict__ det,
+                                                               unsigned long long *__restrict__ n_nonpositive)
+{
+    __shared__ int sh[RS_BLOCK];
+    const int64_t nvox = (int64_t)nx * ny * nz;
+    int cnt = 0;                                                   // a thread sees at most 2^31 / 256 voxels
+    for (int64_t e = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x; e < nvox; e += (int64_t)gridDim.x * RS_BLOCK) {
+        const int z = (int)(e % nz);
+        const int64_t rest = e / nz;
+        const int y = (int)(rest % ny), x = (int)(rest / ny);
+        double dx[3], dy[3], dz[3];                                // d?[a] = D_? u_a
+        wp_diff3(u, e, x, nx, (int64_t)ny * nz, dx);
+        wp_diff3(u, e, y, ny, nz, dy);
+        wp_diff3(u, e, z, nz, 1, dz);
+        const double j00 = rn_add(1.0, dx[0]), j01 = dy[0], j02 = dz[0];
+        const double j10 = dx[1], j11 = rn_add(1.0, dy[1]), j12 = dz[1];
+        const double j20 = dx[2], j21 = dy[2], j22 = rn_add(1.0, dz[2]);
+        const double m0 = rn_sub(rn_mul(j11, j22), rn_mul(j12, j21)), m1 = rn_sub(rn_mul(j10, j22), rn_mul(j12, j20)),
+                     m2 = rn_sub(rn_mul(j10, j21), rn_mul(j11, j20));
+        const double d = rn_mul(scale, rn_add(rn_sub(rn_mul(j00, m0), rn_mul(j01, m1)), rn_mul(j02, m2)));
+        det[e] = d;
+        if (!(d > 0.0)) ++cnt;
+    }
+    if (!n_nonpositive) return;                                    // the same for every thread of the launch
+    sh[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int s = RS_BLOCK / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && sh[0] > 0) atomicAdd(n_nonpositive, (unsigned long long)sh[0]);
 }
 
 // window <- window shifted by one, `x` coming in at the far end
@@ -485,6 +597,45 @@ extern "C" int met2_warp_max_norm2(int32_t device, int64_t n_voxels, const doubl
     HIPCHK(hipMemsetAsync(vmax2, 0, sizeof(double), st));
     hipLaunchKernelGGL(wp_max_norm2_kernel, dim3(std::min(rs_grid(n_voxels, RS_BLOCK), WP_FORCE_GRID)), dim3(RS_BLOCK), 0, st, n_voxels, v,
                        (unsigned long long *)vmax2);
+    HIPCHK(hipGetLastError());
+    return MET2_OK;
+}
+
+extern "C" int met2_warp_invert_step(int32_t device, const int32_t src_dims[3], const double *u_src, const int32_t dst_dims[3], const double B[12],
+                                     const double N[9], const double *v_in, double *v_out, uint8_t *inside, double *res2, void *stream)
+{
+    int rc;
+    if ((rc = wp_check_dims(src_dims, "source")) || (rc = wp_check_dims(dst_dims, "destination")) || (rc = rs_check_transform(B))) return rc;
+    if (!N || !u_src || !v_out) return fail(MET2_E_INVALID, "NULL argument");
+    for (int e = 0; e < 9; ++e)
+        if (!std::isfinite(N[e])) return fail(MET2_E_INVALID, "every entry of N must be finite");
+    if (v_out == u_src || v_out == v_in) return fail(MET2_E_INVALID, "v_out must not alias u_src or v_in");
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    const RsGeom G = rs_geom(src_dims, dst_dims, B);
+    WpMat3 M;
+    for (int e = 0; e < 9; ++e) M.n[e] = N[e];
+    if (res2) HIPCHK(hipMemsetAsync(res2, 0, sizeof(double), st));
+    const int64_t n_dst = (int64_t)G.mx * G.my * G.mz;
+    hipLaunchKernelGGL(wp_invert_step_kernel, dim3(std::min(rs_grid(n_dst, RS_BLOCK), WP_INVERSE_GRID)), dim3(RS_BLOCK), 0, st, G, M, u_src, v_in, v_out,
+                       inside, (unsigned long long *)res2);
+    HIPCHK(hipGetLastError());
+    return MET2_OK;
+}
+
+extern "C" int met2_warp_jacobian(int32_t device, const int32_t dims[3], const double *u, double scale, double *det, int64_t *n_nonpositive, void *stream)
+{
+    int rc = wp_check_dims(dims, "volume");
+    if (rc) return rc;
+    if (!u || !det) return fail(MET2_E_INVALID, "NULL argument");
+    if (!std::isfinite(scale)) return fail(MET2_E_INVALID, "scale must be finite");
+    if ((const void *)det == (const void *)u) return fail(MET2_E_INVALID, "det must not alias u");
+    USE_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_nonpositive) HIPCHK(hipMemsetAsync(n_nonpositive, 0, sizeof(int64_t), st));
+    const int64_t nvox = (int64_t)dims[0] * dims[1] * dims[2];
+    hipLaunchKernelGGL(wp_jacobian_kernel, dim3(std::min(rs_grid(nvox, RS_BLOCK), WP_INVERSE_GRID)), dim3(RS_BLOCK), 0, st, dims[0], dims[1], dims[2], u, scale,
+                       det, (unsigned long long *)n_nonpositive);
     HIPCHK(hipGetLastError());
     return MET2_OK;
 }

@@ -347,6 +347,61 @@ def warp_labels_filter(labels, A, disp, fill=0, device=0):
     return warp.warp_labels(labels, A, disp, fill=fill, device=device)
 
 
+def warp_invert_filter(disp, A, shape, n_iter=20, device=0):
+    """The inverse of the transform (A, disp) of warp_filter -- voxel x of the grid of `disp` samples at A (x + disp(x)) -- in the same form, on
+    the other grid: `shape` is that of the image A leads to.  Fixed-point iteration (Chen et al., Med. Phys. 35:81-88, 2008; warp.invert holds
+    the loop, met2_warp_invert_step in include/met2_hip.h the step), `n_iter` steps, no convergence test: it converges only where the field
+    is a contraction, so judge `residual` and warp_jacobian_filter's count.  Parity with antsApplyTransforms -i or invwarp is unpinned: none
+    was available.
+    -> dict(disp [shape + (3,)] in voxels of that grid, B [3, 4] = A^-1 -- what warp_filter and warp_labels_filter take to bring an image on
+    the grid of the original field onto `shape` --, inside [shape] uint8: 1 where the last step sampled the original field within its grid,
+    residual [n_iter]: the largest change of every step in voxels)."""
+    from . import warp
+    return warp.invert(disp, A, shape, n_iter=n_iter, device=device)
+
+
+def warp_jacobian_filter(disp, scale=1.0, device=0):
+    """The Jacobian determinant of x -> x + disp(x) on the grid of `disp` [nx, ny, nz, 3], times `scale` (met2_warp_jacobian: central
+    differences, one-sided at the rim), and the number of voxels at which it is not > 0: there the field folds and has no inverse.
+    -> (det [nx, ny, nz], n_nonpositive).  numpy in -> (numpy, int), CUDA tensor in -> tensors."""
+    from . import warp
+    return warp.jacobian(disp, scale=scale, device=device)
+
+
+def maps_to_template_filter(res, affine, template_shape, template_affine, world=None, disp=None, order=1, n_iter=20, device=0):
+    """The STAT_QUANTITIES maps of a result dict of recon_met2_arrays onto the grid of a template: the direction opposite to
+    atlas_stats_filter, for voxel-wise comparison across subjects.  `affine` is the maps' voxel-to-world affine, template_shape and
+    template_affine the template's grid, `world` [4, 4] the matrix of atlas_stats_filter (the maps' world mm -> the template's; None: both
+    share scanner space), disp [nx, ny, nz, 3] the field of warp_register_filter on the maps' grid (applied after `world`).  With
+    A = resample.voxel_matrix(affine, template_affine, world) and B = A^-1: without a field the maps go through resample_filter with B alone;
+    with one its inverse is taken (warp_invert_filter, n_iter steps) and they go through warp_filter with (B, inverse field), order 0 or 1.
+    Voxels of the template that fall outside the maps get 0.
+    -> dict(the maps by name on the template grid, inside [template_shape] uint8, inverse_disp [template_shape + (3,)] (None without a
+    field), residual [n_iter] (empty without a field), jacobian [nx, ny, nz] on the maps' grid: det(I + grad disp), the local volume change
+    of the field alone in voxels (None without a field), n_nonpositive: the number of its voxels that are not > 0)."""
+    from . import resample, warp
+    shape = resample._dims(template_shape, "template", disp is not None)     # a field lives on grids of at most 512 voxels per axis
+    A = resample.voxel_matrix(affine, template_affine, world)
+    B = np.ascontiguousarray(resample.invert(A)[:3])
+    maps_shape = tuple(np.shape(res[STAT_QUANTITIES[0]]))
+    stack = np.stack([np.asarray(res[k].cpu() if torch.is_tensor(res[k]) else res[k], dtype=np.float64) for k in STAT_QUANTITIES])
+    out = {"inverse_disp": None, "residual": np.zeros(0), "jacobian": None, "n_nonpositive": 0}
+    if disp is None:
+        on_tpl, inside = resample_filter(stack, B, shape, order=order, cval=0.0, device=device, return_inside=True, series_axis=0)
+    else:
+        if tuple(np.shape(disp)) != maps_shape + (3,):
+            raise ValueError("disp must be [nx,ny,nz,3] on the grid of the maps")
+        if isinstance(order, bool) or order not in (0, 1):
+            raise ValueError("order must be 0 (nearest) or 1 (trilinear) through a field")
+        disp = np.asarray(disp.cpu() if torch.is_tensor(disp) else disp, dtype=np.float64)
+        inv = warp.invert(disp, A, shape, n_iter=n_iter, device=device)
+        on_tpl, inside = warp_filter(stack, B, inv["disp"], order=order, cval=0.0, series_axis=0, return_inside=True, device=device)
+        det, count = warp.jacobian(disp, 1.0, device=device)
+        out.update(inverse_disp=inv["disp"], residual=inv["residual"], jacobian=det, n_nonpositive=count)
+    out.update({k: on_tpl[i] for i, k in enumerate(STAT_QUANTITIES)}, inside=inside)
+    return out
+
+
 def atlas_stats_filter(res, labels, labels_affine, affine, world=None, q=None, device=0, template=None, template_affine=None, register=None,
                        reference=None, nonlinear=None, disp=None):
     """label_stats_filter for a label image that does not lie on the grid of the maps: `labels` [lx,ly,lz] integers with the voxel-to-world

@@ -1,6 +1,6 @@
 """Drop-ins for motor/motor_recon_met2_real_data.py: create_Laplacian_matrix, fitting_slice_T2, recon_met2_arrays (the driver's steps 1-4
 on in-memory arrays), motor_recon_met2 (the same with the on-disk contract), the ROI mode (recon_met2_rois, motor_recon_met2_ROIs) and the
-atlas statistics of written maps (motor_atlas_stats).
+atlas statistics of written maps (motor_atlas_stats) and the written maps on a template's grid (motor_maps_to_template).
 The whole-volume filters the drivers call (nesma_filter ... gaussian_smooth) are filters.py's, re-exported here; the drivers reach them
 through this module's names.  Plots and the mean-spectrum PNG are not reproduced."""
 import collections
@@ -13,9 +13,9 @@ from ._cache import plan_for
 from ._lib import check, lib
 from .evaluate import study_t2_grid
 from .filters import (STAT_KEYS, STAT_QUANTITIES, atlas_stats_filter, bias_field_filter, brain_mask_filter, gaussian_smooth,  # noqa: F401
-                      gibbs_filter, label_stats_filter, mppca_filter, nesma_filter, partial_volume_filter, register_filter,
-                      resample_filter, resample_labels_filter, tissue_segment_filter, warp_filter, warp_labels_filter,
-                      warp_register_filter)
+                      gibbs_filter, label_stats_filter, maps_to_template_filter, mppca_filter, nesma_filter, partial_volume_filter,
+                      register_filter, resample_filter, resample_labels_filter, tissue_segment_filter, warp_filter, warp_invert_filter,
+                      warp_jacobian_filter, warp_labels_filter, warp_register_filter)
 from .plan import BOOT_QUANTITIES, BOOT_STATS, MAP_NAMES, Met2Plan
 
 
@@ -940,6 +940,80 @@ def motor_atlas_stats(path_to_save_data, path_to_labels, path_to_world=None, nam
     np.savetxt(path_to_save_data + "table_roi_stats.csv", table, delimiter=",", fmt="%s")
     np.savetxt(path_to_save_data + "table_roi_spectra.csv", spectra, delimiter=",", fmt="%s")
     return st
+
+
+def motor_maps_to_template(path_to_save_data, path_to_template, path_to_world=None, path_to_warp=None, register=None, nonlinear=None, order=1,
+                           n_iter=20):
+    """The maps motor_recon_met2 wrote at path_to_save_data (MWF ... reg_param .nii.gz, found as motor_atlas_stats finds them) brought INTO
+    template space, the direction opposite to motor_atlas_stats: for voxel-wise comparison and averaging across subjects.  path_to_template
+    is the template's NIfTI.  The world matrix (the maps' world mm -> the template's) comes from path_to_world -- a plain-text 4 x 4 matrix,
+    e.g. the template_to_maps_world.txt motor_atlas_stats wrote -- or is estimated as motor_atlas_stats estimates it: the template is
+    registered (register_filter; `register`: a dict of its options) to Data_avg.nii.gz or, where that is absent, TWC.nii.gz.  The field
+    comes from path_to_warp (4-D [x, y, z, 3] on the maps' grid, e.g. template_to_maps_warp.nii.gz), or is estimated after the registration
+    (nonlinear: True or a dict of warp_register_filter's options), or there is none.  path_to_warp together with nonlinear is refused, and so
+    are register or nonlinear together with path_to_world.  The field is inverted by `n_iter` fixed-point steps (warp_invert_filter: it
+    converges only where the field is a contraction; the report holds what to judge it by) and the maps go through its inverse
+    (maps_to_template_filter; order 0 or 1 with a field), 0 outside.  Runs on device 0.
+    Written with the template's affine: <map>_in_template.nii.gz per map, maps_to_template_inside.nii.gz and, with a field,
+    maps_to_template_warp.nii.gz (the inverse field, 4-D [x, y, z, 3], in voxels of the template's grid, applied after the inverse of the
+    world matrix); with the maps' affine template_to_maps_jacobian.nii.gz (with a field); maps_to_template_report.txt: the residual per
+    step, the number and share of voxels whose Jacobian determinant is not positive, and its smallest and largest value.
+    -> the dict of maps_to_template_filter, with 'world' and 'disp' (the field on the maps' grid that was inverted; None without one)."""
+    import os
+    from . import nifti
+    if path_to_world is not None and (register is not None or nonlinear is not None):
+        raise ValueError("register and nonlinear estimate the world matrix: give them or path_to_world, not both")
+    if path_to_warp is not None and nonlinear is not None:
+        raise ValueError("give path_to_warp or nonlinear, not both")
+    if nonlinear is not None and not (nonlinear is True or isinstance(nonlinear, dict)):
+        raise ValueError("nonlinear must be None, True or a dict of warp_register_filter's options")
+    stems = {key: stem for key, stem, _, _, _ in _OUTPUT_FILES}
+    res, affine = {}, None
+    for key in STAT_QUANTITIES:
+        img = nifti.load(path_to_save_data + stems[key] + ".nii.gz")
+        res[key] = img.get_fdata()
+        affine = img.affine if affine is None else affine
+    shape = res[STAT_QUANTITIES[0]].shape
+    if len(shape) != 3 or any(res[k].shape != shape for k in STAT_QUANTITIES):
+        raise ValueError("the maps at path_to_save_data do not share one grid")
+    tpl = nifti.load(path_to_template)
+    template = tpl.get_fdata()
+    if template.ndim != 3:
+        raise ValueError("the template must be a 3-D volume")
+    disp = None
+    if path_to_warp is not None:
+        disp = nifti.load(path_to_warp).get_fdata()
+        if disp.shape != shape + (3,):
+            raise ValueError("the field at path_to_warp must be [x, y, z, 3] on the grid of the maps")
+    if path_to_world is not None:
+        world = np.loadtxt(path_to_world, dtype=np.float64)
+        if world.shape != (4, 4):
+            raise ValueError("path_to_world must hold a 4 x 4 matrix")
+    else:
+        ref_path = path_to_save_data + "Data_avg.nii.gz"
+        ref = nifti.load(ref_path if os.path.exists(ref_path) else path_to_save_data + stems["TWC"] + ".nii.gz").get_fdata()
+        if ref.shape != shape:
+            raise ValueError("the reference volume does not lie on the grid of the maps")
+        world = register_filter(ref, affine, template, tpl.affine, **dict(register or {}))
+        if nonlinear is not None:
+            disp = warp_register_filter(ref, affine, template, tpl.affine, world, **(nonlinear if isinstance(nonlinear, dict) else {}))["disp"]
+    out = maps_to_template_filter(res, affine, template.shape, tpl.affine, world=world, disp=disp, order=order, n_iter=n_iter)
+    out["world"], out["disp"] = world, disp
+    for key in STAT_QUANTITIES:
+        nifti.save(nifti.NiftiImage(out[key], tpl.affine), path_to_save_data + stems[key] + "_in_template.nii.gz")
+    nifti.save(nifti.NiftiImage(out["inside"], tpl.affine), path_to_save_data + "maps_to_template_inside.nii.gz")
+    lines = ["maps to template: %s" % ("the inverse of the world matrix alone, no field" if disp is None else "%d fixed-point steps" % len(out["residual"]))]
+    if disp is not None:
+        nifti.save(nifti.NiftiImage(out["inverse_disp"], tpl.affine), path_to_save_data + "maps_to_template_warp.nii.gz")
+        nifti.save(nifti.NiftiImage(out["jacobian"], affine), path_to_save_data + "template_to_maps_jacobian.nii.gz")
+        lines += ["step %d: residual %.6e voxels" % (k + 1, r) for k, r in enumerate(out["residual"])]
+        n_vox = int(np.prod(shape))
+        lines += ["Jacobian determinant of the field on the maps' grid: %d of %d voxels not positive (%.4f %%)"
+                  % (out["n_nonpositive"], n_vox, 100.0 * out["n_nonpositive"] / n_vox),
+                  "Jacobian determinant: min %.6e, max %.6e" % (np.nanmin(out["jacobian"]), np.nanmax(out["jacobian"]))]
+    with open(path_to_save_data + "maps_to_template_report.txt", "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return out
 
 
 def recon_met2_rois(data, rois, fa_index, Dic_3D, T2s, Laplac, factor=1.01, myelin_T2=40.0, device=0, plan=None):

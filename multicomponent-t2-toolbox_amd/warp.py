@@ -1,12 +1,14 @@
 """Non-linear (deformable) registration and resampling through a displacement field (met2_warp, met2_warp_labels, met2_warp_compose,
-met2_warp_max_norm2, met2_warp_lncc in include/met2_hip.h, which states the rules; csrc/met2_warp.hip).  The five stages run on the device;
-the loop around them is here.
+met2_warp_max_norm2, met2_warp_lncc in include/met2_hip.h, which states the rules; csrc/met2_warp.hip), the inverse of a field and its
+Jacobian determinant (met2_warp_invert_step, met2_warp_jacobian).  The stages run on the device; the loops around them are here.
 
 A displacement field `disp` is fp64 [mx, my, mz, 3] on the fixed (destination) grid, in voxels of that grid: with A of resample.voxel_matrix
 (fixed voxel -> moving voxel), fixed voxel x samples the moving image at A (x + disp(x)).
 
   warp, warp_labels, compose, max_norm2, lncc, lncc_sums, lncc_force, work_bytes   the stage wrappers (numpy in, numpy out; tensors in, tensors out)
   register                                                                      greedy registration, coarse to fine
+  invert_step, jacobian                                                         one step of the inverse; the determinant and the count of folded voxels
+  invert                                                                        the inverse field by fixed-point iteration
 
 register.  Greedy registration with the squared local normalised cross-correlation (the metric of ANTs' CC and of `greedy -m NCC`): per
 iteration the moving image is warped (order 1), the metric force is taken (met2_warp_lncc: ANTs' centre-voxel approximation of the gradient,
@@ -15,7 +17,14 @@ not the sum over all windows that hold a voxel), smoothed (sigma_fluid, the flui
 iteration counts are fixed: with a constant normalised step the metric is not monotone near the end, so the trace is returned for the user
 to judge.  Inside a level nothing is copied from the device to the host.
 
-Out of scope: symmetric (SyN) updates and inverse fields, mutual-information forces, the exact LNCC gradient, masks or weights, order 3,
+invert.  With T(x) = A (x + u(x)) the inverse is returned in the same form, v on the moving grid with B = A^-1 (moving voxel y samples the
+fixed grid at B (y + v(y))), so warp and warp_labels apply it unchanged.  v solves v(y) = -L u(B (y + v(y))), L the 3 x 3 part of A, iterated
+from v = 0 (Chen et al., Med. Phys. 35:81-88, 2008).  The iteration converges only where L u B is a contraction (a Lipschitz constant below
+1): greedy LNCC registration with a fixed step does not promise that, so the largest change of every step is returned as `residual`, and
+jacobian counts the voxels at which the field folds, for the user to judge.  The number of steps is fixed and nothing is copied to the host
+inside the loop.  Beyond the rim of the fixed grid u is taken at the nearest voxel (the clamp of compose); `inside` tells where that happened.
+
+Out of scope: symmetric (SyN) updates, mutual-information forces, the exact LNCC gradient, masks or weights, order 3,
 convergence-based stopping.  Parity with ANTs, greedy or fnirt is unpinned: none was available."""
 import ctypes as C
 
@@ -224,6 +233,118 @@ def lncc(fixed, warped, inside, radius, eps=EPS, device=0, work=None, metric=Non
         check(lib().met2_warp_lncc(dev.index or 0, resample._i3(dims), f.data_ptr(), w.data_ptr(), m.data_ptr(), radius, eps, force.data_ptr(),
                                    metric.data_ptr(), wk.data_ptr(), wk.numel() * 8, resample._stream(dev)))
     return resample._leave((force, metric), as_numpy)
+
+
+# ---------------------------------------------------------------- the inverse of a field and the Jacobian determinant
+
+def _matrix33(N, what="N"):
+    n = np.ascontiguousarray(np.asarray(N, dtype=np.float64))
+    if n.shape != (3, 3) or not np.isfinite(n).all():
+        raise ValueError("%s must be a finite 3 x 3 matrix" % what)
+    return n
+
+
+def _scalar_out(t, what):
+    import torch
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.numel() == 1 and t.is_contiguous()):
+        raise ValueError("%s must be a one-element float64 device tensor" % what)
+    return t
+
+
+def _step_into(dev, src_dims, u, dst_dims, b, n, v_in, v_out, inside, res2):
+    """met2_warp_invert_step on tensors that are already on `dev`, contiguous and of the right type"""
+    import torch
+    with torch.cuda.device(dev):
+        check(lib().met2_warp_invert_step(dev.index or 0, resample._i3(src_dims), u.data_ptr(), resample._i3(dst_dims), b.ctypes.data_as(_dp),
+                                          n.ctypes.data_as(_dp), None if v_in is None else v_in.data_ptr(), v_out.data_ptr(),
+                                          None if inside is None else inside.data_ptr(), None if res2 is None else res2.data_ptr(), resample._stream(dev)))
+
+
+def invert_step(u, B, N, shape, v_in=None, return_inside=False, return_res2=False, res2=None, device=0):
+    """met2_warp_invert_step: v_out(y) = N u(clamp(B (y + v_in(y)))) on the grid `shape` (v_in None: zeros), `inside` from the coordinates
+    before the clamp, res2 = max |v_out - v_in|^2.  u [nx, ny, nz, 3], B [3, 4], N [3, 3]; an inverse step is B = A^-1, N = -A[:, :3].  res2:
+    a one-element float64 device tensor to write into (a row of a loop's trace).
+    -> v_out [mx, my, mz, 3]; with return_inside and return_res2 a tuple (v_out, inside uint8, res2: a one-element device tensor for tensors,
+    a float for numpy)."""
+    import torch
+    src_dims = _field_dims(_shape(u), "u")
+    dst_dims = _grid(shape, "destination")
+    b, n = resample._matrix(B), _matrix33(N)
+    if v_in is not None and tuple(_shape(v_in)) != dst_dims + (3,):
+        raise ValueError("v_in must be [mx, my, mz, 3] on the destination grid")
+    if res2 is not None:
+        _scalar_out(res2, "res2")
+    t, dev, as_numpy = resample._enter(u, device, torch.float64)
+    vv = None if v_in is None else torch.as_tensor(v_in, device=dev).to(torch.float64).contiguous()
+    out = torch.empty(dst_dims + (3,), dtype=torch.float64, device=dev)
+    inside = torch.empty(dst_dims, dtype=torch.uint8, device=dev) if return_inside else None
+    r2 = res2 if res2 is not None else (torch.empty(1, dtype=torch.float64, device=dev) if return_res2 else None)
+    _step_into(dev, src_dims, t, dst_dims, b, n, vv, out, inside, r2)
+    res = (resample._leave(out, as_numpy),)
+    if return_inside:
+        res += (resample._leave(inside, as_numpy),)
+    if return_res2:
+        res += (float(r2.cpu()[0]) if as_numpy else r2,)
+    return res if len(res) > 1 else res[0]
+
+
+def jacobian(disp, scale=1.0, device=0):
+    """met2_warp_jacobian: det = scale * det(I + grad u) by central differences, one-sided at the rim, and the number of voxels at which it is
+    not > 0 (not-a-number included) -> (det [nx, ny, nz], n_nonpositive: an int for numpy, a one-element int64 device tensor for tensors)"""
+    import torch
+    dims = _field_dims(_shape(disp))
+    scale = float(scale)
+    if not np.isfinite(scale):
+        raise ValueError("scale must be finite")
+    t, dev, as_numpy = resample._enter(disp, device, torch.float64)
+    det = torch.empty(dims, dtype=torch.float64, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().met2_warp_jacobian(dev.index or 0, resample._i3(dims), t.data_ptr(), scale, det.data_ptr(), count.data_ptr(), resample._stream(dev)))
+    return (det.cpu().numpy(), int(count.cpu()[0])) if as_numpy else (det, count)
+
+
+def invert(disp, A, shape, n_iter=20, device=0, step=None):
+    """The inverse of T(x) = A (x + disp(x)) on the grid `shape` of the moving image, by `n_iter` steps of v <- -L disp(B (y + v)) from v = 0
+    (see the module's docstring; it converges only where the field is a contraction).  disp [nx, ny, nz, 3] numpy, A [3, 4] of
+    resample.voxel_matrix.  The loop ping-pongs between two device tensors, every step writes its res2 into a row of one device tensor, and
+    that tensor is read back once after the loop.  step: a numpy callable with invert_step's meaning -- step(u, B, N, shape, v_in=...,
+    return_inside=True, return_res2=True) -> (v_out, inside, res2) -- replaces the device stage: the loop then needs no device.
+    -> dict(disp [shape + (3,)] on the destination grid in its voxels, B [3, 4] = A^-1, inside [shape] uint8 from the last step (None with
+    n_iter = 0), residual [n_iter] in voxels: the largest change of every step)."""
+    src_dims = _field_dims(np.shape(disp))
+    dst_dims = _grid(shape, "destination")
+    a = resample._matrix(A)
+    if abs(np.linalg.det(a[:, :3])) == 0.0:
+        raise ValueError("A is singular")
+    if isinstance(n_iter, bool) or int(n_iter) != n_iter or int(n_iter) < 0:
+        raise ValueError("n_iter must be a count >= 0")
+    n_iter = int(n_iter)
+    B = np.ascontiguousarray(resample.invert(a)[:3])
+    N = np.ascontiguousarray(-a[:, :3])
+    if not (np.isfinite(B).all()):
+        raise ValueError("the inverse of A is not finite")
+    u = np.ascontiguousarray(disp, dtype=np.float64)
+    if step is not None:
+        if not callable(step):
+            raise ValueError("step must be a callable with invert_step's meaning")
+        v, inside, rows = None, None, []
+        for _ in range(n_iter):
+            v, inside, r2 = step(u, B, N, dst_dims, v_in=v, return_inside=True, return_res2=True)
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            rows.append(float(r2))
+        v = np.zeros(dst_dims + (3,)) if v is None else v
+        return {"disp": v, "B": B, "inside": None if inside is None else np.asarray(inside, dtype=np.uint8), "residual": np.sqrt(np.asarray(rows, dtype=np.float64))}
+    import torch
+    dev = torch.device("cuda", device)
+    ut = torch.as_tensor(u, device=dev)
+    bufs = [torch.zeros(dst_dims + (3,), dtype=torch.float64, device=dev), torch.empty(dst_dims + (3,), dtype=torch.float64, device=dev)]
+    inside = torch.empty(dst_dims, dtype=torch.uint8, device=dev) if n_iter else None
+    trace = torch.zeros(max(n_iter, 1), dtype=torch.float64, device=dev)
+    for k in range(n_iter):
+        _step_into(dev, src_dims, ut, dst_dims, B, N, None if k == 0 else bufs[k % 2], bufs[(k + 1) % 2], inside if k == n_iter - 1 else None, trace[k:k + 1])
+    return {"disp": bufs[n_iter % 2].cpu().numpy(), "B": B, "inside": None if inside is None else inside.cpu().numpy(),
+            "residual": np.sqrt(trace[:n_iter].cpu().numpy())}
 
 
 # ---------------------------------------------------------------- the loop
