@@ -1359,6 +1359,43 @@ int met2_warp_invert_step(int32_t device, const int32_t src_dims[3], const doubl
                           const double N[9], const double *v_in, double *v_out, uint8_t *inside, double *res2, void *stream);
 int met2_warp_jacobian(int32_t device, const int32_t dims[3], const double *u, double scale, double *det, int64_t *n_nonpositive, void *stream);
 
+/* Voxel-wise group statistics by permutation (an extension; additive, ABI stays 6).  One form covers one-sample sign flipping, the
+ * permutation of group labels and the Freedman-Lane scheme with nuisance regressors (Winkler et al., NeuroImage 92:381-397, 2014): the
+ * caller residualises the data against the nuisance once (Y, with s0 the residual sum of squares per voxel) and turns every candidate
+ * permutation into r + 1 weight rows over the n subjects (group.py: partition, weights, residualise); the statistic is then
+ * met2_group_perm_stats.  Y [n][n_vox] (series-major: one row per subject), s0 [n_vox], W [K][r + 1][n], two_sided 0 | 1, t_ref [n_vox] or
+ *   NULL, t_first [n_vox] or NULL, kmax [K], count [n_vox] uint32 (required with t_ref).  For voxel v and candidate k:
+ *     b   = sum_i W[k][0][i] Y[i][v]
+ *     g_j = sum_i W[k][j][i] Y[i][v]                 j = 1 .. r
+ *     q   = sum_j g_j g_j;   rss = s0[v] - q
+ *     t   = rss > 0 ? b / sqrt(rss) : 0              (two_sided: t = |t|)
+ *   Order.  All arithmetic is fp64; no product is fused into a sum; every operation rounds once.  A sum over i starts from 0.0 and takes
+ *   its terms one by one, i = 0, 1, .. n - 1: a <- a + W[k][j][i] Y[i][v].  q = g_1 g_1, then q <- q + g_j g_j for j = 2 .. r.  The
+ *   quotient and the square root are correctly rounded.  So the bits of t(k, v) depend on W[k], Y[:, v] and s0[v] alone -- not on K, not
+ *   on where the candidate stands in W, not on n_vox or the voxel's place, not on the device -- and numpy reproduces them in float64 with
+ *   the same loop (tests/tools/group_numpy.py).  That is what makes t >= t_obs exact for the identity permutation.
+ *   Outputs.  kmax[k] = max over v of t(k, v), as a double; the entry sets it itself (per wave by comparisons, per block through LDS,
+ *     then one integer atomic max per block and candidate on a key that orders as the doubles do, turned back into the double by a last
+ *     launch; +0 orders above -0; a t that is not a number is passed over; -infinity when n_vox = 0 or every t is not a number).  No
+ *     floating-point atomics, no scratch.
+ *     count[v] += the number of candidates k with t(k, v) >= t_ref[v]: accumulated over launches, so the caller zeroes it once; the voxel's
+ *     count is owned by one thread.  Skipped when t_ref is NULL.
+ *     t_first[v] = t(0, v) when t_first is not NULL.
+ *   DEVICE pointers throughout.  Asynchronous on `stream`.
+ * met2_group_limits (host only; any output may be NULL): MET2_GROUP_MAX_N, MET2_GROUP_MAX_R, MET2_GROUP_MAX_K and MET2_GROUP_VOXEL_TILE, the
+ *   number of consecutive voxels a block owns (what a test stands on the edges of).
+ * Limits.  r < n <= MET2_GROUP_MAX_N, 1 <= r <= MET2_GROUP_MAX_R, 1 <= K <= MET2_GROUP_MAX_K per launch (MET2_E_UNSUPPORTED beyond the upper
+ * ends).  MET2_E_INVALID: r or K < 1, n <= r, n_vox < 0, two_sided outside {0, 1}, W or kmax NULL, Y or s0 NULL with n_vox > 0, t_ref
+ * without count.  n_vox = 0 is valid (Y and s0 are then not read and may be NULL).  Every check comes before any device work: the outputs
+ * are then untouched. */
+#define MET2_GROUP_MAX_N 128
+#define MET2_GROUP_MAX_R 8
+#define MET2_GROUP_MAX_K 256
+#define MET2_GROUP_VOXEL_TILE 256
+int met2_group_limits(int32_t *max_n, int32_t *max_r, int32_t *max_k, int32_t *voxel_tile);
+int met2_group_perm_stats(int32_t device, int32_t n, int64_t n_vox, const double *Y, const double *s0, int32_t r, int32_t K, const double *W,
+                          int32_t two_sided, const double *t_ref, double *t_first, double *kmax, uint32_t *count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
                             dictionaries for 2-D multi-slice data (slice_profile=... of Met2Plan.build_dictionary_epg and the drivers)
   flip_angle_algorithms.py  compute_optimal_FA, fitting_slice_FA_brute_force
   motor.py                  create_Laplacian_matrix, fitting_slice_T2, the drivers: recon_met2_arrays (steps 1-4 on arrays; _resolve_run states what the options
-                            refuse and where they run), motor_recon_met2 (the on-disk contract), the ROI mode, motor_atlas_stats, motor_maps_to_template; re-exports the filters
+                            refuse and where they run), motor_recon_met2 (the on-disk contract), the ROI mode, motor_atlas_stats, motor_maps_to_template, motor_group_stats; re-exports the filters
   filters.py                the whole-volume filters, one C ABI call each: nesma_filter, mppca_filter (MP-PCA denoising, cubic or box window, optional overlapping-patch averaging: csrc/met2_mppca.hip),
                             gibbs_filter (Gibbs-ringing removal, degibbs='yes' and '3d': csrc/met2_gibbs.hip),
                             bias_field_filter (bias-field correction of the TWC map, bias_correct='yes': csrc/met2_bias.hip),
@@ -22,6 +22,7 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
                             warp_register_filter / warp_filter / warp_labels_filter (non-linear registration and resampling through a displacement
                             field; atlas_stats_filter(nonlinear=...)), warp_invert_filter / warp_jacobian_filter / maps_to_template_filter (the
                             inverse of a field by fixed-point iteration, its Jacobian determinant, the maps onto a template's grid): warp.py, csrc/met2_warp.hip,
+                            group_stats_filter (voxel-wise group statistics with permutation inference over subjects' maps on one grid: group.py, csrc/met2_group.hip),
                             gaussian_smooth
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
   gibbs.py                  gibbs_tables / gibbs_split / gibbs_split3d / gibbs_lines: the stages of the Gibbs-ringing filter one by one (tests and diagnostics)
@@ -38,6 +39,8 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
   warp.py                   register: greedy deformable registration with the squared local normalised cross-correlation, coarse to fine, after the world
                             matrix of register.py; warp / warp_labels / compose / max_norm2 / lncc / lncc_sums / lncc_force: its stages one by one (csrc/met2_warp.hip);
                             invert: the inverse field by fixed-point iteration, invert_step / jacobian: its step and the determinant with the count of folded voxels
+  group.py                  partition / residualise / permutation_set / weights: a design and a t-contrast as the weight rows of met2_group_perm_stats;
+                            perm_stats: the entry on arrays; randomise: the permutation test (uncorrected and FWE-corrected p-values) (csrc/met2_group.hip)
   rician.py                 bias / step / invert: the kernels of the Rician noise-floor correction one by one (csrc/met2_rician.hip; Met2Plan.fit_rician and
                             noise_sigma, rician='iterative' | 'direct' of the drivers)
   mppca.py                  mppca_stages: the MP-PCA denoiser with what each of its steps leaves (tests and diagnostics)

@@ -1,6 +1,6 @@
 """The whole-volume filters of the drivers, each one call into the C ABI (one translation unit under csrc/ per filter): nesma_filter,
 mppca_filter (with mppca_window and mppca_work_bytes), gibbs_filter, brain_mask_filter, bias_field_filter, tissue_segment_filter, partial_volume_filter, label_stats_filter,
-resample_filter, resample_labels_filter, register_filter, warp_register_filter, warp_filter, warp_labels_filter, atlas_stats_filter and gaussian_smooth.  All take numpy arrays (and return numpy) or CUDA tensors (and return tensors on the same device); motor.py's drivers
+resample_filter, resample_labels_filter, register_filter, warp_register_filter, warp_filter, warp_labels_filter, atlas_stats_filter, group_stats_filter and gaussian_smooth.  All take numpy arrays (and return numpy) or CUDA tensors (and return tensors on the same device); motor.py's drivers
 call them and re-export the names."""
 import numpy as np
 import torch
@@ -400,6 +400,35 @@ def maps_to_template_filter(res, affine, template_shape, template_affine, world=
         out.update(inverse_disp=inv["disp"], residual=inv["residual"], jacobian=det, n_nonpositive=count)
     out.update({k: on_tpl[i] for i, k in enumerate(STAT_QUANTITIES)}, inside=inside)
     return out
+
+
+GROUP_VOLUMES = ("tstat", "cope", "p_uncorrected", "p_fwe")
+
+
+def group_stats_filter(volumes, X, c, mask=None, **options):
+    """The permutation test of the t-contrast c in the design X [n, p] at every voxel of n subjects' volumes [n, x, y, z] on one grid (the
+    <map>_in_template volumes of maps_to_template_filter): group.randomise on the voxels of `mask` (None: all), unfolded into volumes.
+    options: n_perm, seed, exchange ('permute' | 'flip'), two_sided, device, batch_stat -- group.randomise's.
+    -> its dict with tstat, cope, p_uncorrected, p_fwe and count as [x, y, z] volumes (outside the mask t = 0, cope = 0, p = 1, count =
+    n_perm) and mask [x, y, z] bool: the voxels that were tested.  Parity with FSL randomise is unpinned: FSL was not available."""
+    from . import group
+    vols = np.asarray(volumes.cpu() if torch.is_tensor(volumes) else volumes, dtype=np.float64)
+    if vols.ndim != 4:
+        raise ValueError("volumes must be [n, x, y, z]: one volume per subject")
+    shape = vols.shape[1:]
+    m = np.ones(shape, dtype=bool) if mask is None else np.asarray(mask.cpu() if torch.is_tensor(mask) else mask) != 0
+    if m.shape != shape:
+        raise ValueError("the mask does not lie on the grid of the volumes")
+    at = np.flatnonzero(m.reshape(-1))
+    res = group.randomise(np.ascontiguousarray(vols.reshape(vols.shape[0], -1)[:, at]), X, c, **options)
+    for key in GROUP_VOLUMES:
+        vol = np.full(int(np.prod(shape)), 0.0 if key in ("tstat", "cope") else 1.0)
+        vol[at] = res[key]
+        res[key] = vol.reshape(shape)
+    count = np.full(int(np.prod(shape)), res["n_perm"], dtype=np.uint32)
+    count[at] = res["count"]
+    res.update(count=count.reshape(shape), mask=m)
+    return res
 
 
 def atlas_stats_filter(res, labels, labels_affine, affine, world=None, q=None, device=0, template=None, template_affine=None, register=None,

@@ -1,0 +1,307 @@
+"""Voxel-wise group statistics with permutation inference (csrc/met2_group.hip; include/met2_hip.h states the entry's contract).
+
+A general linear model Y = X beta + e over n subjects, a t-contrast c, and the permutation distribution of the t statistic at every voxel:
+uncorrected p-values from the voxel's own distribution, family-wise-error-corrected ones from the distribution of the maximum over the voxels
+(Winkler et al., NeuroImage 92:381-397, 2014).  One form covers one-sample sign flipping, the permutation of group labels and the
+Freedman-Lane scheme with nuisance regressors:
+
+  partition(X, c)        the effect of interest x1 and the nuisance Z with x1' Z = 0 (Beckmann's form), so that the coefficient of x1 in
+                         [x1 Z] is c' beta
+  residualise(Y, X, c)   Yr = R_z Y with R_z = I - Z Z+, and s0 = sum_i Yr^2 per voxel
+  permutation_set(...)   signed permutations P_k, row 0 the identity, unique by the x1 they produce, exhaustive where that is affordable
+  weights(X, c, perms)   W [P][r + 1][n]: row 0 = sqrt(dof) P_k' x1 / sqrt(x1' x1), rows 1 .. r = P_k' q_j for an orthonormal basis q_j of [x1 Z]
+
+Freedman-Lane fits the full model to y* = (P_k R_z + H_z) y.  H_z y lies in the model's column space and x1 is orthogonal to Z, so the
+coefficient of x1 is x1' P_k Yr / (x1' x1), the residual sum of squares is |P_k Yr|^2 - sum_j (q_j' P_k Yr)^2 = s0 - sum_j ((P_k' q_j)' Yr)^2
+(a signed permutation keeps the norm), and t = b / sqrt(rss) with b = (row 0)' Yr: the statistic of met2_group_perm_stats.  The V x P table of
+statistics is never formed: the entry keeps the maximum per candidate and the count per voxel.
+
+perm_stats is the entry on arrays; randomise batches the candidates through it (or through batch_stat, a numpy callable with the entry's
+meaning: the loop then needs no device).  Parity with FSL randomise is unpinned: FSL was not available.  Not provided: F-contrasts,
+exchangeability blocks, TFCE and cluster-extent statistics, variance smoothing, several devices."""
+import collections
+import ctypes as C
+import math
+
+import numpy as np
+
+from ._lib import check, lib
+
+PermSet = collections.namedtuple("PermSet", "index sign exhaustive exchange")   # (P_k y)_i = sign[k, i] y[index[k, i]]
+EXCHANGES = ("permute", "flip")
+TINY = 1e-24                       # a voxel whose s0 <= TINY sum_i Y^2 is explained by the nuisance alone: t = 0, p = 1
+
+
+def limits():
+    """met2_group_limits -> dict(max_n, max_r, max_k, voxel_tile); needs no device"""
+    v = [C.c_int32(-1) for _ in range(4)]
+    check(lib().met2_group_limits(*[C.byref(x) for x in v]))
+    return dict(zip(("max_n", "max_r", "max_k", "voxel_tile"), (x.value for x in v)))
+
+
+# ---------------------------------------------------------------- the design
+
+def _design(X, c):
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 1:
+        X = X[:, None]
+    c = np.asarray(c, dtype=np.float64).reshape(-1, 1)
+    if X.ndim != 2 or c.shape[0] != X.shape[1] or not (np.isfinite(X).all() and np.isfinite(c).all()):
+        raise ValueError("X must be a finite [n, p] design and c a finite t-contrast of p entries")
+    if not c.any():
+        raise ValueError("the contrast is zero")
+    if X.shape[0] <= X.shape[1] or np.linalg.matrix_rank(X) < X.shape[1]:
+        raise ValueError("the design is rank deficient or leaves no degree of freedom: drop the redundant columns")
+    return X, c
+
+
+def partition(X, c):
+    """The partition of a design X [n, p] and a t-contrast c [p] into the effect of interest x1 [n, 1] and the nuisance Z [n, p - 1] with
+    x1' Z = 0 (Winkler et al. 2014, appendix; Beckmann's form).  With D = (X'X)^-1 and Cu an orthonormal basis of null(c'):
+    x1 = X D c (c'Dc)^-1, Cv = Cu - c (c'Dc)^-1 c' D Cu, Z = X D Cv (Cv'DCv)^-1.  A rank-deficient X is refused."""
+    X, c = _design(X, c)
+    p = X.shape[1]
+    D = np.linalg.inv(X.T @ X)
+    cdc = np.linalg.inv(c.T @ D @ c)
+    x1 = X @ D @ c @ cdc
+    if p == 1:
+        return x1, np.zeros((X.shape[0], 0))
+    Cu = np.linalg.svd(c, full_matrices=True)[0][:, 1:]            # the left singular vectors beyond the first span null(c')
+    Cv = Cu - c @ cdc @ c.T @ D @ Cu
+    Z = X @ D @ Cv @ np.linalg.inv(Cv.T @ D @ Cv)
+    return x1, Z
+
+
+def residualise(Y, X, c):
+    """Yr = R_z Y [n, V] with R_z = I - Z Z+ of partition(X, c), and s0 [V] = sum_i Yr^2: a sum of squared residuals, not a difference"""
+    Y = np.asarray(Y, dtype=np.float64)
+    _, Z = partition(X, c)
+    if Y.ndim != 2 or Y.shape[0] != Z.shape[0]:
+        raise ValueError("Y must be [n, V] with one row per subject")
+    Yr = Y - Z @ (np.linalg.pinv(Z) @ Y) if Z.shape[1] else Y.copy()
+    return np.ascontiguousarray(Yr), np.sum(Yr * Yr, axis=0)
+
+
+# ---------------------------------------------------------------- the permutations
+
+def _labels(x1):
+    """equal entries of x1 (to 1e-10 of its largest) get one label"""
+    x = np.asarray(x1, dtype=np.float64).ravel()
+    scale = np.abs(x).max()
+    return np.unique(np.round(x / (scale if scale > 0 else 1.0), 10), return_inverse=True)[1].ravel()
+
+
+def _arrangements(counts):
+    """every distinct sequence with counts[l] copies of label l, in lexicographic order"""
+    n = sum(counts)
+    left, seq = list(counts), []
+
+    def walk():
+        if len(seq) == n:
+            yield tuple(seq)
+            return
+        for lab in range(len(left)):
+            if left[lab]:
+                left[lab] -= 1
+                seq.append(lab)
+                yield from walk()
+                seq.pop()
+                left[lab] += 1
+    return walk()
+
+
+def _index_for(arrangement, labels):
+    """the permutation that carries the labels onto `arrangement`: P' x1 has the label arrangement[m] at m; sources and targets of one label
+    are matched in ascending order, so the labels' own arrangement gives the identity"""
+    arrangement = np.asarray(arrangement)
+    index = np.empty(labels.size, dtype=np.int64)
+    for lab in np.unique(labels):
+        index[np.flatnonzero(labels == lab)] = np.flatnonzero(arrangement == lab)
+    return index
+
+
+def permutation_set(X, c, n_perm, seed=0, exchange="permute"):
+    """At most n_perm signed permutations for the test of c in X -> PermSet(index [P, n], sign [P, n], exhaustive, exchange), with
+    (P_k y)_i = sign[k, i] y[index[k, i]].  Row 0 is the identity.  Rows are unique by the x1 they produce (P_k' x1), so swaps within a group
+    count once.  The set is exhaustive when the number of distinct arrangements -- n! / prod(group sizes!) for 'permute', 2^n for 'flip' (2^m
+    with m the entries of x1 that are not zero) -- is <= n_perm; otherwise it is drawn at random, deterministic in `seed`."""
+    if exchange not in EXCHANGES:
+        raise ValueError("exchange must be one of %s" % (EXCHANGES,))
+    if isinstance(n_perm, bool) or int(n_perm) != n_perm or int(n_perm) < 1:
+        raise ValueError("n_perm must be a count >= 1")
+    n_perm = int(n_perm)
+    x1, _ = partition(X, c)
+    n = x1.shape[0]
+    rng = np.random.default_rng(seed)
+    ident = np.arange(n, dtype=np.int64)
+    if exchange == "flip":
+        free = np.flatnonzero(x1.ravel() != 0.0)
+        total = 2 ** free.size
+        sign = np.ones((min(total, n_perm), n))
+        if total <= n_perm:
+            for k in range(total):                                 # row 0: no flip
+                sign[k, free] = 1.0 - 2.0 * ((k >> np.arange(free.size)) & 1)
+        else:
+            seen, k = {(0,) * free.size}, 1
+            while k < n_perm:
+                bits = rng.integers(0, 2, free.size)
+                key = tuple(int(b) for b in bits)
+                if key not in seen:
+                    seen.add(key)
+                    sign[k, free] = 1.0 - 2.0 * bits
+                    k += 1
+        return PermSet(np.tile(ident, (sign.shape[0], 1)), sign, total <= n_perm, exchange)
+    labels = _labels(x1)
+    counts = np.bincount(labels).tolist()
+    if len(counts) < 2:
+        raise ValueError("permuting the subjects cannot change the effect of interest (every entry of x1 is the same, as in a one-sample "
+                         "test): use exchange='flip'")
+    total = math.factorial(n)
+    for m in counts:
+        total //= math.factorial(m)
+    own = tuple(int(l) for l in labels)
+    if total <= n_perm:
+        rows = [ident] + [_index_for(a, labels) for a in _arrangements(counts) if a != own]
+    else:
+        rows, seen = [ident], {own}
+        while len(rows) < n_perm:
+            index = rng.permutation(n)
+            arrangement = np.empty(n, dtype=np.int64)
+            arrangement[index] = labels                            # (P' x1)[index[i]] = x1[i]
+            key = tuple(int(l) for l in arrangement)
+            if key not in seen:
+                seen.add(key)
+                rows.append(index.astype(np.int64))
+    index = np.stack(rows)
+    return PermSet(index, np.ones(index.shape), total <= n_perm, exchange)
+
+
+def _transposed(perms, x):
+    """P_k' x for every k: x [n, m] -> [P, m, n]; (P' x)[index[i]] = sign[i] x[i]"""
+    P, n = perms.index.shape
+    out = np.empty((P, x.shape[1], n))
+    rows = np.arange(P)[:, None]
+    for j in range(x.shape[1]):
+        out[rows, j, perms.index] = perms.sign * x[:, j][None, :]
+    return out
+
+
+def weights(X, c, perms):
+    """The weight rows of met2_group_perm_stats for the signed permutations `perms` -> (W [P, r + 1, n], dof) with r = rank(X), dof = n - r:
+    row 0 = sqrt(dof) P_k' x1 / sqrt(x1' x1), rows 1 .. r = P_k' q_j, q_j an orthonormal basis of [x1 Z] (see the module's docstring)."""
+    x1, Z = partition(X, c)
+    n = x1.shape[0]
+    M = np.hstack([x1, Z])
+    r = M.shape[1]
+    dof = n - r
+    if perms.index.shape[1] != n:
+        raise ValueError("the permutations are not of the design's %d subjects" % n)
+    Q = np.linalg.qr(M)[0]
+    first = math.sqrt(dof) * x1 / math.sqrt(float(np.sum(x1 * x1)))
+    return np.ascontiguousarray(_transposed(perms, np.hstack([first, Q]))), dof
+
+
+# ---------------------------------------------------------------- the entry on arrays
+
+def _launch(dev, Y, s0, r, W, two_sided, t_ref, t_first, kmax, count):
+    """met2_group_perm_stats on tensors that are already on `dev`, contiguous and of the right type (count: int32, the bits of uint32)"""
+    import torch
+    n, V = Y.shape
+    with torch.cuda.device(dev):
+        check(lib().met2_group_perm_stats(dev.index or 0, n, V, Y.data_ptr(), s0.data_ptr(), r, W.shape[0], W.data_ptr(), 1 if two_sided else 0,
+                                          None if t_ref is None else t_ref.data_ptr(), None if t_first is None else t_first.data_ptr(),
+                                          kmax.data_ptr(), None if count is None else count.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+
+
+def _check_batch(Y, s0, W, t_ref, count):
+    if len(Y.shape) != 2 or tuple(s0.shape) != (Y.shape[1],):
+        raise ValueError("Y must be [n, V] and s0 [V]")
+    if len(W.shape) != 3 or W.shape[2] != Y.shape[0] or W.shape[1] < 2 or W.shape[0] < 1:
+        raise ValueError("W must be [K, r + 1, n] with K >= 1 and r >= 1")
+    if t_ref is not None and tuple(t_ref.shape) != (Y.shape[1],):
+        raise ValueError("t_ref must be [V]")
+    if count is not None and tuple(count.shape) != (Y.shape[1],):
+        raise ValueError("count must be [V]")
+
+
+def perm_stats(Y, s0, W, two_sided=False, t_ref=None, count=None, want_first=False, device=0):
+    """met2_group_perm_stats on numpy arrays: Y [n, V], s0 [V], W [K, r + 1, n], t_ref [V] or None, count [V] uint32 to add to (zeros when None)
+    -> (kmax [K], count [V] uint32 or None without t_ref, t_first [V] or None without want_first)"""
+    import torch
+    dev = torch.device("cuda", device)
+    Y, s0, W = (np.ascontiguousarray(a, dtype=np.float64) for a in (Y, s0, W))
+    _check_batch(Y, s0, W, t_ref, count)
+    put = lambda a: torch.as_tensor(a, device=dev)
+    V = Y.shape[1]
+    kmax = torch.empty(W.shape[0], dtype=torch.float64, device=dev)
+    ref = None if t_ref is None else put(np.ascontiguousarray(t_ref, dtype=np.float64))
+    cnt = None
+    if ref is not None:
+        cnt = put(np.zeros(V, dtype=np.int32) if count is None else np.ascontiguousarray(count, dtype=np.uint32).view(np.int32))
+    first = torch.empty(V, dtype=torch.float64, device=dev) if want_first else None
+    _launch(dev, put(Y), put(s0), W.shape[1] - 1, put(W), two_sided, ref, first, kmax, cnt)
+    return (kmax.cpu().numpy(), None if cnt is None else cnt.cpu().numpy().view(np.uint32), None if first is None else first.cpu().numpy())
+
+
+# ---------------------------------------------------------------- the test
+
+def randomise(Y, X, c, n_perm=5000, seed=0, exchange="permute", two_sided=False, device=0, batch_stat=None):
+    """The permutation test of the t-contrast c in the design X [n, p] at every voxel of Y [n, V] (one row per subject).
+    batch_stat: None runs met2_group_perm_stats on `device`; a numpy callable with its meaning -- batch_stat(Y, s0, W, two_sided, t_ref,
+    want_first) -> (kmax [K], count increment [V] or None, t_first [V] or None) -- replaces it, and the loop then needs no device.
+    -> dict(tstat [V] (signed; two_sided tests |t|), cope [V] (c' beta), p_uncorrected [V] = count / P with count the permutations whose
+    statistic at the voxel reaches the observed one, p_fwe [V] = #{k: max_dist[k] >= tstat(v)} / P, count [V], max_dist [P] (the maximum over
+    the voxels per permutation), n_perm (the number actually used), exhaustive, dof, t_crit: np.quantile(max_dist, 0.95)).  Both p-values
+    count the identity, so neither is below 1 / P.  A voxel whose residualised data are all zero, or whose s0 <= 1e-24 sum_i Y^2 (the
+    nuisance explains it), is left out of the launch and gets t = 0, cope = 0, p = 1."""
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    if Y.ndim != 2:
+        raise ValueError("Y must be [n, V] with one row per subject")
+    if batch_stat is not None and not callable(batch_stat):
+        raise ValueError("batch_stat must be a callable with the entry's meaning")
+    x1, _ = partition(X, c)
+    perms = permutation_set(X, c, n_perm, seed, exchange)
+    W, dof = weights(X, c, perms)
+    P, r = W.shape[0], W.shape[1] - 1
+    lim = limits() if batch_stat is None else {"max_n": Y.shape[0], "max_r": r, "max_k": 256}
+    if Y.shape[0] > lim["max_n"] or r > lim["max_r"]:
+        raise ValueError("at most %d subjects and %d model columns" % (lim["max_n"], lim["max_r"]))
+    Yr, s0 = residualise(Y, X, c)
+    keep = np.flatnonzero((Yr != 0.0).any(axis=0) & (s0 > TINY * np.sum(Y * Y, axis=0)))
+    Yk, sk = np.ascontiguousarray(Yr[:, keep]), np.ascontiguousarray(s0[keep])
+    V, K = keep.size, lim["max_k"]
+    if batch_stat is not None:
+        _, _, t_obs = batch_stat(Yk, sk, W[:1], False, None, True)
+        t_obs = np.asarray(t_obs, dtype=np.float64)
+        ref = np.abs(t_obs) if two_sided else t_obs
+        count, max_dist = np.zeros(V, dtype=np.uint32), np.empty(P)
+        for k0 in range(0, P, K):
+            km, inc, _ = batch_stat(Yk, sk, W[k0:k0 + K], two_sided, ref, False)
+            max_dist[k0:k0 + K] = km
+            count += np.asarray(inc, dtype=np.uint32)
+        n_ge = P - np.searchsorted(np.sort(max_dist), ref, side="left")
+    else:
+        import torch
+        dev = torch.device("cuda", device)
+        put = lambda a: torch.as_tensor(a, device=dev)
+        Yt, st, Wt = put(Yk), put(sk), put(W)
+        t_dev = torch.empty(V, dtype=torch.float64, device=dev)
+        cnt = torch.zeros(V, dtype=torch.int32, device=dev)
+        md = torch.empty(P, dtype=torch.float64, device=dev)
+        _launch(dev, Yt, st, r, Wt[:1], False, None, t_dev, md[:1], None)
+        ref_t = t_dev.abs() if two_sided else t_dev
+        for k0 in range(0, P, K):
+            _launch(dev, Yt, st, r, Wt[k0:k0 + K], two_sided, ref_t, None, md[k0:k0 + K], cnt)
+        n_ge_t = P - torch.searchsorted(torch.sort(md)[0], ref_t.contiguous(), right=False)      # exact integers, on the device
+        t_obs, count, max_dist, n_ge = t_dev.cpu().numpy(), cnt.cpu().numpy().view(np.uint32), md.cpu().numpy(), n_ge_t.cpu().numpy()
+    full = Y.shape[1]
+    out = {"tstat": np.zeros(full), "cope": np.zeros(full), "p_uncorrected": np.ones(full), "p_fwe": np.ones(full),
+           "count": np.full(full, P, dtype=np.uint32)}
+    out["tstat"][keep] = t_obs
+    out["cope"][keep] = (x1.T @ Yk).ravel() / float(np.sum(x1 * x1))
+    out["count"][keep] = count
+    out["p_uncorrected"][keep] = count / float(P)
+    out["p_fwe"][keep] = n_ge / float(P)
+    out.update(max_dist=max_dist, n_perm=P, exhaustive=bool(perms.exhaustive), dof=dof,
+               t_crit=float(np.quantile(max_dist, 0.95)) if V else float("nan"))
+    return out

@@ -1,6 +1,7 @@
 """Drop-ins for motor/motor_recon_met2_real_data.py: create_Laplacian_matrix, fitting_slice_T2, recon_met2_arrays (the driver's steps 1-4
 on in-memory arrays), motor_recon_met2 (the same with the on-disk contract), the ROI mode (recon_met2_rois, motor_recon_met2_ROIs) and the
-atlas statistics of written maps (motor_atlas_stats) and the written maps on a template's grid (motor_maps_to_template).
+atlas statistics of written maps (motor_atlas_stats), the written maps on a template's grid (motor_maps_to_template) and the voxel-wise
+group statistics of several subjects' maps on that grid (motor_group_stats).
 The whole-volume filters the drivers call (nesma_filter ... gaussian_smooth) are filters.py's, re-exported here; the drivers reach them
 through this module's names.  Plots and the mean-spectrum PNG are not reproduced."""
 import collections
@@ -13,7 +14,7 @@ from ._cache import plan_for
 from ._lib import check, lib
 from .evaluate import study_t2_grid
 from .filters import (STAT_KEYS, STAT_QUANTITIES, atlas_stats_filter, bias_field_filter, brain_mask_filter, gaussian_smooth,  # noqa: F401
-                      gibbs_filter, label_stats_filter, maps_to_template_filter, mppca_filter, nesma_filter, partial_volume_filter,
+                      gibbs_filter, group_stats_filter, label_stats_filter, maps_to_template_filter, mppca_filter, nesma_filter, partial_volume_filter,
                       register_filter, resample_filter, resample_labels_filter, tissue_segment_filter, warp_filter, warp_invert_filter,
                       warp_jacobian_filter, warp_labels_filter, warp_register_filter)
 from .plan import BOOT_QUANTITIES, BOOT_STATS, MAP_NAMES, Met2Plan
@@ -1012,6 +1013,59 @@ def motor_maps_to_template(path_to_save_data, path_to_template, path_to_world=No
                   % (out["n_nonpositive"], n_vox, 100.0 * out["n_nonpositive"] / n_vox),
                   "Jacobian determinant: min %.6e, max %.6e" % (np.nanmin(out["jacobian"]), np.nanmax(out["jacobian"]))]
     with open(path_to_save_data + "maps_to_template_report.txt", "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return out
+
+
+def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_mask=None, **options):
+    """Voxel-wise group statistics of one map over several subjects, after motor_maps_to_template brought every subject's maps onto one
+    template grid.  paths_to_save_data: one path_to_save_data per subject, in the order of the rows of the design X [n, p]; `quantity`: one of
+    STAT_QUANTITIES; c: the t-contrast.  Every subject's <stem>_in_template.nii.gz is loaded; differing shapes or affines are refused.  The
+    test runs on the intersection of the subjects' maps_to_template_inside.nii.gz and, where given, the mask at path_to_mask (non-zero voxels,
+    on the same grid).  options: group_stats_filter's (n_perm, seed, exchange, two_sided, device, batch_stat).
+    Written at path_to_out with the template's affine: <quantity>_tstat.nii.gz, <quantity>_cope.nii.gz, <quantity>_p_unc.nii.gz and
+    <quantity>_p_fwe.nii.gz; <quantity>_max_dist.txt (the maximum statistic of every permutation, the identity first) and
+    <quantity>_group_report.txt: n, dof, the number of permutations, whether the set was exhaustive, t_crit (the 0.95 quantile of the maximum
+    statistic) and the number of voxels with p_fwe <= 0.05.  The p-value files hold p itself, NOT FSL randomise's 1 - p: small is significant,
+    and no value is below 1 / n_perm.  Parity with FSL randomise is unpinned.
+    -> the dict of group_stats_filter."""
+    from . import nifti
+    if quantity not in STAT_QUANTITIES:
+        raise ValueError("quantity must be one of %s" % (STAT_QUANTITIES,))
+    paths = list(paths_to_save_data)
+    if len(paths) != np.shape(X)[0]:
+        raise ValueError("the design has %d rows for %d subjects" % (np.shape(X)[0], len(paths)))
+    stem = {key: st for key, st, _, _, _ in _OUTPUT_FILES}[quantity]
+    vols, inside, affine = [], None, None
+    for path in paths:
+        img = nifti.load(path + stem + "_in_template.nii.gz")
+        ins = nifti.load(path + "maps_to_template_inside.nii.gz")
+        vol = img.get_fdata()
+        if affine is None:
+            affine = img.affine
+        if vol.ndim != 3 or (vols and vol.shape != vols[0].shape) or not np.allclose(img.affine, affine, rtol=0.0, atol=1e-6):
+            raise ValueError("%s does not lie on the template grid of the first subject: run motor_maps_to_template with one template" % path)
+        m = ins.get_fdata() != 0
+        if m.shape != vol.shape:
+            raise ValueError("maps_to_template_inside at %s does not lie on the grid of its maps" % path)
+        inside = m if inside is None else inside & m
+        vols.append(vol)
+    if path_to_mask is not None:
+        m = nifti.load(path_to_mask).get_fdata() != 0
+        if m.shape != inside.shape:
+            raise ValueError("the mask does not lie on the template grid")
+        inside = inside & m
+    out = group_stats_filter(np.stack(vols), X, c, mask=inside, **options)
+    for key, name in (("tstat", "tstat"), ("cope", "cope"), ("p_uncorrected", "p_unc"), ("p_fwe", "p_fwe")):
+        nifti.save(nifti.NiftiImage(out[key], affine), path_to_out + quantity + "_" + name + ".nii.gz")
+    np.savetxt(path_to_out + quantity + "_max_dist.txt", out["max_dist"])
+    n = len(paths)
+    lines = ["group statistics of %s: n = %d subjects, dof = %d" % (quantity, n, out["dof"]),
+             "permutations: %d (%s)" % (out["n_perm"], "exhaustive" if out["exhaustive"] else "drawn at random"),
+             "voxels tested: %d" % int(out["mask"].sum()),
+             "t_crit (0.95 quantile of the maximum statistic): %.6f" % out["t_crit"],
+             "voxels with p_fwe <= 0.05: %d" % int(((out["p_fwe"] <= 0.05) & out["mask"]).sum())]
+    with open(path_to_out + quantity + "_group_report.txt", "w") as f:
         f.write("\n".join(lines) + "\n")
     return out
 
