@@ -1396,6 +1396,57 @@ int met2_group_limits(int32_t *max_n, int32_t *max_r, int32_t *max_k, int32_t *v
 int met2_group_perm_stats(int32_t device, int32_t n, int64_t n_vox, const double *Y, const double *s0, int32_t r, int32_t K, const double *W,
                           int32_t two_sided, const double *t_ref, double *t_first, double *kmax, uint32_t *count, void *stream);
 
+/* Threshold-free cluster enhancement (Smith & Nichols, NeuroImage 44:83-98, 2009) and cluster extent of statistic maps, and both as the
+ * statistic of the permutation test above (an extension; additive, ABI stays 6).  Written from the paper and from the statement below.
+ * A map t lies on a grid dims = {nx, ny, nz}, the voxel (x, y, z) at (x ny + y) nz + z, with a mask (uint8, non-zero = inside; NULL: all).
+ *   Level.    h_j = (double)j * dh (one rounding).  level(v) = the largest j in 1 .. MET2_TFCE_MAX_STEPS with h_j <= t(v), found by comparisons
+ *             (a bisection over j; no division); 0 if there is none, if v lies outside the mask or if t(v) is not a number.  A map that rises
+ *             above MET2_TFCE_MAX_STEPS dh is treated as if it stopped there (+infinity too).
+ *   Support.  S_j = {v: level(v) >= j};  e_j(v) = the number of voxels of the connected component of S_j that holds v, under connectivity
+ *             6 (faces), 18 (faces and edges) or 26 (faces, edges and corners).  Neighbours are found on (x, y, z): the grid does not wrap,
+ *             and a voxel outside the mask joins nothing.
+ *   MET2_TFCE_MODE_TFCE:    out(v) = dh * sum_j e_j(v)^E h_j^H, the sum from 0.0 over j = level(v), level(v) - 1, .. 1 in that order, every
+ *             product and sum rounded once, nothing fused.  For E = 0.5 and H = 2 exactly, a term is sqrt((double)e) * (h * h), with a
+ *             correctly rounded square root: numpy reproduces the bits in float64 (tests/tools/tfce_numpy.py).  Any other (E, H): a term is
+ *             pow((double)e, E) * pow(h, H), held to an accuracy bound only.  out = 0 where level = 0.
+ *   MET2_TFCE_MODE_EXTENT:  dh is THE threshold h: out(v) = the size of v's component of {t >= h} as a double, 0 outside it.  E and H are
+ *             not read.
+ * met2_tfce: maps [K][nx][ny][nz] -> out [K][nx][ny][nz] (must not overlap maps) and, when not NULL, kmax [K] = max over the grid of out
+ *   (>= 0; by an integer atomic max per block and map on the key of met2_group_perm_stats).  A map's bits depend on that map, the mask and the
+ *   parameters alone: not on K, its place in the batch or the other maps.
+ * met2_group_perm_tfce: n, n_vox, Y, s0, r, K, W as for met2_group_perm_stats (one-sided); at [n_vox] int32, strictly ascending: voxel v's
+ *   index in the grid.  For each candidate k, t(k, v) is computed by met2_group_perm_stats's own kernel code -- the same sums in the same
+ *   order, hence the same bits -- and scattered to a dense map on the grid, with the mask {at[v]}; the maps are transformed as above, and
+ *   s(k, v) = out_k(at[v]) gathered:  kmax[k] = max_v s(k, v);  first[v] = s(0, v) when first is not NULL;  count[v] += #{k: s(k, v) >=
+ *   ref[v]} when ref is not NULL (count is then required; accumulated over launches; one thread owns a voxel).
+ * How.  One union-find forest per map over the grid, kept across the levels, which are walked downward from the batch's top level (one
+ *   4-byte device-to-host read per call; nothing per level): voxels of level j unite with their neighbours of level >= j by an integer
+ *   atomic min on a parent array with parent[v] <= v; sizes are kept at the roots by integer atomic adds (a voxel adds itself once, at its own
+ *   level; a root that stopped being one hands its size on); then every voxel of S_j adds its root's term to its own running sum.  Integer
+ *   atomics only; results do not depend on the order of execution.  Every device loop is bounded (a chase or a retry by the voxel count, the
+ *   levels by MET2_TFCE_MAX_STEPS); a bound that runs out, or an `at` that is not strictly ascending inside the grid, raises a device flag,
+ *   read when the call's work is waited for: MET2_E_HIP, resp. MET2_E_INVALID, and kmax, first and count are then untouched for `at`.
+ * Work space.  met2_tfce_work_bytes: the bytes a call needs for K maps on dims (n_vox = 0: met2_tfce, 10 bytes per map and grid voxel: level,
+ *   parent, size; n_vox > 0: met2_group_perm_tfce, 18 bytes: the dense map, which becomes the running sum, as well).  work = NULL: the call
+ *   allocates and frees it; else a device block of work_bytes >= that (MET2_E_INVALID if smaller).  Either way the call returns after its
+ *   work is done.
+ * DEVICE pointers throughout but dims.  met2_tfce_limits is host only.
+ * Limits.  1 <= K <= MET2_TFCE_MAX_K, nx, ny, nz >= 1 and nx ny nz < 2^31 (MET2_E_UNSUPPORTED beyond the upper ends); the group entry's
+ * n, r as above.  MET2_E_INVALID: a mode or connectivity other than those named, dh not finite or <= 0, in TFCE mode E not finite or <= 0 or
+ * H not finite or < 0, K or an axis < 1, a NULL required pointer, ref without count.  Every such check comes before any device work: the
+ * outputs are then untouched. */
+#define MET2_TFCE_MAX_K 32
+#define MET2_TFCE_MAX_STEPS 1024
+#define MET2_TFCE_MODE_TFCE 0
+#define MET2_TFCE_MODE_EXTENT 1
+int met2_tfce_limits(int32_t *max_k, int32_t *max_steps);
+int met2_tfce_work_bytes(int32_t K, const int32_t dims[3], int64_t n_vox, int64_t *bytes);
+int met2_tfce(int32_t device, int32_t K, const int32_t dims[3], const double *maps, const uint8_t *mask, int32_t mode, double dh, double E,
+              double H, int32_t connectivity, double *out, double *kmax, void *work, int64_t work_bytes, void *stream);
+int met2_group_perm_tfce(int32_t device, int32_t n, int64_t n_vox, const double *Y, const double *s0, int32_t r, int32_t K, const double *W,
+                         const int32_t dims[3], const int32_t *at, int32_t mode, double dh, double E, double H, int32_t connectivity,
+                         const double *ref, double *first, double *kmax, uint32_t *count, void *work, int64_t work_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,8 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
                             warp_register_filter / warp_filter / warp_labels_filter (non-linear registration and resampling through a displacement
                             field; atlas_stats_filter(nonlinear=...)), warp_invert_filter / warp_jacobian_filter / maps_to_template_filter (the
                             inverse of a field by fixed-point iteration, its Jacobian determinant, the maps onto a template's grid): warp.py, csrc/met2_warp.hip,
-                            group_stats_filter (voxel-wise group statistics with permutation inference over subjects' maps on one grid: group.py, csrc/met2_group.hip),
+                            group_stats_filter (voxel-wise group statistics with permutation inference over subjects' maps on one grid: group.py, csrc/met2_group.hip;
+                            tfce=... / cluster_threshold=...: TFCE and cluster-extent inference), tfce_filter (the TFCE of one volume: csrc/met2_tfce.hip),
                             gaussian_smooth
   tv.py                     tv_denoise_volume / tv_chambolle: denoise='TV' of the driver through met2_tv_chambolle (csrc/met2_tv.hip)
   gibbs.py                  gibbs_tables / gibbs_split / gibbs_split3d / gibbs_lines: the stages of the Gibbs-ringing filter one by one (tests and diagnostics)
@@ -40,7 +41,8 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
                             matrix of register.py; warp / warp_labels / compose / max_norm2 / lncc / lncc_sums / lncc_force: its stages one by one (csrc/met2_warp.hip);
                             invert: the inverse field by fixed-point iteration, invert_step / jacobian: its step and the determinant with the count of folded voxels
   group.py                  partition / residualise / permutation_set / weights: a design and a t-contrast as the weight rows of met2_group_perm_stats;
-                            perm_stats: the entry on arrays; randomise: the permutation test (uncorrected and FWE-corrected p-values) (csrc/met2_group.hip)
+                            perm_stats: the entry on arrays; randomise: the permutation test (uncorrected and FWE-corrected p-values) (csrc/met2_group.hip);
+                            tfce / cluster_extent: the spatial statistics of maps; randomise(tfce=..., cluster_threshold=...): their permutation test (csrc/met2_tfce.hip)
   rician.py                 bias / step / invert: the kernels of the Rician noise-floor correction one by one (csrc/met2_rician.hip; Met2Plan.fit_rician and
                             noise_sigma, rician='iterative' | 'direct' of the drivers)
   mppca.py                  mppca_stages: the MP-PCA denoiser with what each of its steps leaves (tests and diagnostics)
@@ -53,7 +55,7 @@ from ._lib import Met2Error  # noqa: F401
 from .plan import BOOT_QUANTITIES, BOOT_QUANTITIES_FA, BOOT_STATS, MAP_NAMES, METHODS, PENALTIES, Met2Plan  # noqa: F401
 
 
-_LAZY = ("gibbs_filter", "bias_field_filter", "brain_mask_filter", "tissue_segment_filter", "partial_volume_filter")   # motor's, imported on first use
+_LAZY = ("gibbs_filter", "bias_field_filter", "brain_mask_filter", "tissue_segment_filter", "partial_volume_filter", "tfce_filter")   # motor's, imported on first use
 
 
 def __getattr__(name):

@@ -2,18 +2,7 @@
 // permutations, with the maximum over the voxels per candidate and the count per voxel of the candidates that reach a reference fused in
 // (include/met2_hip.h states the contract; group.py holds the partition of the design, the permutation set and the loop over batches).
 // Written from that statement and from Winkler et al. (NeuroImage 92:381-397, 2014) and Freedman & Lane (J. Bus. Econ. Stat. 1:292-298, 1983).
-//   gp_stats_kernel<R1, KB>    lanes = voxels: a block owns GP_TILE consecutive voxels, one per thread, for ALL candidates of the launch, so a
-//                              voxel's count has one owner and is written once.  The candidates go through in groups of KB: the group's
-//                              KB (r + 1) weight rows are staged in LDS transposed to [subject][row], so that for one subject every thread
-//                              reads the same consecutive addresses (a broadcast, no bank conflict), and each thread carries KB (r + 1)
-//                              running sums in registers while it walks its voxel's column of Y once per group (coalesced over the wave;
-//                              the tile's columns stay in cache between groups).  R1 = r + 1 and KB are compile-time, so no register array
-//                              is indexed at run time: KB = 8 up to r = 3 (16 .. 32 sums), 4 beyond (20 .. 36 sums).
-//                              A candidate's maximum: per wave by an xor butterfly of comparisons, the four waves through LDS, then ONE integer
-//                              atomic max per (block, candidate) on an order-preserving key, skipped when kmax already holds as much -- a
-//                              maximum does not depend on the order, and no floating-point atomic is used.
-//   gp_key_kernel              writes the key of -infinity into kmax before, and turns the keys into doubles in place after: no scratch
-// A candidate beyond K in the last group has zero weights and is left out of every output; a thread beyond n_vox reads nothing and writes nothing.
+// The kernels (gp_stats_kernel, gp_key_kernel) are group_kernel.hpp's, which met2_tfce.hip shares: that header describes them.
 // The file is compiled without contraction; every loop is bounded by a shape or a compile-time constant.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,118 +13,9 @@
 #include "../../include/met2_hip.h"
 #include "abi_common.hpp"
 #include "device_helpers.hpp"
+#include "group_kernel.hpp"
 
 #pragma clang fp contract(off)
-
-namespace {
-
-#define GP_TILE MET2_GROUP_VOXEL_TILE      // voxels of a block, one per thread
-#define GP_WAVES (GP_TILE / 64)
-
-// the bit pattern of a double as an unsigned integer that orders as the values do (-inf lowest, -0 below +0, +inf highest)
-__host__ __device__ __forceinline__ unsigned long long gp_key(unsigned long long bits)
-{
-    return (bits >> 63) ? ~bits : (bits | 0x8000000000000000ull);
-}
-__device__ __forceinline__ unsigned long long gp_unkey(unsigned long long key)
-{
-    return (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
-}
-
-// decode = 0: every key the key of -infinity; decode = 1: every key back to the double it stands for
-__global__ void __launch_bounds__(256) gp_key_kernel(int K, unsigned long long *__restrict__ kmax, int decode)
-{
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= K) return;
-    kmax[k] = decode ? gp_unkey(kmax[k]) : gp_key(0xfff0000000000000ull);
-}
-
-template <int R1, int KB>
-__global__ void __launch_bounds__(GP_TILE) gp_stats_kernel(int n, int64_t n_vox, const double *__restrict__ Y, const double *__restrict__ s0, int K,
-                                                           const double *__restrict__ W, int two_sided, const double *__restrict__ t_ref,
-                                                           double *__restrict__ t_first, unsigned long long *__restrict__ kmax, uint32_t *__restrict__ count)
-{
-    constexpr int ROWS = KB * R1;
-    extern __shared__ double gp_lds[];
-    double *wt = gp_lds;                                           // [n][ROWS]: the group's weights, subject-major
-    double *wmax = gp_lds + (size_t)n * ROWS;                      // [GP_WAVES][KB]: the waves' maxima
-    const int64_t v = (int64_t)blockIdx.x * GP_TILE + threadIdx.x;
-    const bool live = v < n_vox;
-    const double *y = Y + (live ? v : 0);
-    const double s = live ? s0[v] : 0.0;
-    const double ref = (t_ref && live) ? t_ref[v] : 0.0;
-    uint32_t cnt = 0;
-    for (int k0 = 0; k0 < K; k0 += KB) {
-        __syncthreads();                                           // the previous group's readers of wt and wmax are done
-        for (int e = threadIdx.x; e < ROWS * n; e += GP_TILE) {
-            const int row = e / n, i = e - row * n;
-            wt[i * ROWS + row] = k0 + row / R1 < K ? W[((int64_t)k0 * R1 + row) * n + i] : 0.0;
-        }
-        __syncthreads();
-        double acc[KB][R1];
-#pragma unroll
-        for (int c = 0; c < KB; ++c)
-#pragma unroll
-            for (int j = 0; j < R1; ++j) acc[c][j] = 0.0;
-        double y_next = live ? y[0] : 0.0;
-#pragma unroll 1
-        for (int i = 0; i < n; ++i) {                              // not unrolled: a second subject's weights in registers cost a wave per SIMD
-            const double yi = y_next;
-            y_next = live && i + 1 < n ? y[(int64_t)(i + 1) * n_vox] : 0.0;    // the next subject's value is on its way during this one's sums
-            const double *w = wt + i * ROWS;
-#pragma unroll
-            for (int c = 0; c < KB; ++c)
-#pragma unroll
-                for (int j = 0; j < R1; ++j) acc[c][j] = rn_add(acc[c][j], rn_mul(w[c * R1 + j], yi));
-        }
-#pragma unroll
-        for (int c = 0; c < KB; ++c) {
-            double q = rn_mul(acc[c][1], acc[c][1]);
-#pragma unroll
-            for (int j = 2; j < R1; ++j) q = rn_add(q, rn_mul(acc[c][j], acc[c][j]));
-            const double rss = rn_sub(s, q);
-            double t = rss > 0.0 ? acc[c][0] / sqrt(rss) : 0.0;
-            if (two_sided) t = fabs(t);
-            const bool mine = live && k0 + c < K;
-            if (mine) {
-                if (t_ref && t >= ref) ++cnt;
-                if (t_first && k0 + c == 0) t_first[v] = t;
-            }
-            double m = mine && t == t ? t : -INFINITY;             // a statistic that is not a number is passed over
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double other = __shfl_xor(m, o);
-                if (other > m) m = other;
-            }
-            if ((threadIdx.x & 63) == 0) wmax[(threadIdx.x >> 6) * KB + c] = m;
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < KB && k0 + (int)threadIdx.x < K) {
-            double m = wmax[threadIdx.x];
-#pragma unroll
-            for (int wv = 1; wv < GP_WAVES; ++wv)
-                if (wmax[wv * KB + threadIdx.x] > m) m = wmax[wv * KB + threadIdx.x];
-            // kmax[k] only grows during the launch, so a block whose maximum does not exceed what it reads there has nothing to add
-            const unsigned long long key = gp_key((unsigned long long)__double_as_longlong(m));
-            unsigned long long *dst = kmax + k0 + threadIdx.x;
-            if (key > __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(dst, key);
-        }
-    }
-    if (t_ref && live) count[v] += cnt;                            // this thread owns the voxel
-}
-
-template <int R1>
-void gp_launch(int64_t n_vox, int n, int K, const double *Y, const double *s0, const double *W, int two_sided, const double *t_ref, double *t_first,
-               double *kmax, uint32_t *count, hipStream_t st)
-{
-    constexpr int KB = R1 <= 4 ? 8 : 4;
-    const size_t lds = ((size_t)n * KB * R1 + GP_WAVES * KB) * sizeof(double);          // <= 128 * 36 * 8 + 256 = 37 120 bytes
-    const unsigned blocks = (unsigned)((n_vox + GP_TILE - 1) / GP_TILE);
-    hipLaunchKernelGGL((gp_stats_kernel<R1, KB>), dim3(blocks), dim3(GP_TILE), lds, st, n, n_vox, Y, s0, K, W, two_sided, t_ref, t_first,
-                       (unsigned long long *)kmax, count);
-}
-
-}  // namespace
 
 extern "C" int met2_group_limits(int32_t *max_n, int32_t *max_r, int32_t *max_k, int32_t *voxel_tile)
 {
@@ -162,13 +42,7 @@ extern "C" int met2_group_perm_stats(int32_t device, int32_t n, int64_t n_vox, c
     hipStream_t st = (hipStream_t)stream;
     const dim3 kgrid((K + 255) / 256);
     hipLaunchKernelGGL(gp_key_kernel, kgrid, dim3(256), 0, st, K, (unsigned long long *)kmax, 0);
-    if (n_vox > 0) {
-        switch (r) {
-#define GP_CASE(R) case R: gp_launch<R + 1>(n_vox, n, K, Y, s0, W, two_sided, t_ref, t_first, kmax, count, st); break
-            GP_CASE(1); GP_CASE(2); GP_CASE(3); GP_CASE(4); GP_CASE(5); GP_CASE(6); GP_CASE(7); GP_CASE(8);
-#undef GP_CASE
-        }
-    }
+    if (n_vox > 0) gp_launch_r<false>(r, n_vox, n, K, Y, s0, W, two_sided, t_ref, t_first, kmax, count, nullptr, 0, nullptr, st);
     hipLaunchKernelGGL(gp_key_kernel, kgrid, dim3(256), 0, st, K, (unsigned long long *)kmax, 1);
     HIPCHK(hipGetLastError());
     return MET2_OK;

@@ -1,6 +1,6 @@
 """The whole-volume filters of the drivers, each one call into the C ABI (one translation unit under csrc/ per filter): nesma_filter,
 mppca_filter (with mppca_window and mppca_work_bytes), gibbs_filter, brain_mask_filter, bias_field_filter, tissue_segment_filter, partial_volume_filter, label_stats_filter,
-resample_filter, resample_labels_filter, register_filter, warp_register_filter, warp_filter, warp_labels_filter, atlas_stats_filter, group_stats_filter and gaussian_smooth.  All take numpy arrays (and return numpy) or CUDA tensors (and return tensors on the same device); motor.py's drivers
+resample_filter, resample_labels_filter, register_filter, warp_register_filter, warp_filter, warp_labels_filter, atlas_stats_filter, group_stats_filter, tfce_filter and gaussian_smooth.  All take numpy arrays (and return numpy) or CUDA tensors (and return tensors on the same device); motor.py's drivers
 call them and re-export the names."""
 import numpy as np
 import torch
@@ -403,12 +403,18 @@ def maps_to_template_filter(res, affine, template_shape, template_affine, world=
 
 
 GROUP_VOLUMES = ("tstat", "cope", "p_uncorrected", "p_fwe")
+# the spatial statistics' maps (group.randomise(tfce=..., cluster_threshold=...)): the statistic is 0 outside the mask, a p-value 1
+GROUP_SPATIAL_VOLUMES = ("tfce", "p_tfce_uncorrected", "p_tfce_fwe", "cluster_extent", "p_cluster_uncorrected", "p_cluster_fwe")
+GROUP_SPATIAL_COUNTS = ("tfce_count", "cluster_count")
 
 
-def group_stats_filter(volumes, X, c, mask=None, **options):
+def group_stats_filter(volumes, X, c, mask=None, tfce=None, cluster_threshold=None, cluster_connectivity=26, **options):
     """The permutation test of the t-contrast c in the design X [n, p] at every voxel of n subjects' volumes [n, x, y, z] on one grid (the
     <map>_in_template volumes of maps_to_template_filter): group.randomise on the voxels of `mask` (None: all), unfolded into volumes.
     options: n_perm, seed, exchange ('permute' | 'flip'), two_sided, device, batch_stat -- group.randomise's.
+    tfce (True or a dict of E, H, dh, connectivity) and / or cluster_threshold (with cluster_connectivity) add the spatial statistics, for
+    which the grid and the voxels' places in it are handed on (options then also: batch_spatial, work_bytes): tfce, p_tfce_uncorrected,
+    p_tfce_fwe, tfce_count, cluster_extent, p_cluster_uncorrected, p_cluster_fwe and cluster_count as volumes too.
     -> its dict with tstat, cope, p_uncorrected, p_fwe and count as [x, y, z] volumes (outside the mask t = 0, cope = 0, p = 1, count =
     n_perm) and mask [x, y, z] bool: the voxels that were tested.  Parity with FSL randomise is unpinned: FSL was not available."""
     from . import group
@@ -420,15 +426,33 @@ def group_stats_filter(volumes, X, c, mask=None, **options):
     if m.shape != shape:
         raise ValueError("the mask does not lie on the grid of the volumes")
     at = np.flatnonzero(m.reshape(-1))
+    if (tfce is not None and tfce is not False) or cluster_threshold is not None:
+        options = dict(options, tfce=tfce, cluster_threshold=cluster_threshold, cluster_connectivity=cluster_connectivity, grid=shape, at=at)
     res = group.randomise(np.ascontiguousarray(vols.reshape(vols.shape[0], -1)[:, at]), X, c, **options)
-    for key in GROUP_VOLUMES:
-        vol = np.full(int(np.prod(shape)), 0.0 if key in ("tstat", "cope") else 1.0)
+    for key in GROUP_VOLUMES + tuple(k for k in GROUP_SPATIAL_VOLUMES if k in res):
+        vol = np.full(int(np.prod(shape)), 1.0 if key.startswith("p_") else 0.0)
         vol[at] = res[key]
         res[key] = vol.reshape(shape)
-    count = np.full(int(np.prod(shape)), res["n_perm"], dtype=np.uint32)
-    count[at] = res["count"]
-    res.update(count=count.reshape(shape), mask=m)
+    for key in ("count",) + tuple(k for k in GROUP_SPATIAL_COUNTS if k in res):
+        count = np.full(int(np.prod(shape)), res["n_perm"], dtype=np.uint32)
+        count[at] = res[key]
+        res[key] = count.reshape(shape)
+    res.update(mask=m)
     return res
+
+
+def tfce_filter(vol, mask=None, dh=None, E=0.5, H=2.0, connectivity=6, device=0):
+    """Threshold-free cluster enhancement of one volume [x, y, z] (group.tfce: csrc/met2_tfce.hip) -> the enhanced volume.  mask: the voxels that
+    take part (None: all); dh None: a hundredth of the volume's largest finite value inside the mask; connectivity 6 | 18 | 26.  numpy in,
+    numpy out; a CUDA tensor in, a tensor on its device out."""
+    from . import group
+    is_t = torch.is_tensor(vol)
+    a = np.asarray(vol.cpu() if is_t else vol, dtype=np.float64)
+    if a.ndim != 3:
+        raise ValueError("vol must be [x, y, z]")
+    m = None if mask is None else np.asarray(mask.cpu() if torch.is_tensor(mask) else mask) != 0
+    out = group.tfce(a, m, dh=dh, E=E, H=H, connectivity=connectivity, device=vol.device.index or 0 if is_t and vol.is_cuda else device)
+    return torch.as_tensor(out, device=vol.device) if is_t else out
 
 
 def atlas_stats_filter(res, labels, labels_affine, affine, world=None, q=None, device=0, template=None, template_affine=None, register=None,

@@ -17,8 +17,18 @@ coefficient of x1 is x1' P_k Yr / (x1' x1), the residual sum of squares is |P_k 
 statistics is never formed: the entry keeps the maximum per candidate and the count per voxel.
 
 perm_stats is the entry on arrays; randomise batches the candidates through it (or through batch_stat, a numpy callable with the entry's
-meaning: the loop then needs no device).  Parity with FSL randomise is unpinned: FSL was not available.  Not provided: F-contrasts,
-exchangeability blocks, TFCE and cluster-extent statistics, variance smoothing, several devices."""
+meaning: the loop then needs no device).
+
+Spatial statistics (csrc/met2_tfce.hip; the header states the definitions): tfce and cluster_extent transform maps on a grid;
+randomise(tfce=..., cluster_threshold=..., grid=, at=) tests them by permutation through met2_group_perm_tfce (perm_tfce on arrays), which
+computes every candidate's t with met2_group_perm_stats's own kernel code, keeps a batch of dense maps on the device and returns, as the t
+entry does, one maximum per candidate and one count per voxel.  dh defaults to a hundredth of the observed map's maximum and is the same for
+every permutation; a level holds the voxels with t >= h (not >); a map is followed up to MET2_TFCE_MAX_STEPS = 1 024 levels, i.e. with the
+default dh to 10.24 times the observed maximum, and treated above that as if it stopped there -- three places where FSL's randomise -T may
+differ.  One-sided only: on |t| a positive and a negative blob would fuse into one cluster, so test c and -c.
+
+Parity with FSL randomise (-T and -c included) is unpinned: FSL was not available.  Not provided: cluster mass, F-contrasts, exchangeability
+blocks, variance smoothing, several devices, 2-D connectivity."""
 import collections
 import ctypes as C
 import math
@@ -243,9 +253,224 @@ def perm_stats(Y, s0, W, two_sided=False, t_ref=None, count=None, want_first=Fal
     return (kmax.cpu().numpy(), None if cnt is None else cnt.cpu().numpy().view(np.uint32), None if first is None else first.cpu().numpy())
 
 
+# ---------------------------------------------------------------- the spatial statistics on arrays
+
+MODES = {"tfce": 0, "extent": 1}                                   # MET2_TFCE_MODE_*
+CONNECTIVITIES = (6, 18, 26)
+TFCE_DEFAULTS = {"E": 0.5, "H": 2.0, "dh": None, "connectivity": 6}
+
+
+def tfce_limits():
+    """met2_tfce_limits -> dict(max_k, max_steps); needs no device"""
+    v = [C.c_int32(-1) for _ in range(2)]
+    check(lib().met2_tfce_limits(*[C.byref(x) for x in v]))
+    return dict(zip(("max_k", "max_steps"), (x.value for x in v)))
+
+
+def _dims(grid):
+    g = tuple(int(x) for x in grid)
+    if len(g) != 3 or min(g) < 1:
+        raise ValueError("grid must be (nx, ny, nz) with every axis >= 1")
+    return g
+
+
+def tfce_work_bytes(K, grid, n_vox=0):
+    """met2_tfce_work_bytes: the device work space of one call for K maps on `grid` (n_vox > 0: of met2_group_perm_tfce)"""
+    out = C.c_int64(-1)
+    check(lib().met2_tfce_work_bytes(int(K), (C.c_int32 * 3)(*_dims(grid)), int(n_vox), C.byref(out)))
+    return out.value
+
+
+def _batch_for(grid, n_vox, budget, most):
+    """the largest K <= most (and <= max_k) whose work space stays within `budget` bytes"""
+    K = max(1, min(int(most), tfce_limits()["max_k"]))
+    while K > 1 and tfce_work_bytes(K, grid, n_vox) > budget:
+        K -= 1
+    if tfce_work_bytes(K, grid, n_vox) > budget:
+        raise ValueError("one map on a grid of %s needs %d bytes of work space, more than work_bytes = %d" % (grid, tfce_work_bytes(1, grid, n_vox), budget))
+    return K
+
+
+def spatial(maps, mask=None, mode="tfce", dh=None, E=0.5, H=2.0, connectivity=6, device=0, work_bytes=2 ** 30):
+    """met2_tfce on numpy arrays: maps [K, nx, ny, nz] (any K: batches of at most max_k maps, fewer if the work space would pass work_bytes),
+    mask [nx, ny, nz] or None, mode 'tfce' | 'extent' (dh is then the threshold) -> (out [K, nx, ny, nz], kmax [K]).  dh is required."""
+    import torch
+    if mode not in MODES:
+        raise ValueError("mode must be one of %s" % (tuple(MODES),))
+    maps = np.ascontiguousarray(maps, dtype=np.float64)
+    if maps.ndim != 4:
+        raise ValueError("maps must be [K, nx, ny, nz]")
+    grid = _dims(maps.shape[1:])
+    if dh is None:
+        raise ValueError("dh is required")
+    dev = torch.device("cuda", device)
+    m = None
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mask.shape != grid:
+            raise ValueError("the mask does not lie on the grid of the maps")
+        m = torch.as_tensor(mask, device=dev)
+    out, kmax = np.empty_like(maps), np.empty(maps.shape[0])
+    if not maps.shape[0]:
+        return out, kmax
+    step = _batch_for(grid, 0, work_bytes, maps.shape[0])
+    dims = (C.c_int32 * 3)(*grid)
+    with torch.cuda.device(dev):
+        for k0 in range(0, maps.shape[0], step):
+            src = torch.as_tensor(maps[k0:k0 + step], device=dev)
+            dst, km = torch.empty_like(src), torch.empty(src.shape[0], dtype=torch.float64, device=dev)
+            check(lib().met2_tfce(device, src.shape[0], dims, src.data_ptr(), None if m is None else m.data_ptr(), MODES[mode], float(dh), float(E),
+                                  float(H), int(connectivity), dst.data_ptr(), km.data_ptr(), None, 0, torch.cuda.current_stream(dev).cuda_stream))
+            out[k0:k0 + step], kmax[k0:k0 + step] = dst.cpu().numpy(), km.cpu().numpy()
+    return out, kmax
+
+
+def _inside(maps, mask):
+    vals = maps if mask is None else maps[..., np.asarray(mask) != 0]
+    vals = vals[np.isfinite(vals)]
+    return float(vals.max()) if vals.size else 0.0
+
+
+def tfce(maps, mask=None, dh=None, E=0.5, H=2.0, connectivity=6, device=0):
+    """Threshold-free cluster enhancement of one map [nx, ny, nz] or several [K, nx, ny, nz] -> the same shape.  dh None: a hundredth of the
+    largest finite value inside the mask over all the maps; when that is <= 0 every value is 0 and nothing is launched.  connectivity
+    6 | 18 | 26.  E = 0.5, H = 2 reproduce a float64 numpy loop to the bit; other exponents go through pow."""
+    a = np.asarray(maps, dtype=np.float64)
+    one = a.ndim == 3
+    a = a[None] if one else a
+    if a.ndim != 4:
+        raise ValueError("maps must be [nx, ny, nz] or [K, nx, ny, nz]")
+    if dh is None:
+        top = _inside(a, mask)
+        if top <= 0.0:
+            return np.zeros(a.shape[1:] if one else a.shape)
+        dh = top / 100.0
+    out = spatial(a, mask, "tfce", dh, E, H, connectivity, device)[0]
+    return out[0] if one else out
+
+
+def cluster_extent(maps, threshold, mask=None, connectivity=26, device=0):
+    """The size of every voxel's connected component of {t >= threshold} (0 outside it), for one map [nx, ny, nz] or several [K, nx, ny, nz]"""
+    a = np.asarray(maps, dtype=np.float64)
+    one = a.ndim == 3
+    out = spatial(a[None] if one else a, mask, "extent", threshold, 1.0, 1.0, connectivity, device)[0]
+    return out[0] if one else out
+
+
+def _launch_spatial(dev, Y, s0, r, W, dims, at, mode, dh, E, H, connectivity, ref, first, kmax, count, work):
+    """met2_group_perm_tfce on tensors that are already on `dev` (at: int32; count: int32, the bits of uint32; work: a uint8 tensor or None)"""
+    import torch
+    n, V = Y.shape
+    with torch.cuda.device(dev):
+        check(lib().met2_group_perm_tfce(dev.index or 0, n, V, Y.data_ptr(), s0.data_ptr(), r, W.shape[0], W.data_ptr(), (C.c_int32 * 3)(*dims),
+                                         at.data_ptr(), MODES[mode], float(dh), float(E), float(H), int(connectivity),
+                                         None if ref is None else ref.data_ptr(), None if first is None else first.data_ptr(), kmax.data_ptr(),
+                                         None if count is None else count.data_ptr(), None if work is None else work.data_ptr(),
+                                         0 if work is None else work.numel(), torch.cuda.current_stream(dev).cuda_stream))
+
+
+def perm_tfce(Y, s0, W, grid, at, mode="tfce", dh=None, E=0.5, H=2.0, connectivity=6, ref=None, count=None, want_first=False, device=0):
+    """met2_group_perm_tfce on numpy arrays: perm_stats's Y, s0, W; grid (nx, ny, nz); at [V] the voxels' indices in the grid, strictly
+    ascending; ref [V] or None; count [V] uint32 to add to -> (kmax [K], count or None without ref, first [V] or None without want_first)"""
+    import torch
+    if mode not in MODES:
+        raise ValueError("mode must be one of %s" % (tuple(MODES),))
+    dev = torch.device("cuda", device)
+    Y, s0, W = (np.ascontiguousarray(a, dtype=np.float64) for a in (Y, s0, W))
+    _check_batch(Y, s0, W, ref, count)
+    put = lambda a: torch.as_tensor(a, device=dev)
+    V = Y.shape[1]
+    at = np.ascontiguousarray(at, dtype=np.int32)
+    if at.shape != (V,):
+        raise ValueError("at must be [V]")
+    kmax = torch.empty(W.shape[0], dtype=torch.float64, device=dev)
+    rf = None if ref is None else put(np.ascontiguousarray(ref, dtype=np.float64))
+    cnt = None
+    if rf is not None:
+        cnt = put(np.zeros(V, dtype=np.int32) if count is None else np.ascontiguousarray(count, dtype=np.uint32).view(np.int32))
+    first = torch.empty(V, dtype=torch.float64, device=dev) if want_first else None
+    _launch_spatial(dev, put(Y), put(s0), W.shape[1] - 1, put(W), _dims(grid), put(at), mode, dh, E, H, connectivity, rf, first, kmax, cnt, None)
+    return (kmax.cpu().numpy(), None if cnt is None else cnt.cpu().numpy().view(np.uint32), None if first is None else first.cpu().numpy())
+
+
+def _crop(grid, at):
+    """the grid cut to the bounding box of the voxels `at` -> (grid, at) there"""
+    if not at.size:
+        return (1, 1, 1), at.astype(np.int32)
+    x, y, z = np.unravel_index(at, grid)
+    lo = (x.min(), y.min(), z.min())
+    box = (int(x.max() - lo[0] + 1), int(y.max() - lo[1] + 1), int(z.max() - lo[2] + 1))
+    return box, np.ravel_multi_index((x - lo[0], y - lo[1], z - lo[2]), box).astype(np.int32)    # the order of the voxels is kept: still ascending
+
+
+def _spatial_test(Yk, sk, W, r, grid, at, mode, dh, E, H, connectivity, device, batch_spatial, work_bytes):
+    """the permutation distribution of one spatial statistic -> (observed [V], count [V] uint32, max_dist [P])"""
+    P, V = W.shape[0], Yk.shape[1]
+    if batch_spatial is not None:
+        _, _, obs = batch_spatial(Yk, sk, W[:1], grid, at, mode, dh, E, H, connectivity, None, True)
+        obs = np.asarray(obs, dtype=np.float64)
+        count, max_dist, K = np.zeros(V, dtype=np.uint32), np.empty(P), 32
+        for k0 in range(0, P, K):
+            km, inc, _ = batch_spatial(Yk, sk, W[k0:k0 + K], grid, at, mode, dh, E, H, connectivity, obs, False)
+            max_dist[k0:k0 + K] = km
+            count += np.asarray(inc, dtype=np.uint32)
+        return obs, count, max_dist
+    import torch
+    dev = torch.device("cuda", device)
+    put = lambda a: torch.as_tensor(a, device=dev)
+    K = _batch_for(grid, V, work_bytes, P)
+    work = torch.empty(tfce_work_bytes(K, grid, V), dtype=torch.uint8, device=dev)
+    Yt, st, Wt, at_t = put(Yk), put(sk), put(W), put(at)
+    obs_t = torch.empty(V, dtype=torch.float64, device=dev)
+    cnt = torch.zeros(V, dtype=torch.int32, device=dev)
+    md = torch.empty(P, dtype=torch.float64, device=dev)
+    _launch_spatial(dev, Yt, st, r, Wt[:1], grid, at_t, mode, dh, E, H, connectivity, None, obs_t, md[:1], None, work)
+    for k0 in range(0, P, K):
+        _launch_spatial(dev, Yt, st, r, Wt[k0:k0 + K], grid, at_t, mode, dh, E, H, connectivity, obs_t, None, md[k0:k0 + K], cnt, work)
+    return obs_t.cpu().numpy(), cnt.cpu().numpy().view(np.uint32), md.cpu().numpy()
+
+
+def _spatial_options(tfce, cluster_threshold, cluster_connectivity, two_sided, grid, at, V, batch_stat, batch_spatial):
+    """the checked options of randomise's spatial statistics -> (tfce dict or None, grid, at)"""
+    if two_sided:
+        raise ValueError("tfce and cluster_threshold are one-sided: on |t| a positive and a negative blob would fuse into one cluster; "
+                         "test c and -c instead of two_sided=True")
+    if grid is None or at is None:
+        raise ValueError("tfce and cluster_threshold need grid=(nx, ny, nz) and at=[V], the columns' voxel indices in it")
+    if batch_stat is not None and batch_spatial is None:
+        raise ValueError("batch_stat together with tfce or cluster_threshold needs batch_spatial, the numpy callable with met2_group_perm_tfce's meaning")
+    if batch_spatial is not None and not callable(batch_spatial):
+        raise ValueError("batch_spatial must be a callable with the entry's meaning")
+    grid = _dims(grid)
+    at = np.asarray(at, dtype=np.int64).ravel()
+    if at.size != V or (at.size and (at[0] < 0 or at[-1] >= int(np.prod(grid)))) or (np.diff(at) <= 0).any():
+        raise ValueError("at must hold one strictly ascending index into the grid per column of Y")
+    if int(np.prod(grid)) >= 2 ** 31:
+        raise ValueError("the grid must hold fewer than 2^31 voxels")
+    opts = None
+    if tfce is not None and tfce is not False:
+        opts = dict(TFCE_DEFAULTS)
+        if isinstance(tfce, dict):
+            unknown = set(tfce) - set(opts)
+            if unknown:
+                raise ValueError("tfce takes E, H, dh and connectivity, not %s" % sorted(unknown))
+            opts.update(tfce)
+        elif tfce is not True:
+            raise ValueError("tfce must be None, True or a dict of E, H, dh, connectivity")
+        if opts["connectivity"] not in CONNECTIVITIES or not (np.isfinite(opts["E"]) and opts["E"] > 0 and np.isfinite(opts["H"]) and opts["H"] >= 0):
+            raise ValueError("tfce: connectivity 6 | 18 | 26, E > 0, H >= 0")
+        if opts["dh"] is not None and not (np.isfinite(opts["dh"]) and opts["dh"] > 0):
+            raise ValueError("tfce: dh must be finite and > 0")
+    if cluster_threshold is not None:
+        if not (np.isfinite(cluster_threshold) and cluster_threshold > 0) or cluster_connectivity not in CONNECTIVITIES:
+            raise ValueError("cluster_threshold must be finite and > 0, cluster_connectivity 6 | 18 | 26")
+    return opts, grid, at
+
+
 # ---------------------------------------------------------------- the test
 
-def randomise(Y, X, c, n_perm=5000, seed=0, exchange="permute", two_sided=False, device=0, batch_stat=None):
+def randomise(Y, X, c, n_perm=5000, seed=0, exchange="permute", two_sided=False, device=0, batch_stat=None, tfce=None, cluster_threshold=None,
+              cluster_connectivity=26, grid=None, at=None, batch_spatial=None, work_bytes=2 ** 30):
     """The permutation test of the t-contrast c in the design X [n, p] at every voxel of Y [n, V] (one row per subject).
     batch_stat: None runs met2_group_perm_stats on `device`; a numpy callable with its meaning -- batch_stat(Y, s0, W, two_sided, t_ref,
     want_first) -> (kmax [K], count increment [V] or None, t_first [V] or None) -- replaces it, and the loop then needs no device.
@@ -253,10 +478,22 @@ def randomise(Y, X, c, n_perm=5000, seed=0, exchange="permute", two_sided=False,
     statistic at the voxel reaches the observed one, p_fwe [V] = #{k: max_dist[k] >= tstat(v)} / P, count [V], max_dist [P] (the maximum over
     the voxels per permutation), n_perm (the number actually used), exhaustive, dof, t_crit: np.quantile(max_dist, 0.95)).  Both p-values
     count the identity, so neither is below 1 / P.  A voxel whose residualised data are all zero, or whose s0 <= 1e-24 sum_i Y^2 (the
-    nuisance explains it), is left out of the launch and gets t = 0, cope = 0, p = 1."""
+    nuisance explains it), is left out of the launch and gets t = 0, cope = 0, p = 1.
+    Spatial statistics, one-sided: tfce = True or dict(E, H, dh, connectivity) (defaults 0.5, 2, a hundredth of the observed maximum of t, 6)
+    and / or cluster_threshold = h with cluster_connectivity; both need grid = (nx, ny, nz) and at [V], the strictly ascending index of every
+    column of Y in that grid (the grid is cropped to the tested voxels' bounding box before the launches).  batch_spatial: None runs
+    met2_group_perm_tfce in batches whose work space stays within work_bytes; a numpy callable with its meaning -- batch_spatial(Y, s0, W, grid,
+    at, mode, dh, E, H, connectivity, ref, want_first) -> (kmax [K], count increment [V] or None, first [V] or None), mode 'tfce' | 'extent' --
+    replaces it, and is required when batch_stat is given.  Adds for tfce: tfce [V], p_tfce_uncorrected, p_tfce_fwe, tfce_count, tfce_max_dist
+    [P], tfce_crit, dh, tfce_options; for the extent: cluster_extent [V], p_cluster_uncorrected, p_cluster_fwe, cluster_count,
+    cluster_max_dist [P], cluster_crit -- each defined as its t counterpart.  When the observed maximum of t is <= 0 (and dh is not given)
+    every TFCE value is 0 and every p is 1, with no launch.  With neither option the results and the launches are what they were."""
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     if Y.ndim != 2:
         raise ValueError("Y must be [n, V] with one row per subject")
+    want_spatial = (tfce is not None and tfce is not False) or cluster_threshold is not None
+    if want_spatial:
+        tfce_opts, grid, at = _spatial_options(tfce, cluster_threshold, cluster_connectivity, two_sided, grid, at, Y.shape[1], batch_stat, batch_spatial)
     if batch_stat is not None and not callable(batch_stat):
         raise ValueError("batch_stat must be a callable with the entry's meaning")
     x1, _ = partition(X, c)
@@ -304,4 +541,40 @@ def randomise(Y, X, c, n_perm=5000, seed=0, exchange="permute", two_sided=False,
     out["p_fwe"][keep] = n_ge / float(P)
     out.update(max_dist=max_dist, n_perm=P, exhaustive=bool(perms.exhaustive), dof=dof,
                t_crit=float(np.quantile(max_dist, 0.95)) if V else float("nan"))
+    if not want_spatial:
+        return out
+    box, at_box = _crop(grid, at[keep])
+    spatial_fn = batch_spatial                                     # None: the device
+
+    def fill(prefix, stat_key, keys, obs, count_s, md):
+        """one statistic's results, unfolded to the V columns: left-out voxels get 0 and p = 1"""
+        stat, cnt = np.zeros(full), np.full(full, P, dtype=np.uint32)
+        p_unc, p_fwe = np.ones(full), np.ones(full)
+        stat[keep], cnt[keep] = obs, count_s
+        p_unc[keep] = count_s / float(P)
+        p_fwe[keep] = (P - np.searchsorted(np.sort(md), obs, side="left")) / float(P)
+        out.update({stat_key: stat, keys[0]: p_unc, keys[1]: p_fwe, prefix + "_count": cnt, prefix + "_max_dist": md,
+                    prefix + "_crit": float(np.quantile(md, 0.95))})
+
+    if tfce_opts is not None:
+        dh = tfce_opts["dh"]
+        if dh is None:
+            top = float(np.max(t_obs)) if V else 0.0
+            dh = top / 100.0 if top > 0.0 and np.isfinite(top) else None
+        if dh is None or not V:                                    # nothing rises above zero: every value 0, every p 1, no launch
+            obs, count_s, md = np.zeros(V), np.full(V, P, dtype=np.uint32), np.zeros(P)
+        else:
+            obs, count_s, md = _spatial_test(Yk, sk, W, r, box, at_box, "tfce", dh, tfce_opts["E"], tfce_opts["H"], tfce_opts["connectivity"],
+                                             device, spatial_fn, work_bytes)
+        fill("tfce", "tfce", ("p_tfce_uncorrected", "p_tfce_fwe"), obs, count_s, md)
+        out.update(dh=dh if dh is not None else 0.0, tfce_options={"E": float(tfce_opts["E"]), "H": float(tfce_opts["H"]),
+                                                                   "connectivity": int(tfce_opts["connectivity"])})
+    if cluster_threshold is not None:
+        if V:
+            obs, count_s, md = _spatial_test(Yk, sk, W, r, box, at_box, "extent", float(cluster_threshold), 1.0, 1.0, cluster_connectivity, device,
+                                             spatial_fn, work_bytes)
+        else:
+            obs, count_s, md = np.zeros(V), np.full(V, P, dtype=np.uint32), np.zeros(P)
+        fill("cluster", "cluster_extent", ("p_cluster_uncorrected", "p_cluster_fwe"), obs, count_s, md)
+        out.update(cluster_threshold=float(cluster_threshold), cluster_connectivity=int(cluster_connectivity))
     return out

@@ -15,7 +15,7 @@ from ._lib import check, lib
 from .evaluate import study_t2_grid
 from .filters import (STAT_KEYS, STAT_QUANTITIES, atlas_stats_filter, bias_field_filter, brain_mask_filter, gaussian_smooth,  # noqa: F401
                       gibbs_filter, group_stats_filter, label_stats_filter, maps_to_template_filter, mppca_filter, nesma_filter, partial_volume_filter,
-                      register_filter, resample_filter, resample_labels_filter, tissue_segment_filter, warp_filter, warp_invert_filter,
+                      register_filter, resample_filter, resample_labels_filter, tfce_filter, tissue_segment_filter, warp_filter, warp_invert_filter,
                       warp_jacobian_filter, warp_labels_filter, warp_register_filter)
 from .plan import BOOT_QUANTITIES, BOOT_STATS, MAP_NAMES, Met2Plan
 
@@ -1022,12 +1022,17 @@ def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_m
     template grid.  paths_to_save_data: one path_to_save_data per subject, in the order of the rows of the design X [n, p]; `quantity`: one of
     STAT_QUANTITIES; c: the t-contrast.  Every subject's <stem>_in_template.nii.gz is loaded; differing shapes or affines are refused.  The
     test runs on the intersection of the subjects' maps_to_template_inside.nii.gz and, where given, the mask at path_to_mask (non-zero voxels,
-    on the same grid).  options: group_stats_filter's (n_perm, seed, exchange, two_sided, device, batch_stat).
+    on the same grid).  options: group_stats_filter's (n_perm, seed, exchange, two_sided, device, batch_stat; tfce, cluster_threshold,
+    cluster_connectivity, batch_spatial, work_bytes).
     Written at path_to_out with the template's affine: <quantity>_tstat.nii.gz, <quantity>_cope.nii.gz, <quantity>_p_unc.nii.gz and
     <quantity>_p_fwe.nii.gz; <quantity>_max_dist.txt (the maximum statistic of every permutation, the identity first) and
     <quantity>_group_report.txt: n, dof, the number of permutations, whether the set was exhaustive, t_crit (the 0.95 quantile of the maximum
     statistic) and the number of voxels with p_fwe <= 0.05.  The p-value files hold p itself, NOT FSL randomise's 1 - p: small is significant,
     and no value is below 1 / n_perm.  Parity with FSL randomise is unpinned.
+    With tfce=True | dict(E, H, dh, connectivity) (one-sided): also <quantity>_tfce.nii.gz, <quantity>_p_tfce_unc.nii.gz,
+    <quantity>_p_tfce_fwe.nii.gz and <quantity>_tfce_max_dist.txt, and in the report dh, E, H, the connectivity, tfce_crit and the number of
+    voxels with p_tfce_fwe <= 0.05.  With cluster_threshold=h (cluster_connectivity=26): <quantity>_cluster_extent.nii.gz and
+    <quantity>_p_cluster_fwe.nii.gz, and their line in the report.  Parity with randomise -T / -c is unpinned as well.
     -> the dict of group_stats_filter."""
     from . import nifti
     if quantity not in STAT_QUANTITIES:
@@ -1065,6 +1070,20 @@ def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_m
              "voxels tested: %d" % int(out["mask"].sum()),
              "t_crit (0.95 quantile of the maximum statistic): %.6f" % out["t_crit"],
              "voxels with p_fwe <= 0.05: %d" % int(((out["p_fwe"] <= 0.05) & out["mask"]).sum())]
+    if "tfce" in out:
+        for key, name in (("tfce", "tfce"), ("p_tfce_uncorrected", "p_tfce_unc"), ("p_tfce_fwe", "p_tfce_fwe")):
+            nifti.save(nifti.NiftiImage(out[key], affine), path_to_out + quantity + "_" + name + ".nii.gz")
+        np.savetxt(path_to_out + quantity + "_tfce_max_dist.txt", out["tfce_max_dist"])
+        o = out["tfce_options"]
+        lines += ["tfce: dh = %.6g, E = %g, H = %g, connectivity = %d" % (out["dh"], o["E"], o["H"], o["connectivity"]),
+                  "tfce_crit (0.95 quantile of the maximum TFCE): %.6f" % out["tfce_crit"],
+                  "voxels with p_tfce_fwe <= 0.05: %d" % int(((out["p_tfce_fwe"] <= 0.05) & out["mask"]).sum())]
+    if "cluster_extent" in out:
+        for key, name in (("cluster_extent", "cluster_extent"), ("p_cluster_fwe", "p_cluster_fwe")):
+            nifti.save(nifti.NiftiImage(out[key], affine), path_to_out + quantity + "_" + name + ".nii.gz")
+        lines += ["cluster extent: threshold = %.6g, connectivity = %d, cluster_crit (0.95 quantile of the maximum extent): %.6f, "
+                  "voxels with p_cluster_fwe <= 0.05: %d" % (out["cluster_threshold"], out["cluster_connectivity"], out["cluster_crit"],
+                                                            int(((out["p_cluster_fwe"] <= 0.05) & out["mask"]).sum()))]
     with open(path_to_out + quantity + "_group_report.txt", "w") as f:
         f.write("\n".join(lines) + "\n")
     return out

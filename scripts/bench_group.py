@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Timing of the voxel-wise permutation test (met2_group_perm_stats, group.randomise) on the device, written to profiles/group_bench.json:
     python3 scripts/bench_group.py [--perms 5000] [--voxels 250000] [--subjects 32] [--reps 5] [--numpy-candidates 32] [--out FILE]
+                                   [--tfce [--grid 96 112 96] [--numpy-seconds 60] [--device-only]]
 The case: two groups of subjects / 2 (r = 2 model columns), seeded normal data with a group difference in 1 % of the voxels, `perms`
 permutations drawn at random, one map.
   kernels     the launches of the whole set (ceil(perms / max_k) calls of the entry with t_ref and count, inputs resident on the device), between
@@ -13,6 +14,13 @@ permutations drawn at random, one map.
   numpy       the float64 restatement of the entry (tests/tools/group_numpy.py, the same loop) on this machine's 16 threads, the voxels split
               over the threads, for `numpy-candidates` candidates; the time for the whole set is that time scaled by perms / candidates (the
               work is linear in the candidates), and is marked as scaled.
+With --tfce the same case is placed on a grid (--grid 96 112 96: the voxels are an ellipsoid's, trimmed to `voxels`) and the test is the TFCE
+one (group.randomise(tfce=True): met2_group_perm_tfce in batches of at most 32 maps), written to profiles/group_tfce_bench.json:
+  randomise   end to end with tfce=True, and beside it the t-only call on the same data: the median of `reps` calls after a warm-up call
+  numpy       the restatement (tests/tools/tfce_numpy.py: scipy.ndimage.label per level) on 16 threads, one candidate per task, for as many
+              candidates as are finished within --numpy-seconds (60); the whole set is that rate scaled, and is marked as scaled
+  --device-only leaves the restatement out and makes one call: the form for a kernel trace of its own (rocprofv3 --kernel-trace --stats),
+              from which the stages' shares of the kernel time are read (gp_stats: t; tf_union, tf_count, tf_sum: the levels).
 A record, not a pass mark."""
 import argparse
 import importlib
@@ -33,6 +41,71 @@ FP64_VECTOR_PEAK = 78.6e12                                         # bench.py's 
 THREADS = 16
 
 
+def ellipsoid(grid, voxels):
+    """the indices of the `voxels` grid voxels nearest the centre in the grid's own ellipsoidal metric, ascending"""
+    axes = [(np.arange(m) - (m - 1) / 2.0) / (m / 2.0) for m in grid]
+    d = (axes[0][:, None, None] ** 2 + axes[1][None, :, None] ** 2 + axes[2][None, None, :] ** 2).ravel()
+    return np.sort(np.argpartition(d, voxels - 1)[:voxels])
+
+
+def tfce_case(a, group, gn):
+    import tfce_numpy as tn
+    n, V, P, grid = a.subjects, a.voxels, a.perms, tuple(a.grid)
+    at = ellipsoid(grid, V)
+    g = np.repeat([1.0, 0.0], n // 2)
+    X, c = np.stack([g, 1.0 - g], axis=1), np.array([1.0, -1.0])
+    rng = np.random.default_rng(0)
+    Y = rng.standard_normal((n, V))
+    centre = np.argsort(np.abs(at - at[V // 2]))[: V // 100]      # 1 % of the voxels around the middle one (runs of a few rows: small blobs)
+    Y[: n // 2, centre] += 1.5
+    kw = dict(n_perm=P, seed=0)
+    sp = dict(tfce=True, grid=grid, at=at)
+    out = group.randomise(Y, X, c, **kw, **sp)                      # warm-up
+    if a.device_only:
+        print(json.dumps({"perms": out["n_perm"], "dh": out["dh"], "tfce_crit": out["tfce_crit"]}))
+        return
+    t_s, tfce_s = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        group.randomise(Y, X, c, **kw)
+        t1 = time.perf_counter()
+        out = group.randomise(Y, X, c, **kw, **sp)
+        t_s.append(t1 - t0)
+        tfce_s.append(time.perf_counter() - t1)
+    box, at_box = group._crop(grid, at)
+    K = group._batch_for(box, V, 2 ** 30, out["n_perm"])
+
+    perms = group.permutation_set(X, c, P, 0, "permute")
+    W, _ = group.weights(X, c, perms)
+    Yr, s0 = group.residualise(Y, X, c)
+    t_start, done = time.perf_counter(), []
+
+    def one(k):
+        if time.perf_counter() - t_start > a.numpy_seconds:
+            return None
+        return float(tn.perm_spatial(Yr, s0, W[k:k + 1], box, at_box, "tfce", out["dh"], 0.5, 2.0, 6)["kmax"][0])
+    with ThreadPoolExecutor(THREADS) as pool:
+        done = [x for x in pool.map(one, range(min(W.shape[0], 4096))) if x is not None]
+        numpy_s = time.perf_counter() - t_start
+    same = bool(np.array_equal(np.array(done), out["tfce_max_dist"][:len(done)]))
+    rec = {"case": {"perms": out["n_perm"], "voxels": V, "subjects": n, "grid": list(grid), "cropped_grid": list(box), "maps_per_launch": K,
+                    "launches": 1 + (out["n_perm"] + K - 1) // K, "dh": out["dh"], "E": 0.5, "H": 2.0, "connectivity": 6},
+           "randomise_tfce": {"seconds": float(np.median(tfce_s)), "all_s": tfce_s, "tfce_crit": out["tfce_crit"],
+                              "voxels_p_tfce_fwe_le_0.05": int((out["p_tfce_fwe"] <= 0.05).sum()),
+                              "voxels_p_fwe_le_0.05": int((out["p_fwe"] <= 0.05).sum())},
+           "randomise_t_only": {"seconds": float(np.median(t_s)), "all_s": t_s},
+           "numpy_float64": {"threads": THREADS, "candidates_timed": len(done), "seconds_timed": numpy_s,
+                             "seconds_whole_set_scaled": numpy_s * out["n_perm"] / max(len(done), 1), "scaled": True,
+                             "tfce_max_equal_to_device": same},
+           "device": torch.cuda.get_device_name(0), "reps": a.reps}
+    path = a.out if a.out != os.path.join(ROOT, "profiles", "group_bench.json") else os.path.join(ROOT, "profiles", "group_tfce_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--perms", type=int, default=5000)
@@ -41,10 +114,16 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--numpy-candidates", type=int, default=32)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "group_bench.json"))
+    ap.add_argument("--tfce", action="store_true")
+    ap.add_argument("--grid", type=int, nargs=3, default=[96, 112, 96])
+    ap.add_argument("--numpy-seconds", type=float, default=60.0)
+    ap.add_argument("--device-only", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "the benchmark needs a GPU"
     group = importlib.import_module(PKG + ".group")
     import group_numpy as gn
+    if a.tfce:
+        return tfce_case(a, group, gn)
     n, V, P = a.subjects, a.voxels, a.perms
     g = np.repeat([1.0, 0.0], n // 2)
     X, c = np.stack([g, 1.0 - g], axis=1), np.array([1.0, -1.0])
