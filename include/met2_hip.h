@@ -418,7 +418,9 @@ int met2_eval_voxel_metrics(met2_plan *plan, int64_t n, const double *fsol, cons
  * met2_eval_voxel_metrics), truth [MET2_EVAL_NTRUTH][n] (of met2_synth_two_lobe), lam [n] or NULL (zeros), fie [n] or NULL: the fIE array
  * GMARE's second term reads (NULL: per_voxel's own; the reference reads its NNLS array for every method, :107).  out [MET2_EVAL_NAGG] = MAE,
  * MARE, RMSE, cRMSE, RMSRE, U95, MBE, R, GMARE, MAE-k, MAE-S, MJSD-S, MWD-S (the columns of table_errors.txt), mean and std (ddof 0) of
- * lambda.  One workgroup in a fixed reduction order: the same inputs give the same bits.  Runs on the current device; asynchronous. */
+ * lambda.  Every aggregate is what its formula gives in IEEE arithmetic, NaN and Inf included: R is clamped to [-1, 1] only when it is a
+ * number, so a constant column, n = 1 or a NaN voxel gives R = NaN (0/0), as scipy.stats.pearsonr does.  One workgroup in a fixed
+ * reduction order: the same inputs give the same bits.  Runs on the current device; asynchronous. */
 #define MET2_EVAL_NAGG 15
 int met2_eval_reduce(int64_t n, const double *per_voxel, const double *truth, const double *lam, const double *fie, double *out, void *stream);
 

@@ -335,7 +335,9 @@ __global__ __launch_bounds__(RED_THREADS) void eval_reduce_kernel(ReduceArgs A)
     block_reduce(buf, RED_S2, tid);
     if (tid == 0) {
         const double rmse = sqrt(m[3]), sdd = sqrt(buf[1][0] / dn);
-        const double R = fmax(fmin(buf[2][0] / (sqrt(buf[3][0]) * sqrt(buf[4][0])), 1.0), -1.0);
+        // fmin / fmax return the operand that is a number: a NaN quotient (a constant column, n = 1, a NaN voxel) stays NaN, as pearsonr's does
+        const double q = buf[2][0] / (sqrt(buf[3][0]) * sqrt(buf[4][0]));
+        const double R = q != q ? q : fmax(fmin(q, 1.0), -1.0);
         const double o[MET2_EVAL_NAGG] = {m[1], m[2], rmse, sqrt(buf[0][0] / dn), sqrt(m[4]), 1.96 * sqrt(sdd * sdd + rmse * rmse), m[0], R,
                                           m[2] + m[7] + m[8] + m[9] + m[10], m[11], m[12], m[13], m[14], ml, sqrt(buf[5][0] / dn)};
         for (int k = 0; k < MET2_EVAL_NAGG; ++k) A.out[k] = o[k];

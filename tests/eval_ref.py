@@ -13,12 +13,18 @@ EPS = 1.0e-50
 T2GRID, DT2GRID = np.linspace(1.0, 300.0, 1000, retstep=True)
 
 
+def _real(a):
+    """a as a floating array: long double stays long double (the GPU tests run this module in np.longdouble), everything else float64"""
+    a = np.asarray(a)
+    return a if a.dtype == np.longdouble else a.astype(np.float64)
+
+
 def count_peaks(x):
     """scipy.signal.find_peaks(x, height=1e-5 * max(x)) -> number of peaks: maximal runs of equal values [a, b] with a >= 1, b + 1 <= n - 1,
     x[a-1] < x[a] and x[b+1] < x[a] (plateaus count once, endpoints never), kept when x[a] >= 1e-5 max(x) (exact comparisons)."""
-    x = np.asarray(x, dtype=np.float64)
+    x = _real(x)
     n = x.shape[0]
-    hmin = 1e-5 * np.max(x)
+    hmin = x.dtype.type(1e-5) * np.max(x)
     cnt = 0
     for a in range(1, n - 1):
         if not x[a - 1] < x[a]:
@@ -40,8 +46,8 @@ def rel_entr(x, y):
 
 def jensenshannon(p, q):
     """scipy.spatial.distance.jensenshannon(p, q): both renormalised, natural log, sqrt of the divergence, 0 log 0 = 0"""
-    p = np.asarray(p, dtype=np.float64) / np.sum(p)
-    q = np.asarray(q, dtype=np.float64) / np.sum(q)
+    p = _real(p) / np.sum(p)
+    q = _real(q) / np.sum(q)
     m = (p + q) / 2.0
     return np.sqrt((np.sum(rel_entr(p, m)) + np.sum(rel_entr(q, m))) / 2.0)
 

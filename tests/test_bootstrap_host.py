@@ -3,32 +3,19 @@ against Random123's known-answer vectors (the GPU tests compare the device's rep
 checks of the C entries and of Met2Plan.fit_bootstrap, which run before anything touches a device."""
 import ctypes as C
 import importlib
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
+from conftest import ROOT
+
 PKG = "multicomponent-t2-toolbox_amd"
 
-M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
-W0, W1 = np.uint32(0x9E3779B9), np.uint32(0xBB67AE85)
-
-
-def philox4x32_10(ctr, key):
-    """ctr: 4 uint32 arrays (broadcastable), key: 2 uint32 arrays -> the 4 output words (uint32 arrays)."""
-    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint32) for c in ctr)
-    k0, k1 = (np.asarray(k, dtype=np.uint32) for k in key)
-    with np.errstate(over="ignore"):
-        for r in range(10):
-            if r:
-                k0 = (k0 + W0).astype(np.uint32)
-                k1 = (k1 + W1).astype(np.uint32)
-            p0 = M0 * c0.astype(np.uint64)
-            p1 = M1 * c2.astype(np.uint64)
-            n0 = (p1 >> np.uint64(32)).astype(np.uint32) ^ c1 ^ k0
-            n2 = (p0 >> np.uint64(32)).astype(np.uint32) ^ c3 ^ k1
-            c0, c1, c2, c3 = n0, p1.astype(np.uint32), n2, p0.astype(np.uint32)
-    return c0, c1, c2, c3
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+from philox_numpy import philox4x32_10                             # noqa: E402  (moved there; shared with the Monte-Carlo study's tests)
 
 
 def replicates_np(center, sigma, vid, n_rep, seed):

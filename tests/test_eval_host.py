@@ -1,15 +1,23 @@
 """CPU tests of the Monte-Carlo study (met2_amd.evaluate): the numpy restatement tests/eval_ref.py against SciPy on adversarial spectra
-(the GPU kernels are checked against eval_ref in test_gpu_evaluate.py), and the table writer against the reference's committed tables."""
+(the GPU kernels are checked against eval_ref in test_gpu_evaluate.py and test_gpu_eval_kernels.py), the table writer against the reference's
+committed tables, and the preconditions of the cases test_gpu_eval_kernels.py shows the kernels (tests/tools/eval_cases.py): exact sums, the
+threshold tie and its twin, the NaN patterns, the conditioning gate, the reduction's degenerate columns, the bin edge on a fine grid point."""
 import hashlib
 import importlib
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
 
 import eval_ref
-from conftest import GOLDEN
+from conftest import GOLDEN, ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import eval_cases as ec                                             # noqa: E402
+import philox_numpy as ph                                           # noqa: E402
+from eval_cases import adversarial_spectra                          # noqa: E402  (moved there; the GPU tests of the kernels share them)
 
 PKG = "multicomponent-t2-toolbox_amd"
 
@@ -17,24 +25,6 @@ PKG = "multicomponent-t2-toolbox_amd"
 def fixture():
     with open(os.path.join(GOLDEN, "eval_tables_paper.json")) as f:
         return json.load(f)
-
-
-def adversarial_spectra():
-    rng = np.random.default_rng(5)
-    xs = [
-        np.array([0.0, 1.0, 1.0, 1.0, 0.0, 2.0, 2.0, 0.5, 0.0, 0.0]),          # plateaus
-        np.array([0.0, 0.0, 0.0, 3.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]),          # a single non-zero
-        np.array([5.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 4.0]),          # endpoints only: never peaks
-        np.array([0.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0]),          # a plateau that runs into the last sample
-        np.array([0.0, 1e-5, 0.0, 1.0, 0.0, 0.99999e-5, 0.0, 0.0, 2e-5, 1e-5]), # ties at the height threshold 1e-5 max
-        np.array([0.0, 2.0, 1.0, 2.0, 1.0, 2.0, 2.0, 1.0, 3.0, 3.0]),
-    ]
-    for _ in range(6):                                                         # sparse NNLS-like spectra with runs of exact zeros
-        x = np.where(rng.random(60) < 0.2, rng.random(60), 0.0)
-        x[rng.integers(0, 60, 3)] = 0.5                                        # exact ties
-        xs.append(x)
-    xs.append(np.exp(-0.5 * ((np.arange(120) - 40.0) / 6.0) ** 2))           # smooth, 120 bins
-    return xs
 
 
 def test_peaks_match_scipy():
@@ -159,3 +149,168 @@ def test_study_grids_and_params():
         ev.synth_params((50, 150), bogus=(1, 2))
     with pytest.raises(ValueError):
         ev.evaluate_methods(methods=("11. nonsense",))
+
+
+# ---------------------------------------------------------------- the preconditions of tests/test_gpu_eval_kernels.py, checked without a device
+
+LD = np.longdouble
+GATE = 1e-13
+
+
+def metrics_ref(case, T2s, cuts=(40.0, 200.0), dtype=np.float64):
+    """eval_ref.voxel_metrics in dtype.  The peak count is a matter of exact float64 comparisons (a tie at the height threshold is no tie in
+    long double), so it is always the float64 restatement's."""
+    with np.errstate(all="ignore"):
+        m = eval_ref.voxel_metrics(case[2].astype(dtype), case[3].astype(dtype), T2s.astype(dtype), *cuts)
+        if dtype != np.float64:
+            m[5] = eval_ref.count_peaks(case[2] / np.sum(case[2]))
+    return m
+
+
+def test_philox_restatement_and_uniform_rules():
+    ph.check_known_answers()
+    top = 0xFFFFFFFF
+    assert ph.u01_co(0, 0) == 0.0 and ph.u01_co(top, top) == 1.0 - 2.0 ** -53
+    assert ph.u01_oc(0, 0) == 2.0 ** -53 and ph.u01_oc(top, top) == 1.0
+    assert ph.u01_co(1 << 5, 0) == 2.0 ** -27 and ph.u01_co(0, 1 << 6) == 2.0 ** -53 and ph.u01_co(31, 63) == 0.0
+    assert ph.u01_co(top, 12345, LD) == ph.u01_co(top, 12345) and ph.u01_oc(top, 12345, LD) == ph.u01_oc(top, 12345)
+    lo, hi = ph.halves([0, 2 ** 31, 2 ** 32 + 5, 2 ** 63 + 1, -1, 2 ** 32 - 3])
+    assert lo.tolist() == [0, 2 ** 31, 5, 1, top, top - 2] and hi.tolist() == [0, 0, 1, 2 ** 31, top, 0]
+    # voxel_words is philox4x32_10 at counter (c0, stream, lo32(id), hi32(id)) under key (lo32(seed), hi32(seed))
+    w = ph.voxel_words(-1, [2 ** 32 + 7], [3], 2)
+    assert ph.words(*(x[0, 0] for x in w)) == ph.words(*ph.philox4x32_10([3, 2, 7, 1], [top, top]))
+
+
+def test_exact_sum_cases_are_exact_and_have_their_structure():
+    signal = pytest.importorskip("scipy.signal")
+    for n in ec.N_T2:
+        T2s = ec.t2_grid(n)
+        names = {}
+        for name, f in ec.exact_spectra(n):
+            for cuts in ((40.0, 200.0), ec.other_cuts(T2s)):
+                km, x = ec.assert_exact_sums(f, T2s, *cuts)
+                m = eval_ref.voxel_metrics(f, ec.default_dist2(n), T2s, *cuts)
+                assert m[4] == km and m[0] == np.sum(x[T2s <= cuts[0]]) and m[1] == np.sum(x[(T2s > cuts[0]) & (T2s <= cuts[1])])
+            peaks, _ = signal.find_peaks(x, height=1e-5 * np.max(x))
+            assert eval_ref.count_peaks(x) == peaks.size, (n, name)
+            names[name] = peaks.size
+        assert len(names) >= (3 if n == 3 else 20), (n, len(names))
+        if n >= 10:
+            want = {"plateau_from_1": 1, "plateau_from_1_long": 1, "plateau_into_last": 0, "plateau_into_last_long": 0, "peak_at_n-2": 1,
+                    "peak_at_n-2_and_1": 2, "endpoints_only": 0, "plateaus@0": 2, "single@0": 1, "endpoints@0": 1,
+                    "plateau_to_end@%d" % (n - 10): 0, "plateau_to_end@0": 1, "threshold_ties@0": 4, "zigzag@%d" % (n - 10): 3}
+            if n >= 65:
+                want["plateau_61..64"] = 0 if n == 65 else 1
+            if n >= 66:
+                want.update({"plateau_62..65": 1, "plateau_63..64": 1, "step_up_63_64": 1, "plateau_1..64": 1})
+            if n >= 68:
+                assert any(k.endswith("@58") for k in names)        # 58..67 straddles 62..66
+            for k, v in want.items():
+                assert names[k] == v, (n, k, names[k], v)
+        else:
+            assert set(np.unique(list(names.values()))) >= ({0, 1} if n < 5 else {0, 1, 2})
+
+
+def test_threshold_tie_and_its_twin():
+    signal = pytest.importorskip("scipy.signal")
+    assert 1e-5 * (ec.BIG / ec.TOTAL) == 1.0 / ec.TOTAL and 1e-5 * (2 * ec.BIG / (2 * ec.TOTAL)) == 2.0 / (2 * ec.TOTAL)
+    for tie, two, twin, npk in ((ec.TIE10, ec.TIE10_TWO, ec.TIE10_TWIN, 3), (ec.TIE5, ec.TIE5_TWO, ec.TIE5_TWIN, 2)):
+        for f, want in ((tie, npk), (two, npk), (twin, npk - 1)):
+            f = np.asarray(f, dtype=np.float64)
+            assert ec.is_pow2(float(f.sum()))
+            x = f / f.sum()
+            b = len(f) - 4 if len(f) == 10 else 3                  # the bin on (or one level under) the threshold
+            hmin = 1e-5 * np.max(x)
+            assert (x[b] == hmin) == (want == npk) and (want == npk or x[b] < hmin)
+            assert eval_ref.count_peaks(x) == want == signal.find_peaks(x, height=hmin)[0].size
+            # with hmin < x in place of hmin <= x the tie would lose that peak
+            strict = sum(1 for a in range(1, len(x) - 1) if x[a - 1] < x[a] > x[a + 1] and hmin < x[a])
+            assert strict == npk - 1
+
+
+def test_special_cases_have_the_nan_patterns_they_are_named_for():
+    for n in ec.N_T2:
+        T2s = ec.t2_grid(n)
+        got = {c[0]: metrics_ref(c, T2s) for c in [(nm, "special", f, d) for nm, f, d in ec.special_cases(n)]}
+        m = got["all_zero"]
+        assert np.all(np.isnan(m[[0, 1, 2, 3, 6, 7, 8]])) and m[4] == 0.0 and m[5] == 0.0
+        for k, m in got.items():
+            if k.startswith("inf@"):
+                f = dict((nm, f) for nm, f, _ in ec.special_cases(n))[k]
+                with np.errstate(all="ignore"):
+                    x = f / f.sum()
+                assert np.isinf(m[4]) and m[5] == 0.0 and np.isnan(x).sum() == 1 and np.all(x[~np.isnan(x)] == 0.0)
+            if k.startswith("nan@"):
+                assert np.isnan(m[4]) and m[5] == 0.0 and np.all(np.isnan(m[[0, 1, 6, 7, 8]]))
+            if k.startswith("dist2_equals_x"):
+                assert m[7] == 0.0 and m[8] == 0.0 and m[6] == 0.0
+            if k.startswith("dist2_zero"):
+                assert np.all(np.isfinite(m))
+        # a grid wholly above cut_ie: no bin in either compartment, the T2 means are 0 / 1e-50
+        m = eval_ref.voxel_metrics(np.arange(1.0, n + 1.0), ec.default_dist2(n), ec.grid_above_ie(n))
+        assert np.all(m[:4] == 0.0)
+
+
+def test_conditioning_gate():
+    """float64 numpy agrees with long double within 1e-13 on every finite value of every case (none is left out), and so does SciPy on the
+    jsd and wd of the well-conditioned ('float') cases: what the device is compared with is then known far below the device's bound"""
+    pytest.importorskip("scipy")
+    from scipy.spatial import distance
+    from scipy.stats import wasserstein_distance
+    assert np.finfo(LD).eps < 1e-18
+    worst = 0.0
+    for n in ec.N_T2:
+        T2s = ec.t2_grid(n)
+        for grid, cuts in ((T2s, (40.0, 200.0)), (T2s, ec.other_cuts(T2s)), (ec.grid_above_ie(n), (40.0, 200.0))):
+            for c in ec.voxel_cases(n):
+                ld, f64 = metrics_ref(c, grid, cuts, LD), metrics_ref(c, grid, cuts)
+                e = ec.rel_err(f64, ld)
+                assert e <= GATE, (n, c[0], e, f64, ld)
+                worst = max(worst, e)
+                if c[1] == "float" and grid is T2s and cuts == (40.0, 200.0):
+                    x = c[2] / np.sum(c[2])
+                    assert ec.rel_err([distance.jensenshannon(c[3], x), wasserstein_distance(c[3], x)], ld[7:9]) <= GATE, (n, c[0])
+    print("float64 against long double: %.3g" % worst)
+
+
+def test_reduce_reference_on_degenerate_columns():
+    stats = pytest.importorskip("scipy.stats")
+    nan_column = metrics_ref(("z", "special", np.zeros(8), ec.default_dist2(8)), ec.t2_grid(8))
+    assert np.isnan(nan_column[0]) and nan_column[4] == 0.0
+    for name, (pv, truth, lam, fie) in ec.degenerate_reduce_inputs(nan_column).items():
+        with np.errstate(all="ignore"):
+            r64 = eval_ref.reduce_metrics(pv, truth, lam, fie)
+            rld = eval_ref.reduce_metrics(pv.astype(LD), truth.astype(LD), lam.astype(LD), fie.astype(LD))
+        assert ec.rel_err(r64, rld) <= 1e-10, (name, r64, rld)
+        if name.startswith("constant") or name == "n1" or name.startswith("nan_voxel"):
+            assert np.isnan(r64[7]), (name, r64[7])               # R = 0/0 (or NaN): what pearsonr gives on a constant input
+        if name.startswith("constant"):
+            import warnings
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                assert np.isnan(stats.pearsonr(pv[0], truth[0])[0])
+        if name.startswith("T_is_0"):
+            assert np.isinf(r64[1]) and np.isinf(r64[4]) and np.isinf(r64[8])
+        if name.startswith("T_and_M_are_0"):
+            assert np.isnan(r64[1]) and np.isnan(r64[8])
+        if name.startswith("T_is_1"):
+            assert np.isinf(r64[8]) and np.isfinite(r64[1])
+        if name.startswith("nan_voxel"):
+            assert np.all(np.isnan(r64[[0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11, 12]])) and np.isfinite(r64[9]) and np.isfinite(r64[13])
+
+
+def test_midpoint_grid_puts_an_edge_on_a_fine_grid_point():
+    T2s, i, j = ec.midpoint_grid()
+    g = eval_ref.T2GRID[j]
+    assert T2s[i - 1] + (T2s[i] - T2s[i - 1]) / 2.0 == g           # the edge between bins i - 1 and i, as rebin and the kernel compute it
+    dist = np.zeros(1000)
+    dist[j] = 1.0
+    d2 = eval_ref.rebin(dist, T2s)
+    assert d2[i] == 1.0 and d2[i - 1] == 0.0                       # >= lo, < hi: the point belongs to the upper bin
+
+
+def test_sort_padding_cases_are_present():
+    # 128 bins sort without padding, 127 and 65 with NaN padding behind data that hold negative numbers, zeros and a NaN of their own
+    for n in (65, 127, 128):
+        kinds = {c[0] for c in ec.voxel_cases(n) if c[1] == "sort"}
+        assert {"sorted", "reversed", "ties", "negative", "signed_zeros", "nan_in_dist2", "x_all_equal"} <= kinds
