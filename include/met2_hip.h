@@ -1398,6 +1398,35 @@ int met2_group_limits(int32_t *max_n, int32_t *max_r, int32_t *max_k, int32_t *v
 int met2_group_perm_stats(int32_t device, int32_t n, int64_t n_vox, const double *Y, const double *s0, int32_t r, int32_t K, const double *W,
                           int32_t two_sided, const double *t_ref, double *t_first, double *kmax, uint32_t *count, void *stream);
 
+/* F-contrasts: the same test for a contrast matrix C [p][s] of rank s, 1 <= s <= r (an extension; additive, ABI stays 6).  The caller
+ * partitions the design into the effect X1 [n][s] and the nuisance Z with X1' Z = 0, residualises against Z (Y, s0 as above) and turns every
+ * candidate into r weight rows W[k][j] = P_k' q_j, q_1 .. q_r the orthonormal basis from the QR factorisation of [X1 Z], so that q_1 .. q_s
+ * span X1 (group.py: partition, weights_f).  There is no row 0: W [K][r][n].  scale = (n - r) / s.  For voxel v and candidate k:
+ *     g_j = sum_i W[k][j][i] Y[i][v]                 j = 1 .. r
+ *     qs  = g_1 g_1 + .. + g_s g_s;   q = qs + g_{s+1} g_{s+1} + .. + g_r g_r;   rss = s0[v] - q
+ *     F   = rss > 0 ? (scale qs) / rss : 0
+ *   the Freedman-Lane F of the full model against the nuisance: H_z y lies in the column space of Z, X1 is orthogonal to Z and a signed
+ *   permutation keeps the norm, so the extra sum of squares is |Q1' P_k Y|^2 = qs and the residual one s0 - q.  For s = 1, F = t^2 up to
+ *   rounding.
+ *   Order.  All arithmetic is fp64; no product is fused into a sum; every operation rounds once.  Each g_j is a sum from 0.0 over
+ *   i = 0, 1, .. n - 1: a <- a + W[k][j][i] Y[i][v].  q = g_1 g_1, then q <- q + g_j g_j for j = 2 .. r in ascending order; qs is the value q
+ *   holds after the term j = s -- a prefix of the same sum, no addition of its own.  rss = s0 - q; num = scale qs; F = num / rss, correctly
+ *   rounded.  So the bits of F(k, v) depend on W[k], Y[:, v], s0[v], s and scale alone, and numpy reproduces them in float64 with the same loop
+ *   (tests/tools/group_f_numpy.py).  rss <= 0 gives F = 0; an rss that is not a number (a NaN in Y or s0) gives an F that is not a number, which
+ *   the maximum passes over and which reaches no reference.
+ * met2_group_perm_fstats: Y, s0, K, stream as for met2_group_perm_stats; s and scale are the same for every candidate of the launch; f_ref,
+ *   f_first, kmax and count have the meaning of t_ref, t_first, kmax and count there, for F (kmax by the same integer atomic max on the same
+ *   key, -infinity when n_vox = 0 or every F is not a number; count[v] += #{k: F(k, v) >= f_ref[v]}, one owner per voxel; no floating-point
+ *   atomics, no scratch).  There is no two_sided: F does not see the sign (all weights negated give the same bits).
+ * met2_group_perm_ftfce: met2_group_perm_tfce with F(k, v) in the place of t(k, v): computed by met2_group_perm_fstats's own kernel code -- the
+ *   same bits -- scattered to the dense maps, then the same transform, gather, work space (met2_tfce_work_bytes with n_vox > 0) and late errors.
+ *   TFCE is taken on F itself, with the same E, H and dh; the extent's threshold is one on F.
+ * Limits.  1 <= s <= r <= MET2_GROUP_MAX_R, r < n <= MET2_GROUP_MAX_N, 1 <= K <= MET2_GROUP_MAX_K (MET2_TFCE_MAX_K for met2_group_perm_ftfce);
+ * MET2_E_UNSUPPORTED beyond the upper ends.  MET2_E_INVALID: s < 1 or s > r, scale not finite or <= 0, and every case of the t entries (no
+ * two_sided).  n_vox = 0 is valid for met2_group_perm_fstats.  Every check comes before any device work: the outputs are then untouched. */
+int met2_group_perm_fstats(int32_t device, int32_t n, int64_t n_vox, const double *Y, const double *s0, int32_t r, int32_t s, double scale,
+                           int32_t K, const double *W, const double *f_ref, double *f_first, double *kmax, uint32_t *count, void *stream);
+
 /* Threshold-free cluster enhancement (Smith & Nichols, NeuroImage 44:83-98, 2009) and cluster extent of statistic maps, and both as the
  * statistic of the permutation test above (an extension; additive, ABI stays 6).  Written from the paper and from the statement below.
  * A map t lies on a grid dims = {nx, ny, nz}, the voxel (x, y, z) at (x ny + y) nz + z, with a mask (uint8, non-zero = inside; NULL: all).
@@ -1448,6 +1477,11 @@ int met2_tfce(int32_t device, int32_t K, const int32_t dims[3], const double *ma
 int met2_group_perm_tfce(int32_t device, int32_t n, int64_t n_vox, const double *Y, const double *s0, int32_t r, int32_t K, const double *W,
                          const int32_t dims[3], const int32_t *at, int32_t mode, double dh, double E, double H, int32_t connectivity,
                          const double *ref, double *first, double *kmax, uint32_t *count, void *work, int64_t work_bytes, void *stream);
+/* the F counterpart (stated with met2_group_perm_fstats above) */
+int met2_group_perm_ftfce(int32_t device, int32_t n, int64_t n_vox, const double *Y, const double *s0, int32_t r, int32_t s, double scale,
+                          int32_t K, const double *W, const int32_t dims[3], const int32_t *at, int32_t mode, double dh, double E, double H,
+                          int32_t connectivity, const double *ref, double *first, double *kmax, uint32_t *count, void *work, int64_t work_bytes,
+                          void *stream);
 
 #ifdef __cplusplus
 }

@@ -52,8 +52,8 @@ SYMBOLS = ["met2_default_options", "met2_abi_version", "met2_device_count", "met
            "met2_register_joint_work_bytes", "met2_register_joint_cost",
            "met2_warp", "met2_warp_labels", "met2_warp_compose", "met2_warp_max_norm2", "met2_warp_work_bytes", "met2_warp_lncc_sums",
            "met2_warp_lncc_force", "met2_warp_lncc", "met2_warp_invert_step", "met2_warp_jacobian",
-           "met2_group_limits", "met2_group_perm_stats",
-           "met2_tfce_limits", "met2_tfce_work_bytes", "met2_tfce", "met2_group_perm_tfce"]
+           "met2_group_limits", "met2_group_perm_stats", "met2_group_perm_fstats",
+           "met2_tfce_limits", "met2_tfce_work_bytes", "met2_tfce", "met2_group_perm_tfce", "met2_group_perm_ftfce"]
 
 
 def lib():
@@ -190,6 +190,9 @@ def lib():
         L.met2_tfce.argtypes = [C.c_int32, C.c_int32, i3, vp, vp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, vp, vp, vp, C.c_int64, vp]
         L.met2_group_perm_tfce.argtypes = [C.c_int32, C.c_int32, C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, i3, vp, C.c_int32, C.c_double, C.c_double,
                                            C.c_double, C.c_int32, vp, vp, vp, vp, vp, C.c_int64, vp]
+        L.met2_group_perm_fstats.argtypes = [C.c_int32, C.c_int32, C.c_int64, vp, vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, vp, vp, vp, vp, vp, vp]
+        L.met2_group_perm_ftfce.argtypes = [C.c_int32, C.c_int32, C.c_int64, vp, vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, vp, i3, vp, C.c_int32,
+                                            C.c_double, C.c_double, C.c_double, C.c_int32, vp, vp, vp, vp, vp, C.c_int64, vp]
         L.met2_synth_two_lobe.argtypes = [vp, C.POINTER(SynthParams), C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp]
         L.met2_eval_voxel_metrics.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
         L.met2_eval_reduce.argtypes = [C.c_int64, vp, vp, vp, vp, vp, vp]

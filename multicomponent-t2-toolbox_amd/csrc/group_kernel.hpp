@@ -15,6 +15,9 @@
 //                              as much -- a maximum does not depend on the order, and no floating-point atomic is used.
 //                              SCATTER = true: t(k, v) goes to dense[k][at[v]] (a grid of dense_stride voxels per candidate; an index outside
 //                              the grid is passed over) and nothing else is written: no maximum, no count.
+//   gp_fstats_kernel<R, KB, SCATTER>
+//                              the F statistic of an F-contrast (met2_group_perm_fstats, met2_group_perm_ftfce): the same structure with R = r
+//                              rows per candidate (no row 0) and both finishes; stated with the kernel below.  KB = 8 up to r = 4, 4 beyond.
 //   gp_key_kernel              writes the key of -infinity into kmax before, and turns the keys into doubles in place after: no scratch
 // A candidate beyond K in the last group has zero weights and is left out of every output; a thread beyond n_vox reads nothing and writes nothing.
 // The including unit is compiled without contraction; every loop is bounded by a shape or a compile-time constant.
@@ -157,6 +160,126 @@ void gp_launch_r(int r, int64_t n_vox, int n, int K, const double *Y, const doub
 {
     switch (r) {
 #define GP_CASE(R) case R: gp_launch<R + 1, SCATTER>(n_vox, n, K, Y, s0, W, two_sided, t_ref, t_first, kmax, count, at, dense_stride, dense, st); break
+        GP_CASE(1); GP_CASE(2); GP_CASE(3); GP_CASE(4); GP_CASE(5); GP_CASE(6); GP_CASE(7); GP_CASE(8);
+#undef GP_CASE
+    }
+}
+
+// The F statistic over the first s of r orthonormal rows (met2_group_perm_fstats, met2_group_perm_ftfce): gp_stats_kernel's structure with R = r
+// rows per candidate (there is no row 0), W [K][R][n].  s and scale are wave-uniform run-time arguments; the prefix qs of the sum of squares is
+// taken by a compare on the compile-time row index inside the unrolled loop, so it costs no addition and no register is indexed at run time.
+// An rss that is not a number gives an F that is not a number (the maximum passes it over); rss <= 0 gives 0.
+template <int R, int KB, bool SCATTER>
+__global__ void __launch_bounds__(GP_TILE) gp_fstats_kernel(int n, int64_t n_vox, const double *__restrict__ Y, const double *__restrict__ s0, int K,
+                                                            const double *__restrict__ W, int s, double scale, const double *__restrict__ f_ref,
+                                                            double *__restrict__ f_first, unsigned long long *__restrict__ kmax,
+                                                            uint32_t *__restrict__ count, const int32_t *__restrict__ at, int64_t dense_stride,
+                                                            double *__restrict__ dense)
+{
+    constexpr int ROWS = KB * R;
+    extern __shared__ double gp_lds[];
+    double *wt = gp_lds;                                           // [n][ROWS]: the group's weights, subject-major
+    double *wmax = gp_lds + (size_t)n * ROWS;                      // [GP_WAVES][KB]: the waves' maxima
+    const int64_t v = (int64_t)blockIdx.x * GP_TILE + threadIdx.x;
+    const bool live = v < n_vox;
+    const double *y = Y + (live ? v : 0);
+    const double sv = live ? s0[v] : 0.0;
+    const double ref = (f_ref && live) ? f_ref[v] : 0.0;
+    int64_t cell = -1;                                             // SCATTER: the voxel's place in a dense map
+    if constexpr (SCATTER) {
+        if (live) cell = at[v];
+        if (cell >= dense_stride) cell = -1;
+    }
+    uint32_t cnt = 0;
+    for (int k0 = 0; k0 < K; k0 += KB) {
+        __syncthreads();                                           // the previous group's readers of wt and wmax are done
+        for (int e = threadIdx.x; e < ROWS * n; e += GP_TILE) {
+            const int row = e / n, i = e - row * n;
+            wt[i * ROWS + row] = k0 + row / R < K ? W[((int64_t)k0 * R + row) * n + i] : 0.0;
+        }
+        __syncthreads();
+        double acc[KB][R];
+#pragma unroll
+        for (int c = 0; c < KB; ++c)
+#pragma unroll
+            for (int j = 0; j < R; ++j) acc[c][j] = 0.0;
+        double y_next = live ? y[0] : 0.0;
+#pragma unroll 1
+        for (int i = 0; i < n; ++i) {                              // not unrolled, as in gp_stats_kernel
+            const double yi = y_next;
+            y_next = live && i + 1 < n ? y[(int64_t)(i + 1) * n_vox] : 0.0;
+            const double *w = wt + i * ROWS;
+#pragma unroll
+            for (int c = 0; c < KB; ++c)
+#pragma unroll
+                for (int j = 0; j < R; ++j) acc[c][j] = rn_add(acc[c][j], rn_mul(w[c * R + j], yi));
+        }
+#pragma unroll
+        for (int c = 0; c < KB; ++c) {
+            double q = rn_mul(acc[c][0], acc[c][0]);
+            double qs = q;                                         // the value q holds after the term j = s (1-based)
+#pragma unroll
+            for (int j = 1; j < R; ++j) {
+                q = rn_add(q, rn_mul(acc[c][j], acc[c][j]));
+                if (j < s) qs = q;
+            }
+            const double rss = rn_sub(sv, q);
+            const double num = rn_mul(scale, qs);
+            const double f = rss <= 0.0 ? 0.0 : num / rss;
+            const bool mine = live && k0 + c < K;
+            if constexpr (SCATTER) {
+                if (mine && cell >= 0) dense[(int64_t)(k0 + c) * dense_stride + cell] = f;
+            } else {
+                if (mine) {
+                    if (f_ref && f >= ref) ++cnt;
+                    if (f_first && k0 + c == 0) f_first[v] = f;
+                }
+                double m = mine && f == f ? f : -INFINITY;         // a statistic that is not a number is passed over
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const double other = __shfl_xor(m, o);
+                    if (other > m) m = other;
+                }
+                if ((threadIdx.x & 63) == 0) wmax[(threadIdx.x >> 6) * KB + c] = m;
+            }
+        }
+        if constexpr (!SCATTER) {
+            __syncthreads();
+            if ((int)threadIdx.x < KB && k0 + (int)threadIdx.x < K) {
+                double m = wmax[threadIdx.x];
+#pragma unroll
+                for (int wv = 1; wv < GP_WAVES; ++wv)
+                    if (wmax[wv * KB + threadIdx.x] > m) m = wmax[wv * KB + threadIdx.x];
+                const unsigned long long key = gp_key((unsigned long long)__double_as_longlong(m));
+                unsigned long long *dst = kmax + k0 + threadIdx.x;
+                if (key > __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(dst, key);
+            }
+        }
+    }
+    if constexpr (!SCATTER)
+        if (f_ref && live) count[v] += cnt;                        // this thread owns the voxel
+}
+
+#define GP_F_KB(R) ((R) <= 4 ? 8 : 4)      // candidates per group of the F kernel: 8 .. 32 sums up to r = 4, 20 .. 32 beyond (tests stand on it)
+
+template <int R, bool SCATTER>
+void gp_flaunch(int64_t n_vox, int n, int K, const double *Y, const double *s0, const double *W, int s, double scale, const double *f_ref,
+                double *f_first, double *kmax, uint32_t *count, const int32_t *at, int64_t dense_stride, double *dense, hipStream_t st)
+{
+    constexpr int KB = GP_F_KB(R);
+    const size_t lds = ((size_t)n * KB * R + GP_WAVES * KB) * sizeof(double);           // <= 128 * 32 * 8 + 256 = 33 024 bytes
+    const unsigned blocks = (unsigned)((n_vox + GP_TILE - 1) / GP_TILE);
+    hipLaunchKernelGGL((gp_fstats_kernel<R, KB, SCATTER>), dim3(blocks), dim3(GP_TILE), lds, st, n, n_vox, Y, s0, K, W, s, scale, f_ref, f_first,
+                       (unsigned long long *)kmax, count, at, dense_stride, dense);
+}
+
+// the F launch for r = 1 .. MET2_GROUP_MAX_R model columns (the caller has checked the range, and 1 <= s <= r)
+template <bool SCATTER>
+void gp_flaunch_r(int r, int64_t n_vox, int n, int K, const double *Y, const double *s0, const double *W, int s, double scale, const double *f_ref,
+                  double *f_first, double *kmax, uint32_t *count, const int32_t *at, int64_t dense_stride, double *dense, hipStream_t st)
+{
+    switch (r) {
+#define GP_CASE(R) case R: gp_flaunch<R, SCATTER>(n_vox, n, K, Y, s0, W, s, scale, f_ref, f_first, kmax, count, at, dense_stride, dense, st); break
         GP_CASE(1); GP_CASE(2); GP_CASE(3); GP_CASE(4); GP_CASE(5); GP_CASE(6); GP_CASE(7); GP_CASE(8);
 #undef GP_CASE
     }

@@ -1,6 +1,7 @@
 """Voxel-wise group statistics with permutation inference (csrc/met2_group.hip; include/met2_hip.h states the entry's contract).
 
-A general linear model Y = X beta + e over n subjects, a t-contrast c, and the permutation distribution of the t statistic at every voxel:
+A general linear model Y = X beta + e over n subjects, a t-contrast c (or an F-contrast: several at once, below), and the permutation
+distribution of the statistic at every voxel:
 uncorrected p-values from the voxel's own distribution, family-wise-error-corrected ones from the distribution of the maximum over the voxels
 (Winkler et al., NeuroImage 92:381-397, 2014).  One form covers one-sample sign flipping, the permutation of group labels and the
 Freedman-Lane scheme with nuisance regressors:
@@ -27,7 +28,13 @@ every permutation; a level holds the voxels with t >= h (not >); a map is follow
 default dh to 10.24 times the observed maximum, and treated above that as if it stopped there -- three places where FSL's randomise -T may
 differ.  One-sided only: on |t| a positive and a negative blob would fuse into one cluster, so test c and -c.
 
-Parity with FSL randomise (-T and -c included) is unpinned: FSL was not available.  Not provided: cluster mass, F-contrasts, exchangeability
+F-contrasts (randomise(f_contrast=[s, p]); met2_group_perm_fstats, met2_group_perm_ftfce): partition, residualise and permutation_set take a
+contrast matrix C [p, s] of rank s and give x1 [n, s]; weights_f gives W [P][r][n], rows P_k' q_j of the QR basis of [x1 Z], whose first s
+span x1.  F = ((n - r) / s) qs / (s0 - q) with qs the sum of the first s squared sums and q of all r: the Freedman-Lane F of the full model
+against the nuisance, by the argument above with |Q1' P_k Yr|^2 in the place of b^2.  perm_fstats and perm_ftfce are the entries on arrays.
+TFCE and the cluster extent are taken on F itself, with the same E, H and dh rule.
+
+Parity with FSL randomise (-T, -c and -f included) is unpinned: FSL was not available.  Not provided: cluster mass, exchangeability
 blocks, variance smoothing, several devices, 2-D connectivity."""
 import collections
 import ctypes as C
@@ -55,28 +62,33 @@ def _design(X, c):
     X = np.asarray(X, dtype=np.float64)
     if X.ndim == 1:
         X = X[:, None]
-    c = np.asarray(c, dtype=np.float64).reshape(-1, 1)
+    c = np.asarray(c, dtype=np.float64)
+    if X.ndim != 2 or c.ndim != 2 or c.shape[0] != X.shape[1]:     # a t-contrast of p entries in any shape; a matrix is [p, s]
+        c = c.reshape(-1, 1)
     if X.ndim != 2 or c.shape[0] != X.shape[1] or not (np.isfinite(X).all() and np.isfinite(c).all()):
-        raise ValueError("X must be a finite [n, p] design and c a finite t-contrast of p entries")
+        raise ValueError("X must be a finite [n, p] design and c a finite t-contrast of p entries or a contrast matrix [p, s]")
     if not c.any():
         raise ValueError("the contrast is zero")
+    if c.shape[1] > c.shape[0] or np.linalg.matrix_rank(c) < c.shape[1]:
+        raise ValueError("the contrast matrix is rank deficient: its %d columns must be linearly independent (s <= p)" % c.shape[1])
     if X.shape[0] <= X.shape[1] or np.linalg.matrix_rank(X) < X.shape[1]:
         raise ValueError("the design is rank deficient or leaves no degree of freedom: drop the redundant columns")
     return X, c
 
 
 def partition(X, c):
-    """The partition of a design X [n, p] and a t-contrast c [p] into the effect of interest x1 [n, 1] and the nuisance Z [n, p - 1] with
-    x1' Z = 0 (Winkler et al. 2014, appendix; Beckmann's form).  With D = (X'X)^-1 and Cu an orthonormal basis of null(c'):
-    x1 = X D c (c'Dc)^-1, Cv = Cu - c (c'Dc)^-1 c' D Cu, Z = X D Cv (Cv'DCv)^-1.  A rank-deficient X is refused."""
+    """The partition of a design X [n, p] and a t-contrast c [p] (or a contrast matrix C [p, s] of rank s: an F-contrast) into the effect of
+    interest x1 [n, s] and the nuisance Z [n, p - s] with x1' Z = 0 (Winkler et al. 2014, appendix; Beckmann's form).  With D = (X'X)^-1 and
+    Cu an orthonormal basis of null(c'): x1 = X D c (c'Dc)^-1, Cv = Cu - c (c'Dc)^-1 c' D Cu, Z = X D Cv (Cv'DCv)^-1.  A rank-deficient X
+    or C is refused.  A 1-D c and a [p, 1] column give the same bits."""
     X, c = _design(X, c)
-    p = X.shape[1]
+    p, s = X.shape[1], c.shape[1]
     D = np.linalg.inv(X.T @ X)
     cdc = np.linalg.inv(c.T @ D @ c)
     x1 = X @ D @ c @ cdc
-    if p == 1:
+    if p == s:
         return x1, np.zeros((X.shape[0], 0))
-    Cu = np.linalg.svd(c, full_matrices=True)[0][:, 1:]            # the left singular vectors beyond the first span null(c')
+    Cu = np.linalg.svd(c, full_matrices=True)[0][:, s:]            # the left singular vectors beyond the first s span null(c')
     Cv = Cu - c @ cdc @ c.T @ D @ Cu
     Z = X @ D @ Cv @ np.linalg.inv(Cv.T @ D @ Cv)
     return x1, Z
@@ -95,8 +107,12 @@ def residualise(Y, X, c):
 # ---------------------------------------------------------------- the permutations
 
 def _labels(x1):
-    """equal entries of x1 (to 1e-10 of its largest) get one label"""
-    x = np.asarray(x1, dtype=np.float64).ravel()
+    """equal entries of x1 (to 1e-10 of its largest) get one label; of an x1 with several columns, equal rows"""
+    x = np.asarray(x1, dtype=np.float64)
+    if x.ndim == 2 and x.shape[1] > 1:
+        scale = np.abs(x).max()
+        return np.unique(np.round(x / (scale if scale > 0 else 1.0), 10), axis=0, return_inverse=True)[1].ravel()
+    x = x.ravel()
     scale = np.abs(x).max()
     return np.unique(np.round(x / (scale if scale > 0 else 1.0), 10), return_inverse=True)[1].ravel()
 
@@ -134,7 +150,10 @@ def permutation_set(X, c, n_perm, seed=0, exchange="permute"):
     """At most n_perm signed permutations for the test of c in X -> PermSet(index [P, n], sign [P, n], exhaustive, exchange), with
     (P_k y)_i = sign[k, i] y[index[k, i]].  Row 0 is the identity.  Rows are unique by the x1 they produce (P_k' x1), so swaps within a group
     count once.  The set is exhaustive when the number of distinct arrangements -- n! / prod(group sizes!) for 'permute', 2^n for 'flip' (2^m
-    with m the entries of x1 that are not zero) -- is <= n_perm; otherwise it is drawn at random, deterministic in `seed`."""
+    with m the entries of x1 that are not zero) -- is <= n_perm; otherwise it is drawn at random, deterministic in `seed`.
+    c may be a contrast matrix [p, s] (an F-contrast): the labels are then those of the rows of x1 [n, s], by the same 1e-10 rule, and m counts
+    the subjects whose row of x1 is not zero.  Under 'flip' a sign pattern and its negation give the same F; both are kept, since the rule
+    stays "unique by P_k' x1": with the exhaustive set every F then appears twice, the identity's too, and no p-value changes."""
     if exchange not in EXCHANGES:
         raise ValueError("exchange must be one of %s" % (EXCHANGES,))
     if isinstance(n_perm, bool) or int(n_perm) != n_perm or int(n_perm) < 1:
@@ -145,7 +164,7 @@ def permutation_set(X, c, n_perm, seed=0, exchange="permute"):
     rng = np.random.default_rng(seed)
     ident = np.arange(n, dtype=np.int64)
     if exchange == "flip":
-        free = np.flatnonzero(x1.ravel() != 0.0)
+        free = np.flatnonzero((x1 != 0.0).any(axis=1))
         total = 2 ** free.size
         sign = np.ones((min(total, n_perm), n))
         if total <= n_perm:
@@ -211,6 +230,18 @@ def weights(X, c, perms):
     return np.ascontiguousarray(_transposed(perms, np.hstack([first, Q]))), dof
 
 
+def weights_f(X, C, perms):
+    """The weight rows of met2_group_perm_fstats for the contrast matrix C [p, s] and the signed permutations `perms` -> (W [P, r, n], s, dof)
+    with r = rank(X), dof = n - r: rows j = 1 .. r are P_k' q_j, q_j the orthonormal basis from np.linalg.qr([x1 Z]), so that q_1 .. q_s span
+    x1.  There is no row 0.  The entry's scale is dof / s."""
+    x1, Z = partition(X, C)
+    n, s = x1.shape
+    M = np.hstack([x1, Z])
+    if perms.index.shape[1] != n:
+        raise ValueError("the permutations are not of the design's %d subjects" % n)
+    return np.ascontiguousarray(_transposed(perms, np.linalg.qr(M)[0])), s, n - M.shape[1]
+
+
 # ---------------------------------------------------------------- the entry on arrays
 
 def _launch(dev, Y, s0, r, W, two_sided, t_ref, t_first, kmax, count):
@@ -250,6 +281,50 @@ def perm_stats(Y, s0, W, two_sided=False, t_ref=None, count=None, want_first=Fal
         cnt = put(np.zeros(V, dtype=np.int32) if count is None else np.ascontiguousarray(count, dtype=np.uint32).view(np.int32))
     first = torch.empty(V, dtype=torch.float64, device=dev) if want_first else None
     _launch(dev, put(Y), put(s0), W.shape[1] - 1, put(W), two_sided, ref, first, kmax, cnt)
+    return (kmax.cpu().numpy(), None if cnt is None else cnt.cpu().numpy().view(np.uint32), None if first is None else first.cpu().numpy())
+
+
+def _launch_f(dev, Y, s0, W, s, scale, f_ref, f_first, kmax, count):
+    """met2_group_perm_fstats on tensors that are already on `dev`, contiguous and of the right type (count: int32, the bits of uint32)"""
+    import torch
+    n, V = Y.shape
+    with torch.cuda.device(dev):
+        check(lib().met2_group_perm_fstats(dev.index or 0, n, V, Y.data_ptr(), s0.data_ptr(), W.shape[1], int(s), float(scale), W.shape[0],
+                                           W.data_ptr(), None if f_ref is None else f_ref.data_ptr(),
+                                           None if f_first is None else f_first.data_ptr(), kmax.data_ptr(),
+                                           None if count is None else count.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+
+
+def _check_fbatch(Y, s0, W, s, ref, count):
+    if len(Y.shape) != 2 or tuple(s0.shape) != (Y.shape[1],):
+        raise ValueError("Y must be [n, V] and s0 [V]")
+    if len(W.shape) != 3 or W.shape[2] != Y.shape[0] or W.shape[1] < 1 or W.shape[0] < 1:
+        raise ValueError("W must be [K, r, n] with K >= 1 and r >= 1")
+    if isinstance(s, bool) or int(s) != s or not 1 <= int(s) <= W.shape[1]:
+        raise ValueError("s must lie in 1 .. r = %d" % W.shape[1])
+    if ref is not None and tuple(ref.shape) != (Y.shape[1],):
+        raise ValueError("f_ref must be [V]")
+    if count is not None and tuple(count.shape) != (Y.shape[1],):
+        raise ValueError("count must be [V]")
+
+
+def perm_fstats(Y, s0, W, s, scale, f_ref=None, count=None, want_first=False, device=0):
+    """met2_group_perm_fstats on numpy arrays: Y [n, V], s0 [V], W [K, r, n] (weights_f), s the number of leading rows that span the effect,
+    scale = dof / s, f_ref [V] or None, count [V] uint32 to add to (zeros when None)
+    -> (kmax [K], count [V] uint32 or None without f_ref, f_first [V] or None without want_first)"""
+    import torch
+    dev = torch.device("cuda", device)
+    Y, s0, W = (np.ascontiguousarray(a, dtype=np.float64) for a in (Y, s0, W))
+    _check_fbatch(Y, s0, W, s, f_ref, count)
+    put = lambda a: torch.as_tensor(a, device=dev)
+    V = Y.shape[1]
+    kmax = torch.empty(W.shape[0], dtype=torch.float64, device=dev)
+    ref = None if f_ref is None else put(np.ascontiguousarray(f_ref, dtype=np.float64))
+    cnt = None
+    if ref is not None:
+        cnt = put(np.zeros(V, dtype=np.int32) if count is None else np.ascontiguousarray(count, dtype=np.uint32).view(np.int32))
+    first = torch.empty(V, dtype=torch.float64, device=dev) if want_first else None
+    _launch_f(dev, put(Y), put(s0), put(W), s, scale, ref, first, kmax, cnt)
     return (kmax.cpu().numpy(), None if cnt is None else cnt.cpu().numpy().view(np.uint32), None if first is None else first.cpu().numpy())
 
 
@@ -393,6 +468,42 @@ def perm_tfce(Y, s0, W, grid, at, mode="tfce", dh=None, E=0.5, H=2.0, connectivi
     return (kmax.cpu().numpy(), None if cnt is None else cnt.cpu().numpy().view(np.uint32), None if first is None else first.cpu().numpy())
 
 
+def _launch_fspatial(dev, Y, s0, W, s, scale, dims, at, mode, dh, E, H, connectivity, ref, first, kmax, count, work):
+    """met2_group_perm_ftfce on tensors that are already on `dev` (as _launch_spatial; W [K, r, n])"""
+    import torch
+    n, V = Y.shape
+    with torch.cuda.device(dev):
+        check(lib().met2_group_perm_ftfce(dev.index or 0, n, V, Y.data_ptr(), s0.data_ptr(), W.shape[1], int(s), float(scale), W.shape[0],
+                                          W.data_ptr(), (C.c_int32 * 3)(*dims), at.data_ptr(), MODES[mode], float(dh), float(E), float(H),
+                                          int(connectivity), None if ref is None else ref.data_ptr(), None if first is None else first.data_ptr(),
+                                          kmax.data_ptr(), None if count is None else count.data_ptr(), None if work is None else work.data_ptr(),
+                                          0 if work is None else work.numel(), torch.cuda.current_stream(dev).cuda_stream))
+
+
+def perm_ftfce(Y, s0, W, s, scale, grid, at, mode="tfce", dh=None, E=0.5, H=2.0, connectivity=6, ref=None, count=None, want_first=False, device=0):
+    """met2_group_perm_ftfce on numpy arrays: perm_fstats's Y, s0, W, s, scale; the rest as perm_tfce
+    -> (kmax [K], count or None without ref, first [V] or None without want_first)"""
+    import torch
+    if mode not in MODES:
+        raise ValueError("mode must be one of %s" % (tuple(MODES),))
+    dev = torch.device("cuda", device)
+    Y, s0, W = (np.ascontiguousarray(a, dtype=np.float64) for a in (Y, s0, W))
+    _check_fbatch(Y, s0, W, s, ref, count)
+    put = lambda a: torch.as_tensor(a, device=dev)
+    V = Y.shape[1]
+    at = np.ascontiguousarray(at, dtype=np.int32)
+    if at.shape != (V,):
+        raise ValueError("at must be [V]")
+    kmax = torch.empty(W.shape[0], dtype=torch.float64, device=dev)
+    rf = None if ref is None else put(np.ascontiguousarray(ref, dtype=np.float64))
+    cnt = None
+    if rf is not None:
+        cnt = put(np.zeros(V, dtype=np.int32) if count is None else np.ascontiguousarray(count, dtype=np.uint32).view(np.int32))
+    first = torch.empty(V, dtype=torch.float64, device=dev) if want_first else None
+    _launch_fspatial(dev, put(Y), put(s0), put(W), s, scale, _dims(grid), put(at), mode, dh, E, H, connectivity, rf, first, kmax, cnt, None)
+    return (kmax.cpu().numpy(), None if cnt is None else cnt.cpu().numpy().view(np.uint32), None if first is None else first.cpu().numpy())
+
+
 def _crop(grid, at):
     """the grid cut to the bounding box of the voxels `at` -> (grid, at) there"""
     if not at.size:
@@ -403,9 +514,18 @@ def _crop(grid, at):
     return box, np.ravel_multi_index((x - lo[0], y - lo[1], z - lo[2]), box).astype(np.int32)    # the order of the voxels is kept: still ascending
 
 
-def _spatial_test(Yk, sk, W, r, grid, at, mode, dh, E, H, connectivity, device, batch_spatial, work_bytes):
-    """the permutation distribution of one spatial statistic -> (observed [V], count [V] uint32, max_dist [P])"""
+def _spatial_test(Yk, sk, W, r, grid, at, mode, dh, E, H, connectivity, device, batch_spatial, work_bytes, fstat=None):
+    """the permutation distribution of one spatial statistic -> (observed [V], count [V] uint32, max_dist [P]); fstat = (s, scale): of F"""
     P, V = W.shape[0], Yk.shape[1]
+    if fstat is not None:
+        launch = lambda Wk, ref, first, km, cnt, work: _launch_fspatial(dev, Yt, st, Wk, fstat[0], fstat[1], grid, at_t, mode, dh, E, H,
+                                                                        connectivity, ref, first, km, cnt, work)
+        if batch_spatial is not None:
+            f_spatial = batch_spatial
+            batch_spatial = lambda Y_, s_, W_, *rest: f_spatial(Y_, s_, W_, fstat[0], fstat[1], *rest)
+    else:
+        launch = lambda Wk, ref, first, km, cnt, work: _launch_spatial(dev, Yt, st, r, Wk, grid, at_t, mode, dh, E, H, connectivity, ref, first,
+                                                                       km, cnt, work)
     if batch_spatial is not None:
         _, _, obs = batch_spatial(Yk, sk, W[:1], grid, at, mode, dh, E, H, connectivity, None, True)
         obs = np.asarray(obs, dtype=np.float64)
@@ -424,9 +544,9 @@ def _spatial_test(Yk, sk, W, r, grid, at, mode, dh, E, H, connectivity, device, 
     obs_t = torch.empty(V, dtype=torch.float64, device=dev)
     cnt = torch.zeros(V, dtype=torch.int32, device=dev)
     md = torch.empty(P, dtype=torch.float64, device=dev)
-    _launch_spatial(dev, Yt, st, r, Wt[:1], grid, at_t, mode, dh, E, H, connectivity, None, obs_t, md[:1], None, work)
+    launch(Wt[:1], None, obs_t, md[:1], None, work)
     for k0 in range(0, P, K):
-        _launch_spatial(dev, Yt, st, r, Wt[k0:k0 + K], grid, at_t, mode, dh, E, H, connectivity, obs_t, None, md[k0:k0 + K], cnt, work)
+        launch(Wt[k0:k0 + K], obs_t, None, md[k0:k0 + K], cnt, work)
     return obs_t.cpu().numpy(), cnt.cpu().numpy().view(np.uint32), md.cpu().numpy()
 
 
@@ -469,8 +589,105 @@ def _spatial_options(tfce, cluster_threshold, cluster_connectivity, two_sided, g
 
 # ---------------------------------------------------------------- the test
 
-def randomise(Y, X, c, n_perm=5000, seed=0, exchange="permute", two_sided=False, device=0, batch_stat=None, tfce=None, cluster_threshold=None,
-              cluster_connectivity=26, grid=None, at=None, batch_spatial=None, work_bytes=2 ** 30):
+def _randomise_f(Y, X, f_contrast, n_perm, seed, exchange, device, batch_stat, tfce, cluster_threshold, cluster_connectivity, grid, at,
+                 batch_spatial, work_bytes):
+    """randomise for an F-contrast (its docstring states the results)"""
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    if Y.ndim != 2:
+        raise ValueError("Y must be [n, V] with one row per subject")
+    fc = np.asarray(f_contrast, dtype=np.float64)
+    fc = fc[None, :] if fc.ndim == 1 else fc
+    p = np.shape(X)[1] if np.ndim(X) == 2 else 1
+    if fc.ndim != 2 or fc.shape[1] != p:
+        raise ValueError("f_contrast must be [s, p]: one t-contrast of the design's %d columns per row" % p)
+    Cm = np.ascontiguousarray(fc.T)                                # [p, s]
+    want_spatial = (tfce is not None and tfce is not False) or cluster_threshold is not None
+    if want_spatial:
+        tfce_opts, grid, at = _spatial_options(tfce, cluster_threshold, cluster_connectivity, False, grid, at, Y.shape[1], batch_stat, batch_spatial)
+    if batch_stat is not None and not callable(batch_stat):
+        raise ValueError("batch_stat must be a callable with the entry's meaning")
+    perms = permutation_set(X, Cm, n_perm, seed, exchange)
+    W, s, dof = weights_f(X, Cm, perms)
+    P, r = W.shape[0], W.shape[1]
+    scale = float(dof) / float(s)
+    lim = limits() if batch_stat is None else {"max_n": Y.shape[0], "max_r": r, "max_k": 256}
+    if Y.shape[0] > lim["max_n"] or r > lim["max_r"]:
+        raise ValueError("at most %d subjects and %d model columns" % (lim["max_n"], lim["max_r"]))
+    Yr, s0 = residualise(Y, X, Cm)
+    keep = np.flatnonzero((Yr != 0.0).any(axis=0) & (s0 > TINY * np.sum(Y * Y, axis=0)))
+    Yk, sk = np.ascontiguousarray(Yr[:, keep]), np.ascontiguousarray(s0[keep])
+    V, K = keep.size, lim["max_k"]
+    if batch_stat is not None:
+        _, _, f_obs = batch_stat(Yk, sk, W[:1], s, scale, None, True)
+        f_obs = np.asarray(f_obs, dtype=np.float64)
+        count, max_dist = np.zeros(V, dtype=np.uint32), np.empty(P)
+        for k0 in range(0, P, K):
+            km, inc, _ = batch_stat(Yk, sk, W[k0:k0 + K], s, scale, f_obs, False)
+            max_dist[k0:k0 + K] = km
+            count += np.asarray(inc, dtype=np.uint32)
+        n_ge = P - np.searchsorted(np.sort(max_dist), f_obs, side="left")
+    else:
+        import torch
+        dev = torch.device("cuda", device)
+        put = lambda a: torch.as_tensor(a, device=dev)
+        Yt, st, Wt = put(Yk), put(sk), put(W)
+        f_dev = torch.empty(V, dtype=torch.float64, device=dev)
+        cnt = torch.zeros(V, dtype=torch.int32, device=dev)
+        md = torch.empty(P, dtype=torch.float64, device=dev)
+        _launch_f(dev, Yt, st, Wt[:1], s, scale, None, f_dev, md[:1], None)
+        for k0 in range(0, P, K):
+            _launch_f(dev, Yt, st, Wt[k0:k0 + K], s, scale, f_dev, None, md[k0:k0 + K], cnt)
+        n_ge_t = P - torch.searchsorted(torch.sort(md)[0], f_dev.contiguous(), right=False)      # exact integers, on the device
+        f_obs, count, max_dist, n_ge = f_dev.cpu().numpy(), cnt.cpu().numpy().view(np.uint32), md.cpu().numpy(), n_ge_t.cpu().numpy()
+    full = Y.shape[1]
+    out = {"fstat": np.zeros(full), "p_uncorrected": np.ones(full), "p_fwe": np.ones(full), "count": np.full(full, P, dtype=np.uint32)}
+    out["fstat"][keep] = f_obs
+    out["count"][keep] = count
+    out["p_uncorrected"][keep] = count / float(P)
+    out["p_fwe"][keep] = n_ge / float(P)
+    out.update(max_dist=max_dist, n_perm=P, exhaustive=bool(perms.exhaustive), dof=(int(s), int(dof)),
+               f_crit=float(np.quantile(max_dist, 0.95)) if V else float("nan"))
+    if not want_spatial:
+        return out
+    box, at_box = _crop(grid, at[keep])
+
+    def fill(prefix, stat_key, keys, obs, count_s, md):
+        """one statistic's results, unfolded to the V columns: left-out voxels get 0 and p = 1"""
+        stat, cnt = np.zeros(full), np.full(full, P, dtype=np.uint32)
+        p_unc, p_fwe = np.ones(full), np.ones(full)
+        stat[keep], cnt[keep] = obs, count_s
+        p_unc[keep] = count_s / float(P)
+        p_fwe[keep] = (P - np.searchsorted(np.sort(md), obs, side="left")) / float(P)
+        out.update({stat_key: stat, keys[0]: p_unc, keys[1]: p_fwe, prefix + "_count": cnt, prefix + "_max_dist": md,
+                    prefix + "_crit": float(np.quantile(md, 0.95))})
+
+    nothing = lambda: (np.zeros(V), np.full(V, P, dtype=np.uint32), np.zeros(P))
+    if tfce_opts is not None:
+        dh = tfce_opts["dh"]
+        if dh is None:
+            top = float(np.max(f_obs)) if V else 0.0
+            dh = top / 100.0 if top > 0.0 and np.isfinite(top) else None
+        if dh is None or not V:                                    # nothing rises above zero: every value 0, every p 1, no launch
+            obs, count_s, md = nothing()
+        else:
+            obs, count_s, md = _spatial_test(Yk, sk, W, r, box, at_box, "tfce", dh, tfce_opts["E"], tfce_opts["H"], tfce_opts["connectivity"],
+                                             device, batch_spatial, work_bytes, fstat=(s, scale))
+        fill("tfce", "tfce", ("p_tfce_uncorrected", "p_tfce_fwe"), obs, count_s, md)
+        out.update(dh=dh if dh is not None else 0.0, tfce_options={"E": float(tfce_opts["E"]), "H": float(tfce_opts["H"]),
+                                                                   "connectivity": int(tfce_opts["connectivity"])})
+    if cluster_threshold is not None:
+        if V:
+            obs, count_s, md = _spatial_test(Yk, sk, W, r, box, at_box, "extent", float(cluster_threshold), 1.0, 1.0, cluster_connectivity, device,
+                                             batch_spatial, work_bytes, fstat=(s, scale))
+        else:
+            obs, count_s, md = nothing()
+        fill("cluster", "cluster_extent", ("p_cluster_uncorrected", "p_cluster_fwe"), obs, count_s, md)
+        out.update(cluster_threshold=float(cluster_threshold), cluster_connectivity=int(cluster_connectivity))
+    return out
+
+
+def randomise(Y, X, c=None, n_perm=5000, seed=0, exchange="permute", two_sided=False, device=0, batch_stat=None, tfce=None, cluster_threshold=None,
+              cluster_connectivity=26, grid=None, at=None, batch_spatial=None, work_bytes=2 ** 30, f_contrast=None):
     """The permutation test of the t-contrast c in the design X [n, p] at every voxel of Y [n, V] (one row per subject).
     batch_stat: None runs met2_group_perm_stats on `device`; a numpy callable with its meaning -- batch_stat(Y, s0, W, two_sided, t_ref,
     want_first) -> (kmax [K], count increment [V] or None, t_first [V] or None) -- replaces it, and the loop then needs no device.
@@ -487,7 +704,20 @@ def randomise(Y, X, c, n_perm=5000, seed=0, exchange="permute", two_sided=False,
     replaces it, and is required when batch_stat is given.  Adds for tfce: tfce [V], p_tfce_uncorrected, p_tfce_fwe, tfce_count, tfce_max_dist
     [P], tfce_crit, dh, tfce_options; for the extent: cluster_extent [V], p_cluster_uncorrected, p_cluster_fwe, cluster_count,
     cluster_max_dist [P], cluster_crit -- each defined as its t counterpart.  When the observed maximum of t is <= 0 (and dh is not given)
-    every TFCE value is 0 and every p is 1, with no launch.  With neither option the results and the launches are what they were."""
+    every TFCE value is 0 and every p is 1, with no launch.  With neither option the results and the launches are what they were.
+    F-contrasts: exactly one of c and f_contrast.  f_contrast [s, p] holds one t-contrast per row, as the rows an FSL .fts line selects; the
+    test is the F-test of all of them at once (met2_group_perm_fstats; the header states the statistic), one-sided by nature: two_sided=True
+    is refused.  -> dict(fstat [V], p_uncorrected, p_fwe, count, max_dist, f_crit, dof = (s, n - r), n_perm, exhaustive); there is no cope.
+    tfce (dh defaults to a hundredth of the observed maximum of F) and cluster_threshold (a threshold on F) go through met2_group_perm_ftfce
+    and add the keys they add above.  batch_stat(Y, s0, W, s, scale, f_ref, want_first) and batch_spatial(Y, s0, W, s, scale, grid, at,
+    mode, dh, E, H, connectivity, ref, want_first) keep their role, with s and scale = dof / s handed on.  Left-out voxels get F = 0, p = 1."""
+    if (c is None) == (f_contrast is None):
+        raise ValueError("give exactly one of c (a t-contrast) and f_contrast (an F-contrast [s, p])")
+    if f_contrast is not None:
+        if two_sided:
+            raise ValueError("an F-contrast has no sides: two_sided=True is refused")
+        return _randomise_f(Y, X, f_contrast, n_perm, seed, exchange, device, batch_stat, tfce, cluster_threshold, cluster_connectivity, grid, at,
+                            batch_spatial, work_bytes)
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     if Y.ndim != 2:
         raise ValueError("Y must be [n, V] with one row per subject")

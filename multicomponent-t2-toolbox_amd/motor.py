@@ -1017,7 +1017,7 @@ def motor_maps_to_template(path_to_save_data, path_to_template, path_to_world=No
     return out
 
 
-def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_mask=None, **options):
+def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_mask=None, f_contrast=None, **options):
     """Voxel-wise group statistics of one map over several subjects, after motor_maps_to_template brought every subject's maps onto one
     template grid.  paths_to_save_data: one path_to_save_data per subject, in the order of the rows of the design X [n, p]; `quantity`: one of
     STAT_QUANTITIES; c: the t-contrast.  Every subject's <stem>_in_template.nii.gz is loaded; differing shapes or affines are refused.  The
@@ -1033,6 +1033,9 @@ def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_m
     <quantity>_p_tfce_fwe.nii.gz and <quantity>_tfce_max_dist.txt, and in the report dh, E, H, the connectivity, tfce_crit and the number of
     voxels with p_tfce_fwe <= 0.05.  With cluster_threshold=h (cluster_connectivity=26): <quantity>_cluster_extent.nii.gz and
     <quantity>_p_cluster_fwe.nii.gz, and their line in the report.  Parity with randomise -T / -c is unpinned as well.
+    f_contrast [s, p] with c = None: the F-test of its rows at once.  Written then: <quantity>_fstat.nii.gz, <quantity>_p_unc.nii.gz,
+    <quantity>_p_fwe.nii.gz, <quantity>_max_dist.txt, the TFCE / cluster files under the names above (taken on F), and the report with s, the
+    degrees of freedom (s, n - r), f_crit and the counts at p <= 0.05; no _tstat and no _cope file.  Parity with randomise -f is unpinned.
     -> the dict of group_stats_filter."""
     from . import nifti
     if quantity not in STAT_QUANTITIES:
@@ -1060,16 +1063,21 @@ def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_m
         if m.shape != inside.shape:
             raise ValueError("the mask does not lie on the template grid")
         inside = inside & m
-    out = group_stats_filter(np.stack(vols), X, c, mask=inside, **options)
-    for key, name in (("tstat", "tstat"), ("cope", "cope"), ("p_uncorrected", "p_unc"), ("p_fwe", "p_fwe")):
+    out = group_stats_filter(np.stack(vols), X, c, mask=inside, f_contrast=f_contrast, **options)
+    files = (("tstat", "tstat"), ("cope", "cope")) if f_contrast is None else (("fstat", "fstat"),)
+    for key, name in files + (("p_uncorrected", "p_unc"), ("p_fwe", "p_fwe")):
         nifti.save(nifti.NiftiImage(out[key], affine), path_to_out + quantity + "_" + name + ".nii.gz")
     np.savetxt(path_to_out + quantity + "_max_dist.txt", out["max_dist"])
     n = len(paths)
-    lines = ["group statistics of %s: n = %d subjects, dof = %d" % (quantity, n, out["dof"]),
-             "permutations: %d (%s)" % (out["n_perm"], "exhaustive" if out["exhaustive"] else "drawn at random"),
-             "voxels tested: %d" % int(out["mask"].sum()),
-             "t_crit (0.95 quantile of the maximum statistic): %.6f" % out["t_crit"],
-             "voxels with p_fwe <= 0.05: %d" % int(((out["p_fwe"] <= 0.05) & out["mask"]).sum())]
+    if f_contrast is None:
+        head = ["group statistics of %s: n = %d subjects, dof = %d" % (quantity, n, out["dof"])]
+        crit = "t_crit (0.95 quantile of the maximum statistic): %.6f" % out["t_crit"]
+    else:
+        head = ["group statistics of %s: n = %d subjects, F-contrast of s = %d rows, dof = (%d, %d)" % ((quantity, n, out["dof"][0]) + out["dof"])]
+        crit = "f_crit (0.95 quantile of the maximum statistic): %.6f" % out["f_crit"]
+    lines = head + ["permutations: %d (%s)" % (out["n_perm"], "exhaustive" if out["exhaustive"] else "drawn at random"),
+                    "voxels tested: %d" % int(out["mask"].sum()), crit,
+                    "voxels with p_fwe <= 0.05: %d" % int(((out["p_fwe"] <= 0.05) & out["mask"]).sum())]
     if "tfce" in out:
         for key, name in (("tfce", "tfce"), ("p_tfce_uncorrected", "p_tfce_unc"), ("p_tfce_fwe", "p_tfce_fwe")):
             nifti.save(nifti.NiftiImage(out[key], affine), path_to_out + quantity + "_" + name + ".nii.gz")

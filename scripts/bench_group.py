@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Timing of the voxel-wise permutation test (met2_group_perm_stats, group.randomise) on the device, written to profiles/group_bench.json:
     python3 scripts/bench_group.py [--perms 5000] [--voxels 250000] [--subjects 32] [--reps 5] [--numpy-candidates 32] [--out FILE]
-                                   [--tfce [--grid 96 112 96] [--numpy-seconds 60] [--device-only]]
+                                   [--tfce [--grid 96 112 96] [--numpy-seconds 60] [--device-only]] [--fstat [--grid 96 112 96]]
 The case: two groups of subjects / 2 (r = 2 model columns), seeded normal data with a group difference in 1 % of the voxels, `perms`
 permutations drawn at random, one map.
   kernels     the launches of the whole set (ceil(perms / max_k) calls of the entry with t_ref and count, inputs resident on the device), between
@@ -21,6 +21,11 @@ one (group.randomise(tfce=True): met2_group_perm_tfce in batches of at most 32 m
               candidates as are finished within --numpy-seconds (60); the whole set is that rate scaled, and is marked as scaled
   --device-only leaves the restatement out and makes one call: the form for a kernel trace of its own (rocprofv3 --kernel-trace --stats),
               from which the stages' shares of the kernel time are read (gp_stats: t; tf_union, tf_count, tf_sum: the levels).
+With --fstat the test is the F-test of three groups (subjects split 11 / 11 / 10 at 32; r = 3 model columns, s = 2 contrast rows), written to
+profiles/group_f_bench.json:
+  kernels     the launches of the whole set through met2_group_perm_fstats, as above, and in the same run the t entry (met2_group_perm_stats,
+              group 1 against group 2) at the same n, r, V and P: the yardstick.  The F kernel carries r sums per candidate, the t kernel r + 1.
+  randomise   group.randomise(f_contrast=...) end to end, and with tfce=True on the grid (--grid; the voxels an ellipsoid's, as with --tfce)
 A record, not a pass mark."""
 import argparse
 import importlib
@@ -106,6 +111,95 @@ def tfce_case(a, group, gn):
     print(json.dumps(rec))
 
 
+def events_ms(fn, reps):
+    """the times of `reps` passes of fn between HIP events, after a warm-up pass"""
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return out
+
+
+def fstat_case(a, group):
+    n, V, P, grid = a.subjects, a.voxels, a.perms, tuple(a.grid)
+    sizes = [-(-n // 3), -(-n // 3), n - 2 * -(-n // 3)]           # 32 -> 11 / 11 / 10
+    g = np.repeat(np.arange(3), sizes)
+    X = np.stack([(g == j).astype(np.float64) for j in range(3)], axis=1)
+    fc = np.array([[1.0, -1.0, 0.0], [0.0, 1.0, -1.0]])
+    c = fc[0]
+    at = ellipsoid(grid, V)
+    rng = np.random.default_rng(0)
+    Y = rng.standard_normal((n, V))
+    centre = np.argsort(np.abs(at - at[V // 2]))[: V // 100]      # 1 % of the voxels around the middle one
+    Y[np.ix_(g == 1, centre)] += 1.5
+    Y[np.ix_(g == 2, centre)] -= 1.5
+    dev = torch.device("cuda", 0)
+    K = group.limits()["max_k"]
+
+    perms = group.permutation_set(X, fc.T, P, 0, "permute")
+    Wf, s, dof = group.weights_f(X, fc.T, perms)
+    Yf, s0f = group.residualise(Y, X, fc.T)
+    Wt, _ = group.weights(X, c, group.permutation_set(X, c, P, 0, "permute"))
+    Yc, s0c = group.residualise(Y, X, c)
+    P, r = Wf.shape[0], Wf.shape[1]
+    assert Wt.shape == (P, r + 1, n)
+    put = lambda x: torch.as_tensor(x, device=dev)
+    Yft, sft, Wft, Yct, sct, Wtt = (put(x) for x in (Yf, s0f, Wf, Yc, s0c, Wt))
+    obs_f, obs_t = (torch.empty(V, dtype=torch.float64, device=dev) for _ in range(2))
+    md = torch.empty(P, dtype=torch.float64, device=dev)
+    cnt = torch.zeros(V, dtype=torch.int32, device=dev)
+    scale = float(dof) / s
+    group._launch_f(dev, Yft, sft, Wft[:1], s, scale, None, obs_f, md[:1], None)
+    group._launch(dev, Yct, sct, r, Wtt[:1], False, None, obs_t, md[:1], None)
+
+    def f_set():
+        for k0 in range(0, P, K):
+            group._launch_f(dev, Yft, sft, Wft[k0:k0 + K], s, scale, obs_f, None, md[k0:k0 + K], cnt)
+
+    def t_set():
+        for k0 in range(0, P, K):
+            group._launch(dev, Yct, sct, r, Wtt[k0:k0 + K], False, obs_t, None, md[k0:k0 + K], cnt)
+
+    f_ms, t_ms = events_ms(f_set, a.reps), events_ms(t_set, a.reps)
+    f_ms2 = events_ms(f_set, a.reps)                                # once more after the t passes: the order of the two does not decide
+    kw = dict(n_perm=P, seed=0)
+    group.randomise(Y, X, f_contrast=fc, **kw)
+    group.randomise(Y, X, f_contrast=fc, tfce=True, grid=grid, at=at, **kw)
+    plain_s, tfce_s = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        out = group.randomise(Y, X, f_contrast=fc, **kw)
+        t1 = time.perf_counter()
+        out_s = group.randomise(Y, X, f_contrast=fc, tfce=True, grid=grid, at=at, **kw)
+        plain_s.append(t1 - t0)
+        tfce_s.append(time.perf_counter() - t1)
+    med = lambda x: float(np.median(x))
+    rec = {"case": {"perms": P, "voxels": V, "subjects": n, "groups": sizes, "r": r, "s": int(s), "dof": [int(s), int(dof)],
+                    "launches": (P + K - 1) // K, "grid": list(grid)},
+           "kernels_f": {"seconds": med(f_ms) * 1e-3, "all_ms": f_ms, "all_ms_after_the_t_passes": f_ms2, "flop": 2.0 * n * r * P * V,
+                         "achieved_tflops": 2.0 * n * r * P * V / (med(f_ms) * 1e-3) / 1e12},
+           "kernels_t_same_n_r_V_P": {"seconds": med(t_ms) * 1e-3, "all_ms": t_ms, "flop": 2.0 * n * (r + 1) * P * V,
+                                      "achieved_tflops": 2.0 * n * (r + 1) * P * V / (med(t_ms) * 1e-3) / 1e12},
+           "f_over_t": med(f_ms) / med(t_ms), "spread_of_the_passes_ms": {"f": max(f_ms) - min(f_ms), "t": max(t_ms) - min(t_ms)},
+           "randomise_f": {"seconds": med(plain_s), "all_s": plain_s, "f_crit": out["f_crit"],
+                           "voxels_p_fwe_le_0.05": int((out["p_fwe"] <= 0.05).sum())},
+           "randomise_f_tfce": {"seconds": med(tfce_s), "all_s": tfce_s, "dh": out_s["dh"], "tfce_crit": out_s["tfce_crit"],
+                                "voxels_p_tfce_fwe_le_0.05": int((out_s["p_tfce_fwe"] <= 0.05).sum())},
+           "device": torch.cuda.get_device_name(0), "reps": a.reps}
+    path = a.out if a.out != os.path.join(ROOT, "profiles", "group_bench.json") else os.path.join(ROOT, "profiles", "group_f_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--perms", type=int, default=5000)
@@ -118,10 +212,13 @@ def main():
     ap.add_argument("--grid", type=int, nargs=3, default=[96, 112, 96])
     ap.add_argument("--numpy-seconds", type=float, default=60.0)
     ap.add_argument("--device-only", action="store_true")
+    ap.add_argument("--fstat", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "the benchmark needs a GPU"
     group = importlib.import_module(PKG + ".group")
     import group_numpy as gn
+    if a.fstat:
+        return fstat_case(a, group)
     if a.tfce:
         return tfce_case(a, group, gn)
     n, V, P = a.subjects, a.voxels, a.perms
