@@ -1483,6 +1483,66 @@ int met2_group_perm_ftfce(int32_t device, int32_t n, int64_t n_vox, const double
                           int32_t connectivity, const double *ref, double *first, double *kmax, uint32_t *count, void *work, int64_t work_bytes,
                           void *stream);
 
+/* ---- Variance smoothing: the pseudo-t of small-sample studies (csrc/met2_group_vsm.hip) ---------------------------------------------
+ * With few degrees of freedom the residual variance of a voxel is noisy and the permutation distribution of the maximum t is driven by voxels
+ * whose variance happens to be tiny.  The remedy of Holmes et al. (1996) and Nichols & Holmes (2002), FSL randomise's -v: pool the variance
+ * over a Gaussian neighbourhood and test the pseudo-t, cope / sqrt(smoothed variance).
+ * Grid, mask, at: as for met2_group_perm_tfce (dims = (nx, ny, nz), z contiguous; the mask of the group entry is {at[v]}).
+ * Taps.  taps_a holds 2 R_a + 1 doubles for axis a in x, y, z, with R_a = radius[a], 0 <= R_a <= MET2_GROUP_VSM_MAX_RADIUS.  Every tap is
+ *   finite and >= 0 and the centre tap is > 0.  HOST arrays, like dims and radius: the entries do not form them, so no result depends on a
+ *   device exp (group.py: smoothing_taps).
+ * Masked smoothing S(m) of a map m, which is read as 0 outside the mask.  Three passes in the order x, y, z, each complete over the WHOLE grid
+ *   before the next starts: values outside the mask are computed and used in between.  One pass along axis a:
+ *       out(p) = sum over d = -R_a .. +R_a, in ascending d, of taps_a[d + R_a] * in(p + d e_a),
+ *   the sum from 0.0, a term whose source lies outside the grid skipped, product and sum rounded separately, nothing fused, fp64 throughout.
+ *   N = S(the mask's indicator, 1.0 / 0.0), computed once per call.
+ * Pseudo-t of candidate k at tested voxel v.  b, g_j, q and rss are met2_group_perm_stats's, by that entry's own kernel code: the same sums in
+ *   the same order, the same bits.  rho(k, v) = rss > 0 ? rss : 0 (an rss that is not a number contributes 0 and does not spread);
+ *   sigma2(k, v) = S(rho_k)(v) / N(v), one correctly rounded division (N > 0 on the mask since the centre taps are);
+ *   pt(k, v) = sigma2 > 0 ? b / sqrt(sigma2) : 0, correctly rounded; two_sided: |pt|.  A b that is not a number gives a pt that is not one:
+ *   the maximum passes over it and it reaches no reference.
+ * Consequences.  The bits of pt(k, .) depend on W[k], Y, s0, the mask and the taps alone: not on K, the candidate's place, its batch mates,
+ *   the tiling or the device; a float64 numpy loop in that order reproduces them (tests/tools/group_vsm_numpy.py).  With taps {[1.0], [1.0],
+ *   [1.0]} the result is met2_group_perm_stats's t to the bit: rss * 1.0 / 1.0 is exact.  Cropping the grid to the mask's bounding box changes
+ *   no bit: what is cut away holds zeros, and a sum skips a term or adds an exact zero.
+ * met2_masked_smooth: maps [K][nx][ny][nz], read as 0 where mask [nx][ny][nz] (uint8; NULL: no mask) is 0 -> out [K][nx][ny][nz] = S at EVERY
+ *   grid voxel (must not overlap maps) and, when not NULL, norm_out [nx][ny][nz] = N.  What lies outside the mask in maps (-0, infinities,
+ *   values that are not numbers) is not read.
+ * met2_group_perm_vsm: n, n_vox, Y, s0, r, K, W, dims, at, dh, E, H, connectivity, ref, first, kmax, count as for met2_group_perm_tfce.  Stages:
+ *   b and rho of the batch to dense maps; the three passes; the pseudo-t into a dense map (0 off the mask); then by mode
+ *   MET2_GROUP_VSM_MODE_VOXEL: s(k, v) = pt(k, at[v]):  kmax[k] = max_v s(k, v);  first[v] = s(0, v);  count[v] += #{k: s(k, v) >= ref[v]}, with
+ *     the meaning they have for met2_group_perm_tfce; dh, E, H and connectivity are not read;
+ *   MET2_TFCE_MODE_TFCE, MET2_TFCE_MODE_EXTENT: met2_group_perm_tfce's transform and gather on the pseudo-t maps, unchanged.  One-sided:
+ *     two_sided = 1 with a spatial mode is MET2_E_INVALID.
+ *   Late errors as for met2_group_perm_tfce: an `at` that is not strictly ascending inside the grid is MET2_E_INVALID with kmax, first and
+ *   count untouched; a bound of the union-find that ran out is MET2_E_HIP.
+ * Work space.  met2_group_vsm_work_bytes(K, dims, n_vox, mode): n_vox = 0: met2_masked_smooth, 8 bytes per map and grid voxel and 8 per grid
+ *   voxel; n_vox > 0: met2_group_perm_vsm: b and two maps that take turns (24 bytes per map and grid voxel), N and the mask (9 per grid voxel)
+ *   and, in the spatial modes, the forest (10 per map and grid voxel).  work = NULL: the call allocates and frees it; else a device block of
+ *   work_bytes >= that (MET2_E_INVALID if smaller).  Either way the call returns after its work is done.
+ * DEVICE pointers throughout but dims, radius and the taps.  met2_group_vsm_limits and met2_group_vsm_work_bytes are host only;
+ * met2_group_vsm_limits reports MET2_GROUP_VSM_MAX_RADIUS, MET2_GROUP_VSM_MAX_K and the smoothing kernel's tile: samples along the axis of a
+ * pass, and lines across it (any output may be NULL).
+ * Limits.  1 <= K <= MET2_GROUP_VSM_MAX_K and R_a <= MET2_GROUP_VSM_MAX_RADIUS (MET2_E_UNSUPPORTED beyond), the grid and n, r as for
+ * met2_group_perm_tfce.  MET2_E_INVALID: a negative radius, a tap that is not finite or < 0, a centre tap <= 0, out overlapping maps, norm_out
+ * overlapping either, a mode other than the three named, a NULL required pointer, ref without count, and what met2_group_perm_tfce refuses.
+ * Every such check comes before any device work: the outputs are then untouched.
+ * Parity with FSL randomise -v is unpinned (FSL was not available).  The definitions may differ from FSL's in the truncation of the kernel (the
+ * caller's taps; group.py cuts at 3 sigma), in the width FSL gives the kernel it smooths its variance image with, and in the normalisation by
+ * the smoothed mask. */
+#define MET2_GROUP_VSM_MAX_RADIUS 16
+#define MET2_GROUP_VSM_MAX_K 32
+#define MET2_GROUP_VSM_MODE_VOXEL 2
+int met2_group_vsm_limits(int32_t *max_radius, int32_t *max_k, int32_t *tile_axis, int32_t *tile_lines);
+int met2_group_vsm_work_bytes(int32_t K, const int32_t dims[3], int64_t n_vox, int32_t mode, int64_t *bytes);
+int met2_masked_smooth(int32_t device, int32_t K, const int32_t dims[3], const double *maps, const uint8_t *mask, const int32_t radius[3],
+                       const double *taps_x, const double *taps_y, const double *taps_z, double *out, double *norm_out, void *work,
+                       int64_t work_bytes, void *stream);
+int met2_group_perm_vsm(int32_t device, int32_t n, int64_t n_vox, const double *Y, const double *s0, int32_t r, int32_t K, const double *W,
+                        int32_t two_sided, const int32_t dims[3], const int32_t *at, int32_t mode, double dh, double E, double H,
+                        int32_t connectivity, const int32_t radius[3], const double *taps_x, const double *taps_y, const double *taps_z,
+                        const double *ref, double *first, double *kmax, uint32_t *count, void *work, int64_t work_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

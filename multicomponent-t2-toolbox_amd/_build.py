@@ -7,11 +7,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmet2_hip.so")
 # one object per translation unit (compiled side by side, linked into ONE library): the core (plan, sort, fit, FA walk), the fit kernels, the dictionary and
-# penalty entries, the pre-fit filters (NESMA, smoother, FA spline selection), the ROI reduction and stand-alone metrics, the TV and MP-PCA denoisers, the Gibbs-ringing filter, the bias-field correction, the brain extraction, the tissue segmentation and its partial-volume maps, the label statistics, the Rician noise-floor correction, the affine resampling, the registration cost, the displacement-field warp and the stages of the deformable registration, the group statistics by permutation, their spatial statistics (TFCE, cluster extent)
+# penalty entries, the pre-fit filters (NESMA, smoother, FA spline selection), the ROI reduction and stand-alone metrics, the TV and MP-PCA denoisers, the Gibbs-ringing filter, the bias-field correction, the brain extraction, the tissue segmentation and its partial-volume maps, the label statistics, the Rician noise-floor correction, the affine resampling, the registration cost, the displacement-field warp and the stages of the deformable registration, the group statistics by permutation, their spatial statistics (TFCE, cluster extent), their variance smoothing (the pseudo-t)
 # (-DMET2_SPLIT_TU, the shipped build: the fit kernels are instantiated in met2_fit_*.hip, one family of methods per file -- fit_kernel.hpp;
 #  with extra MET2_BUILD_DEFINES -- development builds -- met2_hip.hip instantiates them all and those files compile to nothing)
-SOURCES = ["met2_hip.hip", "met2_dictionary.hip", "met2_prefilter.hip", "met2_roi_metrics.hip", "met2_fit_x2_nb1.hip", "met2_fit_x2_nb2.hip", "met2_fit_x2_second.hip", "met2_fit_nnls_lcurve.hip", "met2_fit_gcv.hip", "met2_fit_bayes.hip", "met2_tv.hip", "met2_host.hip", "met2_bootstrap.hip", "met2_eval.hip", "met2_mppca.hip", "met2_gibbs.hip", "met2_bias.hip", "met2_bet.hip", "met2_seg.hip", "met2_pve.hip", "met2_stats.hip", "met2_rician.hip", "met2_resample.hip", "met2_register.hip", "met2_warp.hip", "met2_group.hip", "met2_tfce.hip"]
-HEADERS = ["abi_common.hpp", "plan.hpp", "brent.hpp", "metrics.hpp", "philox.hpp", "wave_ops.hpp", "nnls_wave.hpp", "nnls_big.hpp", "objectives.hpp", "fit_kernel.hpp", "bias_common.hpp", "quantile.hpp", "rician_math.hpp", "rician_bessel.hpp", "resample_taps.hpp", "resample_checks.hpp", "device_work.hpp", "device_helpers.hpp", "group_kernel.hpp", os.path.join("..", "..", "include", "met2_hip.h")]
+SOURCES = ["met2_hip.hip", "met2_dictionary.hip", "met2_prefilter.hip", "met2_roi_metrics.hip", "met2_fit_x2_nb1.hip", "met2_fit_x2_nb2.hip", "met2_fit_x2_second.hip", "met2_fit_nnls_lcurve.hip", "met2_fit_gcv.hip", "met2_fit_bayes.hip", "met2_tv.hip", "met2_host.hip", "met2_bootstrap.hip", "met2_eval.hip", "met2_mppca.hip", "met2_gibbs.hip", "met2_bias.hip", "met2_bet.hip", "met2_seg.hip", "met2_pve.hip", "met2_stats.hip", "met2_rician.hip", "met2_resample.hip", "met2_register.hip", "met2_warp.hip", "met2_group.hip", "met2_tfce.hip", "met2_group_vsm.hip"]
+HEADERS = ["abi_common.hpp", "plan.hpp", "brent.hpp", "metrics.hpp", "philox.hpp", "wave_ops.hpp", "nnls_wave.hpp", "nnls_big.hpp", "objectives.hpp", "fit_kernel.hpp", "bias_common.hpp", "quantile.hpp", "rician_math.hpp", "rician_bessel.hpp", "resample_taps.hpp", "resample_checks.hpp", "device_work.hpp", "device_helpers.hpp", "group_kernel.hpp", "tfce_kernel.hpp", os.path.join("..", "..", "include", "met2_hip.h")]
 STAMP = LIB + ".flags"          # extra compile flags the library was built with (MET2_BUILD_DEFINES, e.g. -DMET2_CYCSTATS)
 # Machine LICM off: it hoists the materialisation of fp64 literals (erf/log coefficients of the BayesReg objective, 20 register
 # pairs) and per-lane address constants out of the voxel loop, runs out of registers and spills them to scratch -- BayesReg at

@@ -53,7 +53,8 @@ SYMBOLS = ["met2_default_options", "met2_abi_version", "met2_device_count", "met
            "met2_warp", "met2_warp_labels", "met2_warp_compose", "met2_warp_max_norm2", "met2_warp_work_bytes", "met2_warp_lncc_sums",
            "met2_warp_lncc_force", "met2_warp_lncc", "met2_warp_invert_step", "met2_warp_jacobian",
            "met2_group_limits", "met2_group_perm_stats", "met2_group_perm_fstats",
-           "met2_tfce_limits", "met2_tfce_work_bytes", "met2_tfce", "met2_group_perm_tfce", "met2_group_perm_ftfce"]
+           "met2_tfce_limits", "met2_tfce_work_bytes", "met2_tfce", "met2_group_perm_tfce", "met2_group_perm_ftfce",
+           "met2_group_vsm_limits", "met2_group_vsm_work_bytes", "met2_masked_smooth", "met2_group_perm_vsm"]
 
 
 def lib():
@@ -193,6 +194,11 @@ def lib():
         L.met2_group_perm_fstats.argtypes = [C.c_int32, C.c_int32, C.c_int64, vp, vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, vp, vp, vp, vp, vp, vp]
         L.met2_group_perm_ftfce.argtypes = [C.c_int32, C.c_int32, C.c_int64, vp, vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, vp, i3, vp, C.c_int32,
                                             C.c_double, C.c_double, C.c_double, C.c_int32, vp, vp, vp, vp, vp, C.c_int64, vp]
+        L.met2_group_vsm_limits.argtypes = [i3] * 4
+        L.met2_group_vsm_work_bytes.argtypes = [C.c_int32, i3, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
+        L.met2_masked_smooth.argtypes = [C.c_int32, C.c_int32, i3, vp, vp, i3, _dp, _dp, _dp, vp, vp, vp, C.c_int64, vp]
+        L.met2_group_perm_vsm.argtypes = [C.c_int32, C.c_int32, C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, i3, vp, C.c_int32, C.c_double,
+                                          C.c_double, C.c_double, C.c_int32, i3, _dp, _dp, _dp, vp, vp, vp, vp, vp, C.c_int64, vp]
         L.met2_synth_two_lobe.argtypes = [vp, C.POINTER(SynthParams), C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp]
         L.met2_eval_voxel_metrics.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
         L.met2_eval_reduce.argtypes = [C.c_int64, vp, vp, vp, vp, vp, vp]

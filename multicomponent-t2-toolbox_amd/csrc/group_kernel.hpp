@@ -18,6 +18,8 @@
 //   gp_fstats_kernel<R, KB, SCATTER>
 //                              the F statistic of an F-contrast (met2_group_perm_fstats, met2_group_perm_ftfce): the same structure with R = r
 //                              rows per candidate (no row 0) and both finishes; stated with the kernel below.  KB = 8 up to r = 4, 4 beyond.
+//   gp_moments_kernel<R1, KB>  met2_group_perm_vsm's first stage: gp_stats_kernel's sums, with b and the clamped rss scattered in the place of t;
+//                              stated with the kernel below.
 //   gp_key_kernel              writes the key of -infinity into kmax before, and turns the keys into doubles in place after: no scratch
 // A candidate beyond K in the last group has zero weights and is left out of every output; a thread beyond n_vox reads nothing and writes nothing.
 // The including unit is compiled without contraction; every loop is bounded by a shape or a compile-time constant.
@@ -163,6 +165,72 @@ void gp_launch_r(int r, int64_t n_vox, int n, int K, const double *Y, const doub
         GP_CASE(1); GP_CASE(2); GP_CASE(3); GP_CASE(4); GP_CASE(5); GP_CASE(6); GP_CASE(7); GP_CASE(8);
 #undef GP_CASE
     }
+}
+
+// The numerator and the clamped residual sum of squares of the pseudo-t (met2_group_perm_vsm): gp_stats_kernel<R1, KB, true>'s text up to rss --
+// the same sums in the same order, hence the same bits -- with b = acc[c][0] and rho = rss > 0 ? rss : 0 (an rss that is not a number gives 0)
+// written to two dense maps in the place of t.  A sibling, not a third variant of gp_stats_kernel: that kernel's template arguments, and with
+// them the names and registers of its instantiations, stay what they were.  Instantiated by met2_group_vsm.hip alone.
+template <int R1, int KB>
+__global__ void __launch_bounds__(GP_TILE) gp_moments_kernel(int n, int64_t n_vox, const double *__restrict__ Y, const double *__restrict__ s0, int K,
+                                                             const double *__restrict__ W, const int32_t *__restrict__ at, int64_t dense_stride,
+                                                             double *__restrict__ dense_b, double *__restrict__ dense_rho)
+{
+    constexpr int ROWS = KB * R1;
+    extern __shared__ double gp_lds[];
+    double *wt = gp_lds;                                           // [n][ROWS]: the group's weights, subject-major
+    const int64_t v = (int64_t)blockIdx.x * GP_TILE + threadIdx.x;
+    const bool live = v < n_vox;
+    const double *y = Y + (live ? v : 0);
+    const double s = live ? s0[v] : 0.0;
+    int64_t cell = -1;                                             // the voxel's place in a dense map
+    if (live) cell = at[v];
+    if (cell >= dense_stride) cell = -1;
+    for (int k0 = 0; k0 < K; k0 += KB) {
+        __syncthreads();                                           // the previous group's readers of wt are done
+        for (int e = threadIdx.x; e < ROWS * n; e += GP_TILE) {
+            const int row = e / n, i = e - row * n;
+            wt[i * ROWS + row] = k0 + row / R1 < K ? W[((int64_t)k0 * R1 + row) * n + i] : 0.0;
+        }
+        __syncthreads();
+        double acc[KB][R1];
+#pragma unroll
+        for (int c = 0; c < KB; ++c)
+#pragma unroll
+            for (int j = 0; j < R1; ++j) acc[c][j] = 0.0;
+        double y_next = live ? y[0] : 0.0;
+#pragma unroll 1
+        for (int i = 0; i < n; ++i) {                              // not unrolled, as in gp_stats_kernel
+            const double yi = y_next;
+            y_next = live && i + 1 < n ? y[(int64_t)(i + 1) * n_vox] : 0.0;
+            const double *w = wt + i * ROWS;
+#pragma unroll
+            for (int c = 0; c < KB; ++c)
+#pragma unroll
+                for (int j = 0; j < R1; ++j) acc[c][j] = rn_add(acc[c][j], rn_mul(w[c * R1 + j], yi));
+        }
+#pragma unroll
+        for (int c = 0; c < KB; ++c) {
+            double q = rn_mul(acc[c][1], acc[c][1]);
+#pragma unroll
+            for (int j = 2; j < R1; ++j) q = rn_add(q, rn_mul(acc[c][j], acc[c][j]));
+            const double rss = rn_sub(s, q);
+            if (live && k0 + c < K && cell >= 0) {
+                dense_b[(int64_t)(k0 + c) * dense_stride + cell] = acc[c][0];
+                dense_rho[(int64_t)(k0 + c) * dense_stride + cell] = rss > 0.0 ? rss : 0.0;
+            }
+        }
+    }
+}
+
+template <int R1>
+void gp_moments_launch(int64_t n_vox, int n, int K, const double *Y, const double *s0, const double *W, const int32_t *at, int64_t dense_stride,
+                       double *dense_b, double *dense_rho, hipStream_t st)
+{
+    constexpr int KB = R1 <= 4 ? 8 : 4;                            // gp_launch's groups
+    const size_t lds = (size_t)n * KB * R1 * sizeof(double);       // <= 128 * 36 * 8 = 36 864 bytes
+    const unsigned blocks = (unsigned)((n_vox + GP_TILE - 1) / GP_TILE);
+    hipLaunchKernelGGL((gp_moments_kernel<R1, KB>), dim3(blocks), dim3(GP_TILE), lds, st, n, n_vox, Y, s0, K, W, at, dense_stride, dense_b, dense_rho);
 }
 
 // The F statistic over the first s of r orthonormal rows (met2_group_perm_fstats, met2_group_perm_ftfce): gp_stats_kernel's structure with R = r

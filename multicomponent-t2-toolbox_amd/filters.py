@@ -409,7 +409,8 @@ GROUP_SPATIAL_VOLUMES = ("tfce", "p_tfce_uncorrected", "p_tfce_fwe", "cluster_ex
 GROUP_SPATIAL_COUNTS = ("tfce_count", "cluster_count")
 
 
-def group_stats_filter(volumes, X, c=None, mask=None, tfce=None, cluster_threshold=None, cluster_connectivity=26, f_contrast=None, **options):
+def group_stats_filter(volumes, X, c=None, mask=None, tfce=None, cluster_threshold=None, cluster_connectivity=26, f_contrast=None, variance_smoothing=None,
+                       **options):
     """The permutation test of the t-contrast c in the design X [n, p] at every voxel of n subjects' volumes [n, x, y, z] on one grid (the
     <map>_in_template volumes of maps_to_template_filter): group.randomise on the voxels of `mask` (None: all), unfolded into volumes.
     options: n_perm, seed, exchange ('permute' | 'flip'), two_sided, device, batch_stat -- group.randomise's.
@@ -419,7 +420,9 @@ def group_stats_filter(volumes, X, c=None, mask=None, tfce=None, cluster_thresho
     -> its dict with tstat, cope, p_uncorrected, p_fwe and count as [x, y, z] volumes (outside the mask t = 0, cope = 0, p = 1, count =
     n_perm) and mask [x, y, z] bool: the voxels that were tested.  Parity with FSL randomise is unpinned: FSL was not available.
     f_contrast [s, p] in the place of c: the F-test of its rows at once (group.randomise(f_contrast=...)), with fstat in the place of tstat and
-    cope (outside the mask F = 0), dof = (s, n - r) and f_crit; the spatial statistics are then taken on F."""
+    cope (outside the mask F = 0), dof = (s, n - r) and f_crit; the spatial statistics are then taken on F.
+    variance_smoothing = sigma or (sx, sy, sz), in VOXELS (the filter has no affine): handed on to group.randomise with the grid and the
+    voxels' places; tstat is then the pseudo-t and every p-value, and the spatial statistics, are taken on it."""
     from . import group
     vols = np.asarray(volumes.cpu() if torch.is_tensor(volumes) else volumes, dtype=np.float64)
     if vols.ndim != 4:
@@ -433,6 +436,8 @@ def group_stats_filter(volumes, X, c=None, mask=None, tfce=None, cluster_thresho
         options = dict(options, tfce=tfce, cluster_threshold=cluster_threshold, cluster_connectivity=cluster_connectivity, grid=shape, at=at)
     if f_contrast is not None:
         options = dict(options, f_contrast=f_contrast)
+    if variance_smoothing is not None:
+        options = dict(options, variance_smoothing=variance_smoothing, grid=shape, at=at)
     res = group.randomise(np.ascontiguousarray(vols.reshape(vols.shape[0], -1)[:, at]), X, c, **options)
     for key in (GROUP_VOLUMES if f_contrast is None else GROUP_F_VOLUMES) + tuple(k for k in GROUP_SPATIAL_VOLUMES if k in res):
         vol = np.full(int(np.prod(shape)), 1.0 if key.startswith("p_") else 0.0)

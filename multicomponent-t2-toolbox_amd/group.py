@@ -34,8 +34,17 @@ span x1.  F = ((n - r) / s) qs / (s0 - q) with qs the sum of the first s squared
 against the nuisance, by the argument above with |Q1' P_k Yr|^2 in the place of b^2.  perm_fstats and perm_ftfce are the entries on arrays.
 TFCE and the cluster extent are taken on F itself, with the same E, H and dh rule.
 
-Parity with FSL randomise (-T, -c and -f included) is unpinned: FSL was not available.  Not provided: cluster mass, exchangeability
-blocks, variance smoothing, several devices, 2-D connectivity."""
+Variance smoothing (randomise(variance_smoothing=sigma_vox); csrc/met2_group_vsm.hip; the header states the definitions): for small samples
+the residual variance is pooled over a Gaussian neighbourhood inside the mask, sigma2 = S(rho) / S(mask) with rho = max(rss, 0) and S three
+separable passes with the taps of smoothing_taps, and the statistic is the pseudo-t b / sqrt(sigma2) (Holmes et al. 1996; Nichols & Holmes
+2002).  met2_group_perm_vsm (perm_vsm on arrays) computes b and rss with met2_group_perm_stats's own kernel code, smooths a batch of dense maps
+on the device and then either gathers the pseudo-t (maximum per candidate, count per voxel) or hands the maps to the TFCE / extent machinery
+above.  masked_smooth is the smoothing on its own.  Radii up to 16 voxels (sigma <= 16 / 3 voxels), batches of at most 32 candidates.
+Where FSL's randomise -v may differ: the kernel is cut at 3 sigma here; FSL smooths its variance image with a kernel width of its own
+choosing; and the normalisation by the smoothed mask is this project's definition.
+
+Parity with FSL randomise (-T, -c, -f and -v included) is unpinned: FSL was not available.  Not provided: cluster mass, exchangeability
+blocks, several devices, 2-D connectivity."""
 import collections
 import ctypes as C
 import math
@@ -587,6 +596,269 @@ def _spatial_options(tfce, cluster_threshold, cluster_connectivity, two_sided, g
     return opts, grid, at
 
 
+# ---------------------------------------------------------------- variance smoothing: the pseudo-t
+
+VSM_MAX_RADIUS, VSM_MAX_K = 16, 32                                 # MET2_GROUP_VSM_MAX_RADIUS, MET2_GROUP_VSM_MAX_K (vsm_limits reports them)
+VSM_MODES = dict(MODES, voxel=2)                                   # MET2_GROUP_VSM_MODE_VOXEL beside MET2_TFCE_MODE_*
+
+
+def vsm_limits():
+    """met2_group_vsm_limits -> dict(max_radius, max_k, tile_axis, tile_lines); needs no device"""
+    v = [C.c_int32(-1) for _ in range(4)]
+    check(lib().met2_group_vsm_limits(*[C.byref(x) for x in v]))
+    return dict(zip(("max_radius", "max_k", "tile_axis", "tile_lines"), (x.value for x in v)))
+
+
+def vsm_work_bytes(K, grid, n_vox=0, mode="voxel"):
+    """met2_group_vsm_work_bytes: the device work space of one call for K maps on `grid` (n_vox = 0: of met2_masked_smooth; n_vox > 0: of
+    met2_group_perm_vsm in `mode`, 'voxel' | 'tfce' | 'extent')"""
+    if mode not in VSM_MODES:
+        raise ValueError("mode must be one of %s" % (tuple(VSM_MODES),))
+    out = C.c_int64(-1)
+    check(lib().met2_group_vsm_work_bytes(int(K), (C.c_int32 * 3)(*_dims(grid)), int(n_vox), VSM_MODES[mode], C.byref(out)))
+    return out.value
+
+
+def _sigma3(sigma_vox):
+    s = np.asarray(sigma_vox, dtype=np.float64).ravel()
+    s = np.repeat(s, 3) if s.size == 1 else s
+    if s.size != 3 or not np.isfinite(s).all() or (s < 0).any():
+        raise ValueError("sigma_vox must be one finite value >= 0, in voxels, or one per axis (sx, sy, sz)")
+    return tuple(float(x) for x in s)
+
+
+def smoothing_taps(sigma_vox):
+    """The taps of the variance smoothing for a Gaussian of sigma_vox voxels (a scalar, or one value per axis) -> (radius [3], taps [3]):
+    per axis R = ceil(3 sigma) and tap_d = exp(-d^2 / (2 sigma^2)) / sum over d = -R .. R; sigma = 0 gives R = 0 and [1.0], no smoothing
+    along that axis.  Formed here, on the host, so that no bit of a result depends on a device exp.  R may not exceed VSM_MAX_RADIUS."""
+    radius, taps = [], []
+    for s in _sigma3(sigma_vox):
+        R = int(math.ceil(3.0 * s))
+        if R > VSM_MAX_RADIUS:
+            raise ValueError("sigma_vox = %g voxels needs a radius of %d voxels: at most %d, i.e. sigma_vox <= %g" %
+                             (s, R, VSM_MAX_RADIUS, VSM_MAX_RADIUS / 3.0))
+        d = np.arange(-R, R + 1, dtype=np.float64)
+        w = np.exp(-(d * d) / (2.0 * s * s)) if R else np.ones(1)
+        radius.append(R)
+        taps.append(np.ascontiguousarray(w / w.sum()))
+    return tuple(radius), tuple(taps)
+
+
+def _checked_taps(taps):
+    """three tap arrays of odd length -> (radius (3 ints), taps (3 contiguous float64 arrays)); the entry checks the values"""
+    taps = tuple(np.ascontiguousarray(t, dtype=np.float64).ravel() for t in taps)
+    if len(taps) != 3 or any(t.size % 2 == 0 for t in taps):
+        raise ValueError("taps must hold three arrays of 2 R + 1 values, one per axis x, y, z")
+    return tuple((t.size - 1) // 2 for t in taps), taps
+
+
+def _taps_args(radius, taps):
+    """the ctypes arguments radius[3], taps_x, taps_y, taps_z (host arrays; the tuple keeps them alive)"""
+    dp = C.POINTER(C.c_double)
+    return ((C.c_int32 * 3)(*radius),) + tuple(t.ctypes.data_as(dp) for t in taps)
+
+
+def masked_smooth(maps, mask=None, sigma_vox=None, taps=None, device=0):
+    """met2_masked_smooth on numpy arrays: the masked, separable smoothing S of one map [nx, ny, nz] or several [K, nx, ny, nz] (any K: batches
+    of at most max_k maps), read as 0 where mask [nx, ny, nz] is 0 (None: no mask), with the taps of smoothing_taps(sigma_vox) or `taps`
+    (three arrays) -> (S at every grid voxel, in the shape of maps; N [nx, ny, nz] = S of the mask's indicator).  The variance smoothing
+    divides the two: S(m) / N on the mask."""
+    import torch
+    if (sigma_vox is None) == (taps is None):
+        raise ValueError("give exactly one of sigma_vox and taps")
+    radius, taps = _checked_taps(smoothing_taps(sigma_vox)[1] if taps is None else taps)
+    a = np.ascontiguousarray(maps, dtype=np.float64)
+    one = a.ndim == 3
+    a = a[None] if one else a
+    if a.ndim != 4:
+        raise ValueError("maps must be [nx, ny, nz] or [K, nx, ny, nz]")
+    grid = _dims(a.shape[1:])
+    dev = torch.device("cuda", device)
+    m = None
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mask.shape != grid:
+            raise ValueError("the mask does not lie on the grid of the maps")
+        m = torch.as_tensor(mask, device=dev)
+    out = np.empty_like(a)
+    norm = torch.empty(grid, dtype=torch.float64, device=dev)
+    dims, targs = (C.c_int32 * 3)(*grid), _taps_args(radius, taps)
+    with torch.cuda.device(dev):
+        for k0 in range(0, max(a.shape[0], 1), VSM_MAX_K):
+            src = torch.as_tensor(a[k0:k0 + VSM_MAX_K] if a.shape[0] else np.zeros((1,) + grid), device=dev)
+            dst = torch.empty_like(src)
+            check(lib().met2_masked_smooth(device, src.shape[0], dims, src.data_ptr(), None if m is None else m.data_ptr(), *targs, dst.data_ptr(),
+                                           norm.data_ptr() if k0 == 0 else None, None, 0, torch.cuda.current_stream(dev).cuda_stream))
+            if a.shape[0]:
+                out[k0:k0 + VSM_MAX_K] = dst.cpu().numpy()
+    return (out[0] if one else out), norm.cpu().numpy()
+
+
+def _launch_vsm(dev, Y, s0, r, W, two_sided, dims, at, mode, dh, E, H, connectivity, radius, taps, ref, first, kmax, count, work):
+    """met2_group_perm_vsm on tensors that are already on `dev` (as _launch_spatial; radius and taps: the host arrays of _checked_taps)"""
+    import torch
+    n, V = Y.shape
+    with torch.cuda.device(dev):
+        check(lib().met2_group_perm_vsm(dev.index or 0, n, V, Y.data_ptr(), s0.data_ptr(), r, W.shape[0], W.data_ptr(), 1 if two_sided else 0,
+                                        (C.c_int32 * 3)(*dims), at.data_ptr(), VSM_MODES[mode], float(dh), float(E), float(H), int(connectivity),
+                                        *_taps_args(radius, taps), None if ref is None else ref.data_ptr(),
+                                        None if first is None else first.data_ptr(), kmax.data_ptr(), None if count is None else count.data_ptr(),
+                                        None if work is None else work.data_ptr(), 0 if work is None else work.numel(),
+                                        torch.cuda.current_stream(dev).cuda_stream))
+
+
+def perm_vsm(Y, s0, W, grid, at, taps, mode="voxel", two_sided=False, dh=1.0, E=0.5, H=2.0, connectivity=6, ref=None, count=None, want_first=False,
+             device=0):
+    """met2_group_perm_vsm on numpy arrays: perm_tfce's Y, s0, W, grid, at; taps: three arrays (smoothing_taps(...)[1]); mode 'voxel' (the
+    pseudo-t itself; two_sided allowed; dh, E, H, connectivity not read) | 'tfce' | 'extent' (on the pseudo-t, one-sided)
+    -> (kmax [K], count or None without ref, first [V] or None without want_first)"""
+    import torch
+    if mode not in VSM_MODES:
+        raise ValueError("mode must be one of %s" % (tuple(VSM_MODES),))
+    radius, taps = _checked_taps(taps)
+    dev = torch.device("cuda", device)
+    Y, s0, W = (np.ascontiguousarray(a, dtype=np.float64) for a in (Y, s0, W))
+    _check_batch(Y, s0, W, ref, count)
+    put = lambda a: torch.as_tensor(a, device=dev)
+    V = Y.shape[1]
+    at = np.ascontiguousarray(at, dtype=np.int32)
+    if at.shape != (V,):
+        raise ValueError("at must be [V]")
+    kmax = torch.empty(W.shape[0], dtype=torch.float64, device=dev)
+    rf = None if ref is None else put(np.ascontiguousarray(ref, dtype=np.float64))
+    cnt = None
+    if rf is not None:
+        cnt = put(np.zeros(V, dtype=np.int32) if count is None else np.ascontiguousarray(count, dtype=np.uint32).view(np.int32))
+    first = torch.empty(V, dtype=torch.float64, device=dev) if want_first else None
+    _launch_vsm(dev, put(Y), put(s0), W.shape[1] - 1, put(W), two_sided, _dims(grid), put(at), mode, dh, E, H, connectivity, radius, taps, rf, first,
+                kmax, cnt, None)
+    return (kmax.cpu().numpy(), None if cnt is None else cnt.cpu().numpy().view(np.uint32), None if first is None else first.cpu().numpy())
+
+
+def _vsm_batch_for(grid, n_vox, mode, budget, most):
+    """the largest K <= most (and <= max_k) whose work space stays within `budget` bytes"""
+    K = max(1, min(int(most), VSM_MAX_K))
+    while K > 1 and vsm_work_bytes(K, grid, n_vox, mode) > budget:
+        K -= 1
+    if vsm_work_bytes(K, grid, n_vox, mode) > budget:
+        raise ValueError("one map on a grid of %s needs %d bytes of work space, more than work_bytes = %d" %
+                         (grid, vsm_work_bytes(1, grid, n_vox, mode), budget))
+    return K
+
+
+def _vsm_test(Yk, sk, W, r, grid, at, mode, dh, E, H, connectivity, two_sided, radius, taps, device, batch_spatial, work_bytes):
+    """the permutation distribution of the pseudo-t (mode 'voxel') or of a spatial statistic of it -> (observed [V], signed in voxel mode;
+    ref [V], what the candidates are compared with: |observed| when two_sided; count [V] uint32; max_dist [P])"""
+    P, V = W.shape[0], Yk.shape[1]
+    if batch_spatial is not None:
+        _, _, obs = batch_spatial(Yk, sk, W[:1], grid, at, mode, dh, E, H, connectivity, None, True, False, radius, taps)
+        obs = np.asarray(obs, dtype=np.float64)
+        ref = np.abs(obs) if two_sided else obs
+        count, max_dist, K = np.zeros(V, dtype=np.uint32), np.empty(P), VSM_MAX_K
+        for k0 in range(0, P, K):
+            km, inc, _ = batch_spatial(Yk, sk, W[k0:k0 + K], grid, at, mode, dh, E, H, connectivity, ref, False, two_sided, radius, taps)
+            max_dist[k0:k0 + K] = km
+            count += np.asarray(inc, dtype=np.uint32)
+        return obs, ref, count, max_dist
+    import torch
+    dev = torch.device("cuda", device)
+    put = lambda a: torch.as_tensor(a, device=dev)
+    K = _vsm_batch_for(grid, V, mode, work_bytes, P)
+    work = torch.empty(vsm_work_bytes(K, grid, V, mode), dtype=torch.uint8, device=dev)
+    Yt, st, Wt, at_t = put(Yk), put(sk), put(W), put(np.ascontiguousarray(at, dtype=np.int32))
+    launch = lambda Wk, two, rf, first, km, cnt: _launch_vsm(dev, Yt, st, r, Wk, two, grid, at_t, mode, dh, E, H, connectivity, radius, taps, rf,
+                                                             first, km, cnt, work)
+    obs_t = torch.empty(V, dtype=torch.float64, device=dev)
+    cnt = torch.zeros(V, dtype=torch.int32, device=dev)
+    md = torch.empty(P, dtype=torch.float64, device=dev)
+    launch(Wt[:1], False, None, obs_t, md[:1], None)
+    ref_t = obs_t.abs() if two_sided else obs_t
+    for k0 in range(0, P, K):
+        launch(Wt[k0:k0 + K], two_sided, ref_t, None, md[k0:k0 + K], cnt)
+    return obs_t.cpu().numpy(), ref_t.cpu().numpy(), cnt.cpu().numpy().view(np.uint32), md.cpu().numpy()
+
+
+def _randomise_vsm(Y, X, c, n_perm, seed, exchange, two_sided, device, batch_stat, tfce, cluster_threshold, cluster_connectivity, grid, at,
+                   batch_spatial, work_bytes, variance_smoothing):
+    """randomise with variance_smoothing (its docstring states the results): every statistic is taken on the pseudo-t"""
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    if Y.ndim != 2:
+        raise ValueError("Y must be [n, V] with one row per subject")
+    sigma = _sigma3(variance_smoothing)
+    radius, taps = smoothing_taps(sigma)
+    if grid is None or at is None:
+        raise ValueError("variance_smoothing needs grid=(nx, ny, nz) and at=[V], the columns' voxel indices in it: the statistic is spatial")
+    if batch_stat is not None and batch_spatial is None:
+        raise ValueError("batch_stat together with variance_smoothing needs batch_spatial, the numpy callable with met2_group_perm_vsm's meaning")
+    if batch_stat is not None and not callable(batch_stat):
+        raise ValueError("batch_stat must be a callable with the entry's meaning")
+    # two_sided is handed on only with a spatial statistic, which refuses it; the grid and `at` are checked either way
+    tfce_opts, grid, at = _spatial_options(tfce, cluster_threshold, cluster_connectivity,
+                                           two_sided and ((tfce is not None and tfce is not False) or cluster_threshold is not None), grid, at,
+                                           Y.shape[1], batch_stat, batch_spatial)
+    x1, _ = partition(X, c)
+    perms = permutation_set(X, c, n_perm, seed, exchange)
+    W, dof = weights(X, c, perms)
+    P, r = W.shape[0], W.shape[1] - 1
+    lim = limits() if batch_spatial is None else {"max_n": Y.shape[0], "max_r": r}
+    if Y.shape[0] > lim["max_n"] or r > lim["max_r"]:
+        raise ValueError("at most %d subjects and %d model columns" % (lim["max_n"], lim["max_r"]))
+    Yr, s0 = residualise(Y, X, c)
+    keep = np.flatnonzero((Yr != 0.0).any(axis=0) & (s0 > TINY * np.sum(Y * Y, axis=0)))
+    Yk, sk = np.ascontiguousarray(Yr[:, keep]), np.ascontiguousarray(s0[keep])
+    V, full = keep.size, Y.shape[1]
+    # Cropping to the tested voxels' bounding box changes no bit: what is cut away holds zeros, and a sum skips a term or adds an exact zero
+    box, at_box = _crop(grid, at[keep])
+    test = lambda mode, dh, E, H, conn, two: _vsm_test(Yk, sk, W, r, box, at_box, mode, dh, E, H, conn, two, radius, taps, device, batch_spatial,
+                                                      work_bytes)
+    if V:
+        t_obs, ref, count, max_dist = test("voxel", 1.0, 0.5, 2.0, 6, two_sided)
+    else:
+        t_obs, ref, count, max_dist = np.zeros(0), np.zeros(0), np.zeros(0, dtype=np.uint32), np.full(P, -np.inf)
+    out = {"tstat": np.zeros(full), "cope": np.zeros(full), "p_uncorrected": np.ones(full), "p_fwe": np.ones(full),
+           "count": np.full(full, P, dtype=np.uint32)}
+    out["tstat"][keep] = t_obs
+    out["cope"][keep] = (x1.T @ Yk).ravel() / float(np.sum(x1 * x1))
+    out["count"][keep] = count
+    out["p_uncorrected"][keep] = count / float(P)
+    out["p_fwe"][keep] = (P - np.searchsorted(np.sort(max_dist), ref, side="left")) / float(P)
+    out.update(max_dist=max_dist, n_perm=P, exhaustive=bool(perms.exhaustive), dof=dof,
+               t_crit=float(np.quantile(max_dist, 0.95)) if V else float("nan"),
+               variance_smoothing={"sigma_vox": sigma, "radius": tuple(int(x) for x in radius)})
+
+    def fill(prefix, stat_key, keys, obs, count_s, md):
+        """one statistic's results, unfolded to the V columns: left-out voxels get 0 and p = 1"""
+        stat, cnt = np.zeros(full), np.full(full, P, dtype=np.uint32)
+        p_unc, p_fwe = np.ones(full), np.ones(full)
+        stat[keep], cnt[keep] = obs, count_s
+        p_unc[keep] = count_s / float(P)
+        p_fwe[keep] = (P - np.searchsorted(np.sort(md), obs, side="left")) / float(P)
+        out.update({stat_key: stat, keys[0]: p_unc, keys[1]: p_fwe, prefix + "_count": cnt, prefix + "_max_dist": md,
+                    prefix + "_crit": float(np.quantile(md, 0.95))})
+
+    nothing = lambda: (np.zeros(V), np.full(V, P, dtype=np.uint32), np.zeros(P))
+    if tfce_opts is not None:
+        dh = tfce_opts["dh"]
+        if dh is None:
+            top = float(np.max(t_obs)) if V else 0.0
+            dh = top / 100.0 if top > 0.0 and np.isfinite(top) else None
+        if dh is None or not V:                                    # nothing rises above zero: every value 0, every p 1, no launch
+            obs, count_s, md = nothing()
+        else:
+            obs, _, count_s, md = test("tfce", dh, tfce_opts["E"], tfce_opts["H"], tfce_opts["connectivity"], False)
+        fill("tfce", "tfce", ("p_tfce_uncorrected", "p_tfce_fwe"), obs, count_s, md)
+        out.update(dh=dh if dh is not None else 0.0, tfce_options={"E": float(tfce_opts["E"]), "H": float(tfce_opts["H"]),
+                                                                   "connectivity": int(tfce_opts["connectivity"])})
+    if cluster_threshold is not None:
+        if V:
+            obs, _, count_s, md = test("extent", float(cluster_threshold), 1.0, 1.0, cluster_connectivity, False)
+        else:
+            obs, count_s, md = nothing()
+        fill("cluster", "cluster_extent", ("p_cluster_uncorrected", "p_cluster_fwe"), obs, count_s, md)
+        out.update(cluster_threshold=float(cluster_threshold), cluster_connectivity=int(cluster_connectivity))
+    return out
+
+
 # ---------------------------------------------------------------- the test
 
 def _randomise_f(Y, X, f_contrast, n_perm, seed, exchange, device, batch_stat, tfce, cluster_threshold, cluster_connectivity, grid, at,
@@ -687,7 +959,7 @@ def _randomise_f(Y, X, f_contrast, n_perm, seed, exchange, device, batch_stat, t
 
 
 def randomise(Y, X, c=None, n_perm=5000, seed=0, exchange="permute", two_sided=False, device=0, batch_stat=None, tfce=None, cluster_threshold=None,
-              cluster_connectivity=26, grid=None, at=None, batch_spatial=None, work_bytes=2 ** 30, f_contrast=None):
+              cluster_connectivity=26, grid=None, at=None, batch_spatial=None, work_bytes=2 ** 30, f_contrast=None, variance_smoothing=None):
     """The permutation test of the t-contrast c in the design X [n, p] at every voxel of Y [n, V] (one row per subject).
     batch_stat: None runs met2_group_perm_stats on `device`; a numpy callable with its meaning -- batch_stat(Y, s0, W, two_sided, t_ref,
     want_first) -> (kmax [K], count increment [V] or None, t_first [V] or None) -- replaces it, and the loop then needs no device.
@@ -710,9 +982,25 @@ def randomise(Y, X, c=None, n_perm=5000, seed=0, exchange="permute", two_sided=F
     is refused.  -> dict(fstat [V], p_uncorrected, p_fwe, count, max_dist, f_crit, dof = (s, n - r), n_perm, exhaustive); there is no cope.
     tfce (dh defaults to a hundredth of the observed maximum of F) and cluster_threshold (a threshold on F) go through met2_group_perm_ftfce
     and add the keys they add above.  batch_stat(Y, s0, W, s, scale, f_ref, want_first) and batch_spatial(Y, s0, W, s, scale, grid, at,
-    mode, dh, E, H, connectivity, ref, want_first) keep their role, with s and scale = dof / s handed on.  Left-out voxels get F = 0, p = 1."""
+    mode, dh, E, H, connectivity, ref, want_first) keep their role, with s and scale = dof / s handed on.  Left-out voxels get F = 0, p = 1.
+    Variance smoothing: variance_smoothing = sigma_vox or (sx, sy, sz), the Gaussian's sigma in VOXELS (randomise -v takes mm): the statistic
+    is the pseudo-t of met2_group_perm_vsm, cope / sqrt(the residual variance pooled over the neighbourhood inside the tested voxels), with
+    the taps of smoothing_taps.  It needs grid and at, as TFCE does (the grid is cropped to the tested voxels' bounding box and nothing more,
+    which changes no bit: what is cut away holds zeros, and a sum skips a term or adds an exact zero).  tstat is then the pseudo-t, as
+    randomise -v's _tstat is, and p_uncorrected, p_fwe, count, max_dist and t_crit are taken on it; cope and dof are unchanged; two_sided is
+    allowed; tfce and cluster_threshold are taken on the pseudo-t (dh from its observed maximum; one-sided).  Adds variance_smoothing =
+    {"sigma_vox": (sx, sy, sz), "radius": (Rx, Ry, Rz)}.  Batches are sized by vsm_work_bytes within work_bytes.  The stand-in, required when
+    batch_stat is given and the only one called: batch_spatial(Y, s0, W, grid, at, mode, dh, E, H, connectivity, ref, want_first, two_sided,
+    radius, taps) with mode 'voxel' | 'tfce' | 'extent'.  Together with f_contrast it is refused: FSL smooths the variance for t only, and a
+    pseudo-F is not defined here.  Parity with randomise -v is unpinned (the module's docstring says where the definitions may differ)."""
     if (c is None) == (f_contrast is None):
         raise ValueError("give exactly one of c (a t-contrast) and f_contrast (an F-contrast [s, p])")
+    if variance_smoothing is not None:
+        if f_contrast is not None:
+            raise ValueError("variance_smoothing together with f_contrast is refused: FSL randomise smooths the variance for t statistics only, "
+                             "and a pseudo-F is not defined here")
+        return _randomise_vsm(Y, X, c, n_perm, seed, exchange, two_sided, device, batch_stat, tfce, cluster_threshold, cluster_connectivity, grid,
+                              at, batch_spatial, work_bytes, variance_smoothing)
     if f_contrast is not None:
         if two_sided:
             raise ValueError("an F-contrast has no sides: two_sided=True is refused")

@@ -1017,7 +1017,7 @@ def motor_maps_to_template(path_to_save_data, path_to_template, path_to_world=No
     return out
 
 
-def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_mask=None, f_contrast=None, **options):
+def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_mask=None, f_contrast=None, variance_smoothing_mm=None, **options):
     """Voxel-wise group statistics of one map over several subjects, after motor_maps_to_template brought every subject's maps onto one
     template grid.  paths_to_save_data: one path_to_save_data per subject, in the order of the rows of the design X [n, p]; `quantity`: one of
     STAT_QUANTITIES; c: the t-contrast.  Every subject's <stem>_in_template.nii.gz is loaded; differing shapes or affines are refused.  The
@@ -1036,6 +1036,10 @@ def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_m
     f_contrast [s, p] with c = None: the F-test of its rows at once.  Written then: <quantity>_fstat.nii.gz, <quantity>_p_unc.nii.gz,
     <quantity>_p_fwe.nii.gz, <quantity>_max_dist.txt, the TFCE / cluster files under the names above (taken on F), and the report with s, the
     degrees of freedom (s, n - r), f_crit and the counts at p <= 0.05; no _tstat and no _cope file.  Parity with randomise -f is unpinned.
+    variance_smoothing_mm = sigma in mm (randomise -v): the variance is smoothed with a Gaussian of sigma / (the voxel size along the axis)
+    voxels per axis, the voxel sizes being the norms of the columns of the template's affine.  The same files are written; <quantity>_tstat
+    then holds the pseudo-t, every p-value is taken on it, and the report gains sigma in mm and in voxels, the radii and a line that says so.
+    Parity with randomise -v is unpinned.
     -> the dict of group_stats_filter."""
     from . import nifti
     if quantity not in STAT_QUANTITIES:
@@ -1063,6 +1067,11 @@ def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_m
         if m.shape != inside.shape:
             raise ValueError("the mask does not lie on the template grid")
         inside = inside & m
+    if variance_smoothing_mm is not None:
+        if not np.isfinite(variance_smoothing_mm) or variance_smoothing_mm < 0:
+            raise ValueError("variance_smoothing_mm must be a finite sigma >= 0 in mm")
+        voxel_mm = np.sqrt(np.sum(np.asarray(affine, dtype=np.float64)[:3, :3] ** 2, axis=0))
+        options = dict(options, variance_smoothing=tuple(float(variance_smoothing_mm) / voxel_mm))
     out = group_stats_filter(np.stack(vols), X, c, mask=inside, f_contrast=f_contrast, **options)
     files = (("tstat", "tstat"), ("cope", "cope")) if f_contrast is None else (("fstat", "fstat"),)
     for key, name in files + (("p_uncorrected", "p_unc"), ("p_fwe", "p_fwe")):
@@ -1078,6 +1087,11 @@ def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_m
     lines = head + ["permutations: %d (%s)" % (out["n_perm"], "exhaustive" if out["exhaustive"] else "drawn at random"),
                     "voxels tested: %d" % int(out["mask"].sum()), crit,
                     "voxels with p_fwe <= 0.05: %d" % int(((out["p_fwe"] <= 0.05) & out["mask"]).sum())]
+    if "variance_smoothing" in out:
+        v = out["variance_smoothing"]
+        lines += ["variance smoothing: sigma = %.6g mm = (%.6g, %.6g, %.6g) voxels, radius = (%d, %d, %d) voxels" %
+                  ((float(variance_smoothing_mm),) + tuple(v["sigma_vox"]) + tuple(v["radius"])),
+                  "%s_tstat holds the pseudo-t (cope / sqrt(smoothed variance)); every p-value and critical value is taken on it" % quantity]
     if "tfce" in out:
         for key, name in (("tfce", "tfce"), ("p_tfce_uncorrected", "p_tfce_unc"), ("p_tfce_fwe", "p_tfce_fwe")):
             nifti.save(nifti.NiftiImage(out[key], affine), path_to_out + quantity + "_" + name + ".nii.gz")

@@ -2,6 +2,7 @@
 """Timing of the voxel-wise permutation test (met2_group_perm_stats, group.randomise) on the device, written to profiles/group_bench.json:
     python3 scripts/bench_group.py [--perms 5000] [--voxels 250000] [--subjects 32] [--reps 5] [--numpy-candidates 32] [--out FILE]
                                    [--tfce [--grid 96 112 96] [--numpy-seconds 60] [--device-only]] [--fstat [--grid 96 112 96]]
+                                   [--vsm [--sigma 2.5] [--grid 96 112 96]]
 The case: two groups of subjects / 2 (r = 2 model columns), seeded normal data with a group difference in 1 % of the voxels, `perms`
 permutations drawn at random, one map.
   kernels     the launches of the whole set (ceil(perms / max_k) calls of the entry with t_ref and count, inputs resident on the device), between
@@ -26,6 +27,13 @@ profiles/group_f_bench.json:
   kernels     the launches of the whole set through met2_group_perm_fstats, as above, and in the same run the t entry (met2_group_perm_stats,
               group 1 against group 2) at the same n, r, V and P: the yardstick.  The F kernel carries r sums per candidate, the t kernel r + 1.
   randomise   group.randomise(f_contrast=...) end to end, and with tfce=True on the grid (--grid; the voxels an ellipsoid's, as with --tfce)
+With --vsm the test is the one on the pseudo-t (variance smoothing, --sigma 2.5 voxels: a radius of 8), on the grid of --tfce, written to
+profiles/group_vsm_bench.json, everything measured in one run on one build:
+  kernels     the whole set through met2_group_perm_vsm in voxel mode (batches of at most 32 candidates, the work space handed in), and beside
+              it the plain t entry (met2_group_perm_stats, batches of 256) on the same data
+  passes      the three smoothing passes alone (met2_masked_smooth without N on 32 maps of the cropped grid), per call; a pass reads and
+              writes every cell once, 16 bytes per cell and pass, set against the 8 TB/s HBM peak that bench.py uses
+  randomise   group.randomise(variance_smoothing=sigma) end to end, and beside it the plain call and the tfce=True call on the same data
 A record, not a pass mark."""
 import argparse
 import importlib
@@ -43,6 +51,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
 PKG = "multicomponent-t2-toolbox_amd"
 FP64_VECTOR_PEAK = 78.6e12                                         # bench.py's FP64_VECTOR_PEAK_TFLOPS
+HBM_PEAK_GBPS = 8000.0                                             # bench.py's HBM_PEAK_GBPS
 THREADS = 16
 
 
@@ -200,6 +209,97 @@ def fstat_case(a, group):
     print(json.dumps(rec))
 
 
+def vsm_case(a, group):
+    n, V, P, grid, sigma = a.subjects, a.voxels, a.perms, tuple(a.grid), a.sigma
+    at = ellipsoid(grid, V)
+    g = np.repeat([1.0, 0.0], n // 2)
+    X, c = np.stack([g, 1.0 - g], axis=1), np.array([1.0, -1.0])
+    rng = np.random.default_rng(0)
+    Y = rng.standard_normal((n, V))
+    centre = np.argsort(np.abs(at - at[V // 2]))[: V // 100]      # 1 % of the voxels around the middle one
+    Y[: n // 2, centre] += 1.5
+    W, dof = group.weights(X, c, group.permutation_set(X, c, P, 0, "permute"))
+    Yr, s0 = group.residualise(Y, X, c)
+    P, r = W.shape[0], W.shape[1] - 1
+    box, at_box = group._crop(grid, at)
+    radius, taps = group.smoothing_taps(sigma)
+    dev = torch.device("cuda", 0)
+    put = lambda x: torch.as_tensor(x, device=dev)
+    Yt, st, Wt, at_t = put(Yr), put(s0), put(W), put(at_box)
+    K = group._vsm_batch_for(box, V, "voxel", 2 ** 30, P)
+    work = torch.empty(group.vsm_work_bytes(K, box, V, "voxel"), dtype=torch.uint8, device=dev)
+    obs = torch.empty(V, dtype=torch.float64, device=dev)
+    md = torch.empty(P, dtype=torch.float64, device=dev)
+    cnt = torch.zeros(V, dtype=torch.int32, device=dev)
+    vsm = lambda Wk, ref, first, km, count: group._launch_vsm(dev, Yt, st, r, Wk, False, box, at_t, "voxel", 1.0, 0.5, 2.0, 6, radius, taps, ref,
+                                                              first, km, count, work)
+    vsm(Wt[:1], None, obs, md[:1], None)
+    t_obs = torch.empty(V, dtype=torch.float64, device=dev)
+    group._launch(dev, Yt, st, r, Wt[:1], False, None, t_obs, md[:1], None)
+    Kt = group.limits()["max_k"]
+
+    def vsm_set():
+        for k0 in range(0, P, K):
+            vsm(Wt[k0:k0 + K], obs, None, md[k0:k0 + K], cnt)
+
+    def t_set():
+        for k0 in range(0, P, Kt):
+            group._launch(dev, Yt, st, r, Wt[k0:k0 + Kt], False, t_obs, None, md[k0:k0 + Kt], cnt)
+
+    G = int(np.prod(box))
+    maps = torch.rand((K, G), dtype=torch.float64, device=dev)
+    out = torch.empty_like(maps)
+    mask = torch.zeros(G, dtype=torch.uint8, device=dev)
+    mask[at_t.long()] = 1
+    ping = torch.empty(group.vsm_work_bytes(K, box), dtype=torch.uint8, device=dev)
+    import ctypes as C
+    lib = importlib.import_module(PKG + "._lib")
+    targs, dims = group._taps_args(radius, taps), (C.c_int32 * 3)(*box)
+
+    def passes():
+        lib.check(lib.lib().met2_masked_smooth(0, K, dims, maps.data_ptr(), mask.data_ptr(), *targs, out.data_ptr(), None, ping.data_ptr(),
+                                               ping.numel(), torch.cuda.current_stream(dev).cuda_stream))
+
+    vsm_ms, t_ms, pass_ms = events_ms(vsm_set, a.reps), events_ms(t_set, a.reps), events_ms(passes, a.reps)
+    kw = dict(n_perm=P, seed=0)
+    sp = dict(grid=grid, at=at)
+    group.randomise(Y, X, c, variance_smoothing=sigma, **kw, **sp)
+    group.randomise(Y, X, c, tfce=True, **kw, **sp)
+    plain_s, vsm_s, tfce_s = [], [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        group.randomise(Y, X, c, **kw)
+        t1 = time.perf_counter()
+        res = group.randomise(Y, X, c, variance_smoothing=sigma, **kw, **sp)
+        t2 = time.perf_counter()
+        res_t = group.randomise(Y, X, c, tfce=True, **kw, **sp)
+        plain_s.append(t1 - t0)
+        vsm_s.append(t2 - t1)
+        tfce_s.append(time.perf_counter() - t2)
+    med = lambda x: float(np.median(x))
+    pass_bytes = 3 * 16.0 * K * G
+    rec = {"case": {"perms": P, "voxels": V, "subjects": n, "r": r, "grid": list(grid), "cropped_grid": list(box), "sigma_vox": sigma,
+                    "radius": list(radius), "maps_per_launch": K, "launches": (P + K - 1) // K},
+           "kernels_vsm_voxel": {"seconds": med(vsm_ms) * 1e-3, "all_ms": vsm_ms},
+           "kernels_t_same_data": {"seconds": med(t_ms) * 1e-3, "all_ms": t_ms, "maps_per_launch": Kt},
+           "vsm_over_t": med(vsm_ms) / med(t_ms),
+           "smoothing_passes": {"maps": K, "cells_per_map": G, "seconds_three_passes": med(pass_ms) * 1e-3, "all_ms": pass_ms,
+                                "bytes_three_passes": pass_bytes, "achieved_gb_per_s": pass_bytes / (med(pass_ms) * 1e-3) / 1e9,
+                                "hbm_peak_gb_per_s": HBM_PEAK_GBPS, "share_of_hbm_peak": pass_bytes / (med(pass_ms) * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                                "note": "16 bytes per cell and pass by the algorithm; the halo's re-reads are not counted"},
+           "randomise_vsm": {"seconds": med(vsm_s), "all_s": vsm_s, "t_crit": res["t_crit"], "voxels_p_fwe_le_0.05": int((res["p_fwe"] <= 0.05).sum())},
+           "randomise_t_only": {"seconds": med(plain_s), "all_s": plain_s},
+           "randomise_tfce": {"seconds": med(tfce_s), "all_s": tfce_s, "voxels_p_tfce_fwe_le_0.05": int((res_t["p_tfce_fwe"] <= 0.05).sum()),
+                              "voxels_p_fwe_le_0.05": int((res_t["p_fwe"] <= 0.05).sum())},
+           "device": torch.cuda.get_device_name(0), "reps": a.reps}
+    path = a.out if a.out != os.path.join(ROOT, "profiles", "group_bench.json") else os.path.join(ROOT, "profiles", "group_vsm_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--perms", type=int, default=5000)
@@ -213,12 +313,16 @@ def main():
     ap.add_argument("--numpy-seconds", type=float, default=60.0)
     ap.add_argument("--device-only", action="store_true")
     ap.add_argument("--fstat", action="store_true")
+    ap.add_argument("--vsm", action="store_true")
+    ap.add_argument("--sigma", type=float, default=2.5)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "the benchmark needs a GPU"
     group = importlib.import_module(PKG + ".group")
     import group_numpy as gn
     if a.fstat:
         return fstat_case(a, group)
+    if a.vsm:
+        return vsm_case(a, group)
     if a.tfce:
         return tfce_case(a, group, gn)
     n, V, P = a.subjects, a.voxels, a.perms

@@ -6,7 +6,7 @@ Registers, spills and occupancy from hipcc -Rpass-analysis=kernel-resource-usage
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRCS = [os.path.join(ROOT, "multicomponent-t2-toolbox_amd", "csrc", f) for f in ("met2_hip.hip", "met2_dictionary.hip", "met2_prefilter.hip", "met2_roi_metrics.hip", "met2_fit_x2_nb1.hip", "met2_fit_x2_nb2.hip", "met2_fit_x2_second.hip", "met2_fit_nnls_lcurve.hip",
-                                                                                  "met2_fit_gcv.hip", "met2_fit_bayes.hip", "met2_tv.hip", "met2_eval.hip", "met2_mppca.hip", "met2_gibbs.hip", "met2_bias.hip", "met2_bet.hip", "met2_seg.hip", "met2_pve.hip", "met2_stats.hip", "met2_rician.hip", "met2_resample.hip", "met2_register.hip", "met2_warp.hip", "met2_group.hip", "met2_tfce.hip")]
+                                                                                  "met2_fit_gcv.hip", "met2_fit_bayes.hip", "met2_tv.hip", "met2_eval.hip", "met2_mppca.hip", "met2_gibbs.hip", "met2_bias.hip", "met2_bet.hip", "met2_seg.hip", "met2_pve.hip", "met2_stats.hip", "met2_rician.hip", "met2_resample.hip", "met2_register.hip", "met2_warp.hip", "met2_group.hip", "met2_tfce.hip", "met2_group_vsm.hip")]
 TAG = sys.argv[1] if len(sys.argv) > 1 else "r05"
 if len(sys.argv) > 2:
     SRCS = [s for s in SRCS if os.path.basename(s) in sys.argv[2:]]
