@@ -1442,6 +1442,19 @@ int met2_group_perm_fstats(int32_t device, int32_t n, int64_t n_vox, const doubl
  *             pow((double)e, E) * pow(h, H), held to an accuracy bound only.  out = 0 where level = 0.
  *   MET2_TFCE_MODE_EXTENT:  dh is THE threshold h: out(v) = the size of v's component of {t >= h} as a double, 0 outside it.  E and H are
  *             not read.
+ *   MET2_TFCE_MODE_MASS:    cluster mass (an extension; additive, the ABI number stays).  dh is THE threshold h, as in extent mode; E and H
+ *             are not read.  Membership is extent mode's: t(v) >= h, inside the mask, t a number.  A member contributes the integer
+ *             q(v) = (int64) rint(min(t(v), MET2_TFCE_MASS_T_CAP) * 2^MET2_TFCE_MASS_FRAC_BITS), ties to even; the scaling is exact and
+ *             +infinity saturates at the cap.  For a member, out(v) = (double)(the sum of q over v's component) * 2^-24: the sum is taken in
+ *             64-bit integers (by integer atomic adds at the component's root, so it does not depend on the order), converted ONCE, round to
+ *             nearest even, and the scaling is exact.  out(v) = 0 elsewhere.  The sum cannot overflow: q <= 2^38 and a grid of at most
+ *             MET2_TFCE_MASS_MAX_G = 2^24 voxels give at most 2^62; a larger grid is MET2_E_UNSUPPORTED in mass mode only, before any device
+ *             work (group.py crops the grid to the tested voxels' bounding box).  Consequence: as long as nothing saturates,
+ *             |out - the exact sum of t over the component| <= e * 2^-25 + one rounding of the result, e the component's size (measured on the
+ *             observed maps of the planted case of tests/tools/tfce_numpy.py against a long double sum: at worst 0.9995 of e * 2^-25).  An
+ *             int64 numpy sum reproduces the bits (tests/tools/cluster_mass_numpy.py).  Every permutation is quantised the same way, so
+ *             the test stays a valid permutation test -- of the quantised statistic.  Parity with randomise -C / -S is unpinned: FSL sums
+ *             the raw doubles and was not available.
  * met2_tfce: maps [K][nx][ny][nz] -> out [K][nx][ny][nz] (must not overlap maps) and, when not NULL, kmax [K] = max over the grid of out
  *   (>= 0; by an integer atomic max per block and map on the key of met2_group_perm_stats).  A map's bits depend on that map, the mask and the
  *   parameters alone: not on K, its place in the batch or the other maps.
@@ -1462,7 +1475,7 @@ int met2_group_perm_fstats(int32_t device, int32_t n, int64_t n_vox, const doubl
  *   allocates and frees it; else a device block of work_bytes >= that (MET2_E_INVALID if smaller).  Either way the call returns after its
  *   work is done.
  * DEVICE pointers throughout but dims.  met2_tfce_limits is host only.
- * Limits.  1 <= K <= MET2_TFCE_MAX_K, nx, ny, nz >= 1 and nx ny nz < 2^31 (MET2_E_UNSUPPORTED beyond the upper ends); the group entry's
+ * Limits.  1 <= K <= MET2_TFCE_MAX_K, nx, ny, nz >= 1 and nx ny nz < 2^31, in mass mode <= 2^24 (MET2_E_UNSUPPORTED beyond the upper ends); the group entry's
  * n, r as above.  MET2_E_INVALID: a mode or connectivity other than those named, dh not finite or <= 0, in TFCE mode E not finite or <= 0 or
  * H not finite or < 0, K or an axis < 1, a NULL required pointer, ref without count.  Every such check comes before any device work: the
  * outputs are then untouched. */
@@ -1470,6 +1483,10 @@ int met2_group_perm_fstats(int32_t device, int32_t n, int64_t n_vox, const doubl
 #define MET2_TFCE_MAX_STEPS 1024
 #define MET2_TFCE_MODE_TFCE 0
 #define MET2_TFCE_MODE_EXTENT 1
+#define MET2_TFCE_MODE_MASS 3              /* 2 is MET2_GROUP_VSM_MODE_VOXEL, which met2_tfce refuses */
+#define MET2_TFCE_MASS_FRAC_BITS 24
+#define MET2_TFCE_MASS_T_CAP 16384.0
+#define MET2_TFCE_MASS_MAX_G (1 << 24)
 int met2_tfce_limits(int32_t *max_k, int32_t *max_steps);
 int met2_tfce_work_bytes(int32_t K, const int32_t dims[3], int64_t n_vox, int64_t *bytes);
 int met2_tfce(int32_t device, int32_t K, const int32_t dims[3], const double *maps, const uint8_t *mask, int32_t mode, double dh, double E,
@@ -1512,7 +1529,7 @@ int met2_group_perm_ftfce(int32_t device, int32_t n, int64_t n_vox, const double
  *   b and rho of the batch to dense maps; the three passes; the pseudo-t into a dense map (0 off the mask); then by mode
  *   MET2_GROUP_VSM_MODE_VOXEL: s(k, v) = pt(k, at[v]):  kmax[k] = max_v s(k, v);  first[v] = s(0, v);  count[v] += #{k: s(k, v) >= ref[v]}, with
  *     the meaning they have for met2_group_perm_tfce; dh, E, H and connectivity are not read;
- *   MET2_TFCE_MODE_TFCE, MET2_TFCE_MODE_EXTENT: met2_group_perm_tfce's transform and gather on the pseudo-t maps, unchanged.  One-sided:
+ *   MET2_TFCE_MODE_TFCE, MET2_TFCE_MODE_EXTENT, MET2_TFCE_MODE_MASS: met2_group_perm_tfce's transform and gather on the pseudo-t maps, unchanged.  One-sided:
  *     two_sided = 1 with a spatial mode is MET2_E_INVALID.
  *   Late errors as for met2_group_perm_tfce: an `at` that is not strictly ascending inside the grid is MET2_E_INVALID with kmax, first and
  *   count untouched; a bound of the union-find that ran out is MET2_E_HIP.
@@ -1525,7 +1542,7 @@ int met2_group_perm_ftfce(int32_t device, int32_t n, int64_t n_vox, const double
  * pass, and lines across it (any output may be NULL).
  * Limits.  1 <= K <= MET2_GROUP_VSM_MAX_K and R_a <= MET2_GROUP_VSM_MAX_RADIUS (MET2_E_UNSUPPORTED beyond), the grid and n, r as for
  * met2_group_perm_tfce.  MET2_E_INVALID: a negative radius, a tap that is not finite or < 0, a centre tap <= 0, out overlapping maps, norm_out
- * overlapping either, a mode other than the three named, a NULL required pointer, ref without count, and what met2_group_perm_tfce refuses.
+ * overlapping either, a mode other than the four named, a NULL required pointer, ref without count, and what met2_group_perm_tfce refuses.
  * Every such check comes before any device work: the outputs are then untouched.
  * Parity with FSL randomise -v is unpinned (FSL was not available).  The definitions may differ from FSL's in the truncation of the kernel (the
  * caller's taps; group.py cuts at 3 sigma), in the width FSL gives the kernel it smooths its variance image with, and in the normalisation by

@@ -42,7 +42,7 @@ ejcanalesr/multicomponent-T2-toolbox).  Package layout:
                             invert: the inverse field by fixed-point iteration, invert_step / jacobian: its step and the determinant with the count of folded voxels
   group.py                  partition / residualise / permutation_set / weights: a design and a t-contrast as the weight rows of met2_group_perm_stats;
                             perm_stats: the entry on arrays; randomise: the permutation test (uncorrected and FWE-corrected p-values) (csrc/met2_group.hip);
-                            tfce / cluster_extent: the spatial statistics of maps; randomise(tfce=..., cluster_threshold=...): their permutation test (csrc/met2_tfce.hip)
+                            tfce / cluster_extent / cluster_mass: the spatial statistics of maps; randomise(tfce=..., cluster_threshold=..., cluster_mass_threshold=...): their permutation test (csrc/met2_tfce.hip)
   rician.py                 bias / step / invert: the kernels of the Rician noise-floor correction one by one (csrc/met2_rician.hip; Met2Plan.fit_rician and
                             noise_sigma, rician='iterative' | 'direct' of the drivers)
   mppca.py                  mppca_stages: the MP-PCA denoiser with what each of its steps leaves (tests and diagnostics)

@@ -16,7 +16,7 @@
 //   vs_combine_kernel    sigma^2 = S(rho) / N, pseudo-t = b / sqrt(sigma^2), |.| when two-sided, written over S(rho) at mask voxels, 0 elsewhere
 //   vs_gather_kernel     voxel mode: tf_gather_kernel's first, count and maxima on the pseudo-t, unscaled, with a value that is not a number
 //                        passed over by the maximum
-//   tf_transform, tf_gather_kernel   (tfce_kernel.hpp) the spatial modes, unchanged
+//   tf_transform, tf_gather_kernel   (tfce_kernel.hpp) the spatial modes (TFCE, cluster extent, cluster mass), unchanged
 // Three launches for the three axes: a pass must be complete over the whole grid before the next starts (what else was
 // tried).  No floating-point atomic; every loop is bounded by a shape or a constant.  Compiled without contraction.
 #include <hip/hip_runtime.h>
@@ -224,7 +224,10 @@ VsWork vs_take(DeviceWork &w, int K, int64_t G, bool group, bool forest)
 }
 size_t vs_bytes(const VsWork &t) { return t.mask.off + t.mask.bytes; }
 
-bool vs_mode_ok(int mode) { return mode == MET2_TFCE_MODE_TFCE || mode == MET2_TFCE_MODE_EXTENT || mode == MET2_GROUP_VSM_MODE_VOXEL; }
+bool vs_mode_ok(int mode)
+{
+    return mode == MET2_TFCE_MODE_TFCE || mode == MET2_TFCE_MODE_EXTENT || mode == MET2_TFCE_MODE_MASS || mode == MET2_GROUP_VSM_MODE_VOXEL;
+}
 
 bool vs_overlap(const void *a, size_t na, const void *b, size_t nb)
 {
@@ -261,7 +264,7 @@ extern "C" int met2_group_vsm_work_bytes(int32_t K, const int32_t dims[3], int64
     const int rc = tf_check(K, dims, MET2_TFCE_MODE_EXTENT, 1.0, 1.0, 1.0, 6, &g, &p);
     if (rc != MET2_OK) return rc;
     if (!bytes || n_vox < 0) return fail(MET2_E_INVALID, "bytes is NULL or n_vox < 0");
-    if (!vs_mode_ok(mode)) return fail(MET2_E_INVALID, "mode must be MET2_TFCE_MODE_TFCE, MET2_TFCE_MODE_EXTENT or MET2_GROUP_VSM_MODE_VOXEL");
+    if (!vs_mode_ok(mode)) return fail(MET2_E_INVALID, "mode must be MET2_TFCE_MODE_TFCE, MET2_TFCE_MODE_EXTENT, MET2_TFCE_MODE_MASS or MET2_GROUP_VSM_MODE_VOXEL");
     DeviceWork w(nullptr);
     *bytes = (int64_t)vs_bytes(vs_take(w, K, g.G, n_vox > 0, mode != MET2_GROUP_VSM_MODE_VOXEL));
     return MET2_OK;
@@ -303,7 +306,7 @@ extern "C" int met2_group_perm_vsm(int32_t device, int32_t n, int64_t n_vox, con
     if (r < 1 || n_vox < 1) return fail(MET2_E_INVALID, "r and n_vox must be >= 1");
     if (n <= r) return fail(MET2_E_INVALID, "n must exceed r: no degree of freedom is left");
     if (two_sided != 0 && two_sided != 1) return fail(MET2_E_INVALID, "two_sided must be 0 or 1");
-    if (!vs_mode_ok(mode)) return fail(MET2_E_INVALID, "mode must be MET2_TFCE_MODE_TFCE, MET2_TFCE_MODE_EXTENT or MET2_GROUP_VSM_MODE_VOXEL");
+    if (!vs_mode_ok(mode)) return fail(MET2_E_INVALID, "mode must be MET2_TFCE_MODE_TFCE, MET2_TFCE_MODE_EXTENT, MET2_TFCE_MODE_MASS or MET2_GROUP_VSM_MODE_VOXEL");
     const bool voxel = mode == MET2_GROUP_VSM_MODE_VOXEL;
     if (!voxel && two_sided)
         return fail(MET2_E_INVALID, "the spatial modes are one-sided: on |t| a positive and a negative blob would fuse into one cluster");

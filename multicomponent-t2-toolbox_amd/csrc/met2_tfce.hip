@@ -1,5 +1,5 @@
-// met2_tfce.hip -- met2_tfce_limits, met2_tfce_work_bytes, met2_tfce, met2_group_perm_tfce, met2_group_perm_ftfce (the same on F): threshold-free cluster enhancement and cluster
-// extent of a batch of statistic maps, and both as the statistic of the voxel-wise permutation test (include/met2_hip.h states the
+// met2_tfce.hip -- met2_tfce_limits, met2_tfce_work_bytes, met2_tfce, met2_group_perm_tfce, met2_group_perm_ftfce (the same on F): threshold-free cluster enhancement, cluster
+// extent and cluster mass of a batch of statistic maps, and each as the statistic of the voxel-wise permutation test (include/met2_hip.h states the
 // definitions and the contract; group.py holds the loop over batches).  The kernels, the work space's layout and the walk over the levels
 // are tfce_kernel.hpp's, which met2_group_vsm.hip shares: that header describes them.  Compiled without contraction.
 #include <hip/hip_runtime.h>

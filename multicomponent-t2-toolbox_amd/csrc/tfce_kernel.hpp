@@ -1,4 +1,4 @@
-// tfce_kernel.hpp -- the kernels and host helpers of the spatial statistics (threshold-free cluster enhancement, cluster extent), stated once
+// tfce_kernel.hpp -- the kernels and host helpers of the spatial statistics (threshold-free cluster enhancement, cluster extent and mass), stated once
 // for the two units that run them: met2_tfce.hip (met2_tfce, met2_group_perm_tfce, met2_group_perm_ftfce) and met2_group_vsm.hip
 // (met2_group_perm_vsm: the same transform and gather on the pseudo-t).  include/met2_hip.h states the definitions.  Written from that
 // statement and from Smith & Nichols (NeuroImage 44:83-98, 2009); the lock-free union is the atomic-min hooking of Playne & Hawick's and
@@ -13,6 +13,8 @@
 //                      hands it to its root.  Integer adds at roots, which this kernel does not change: the sums do not depend on the order;
 //                      the lanes of a wave that add to one root are summed by a butterfly first and make one atomic
 //   tf_sum_kernel      level j: a voxel of level >= j adds its root's term e^E h_j^H to its own sum (it alone writes it) and points at its root
+//   tf_mass_*_kernel   cluster mass: the level kernel's sibling that keeps q(v), the add at the roots, the spread and the roots' own conversion
+//                      (described where they stand)
 //   tf_finish_kernel   met2_tfce: out = dh * sum in place, and the map's maximum: one integer atomic max per (block, map) on gp_key
 //   tf_gather_kernel   the group entry: a thread owns a masked voxel for all K maps: first, count, and the maxima as above
 // Three launches per level and no host round trip between them; the level loop is the host's, bounded by MET2_TFCE_MAX_STEPS.  Every device
@@ -212,6 +214,113 @@ __global__ void __launch_bounds__(TF_BLOCK) tf_sum_kernel(TfGrid g, int j, doubl
     f.sum[base + v] = rn_add(f.sum[base + v], term);
 }
 
+// ---- cluster mass (MET2_TFCE_MODE_MASS): the sum of the statistic over a voxel's component of {t >= h}, in 64-bit fixed point ------------
+// A voxel's 8-byte sum cell holds, in turn: the integer q(v) (tf_mass_level_kernel); at a root, the component's integer total
+// (tf_mass_add_kernel); the double out(v) (tf_mass_spread_kernel for the others, tf_mass_root_kernel for the roots).  Integer adds only, so
+// the total does not depend on the order; the one conversion to double rounds to nearest even and the scaling by 2^-24 is exact.
+
+__device__ __forceinline__ double tf_mass_value(unsigned long long total)
+{
+    return rn_mul((double)(long long)total, 1.0 / (double)(1 << MET2_TFCE_MASS_FRAC_BITS));
+}
+
+// tf_level_kernel with one level (dh is the threshold), but the sum cell takes the bits of q(v) = rint(min(t, cap) 2^24), 0 for a non-member
+__global__ void __launch_bounds__(TF_BLOCK) tf_mass_level_kernel(TfGrid g, const double *__restrict__ maps, const uint8_t *__restrict__ mask, double dh, TfForest f)
+{
+    __shared__ int wtop[TF_WAVES];
+    const int64_t v64 = (int64_t)blockIdx.x * TF_BLOCK + threadIdx.x;
+    const bool live = v64 < g.G;
+    const int v = live ? (int)v64 : 0;
+    const int64_t cell = (int64_t)blockIdx.y * g.G + v;
+    int lo = 0;
+    long long q = 0;
+    if (live && (!mask || mask[v])) {
+        const double t = maps[cell];
+        if (rn_mul(1.0, dh) <= t) {                                 // not a number: the test fails
+            lo = 1;
+            const double c = t < MET2_TFCE_MASS_T_CAP ? t : MET2_TFCE_MASS_T_CAP;       // +infinity saturates
+            q = __double2ll_rn(rn_mul(c, (double)(1 << MET2_TFCE_MASS_FRAC_BITS)));      // the product is exact; ties to even; <= 2^38
+        }
+    }
+    if (live) {
+        f.level[cell] = (uint16_t)lo;
+        f.parent[cell] = v;
+        f.size[cell] = 0u;
+        ((long long *)f.sum)[cell] = q;                            // after t was read: maps may be the sum buffer itself
+    }
+    int m = lo;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int other = __shfl_xor(m, o);
+        if (other > m) m = other;
+    }
+    if ((threadIdx.x & 63) == 0) wtop[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < TF_WAVES; ++w)
+            if (wtop[w] > m) m = wtop[w];
+        if (m > 0 && m > tf_load(f.flags)) atomicMax(f.flags, m);
+    }
+}
+
+// every member that is not its own root adds its q to its root's cell.  The forest is fixed here; a cell that is no root's is read by its owner
+// alone, and the adds go to roots only.  As in tf_count_kernel the wave's lanes that share a root make ONE atomic: a round per distinct root.
+__global__ void __launch_bounds__(TF_BLOCK) tf_mass_add_kernel(TfGrid g, TfForest f)
+{
+    const int64_t v64 = (int64_t)blockIdx.x * TF_BLOCK + threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.y * g.G;
+    unsigned long long *cells = (unsigned long long *)f.sum + base;
+    unsigned long long give = 0ull;
+    int root = -1;                                                 // -1: nothing to add.  No lane leaves before the wave's exchange below
+    if (v64 < g.G) {
+        const int v = (int)v64;
+        if (f.level[base + v] == 1) {
+            const int r = tf_find(f.parent + base, v, g.G, f.flags);
+            if (r >= 0 && r != v) {
+                root = r;
+                give = cells[v];
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63;
+    for (int round = 0; round < 64; ++round) {
+        const unsigned long long todo = __ballot(root >= 0);
+        if (todo == 0ull) break;
+        const int lead = __ffsll((long long)todo) - 1;
+        const int r0 = __shfl(root, lead);
+        const bool mine = root == r0;
+        const unsigned long long part = wave_sum_xor(mine ? give : 0ull);      // 64 lanes of at most 2^38: no overflow
+        if (lane == lead) atomicAdd(cells + r0, part);
+        if (mine) root = -1;
+    }
+}
+
+// every member that is not its own root takes its root's integer total and writes the double over its own cell; roots write nothing here,
+// so no cell is read and rewritten in one launch
+__global__ void __launch_bounds__(TF_BLOCK) tf_mass_spread_kernel(TfGrid g, TfForest f)
+{
+    const int64_t v64 = (int64_t)blockIdx.x * TF_BLOCK + threadIdx.x;
+    if (v64 >= g.G) return;
+    const int v = (int)v64;
+    const int64_t base = (int64_t)blockIdx.y * g.G;
+    if (f.level[base + v] != 1) return;
+    const int root = tf_find(f.parent + base, v, g.G, f.flags);
+    if (root < 0 || root == v) return;
+    f.sum[base + v] = tf_mass_value(((const unsigned long long *)f.sum)[base + root]);
+}
+
+// the roots convert their own totals in place
+__global__ void __launch_bounds__(TF_BLOCK) tf_mass_root_kernel(TfGrid g, TfForest f)
+{
+    const int64_t v64 = (int64_t)blockIdx.x * TF_BLOCK + threadIdx.x;
+    if (v64 >= g.G) return;
+    const int v = (int)v64;
+    const int64_t cell = (int64_t)blockIdx.y * g.G + v;
+    if (f.level[cell] != 1 || f.parent[cell] != v) return;
+    f.sum[cell] = tf_mass_value(((const unsigned long long *)f.sum)[cell]);
+}
+
 // the block's maximum of m for map k -> kmax[k], one atomic at the most; wmax: TF_WAVES doubles of LDS
 __device__ __forceinline__ void tf_block_max(double m, double *wmax, unsigned long long *dst)
 {
@@ -275,14 +384,17 @@ int tf_check(int K, const int32_t *dims, int mode, double dh, double E, double H
 {
     if (!dims) return fail(MET2_E_INVALID, "NULL argument");
     if (K < 1 || dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return fail(MET2_E_INVALID, "K and every axis must be >= 1");
-    if (mode != MET2_TFCE_MODE_TFCE && mode != MET2_TFCE_MODE_EXTENT) return fail(MET2_E_INVALID, "mode must be MET2_TFCE_MODE_TFCE or MET2_TFCE_MODE_EXTENT");
+    if (mode != MET2_TFCE_MODE_TFCE && mode != MET2_TFCE_MODE_EXTENT && mode != MET2_TFCE_MODE_MASS)
+        return fail(MET2_E_INVALID, "mode must be MET2_TFCE_MODE_TFCE, MET2_TFCE_MODE_EXTENT or MET2_TFCE_MODE_MASS");
     if (connectivity != 6 && connectivity != 18 && connectivity != 26) return fail(MET2_E_INVALID, "connectivity must be 6, 18 or 26");
-    if (!std::isfinite(dh) || dh <= 0.0) return fail(MET2_E_INVALID, "dh (the threshold in extent mode) must be finite and > 0");
+    if (!std::isfinite(dh) || dh <= 0.0) return fail(MET2_E_INVALID, "dh (the threshold in extent and mass mode) must be finite and > 0");
     if (mode == MET2_TFCE_MODE_TFCE && (!std::isfinite(E) || E <= 0.0 || !std::isfinite(H) || H < 0.0))
         return fail(MET2_E_INVALID, "E must be finite and > 0, H finite and >= 0");
     if (K > MET2_TFCE_MAX_K) return fail(MET2_E_UNSUPPORTED, "K <= " + std::to_string(MET2_TFCE_MAX_K) + " maps per call");
     if ((double)dims[0] * (double)dims[1] * (double)dims[2] >= 2147483648.0) return fail(MET2_E_UNSUPPORTED, "the grid must hold fewer than 2^31 voxels");
     const int64_t G = (int64_t)dims[0] * dims[1] * dims[2];
+    if (mode == MET2_TFCE_MODE_MASS && G > (int64_t)MET2_TFCE_MASS_MAX_G)
+        return fail(MET2_E_UNSUPPORTED, "in mass mode the grid must hold at most 2^24 voxels: the 64-bit sum of the fixed-point statistic must not overflow");
     *g = TfGrid{dims[0], dims[1], dims[2], (int)G};
     *p = TfParams{mode, dh, E, H, connectivity == 6 ? 1 : connectivity == 18 ? 2 : 3};
     return MET2_OK;
@@ -311,13 +423,26 @@ size_t tf_bytes(const TfWork &t) { return t.mask.off + t.mask.bytes; }
 int tf_transform(DeviceWork &w, const TfGrid &g, int K, const TfParams &p, const double *maps, const uint8_t *mask, TfForest f, hipStream_t st, int *err_out)
 {
     const dim3 grid((unsigned)((g.G + TF_BLOCK - 1) / TF_BLOCK), (unsigned)K), block(TF_BLOCK);
-    const int max_level = p.mode == MET2_TFCE_MODE_EXTENT ? 1 : MET2_TFCE_MAX_STEPS;
-    hipLaunchKernelGGL(tf_level_kernel, grid, block, 0, st, g, maps, mask, max_level, p.dh, f);
+    const bool mass = p.mode == MET2_TFCE_MODE_MASS;
+    const int max_level = p.mode == MET2_TFCE_MODE_TFCE ? MET2_TFCE_MAX_STEPS : 1;
+    if (mass)
+        hipLaunchKernelGGL(tf_mass_level_kernel, grid, block, 0, st, g, maps, mask, p.dh, f);
+    else
+        hipLaunchKernelGGL(tf_level_kernel, grid, block, 0, st, g, maps, mask, max_level, p.dh, f);
     int host_flags[2] = {0, 0};
     if (!w.ok(hipMemcpyAsync(host_flags, f.flags, sizeof host_flags, hipMemcpyDeviceToHost, st)) || !w.ok(hipStreamSynchronize(st))) return MET2_E_HIP;
     *err_out = host_flags[1];
     if (host_flags[1]) return MET2_OK;
     const int top = host_flags[0] < max_level ? host_flags[0] : max_level;
+    if (mass) {                                                    // one level: the union, then the three passes over the sum cells
+        if (top >= 1) {
+            hipLaunchKernelGGL(tf_union_kernel, grid, block, 0, st, g, 1, p.reach, f);
+            hipLaunchKernelGGL(tf_mass_add_kernel, grid, block, 0, st, g, f);
+            hipLaunchKernelGGL(tf_mass_spread_kernel, grid, block, 0, st, g, f);
+            hipLaunchKernelGGL(tf_mass_root_kernel, grid, block, 0, st, g, f);
+        }
+        return MET2_OK;
+    }
     const bool half_two = p.E == 0.5 && p.H == 2.0;
     for (int j = top; j >= 1; --j) {                               // <= MET2_TFCE_MAX_STEPS
         hipLaunchKernelGGL(tf_union_kernel, grid, block, 0, st, g, j, p.reach, f);

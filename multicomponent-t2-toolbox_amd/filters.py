@@ -405,18 +405,20 @@ def maps_to_template_filter(res, affine, template_shape, template_affine, world=
 GROUP_VOLUMES = ("tstat", "cope", "p_uncorrected", "p_fwe")
 GROUP_F_VOLUMES = ("fstat", "p_uncorrected", "p_fwe")              # of an F-contrast: no cope, no tstat
 # the spatial statistics' maps (group.randomise(tfce=..., cluster_threshold=...)): the statistic is 0 outside the mask, a p-value 1
-GROUP_SPATIAL_VOLUMES = ("tfce", "p_tfce_uncorrected", "p_tfce_fwe", "cluster_extent", "p_cluster_uncorrected", "p_cluster_fwe")
-GROUP_SPATIAL_COUNTS = ("tfce_count", "cluster_count")
+GROUP_SPATIAL_VOLUMES = ("tfce", "p_tfce_uncorrected", "p_tfce_fwe", "cluster_extent", "p_cluster_uncorrected", "p_cluster_fwe", "cluster_mass",
+                         "p_mass_uncorrected", "p_mass_fwe")
+GROUP_SPATIAL_COUNTS = ("tfce_count", "cluster_count", "mass_count")
 
 
 def group_stats_filter(volumes, X, c=None, mask=None, tfce=None, cluster_threshold=None, cluster_connectivity=26, f_contrast=None, variance_smoothing=None,
-                       **options):
+                       cluster_mass_threshold=None, **options):
     """The permutation test of the t-contrast c in the design X [n, p] at every voxel of n subjects' volumes [n, x, y, z] on one grid (the
     <map>_in_template volumes of maps_to_template_filter): group.randomise on the voxels of `mask` (None: all), unfolded into volumes.
     options: n_perm, seed, exchange ('permute' | 'flip'), two_sided, device, batch_stat -- group.randomise's.
     tfce (True or a dict of E, H, dh, connectivity) and / or cluster_threshold (with cluster_connectivity) add the spatial statistics, for
     which the grid and the voxels' places in it are handed on (options then also: batch_spatial, work_bytes): tfce, p_tfce_uncorrected,
-    p_tfce_fwe, tfce_count, cluster_extent, p_cluster_uncorrected, p_cluster_fwe and cluster_count as volumes too.
+    p_tfce_fwe, tfce_count, cluster_extent, p_cluster_uncorrected, p_cluster_fwe and cluster_count as volumes too.  cluster_mass_threshold
+    (with the same cluster_connectivity) adds the cluster mass in the same way: cluster_mass, p_mass_uncorrected, p_mass_fwe and mass_count.
     -> its dict with tstat, cope, p_uncorrected, p_fwe and count as [x, y, z] volumes (outside the mask t = 0, cope = 0, p = 1, count =
     n_perm) and mask [x, y, z] bool: the voxels that were tested.  Parity with FSL randomise is unpinned: FSL was not available.
     f_contrast [s, p] in the place of c: the F-test of its rows at once (group.randomise(f_contrast=...)), with fstat in the place of tstat and
@@ -438,6 +440,8 @@ def group_stats_filter(volumes, X, c=None, mask=None, tfce=None, cluster_thresho
         options = dict(options, f_contrast=f_contrast)
     if variance_smoothing is not None:
         options = dict(options, variance_smoothing=variance_smoothing, grid=shape, at=at)
+    if cluster_mass_threshold is not None:
+        options = dict(options, cluster_mass_threshold=cluster_mass_threshold, cluster_connectivity=cluster_connectivity, grid=shape, at=at)
     res = group.randomise(np.ascontiguousarray(vols.reshape(vols.shape[0], -1)[:, at]), X, c, **options)
     for key in (GROUP_VOLUMES if f_contrast is None else GROUP_F_VOLUMES) + tuple(k for k in GROUP_SPATIAL_VOLUMES if k in res):
         vol = np.full(int(np.prod(shape)), 1.0 if key.startswith("p_") else 0.0)

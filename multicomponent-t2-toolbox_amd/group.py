@@ -43,7 +43,16 @@ above.  masked_smooth is the smoothing on its own.  Radii up to 16 voxels (sigma
 Where FSL's randomise -v may differ: the kernel is cut at 3 sigma here; FSL smooths its variance image with a kernel width of its own
 choosing; and the normalisation by the smoothed mask is this project's definition.
 
-Parity with FSL randomise (-T, -c, -f and -v included) is unpinned: FSL was not available.  Not provided: cluster mass, exchangeability
+Cluster mass (randomise(cluster_mass_threshold=h); cluster_mass on maps; MET2_TFCE_MODE_MASS, the header states the definition): where the
+extent counts the voxels of a component of {t >= h}, the mass sums the statistic over them, so a compact, strongly altered region outweighs
+a wide rim barely above the threshold.  The sum is taken in 64-bit fixed point: a member contributes rint(min(t, 16384) * 2^24), the
+integers are added (integer atomics: the order does not matter) and the total is converted once, so the device reproduces an int64 numpy
+sum to the bit and differs from the exact sum of the doubles by at most e * 2^-25 plus one rounding for a component of e voxels.  Every
+permutation is quantised the same way: the test is a valid permutation test of the quantised statistic.  Grids of more than 2^24 voxels
+(after the crop to the tested voxels' bounding box) are refused in this mode.  It works on t, on F and on the pseudo-t, one-sided.  FSL's
+randomise -C / -S sums the raw doubles: the values may differ in the last bits, and, as for the extent, a level holds t >= h (not >).
+
+Parity with FSL randomise (-T, -c, -C, -S, -f and -v included) is unpinned: FSL was not available.  Not provided: exchangeability
 blocks, several devices, 2-D connectivity."""
 import collections
 import ctypes as C
@@ -339,7 +348,7 @@ def perm_fstats(Y, s0, W, s, scale, f_ref=None, count=None, want_first=False, de
 
 # ---------------------------------------------------------------- the spatial statistics on arrays
 
-MODES = {"tfce": 0, "extent": 1}                                   # MET2_TFCE_MODE_*
+MODES = {"tfce": 0, "extent": 1, "mass": 3}                        # MET2_TFCE_MODE_* (2 is the pseudo-t's voxel mode, below)
 CONNECTIVITIES = (6, 18, 26)
 TFCE_DEFAULTS = {"E": 0.5, "H": 2.0, "dh": None, "connectivity": 6}
 
@@ -377,7 +386,7 @@ def _batch_for(grid, n_vox, budget, most):
 
 def spatial(maps, mask=None, mode="tfce", dh=None, E=0.5, H=2.0, connectivity=6, device=0, work_bytes=2 ** 30):
     """met2_tfce on numpy arrays: maps [K, nx, ny, nz] (any K: batches of at most max_k maps, fewer if the work space would pass work_bytes),
-    mask [nx, ny, nz] or None, mode 'tfce' | 'extent' (dh is then the threshold) -> (out [K, nx, ny, nz], kmax [K]).  dh is required."""
+    mask [nx, ny, nz] or None, mode 'tfce' | 'extent' | 'mass' (dh is then the threshold) -> (out [K, nx, ny, nz], kmax [K]).  dh is required."""
     import torch
     if mode not in MODES:
         raise ValueError("mode must be one of %s" % (tuple(MODES),))
@@ -438,6 +447,15 @@ def cluster_extent(maps, threshold, mask=None, connectivity=26, device=0):
     a = np.asarray(maps, dtype=np.float64)
     one = a.ndim == 3
     out = spatial(a[None] if one else a, mask, "extent", threshold, 1.0, 1.0, connectivity, device)[0]
+    return out[0] if one else out
+
+
+def cluster_mass(maps, threshold, mask=None, connectivity=26, device=0):
+    """The mass of every voxel's connected component of {t >= threshold}: the sum of t over the component in the header's 64-bit fixed point
+    (0 outside it), for one map [nx, ny, nz] or several [K, nx, ny, nz].  At most 2^24 grid voxels."""
+    a = np.asarray(maps, dtype=np.float64)
+    one = a.ndim == 3
+    out = spatial(a[None] if one else a, mask, "mass", threshold, 1.0, 1.0, connectivity, device)[0]
     return out[0] if one else out
 
 
@@ -559,15 +577,15 @@ def _spatial_test(Yk, sk, W, r, grid, at, mode, dh, E, H, connectivity, device, 
     return obs_t.cpu().numpy(), cnt.cpu().numpy().view(np.uint32), md.cpu().numpy()
 
 
-def _spatial_options(tfce, cluster_threshold, cluster_connectivity, two_sided, grid, at, V, batch_stat, batch_spatial):
+def _spatial_options(tfce, cluster_threshold, cluster_connectivity, two_sided, grid, at, V, batch_stat, batch_spatial, cluster_mass_threshold=None):
     """the checked options of randomise's spatial statistics -> (tfce dict or None, grid, at)"""
     if two_sided:
-        raise ValueError("tfce and cluster_threshold are one-sided: on |t| a positive and a negative blob would fuse into one cluster; "
+        raise ValueError("tfce, cluster_threshold and cluster_mass_threshold are one-sided: on |t| a positive and a negative blob would fuse into one cluster; "
                          "test c and -c instead of two_sided=True")
     if grid is None or at is None:
-        raise ValueError("tfce and cluster_threshold need grid=(nx, ny, nz) and at=[V], the columns' voxel indices in it")
+        raise ValueError("tfce, cluster_threshold and cluster_mass_threshold need grid=(nx, ny, nz) and at=[V], the columns' voxel indices in it")
     if batch_stat is not None and batch_spatial is None:
-        raise ValueError("batch_stat together with tfce or cluster_threshold needs batch_spatial, the numpy callable with met2_group_perm_tfce's meaning")
+        raise ValueError("batch_stat together with tfce, cluster_threshold or cluster_mass_threshold needs batch_spatial, the numpy callable with met2_group_perm_tfce's meaning")
     if batch_spatial is not None and not callable(batch_spatial):
         raise ValueError("batch_spatial must be a callable with the entry's meaning")
     grid = _dims(grid)
@@ -593,6 +611,9 @@ def _spatial_options(tfce, cluster_threshold, cluster_connectivity, two_sided, g
     if cluster_threshold is not None:
         if not (np.isfinite(cluster_threshold) and cluster_threshold > 0) or cluster_connectivity not in CONNECTIVITIES:
             raise ValueError("cluster_threshold must be finite and > 0, cluster_connectivity 6 | 18 | 26")
+    if cluster_mass_threshold is not None:
+        if not (np.isfinite(cluster_mass_threshold) and cluster_mass_threshold > 0) or cluster_connectivity not in CONNECTIVITIES:
+            raise ValueError("cluster_mass_threshold must be finite and > 0, cluster_connectivity 6 | 18 | 26")
     return opts, grid, at
 
 
@@ -611,7 +632,7 @@ def vsm_limits():
 
 def vsm_work_bytes(K, grid, n_vox=0, mode="voxel"):
     """met2_group_vsm_work_bytes: the device work space of one call for K maps on `grid` (n_vox = 0: of met2_masked_smooth; n_vox > 0: of
-    met2_group_perm_vsm in `mode`, 'voxel' | 'tfce' | 'extent')"""
+    met2_group_perm_vsm in `mode`, 'voxel' | 'tfce' | 'extent' | 'mass')"""
     if mode not in VSM_MODES:
         raise ValueError("mode must be one of %s" % (tuple(VSM_MODES),))
     out = C.c_int64(-1)
@@ -710,7 +731,7 @@ def _launch_vsm(dev, Y, s0, r, W, two_sided, dims, at, mode, dh, E, H, connectiv
 def perm_vsm(Y, s0, W, grid, at, taps, mode="voxel", two_sided=False, dh=1.0, E=0.5, H=2.0, connectivity=6, ref=None, count=None, want_first=False,
              device=0):
     """met2_group_perm_vsm on numpy arrays: perm_tfce's Y, s0, W, grid, at; taps: three arrays (smoothing_taps(...)[1]); mode 'voxel' (the
-    pseudo-t itself; two_sided allowed; dh, E, H, connectivity not read) | 'tfce' | 'extent' (on the pseudo-t, one-sided)
+    pseudo-t itself; two_sided allowed; dh, E, H, connectivity not read) | 'tfce' | 'extent' | 'mass' (on the pseudo-t, one-sided)
     -> (kmax [K], count or None without ref, first [V] or None without want_first)"""
     import torch
     if mode not in VSM_MODES:
@@ -779,7 +800,7 @@ def _vsm_test(Yk, sk, W, r, grid, at, mode, dh, E, H, connectivity, two_sided, r
 
 
 def _randomise_vsm(Y, X, c, n_perm, seed, exchange, two_sided, device, batch_stat, tfce, cluster_threshold, cluster_connectivity, grid, at,
-                   batch_spatial, work_bytes, variance_smoothing):
+                   batch_spatial, work_bytes, variance_smoothing, cluster_mass_threshold=None):
     """randomise with variance_smoothing (its docstring states the results): every statistic is taken on the pseudo-t"""
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     if Y.ndim != 2:
@@ -794,8 +815,9 @@ def _randomise_vsm(Y, X, c, n_perm, seed, exchange, two_sided, device, batch_sta
         raise ValueError("batch_stat must be a callable with the entry's meaning")
     # two_sided is handed on only with a spatial statistic, which refuses it; the grid and `at` are checked either way
     tfce_opts, grid, at = _spatial_options(tfce, cluster_threshold, cluster_connectivity,
-                                           two_sided and ((tfce is not None and tfce is not False) or cluster_threshold is not None), grid, at,
-                                           Y.shape[1], batch_stat, batch_spatial)
+                                           two_sided and ((tfce is not None and tfce is not False) or cluster_threshold is not None
+                                                          or cluster_mass_threshold is not None), grid, at,
+                                           Y.shape[1], batch_stat, batch_spatial, cluster_mass_threshold)
     x1, _ = partition(X, c)
     perms = permutation_set(X, c, n_perm, seed, exchange)
     W, dof = weights(X, c, perms)
@@ -856,13 +878,20 @@ def _randomise_vsm(Y, X, c, n_perm, seed, exchange, two_sided, device, batch_sta
             obs, count_s, md = nothing()
         fill("cluster", "cluster_extent", ("p_cluster_uncorrected", "p_cluster_fwe"), obs, count_s, md)
         out.update(cluster_threshold=float(cluster_threshold), cluster_connectivity=int(cluster_connectivity))
+    if cluster_mass_threshold is not None:
+        if V:
+            obs, _, count_s, md = test("mass", float(cluster_mass_threshold), 1.0, 1.0, cluster_connectivity, False)
+        else:
+            obs, count_s, md = nothing()
+        fill("mass", "cluster_mass", ("p_mass_uncorrected", "p_mass_fwe"), obs, count_s, md)
+        out.update(cluster_mass_threshold=float(cluster_mass_threshold), cluster_connectivity=int(cluster_connectivity))
     return out
 
 
 # ---------------------------------------------------------------- the test
 
 def _randomise_f(Y, X, f_contrast, n_perm, seed, exchange, device, batch_stat, tfce, cluster_threshold, cluster_connectivity, grid, at,
-                 batch_spatial, work_bytes):
+                 batch_spatial, work_bytes, cluster_mass_threshold=None):
     """randomise for an F-contrast (its docstring states the results)"""
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     if Y.ndim != 2:
@@ -873,9 +902,10 @@ def _randomise_f(Y, X, f_contrast, n_perm, seed, exchange, device, batch_stat, t
     if fc.ndim != 2 or fc.shape[1] != p:
         raise ValueError("f_contrast must be [s, p]: one t-contrast of the design's %d columns per row" % p)
     Cm = np.ascontiguousarray(fc.T)                                # [p, s]
-    want_spatial = (tfce is not None and tfce is not False) or cluster_threshold is not None
+    want_spatial = (tfce is not None and tfce is not False) or cluster_threshold is not None or cluster_mass_threshold is not None
     if want_spatial:
-        tfce_opts, grid, at = _spatial_options(tfce, cluster_threshold, cluster_connectivity, False, grid, at, Y.shape[1], batch_stat, batch_spatial)
+        tfce_opts, grid, at = _spatial_options(tfce, cluster_threshold, cluster_connectivity, False, grid, at, Y.shape[1], batch_stat, batch_spatial,
+                                               cluster_mass_threshold)
     if batch_stat is not None and not callable(batch_stat):
         raise ValueError("batch_stat must be a callable with the entry's meaning")
     perms = permutation_set(X, Cm, n_perm, seed, exchange)
@@ -955,11 +985,20 @@ def _randomise_f(Y, X, f_contrast, n_perm, seed, exchange, device, batch_stat, t
             obs, count_s, md = nothing()
         fill("cluster", "cluster_extent", ("p_cluster_uncorrected", "p_cluster_fwe"), obs, count_s, md)
         out.update(cluster_threshold=float(cluster_threshold), cluster_connectivity=int(cluster_connectivity))
+    if cluster_mass_threshold is not None:
+        if V:
+            obs, count_s, md = _spatial_test(Yk, sk, W, r, box, at_box, "mass", float(cluster_mass_threshold), 1.0, 1.0, cluster_connectivity, device,
+                                             batch_spatial, work_bytes, fstat=(s, scale))
+        else:
+            obs, count_s, md = nothing()
+        fill("mass", "cluster_mass", ("p_mass_uncorrected", "p_mass_fwe"), obs, count_s, md)
+        out.update(cluster_mass_threshold=float(cluster_mass_threshold), cluster_connectivity=int(cluster_connectivity))
     return out
 
 
 def randomise(Y, X, c=None, n_perm=5000, seed=0, exchange="permute", two_sided=False, device=0, batch_stat=None, tfce=None, cluster_threshold=None,
-              cluster_connectivity=26, grid=None, at=None, batch_spatial=None, work_bytes=2 ** 30, f_contrast=None, variance_smoothing=None):
+              cluster_connectivity=26, grid=None, at=None, batch_spatial=None, work_bytes=2 ** 30, f_contrast=None, variance_smoothing=None,
+              cluster_mass_threshold=None):
     """The permutation test of the t-contrast c in the design X [n, p] at every voxel of Y [n, V] (one row per subject).
     batch_stat: None runs met2_group_perm_stats on `device`; a numpy callable with its meaning -- batch_stat(Y, s0, W, two_sided, t_ref,
     want_first) -> (kmax [K], count increment [V] or None, t_first [V] or None) -- replaces it, and the loop then needs no device.
@@ -972,11 +1011,16 @@ def randomise(Y, X, c=None, n_perm=5000, seed=0, exchange="permute", two_sided=F
     and / or cluster_threshold = h with cluster_connectivity; both need grid = (nx, ny, nz) and at [V], the strictly ascending index of every
     column of Y in that grid (the grid is cropped to the tested voxels' bounding box before the launches).  batch_spatial: None runs
     met2_group_perm_tfce in batches whose work space stays within work_bytes; a numpy callable with its meaning -- batch_spatial(Y, s0, W, grid,
-    at, mode, dh, E, H, connectivity, ref, want_first) -> (kmax [K], count increment [V] or None, first [V] or None), mode 'tfce' | 'extent' --
+    at, mode, dh, E, H, connectivity, ref, want_first) -> (kmax [K], count increment [V] or None, first [V] or None), mode 'tfce' | 'extent' | 'mass' --
     replaces it, and is required when batch_stat is given.  Adds for tfce: tfce [V], p_tfce_uncorrected, p_tfce_fwe, tfce_count, tfce_max_dist
     [P], tfce_crit, dh, tfce_options; for the extent: cluster_extent [V], p_cluster_uncorrected, p_cluster_fwe, cluster_count,
-    cluster_max_dist [P], cluster_crit -- each defined as its t counterpart.  When the observed maximum of t is <= 0 (and dh is not given)
-    every TFCE value is 0 and every p is 1, with no launch.  With neither option the results and the launches are what they were.
+    cluster_max_dist [P], cluster_crit -- each defined as its t counterpart.  cluster_mass_threshold = h (with cluster_connectivity, which
+    it shares with cluster_threshold; under the rules of cluster_threshold for two_sided, grid, at and batch_spatial, whose stand-ins
+    receive mode 'mass' through the same signatures) tests the cluster mass -- the sum of the statistic over a voxel's component of {t >= h}
+    in the header's 64-bit fixed point -- on t, on F (f_contrast) or on the pseudo-t (variance_smoothing), and adds cluster_mass [V],
+    p_mass_uncorrected, p_mass_fwe, mass_count, mass_max_dist [P], mass_crit and cluster_mass_threshold, each defined as its extent
+    counterpart; left-out voxels get mass 0 and p = 1.  When the observed maximum of t is <= 0 (and dh is not given)
+    every TFCE value is 0 and every p is 1, with no launch.  With none of the options the results and the launches are what they were.
     F-contrasts: exactly one of c and f_contrast.  f_contrast [s, p] holds one t-contrast per row, as the rows an FSL .fts line selects; the
     test is the F-test of all of them at once (met2_group_perm_fstats; the header states the statistic), one-sided by nature: two_sided=True
     is refused.  -> dict(fstat [V], p_uncorrected, p_fwe, count, max_dist, f_crit, dof = (s, n - r), n_perm, exhaustive); there is no cope.
@@ -991,7 +1035,7 @@ def randomise(Y, X, c=None, n_perm=5000, seed=0, exchange="permute", two_sided=F
     allowed; tfce and cluster_threshold are taken on the pseudo-t (dh from its observed maximum; one-sided).  Adds variance_smoothing =
     {"sigma_vox": (sx, sy, sz), "radius": (Rx, Ry, Rz)}.  Batches are sized by vsm_work_bytes within work_bytes.  The stand-in, required when
     batch_stat is given and the only one called: batch_spatial(Y, s0, W, grid, at, mode, dh, E, H, connectivity, ref, want_first, two_sided,
-    radius, taps) with mode 'voxel' | 'tfce' | 'extent'.  Together with f_contrast it is refused: FSL smooths the variance for t only, and a
+    radius, taps) with mode 'voxel' | 'tfce' | 'extent' | 'mass'.  Together with f_contrast it is refused: FSL smooths the variance for t only, and a
     pseudo-F is not defined here.  Parity with randomise -v is unpinned (the module's docstring says where the definitions may differ)."""
     if (c is None) == (f_contrast is None):
         raise ValueError("give exactly one of c (a t-contrast) and f_contrast (an F-contrast [s, p])")
@@ -1000,18 +1044,19 @@ def randomise(Y, X, c=None, n_perm=5000, seed=0, exchange="permute", two_sided=F
             raise ValueError("variance_smoothing together with f_contrast is refused: FSL randomise smooths the variance for t statistics only, "
                              "and a pseudo-F is not defined here")
         return _randomise_vsm(Y, X, c, n_perm, seed, exchange, two_sided, device, batch_stat, tfce, cluster_threshold, cluster_connectivity, grid,
-                              at, batch_spatial, work_bytes, variance_smoothing)
+                              at, batch_spatial, work_bytes, variance_smoothing, cluster_mass_threshold)
     if f_contrast is not None:
         if two_sided:
             raise ValueError("an F-contrast has no sides: two_sided=True is refused")
         return _randomise_f(Y, X, f_contrast, n_perm, seed, exchange, device, batch_stat, tfce, cluster_threshold, cluster_connectivity, grid, at,
-                            batch_spatial, work_bytes)
+                            batch_spatial, work_bytes, cluster_mass_threshold)
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     if Y.ndim != 2:
         raise ValueError("Y must be [n, V] with one row per subject")
-    want_spatial = (tfce is not None and tfce is not False) or cluster_threshold is not None
+    want_spatial = (tfce is not None and tfce is not False) or cluster_threshold is not None or cluster_mass_threshold is not None
     if want_spatial:
-        tfce_opts, grid, at = _spatial_options(tfce, cluster_threshold, cluster_connectivity, two_sided, grid, at, Y.shape[1], batch_stat, batch_spatial)
+        tfce_opts, grid, at = _spatial_options(tfce, cluster_threshold, cluster_connectivity, two_sided, grid, at, Y.shape[1], batch_stat, batch_spatial,
+                                               cluster_mass_threshold)
     if batch_stat is not None and not callable(batch_stat):
         raise ValueError("batch_stat must be a callable with the entry's meaning")
     x1, _ = partition(X, c)
@@ -1095,4 +1140,12 @@ def randomise(Y, X, c=None, n_perm=5000, seed=0, exchange="permute", two_sided=F
             obs, count_s, md = np.zeros(V), np.full(V, P, dtype=np.uint32), np.zeros(P)
         fill("cluster", "cluster_extent", ("p_cluster_uncorrected", "p_cluster_fwe"), obs, count_s, md)
         out.update(cluster_threshold=float(cluster_threshold), cluster_connectivity=int(cluster_connectivity))
+    if cluster_mass_threshold is not None:
+        if V:
+            obs, count_s, md = _spatial_test(Yk, sk, W, r, box, at_box, "mass", float(cluster_mass_threshold), 1.0, 1.0, cluster_connectivity, device,
+                                             spatial_fn, work_bytes)
+        else:
+            obs, count_s, md = np.zeros(V), np.full(V, P, dtype=np.uint32), np.zeros(P)
+        fill("mass", "cluster_mass", ("p_mass_uncorrected", "p_mass_fwe"), obs, count_s, md)
+        out.update(cluster_mass_threshold=float(cluster_mass_threshold), cluster_connectivity=int(cluster_connectivity))
     return out

@@ -1023,7 +1023,7 @@ def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_m
     STAT_QUANTITIES; c: the t-contrast.  Every subject's <stem>_in_template.nii.gz is loaded; differing shapes or affines are refused.  The
     test runs on the intersection of the subjects' maps_to_template_inside.nii.gz and, where given, the mask at path_to_mask (non-zero voxels,
     on the same grid).  options: group_stats_filter's (n_perm, seed, exchange, two_sided, device, batch_stat; tfce, cluster_threshold,
-    cluster_connectivity, batch_spatial, work_bytes).
+    cluster_mass_threshold, cluster_connectivity, batch_spatial, work_bytes).
     Written at path_to_out with the template's affine: <quantity>_tstat.nii.gz, <quantity>_cope.nii.gz, <quantity>_p_unc.nii.gz and
     <quantity>_p_fwe.nii.gz; <quantity>_max_dist.txt (the maximum statistic of every permutation, the identity first) and
     <quantity>_group_report.txt: n, dof, the number of permutations, whether the set was exhaustive, t_crit (the 0.95 quantile of the maximum
@@ -1032,7 +1032,10 @@ def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_m
     With tfce=True | dict(E, H, dh, connectivity) (one-sided): also <quantity>_tfce.nii.gz, <quantity>_p_tfce_unc.nii.gz,
     <quantity>_p_tfce_fwe.nii.gz and <quantity>_tfce_max_dist.txt, and in the report dh, E, H, the connectivity, tfce_crit and the number of
     voxels with p_tfce_fwe <= 0.05.  With cluster_threshold=h (cluster_connectivity=26): <quantity>_cluster_extent.nii.gz and
-    <quantity>_p_cluster_fwe.nii.gz, and their line in the report.  Parity with randomise -T / -c is unpinned as well.
+    <quantity>_p_cluster_fwe.nii.gz, and their line in the report.  With cluster_mass_threshold=h (the same cluster_connectivity):
+    <quantity>_cluster_mass.nii.gz, <quantity>_p_mass_fwe.nii.gz and <quantity>_mass_max_dist.txt, and a line with the threshold, the
+    connectivity, mass_crit and the number of voxels with p_mass_fwe <= 0.05 (the mass is the fixed-point sum group.py describes).  Parity
+    with randomise -T / -c / -C / -S is unpinned as well.
     f_contrast [s, p] with c = None: the F-test of its rows at once.  Written then: <quantity>_fstat.nii.gz, <quantity>_p_unc.nii.gz,
     <quantity>_p_fwe.nii.gz, <quantity>_max_dist.txt, the TFCE / cluster files under the names above (taken on F), and the report with s, the
     degrees of freedom (s, n - r), f_crit and the counts at p <= 0.05; no _tstat and no _cope file.  Parity with randomise -f is unpinned.
@@ -1106,6 +1109,13 @@ def motor_group_stats(paths_to_save_data, quantity, X, c, path_to_out, path_to_m
         lines += ["cluster extent: threshold = %.6g, connectivity = %d, cluster_crit (0.95 quantile of the maximum extent): %.6f, "
                   "voxels with p_cluster_fwe <= 0.05: %d" % (out["cluster_threshold"], out["cluster_connectivity"], out["cluster_crit"],
                                                             int(((out["p_cluster_fwe"] <= 0.05) & out["mask"]).sum()))]
+    if "cluster_mass" in out:
+        for key, name in (("cluster_mass", "cluster_mass"), ("p_mass_fwe", "p_mass_fwe")):
+            nifti.save(nifti.NiftiImage(out[key], affine), path_to_out + quantity + "_" + name + ".nii.gz")
+        np.savetxt(path_to_out + quantity + "_mass_max_dist.txt", out["mass_max_dist"])
+        lines += ["cluster mass: threshold = %.6g, connectivity = %d, mass_crit (0.95 quantile of the maximum mass): %.6f, "
+                  "voxels with p_mass_fwe <= 0.05: %d" % (out["cluster_mass_threshold"], out["cluster_connectivity"], out["mass_crit"],
+                                                         int(((out["p_mass_fwe"] <= 0.05) & out["mask"]).sum()))]
     with open(path_to_out + quantity + "_group_report.txt", "w") as f:
         f.write("\n".join(lines) + "\n")
     return out

@@ -2,7 +2,7 @@
 """Timing of the voxel-wise permutation test (met2_group_perm_stats, group.randomise) on the device, written to profiles/group_bench.json:
     python3 scripts/bench_group.py [--perms 5000] [--voxels 250000] [--subjects 32] [--reps 5] [--numpy-candidates 32] [--out FILE]
                                    [--tfce [--grid 96 112 96] [--numpy-seconds 60] [--device-only]] [--fstat [--grid 96 112 96]]
-                                   [--vsm [--sigma 2.5] [--grid 96 112 96]]
+                                   [--vsm [--sigma 2.5] [--grid 96 112 96]] [--mass [--threshold 2.5] [--grid 96 112 96]]
 The case: two groups of subjects / 2 (r = 2 model columns), seeded normal data with a group difference in 1 % of the voxels, `perms`
 permutations drawn at random, one map.
   kernels     the launches of the whole set (ceil(perms / max_k) calls of the entry with t_ref and count, inputs resident on the device), between
@@ -34,6 +34,12 @@ profiles/group_vsm_bench.json, everything measured in one run on one build:
   passes      the three smoothing passes alone (met2_masked_smooth without N on 32 maps of the cropped grid), per call; a pass reads and
               writes every cell once, 16 bytes per cell and pass, set against the 8 TB/s HBM peak that bench.py uses
   randomise   group.randomise(variance_smoothing=sigma) end to end, and beside it the plain call and the tfce=True call on the same data
+With --mass the test is the cluster-mass one (MET2_TFCE_MODE_MASS, --threshold 2.5, connectivity 26) on the case and grid of --tfce, with the
+cluster extent at the same threshold and connectivity in the same run as the yardstick, written to profiles/group_mass_bench.json:
+  transform   met2_tfce alone on one batch of 32 t maps of the cropped grid (the device's own, observed and permuted), extent and mass, between
+              HIP events: the level, union, (count, sum | add, spread, roots) and finish launches
+  kernels     the whole set through met2_group_perm_tfce, extent and mass, as above
+  randomise   group.randomise(cluster_threshold=h) and group.randomise(cluster_mass_threshold=h) end to end
 A record, not a pass mark."""
 import argparse
 import importlib
@@ -300,6 +306,90 @@ def vsm_case(a, group):
     print(json.dumps(rec))
 
 
+def mass_case(a, group):
+    n, V, P, grid, h, conn = a.subjects, a.voxels, a.perms, tuple(a.grid), a.threshold, 26
+    at = ellipsoid(grid, V)
+    g = np.repeat([1.0, 0.0], n // 2)
+    X, c = np.stack([g, 1.0 - g], axis=1), np.array([1.0, -1.0])
+    rng = np.random.default_rng(0)
+    Y = rng.standard_normal((n, V))
+    centre = np.argsort(np.abs(at - at[V // 2]))[: V // 100]      # 1 % of the voxels around the middle one
+    Y[: n // 2, centre] += 1.5
+    W, dof = group.weights(X, c, group.permutation_set(X, c, P, 0, "permute"))
+    Yr, s0 = group.residualise(Y, X, c)
+    P, r = W.shape[0], W.shape[1] - 1
+    box, at_box = group._crop(grid, at)
+    dev = torch.device("cuda", 0)
+    put = lambda x: torch.as_tensor(x, device=dev)
+    Yt, st, Wt, at_t = put(Yr), put(s0), put(W), put(at_box)
+    K = group._batch_for(box, V, 2 ** 30, P)
+    work = torch.empty(group.tfce_work_bytes(K, box, V), dtype=torch.uint8, device=dev)
+    md = torch.empty(P, dtype=torch.float64, device=dev)
+    cnt = torch.zeros(V, dtype=torch.int32, device=dev)
+    obs = {m: torch.empty(V, dtype=torch.float64, device=dev) for m in ("extent", "mass")}
+    entry = lambda m, Wk, ref, first, km, count: group._launch_spatial(dev, Yt, st, r, Wk, box, at_t, m, h, 1.0, 1.0, conn, ref, first, km, count, work)
+    for m in obs:
+        entry(m, Wt[:1], None, obs[m], md[:1], None)
+
+    def whole_set(m):
+        for k0 in range(0, P, K):
+            entry(m, Wt[k0:k0 + K], obs[m], None, md[k0:k0 + K], cnt)
+
+    # one batch of t maps for the transform alone: the device's own t of the first K candidates, scattered to the cropped grid
+    import ctypes as C
+    lib = importlib.import_module(PKG + "._lib")
+    G = int(np.prod(box))
+    t_first = torch.empty(V, dtype=torch.float64, device=dev)
+    maps = torch.zeros((K, G), dtype=torch.float64, device=dev)
+    mask = torch.zeros(G, dtype=torch.uint8, device=dev)
+    mask[at_t.long()] = 1
+    for k in range(K):
+        group._launch(dev, Yt, st, r, Wt[k:k + 1], False, None, t_first, md[:1], None)
+        maps[k, at_t.long()] = t_first
+    out, km = torch.empty_like(maps), torch.empty(K, dtype=torch.float64, device=dev)
+    twork = torch.empty(group.tfce_work_bytes(K, box), dtype=torch.uint8, device=dev)
+    dims = (C.c_int32 * 3)(*box)
+
+    def transform(m):
+        lib.check(lib.lib().met2_tfce(0, K, dims, maps.data_ptr(), mask.data_ptr(), group.MODES[m], float(h), 1.0, 1.0, conn, out.data_ptr(),
+                                      km.data_ptr(), twork.data_ptr(), twork.numel(), torch.cuda.current_stream(dev).cuda_stream))
+
+    tr_ms = {m: events_ms(lambda m=m: transform(m), a.reps) for m in ("extent", "mass", "extent")}     # the extent last as well: the order does not decide
+    members = int((maps >= h).sum().item())
+    set_ms = {m: events_ms(lambda m=m: whole_set(m), a.reps) for m in ("extent", "mass")}
+    kw = dict(n_perm=P, seed=0, grid=grid, at=at, cluster_connectivity=conn)
+    group.randomise(Y, X, c, cluster_threshold=h, **kw)
+    group.randomise(Y, X, c, cluster_mass_threshold=h, **kw)
+    ext_s, mass_s = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        res_e = group.randomise(Y, X, c, cluster_threshold=h, **kw)
+        t1 = time.perf_counter()
+        res_m = group.randomise(Y, X, c, cluster_mass_threshold=h, **kw)
+        ext_s.append(t1 - t0)
+        mass_s.append(time.perf_counter() - t1)
+    med = lambda x: float(np.median(x))
+    rec = {"case": {"perms": P, "voxels": V, "subjects": n, "r": r, "grid": list(grid), "cropped_grid": list(box), "threshold": h,
+                    "connectivity": conn, "maps_per_launch": K, "launches": (P + K - 1) // K, "members_in_the_transform_batch": members},
+           "transform_extent": {"seconds": med(tr_ms["extent"]) * 1e-3, "all_ms": tr_ms["extent"]},
+           "transform_mass": {"seconds": med(tr_ms["mass"]) * 1e-3, "all_ms": tr_ms["mass"]},
+           "transform_mass_over_extent": med(tr_ms["mass"]) / med(tr_ms["extent"]),
+           "kernels_extent": {"seconds": med(set_ms["extent"]) * 1e-3, "all_ms": set_ms["extent"]},
+           "kernels_mass": {"seconds": med(set_ms["mass"]) * 1e-3, "all_ms": set_ms["mass"]},
+           "kernels_mass_over_extent": med(set_ms["mass"]) / med(set_ms["extent"]),
+           "randomise_extent": {"seconds": med(ext_s), "all_s": ext_s, "cluster_crit": res_e["cluster_crit"],
+                                "voxels_p_cluster_fwe_le_0.05": int((res_e["p_cluster_fwe"] <= 0.05).sum())},
+           "randomise_mass": {"seconds": med(mass_s), "all_s": mass_s, "mass_crit": res_m["mass_crit"],
+                              "voxels_p_mass_fwe_le_0.05": int((res_m["p_mass_fwe"] <= 0.05).sum())},
+           "device": torch.cuda.get_device_name(0), "reps": a.reps}
+    path = a.out if a.out != os.path.join(ROOT, "profiles", "group_bench.json") else os.path.join(ROOT, "profiles", "group_mass_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--perms", type=int, default=5000)
@@ -315,6 +405,8 @@ def main():
     ap.add_argument("--fstat", action="store_true")
     ap.add_argument("--vsm", action="store_true")
     ap.add_argument("--sigma", type=float, default=2.5)
+    ap.add_argument("--mass", action="store_true")
+    ap.add_argument("--threshold", type=float, default=2.5)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "the benchmark needs a GPU"
     group = importlib.import_module(PKG + ".group")
@@ -323,6 +415,8 @@ def main():
         return fstat_case(a, group)
     if a.vsm:
         return vsm_case(a, group)
+    if a.mass:
+        return mass_case(a, group)
     if a.tfce:
         return tfce_case(a, group, gn)
     n, V, P = a.subjects, a.voxels, a.perms
